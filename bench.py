@@ -28,13 +28,18 @@ by the reference's own data flow RUN in the same process at the same backbone pr
 MI355X -> ``.cpu()`` of the head fields (``decoder/decoder.py:96-100``) -> the reference's C++ CifCaf decoder
 (oracle/_ref) on one host thread, one decoder instance reused across images like ``decoder/cifcaf.py:119``.
 
-The default single-GPU run (no ``--config``) also carries, under ``"configs"``, short legs of the other BASELINE
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the outputs when
+``--dump-outputs DIR`` is given, print the line.  Everything below that is not the headline -- the bfloat16 leg, the
+network-only and reference-flow timings, ``vs_baseline``, the CPU baselines, roofline, parity stamp, ``f32_check``, the
+other configurations and ``bench_detail.json`` -- runs only with ``--full``.
+
+With ``--full``, the single-GPU run (no ``--config``) also carries, under ``"configs"``, short legs of the other BASELINE
 configurations and settings, each with its own roofline / cpu_baseline / parity: ``config3`` (shufflenetv2k16
 batch 32), ``config4`` (shufflenetv2k30 wholebody batch 16), ``force_complete`` (the reference benchmark CLI's
 decoder setting, ``benchmark.py:77-79``), ``batch1`` (the literal configs[1]: resnet50 641x641 batch 1 latency,
 eager and as one HIP graph, the reference flow at batch 1 beside it) and ``decode_two_in_flight``.
 
-Besides the contract fields the line carries
+Besides the contract fields the line of a ``--full`` run carries
   "roofline":     HBM roofline of the decode kernel that dominates the decode time: SURVEY 8d bytes per
                   launch / its HIP-event time, the kernel's own compulsory bytes beside it, and ``traffic`` =
                   PMC HBM bytes of the whole decode path per launch (profiles/r3/pmc_traffic.json, hash-stamped);
@@ -42,6 +47,8 @@ Besides the contract fields the line carries
                   same fields (reused instance, fresh instance, all cores);
   "parity":       what the timed decode produces, compared image by image with the reference decoder OUTSIDE
                   the timed region.
+
+``--dump-outputs DIR``: see ``write_outputs``.
 """
 import argparse
 import hashlib
@@ -118,6 +125,12 @@ def parse_args():
                    help='print what exists and exit when the run has not finished by then (a default run takes < 3 min)')
     p.add_argument('--dump-annotations', default=None,
                    help='testing: rank 0 writes the gathered annotations of the last step to this .npz')
+    p.add_argument('--dump-outputs', default=None, metavar='DIR',
+                   help='rank 0 writes what the timed path computed in its last timed step to DIR/<name>.npy '
+                        '(see write_outputs)')
+    p.add_argument('--full', action='store_true',
+                   help='everything beside the headline: the bf16 leg, network-only and reference-flow timings, CPU '
+                        'baselines, roofline, parity stamp, f32_check, the other configurations, bench_detail.json')
     return p.parse_args()
 
 
@@ -316,7 +329,10 @@ def compact_line(detail):
         line['configs'] = digest
     if detail.get('watchdog'):
         line['watchdog'] = str(detail['watchdog'])[:80]
-    line['detail'] = DETAIL_FILE
+    if 'full' in detail:
+        line['full'] = detail['full']
+    if detail.get('full', True):                              # (a plain run writes no detail file)
+        line['detail'] = DETAIL_FILE
     line['bench_seconds'] = detail.get('bench_seconds')
     text = json.dumps(line, separators=(',', ':'))
     if len(text) >= LINE_LIMIT:                               # never let an extra take the headline with it
@@ -339,6 +355,48 @@ def write_detail(detail):
             written.append(path)
         except OSError as e:                                  # read-only checkout: the line itself still prints
             print('bench: could not write %s: %r' % (path, e), file=sys.stderr)
+    return written
+
+
+OUTPUT_SAMPLE = 1 << 20   # elements of each head tensor written by write_outputs
+OUTPUT_SAMPLE_SEED = 20
+OUTPUT_DECODE_BYTES = 48 << 20   # annotations + ids + counts: the first images that fit (all of a COCO batch up to 1404)
+
+
+def write_outputs(directory, annotations, ids, counts, heads=None):
+    """``--dump-outputs DIR``: what the timed path computed in its last timed step, as float32 / float64 .npy files, so
+    that two builds can be compared output for output (the inputs depend on the arguments only: seeded images, seeded
+    network weights, seeded field batches).
+      annotations.npy  [B, max_annotations, K, 4] float32 (v, x, y, s); rows past an image's count are zeroed (the decoder
+                       leaves them undefined)
+      ids.npy          [B, max_annotations] float64, zeroed the same way
+      counts.npy       [B] float64, the decoder's counts as returned (row count and flag bits)
+      cif_head.npy, caf_head.npy   float32: the network's head outputs of rank 0 (the decode reads the injected synthetic
+                       fields; these are what the backbone computed), OUTPUT_SAMPLE elements of each at flat indices drawn
+                       with numpy's default_rng(OUTPUT_SAMPLE_SEED), sorted; the whole tensor when it is smaller.
+    About 10 MB at the default batch; the decode's arrays hold the first images that fit in OUTPUT_DECODE_BYTES, so
+    that the whole stays under 64 MB at any batch.  -> list of the files written."""
+    from openpifpaf_amd import native
+    os.makedirs(directory, exist_ok=True)
+    per_image = annotations[0].numel() * 4 + ids[0].numel() * 8 + 8
+    n = max(1, min(len(counts), OUTPUT_DECODE_BYTES // per_image))
+    annotations = annotations[:n].cpu().numpy().astype(np.float32)
+    ids = ids[:n].cpu().numpy().astype(np.float64)
+    counts = counts[:n].cpu().numpy()
+    rows = np.arange(annotations.shape[1])[None, :] < (counts & native.COUNT_ROWS_MASK)[:, None]
+    arrays = {'annotations': np.where(rows[:, :, None, None], annotations, np.float32(0)),
+              'ids': np.where(rows, ids, 0.0), 'counts': counts.astype(np.float64)}
+    for name, h in zip(('cif_head', 'caf_head'), heads or ()):
+        flat = h.detach().reshape(-1)
+        if flat.numel() > OUTPUT_SAMPLE:
+            idx = np.sort(np.random.default_rng(OUTPUT_SAMPLE_SEED).choice(flat.numel(), OUTPUT_SAMPLE, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arrays[name] = flat.float().cpu().numpy()
+    written = []
+    for name, a in arrays.items():
+        path = os.path.join(directory, name + '.npy')
+        np.save(path, a)
+        written.append(path)
     return written
 
 
@@ -717,7 +775,7 @@ def main():
     if rank == 0:
         start_watchdog(args.watchdog_seconds)
     config_id = args.config or 2
-    extras = (args.config is None and world == 1 and not args.no_extras and not args.decode_only
+    extras = (args.full and args.config is None and world == 1 and not args.no_extras and not args.decode_only
               and args.fields == 'synthetic' and not args.force_complete and args.backbone is None and args.batch is None)
     n_variants = 1 if (args.single_batch or args.graph) else 2
     wl = Workload(config_id, args.batch or CONFIGS[config_id]['batch'], rank, device, args.long_edge, n_variants,
@@ -741,9 +799,10 @@ def main():
             torch.cuda.synchronize(device)
 
     def run_leg(wl, images32, dtype_name, steps, warmup, *, params=None, decode_only=False, fields='synthetic',
-                quantised=False, n_streams=1, graph=False, dump=None, tie_inside=None):
+                quantised=False, n_streams=1, graph=False, dump=None, tie_inside=None, dump_outputs=None):
         """W warm-up steps, then EXACTLY `steps` timed steps between barrier + synchronize.  -> dict(elapsed = max over
-        ranks, per-rank times, model, images, annotations of the last step)."""
+        ranks, per-rank times, model, images, annotations of the last step).  `dump_outputs`: rank 0 writes the last
+        timed step's results there (write_outputs), after the timed region."""
         model = None if decode_only else build_model(wl, dtype_name)
         images = images32 if dtype_name == 'fp32' else images32.to(TORCH_DTYPE[dtype_name])
         variants = wl.quantised() if quantised else wl.variants
@@ -762,6 +821,7 @@ def main():
         step_no = [0]
         shapes_checked = [False]
         gathered = [None]
+        last = [None]                                      # (heads, annotations, ids, counts) of the last step: --dump-outputs
         tickets = []
 
         def step():
@@ -805,6 +865,8 @@ def main():
                         gathered[0] = distributed.gather_annotations(out.cpu(), ids.cpu(), counts.cpu())
                 wl.host_out.copy_(out, non_blocking=True)
                 wl.host_counts.copy_(counts, non_blocking=True)
+            if dump_outputs:
+                last[0] = (heads, out, ids, counts)
 
         t_setup = time.perf_counter()
         for _ in range(warmup):
@@ -835,6 +897,13 @@ def main():
             a_, i_, c_ = gathered[0] if gathered[0] is not None else (wl.host_out, None, wl.host_counts)
             np.savez(dump, annotations=a_.cpu().numpy(), counts=c_.cpu().numpy(),
                      variant=(step_no[0] - 1) % len(variants), variant_seed=VARIANT_SEED)
+        if dump_outputs and rank == 0:
+            if last[0] is None:                            # (graph / lanes diagnostics: the host copy of the last batch)
+                raise SystemExit('bench.py: --dump-outputs needs the default step (no --graph, no --decode-streams > 1)')
+            heads, a_, i_, c_ = last[0]
+            if gathered[0] is not None:
+                a_, i_, c_ = gathered[0]
+            write_outputs(dump_outputs, a_, i_, c_, heads)
         return dict(elapsed=elapsed, per_rank=per_rank, model=model, images=images,
                     n_ann=int((wl.host_counts & native.COUNT_ROWS_MASK).sum()), variants=variants)
 
@@ -887,21 +956,28 @@ def main():
         return dict(value=world * wl.B * steps / leg['elapsed'], ms_per_step=leg['elapsed'] / steps * 1e3)
 
     def full_config(wl, images32, steps, warmup, *, primary, bf16_leg, cpu_seconds, profile_steps, params, dump=None,
-                    decode_only=False, fields='synthetic', n_streams=1, graph=False, reference_steps=3, fc=False):
-        """All legs of one configuration on this rank -> result dict (rank 0) or None."""
+                    decode_only=False, fields='synthetic', n_streams=1, graph=False, reference_steps=3, fc=False,
+                    full=True, dump_outputs=None):
+        """All legs of one configuration on this rank -> result dict (rank 0) or None.  `full` False: the timed leg
+        alone (value, ms_per_step, config)."""
+        from openpifpaf_amd import winograd
         legs, nn, ref_run, wino = {}, {}, {}, {}
+        winograd.reset_flop_counter()
         leg = run_leg(wl, images32, primary, steps, warmup, params=params, decode_only=decode_only, fields=fields,
-                      n_streams=n_streams, graph=graph, dump=dump)
+                      n_streams=n_streams, graph=graph, dump=dump, dump_outputs=dump_outputs)
         legs[primary] = leg
         single = rank == 0 and world == 1
-        if leg['model'] is not None and single:
+        if not full:
+            if leg['model'] is not None:                   # (> 0: the stride-1 3x3 convolutions ran as Winograd)
+                wino[primary] = winograd.direct_flops() / 1e9
+        elif leg['model'] is not None and single:
             nn[primary] = network_only(leg['model'], leg['images'], wl)
             wino[primary] = network_only.winograd_gflop
             if not args.no_cpu_baseline:
                 ref_run[primary] = reference_flow_run(leg['model'], leg['images'], wl, reference_steps, FC_KW if fc else None)
         leg['model'] = None
         torch.cuda.empty_cache()
-        if bf16_leg and not decode_only and primary != 'bf16':
+        if full and bf16_leg and not decode_only and primary != 'bf16':
             leg2 = run_leg(wl, images32, 'bf16', steps, warmup, params=params, quantised=True)
             legs['bf16'] = leg2
             if single:
@@ -914,8 +990,10 @@ def main():
         if rank != 0:
             return None
         fc_kw = FC_KW if fc else None
-        with torch.cuda.stream(dec_stream):
-            roofline = decode_roofline(wl, wl.variants, params, profile_steps, force_complete=fc)
+        roofline = None
+        if full:
+            with torch.cuda.stream(dec_stream):
+                roofline = decode_roofline(wl, wl.variants, params, profile_steps, force_complete=fc)
         if not decode_only and not wl.cfg['wholebody'] and wl.backbone == 'resnet50' and nn:
             gflop = 274.0 * wl.B                          # 137 GMAC per 641x641 image
             # [r6] the stride-1 3x3 convolutions of the float32 trunk run as Winograd F(2x2, 3x3): of their direct-form flops
@@ -928,7 +1006,7 @@ def main():
                     'TFLOPs_direct_equivalent': round(gflop / nn[d][0], 1),
                     'winograd_direct_gflop_per_batch': round(wino.get(d, 0.0), 1)} for d in nn}
         cpu = ref_pipe = None
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(wl.variants[0][0], wl.variants[0][1], wl.skeleton0, wl.K, cpu_seconds, fc_kw)
             if nn:
                 ref_pipe = {}
@@ -942,7 +1020,7 @@ def main():
                         'images_per_s_all_cores_composed': round(allc, 1) if allc else None, 'cores': cpu['all_cores'],
                     })
         parity = None
-        if world == 1 and not args.no_parity:
+        if full and world == 1 and not args.no_parity:
             with torch.cuda.stream(dec_stream):
                 parity = parity_stamp(lambda c, f: wl.dec.call_batch(c, wl.stride, f, wl.stride, params=params),
                                       wl.variants, wl.skeleton0, wl.K, fc_kw)
@@ -1006,7 +1084,7 @@ def main():
                          profile_steps=args.profile_steps, params=dec_params, dump=args.dump_annotations,
                          decode_only=args.decode_only, fields=args.fields,
                          n_streams=max(1, args.decode_streams) if args.decode_only else 1, graph=args.graph and args.decode_only,
-                         fc=args.force_complete)
+                         fc=args.force_complete, full=args.full, dump_outputs=args.dump_outputs)
     line = None
     if rank == 0:
         line = {
@@ -1019,7 +1097,7 @@ def main():
             'vs_baseline_definition': 'value / the reference data flow RUN in this process at the same backbone '
                                       'precision: network on the MI355X -> .cpu() of the fields -> reference C++ '
                                       'decoder, 1 host thread (reference_pipeline)',
-            'dtype': 'f32', 'data': 'synthetic',
+            'dtype': 'f32', 'data': 'synthetic', 'full': args.full,
         }
         for k in ('config', 'roofline', 'cpu_baseline', 'reference_pipeline', 'parity', 'bf16_backbone',
                   'decode_vs_cpu_1thread', 'per_rank_ms_per_step'):
@@ -1038,7 +1116,7 @@ def main():
                        'float32 one: see bf16_backbone (reduced precision, reported beside the headline, not as it).'
                        % (primary, nn_ms, ref_ms - nn_ms, ref_ms, nn_ms, ref_ms / nn_ms)}
 
-        if primary == 'fp32' and not args.decode_only:
+        if args.full and primary == 'fp32' and not args.decode_only:
             try:
                 line['f32_check'] = f32_numerics_check()
             except Exception as e:            # noqa: BLE001  (a check, not the measurement)
@@ -1490,7 +1568,8 @@ def main():
             line['configs'] = others
     if rank == 0:
         line['bench_seconds'] = round(time.perf_counter() - t_program, 1)
-        write_detail(line)
+        if args.full:
+            write_detail(line)
         sys.stderr.flush()
         print(compact_line(line), flush=True)
     if world > 1:

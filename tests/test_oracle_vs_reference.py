@@ -1,16 +1,22 @@
 """The restatement against the REAL reference decoder (oracle/_ref, built from the
-reference's own sources).  Skipped where _ref is unavailable (it needs /root/reference
-to build); the committed golden vectors pin the oracle everywhere else."""
+reference's own sources).  Those tests skip where _ref is unavailable (building it needs the
+reference's sources); the committed golden vectors pin the oracle everywhere else.  The host
+mirror's Annotation and CompositeField4 are compared with the reference's results stored in
+tests/golden/host_golden.npz (tests/golden/make_golden_host.py)."""
+import os
+
 import numpy as np
 import pytest
 
 from oracle import reference
 
-pytestmark = pytest.mark.skipif(not reference.available(), reason='oracle/_ref/openpifpaf_ref.so not built')
+HOST_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'host_golden.npz')
 
 
 @pytest.fixture(scope='module')
 def ref():
+    if not reference.available():
+        pytest.skip('oracle/_ref/openpifpaf_ref.so not built')
     torch = reference.load()
     torch.set_num_threads(1)
     reference.reset_statics()
@@ -180,7 +186,7 @@ def test_register_swaps_decoders_inside_the_real_reference_package():
     ``openpifpaf_amd.register()`` the set its decoder factory iterates holds the HIP-backed classes."""
     from oracle import reference_python
     import os
-    if not os.path.isdir(reference_python.REF_SRC):
+    if not os.path.isdir(reference_python.REF_SRC) or not reference.available():
         pytest.skip('reference sources not present')
     opp = reference_python.load()
     import openpifpaf_amd
@@ -206,61 +212,48 @@ def test_register_swaps_decoders_inside_the_real_reference_package():
 
 def test_annotation_objects_equal_the_reference_package():
     """openpifpaf_amd.annotation.Annotation against the reference's own class: score, bbox, json_data and
-    inverse_transform on random poses."""
-    from oracle import reference_python
-    import os
-    if not os.path.isdir(reference_python.REF_SRC):
-        pytest.skip('reference sources not present')
-    opp = reference_python.load()
+    inverse_transform on random poses (the reference's results: tests/golden/make_golden_host.py)."""
+    import json
     from openpifpaf_amd import constants
     from openpifpaf_amd.annotation import Annotation
-    rng = np.random.default_rng(11)
+    golden = np.load(HOST_GOLDEN)
     meta = {'offset': np.array((-7.0, 12.0)), 'scale': np.array((0.8, 0.75)), 'hflip': True,
             'rotation': {'angle': 0.0, 'width': None, 'height': None}, 'width_height': np.array((500, 375)),
             'valid_area': np.array((0.0, 0.0, 499.0, 374.0))}
-    for _ in range(5):
+    rng = np.random.default_rng(11)
+    for i in range(5):
         data = rng.uniform(0, 200, (17, 3)).astype(np.float32)
         data[:, 2] = rng.uniform(0, 1, 17) * (rng.random(17) > 0.3)
         scales = rng.uniform(1, 9, 17).astype(np.float32)
-        pair = []
-        for cls in (Annotation, opp.Annotation):
-            a = cls(constants.COCO_KEYPOINTS, constants.COCO_PERSON_SKELETON,
-                    score_weights=constants.COCO_PERSON_SCORE_WEIGHTS)
-            a.data[:] = data
-            a.joint_scales[:] = scales
-            pair.append(a)
-        mine, ref = pair
-        assert np.isclose(mine.score, ref.score) and np.allclose(mine.bbox(), ref.bbox())
-        assert mine.json_data() == ref.json_data()
-        m2, r2 = mine.inverse_transform(meta), ref.inverse_transform(meta)
-        assert np.allclose(m2.data, r2.data, atol=1e-5) and np.allclose(m2.joint_scales, r2.joint_scales)
+        assert np.array_equal(data, golden['ann%d_data' % i]) and np.array_equal(scales, golden['ann%d_scales' % i])
+        mine = Annotation(constants.COCO_KEYPOINTS, constants.COCO_PERSON_SKELETON,
+                          score_weights=constants.COCO_PERSON_SCORE_WEIGHTS)
+        mine.data[:] = data
+        mine.joint_scales[:] = scales
+        assert np.isclose(mine.score, golden['ann%d_score' % i]) and np.allclose(mine.bbox(), golden['ann%d_bbox' % i])
+        assert json.loads(json.dumps(mine.json_data())) == json.loads(str(golden['ann%d_json' % i]))
+        m2 = mine.inverse_transform(meta)
+        assert np.allclose(m2.data, golden['ann%d_inv_data' % i], atol=1e-5)
+        assert np.allclose(m2.joint_scales, golden['ann%d_inv_scales' % i])
 
 
 def test_composite_field_head_equals_the_reference_package():
     """network.CompositeField4 (conv 1x1 -> PixelShuffle -> crop -> sigmoid / cell offsets / softplus) against
-    the reference's ``network/heads.py:272-378`` with identical weights: the field layout the decoder reads."""
-    from oracle import reference_python
-    import os
-    if not os.path.isdir(reference_python.REF_SRC):
-        pytest.skip('reference sources not present')
-    opp = reference_python.load()
+    the reference's ``network/heads.py:272-378`` with identical weights: the field layout the decoder reads (the
+    reference's outputs: tests/golden/make_golden_host.py)."""
     import torch
     from openpifpaf_amd import headmeta, network
-    torch.manual_seed(0)
+    golden = np.load(HOST_GOLDEN)
     mine_metas = headmeta.cocokp_metas()
-    ref_cif = opp.headmeta.Cif('cif', 'cocokp', keypoints=mine_metas[0].keypoints, sigmas=mine_metas[0].sigmas,
-                               pose=np.asarray(mine_metas[0].pose), draw_skeleton=mine_metas[1].skeleton)
-    ref_caf = opp.headmeta.Caf('caf', 'cocokp', keypoints=mine_metas[0].keypoints, sigmas=mine_metas[0].sigmas,
-                               pose=np.asarray(mine_metas[0].pose), skeleton=mine_metas[1].skeleton)
-    for m in (ref_cif, ref_caf):
-        m.base_stride, m.upsample_stride = 16, 2
-    x = torch.randn(2, 64, 7, 9)
-    for mine_meta, ref_meta in zip(mine_metas, (ref_cif, ref_caf)):
+    x = torch.from_numpy(golden['head_x'])
+    assert tuple(x.shape) == (2, 64, 7, 9)
+    for name, mine_meta in zip(('cif', 'caf'), mine_metas):
         mine = network.CompositeField4(mine_meta, 64).eval()
-        ref = opp.network.heads.CompositeField4(ref_meta, 64).eval()
-        ref.conv.load_state_dict(mine.conv.state_dict())
+        mine.conv.load_state_dict({'weight': torch.from_numpy(golden['head_%s_weight' % name]),
+                                   'bias': torch.from_numpy(golden['head_%s_bias' % name])})
+        b = torch.from_numpy(golden['head_%s_out' % name])
         with torch.no_grad():
-            a, b = mine(x), ref(x)
+            a = mine(x)
         assert a.shape == b.shape == (2, mine_meta.n_fields, 5 if mine_meta is mine_metas[0] else 8, 13, 17)
         assert torch.allclose(a, b, atol=1e-6), float((a - b).abs().max())
 
@@ -300,7 +293,7 @@ def test_host_tracking_classes_run_the_reference_bookkeeping_on_our_annotations(
     reference's tracker produced with its own decoder; and their default pose generator is the HIP CifCaf."""
     from oracle import reference_python
     import os
-    if not os.path.isdir(reference_python.REF_SRC):
+    if not os.path.isdir(reference_python.REF_SRC) or not reference.available():
         pytest.skip('reference sources not present')
     opp = reference_python.load()
     import sys
