@@ -105,7 +105,7 @@ typedef struct opa_shape {
 /* The structs above are passed by pointer and have grown over time (opa_shape::cifhr_pool_tiles is the latest field): a
  * caller built against another header would make the library read past its struct.  Check once at start-up that
  * opa_abi_version() == OPA_ABI_VERSION and opa_shape_bytes() == sizeof(opa_shape), opa_params_bytes() == sizeof(opa_params). */
-#define OPA_ABI_VERSION 6
+#define OPA_ABI_VERSION 7
 int opa_abi_version(void);
 size_t opa_shape_bytes(void);
 size_t opa_params_bytes(void);
@@ -144,9 +144,8 @@ int opa_set_params(const opa_params* in);
 /* ref: module.cpp:25,34  torch.classes.openpifpaf_decoder.CifCaf(n_keypoints, skeleton)
  * skeleton_host: int64 [n_bones, 2], 0-based joint indices, CAF field order
  * (ref: decoder/cifcaf.py:119-122).  The handle owns a small device copy of
- * the skeleton and its adjacency -- and, per caller stream it has decoded on, one side stream and two events (opa_debug::
- * side_stream), created at the first decode on that stream; it holds no per-call state, so one handle may be used from
- * several streams. */
+ * the skeleton and its adjacency; it holds no per-call state, so one handle may be used from several streams.  A decode
+ * queues all its work on the caller's stream. */
 typedef struct opa_cifcaf opa_cifcaf;
 int opa_cifcaf_create(opa_cifcaf** out, int32_t n_keypoints,
                       const int64_t* skeleton_host, int32_t n_bones);
@@ -170,10 +169,8 @@ int opa_cifcaf_set_tie_placement(opa_cifcaf* dec, int32_t inside_association);
 typedef struct opa_debug {
     int32_t stage_worklist;        /* 1: tiles of the CIF map through a work list, seeds from candidate lists (round 6); 0: round 5's
                                     *    per-plane tile kernel and a seed fill that streams the field      OPA_STAGE_WORKLIST      */
-    int32_t fuse_scored;           /* 0; 1: CafScored::fill rides in the seed sort's launch (round 3, slower) OPA_FUSE_SCORED       */
     int32_t scored_one_pass;       /* 1: a force-complete decode builds both CAF list sets from ONE read of the field (round 6);
                                     *    0: two passes                                                       OPA_SCORED_ONE_PASS   */
-    int32_t assoc_waves;           /* 0 = 12 waves per association workgroup; 8 (and 16 in -DOPA_ASSOC_ALL_WAVES builds) OPA_ASSOC_WAVES */
     int32_t assoc_growers;         /* 0 = as many growing waves as fit; n: at most n (other interleavings) OPA_ASSOC_GROWERS      */
     int32_t assoc_bbox;            /* 1: list scans skip chunks whose box misses the window                  OPA_ASSOC_BBOX         */
     int32_t assoc_dedup;           /* 1: later seeds of an occupancy cell already seen are dropped           OPA_ASSOC_DEDUP        */
@@ -185,17 +182,11 @@ typedef struct opa_debug {
     int32_t assoc_collide_shift;   /* 1: ... only near the centre of that box (0: anywhere inside, round 4)  OPA_ASSOC_COLLIDE_SHIFT */
     int32_t assoc_inherit;         /* 1: a candidate inherits the predictions of growths stopped for it      OPA_ASSOC_INHERIT      */
     int32_t assoc_lookahead;       /* 1: large skeletons: the next person's first seed enters the pool early OPA_ASSOC_LOOKAHEAD    */
-    int32_t assoc_help;            /* compiled-in variants only (-DOPA_ASSOC_HELPERS)                        OPA_ASSOC_HELP         */
-    int32_t assoc_spec;            /* compiled-in variants only (-DOPA_ASSOC_WALK)                           OPA_ASSOC_SPEC         */
     int32_t assoc_timing;          /* 0; 1: the coordinator fills its per-phase tick counters                OPA_ASSOC_TIMING       */
     int32_t assoc_persistent;      /* 0 = automatic: in a batch of more images than the chip has compute units the association
                                     *    workgroups take their images from a queue, most seeds first (round 6); 1: always;
                                     *    -1: never (workgroup b = image b)                                   OPA_ASSOC_PERSISTENT   */
     int32_t fc_split;              /* 0 = automatic; n: force-complete workgroups per image                  OPA_FC_SPLIT           */
-    int32_t side_stream;           /* one branch of the decode on a stream of the handle's own, joined before the association kernel
-                                    *    (round 6): 0 none; 1 the CAF lists beside the seed chain (measured: the two do not overlap, the
-                                    *    list building fills the chip); 2 the tie pass (as a launch of its own) beside the list building
-                                    *                                                                        OPA_SIDE_STREAM        */
     int64_t assoc_watchdog_ticks;  /* 1e8 (one second): 10-ns ticks after which a wait inside the association kernel gives up
                                     *    and the image is flagged OPA_COUNT_FAILED                           OPA_ASSOC_WATCHDOG_TICKS */
 } opa_debug;

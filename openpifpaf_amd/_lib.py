@@ -55,21 +55,20 @@ class Params(ctypes.Structure):
         return other
 
 
-ABI_VERSION = 6                      # OPA_ABI_VERSION of include/openpifpaf_amd.h
+ABI_VERSION = 7                      # OPA_ABI_VERSION of include/openpifpaf_amd.h
 
 
 class Debug(ctypes.Structure):
     """``opa_debug``: A/B and test switches of one decoder handle (none changes a result).  The library reads the ``OPA_*``
     environment variables once, when it is loaded, into the defaults; a decode reads only its handle's copy."""
     _fields_ = [
-        ('stage_worklist', ctypes.c_int32), ('fuse_scored', ctypes.c_int32), ('scored_one_pass', ctypes.c_int32),
-        ('assoc_waves', ctypes.c_int32), ('assoc_growers', ctypes.c_int32), ('assoc_bbox', ctypes.c_int32),
+        ('stage_worklist', ctypes.c_int32), ('scored_one_pass', ctypes.c_int32),
+        ('assoc_growers', ctypes.c_int32), ('assoc_bbox', ctypes.c_int32),
         ('assoc_dedup', ctypes.c_int32), ('assoc_prededup', ctypes.c_int32), ('assoc_predict', ctypes.c_int32),
         ('assoc_predict_min_v', ctypes.c_float), ('assoc_predict_th', ctypes.c_float),
         ('assoc_collide', ctypes.c_int32), ('assoc_collide_shift', ctypes.c_int32), ('assoc_inherit', ctypes.c_int32),
-        ('assoc_lookahead', ctypes.c_int32), ('assoc_help', ctypes.c_int32), ('assoc_spec', ctypes.c_int32),
+        ('assoc_lookahead', ctypes.c_int32),
         ('assoc_timing', ctypes.c_int32), ('assoc_persistent', ctypes.c_int32), ('fc_split', ctypes.c_int32),
-        ('side_stream', ctypes.c_int32),
         ('assoc_watchdog_ticks', ctypes.c_int64),
     ]
 

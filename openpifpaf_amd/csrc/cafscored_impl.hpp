@@ -1,24 +1,13 @@
-// CafScored::fill for one (image, CAF field) plane by one group of kScoredThreads threads: shared by cafscored_kernel
-// (cafscored.hip: one group per workgroup) and the fused sort + cafscored launch of the decode (cifseeds.hip: two
-// groups per 1024-thread workgroup, beside the seed sort's workgroups).  See cafscored.hip for the description.
+// CafScored::fill for one (image, CAF field) plane by one group of kScoredThreads threads (cafscored.hip: one group per
+// workgroup).  See cafscored.hip for the description.
 #pragma once
-#ifndef OPA_SCORED_EAGER
-#define OPA_SCORED_EAGER 0
-#endif
-#ifndef OPA_SCORED_PREFETCH
-#define OPA_SCORED_PREFETCH 2      // [r6] 1: the next confidence one step ahead, 250 -> 234 us at 256 images, wholebody 121 -> 110; 2: two steps deep (the
-                                   // next cell's six planes too), 233 -> 223 / 110 -> 106.5 / 46.5 -> 43.7 at 32 images (profiles/r6/cafscored_*prefetch_ab.log); 0: round 5's loop
-#endif
 #include "common.hpp"
 
 namespace opa {
 
 // One workgroup walks a field.  8 waves at 76 VGPRs: three workgroups per CU, so the 608 planes of a bench batch are
 // all resident at once; with 1024 threads a CU held one workgroup and the batch took three rounds (50 -> 37 us).
-#ifndef OPA_SCORED_THREADS
-#define OPA_SCORED_THREADS 512
-#endif
-constexpr int kScoredThreads = OPA_SCORED_THREADS;
+constexpr int kScoredThreads = 512;
 
 // Wave-wide min / max of a float with DPP row operations (register only; result broadcast from lane 63).
 // (A NaN coordinate never passes the window test and must not poison a box: callers feed the identity for it.)
@@ -98,25 +87,22 @@ __device__ __forceinline__ void cafscored_plane(const ScoredArgs& s, int plane_i
     const float stride_f = (float)stride;
     int base_f = 0, base_b = 0, parity = 0;
 
-#if OPA_SCORED_PREFETCH
-    // the confidence of the NEXT step's cell travels while this step is compacted (one load per thread, index clamped: no load
-    // under a condition): the first of a step's three dependent round trips is off its critical path
+    // [r6] the confidence of the NEXT step's cell travels while this step is compacted (one load per thread, index clamped: no load
+    // under a condition): the first of a step's three dependent round trips is off its critical path.  Two steps deep: the
+    // confidence two steps ahead, so that the other six planes of the NEXT step's cell can be requested -- where its confidence
+    // passes -- while this step waits for its map gathers: one exposed round trip per step.  Measured against round 5's loop
+    // (no prefetch) and one step ahead: 250 / 234 / 223 us at 256 images, wholebody 121 / 110 / 106.5, 32 images 46.5 -> 43.7
+    // (profiles/r6/cafscored_*prefetch_ab.log); the two shallower loops are removed.
     float c_pre = P[1 * HW + (tid < HW ? tid : HW - 1)];
-#endif
-#if OPA_SCORED_PREFETCH == 2
-    // two steps deep: the confidence two steps ahead, so that the other six planes of the NEXT step's cell can be
-    // requested -- where its confidence passes -- while this step waits for its map gathers: one exposed round trip per step
     float c_pre2 = P[1 * HW + (tid + kScoredThreads < HW ? tid + kScoredThreads : HW - 1)];
     float q2 = 0.f, q3 = 0.f, q4 = 0.f, q5 = 0.f, q6 = 0.f, q7 = 0.f;
     if (tid < HW && live && !((double)c_pre < score_th)) {
         q2 = P[2 * HW + tid]; q3 = P[3 * HW + tid]; q4 = P[4 * HW + tid]; q5 = P[5 * HW + tid]; q6 = P[6 * HW + tid]; q7 = P[7 * HW + tid];
     }
-#endif
     for (int c0 = 0; c0 < HW; c0 += kScoredThreads, parity ^= 1) {
         const int o = c0 + tid;
         bool keep_f = false, keep_b = false;
         float c = 0.f, cf = 0.f, cb = 0.f, x1 = 0.f, y1 = 0.f, x2 = 0.f, y2 = 0.f, s1 = 0.f, s2 = 0.f;
-#if OPA_SCORED_PREFETCH == 2
         const float c_now = c_pre;
         const float p2 = q2, p3 = q3, p4 = q4, p5 = q5, p6 = q6, p7 = q7;
         c_pre = c_pre2;
@@ -127,33 +113,11 @@ __device__ __forceinline__ void cafscored_plane(const ScoredArgs& s, int plane_i
                 q2 = P[2 * HW + on]; q3 = P[3 * HW + on]; q4 = P[4 * HW + on]; q5 = P[5 * HW + on]; q6 = P[6 * HW + on]; q7 = P[7 * HW + on];
             }
         }
-#elif OPA_SCORED_PREFETCH
-        const float c_now = c_pre;
-        { const int on = o + kScoredThreads; c_pre = P[1 * HW + (on < HW ? on : HW - 1)]; }
-#endif
         if (o < HW && live) {
-            // The source asks for all seven planes of the cell at once; the optimiser SINKS the six coordinate / scale loads
-            // into the threshold block below (ISA: confidence load, vmcnt(0), branch, then the six) -- a wave fetches them only
-            // where one of its cells passes: 41 MB per 32 images instead of 112 (that is the FETCH_SIZE the review of round 5
-            // could not explain), at the price of a second dependent round trip.  Forcing the seven loads to travel together
-            // (-DOPA_SCORED_EAGER=1) is slower: 49-50 against 48 us at 32 images, 277-280 against 250-253 at 256, wholebody
-            // 144 against 121 (profiles/r6/cafscored_eager_loads_ab.log) -- the compiler's choice stays.
-#if OPA_SCORED_PREFETCH
+            // (the six coordinate / scale planes are fetched only where the confidence passes; forcing all seven loads of every
+            // cell to travel together was slower in round 6 and is removed: profiles/r6/cafscored_eager_loads_ab.log)
             c = c_now;
-#else
-            c = P[1 * HW + o];
-#endif
-#if OPA_SCORED_PREFETCH == 2
             const float r2 = p2, r3 = p3, r4 = p4, r5 = p5, r6 = p6, r7 = p7;
-#else
-            const float r2 = P[2 * HW + o], r3 = P[3 * HW + o], r4 = P[4 * HW + o], r5 = P[5 * HW + o],
-                        r6 = P[6 * HW + o], r7 = P[7 * HW + o];
-#endif
-#if OPA_SCORED_EAGER
-            // (experiment: with the products computed out here the seven loads travel together)
-            x1 = r2 * stride_f; y1 = r3 * stride_f; x2 = r4 * stride_f; y2 = r5 * stride_f; s1 = r6 * stride_f; s2 = r7 * stride_f;
-            asm volatile("" : "+v"(x1), "+v"(y1), "+v"(x2), "+v"(y2), "+v"(s1), "+v"(s2));
-#endif
             if (!((double)c < score_th)) {                               // caf_scored.cpp:44
                 x1 = r2 * stride_f; y1 = r3 * stride_f;                  // :46-54
                 x2 = r4 * stride_f; y2 = r5 * stride_f;
@@ -230,17 +194,14 @@ __device__ __forceinline__ void cafscored_plane(const ScoredArgs& s, int plane_i
 // thresholds and outputs; everything that describes the field and the map is taken from `s`).
 //
 // kScoredCells cells per thread and step, the planes of the next step requested before this step's cells are looked at: both
-// are compile-time experiments of round 6 (-DOPA_SCORED_CELLS=n, the prefetch unless -DOPA_SCORED_NO_PREFETCH).  A read-only
+// were measured in round 6 (other cell counts and no prefetch are removed).  A read-only
 // stream of this shape reaches 6.2 TB/s on this chip (tools/gpu/micro/readbw.hip: 144 us for the field of 256 images) where the
 // single-set kernel takes 250 us -- 190 of them with a threshold nothing passes, i.e. no gather and no store: the price of a
 // barrier per step.  Measured at 256 images (profiles/r6/cafscored_variants.log): 1 / 2 / 4 cells per thread 269 / 267 / 314 us
 // with the prefetch, 273 / 271 without; 256-thread groups 271; none beats round 5's loop (252), which therefore stays for
 // the single set (cafscored_plane above) -- this routine serves the two-set pass, with one cell per thread.  Cell order
 // (r, wave, lane) is raster order, and the lists keep it.
-#ifndef OPA_SCORED_CELLS
-#define OPA_SCORED_CELLS 1
-#endif
-constexpr int kScoredCells = OPA_SCORED_CELLS;
+constexpr int kScoredCells = 1;
 
 template <bool TWO>
 __device__ __forceinline__ void cafscored_plane2(const ScoredArgs& s, const ScoredArgs& s2, int plane_in, int tid,
@@ -292,9 +253,6 @@ __device__ __forceinline__ void cafscored_plane2(const ScoredArgs& s, const Scor
     };
     request(0);
     for (int c0 = 0; c0 < HW; c0 += kStep, parity ^= 1) {
-#ifdef OPA_SCORED_NO_PREFETCH
-        if (c0) request(c0);
-#endif
         bool keep_f[kScoredCells], keep_b[kScoredCells], keep_f2[kScoredCells], keep_b2[kScoredCells];
         float cf[kScoredCells], cb[kScoredCells], cf2[kScoredCells], cb2[kScoredCells];
         float x1[kScoredCells], y1[kScoredCells], x2[kScoredCells], y2[kScoredCells], s1[kScoredCells], s2v[kScoredCells];
@@ -309,9 +267,7 @@ __device__ __forceinline__ void cafscored_plane2(const ScoredArgs& s, const Scor
             x2[r] = p4[r] * stride_f; y2[r] = p5[r] * stride_f;
             s1[r] = p6[r] * stride_f; s2v[r] = p7[r] * stride_f;
         }
-#ifndef OPA_SCORED_NO_PREFETCH
         if (c0 + kStep < HW) request(c0 + kStep);
-#endif
         // the map values of the step's cells: all slot-table loads first, then all tile loads (cifhr_value is two dependent loads)
         float fhr[kScoredCells], bhr[kScoredCells];
 #pragma unroll

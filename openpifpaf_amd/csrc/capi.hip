@@ -23,9 +23,7 @@ static float env_float(const char* name, float dflt) { const char* e = std::gete
 static opa_debug debug_from_environment() {
     opa_debug d;
     d.stage_worklist = env_int("OPA_STAGE_WORKLIST", 1) != 0;
-    d.fuse_scored = env_int("OPA_FUSE_SCORED", 0) != 0;
     d.scored_one_pass = env_int("OPA_SCORED_ONE_PASS", 1) != 0;
-    d.assoc_waves = env_int("OPA_ASSOC_WAVES", 0);
     d.assoc_growers = env_int("OPA_ASSOC_GROWERS", 0);
     d.assoc_bbox = env_int("OPA_ASSOC_BBOX", 1) != 0;
     d.assoc_dedup = env_int("OPA_ASSOC_DEDUP", 1) != 0;
@@ -37,11 +35,8 @@ static opa_debug debug_from_environment() {
     d.assoc_collide_shift = env_int("OPA_ASSOC_COLLIDE_SHIFT", 1);
     d.assoc_inherit = env_int("OPA_ASSOC_INHERIT", 1) != 0;
     d.assoc_lookahead = env_int("OPA_ASSOC_LOOKAHEAD", 1) != 0;
-    d.assoc_help = env_int("OPA_ASSOC_HELP", 1) != 0;
-    d.assoc_spec = env_int("OPA_ASSOC_SPEC", 1) != 0;
     d.assoc_timing = env_int("OPA_ASSOC_TIMING", 0) != 0;
     d.assoc_persistent = env_int("OPA_ASSOC_PERSISTENT", 0);
-    d.side_stream = env_int("OPA_SIDE_STREAM", 0);
     d.fc_split = env_int("OPA_FC_SPLIT", 0);
     d.assoc_watchdog_ticks = 100000000ll;
     if (const char* e = std::getenv("OPA_ASSOC_WATCHDOG_TICKS")) { const long long v = std::atoll(e); if (v > 0) d.assoc_watchdog_ticks = v; }
@@ -227,36 +222,7 @@ struct opa_cifcaf {
     int device;
     int tie_inside;                    // opa_cifcaf_set_tie_placement: -1 process-wide choice, 0 own launch, 1 inside the association kernel
     opa_debug debug;                   // opa_cifcaf_set_debug
-    // Side streams (round 6): CafScored::fill only needs the finished map, the seed chain (fill, sort, rank merge, tie pass) only
-    // needs the finished map -- two branches that meet at the association kernel.  The list building runs on a stream of the
-    // library's own beside the seed chain: one per caller stream, created at the first decode on that stream, joined back before
-    // the association kernel is queued (event fork / join: capturable into a HIP graph like everything else).
-    struct Side { hipStream_t main, side; hipEvent_t fork, join; };
-    std::vector<Side> sides;
-    std::mutex sides_mutex;
 };
-
-static bool side_for(opa_cifcaf* dec, hipStream_t main, opa_cifcaf::Side* out) {
-    std::lock_guard<std::mutex> lock(dec->sides_mutex);
-    for (const auto& s : dec->sides)
-        if (s.main == main) { *out = s; return true; }
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(main, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
-        (void)hipGetLastError();
-        return false;                                 // (no stream is created in the middle of a capture: this decode runs on one stream)
-    }
-    opa_cifcaf::Side s; s.main = main;
-    int lo = 0, hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    // (mode 1 -- the lists on the side stream -- wants the LOWEST priority there, mode 2 -- the tie pass -- the highest: its fat
-    // workgroups only find room beside the list building when the dispatcher prefers them)
-    if (hipStreamCreateWithPriority(&s.side, hipStreamNonBlocking, dec->debug.side_stream == 2 ? hi : lo) != hipSuccess) { (void)hipGetLastError(); return false; }
-    if (hipEventCreateWithFlags(&s.fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&s.join, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); return false; }
-    dec->sides.push_back(s);
-    *out = s;
-    return true;
-}
 
 extern "C" {
 
@@ -364,7 +330,6 @@ int opa_cifcaf_create(opa_cifcaf** out, int32_t n_keypoints, const int64_t* skel
 void opa_cifcaf_destroy(opa_cifcaf* dec) {
     if (!dec) return;
     if (dec->dev_block) (void)hipFree(dec->dev_block);
-    for (auto& s : dec->sides) { (void)hipStreamDestroy(s.side); (void)hipEventDestroy(s.fork); (void)hipEventDestroy(s.join); }
     delete dec;
 }
 
@@ -458,12 +423,11 @@ int opa_cifcaf_workspace_view(const opa_shape* shape, const char* what, size_t* 
     return fail(OPA_ERR_INVALID_ARGUMENT, std::string("opa_cifcaf_workspace_view: unknown buffer ") + what);
 }
 
-int opa_cifcaf_decode(const opa_cifcaf* dec_in, const opa_shape* shape, const opa_params* params,
+int opa_cifcaf_decode(const opa_cifcaf* dec, const opa_shape* shape, const opa_params* params,
                       const float* cif_dev, const float* caf_dev,
                       const float* initial_dev, const int64_t* initial_ids_dev, int32_t n_initial,
                       void* workspace_dev, size_t workspace_bytes,
                       float* out_dev, int64_t* out_ids_dev, int32_t* out_count_dev, void* stream) {
-    opa_cifcaf* dec = const_cast<opa_cifcaf*>(dec_in);   // (the handle's side streams are created on first use, under its mutex)
     if (!dec || !shape || !cif_dev || !caf_dev || !workspace_dev || !out_dev || !out_ids_dev || !out_count_dev)
         return fail(OPA_ERR_INVALID_ARGUMENT, "opa_cifcaf_decode: null argument");
     if (n_initial < 0 || (n_initial > 0 && !initial_dev))
@@ -512,10 +476,8 @@ int opa_cifcaf_decode(const opa_cifcaf* dec_in, const opa_shape* shape, const op
                      (int32_t*)(ws + L.off_seed_count), &pool, dec->debug.stage_worklist ? &cand : nullptr);   // cifcaf.cpp:140-141
     if (e != hipSuccess) return fail_hip(e, "cifhr");
     // CafScored::fill (:153-161) of the caf_th list set and, for force complete, of the second one (:419-420): launches of
-    // their own.  (OPA_FUSE_SCORED=1 lets them ride in the seed sort's launch, two 512-thread groups per workgroup beside
-    // the sort's workgroups -- measured in round 3: 90 us against 42 + 41 us one after the other, 323 against 170 us with
-    // the force-complete set: under the sort kernel's 64 KiB of static LDS and 1024-thread workgroups the list building
-    // gets two workgroups per compute unit instead of its six, and loses more than the overlap gives.)
+    // their own.  (Riding in the seed sort's launch was measured in round 3 -- 90 us against 42 + 41 one after the other: under
+    // the sort kernel's 64 KiB of static LDS the list building gets two workgroups per compute unit instead of six -- and removed.)
     ScoredArgs scored[2];
     int n_scored = 0;
     scored[n_scored++] = make_scored_args(caf_dev, L.B, L.A, L.cH, L.cW, L.cstride, cifhr, L.F, L.hr_rows, L.hr_cols, L.hr_pitch,
@@ -530,7 +492,6 @@ int opa_cifcaf_decode(const opa_cifcaf* dec_in, const opa_shape* shape, const op
                                               p.ablation_caf_no_rescore, (float*)(ws + L.off_lists_fc),
                                               (int32_t*)(ws + L.off_list_counts_fc), (float*)(ws + L.off_list_bbox_fc),
                                               L.bbox_chunks, L.bbox_chunks, nullptr, &pool);
-    const bool fuse = dec->debug.fuse_scored != 0;
     TieScratch ties;
     ties.big = ws + L.off_act; ties.big_stride = (size_t)L.F * 4 * (L.H * L.W) * sizeof(float);
     ties.small_ = ws + L.off_tie_small; ties.small_stride = L.tie_small_stride;
@@ -541,67 +502,25 @@ int opa_cifcaf_decode(const opa_cifcaf* dec_in, const opa_shape* shape, const op
     // kernels (wall per decode: 32 COCO images 0.730 -> 0.713 ms, 256 images 1.563 -> 1.502 ms, 16 wholebody images 3.42 -> 3.36 ms).
     // (round 6: inside the association kernel unless the decoder asks for the launch of its own -- measured shorter for one decode
     // of 32 or 256 COCO images and of 16 wholebody images alike, profiles/r6/tie_placement.log)
-    // The branches behind the finished map -- the CAF lists, the seed chain (fill, sort, rank merge), the tie pass -- meet at the
-    // association kernel.  opa_debug::side_stream puts one of them on the handle's side stream (not while this thread profiles the
-    // stream with events -- their times are per kernel in a row -- and not when the side stream cannot be had, e.g. the first
-    // decode of a handle inside a graph capture): 1 = the lists beside the whole seed chain (measured: no overlap, the list
-    // building fills the chip and the sort's fat workgroups find no room beside it); 2 = the TIE PASS, a launch of its own, beside
-    // the list building -- one workgroup per image that needs most of a compute unit's LDS but few of its wave slots.
-    opa_cifcaf::Side side;
-    const bool forked = !fuse && dec->debug.side_stream != 0 && !(g_prof.on && g_prof.st == st) && side_for(dec, st, &side);
-    const bool tie_on_side = forked && dec->debug.side_stream == 2 && seed_tie_order() >= 1 && dec->tie_inside != 1;
-    const bool lists_on_side = forked && dec->debug.side_stream == 1;
-    const bool fuse_ties = seed_tie_order() >= 1 && !tie_on_side && (dec->tie_inside >= 0 ? dec->tie_inside == 1 : true);
-    ties.defer = fuse_ties || tie_on_side ? 1 : 0;
-    auto lists = [&](hipStream_t ls) -> int {
-        if (n_scored == 2 && dec->debug.scored_one_pass) {     // both list sets from one read of the field (round 6)
-            const hipError_t le = launch_cafscored2(scored[0], scored[1], ls);
-            if (le != hipSuccess) return fail_hip(le, "cafscored(both list sets)");
-        } else
-            for (int k = 0; k < n_scored; k++) {
-                const hipError_t le = launch_cafscored(scored[k], ls);
-                if (le != hipSuccess) return fail_hip(le, k ? "cafscored(force complete)" : "cafscored");
-            }
-        return OPA_OK;
-    };
-    if (lists_on_side) {
-        e = hipEventRecord(side.fork, st);
-        if (e == hipSuccess) e = hipStreamWaitEvent(side.side, side.fork, 0);
-        if (e != hipSuccess) return fail_hip(e, "fork to the side stream");
-        const int rc = lists(side.side);
-        if (rc != OPA_OK) return rc;
-        e = hipEventRecord(side.join, side.side);
-        if (e != hipSuccess) return fail_hip(e, "side stream");
-    }
+    // Everything runs on the caller's stream.  (Round 6 measured a side stream and removed it: the lists beside the seed chain did
+    // not overlap, profiles/r6/side_stream_timeline.log; the tie pass beside the lists lost to the pass inside the association
+    // kernel, profiles/r6/tie_side.log.)
+    const bool fuse_ties = seed_tie_order() >= 1 && dec->tie_inside != 0;
+    ties.defer = fuse_ties ? 1 : 0;
     e = launch_cifseeds(cif_dev, L.B, L.F, L.H, L.W, L.stride, cifhr, L.hr_rows, L.hr_cols, L.hr_pitch, p,
                         (unsigned long long*)(ws + L.off_seed_keys), L.sort_cap,
                         (int32_t*)(ws + L.off_seed_count), (int32_t*)(ws + L.off_seed_f),
                         (float*)(ws + L.off_seed_vxys), st, false, (int32_t*)(ws + L.off_seed_cell),
-                        L.occ_h, L.occ_w, true, fuse ? scored : nullptr, fuse ? n_scored : 0, &ties, &pool, &cand,
-                        dec->debug.stage_worklist != 0);                                              // :144-146
+                        L.occ_h, L.occ_w, true, &ties, &pool, &cand, dec->debug.stage_worklist != 0);   // :144-146
     if (e != hipSuccess) return fail_hip(e, "cifseeds");
-    if (lists_on_side) {
-        e = hipStreamWaitEvent(st, side.join, 0);
-        if (e != hipSuccess) return fail_hip(e, "join of the side stream");
-    } else if (!fuse) {
-        if (tie_on_side) {                            // the seeds are sorted: the tie pass beside the list building
-            TieArgs ta; SortArgs tg;
-            make_tie_args(&ta, &tg, (unsigned long long*)(ws + L.off_seed_keys), L.sort_cap, (int32_t*)(ws + L.off_seed_count), cif_dev,
-                          L.F, 5, L.H * L.W, L.stride, (int32_t*)(ws + L.off_seed_f), (float*)(ws + L.off_seed_vxys),
-                          (int32_t*)(ws + L.off_seed_cell), L.occ_h, L.occ_w, ties);
-            e = hipEventRecord(side.fork, st);
-            if (e == hipSuccess) e = hipStreamWaitEvent(side.side, side.fork, 0);
-            if (e == hipSuccess) e = launch_cifseeds_ties(ta, tg, L.B, p, side.side);
-            if (e == hipSuccess) e = hipEventRecord(side.join, side.side);
-            if (e != hipSuccess) return fail_hip(e, "tie pass on the side stream");
+    if (n_scored == 2 && dec->debug.scored_one_pass) {       // both list sets from one read of the field (round 6)
+        e = launch_cafscored2(scored[0], scored[1], st);
+        if (e != hipSuccess) return fail_hip(e, "cafscored(both list sets)");
+    } else
+        for (int k = 0; k < n_scored; k++) {
+            e = launch_cafscored(scored[k], st);
+            if (e != hipSuccess) return fail_hip(e, k ? "cafscored(force complete)" : "cafscored");
         }
-        const int rc = lists(st);
-        if (rc != OPA_OK) return rc;
-        if (tie_on_side) {
-            e = hipStreamWaitEvent(st, side.join, 0);
-            if (e != hipSuccess) return fail_hip(e, "join of the side stream");
-        }
-    }
     // (the occupancy map of :173 is a bitmap the association kernel clears itself)
     AssocArgs a;
     a.B = L.B; a.K = L.K; a.F = L.F; a.A = L.A; a.max_ann = L.max_ann; a.n_initial = n_initial;
@@ -700,7 +619,7 @@ int opa_cifseeds_fill(const float* cif_dev, int32_t batch, int32_t n_cif, int32_
                                    (cif_h - 1) * stride + 1, (cif_w - 1) * stride + 1, opa_cifhr_pitch(cif_w, stride),
                                    p, (unsigned long long*)scratch_dev, sort_cap_for(n_cif * cif_h * cif_w),
                                    seed_count_dev, seed_f_dev, seed_vxys_dev, (hipStream_t)stream, false, nullptr, 0, 0, false,
-                                   nullptr, 0, &ties);
+                                   &ties);
     if (e != hipSuccess) return fail_hip(e, "cifseeds");
     return OPA_OK;
 }
@@ -721,7 +640,7 @@ int opa_cifdetseeds_fill(const float* field_dev, int32_t batch, int32_t n_fields
                                    (field_h - 1) * stride + 1, (field_w - 1) * stride + 1,
                                    opa_cifhr_pitch(field_w, stride), p, (unsigned long long*)scratch_dev,
                                    sort_cap_for(n_fields * field_h * field_w), seed_count_dev, seed_f_dev,
-                                   seed_vxywh_dev, (hipStream_t)stream, true, nullptr, 0, 0, false, nullptr, 0, &ties);
+                                   seed_vxywh_dev, (hipStream_t)stream, true, nullptr, 0, 0, false, &ties);
     if (e != hipSuccess) return fail_hip(e, "cifdetseeds");
     return OPA_OK;
 }
@@ -835,8 +754,7 @@ int opa_cifdet_decode(const opa_det_shape* shape, const opa_params* params, cons
     ties.defer = 0;
     e = launch_cifseeds(field_dev, B, F, H, W, shape->stride, cifhr, L.hr_rows, L.hr_cols, L.hr_pitch, p,
                         (unsigned long long*)(ws + L.off_keys), L.sort_cap, (int32_t*)(ws + L.off_seed_count),
-                        (int32_t*)(ws + L.off_seed_f), (float*)(ws + L.off_seed_v), st, true, nullptr, 0, 0, false, nullptr, 0,
-                        &ties);                                                                          // :34-36
+                        (int32_t*)(ws + L.off_seed_f), (float*)(ws + L.off_seed_v), st, true, nullptr, 0, 0, false, &ties);                                                                          // :34-36
     if (e != hipSuccess) return fail_hip(e, "cifdetseeds");
     const int occ_h = (int)((double)L.hr_rows / hp.occupancy_reduction) + 1;
     const int occ_w = (int)((double)L.hr_cols / hp.occupancy_reduction) + 1;

@@ -58,7 +58,7 @@
 
 namespace opa {
 
-constexpr int kAssocWavesDefault = 12;   // waves per workgroup of the association kernel (OPA_ASSOC_WAVES = 8 | 12 | 16)
+constexpr int kAssocWaves = 12;          // waves per workgroup of the association kernel: 1 coordinator + up to 11 growers
 constexpr int kBlendChunks = 8;
 // Seed-pool slots per coordinator lane.  Every serial step of the coordinator (commit test, head search, hand-out) and every
 // published joint of a grower walks ALL slots, so the pool is as small as the window of live seeds needs to be:
@@ -68,29 +68,11 @@ constexpr int kBlendChunks = 8;
 //   large skeletons (LDS variant, wholebody): 8.  16 (a person has a thousand seeds: a window of several people) was measured in
 //     round 4: the image it was meant for gained 15 %, the batch lost 4 % -- every published joint tests twice the slots, and the
 //     pool's LDS costs the eleventh grower.
-#ifndef OPA_POOL_SLOTS
-#define OPA_POOL_SLOTS 4
-#endif
-#ifndef OPA_POOL_SLOTS_LDS
-#define OPA_POOL_SLOTS_LDS 8
-#endif
-constexpr int kPoolSlots = OPA_POOL_SLOTS;
-// Who hands a candidate to an idle grower (-DOPA_ASSOC_SELFSERVE=1 builds the second variant; build.py builds it as
-// lib/libopenpifpaf_amd_selfserve.so and tests/test_gpu_selfserve.py decodes through it).  0, the default: the coordinator (one
-// more serial step of the one wave everything waits for, 0.7 us per hand-out, a fifth of its time on a crowded image).  1 (round
-// 5): the idle grower itself -- it looks at the mirrored pool the way the coordinator did (smallest eligible seed index, not
-// predicted dead, tested by every candidate in flight, not inside the seed box of a candidate that has not published yet) and
-// CLAIMS the slot with a compare-and-swap on the slot's owner word; the coordinator learns who grows what from those words.
-// Which seeds are grown when is advisory either way: the commit decides, in seed order, from final boxes.  Measured (COCO batch
-// 32, profiles/r5/assoc_selfserve.log): the coordinator then waits for the head's growth 60 % of its time (305 of 513 us on the
-// crowded image, hand-out 88 -> 0, other 127 -> 95) -- and the launch lasts as long as before (508 against 505 us): what is left
-// is the chain of growths itself, not the wave that serialises them.  As a run-time switch the second path costs the default one
-// 1.3 % (eight spilled registers in the growers): compiled out by default; statistics slot 5 is not counted in that variant.
-#ifndef OPA_ASSOC_SELFSERVE
-#define OPA_ASSOC_SELFSERVE 0
-#endif
-constexpr bool kSelfServe = OPA_ASSOC_SELFSERVE != 0;
-constexpr int kPoolSlotsLds = OPA_POOL_SLOTS_LDS;
+constexpr int kPoolSlots = 4, kPoolSlotsLds = 8;
+// The coordinator hands every candidate to an idle grower: one more serial step of the one wave everything waits for (0.7 us per
+// hand-out, a fifth of its time on a crowded image).  Idle growers that claim their next candidate themselves were measured in
+// round 5 and removed (profiles/r5/assoc_selfserve.log): the launch lasted as long as before -- what is left is the chain of
+// growths itself, not the wave that serialises them.
        // list entries per lane held in registers by the single-pass scan
 
 // LDS words shared between the coordinator and the growers: plain loads/stores made atomic at workgroup
@@ -178,17 +160,6 @@ struct ImageCtx {
     int* sh_counts;                      // [2A] list lengths of the active list set
     int n_blend;                         // list scans of this wave (statistics)
     int t_blend, t_blend_mem;            // ticks inside the scans, and of those until the loads had returned
-    // speculative batched evaluation (spec_phase): per joint `kind | flags | slot << 8`, per bone `state | slot << 8` and the
-    // connection value the bone's scans gave (private LDS, null: off)
-    int *sp_j, *sp_b;
-    double* sp_v; float *sp_x, *sp_y, *sp_s;
-    unsigned char *sp_match, *sp_fromc;  // LDS variant of the growth state: joint assigned with its candidate's values [K]; entry of the bone came from the cache [A]
-    int sp_pcap;                         // passing entries the scan area holds during a batch
-    // scan helpers (help_*): requests of this growth [kHelpRing], a word per bone [A], the slot each joint was assigned through [K],
-    // control words (0 epoch, 1 closed, 2-3 mask of assigned joints for the register variant); null: off
-    int *hq, *rq, *jsrc, *hctl;
-    int hq_n, h_epoch;                   // requests posted so far, this growth's epoch
-    int n_hit, n_miss;                   // statistics: connection values taken from the cache / evaluated on demand
 };
 
 __device__ __forceinline__ ListView list_view(const ImageCtx& c, int bone, int dir) {
@@ -809,208 +780,9 @@ __device__ __forceinline__ BlendResult blend(ImageCtx& c, const ListView& L, dou
 #endif
 }
 
-// ------------------------------------------------------------ batched list scans (lane = job)
-// grow_connection_blend (cifcaf.cpp:32-103) for up to 64 (list, query) pairs at once.  _connection_value (:349-411) of a
-// bone depends on nothing but its start joint, so the bones a new joint adds -- and the bones of every joint that became a
-// candidate in the same level of the search -- are scanned TOGETHER: one query setup for all of them (lane = job), the
-// chunk boxes of every job tested side by side, the loads of eight (job, chunk) items in flight at once, the passing
-// entries of all jobs compacted job by job into the wave's scan area, ONE pass of the double-precision exp over them
-// (lane = entry), the top two of every job by the reference's own sequential rule (:65-73, lane = job, each lane walks
-// its job's entries in list order), and one round trip for the target columns of the winners.  A batch costs about what
-// one scan costs (two memory round trips); the results are those of the single scans bit for bit (same score_of, same
-// blend_finish, and the top-2 rule is the reference's loop itself).
-// The level walk (spec_phase, below) is compiled in only with -DOPA_ASSOC_WALK (build.build_diagnostic('OPA_ASSOC_WALK', 'walk')):
-// measured in round 5 (profiles/r5/rejected_level_walk.log) it is exact and halves the growths started, but a batch of n scans
-// costs what n single scans cost, so the growths get slower, not faster; with the switch off the kernels carry none of it.
-#ifdef OPA_ASSOC_WALK
-constexpr bool kWalk = true;
-#else
-constexpr bool kWalk = false;
-#endif
-// ---- scan helpers.  _connection_value (cifcaf.cpp:349-411) of a bone depends on its start joint alone, so it can be computed
-// by ANOTHER wave as soon as that joint's values are known -- i.e. as soon as the connection that leads to the joint has
-// been evaluated, usually long before the search assigns the joint and pops the bone.  The grower posts "joint b, reached
-// through slot u, has these values" (help_post); idle growers look at the requests of the growth that holds the HEAD seed --
-// the one the commit waits for -- claim the bones leaving b one at a time (a word per bone, compare-and-swap) and leave
-// the connection value in the master's entry array; the master's heap loop, unchanged, takes it from there when it pops
-// the bone, provided b was indeed assigned through u (then the values are the ones _connection_value would compute, bit
-// for bit: same code, same inputs); anything else it evaluates itself, as before.  The head's growth becomes a chain of
-// heap operations with the list scans done beside it.
-// Compiled in only with -DOPA_ASSOC_HELPERS: measured in round 5 (profiles/r5/rejected_scan_helpers.log) it is exact (153 GPU
-// tests) and changes nothing -- while the head's pose grows, the other growers are busy with growths of their own (the idle
-// half of the growers' time lies in the tail of one- and two-joint poses), and the second copy of the scan code costs the
-// 12-wave kernel 18 spilled registers (COCO 597 -> 625 us with it on, 558 without it in the build).
-#ifdef OPA_ASSOC_HELPERS
-constexpr bool kHelp = true;
-#else
-constexpr bool kHelp = false;
-#endif
-constexpr int kHelpRing = 16;
-constexpr int kRqFree = 0, kRqTaken = 1, kRqOk = 2, kRqRej = 3, kRqMaster = 4;   // word of a bone: state | slot << 3 | source slot << 12 | epoch << 21
-constexpr int kSrcStart = 511;           // "source slot" of a joint the pose started with
-__device__ __forceinline__ int rq_word(int state, int slot, int src, int ep) { return state | (slot << 3) | (src << 12) | (ep << 21); }
-// memo words of the level walk
-constexpr int kSpActual = 1, kSpCand = 2, kSpKind = 3, kSpOpen = 4, kSpNext = 8;     // per joint: kind, "its bones are this level's jobs", "became a candidate in this level"
-constexpr int kSbOk = 1, kSbRejected = 2, kSbUnknown = 3, kSbPending = 4;            // per bone: connection holds / _connection_value returns the zero joint / not evaluated here / forward scan done, reverse scan outstanding
-constexpr int kSpecItems = 128;          // (job, chunk) items of one batch
-constexpr int kSpecGroup = 6;            // items whose loads are in flight together
-constexpr int kSpecEntryWords = 7;       // a passing entry in the scan area: x1, y1, c -> score, x2, y2, s2, job
-struct SpecOut { int ok; double v; float x, y, s; };   // ok: 1 a joint, 0 the all-zero joint (:76), -1 not evaluated (left to the single scans)
-
-__device__ __forceinline__ int rlane_i(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
-__device__ __forceinline__ float rlane_f(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+// lane-indexed permutes (ds_bpermute): lane l gets `v` of lane `src`
 __device__ __forceinline__ int bperm_i(int v, int src) { return __builtin_amdgcn_ds_bpermute(src << 2, v); }
 __device__ __forceinline__ float bperm_f(float v, int src) { return __int_as_float(bperm_i(__float_as_int(v), src)); }
-__device__ __forceinline__ double bperm_d(double v, int src) {
-    return __hiloint2double(bperm_i(__double2hiint(v), src), bperm_i(__double2loint(v), src));
-}
-__device__ __forceinline__ int spec_pcap(int tgt_floats) {   // the scan area: items, a segment per job, then seven words per passing entry
-    return (tgt_floats - kSpecItems - 2 * kWave) / kSpecEntryWords;
-}
-
-__device__ __forceinline__ SpecOut spec_scan_batch(ImageCtx& c, bool active, int li, double x, double y, double s, double filter_sigmas) {
-    const int lane = lane_id();
-    int* item = reinterpret_cast<int*>(c.tgt);               // job | chunk << 8 | first item of its job << 16
-    int* seg = item + kSpecItems;                            // [2][64] where a job's passing entries start / end
-    const int pcap = c.sp_pcap;
-    float* cx = reinterpret_cast<float*>(seg + 2 * kWave); float* cy = cx + pcap; float* cv = cy + pcap;
-    float* tx = cv + pcap; float* ty = tx + pcap; float* ts = ty + pcap;
-    int* cj = reinterpret_cast<int*>(ts + pcap);             // the entry's job
-    const BlendQuery q = make_query(x, y, s, filter_sigmas);
-    const int n = active ? c.sh_counts[li] : 0;
-    const int nch = (n + kWave - 1) >> 6;
-    int status = !active ? -1 : n <= 0 ? 0 : nch <= kListBboxChunks ? 1 : -1;   // 1: scanned here
-    unsigned mask = 0u;                                      // the chunks of the list whose box meets the window (cifcaf.cpp:54-57)
-    if (c.bbox) {
-        for (int ch0 = 0; __ballot(status == 1 && ch0 < nch) != 0ull; ch0 += 4) {   // four boxes per LDS round trip
-            float4 bb[4];
-#pragma unroll
-            for (int r = 0; r < 4; r++) bb[r] = c.bbox[(status == 1 ? li : 0) * kListBboxChunks + ((ch0 + r) & (kListBboxChunks - 1))];
-#pragma unroll
-            for (int r = 0; r < 4; r++)
-                if (status == 1 && ch0 + r < nch && bb[r].x <= q.fxhi && bb[r].y >= q.fxlo && bb[r].z <= q.fyhi && bb[r].w >= q.fylo)
-                    mask |= 1u << (ch0 + r);
-        }
-    } else if (status == 1) {
-        mask = (1u << nch) - 1u;
-    }
-    PH(22);
-    // where the job's items go: exclusive prefix of the chunk counts (<= 16 each: five ballots)
-    const int cnt = __popc(mask);
-    int base = 0, total = 0;
-#pragma unroll
-    for (int bit = 0; bit < 5; bit++) {
-        const unsigned long long m = __ballot((cnt >> bit) & 1);
-        base += prefix_count(m) << bit; total += __popcll(m) << bit;
-    }
-    int W = total;
-    if (total > kSpecItems) {                                // (the jobs that fit are a prefix of the jobs: the offsets only grow)
-        const bool fits = base + cnt <= kSpecItems;
-        const unsigned long long fm = __ballot(fits && cnt > 0);
-        W = fm ? rlane_i(base + cnt, 63 - __builtin_clzll(fm)) : 0;
-        if (!fits && cnt > 0) { status = -1; mask = 0u; }
-    }
-    {
-        unsigned m = mask; int k = 0;
-        while (__ballot(m != 0u) != 0ull)
-            if (m) { const int ch = __builtin_ctz(m); m &= m - 1u; item[base + k] = lane | (ch << 8) | (k == 0 ? 1 << 16 : 0); k++; }
-    }
-    seg[lane] = 0; seg[kWave + lane] = 0;
-    wave_sync();
-    PH(23);
-    // ---- the items, kSpecGroup at a time: all six columns of a group's entries back to back, then window test + ordered
-    //      compaction of what passes (the target columns travel along: no second round trip for the winners)
-    const gfloat* g = (const gfloat*)c.lists;
-    const unsigned cap = (unsigned)c.list_cap;
-    const unsigned loff = (unsigned)li * 7u * cap;
-    int np = 0;                                              // passing entries so far (uniform)
-    for (int w0 = 0; w0 < W; w0 += kSpecGroup) {
-        int d[kSpecGroup];
-#pragma unroll
-        for (int r = 0; r < kSpecGroup; r++) d[r] = item[w0 + r < W ? w0 + r : W - 1];
-#pragma unroll
-        for (int r = 0; r < kSpecGroup; r++) asm volatile("" : "+v"(d[r]) :: "memory");
-        float x1[kSpecGroup], y1[kSpecGroup], cc[kSpecGroup], x2[kSpecGroup], y2[kSpecGroup], s2[kSpecGroup];
-#pragma unroll
-        for (int r = 0; r < kSpecGroup; r++) {
-            x1[r] = y1[r] = cc[r] = x2[r] = y2[r] = s2[r] = 0.f;
-            if (w0 + r < W) {                                // (uniform)
-                const int dd = __builtin_amdgcn_readfirstlane(d[r]);
-                const int j = dd & 0xff, ch = (dd >> 8) & 0xff;
-                const unsigned i = (unsigned)(ch * kWave + lane);
-                const unsigned o = (unsigned)rlane_i((int)loff, j) + (i < (unsigned)rlane_i(n, j) ? i : 0u);
-                cc[r] = g[o]; x1[r] = g[o + cap]; y1[r] = g[o + 2u * cap];
-                x2[r] = g[o + 3u * cap]; y2[r] = g[o + 4u * cap]; s2[r] = g[o + 6u * cap];
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < kSpecGroup; r++)
-            asm volatile("" : "+v"(x1[r]), "+v"(y1[r]), "+v"(cc[r]), "+v"(x2[r]), "+v"(y2[r]), "+v"(s2[r]) :: "memory");
-#pragma unroll
-        for (int r = 0; r < kSpecGroup; r++) {
-            if (w0 + r >= W) break;
-            const int dd = __builtin_amdgcn_readfirstlane(d[r]);
-            const int j = dd & 0xff, ch = (dd >> 8) & 0xff;
-            const int i = ch * kWave + lane;
-            const bool pass = i < rlane_i(n, j) && x1[r] >= rlane_f(q.fxlo, j) && x1[r] <= rlane_f(q.fxhi, j) &&
-                              y1[r] >= rlane_f(q.fylo, j) && y1[r] <= rlane_f(q.fyhi, j);
-            const unsigned long long m = __ballot(pass);
-            const int pc = __popcll(m);
-            if (lane == 0) { if (dd >> 16) seg[j] = np; seg[kWave + j] = np + pc; }
-            const int slot = np + prefix_count(m);
-            if (pass && slot < pcap) {
-                cx[slot] = x1[r]; cy[slot] = y1[r]; cv[slot] = cc[r]; tx[slot] = x2[r]; ty[slot] = y2[r]; ts[slot] = s2[r]; cj[slot] = j;
-            }
-            np += pc;
-        }
-    }
-    wave_sync();
-    PH(24);
-    // ---- scores of the passing entries (:60-63), lane = entry; the entry's query comes from its job's lane
-    const int tot = np < pcap ? np : pcap;
-    for (int e0 = 0; e0 < tot; e0 += kWave) {
-        const int e = e0 + lane;
-        const bool have = e < tot;
-        const int j = have ? cj[e] : 0;
-        BlendQuery qq;
-        qq.x = bperm_d(q.x, j); qq.y = bperm_d(q.y, j); qq.sigma2 = bperm_f(q.sigma2, j);
-        if (have) cv[e] = score_of(qq, cx[e], cy[e], cv[e]);
-    }
-    wave_sync();
-    PH(25);
-    // ---- the top two of every job: the reference's loop (:65-73) over the job's entries in list order, lane = job
-    //      (four entries per LDS round trip)
-    const int lo = seg[lane], hi = seg[kWave + lane];
-    if (status == 1 && hi > pcap) status = -1;               // more passing entries than the area holds: the single scans
-    float s1 = 0.0f, s2 = 0.0f; int e1 = 0, e2 = 0;
-    for (int e0 = lo; __ballot(status == 1 && e0 < hi) != 0ull; e0 += 4) {
-        float sc[4];
-#pragma unroll
-        for (int r = 0; r < 4; r++) sc[r] = cv[status == 1 && e0 + r < hi ? e0 + r : 0];
-#pragma unroll
-        for (int r = 0; r < 4; r++) asm volatile("" : "+v"(sc[r]) :: "memory");
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-            if (status == 1 && e0 + r < hi) {
-                if (sc[r] >= s1) { s2 = s1; e2 = e1; s1 = sc[r]; e1 = e0 + r; }
-                else if (sc[r] > s2) { s2 = sc[r]; e2 = e0 + r; }
-            }
-    }
-    PH(26);
-    SpecOut o; o.ok = status; o.v = 0.0; o.x = o.y = o.s = 0.f;
-    if (status == 1) {
-        if (s1 == 0.0f) o.ok = 0;                            // :76
-        else {
-            const float e1x = tx[e1], e1y = ty[e1], e1s = ts[e1];
-            const float e2x = tx[e2], e2y = ty[e2], e2s = ts[e2];     // (s2 == 0: e2 = 0, a valid slot nobody looks at, :84)
-            const BlendResult r = blend_finish(s1, s2, true, false, e1x, e1y, e1s, e2x, e2y, e2s);
-            o.v = r.v; o.x = r.x; o.y = r.y; o.s = r.s;
-        }
-    }
-    wave_sync();                                             // the area is free for the next batch
-    PH(27);
-    return o;
-}
 
 // A joint was assigned (cifcaf.cpp:310): during the seed pipeline the grower publishes the occupancy box the
 // joint WILL occupy if the pose is accepted, so that the coordinator can stop handing out -- and growing --
@@ -1018,18 +790,12 @@ __device__ __forceinline__ SpecOut spec_scan_batch(ImageCtx& c, bool active, int
 // task slots of the growers (states, see the kernel)
 constexpr int kTaskIdle = 0, kTaskAssigned = 1, kTaskDone = 2, kTaskAccepted = 3;
 // 72 bytes = 18 banks between the slots: the coordinator's snapshot and publish_joint read one field of ALL slots with lane =
-// grower; at 64 bytes twelve lanes fell on two banks (6-way conflicts on every such read, -DOPA_TASK_SLOT_PAD=0 brings it back)
-#ifndef OPA_TASK_SLOT_PAD
-#define OPA_TASK_SLOT_PAD 2
-#endif
+// grower; at 64 bytes twelve lanes fell on two banks (6-way conflicts on every such read)
 struct __attribute__((aligned(8))) TaskSlot { int state, seed, cancel, epoch, npub, pk, f, pad0; double score; int t_emit, t_done, pad1, coll;
-#if OPA_TASK_SLOT_PAD
-    int pad_bank[OPA_TASK_SLOT_PAD];
-#endif
+    int pad_bank[2];
 };
 template <int WR> __device__ __forceinline__ void publish_joint(ImageCtx& c, const DevParams& p, int k, float x, float y, float s);
 template <int WR> __device__ __forceinline__ void pool_catch_up(ImageCtx& c, int e);
-template <int WR> __device__ __forceinline__ void spec_phase(ImageCtx& c, const DevParams& p, bool reverse_match_, double filter_sigmas);
 // cancel flag and refill epoch of this grower's task slot, one LDS read
 template <int WR>
 __device__ __forceinline__ bool poll_task(ImageCtx& c) {
@@ -1105,13 +871,14 @@ __device__ __forceinline__ int heap_pop(ImageCtx& c) {          // returns the t
 // in_frontier flags suffice (round 2 appended entries to a pool of 4A and searched the adjacency for the slot at
 // every evaluation).  A heap node carries the directed slot (start, end, list), the entry is found through its bone.
 
-// cifcaf.cpp:349-411 for the directed bone `info` (its first slot: the bone _connection_value's scan finds, :361-374) leaving a
-// joint with the values (sv, sx, sy, ss) -- the growing wave's own joint, or (scan helpers) a joint of another wave's growth
+// cifcaf.cpp:349-411 for the directed bone `info` (its first slot: the bone _connection_value's scan finds, :361-374) leaving
+// joint `start` of the growing pose
 template <bool LONG>
-__device__ __forceinline__ bool connection_value_at(ImageCtx& c, const DevParams& p, int info, double sv, double sx, double sy, double ss,
-                                                    bool reverse_match_, double filter_sigmas,
-                                                    double* nv, float* nx, float* ny, float* ns) {
+__device__ __forceinline__ bool connection_value(ImageCtx& c, const DevParams& p, int info,
+                                 bool reverse_match_, double filter_sigmas,
+                                 double* nv, float* nx, float* ny, float* ns) {
     const int start = info & 0xff, bone = (info >> 16) & 0xff, fwd = (info >> 24) & 1;
+    const double sv = c.jv[start], sx = (double)c.jx[start], sy = (double)c.jy[start], ss = (double)c.js[start];
     const ListView caf_f = list_view(c, bone, fwd ? 0 : 1);
     const BlendResult nj = blend<LONG>(c, caf_f, sx, sy, ss, filter_sigmas);
     if (!nj.ok) return false;
@@ -1125,70 +892,6 @@ __device__ __forceinline__ bool connection_value_at(ImageCtx& c, const DevParams
         if (fabs(sx - (double)rj.x) + fabs(sy - (double)rj.y) > ss) return false;   // :404
     }
     return true;
-}
-template <bool LONG>
-__device__ __forceinline__ bool connection_value(ImageCtx& c, const DevParams& p, int info,
-                                 bool reverse_match_, double filter_sigmas,
-                                 double* nv, float* nx, float* ny, float* ns) {
-    const int start = info & 0xff;
-    return connection_value_at<LONG>(c, p, info, c.jv[start], (double)c.jx[start], (double)c.jy[start], (double)c.js[start],
-                                     reverse_match_, filter_sigmas, nv, nx, ny, ns);
-}
-
-// ---- scan helpers, the growing wave's side
-// "joint b, reached through slot u (kSrcStart: filled from the start), has its values": the bones leaving it can be evaluated
-__device__ __forceinline__ void help_post(ImageCtx& c, int b, int u) {
-    if (lane_id() == 0) flag_store(&c.hq[c.hq_n & (kHelpRing - 1)], 1 | (b << 1) | (u << 10) | (c.h_epoch << 19));
-    c.hq_n++;
-}
-// a growth begins: new epoch (words of the last growth mean nothing any more), every bone free, the block open for helpers
-__device__ __forceinline__ void help_begin(ImageCtx& c) {
-    const int lane = lane_id();
-    c.h_epoch = (c.h_epoch + 1) & 0x3ff;
-    for (int a = lane; a < c.A; a += kWave) c.rq[a] = rq_word(kRqFree, 0, 0, c.h_epoch);
-    if (lane < kHelpRing) c.hq[lane] = 0;
-    unsigned long long filled0 = 0ull;
-    for (int k0 = 0; k0 < c.K; k0 += kWave) {
-        const int k = k0 + lane;
-        const bool f = k < c.K && c.jv[k < c.K ? k : 0] != 0.0;
-        if (k < c.K) c.jsrc[k] = f ? kSrcStart : -1;
-        if (k0 == 0) filled0 = __ballot(f);
-    }
-    if (lane == 0) { c.hctl[0] = c.h_epoch; c.hctl[2] = (int)(unsigned)filled0; c.hctl[3] = (int)(unsigned)(filled0 >> 32); }
-    c.hq_n = 0;
-    wave_sync();
-    if (lane == 0) flag_store(&c.hctl[1], 0);
-    for (int k0 = 0; k0 < c.K; k0 += kWave) {
-        unsigned long long filled = __ballot(k0 + lane < c.K && c.jsrc[k0 + lane < c.K ? k0 + lane : 0] == kSrcStart);
-        while (filled) { const int j = k0 + __builtin_ctzll(filled); filled &= filled - 1; help_post(c, j, kSrcStart); }
-    }
-}
-// the growth is over (finished or stopped): no new claims, and nobody writes into this block once this returns
-__device__ __forceinline__ void help_end(ImageCtx& c) {
-    const int lane = lane_id();
-    if (lane == 0) flag_store(&c.hctl[1], 1);
-    for (int spin = 0; spin < (1 << 20); spin++) {
-        bool taken = false;
-        for (int a = lane; a < c.A; a += kWave) taken |= (flag_load(&c.rq[a]) & 7) == kRqTaken;
-        if (__ballot(taken) == 0ull) break;
-        __builtin_amdgcn_s_sleep(1);
-    }
-}
-// The search pops bone `bn` (slot `slot`) for the first time; its start joint was assigned through slot `src`.
-// 1: a helper left the connection value in the entry array, 2: a helper found that the connection does not hold,
-// 0: the wave evaluates it itself (the word is claimed: no helper will write the entry)
-__device__ __forceinline__ int help_claim(ImageCtx& c, int bn, int slot, int src) {
-    for (int spin = 0; spin < (1 << 20); spin++) {
-        const int w = __builtin_amdgcn_readfirstlane(flag_load(&c.rq[bn]));
-        const int st = w & 7;
-        if (st == kRqTaken) { __builtin_amdgcn_s_sleep(1); continue; }        // a helper is at it (3-4 us at most)
-        if ((st == kRqOk || st == kRqRej) && w == rq_word(st, slot, src, c.h_epoch)) return st == kRqOk ? 1 : 2;
-        int old = w;
-        if (lane_id() == 0) old = atomicCAS(&c.rq[bn], w, rq_word(kRqMaster, slot, src & 0x1ff, c.h_epoch));
-        old = __builtin_amdgcn_readfirstlane(old);
-        if (old == w) return 0;                                              // (else a helper was faster: look again)
-    }
-    return 0;
 }
 
 // cifcaf.cpp:316-346: the bones leaving `start` whose other end is still empty and that are not in the frontier yet
@@ -1237,75 +940,38 @@ __device__ __forceinline__ void frontier_start(ImageCtx& c) {
 // cifcaf.cpp:265-313 -- one wavefront, no workgroup barriers
 template <bool LONG>
 __device__ __forceinline__ void grow(ImageCtx& c, const DevParams& p, bool reverse_match_, double filter_sigmas) {
-    if (kWalk && c.sp_j) {                                               // the bones of the pose, level by level, in batches (spec_phase)
-        spec_phase<kPoolSlotsLds>(c, p, reverse_match_, filter_sigmas);
-        if (c.aborted) return;
-        for (int k = lane_id(); k < c.K; k += kWave) c.sp_match[k] = (c.sp_j[k] & kSpKind) == kSpActual ? 1 : 0;
-        for (int a = lane_id(); a < c.A; a += kWave) c.sp_fromc[a] = 0;
-        wave_sync();
-    }
-    const bool help = kHelp && c.hq != nullptr;
-    if (help) help_begin(c);
     frontier_start(c);
     while (c.heap_n > 0) {
         if (poll_task<kPoolSlotsLds>(c)) { c.aborted = 1; break; }                      // the seed died while its pose grew
         const int slot = heap_pop(c);
         const int info = c.slot_info[slot];
-        const int start = info & 0xff, end = (info >> 8) & 0xff, bn = (info >> 16) & 0xff;
+        const int end = (info >> 8) & 0xff, bn = (info >> 16) & 0xff;
         if (c.jv[end] > 0.0) { PH(0); continue; }                        // :284
         double v = 0.0; float x = 0.f, y = 0.f, s = 0.f;
         const bool computed = (c.in_frontier[bn] & 2) != 0;
         if (computed) { v = c.e_v[bn]; x = c.e_x[bn]; y = c.e_y[bn]; s = c.e_s[bn]; }
         PH(0);
         if (!computed) {                                                 // :287: not computed yet
-            // a helper may have evaluated the connection already (from the very joint the search assigned: then it is
-            // what _connection_value returns); the level walk's memo likewise (walk builds)
-            int memo = 0;
-            const int got = help ? help_claim(c, bn, slot, c.jsrc[start]) : 0;
-            if (got == 2) { PH(7); continue; }                           // :290-296
-            if (kWalk && c.sp_j && c.sp_match[start]) {
-                const int w = c.sp_b[bn];
-                if (((w & 0xff) == kSbOk || (w & 0xff) == kSbRejected) && (w >> 8) == slot) memo = w & 0xff;
-            }
-            if (got == 1) {
-                v = c.e_v[bn]; x = c.e_x[bn]; y = c.e_y[bn]; s = c.e_s[bn];
-            } else if (memo) {
-                if (kWalk) c.n_hit++;
-                if (memo == kSbRejected) { PH(7); continue; }            // :290-296
-                v = c.sp_v[bn]; x = c.sp_x[bn]; y = c.sp_y[bn]; s = c.sp_s[bn];
-                c.sp_fromc[bn] = 1;
-            } else {
-                if (kWalk) c.n_miss++;
-                if (!connection_value<LONG>(c, p, info, reverse_match_, filter_sigmas, &v, &x, &y, &s)) {
-                    PH(7);
-                    continue;                                            // :290-296 (block_joints is a no-op)
-                }
-                if (kWalk && c.sp_j) c.sp_fromc[bn] = 0;
+            if (!connection_value<LONG>(c, p, info, reverse_match_, filter_sigmas, &v, &x, &y, &s)) {
+                PH(7);
+                continue;                                                // :290-296 (block_joints is a no-op)
             }
             PH(7);
             if (!p.greedy) {                                             // :298-303
-                if (got != 1) { c.e_v[bn] = v; c.e_x[bn] = x; c.e_y[bn] = y; c.e_s[bn] = s; }
+                c.e_v[bn] = v; c.e_x[bn] = x; c.e_y[bn] = y; c.e_s[bn] = s;
                 c.in_frontier[bn] = 3;
-                if (help) { wave_sync(); help_post(c, end, slot); }      // the joint this connection leads to: its bones can be evaluated
                 heap_push(c, (float)v, slot);
                 PH(8);
                 continue;
             }
         }
         c.jv[end] = v; c.jx[end] = x; c.jy[end] = y; c.js[end] = s;     // :310
-        if (help) c.jsrc[end] = slot;
         PH(9);
-        // assigned exactly the candidate the level walk gave this joint (same bone, entry from the memo): its box is
-        // published already, and the memo of its bones holds
-        bool matched = false;
-        if (kWalk && c.sp_j && c.sp_fromc[bn]) { const int w = c.sp_j[end]; matched = (w & kSpKind) == kSpCand && (w >> 8) == slot; }
-        if (kWalk && c.sp_j) c.sp_match[end] = matched ? 1 : 0;
-        if (!matched) publish_joint<kPoolSlotsLds>(c, p, end, x, y, s);
+        publish_joint<kPoolSlotsLds>(c, p, end, x, y, s);
         PH(10);
         frontier_add_from(c, end);
         PH(11);
     }
-    if (help) help_end(c);
 }
 
 // cifcaf.cpp:429-449
@@ -1490,21 +1156,11 @@ __device__ __forceinline__ void reg_store_pose(ImageCtx& c, const RegState& R) {
 template <bool LONG>
 __device__ __forceinline__ void grow_reg(ImageCtx& c, const DevParams& p, const RegSkeleton& sk, bool reverse_match_,
                                          double filter_sigmas, bool then_flood_fill) {
-    // joints assigned exactly their candidate's values / directed bones whose entry came from the memo (one bit each)
-    unsigned long long sp_match = 0ull, sp_fromc = 0ull;
-    if (kWalk && c.sp_j) {                                                   // the bones of the pose, level by level, in batches (spec_phase)
-        spec_phase<kPoolSlots>(c, p, reverse_match_, filter_sigmas);
-        if (c.aborted) return;
-        sp_match = __ballot(lane_id() < c.K && (c.sp_j[lane_id() < c.K ? lane_id() : 0] & kSpKind) == kSpActual);
-    }
-    const bool help = kHelp && c.hq != nullptr;
-    if (help) help_begin(c);
-    unsigned long long amask = help ? ((unsigned long long)(unsigned)c.hctl[3] << 32) | (unsigned)c.hctl[2] : 0ull;   // joints assigned so far (for the helpers)
     RegState R;
     reg_load_pose(c, R);
     reg_frontier_start(R, sk, c.K);
     while (R.heap_n > 0) {
-        if (poll_task<kPoolSlots>(c)) { c.aborted = 1; if (help) help_end(c); return; }   // the seed died while its pose grew
+        if (poll_task<kPoolSlots>(c)) { c.aborted = 1; return; }            // the seed died while its pose grew
         const int slot = reg_heap_pop(R);
         const int info = rlane(sk.slot_info, slot);
         const int start = info & 0xff, end = (info >> 8) & 0xff;
@@ -1513,40 +1169,14 @@ __device__ __forceinline__ void grow_reg(ImageCtx& c, const DevParams& p, const 
         float x, y, s;
         PH(0);
         if (v == 0.0) {                                                      // :287: not computed yet
-            // a helper may have evaluated the connection already (from the very joint the search assigned: then it is
-            // what _connection_value returns); the level walk's memo likewise (walk builds)
-            int memo = 0;
-            const int bn = (info >> 16) & 0xff;
-            const int got = help ? help_claim(c, bn, slot, __builtin_amdgcn_readfirstlane(c.jsrc[start])) : 0;
-            if (got == 2) { PH(7); continue; }                               // :290-296
-            if (kWalk && c.sp_j && ((sp_match >> start) & 1ull)) {
-                const int w = __builtin_amdgcn_readfirstlane(c.sp_b[bn]);
-                if (((w & 0xff) == kSbOk || (w & 0xff) == kSbRejected) && (w >> 8) == slot) memo = w & 0xff;
-            }
-            if (got == 1) {
-                v = uniform_f64(c.e_v[bn]); x = uniform_f32(c.e_x[bn]); y = uniform_f32(c.e_y[bn]); s = uniform_f32(c.e_s[bn]);
-            } else if (memo) {
-                if (kWalk) c.n_hit++;
-                if (memo == kSbRejected) { PH(7); continue; }                // :290-296
-                v = uniform_f64(c.sp_v[bn]); x = uniform_f32(c.sp_x[bn]); y = uniform_f32(c.sp_y[bn]); s = uniform_f32(c.sp_s[bn]);
-                if (kWalk) sp_fromc |= 1ull << slot;
-            } else {
-                if (kWalk) c.n_miss++;
-                if (!reg_connection_value<LONG>(c, p, R, start, info, reverse_match_, filter_sigmas, &v, &x, &y, &s)) {
-                    PH(7);
-                    continue;                                                // :290-296 (block_joints is a no-op)
-                }
-                if (kWalk) sp_fromc &= ~(1ull << slot);
+            if (!reg_connection_value<LONG>(c, p, R, start, info, reverse_match_, filter_sigmas, &v, &x, &y, &s)) {
+                PH(7);
+                continue;                                                    // :290-296 (block_joints is a no-op)
             }
             PH(7);
             if (!p.greedy) {                                                 // :298-303
                 wlane(R.ev_lo, __double2loint(v), slot); wlane(R.ev_hi, __double2hiint(v), slot);
                 wlanef(R.ex, x, slot); wlanef(R.ey, y, slot); wlanef(R.es, s, slot);
-                if (help) {                                                  // the joint this connection leads to: its bones can be evaluated
-                    if (got != 1 && lane_id() == 0) { c.e_v[bn] = v; c.e_x[bn] = x; c.e_y[bn] = y; c.e_s[bn] = s; }
-                    wave_sync();
-                    help_post(c, end, slot);
-                }
                 reg_heap_push(R, (float)v, slot);
                 PH(8);
                 continue;
@@ -1555,25 +1185,12 @@ __device__ __forceinline__ void grow_reg(ImageCtx& c, const DevParams& p, const 
             x = rlanef(R.ex, slot); y = rlanef(R.ey, slot); s = rlanef(R.es, slot);
         }
         reg_set_joint(R, end, v, x, y, s);                                   // :310
-        if (help) {
-            amask |= 1ull << end;
-            if (lane_id() == 0) { c.jsrc[end] = slot; c.hctl[2] = (int)(unsigned)amask; c.hctl[3] = (int)(unsigned)(amask >> 32); }
-        }
         PH(9);
-        // assigned exactly the candidate the level walk gave this joint (same bone, entry from the memo): its box is
-        // published already, and the memo of its bones holds
-        bool matched = false;
-        if (kWalk && c.sp_j && ((sp_fromc >> slot) & 1ull)) {
-            const int w = __builtin_amdgcn_readfirstlane(c.sp_j[end]);
-            matched = (w & kSpKind) == kSpCand && (w >> 8) == slot;
-        }
-        if (kWalk && matched) sp_match |= 1ull << end;
-        else publish_joint<kPoolSlots>(c, p, end, x, y, s);
+        publish_joint<kPoolSlots>(c, p, end, x, y, s);
         PH(10);
         reg_frontier_add_from(R, sk, end);
         PH(11);
     }
-    if (help) help_end(c);
     if (then_flood_fill) {                                                   // cifcaf.cpp:429-449
         reg_frontier_start(R, sk, c.K);
         while (R.heap_n > 0) {
@@ -1641,14 +1258,8 @@ __device__ __forceinline__ bool box_contains(const OccBox& b, int xi, int yi) {
 
 constexpr int kSeedStage = 1024;          // seeds (field, cell) the coordinator keeps staged in LDS beyond its scan position (ring)
 constexpr int kDedupBits = 10;            // buckets (log2) of the coordinator's first-seed-of-a-cell table
-#ifndef OPA_COMMIT_RUN
-#define OPA_COMMIT_RUN 4
-#endif
-#ifndef OPA_REFILL_NUM
-#define OPA_REFILL_NUM 2
-#endif
-constexpr int kRefillNum = OPA_REFILL_NUM, kRefillDen = 4;   // the pool is refilled when fewer than kRefillNum / kRefillDen of its slots are live
-constexpr int kCommitRun = OPA_COMMIT_RUN;             // commits per round of the coordinator before it looks at the idle growers again
+constexpr int kRefillNum = 2, kRefillDen = 4;   // the pool is refilled when fewer than kRefillNum / kRefillDen of its slots are live
+constexpr int kCommitRun = 4;             // commits per round of the coordinator before it looks at the idle growers again
 constexpr int kPoolIdxMask = 0xFFFFFF;    // seed index bits of a slot word (all ones: empty slot); field above
 constexpr int kPreDedupMin = 1024;        // images with fewer seeds go through the pool refill as they are (two refill rounds)
 
@@ -1768,16 +1379,8 @@ struct PredictArgs {
     int E, K, F, occ_w, occ_h, my_idx;
     OccBox* jbox; const int* pool_if; const int* pool_pack; unsigned* shadow; int* n_predicted;
 };
-#ifndef OPA_PREDICT_INLINE
-#define OPA_PREDICT_INLINE 1
-#endif
-#if OPA_PREDICT_INLINE
-#define OPA_PREDICT_ATTR __forceinline__
-#else
-#define OPA_PREDICT_ATTR __attribute__((noinline))
-#endif
 template <int WR>
-__device__ OPA_PREDICT_ATTR void predict_pose_call(PredictArgs q, const DevParams* pp, int info, int first, int seed_joint,
+__device__ __forceinline__ void predict_pose_call(PredictArgs q, const DevParams* pp, int info, int first, int seed_joint,
                                                    float sx, float sy, float ss) {
     const DevParams& p = *pp;
     const int lane = lane_id();
@@ -1908,211 +1511,6 @@ __device__ __forceinline__ void predict_pose_lds(ImageCtx& c, const DevParams& p
     wave_sync();                                     // (the scan area is the search's from here on)
 }
 
-// ------------------------------------------------ speculative batched evaluation of a growth (spec_phase)
-// The reference evaluates one bone per pop of its frontier (cifcaf.cpp:287-303), a chain of ~2 list scans per bone -- but
-// _connection_value (:349-411) of a bone depends on its START JOINT alone, and a joint, once assigned, never changes.  So
-// before the search itself runs, the wave walks the skeleton level by level from the joints the pose starts with: all
-// bones leaving the joints of a level are evaluated in ONE batch of forward scans and ONE batch of reverse scans
-// (spec_scan_batch), each result is remembered per bone, and the end joint of every connection that holds becomes a
-// CANDIDATE -- the start joint of the next level's bones.  The search (grow / grow_reg) then runs the reference's heap
-// loop unchanged and takes a bone's connection value from the memo instead of scanning -- but only when the start joint
-// was assigned exactly the candidate the memo was computed from (it was reached through the same bone, whose own entry
-// came from the memo): then the value IS what _connection_value returns, bit for bit.  Anything else -- a joint reached
-// through another bone first, a batch that did not fit -- is evaluated on demand as before.  The sequence of heap
-// operations, and with it every tie, is the reference's.
-// The candidates are also this growth's PREDICTIONS: their occupancy boxes are published level by level (a pose of 17
-// joints is known after ~8 levels, long before the heap loop has assigned it), which is what keeps the other growers off
-// the same person.  Advisory as before: the commit re-tests every seed against the final boxes.
-
-// boxes of the joints that became candidates in this round: published like the boxes of assigned joints (publish_joint)
-template <int WR>
-__device__ __forceinline__ void spec_publish(ImageCtx& c, const DevParams& p) {
-    const int lane = lane_id();
-    bool any_new = false;
-    for (int k0 = 0; k0 < c.F; k0 += kWave) {
-        const int k = k0 + lane;
-        const int w = k < c.F ? c.sp_j[k] : 0;
-        if (w & kSpNext) {
-            const int pb = (c.slot_info[w >> 8] >> 16) & 0xff;
-            c.jbox[k] = occ_box(c, p, (double)c.sp_x[pb], (double)c.sp_y[pb], (double)c.sp_s[pb]);
-            any_new = true;
-        }
-    }
-    if (__ballot(any_new) == 0ull) return;
-    wave_sync();
-    // every pooled seed that comes later in seed order and lies in one of this growth's boxes is shadowed (re-testing the
-    // boxes of earlier rounds sets the same bits again)
-    unsigned bits = 0u;
-#pragma unroll
-    for (int r0 = 0; r0 < WR; r0 += 4) {
-        int sif[4], spk[4];
-#pragma unroll
-        for (int r = 0; r < 4; r++) { sif[r] = c.pool_if[(r0 + r) * kWave + lane]; spk[r] = c.pool_pack[(r0 + r) * kWave + lane]; }
-#pragma unroll
-        for (int r = 0; r < 4; r++) asm volatile("" : "+v"(sif[r]), "+v"(spk[r]) :: "memory");
-        OccBox bx[4];
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int f = (int)((unsigned)sif[r] >> 24);
-            bx[r] = c.jbox[f < c.F ? f : 0];
-        }
-#pragma unroll
-        for (int r = 0; r < 4; r++) asm volatile("" : "+v"(bx[r].minx), "+v"(bx[r].miny), "+v"(bx[r].maxx), "+v"(bx[r].maxy) :: "memory");
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int f = (int)((unsigned)sif[r] >> 24), idx = sif[r] & kPoolIdxMask;
-            if (idx != kPoolIdxMask && idx > c.my_idx && f < c.F &&
-                box_contains(bx[r], spk[r] & 0xfff, (spk[r] >> 12) & 0xfff)) bits |= 1u << (r0 + r);
-        }
-    }
-    if (bits) atomicOr(&c.shadow_mine[lane], bits);
-    ++c.n_pub;
-    if (lane == 0) *c.pub = c.n_pub;
-    // a new candidate inside the box an EARLIER live growth has published for the same joint: most likely the same person
-    // (publish_joint's test: lane = grower, the new joints one after the other)
-    const int cfg = c.head_g[2];
-    if ((cfg >> 28) & 1) {
-        const TaskSlot* tasks = reinterpret_cast<const TaskSlot*>(opa_dyn_lds);
-        const unsigned char* blocks = opa_dyn_lds + c.head_g[1];
-        const int n_growers = (cfg >> 20) & 0xff, block_bytes = cfg & 0xfffff;
-        bool earlier = false; int sd = 0;
-        if (lane >= 1 && lane <= n_growers && lane != c.wave) {
-            const int st = flag_peek(&tasks[lane].state), cn = flag_peek(&tasks[lane].cancel);
-            sd = tasks[lane].seed;
-            earlier = (st == kTaskAssigned || st == kTaskDone) && !cn && sd < c.my_idx;
-        }
-        if (__ballot(earlier) != 0ull) {
-            unsigned key = 0xFFFFFFFFu;
-            const OccBox* theirs = reinterpret_cast<const OccBox*>(blocks + (size_t)(earlier ? lane - 1 : 0) * block_bytes);
-            for (int k0 = 0; k0 < c.F; k0 += kWave) {
-                const int kk = k0 + lane;
-                unsigned long long nm = __ballot(kk < c.F && (c.sp_j[kk < c.F ? kk : 0] & kSpNext));
-                while (nm) {
-                    const int k = k0 + __builtin_ctzll(nm);
-                    nm &= nm - 1;
-                    const int pb = (c.slot_info[c.sp_j[k] >> 8] >> 16) & 0xff;
-                    int cx, cy;
-                    occ_xy(c, p, (double)c.sp_x[pb], (double)c.sp_y[pb], &cx, &cy);
-                    const OccBox ob = theirs[k];
-                    if (earlier && box_contains(ob, cx, cy)) key = min(key, ((unsigned)sd << 6) | (unsigned)lane);
-                }
-            }
-            if (__ballot(key != 0xFFFFFFFFu) != 0ull) {
-                const unsigned first = ~wave_max_u32(~key);      // the earliest of them
-                if (lane == 0) flag_store(const_cast<int*>(&tasks[c.wave].coll), (int)(first & 63u));
-            }
-        }
-    }
-}
-
-// One round = ONE batch: the forward scans of the bones leaving the joints that became candidates in the round before
-// TOGETHER with the reverse scans (cifcaf.cpp:397-409) of that round's connections -- a candidate's values are known
-// after its forward scan, the reverse scan only confirms or rejects the connection.  A rejected connection leaves its
-// candidate (and what was computed from it) in the memo, where nothing will ever match it: the search never assigns a
-// joint through a rejected bone.
-template <int WR>
-__device__ __forceinline__ void spec_phase(ImageCtx& c, const DevParams& p, bool reverse_match_, double filter_sigmas) {
-    const int lane = lane_id();
-    const int K = c.K, A = c.A, E = 2 * A;
-    int* joblist = reinterpret_cast<int*>(c.tgt);            // (the scan area is free between two batches)
-    for (int k = lane; k < K; k += kWave) c.sp_j[k] = c.jv[k] != 0.0 ? (kSpActual | kSpOpen) : 0;
-    for (int a = lane; a < A; a += kWave) c.sp_b[a] = 0;
-    wave_sync();
-    bool pending = false;                                    // connections whose reverse scan is outstanding (uniform)
-    for (;;) {
-        int nj = 0;
-        // ---- reverse jobs: the connections of the round before
-        if (pending)
-            for (int a0 = 0; a0 < A; a0 += kWave) {
-                const int bn = a0 + lane;
-                const int w = bn < A ? c.sp_b[bn] : 0;
-                const bool cand = (w & 0xff) == kSbPending;
-                const unsigned long long m = __ballot(cand);
-                const int slot = nj + prefix_count(m);
-                if (cand && slot < kWave) joblist[slot] = (w >> 8) | (1 << 16);
-                nj += __popcll(m);
-                if (nj >= kWave) break;
-            }
-        const bool rev_left = nj > kWave;                    // (more than a batch holds: the rest in the next round)
-        if (nj > kWave) nj = kWave;
-        // ---- forward jobs: the first slot of every (start, end) pair whose start joint is open, whose end is not filled
-        //      from the start (cifcaf.cpp:327,336) and whose bone has not been evaluated in either direction; of a bone
-        //      between two open joints the direction from the lower joint
-        bool fwd_left = nj >= kWave;                         // (the batch is full of reverse jobs: the open joints wait)
-        for (int t0 = 0; t0 < E && nj < kWave; t0 += kWave) {
-            const int t = t0 + lane;
-            bool cand = false;
-            if (t < E) {
-                const int info = c.slot_info[t];
-                const int a = info & 0xff, b = (info >> 8) & 0xff, bn = (info >> 16) & 0xff;
-                const int wa = c.sp_j[a], wb = c.sp_j[b];
-                cand = c.adj_first[t] == t && (wa & kSpOpen) && (wb & kSpKind) != kSpActual && (c.sp_b[bn] & 0xff) == 0 &&
-                       !((wb & kSpOpen) && b < a);
-            }
-            const unsigned long long m = __ballot(cand);
-            const int slot = nj + prefix_count(m);
-            if (cand && slot < kWave) joblist[slot] = t;
-            nj += __popcll(m);
-            if (nj > kWave) { fwd_left = true; nj = kWave; }
-            else if (nj == kWave && t0 + kWave < E) fwd_left = true;       // (possibly: look again next round)
-        }
-        if (nj == 0) break;
-        wave_sync();
-        PH(20);
-        const bool job = lane < nj;
-        const int jw = job ? joblist[lane] : 0;
-        wave_sync();
-        const int t = jw & 0xffff;
-        const bool is_rev = (jw >> 16) != 0;
-        const int info = c.slot_info[t];
-        const int a = info & 0xff, b = (info >> 8) & 0xff, bn = (info >> 16) & 0xff, fwd = (info >> 24) & 1;
-        // the start joint: filled from the start, or the candidate its bone gave it
-        const int wa = c.sp_j[a];
-        double sv; float sxf, syf, ssf;
-        if ((wa & kSpKind) == kSpActual) { sv = c.jv[a]; sxf = c.jx[a]; syf = c.jy[a]; ssf = c.js[a]; }
-        else { const int pb = (c.slot_info[wa >> 8] >> 16) & 0xff; sv = c.sp_v[pb]; sxf = c.sp_x[pb]; syf = c.sp_y[pb]; ssf = c.sp_s[pb]; }
-        const double sx = (double)sxf, sy = (double)syf, ss = (double)ssf;
-        // forward: the start joint against the bone's list in its direction; reverse: the new joint against the other list
-        double qx = sx, qy = sy, qs = ss;
-        if (is_rev) { qx = (double)c.sp_x[bn]; qy = (double)c.sp_y[bn]; qs = (double)c.sp_s[bn]; }
-        const int li = bn * 2 + ((fwd != 0) != is_rev ? 0 : 1);
-        PH(21);
-        c.n_blend += nj;
-        const SpecOut o = spec_scan_batch(c, job, li, qx, qy, qs, filter_sigmas);
-        int res = 0;
-        if (job) {
-            if (o.ok < 0) res = kSbUnknown;
-            else if (o.ok == 0) res = kSbRejected;                                          // :384, :400-403
-            else if (is_rev) res = fabs(sx - (double)o.x) + fabs(sy - (double)o.y) > ss ? kSbRejected : kSbOk;   // :404
-            else {
-                const double nv = sqrt(o.v * sv);                                           // :386
-                if (nv < p.keypoint_threshold || nv < sv * p.keypoint_threshold_rel) res = kSbRejected;          // :387-390
-                else {
-                    res = p.reverse_match && reverse_match_ && a < c.F ? kSbPending : kSbOk;                     // :397
-                    c.sp_v[bn] = nv; c.sp_x[bn] = o.x; c.sp_y[bn] = o.y; c.sp_s[bn] = o.s;
-                }
-            }
-            c.sp_b[bn] = res | (t << 8);
-        }
-        pending = __ballot(job && res == kSbPending) != 0ull || rev_left;
-        wave_sync();
-        // the level is done (unless jobs were left over): the joints that became candidates in the round before are closed,
-        // the end joint of every new connection becomes a candidate -- unless it is one already (first come) -- and open
-        if (!fwd_left)
-            for (int k = lane; k < K; k += kWave) { const int w = c.sp_j[k]; if (w & kSpOpen) c.sp_j[k] = w & ~kSpOpen; }
-        wave_sync();
-        if (job && !is_rev && (res == kSbOk || res == kSbPending)) atomicCAS(&c.sp_j[b], 0, kSpCand | kSpNext | kSpOpen | (t << 8));
-        wave_sync();
-        PH(28);
-        if (c.pub) spec_publish<WR>(c, p);
-        for (int k = lane; k < K; k += kWave) { const int w = c.sp_j[k]; if (w & kSpNext) c.sp_j[k] = w & ~kSpNext; }
-        wave_sync();
-        PH(29);
-        if (poll_task<WR>(c)) { c.aborted = 1; return; }
-        PH(30);
-    }
-}
-
 // Occupancy::get on the bitmap (one bit per cell, rows of occ_wpr 32-bit words)
 __device__ __forceinline__ bool occ_test(const ImageCtx& c, int f, int xi, int yi) {
     const unsigned w = c.occ[((size_t)f * c.occ_h + yi) * c.occ_wpr + (xi >> 5)];
@@ -2124,32 +1522,17 @@ __device__ __forceinline__ bool occ_test(const ImageCtx& c, int f, int xi, int y
 // area (`tgt_floats`: kBlendLdsFloats, or kSmallTgtFloats when that buys more growers).  16-byte sized.
 constexpr int kSmallTgtChunks = 2;
 constexpr int kSmallTgtFloats = 3 * kSmallTgtChunks * kWave + 4 * kWave;
-constexpr int kSpecTgtFloats = kSpecItems + 2 * kWave + kSpecEntryWords * 160;   // the small scan area when the level walk runs: batches of up to 160 passing entries
 __host__ __device__ inline size_t assoc_pose_bytes(int K) {
     return (16 * (size_t)K + sizeof(double) * K + sizeof(float) * 3 * K + 15) / 16 * 16;
 }
-// the level walk's memo (spec_phase): a word per joint, a word + a connection value per bone; the LDS variant also keeps its two flag sets here
-__host__ __device__ inline size_t assoc_spec_bytes(int K, int A, bool reg) {
-    return (sizeof(double) * A + sizeof(int) * (K + A) + sizeof(float) * 3 * A + (reg ? 0 : K + A) + 15) / 16 * 16;
-}
-// the scan helpers' words (requests, a word per bone, the slot each joint was assigned through, control words); the
-// register variant also keeps an LDS copy of its computed entries here (what the helpers read and write)
-__host__ __device__ inline size_t assoc_help_bytes(int K, int A, bool reg) {
-    return (sizeof(int) * (kHelpRing + A + K + 4) + (reg ? (sizeof(double) + 3 * sizeof(float)) * A + 8 : 0) + 15) / 16 * 16;
-}
-__host__ __device__ inline size_t assoc_private_bytes(int K, int A, bool reg, int tgt_floats, bool spec = false, bool help = false) {
+__host__ __device__ inline size_t assoc_private_bytes(int K, int A, bool reg, int tgt_floats) {
     size_t b = assoc_pose_bytes(K);
     if (!reg) b += sizeof(double) * A + sizeof(unsigned long long) * A + sizeof(float) * 3 * A + (A + 15) / 16 * 16 + (A & 1 ? 4 : 0);
     b = (b + 15) / 16 * 16;
-    if (spec) b += assoc_spec_bytes(K, A, reg);
-    if (help) b += assoc_help_bytes(K, A, reg);
-#ifdef OPA_ASSOC_PRIVATE_PAD     // experiment: other distances between the growers' blocks (LDS bank conflicts)
-    b += OPA_ASSOC_PRIVATE_PAD;
-#endif
     return b + sizeof(float) * tgt_floats;
 }
 template <bool REG>
-__device__ __forceinline__ void carve_private(ImageCtx& c, unsigned char* sp, int tgt_floats, bool spec = false, bool help = false) {
+__device__ __forceinline__ void carve_private(ImageCtx& c, unsigned char* sp, int tgt_floats) {
     const int K = c.K, A = c.A;
     unsigned char* base = sp;
     c.jbox = (OccBox*)sp; sp += sizeof(OccBox) * K;
@@ -2168,98 +1551,9 @@ __device__ __forceinline__ void carve_private(ImageCtx& c, unsigned char* sp, in
         c.in_frontier = sp; sp += (A + 15) / 16 * 16 + (A & 1 ? 4 : 0);
         sp = base + (((size_t)(sp - base) + 15) & ~(size_t)15);
     }
-    c.sp_j = c.sp_b = nullptr; c.sp_v = nullptr; c.sp_x = c.sp_y = c.sp_s = nullptr; c.sp_match = c.sp_fromc = nullptr;
-    c.sp_pcap = 0; c.n_hit = c.n_miss = 0;
-    if (kWalk && spec) {
-        unsigned char* s0 = sp;
-        c.sp_v = (double*)sp; sp += sizeof(double) * A;
-        c.sp_j = (int*)sp; sp += sizeof(int) * K;
-        c.sp_b = (int*)sp; sp += sizeof(int) * A;
-        c.sp_x = (float*)sp; sp += sizeof(float) * A;
-        c.sp_y = (float*)sp; sp += sizeof(float) * A;
-        c.sp_s = (float*)sp; sp += sizeof(float) * A;
-        if constexpr (!REG) { c.sp_match = sp; sp += K; c.sp_fromc = sp; sp += A; }
-        sp = s0 + assoc_spec_bytes(K, A, REG);
-        c.sp_pcap = spec_pcap(tgt_floats);
-    }
-    c.hq = c.rq = c.jsrc = c.hctl = nullptr;
-    if (kHelp && help) {
-        unsigned char* s0 = sp;
-        if constexpr (REG) {                                 // (the LDS variant's entry arrays are the ones above)
-            c.e_v = (double*)sp; sp += sizeof(double) * A + (A & 1 ? 8 : 0);
-            c.e_x = (float*)sp; sp += sizeof(float) * A;
-            c.e_y = (float*)sp; sp += sizeof(float) * A;
-            c.e_s = (float*)sp; sp += sizeof(float) * A;
-        }
-        c.hq = (int*)sp; sp += sizeof(int) * kHelpRing;
-        c.rq = (int*)sp; sp += sizeof(int) * A;
-        c.jsrc = (int*)sp; sp += sizeof(int) * K;
-        c.hctl = (int*)sp; sp += sizeof(int) * 4;
-        sp = s0 + assoc_help_bytes(K, A, REG);
-    }
     c.tgt = (float*)sp;
     c.max_r = tgt_floats >= kBlendLdsFloats ? kBlendChunks : kSmallTgtChunks;
     c.heap_n = 0;
-}
-
-// ---- scan helpers, the helping wave's side: ONE connection of the growth in block `mblock` (the one that holds the head
-// seed), if any is waiting.  The bones leaving a posted joint are claimed one at a time (compare-and-swap on the bone's
-// word), evaluated with this wave's own scan area, and left in the master's entry array.
-template <bool REG>
-__device__ __forceinline__ void help_once(ImageCtx& c, const DevParams& p, unsigned char* mblock, int tgt_floats, bool spec) {
-    ImageCtx m;
-    m.K = c.K; m.A = c.A;
-    carve_private<REG>(m, mblock, tgt_floats, spec, true);
-    const int lane = lane_id();
-    if (flag_load(&m.hctl[1])) return;                       // not growing
-    const int ep = flag_load(&m.hctl[0]);
-    const int free_w = rq_word(kRqFree, 0, 0, ep);
-    const int hw = lane < kHelpRing ? flag_peek(&m.hq[lane]) : 0;
-    unsigned long long vm = __ballot(hw != 0 && ((hw >> 19) & 0x3ff) == ep);
-    while (vm) {
-        const int i = __builtin_ctzll(vm); vm &= vm - 1;
-        const int w = rlane_i(hw, i);
-        const int b = (w >> 1) & 0x1ff, u = (w >> 10) & 0x1ff;
-        const int parent = u == kSrcStart ? -1 : (c.slot_info[u] & 0xff);
-        const int t1 = c.adj_off[b + 1];
-        for (int t0 = c.adj_off[b]; t0 < t1; t0 += kWave) {
-            const int t = t0 + lane;
-            bool cand = false; int bn = 0;
-            if (t < t1) {
-                const int info = c.slot_info[t];
-                const int other = (info >> 8) & 0xff; bn = (info >> 16) & 0xff;
-                bool assigned;
-                if constexpr (REG) assigned = (((((unsigned long long)(unsigned)m.hctl[3]) << 32) | (unsigned)m.hctl[2]) >> other) & 1ull;
-                else assigned = m.jv[other] > 0.0;
-                cand = c.adj_first[t] == t && other != parent && !assigned && flag_peek(&m.rq[bn]) == free_w;
-            }
-            unsigned long long cm = __ballot(cand);
-            while (cm) {
-                const int l = __builtin_ctzll(cm); cm &= cm - 1;
-                const int ts = t0 + l, bs = rlane_i(bn, l);
-                const int mine = rq_word(kRqTaken, ts, u, ep);
-                int old = 0;
-                if (lane == 0) old = atomicCAS(&m.rq[bs], free_w, mine);
-                if (__builtin_amdgcn_readfirstlane(old) != free_w) continue;   // somebody else has it
-                // the block closed, or went on to its next growth, in between: hand the bone back untouched
-                if (flag_load(&m.hctl[1]) || flag_load(&m.hctl[0]) != ep) {
-                    if (lane == 0) atomicCAS(&m.rq[bs], mine, free_w);
-                    return;
-                }
-                double sv; float sx, sy, ss;
-                if (u == kSrcStart) { sv = m.jv[b]; sx = m.jx[b]; sy = m.jy[b]; ss = m.js[b]; }
-                else { const int bu = (c.slot_info[u] >> 16) & 0xff; sv = m.e_v[bu]; sx = m.e_x[bu]; sy = m.e_y[bu]; ss = m.e_s[bu]; }
-                double nv = 0.0; float nx = 0.f, ny = 0.f, ns = 0.f;
-                const bool ok = connection_value_at<false>(c, p, c.slot_info[ts], sv, (double)sx, (double)sy, (double)ss, true, 1.0,
-                                                           &nv, &nx, &ny, &ns);
-                if (ok && lane == 0) { m.e_v[bs] = nv; m.e_x[bs] = nx; m.e_y[bs] = ny; m.e_s[bs] = ns; }
-                wave_sync();
-                if (lane == 0) flag_store(&m.rq[bs], rq_word(ok ? kRqOk : kRqRej, ts, u, ep));
-                return;                                      // one connection at a time: back to the own task slot
-            }
-        }
-        if (lane == 0) atomicCAS(&m.hq[i], w, 0);            // nothing left of this request
-    }
 }
 
 // LDS scratch of one wave during keypoint NMS (aliases the growth state): a box and a cell per pose
@@ -2515,12 +1809,11 @@ __device__ __forceinline__ void assoc_image(const AssocArgs& a, const DevSkeleto
     int* l_first = (int*)sp; sp += sizeof(int) * E;
     int* sh_ctl = (int*)sp; sp += sizeof(int) * 16;  // 0 exit flag, 1 n_kept, 2 n_dropped, 3 grower ticks, 4 list scans, 5 watchdog,
                                                      // 6-7 scan timing (diagnostic builds), 8 refill epoch, 9 grower of the head seed,
-                                                     // 10-11 see below, 12 the head seed's index (self-serve hand-out)
+                                                     // 10-11 see below
     int* sh_stats = (int*)sp; sp += sizeof(int) * kAssocStats;
     int* pool_if = (int*)sp; sp += sizeof(int) * WR * kWave;        // the coordinator's seed pool, mirrored for the growers
     int* pool_pack = (int*)sp; sp += sizeof(int) * WR * kWave;
     int* pool_ep = (int*)sp; sp += sizeof(int) * WR * kWave;
-    int* pool_own = (int*)sp; if (kSelfServe) sp += sizeof(int) * WR * kWave;   // 0, or the grower that claimed the slot's seed (self-serve variant only)
     unsigned* shadow_by = (unsigned*)sp; sp += sizeof(unsigned) * NW * kWave; // [grower][lane]: pool slots in its published boxes
     int* stage_f = (int*)sp; sp += sizeof(int) * kSeedStage;                // the next seeds' field and cell, staged ahead of the pool refill
     int* stage_pk = (int*)sp; sp += sizeof(int) * kSeedStage;
@@ -2529,11 +1822,8 @@ __device__ __forceinline__ void assoc_image(const AssocArgs& a, const DevSkeleto
     if (use_bbox) sp += sizeof(float4) * E * kListBboxChunks;
     unsigned char* work_base = sp;                   // growth phase: private blocks; NMS phase: its arrays and scratch
     unsigned char* private_base = sp;
-    const bool help_on = kHelp && a.help != 0;
-    const size_t private_bytes = assoc_private_bytes(K, A, REG, tgt_floats, a.spec != 0, help_on);
-    carve_private<REG>(c, private_base + (size_t)(wave >= 1 && wave <= S ? wave - 1 : 0) * private_bytes, tgt_floats, a.spec != 0, help_on);   // other waves never touch theirs
-    c.hq_n = 0; c.h_epoch = 0;
-    if (help_on && wave >= 1 && wave <= S && lane == 0) { c.hctl[0] = 0; c.hctl[1] = 1; }     // (no growth yet: closed to helpers)
+    const size_t private_bytes = a.private_bytes;    // (assoc_private_bytes(K, A, REG, tgt_floats), sized by the launch)
+    carve_private<REG>(c, private_base + (size_t)(wave >= 1 && wave <= S ? wave - 1 : 0) * private_bytes, tgt_floats);   // other waves never touch theirs
 
     // the image's occupancy bitmap starts empty (cifcaf.cpp:173); 16-byte stores, region is 256-B aligned
     {
@@ -2564,7 +1854,7 @@ __device__ __forceinline__ void assoc_image(const AssocArgs& a, const DevSkeleto
         t.t_emit = t.t_done = t.pad0 = t.pad1 = t.coll = 0;
         task[tid] = t;
     }
-    if (tid < 16) sh_ctl[tid] = tid == 9 || tid == 12 ? -1 : 0;   // (9: the grower holding the head seed, 12: the head seed)
+    if (tid < 16) sh_ctl[tid] = tid == 9 ? -1 : 0;              // (9: the grower holding the head seed)
     if (tid == 10) sh_ctl[10] = (int)(private_base - smem);        // 10, 11: for publish_joint's look at the other growers' boxes
     if (tid == 11) sh_ctl[11] = (int)private_bytes | (S << 20) | ((a.collide ? 1 : 0) << 28);
     if (tid < kAssocStats) sh_stats[tid] = 0;
@@ -2572,11 +1862,10 @@ __device__ __forceinline__ void assoc_image(const AssocArgs& a, const DevSkeleto
     if (tid < kPhases) { g_ph[tid] = 0; g_phn[tid] = 0; }
     if (tid < 16) g_ph_last[tid] = clock64();
 #endif
-    for (int k = tid; k < WR * kWave; k += kThreads) { pool_if[k] = kPoolIdxMask; pool_pack[k] = 0; pool_ep[k] = 0; if (kSelfServe) pool_own[k] = 0; }
+    for (int k = tid; k < WR * kWave; k += kThreads) { pool_if[k] = kPoolIdxMask; pool_pack[k] = 0; pool_ep[k] = 0; }
     for (int k = tid; k < NW * kWave; k += kThreads) shadow_by[k] = 0u;
     for (int k = tid; k < (1 << kDedupBits); k += kThreads) dedup[k] = ~0ull;
     const bool dedup_on = a.dedup != 0;
-    constexpr bool self = kSelfServe;                // idle growers take their next candidate themselves (see kPoolSlots' neighbour above)
     c.adj_off = l_off; c.slot_info = l_info; c.adj_first = l_first;
     c.n_predicted = &sh_ctl[6];                      // (statistics slot 21: joint boxes published from predictions)
 
@@ -2798,20 +2087,7 @@ __device__ __forceinline__ void assoc_image(const AssocArgs& a, const DevSkeleto
 #pragma unroll
             for (int r = 0; r < WR; r++)
                 if ((occupied >> r) & 1u) m = min(m, (unsigned)(s_if[r] & kIdxMask));
-            const unsigned was = hd;
             hd = ~wave_max_u32(~m);
-            if (self && hd != was && lane == 0) __hip_atomic_store(&sh_ctl[12], (int)hd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        };
-        // self-serve: who grows what is read from the slots' owner words (the growers claim them), once per round
-        auto read_owners = [&]() {
-            emitted = 0u;
-#pragma unroll
-            for (int k = 0; k < (WR + 7) / 8; k++) gmap[k] = 0u;
-#pragma unroll
-            for (int r = 0; r < WR; r++) {
-                const int o = flag_peek(&pool_own[r * kWave + lane]);
-                if (o != 0 && (occupied >> r) & 1u) { emitted |= 1u << r; gm_set(r, o); }
-            }
         };
         auto head_grower = [&]() -> int {
             int mine = -1;
@@ -2847,10 +2123,8 @@ __device__ __forceinline__ void assoc_image(const AssocArgs& a, const DevSkeleto
 
             // ---- 1. commit the head while its growth is done (:213-230): every commit of a run costs the commit alone,
             //         not a round of the whole loop (a crowded image ends in dozens of poses of one or two joints)
-            if (self) read_owners();
             int hg = hd == kNone ? -1 : head_grower();
-            for (int run = 0; run < kCommitRun && hg >= 0 && flag_load(&task[hg].state) == kTaskDone &&
-                              (!self || task[hg].seed == (int)hd) && (!la_on || hd < bound); run++) {
+            for (int run = 0; run < kCommitRun && hg >= 0 && flag_load(&task[hg].state) == kTaskDone && (!la_on || hd < bound); run++) {
                 const long long t_cm = tick();
                 const PoseView q = pose_of_block(private_base, hg - 1, private_bytes, K);
                 unsigned dead = 0u;                      // pooled seeds inside one of its joint boxes (:211 for them)
@@ -2867,7 +2141,6 @@ __device__ __forceinline__ void assoc_image(const AssocArgs& a, const DevSkeleto
                              (unsigned)(s_if[r0 + r] & kIdxMask) == hd))
                             dead |= 1u << (r0 + r);
                 }
-                if (!self) {
                 if (__ballot((dead & emitted) != 0u) != 0ull) {   // growths of seeds that just died: drop finished ones, stop running ones
                     int n_drop = 0, n_stop = 0;
 #pragma unroll
@@ -2888,28 +2161,6 @@ __device__ __forceinline__ void assoc_image(const AssocArgs& a, const DevSkeleto
                         occupied &= ~(1u << r); emitted &= ~(1u << r); s_if[r] |= kIdxMask;
                         pool_if[r * kWave + lane] = s_if[r];
                     }
-                } else {
-                    // the slot is emptied FIRST, then its owner word is taken: a grower that claims the slot in between finds it
-                    // empty when it looks again (try_claim), one that claimed it before is found here and stopped
-                    int n_drop = 0, n_stop = 0;
-#pragma unroll
-                    for (int r = 0; r < WR; r++)
-                        if ((dead >> r) & 1u) {
-                            const int idx = s_if[r] & kIdxMask;
-                            occupied &= ~(1u << r); emitted &= ~(1u << r); s_if[r] |= kIdxMask;
-                            __hip_atomic_store(&pool_if[r * kWave + lane], s_if[r], __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                            const int g = __hip_atomic_exchange(&pool_own[r * kWave + lane], 0, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
-                            if (g != 0 && (unsigned)idx != hd) {
-                                // (a claim whose task is not set up yet -- the seed word is still the last task's -- finds the flag when it starts)
-                                if (flag_load(&task[g].state) == kTaskDone && task[g].seed == idx) { flag_store(&task[g].state, kTaskIdle); n_drop++; }
-                                else { flag_store(&task[g].cancel, 1); n_stop++; }
-                            }
-                        }
-                    if (__ballot(n_drop + n_stop > 0) != 0ull) {
-#pragma unroll
-                        for (int k = 0; k < WR; k++) { stat(3, __popcll(__ballot(n_drop > k))); stat(2, __popcll(__ballot(n_stop > k))); }
-                    }
-                }
                 if (a.trace && n_commits < kAssocTrace && lane == 0) {
                     int* tr = a.trace + ((size_t)b * kAssocTrace + n_commits) * 4;
                     tr[0] = (int)(wall_clock64() - t_kernel); tr[1] = task[hg].t_emit; tr[2] = task[hg].t_done;
@@ -2949,7 +2200,7 @@ __device__ __forceinline__ void assoc_image(const AssocArgs& a, const DevSkeleto
             }
             const bool g_live = (g_state == kTaskAssigned || g_state == kTaskDone) && !g_cancel;
             const unsigned long long live_mask = __ballot(g_live);
-            if (!self && __ballot(unver != 0u) != 0ull && __ballot(g_live && g_ack != epoch) == 0ull) unver = 0u;   // everyone has tested the newcomers
+            if (__ballot(unver != 0u) != 0ull && __ballot(g_live && g_ack != epoch) == 0ull) unver = 0u;   // everyone has tested the newcomers
 
             // ---- 3. refill free slots with the next seeds that are still free in the bitmap (:211 for the
             //         poses accepted so far); slot (r, lane) takes the seed of its rank among the free slots
@@ -3210,10 +2461,9 @@ __device__ __forceinline__ void assoc_image(const AssocArgs& a, const DevSkeleto
                     for (int r = 0; r < WR; r++)
                         if ((pc >> r) & 1u) {
                             const int g = gm_get(r);
-                            if (flag_load(&task[g].state) == kTaskAssigned &&
-                                (!self || (task[g].seed == (s_if[r] & kIdxMask) && !flag_peek(&task[g].cancel)))) {
+                            if (flag_load(&task[g].state) == kTaskAssigned) {
                                 flag_store(&task[g].cancel, 1);
-                                if (!self) emitted &= ~(1u << r);   // (self-serve: the grower gives the slot back when it has stopped)
+                                emitted &= ~(1u << r);
                                 n_pc++;
                                 d_sel = g;               // the stopped growth, and the (first) live candidate whose box holds its seed
                                 for (int h = NW - 1; h >= 1; h--)
@@ -3257,9 +2507,8 @@ __device__ __forceinline__ void assoc_image(const AssocArgs& a, const DevSkeleto
                         if (((occupied & emitted) >> r) & 1u && gm_get(r) == d &&
                             (s_if[r] & kIdxMask) == rlane(g_seed, d)) bit |= 1u << r;
                     if (__ballot(bit != 0u) == 0ull) continue;
-                    if (self && rlane(g_cancel, d)) continue;   // (told already)
                     if (lane == 0) flag_store(&task[d].cancel, 1);
-                    if (!self) emitted &= ~bit;
+                    emitted &= ~bit;
                     const unsigned v = (shadow_by[d * kWave + lane] & occupied) | bit;
                     if (v) atomicOr(&shadow_by[h * kWave + lane], v);
                     shadow |= v; ever |= v;
@@ -3269,7 +2518,7 @@ __device__ __forceinline__ void assoc_image(const AssocArgs& a, const DevSkeleto
 
             // ---- 5. hand the next candidates, in seed order, to the idle growers (newcomers the candidates in
             //         flight have not tested yet wait for that -- except the head, which nothing can shadow)
-            unsigned long long idle = self ? 0ull : __ballot(g_state == kTaskIdle);
+            unsigned long long idle = __ballot(g_state == kTaskIdle);
             if (idle) {
                 const long long t_em = tick();
                 // A candidate's own seed box is published by its grower a moment after the hand-out.  Until then (npub == 0)
@@ -3328,7 +2577,6 @@ __device__ __forceinline__ void assoc_image(const AssocArgs& a, const DevSkeleto
                 continue;                                // pool ran empty: refill
             }
             if (hg < 0) hg = head_grower();
-            if (self && hg < 0) { read_owners(); hg = head_grower(); }   // (claimed since the round's look at the owner words?)
             if (hg != last_hg) { if (lane == 0) __hip_atomic_store(&sh_ctl[9], hg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); last_hg = hg; }
             if (hg < 0) {
                 // A head that was never handed out, or whose growth was stopped by a prediction that did not
@@ -3340,16 +2588,10 @@ __device__ __forceinline__ void assoc_image(const AssocArgs& a, const DevSkeleto
                     __builtin_amdgcn_s_sleep(1);         // a grower is idle or about to be
                     continue;
                 }
-                // (self-serve: a grower may have claimed the head a moment ago -- its slot says so before the owner word is read here)
-                if (self && __ballot(is_grower_lane && vstate == kTaskAssigned && task[lane].seed == (int)hd) != 0ull) continue;
                 const unsigned key = is_grower_lane ? ((unsigned)task[lane].seed << 6) | (unsigned)lane : 0u;
                 const int victim = (int)(wave_max_u32(key) & 63u);
                 const int vseed = task[victim].seed;
                 if (lane == 0) flag_store(&task[victim].cancel, 1);
-                if (self) {                              // (it stops or its result is dropped by step 2, gives its slot back and takes the head)
-                    stat(4, 1);
-                    continue;
-                }
                 while (flag_load(&task[victim].state) == kTaskAssigned && wall_clock64() - t_kernel <= kWatchdogTicks)
                     __builtin_amdgcn_s_sleep(2);
                 if (lane == 0) flag_store(&task[victim].state, kTaskIdle);
@@ -3377,16 +2619,17 @@ __device__ __forceinline__ void assoc_image(const AssocArgs& a, const DevSkeleto
             int* tr = a.trace + (size_t)b * kAssocTrace * 4;
             if (lane < NW) { int* t4 = tr + (40 + lane) * 4; t4[0] = task[lane].state; t4[1] = task[lane].seed; t4[2] = task[lane].cancel; t4[3] = task[lane].npub | (task[lane].pad1 << 16); }
             if (lane == 0) { int* t4 = tr + 60 * 4; t4[0] = (int)hd; t4[1] = scan_pos; t4[2] = n_live; t4[3] = epoch; }
-            unsigned best = kNone; int bo = 0, be = 0, bs = 0;
+            unsigned best = kNone; int be = 0, bs = 0;
 #pragma unroll
             for (int r = 0; r < WR; r++) {
                 const unsigned idx = (unsigned)(s_if[r] & kIdxMask);
-                if ((occupied >> r) & 1u && idx < best) { best = idx; bo = pool_own[r * kWave + lane]; be = pool_ep[r * kWave + lane]; bs = 0;
+                if ((occupied >> r) & 1u && idx < best) { best = idx; be = pool_ep[r * kWave + lane]; bs = 0;
                     for (int g = 1; g < NW; g++) bs |= ((shadow_by[g * kWave + lane] >> r) & 1u) << g; }
             }
             const unsigned mn = ~wave_max_u32(~best);
-            if (best == mn && mn != kNone) { int* t4 = tr + 61 * 4; t4[0] = (int)mn; t4[1] = bo; t4[2] = be; t4[3] = bs; }
-            if (lane == 0) { int* t4 = tr + 62 * 4; t4[0] = sh_ctl[12]; t4[1] = sh_ctl[9]; t4[2] = (int)iter; t4[3] = n_commits; }
+            // (words 61[1] and 62[0] are reserved: the removed self-serve hand-out put its owner word and head seed there)
+            if (best == mn && mn != kNone) { int* t4 = tr + 61 * 4; t4[0] = (int)mn; t4[1] = 0; t4[2] = be; t4[3] = bs; }
+            if (lane == 0) { int* t4 = tr + 62 * 4; t4[0] = -1; t4[1] = sh_ctl[9]; t4[2] = (int)iter; t4[3] = n_commits; }
         }
 #endif
         if (lane == 0) {
@@ -3406,85 +2649,6 @@ __device__ __forceinline__ void assoc_image(const AssocArgs& a, const DevSkeleto
         TaskSlot* my = &task[wave];
         c.cancel = &my->cancel;
         long long busy_ticks = 0;
-        int my_pos = -1;                                 // self-serve: the pool slot (slot * 64 + lane) this wave claimed last
-        // Self-serve hand-out: take the next candidate -- the smallest-index pooled seed that is nobody's, is not predicted dead by
-        // a candidate in flight, has been tested by every candidate in flight (or is the head, which nothing can shadow), and does
-        // not lie in the seed box of an earlier candidate that has not published that box yet -- by a compare-and-swap on the
-        // slot's owner word.  What the coordinator's hand-out loop did (step 5), done by the wave that would otherwise wait for it.
-        auto try_claim = [&]() -> bool {
-            constexpr unsigned kNone = 0xFFFFFFFFu;
-            int st = kTaskIdle, cn = 0, sd = -1, npub = 0, gpk = 0, gf = -1, ack = 0;
-            const bool gl = lane >= 1 && lane <= S && lane != wave;
-            if (gl) {
-                st = flag_load(&task[lane].state); cn = flag_peek(&task[lane].cancel); sd = task[lane].seed;
-                npub = flag_peek(&task[lane].npub); gpk = task[lane].pk; gf = task[lane].f; ack = flag_peek(&task[lane].pad1);
-            }
-            const bool live = gl && (st == kTaskAssigned || st == kTaskDone) && !cn;
-            const unsigned long long live_mask = __ballot(live);
-            const unsigned min_ack = ~wave_max_u32(~(live ? (unsigned)ack : kNone));   // (all ones: no candidate in flight)
-            const unsigned hd_now = (unsigned)flag_peek(&sh_ctl[12]);
-            int sif[WR], spk[WR];
-            unsigned elig = 0u;
-            {
-                int sep[WR], own[WR];
-#pragma unroll
-                for (int r = 0; r < WR; r++) {
-                    sif[r] = flag_peek(&pool_if[r * kWave + lane]); spk[r] = pool_pack[r * kWave + lane];
-                    sep[r] = pool_ep[r * kWave + lane]; own[r] = flag_peek(&pool_own[r * kWave + lane]);
-                }
-                unsigned sh = 0u;
-                for (int g = 1; g <= S; g++)
-                    if ((live_mask >> g) & 1ull) sh |= shadow_by[g * kWave + lane];
-#pragma unroll
-                for (int r = 0; r < WR; r++) {
-                    const unsigned idx = (unsigned)(sif[r] & kPoolIdxMask);
-                    const bool tested = min_ack == kNone || sep[r] - (int)min_ack <= 0 || idx == hd_now;
-                    if (idx != (unsigned)kPoolIdxMask && own[r] == 0 && !((sh >> r) & 1u) && tested) elig |= 1u << r;
-                }
-            }
-            const bool unp = live && npub == 0;
-            for (;;) {
-                unsigned l_min = kNone; int l_r = 0, l_pk = 0, l_if = 0;
-#pragma unroll
-                for (int r = 0; r < WR; r++) {
-                    const unsigned idx = (unsigned)(sif[r] & kPoolIdxMask);
-                    if ((elig >> r) & 1u && idx < l_min) { l_min = idx; l_r = r; l_pk = spk[r]; l_if = sif[r]; }
-                }
-                const unsigned mn = ~wave_max_u32(~l_min);
-                if (mn == kNone) return false;
-                const bool own_lane = l_min == mn;
-                const int owner = __builtin_ctzll(__ballot(own_lane));
-                const int pk = rlane(l_pk, owner), fo = (int)((unsigned)rlane(l_if, owner) >> 24), slot = rlane(l_r, owner);
-                {   // inside the seed box of an earlier candidate that has not published it yet?
-                    const int ccx = gpk & 0xfff, ccy = (gpk >> 12) & 0xfff, half = (gpk >> 24) & 0xff;
-                    const int dx = (pk & 0xfff) - ccx, dy = ((pk >> 12) & 0xfff) - ccy;
-                    const bool hit = unp && gf == fo && (unsigned)sd < mn && dx > -half && dx < half && dy > -half && dy < half;
-                    if (__ballot(hit) != 0ull) { if (own_lane) elig &= ~(1u << l_r); continue; }
-                }
-                int won = 0;
-                if (lane == owner) {
-                    flag_store(&my->cancel, 0);          // (before the claim: a cancel that follows it is meant for it)
-                    int* ow = &pool_own[slot * kWave + lane];
-                    int expected = 0;
-                    if (__hip_atomic_compare_exchange_strong(ow, &expected, wave, __ATOMIC_ACQ_REL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) {
-                        // the slot may have changed hands between the look at it and the claim: the occupant has to be the same
-                        if (flag_load(&pool_if[slot * kWave + lane]) == l_if) won = 1;
-                        else { expected = wave; __hip_atomic_compare_exchange_strong(ow, &expected, 0, __ATOMIC_ACQ_REL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-                    }
-                }
-                if (__ballot(won) == 0ull) return false; // (somebody else's: look again at everything -- the winner's seed box is among the unpublished ones then)
-                my_pos = slot * kWave + owner;
-                shadow_by[wave * kWave + lane] = 0u;     // nothing published for this task yet
-                if (lane == 0) {
-                    my->seed = (int)mn; my->pk = pk; my->f = fo; my->npub = 0; my->coll = 0;
-                    my->t_emit = (int)(wall_clock64() - t_kernel);
-                    __hip_atomic_fetch_add(&sh_stats[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-                wave_sync();
-                if (lane == 0) flag_store(&my->state, kTaskAssigned);
-                return true;
-            }
-        };
         for (;;) {
             bool leave = false;
             for (;;) {
@@ -3510,23 +2674,6 @@ __device__ __forceinline__ void assoc_image(const AssocArgs& a, const DevSkeleto
                     continue;
                 }
                 if (flag_load(&sh_ctl[0]) || wall_clock64() - t_kernel > 2 * kWatchdogTicks) { leave = true; break; }
-                if (self && state == kTaskIdle) {
-                    if (my_pos >= 0) {                   // a growth that was stopped, or a result that was dropped: the seed is somebody's again
-                        if (lane == 0) {
-                            int expected = wave;
-                            __hip_atomic_compare_exchange_strong(&pool_own[my_pos], &expected, 0, __ATOMIC_ACQ_REL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        }
-                        my_pos = -1;
-                    }
-                    if (try_claim()) break;
-                }
-                if (help_on) {                           // nothing of its own to do: a connection of the growth the commit waits for
-                    const int hgw = flag_peek(&sh_ctl[9]);
-                    if (hgw >= 1 && hgw <= S && hgw != wave) {
-                        help_once<REG>(c, p, private_base + (size_t)(hgw - 1) * private_bytes, tgt_floats, a.spec != 0);
-                        continue;
-                    }
-                }
                 __builtin_amdgcn_s_sleep(2);
             }
             if (leave) break;
@@ -3580,7 +2727,7 @@ __device__ __forceinline__ void assoc_image(const AssocArgs& a, const DevSkeleto
 #ifdef OPA_ASSOC_SCAN_TIMING
         if (lane == 0) { atomicAdd(&sh_ctl[3], (int)busy_ticks); atomicAdd(&sh_ctl[4], c.n_blend); atomicAdd(&sh_ctl[6], c.t_blend); atomicAdd(&sh_ctl[7], c.t_blend_mem); }
 #else
-        if (lane == 0) { atomicAdd(&sh_ctl[3], (int)busy_ticks); atomicAdd(&sh_ctl[4], c.n_blend); atomicAdd(&sh_ctl[6], c.n_hit); atomicAdd(&sh_ctl[7], c.n_miss); }
+        if (lane == 0) { atomicAdd(&sh_ctl[3], (int)busy_ticks); atomicAdd(&sh_ctl[4], c.n_blend); }
 #endif
     }
     sync_global();                        // stored poses visible to every wave; the private blocks are free
@@ -3822,7 +2969,7 @@ template <bool REG, int NW>
 static hipError_t launch_assoc_nw(const AssocArgs& a, const DevSkeleton& sk, const DevParams& p, hipStream_t st) {
     const int K = a.K, A = a.A, E = 2 * A;
     size_t shared = sizeof(TaskSlot) * NW + (sizeof(unsigned long long) << kDedupBits) + sizeof(int) * (3 * E + K + 1 + 16 + kAssocStats)
-                  + sizeof(int) * ((kSelfServe ? 4 : 3) * (REG ? kPoolSlots : kPoolSlotsLds) + NW) * kWave + sizeof(int) * 2 * kSeedStage;
+                  + sizeof(int) * (3 * (REG ? kPoolSlots : kPoolSlotsLds) + NW) * kWave + sizeof(int) * 2 * kSeedStage;
     shared = (shared + 15) / 16 * 16 + (REG && a.list_bbox ? sizeof(float4) * E * kListBboxChunks : 0);
     // work area behind it: one private block per grower while poses grow, the keypoint-NMS arrays afterwards
 #ifdef OPA_ASSOC_PHASE_TIMING
@@ -3832,16 +2979,13 @@ static hipError_t launch_assoc_nw(const AssocArgs& a, const DevSkeleton& sk, con
 #endif
     // the scan area of a grower: the full one (lists of up to 8 chunks in one round trip), or the small one when that
     // buys more growers (large skeletons: the frontier lives in LDS too, and their lists are short)
-    const bool spec = a.spec != 0;
     int tgt_floats = kBlendLdsFloats;
-    const bool help = kHelp && a.help != 0;
-    size_t priv = assoc_private_bytes(K, A, REG, tgt_floats, spec, help);
+    size_t priv = assoc_private_bytes(K, A, REG, tgt_floats);
     int growers = shared + priv <= budget ? (int)((budget - shared) / priv) : 0;
     if (growers < NW - 1) {
-        const int small_floats = spec ? kSpecTgtFloats : kSmallTgtFloats;     // (the level walk's batches need more of it than two chunks)
-        const size_t priv_small = assoc_private_bytes(K, A, REG, small_floats, spec, help);
+        const size_t priv_small = assoc_private_bytes(K, A, REG, kSmallTgtFloats);
         const int growers_small = shared + priv_small <= budget ? (int)((budget - shared) / priv_small) : 0;
-        if (growers_small > growers) { growers = growers_small; priv = priv_small; tgt_floats = small_floats; }
+        if (growers_small > growers) { growers = growers_small; priv = priv_small; tgt_floats = kSmallTgtFloats; }
     }
     if (growers < 1) return hipErrorInvalidValue;
     if (growers > NW - 1) growers = NW - 1;
@@ -3861,19 +3005,10 @@ static hipError_t launch_assoc_nw(const AssocArgs& a, const DevSkeleton& sk, con
     }
     if (a.queue_order)                                // more images than compute units: longest first
         assoc_order_kernel<<<(a.B + 1023) / 1024, 1024, 0, st>>>(a.seed_count, a.B, a.queue_order, a.queue_head);
-    cifcaf_assoc_kernel<REG, NW><<<a.B, NW * kWave, lds, st>>>(a, sk, p, growers, nms_waves, tgt_floats);
+    AssocArgs ak = a;
+    ak.private_bytes = priv;
+    cifcaf_assoc_kernel<REG, NW><<<a.B, NW * kWave, lds, st>>>(ak, sk, p, growers, nms_waves, tgt_floats);
     return hipGetLastError();
-}
-
-// waves per workgroup of the association kernel: 1 coordinator + up to NW-1 growers.  12 is what ships; the 8- and
-// 16-wave instantiations (OPA_ASSOC_WAVES, interleaving experiments of round 2) double the compile time of this file
-// and are built only with -DOPA_ASSOC_ALL_WAVES.
-static int assoc_waves(int v) {
-#ifdef OPA_ASSOC_ALL_WAVES
-    return v == 8 || v == 12 || v == 16 ? v : kAssocWavesDefault;
-#else
-    return v == 8 || v == 12 ? v : kAssocWavesDefault;
-#endif
 }
 
 hipError_t launch_assoc(const AssocArgs& args, const DevSkeleton& sk, const DevParams& p, hipStream_t st, const opa_debug& dbg) {
@@ -3895,31 +3030,21 @@ hipError_t launch_assoc(const AssocArgs& args, const DevSkeleton& sk, const DevP
     a.inherit = dbg.assoc_inherit != 0;           // 0: predictions lapse with the growth that made them
     a.collide = dbg.assoc_collide != 0;           // 0: growths stop only when their SEED is covered
     a.timing = dbg.assoc_timing != 0;             // phase tick counters of the coordinator (statistics slots 12, 17-20)
-    a.help = kHelp && dbg.assoc_help != 0;        // (helper builds) 0: every growth scans its own lists
-    a.spec = kWalk && dbg.assoc_spec != 0;        // (walk builds) 0: every bone scanned on demand, one at a time
     a.watchdog_ticks = dbg.assoc_watchdog_ticks > 0 ? dbg.assoc_watchdog_ticks : kWatchdogTicksDefault;
     a.max_growers = dbg.assoc_growers;
     if (dbg.assoc_persistent < 0 || (dbg.assoc_persistent == 0 && a.B <= assoc_compute_units())) a.queue_order = a.queue_head = nullptr;
     a.fc_split = dbg.fc_split;
-    const int waves = assoc_waves(dbg.assoc_waves);
     const int K = a.K, E = 2 * a.A;
     // the seed pool packs cell coordinates into 12 bits, the field into 8 and the seed index into 24
     if (a.occ_w > 4096 || a.occ_h > 4096 || a.F > 256 || a.seed_cap > 0xFFFFFF) return hipErrorInvalidValue;
     if (K > 256 || a.A > 256) return hipErrorInvalidValue;      // a slot's joints and bone are packed into 8 bits each
     const bool reg = K <= kWave && E <= kWave;       // pose, frontier and heap fit the lanes of a wave
-    hipError_t e;
-    if (!reg) e = waves == 8 ? launch_assoc_nw<false, 8>(a, sk, p, st) : launch_assoc_nw<false, 12>(a, sk, p, st);  // LDS-resident growth state
-    else switch (waves) {
-        case 8: e = launch_assoc_nw<true, 8>(a, sk, p, st); break;
-#ifdef OPA_ASSOC_ALL_WAVES
-        case 16: e = launch_assoc_nw<true, 16>(a, sk, p, st); break;
-#endif
-        default: e = launch_assoc_nw<true, 12>(a, sk, p, st); break;
-    }
+    hipError_t e = reg ? launch_assoc_nw<true, kAssocWaves>(a, sk, p, st)
+                       : launch_assoc_nw<false, kAssocWaves>(a, sk, p, st);   // (else: LDS-resident growth state)
     prof_mark(st, "cifcaf_assoc_kernel");
     if (e == hipSuccess && p.force_complete) {
         if (!a.fc_meta || !a.lists_fc) return hipErrorInvalidValue;
-        e = reg ? launch_fc_nw<true, 12>(a, sk, p, st) : launch_fc_nw<false, 12>(a, sk, p, st);
+        e = reg ? launch_fc_nw<true, kAssocWaves>(a, sk, p, st) : launch_fc_nw<false, kAssocWaves>(a, sk, p, st);
         prof_mark(st, "cifcaf_fc_kernel");
     }
     return e;

@@ -35,10 +35,7 @@ __device__ __forceinline__ void gauss_box(float cx, float cy, float sigma, int r
 
 // ---------------------------------------------------------------- pass 1
 // DET: CifDet fields [F,6,H,W] (w,h instead of scale), CifDetHr::accumulate cif_hr.cpp:124-150
-#ifndef OPA_ACTIVE_THREADS
-#define OPA_ACTIVE_THREADS 256
-#endif
-constexpr int kActiveThreads = OPA_ACTIVE_THREADS;
+constexpr int kActiveThreads = 256;
 constexpr int kActiveCells = 4;
 
 // WL (the decode path's pooled map): the kernel also
@@ -297,9 +294,6 @@ __device__ __forceinline__ void build_tile(const float* __restrict__ A, int n, i
             hit = minx < x1 && maxx > x0 && miny < y1 && maxy > y0;
         }
         unsigned long long mask = __ballot(hit);
-#ifdef OPA_TILE_WALK_ONLY               // diagnostic: the list walk without the accumulation (what tile-binned lists could save)
-        mask = 0ull;
-#endif
         while (mask) {
             const int l = __builtin_ctzll(mask);
             mask &= mask - 1;
@@ -327,10 +321,7 @@ __device__ __forceinline__ void build_tile(const float* __restrict__ A, int n, i
 // workspace remembers the bitmap of the previous call (`prev`); only tiles in cur | prev are visited --
 // built if in cur, zeroed if only in prev -- and every other tile is already all-zero in HBM.  Most of the
 // map is such tiles.  Without workspace state (stage-level entry point, invalid header) every tile is built.
-#ifndef OPA_TILE_GROUPS
-#define OPA_TILE_GROUPS 8
-#endif
-constexpr int kTileGroups = OPA_TILE_GROUPS;
+constexpr int kTileGroups = 8;
 
 __global__ __launch_bounds__(256) void cifhr_tile_kernel(
         const float* __restrict__ act, const int32_t* __restrict__ act_count, int HW,

@@ -15,7 +15,6 @@
 //      u64 keys, entirely in LDS when n <= 8192 (64 KiB), otherwise LDS-blocked
 //      with the far strides done through L2.  The epilogue decodes the keys and
 //      writes the sorted (f, v, x, y, s) arrays the association kernel streams.
-#include "cafscored_impl.hpp"
 #include "cifseeds_tie.hpp"
 
 
@@ -211,7 +210,8 @@ __device__ __forceinline__ void compare_exchange_desc(unsigned long long& a, uns
 // compare-exchange passes of a bitonic network.  The key order (score descending, then cell index ascending) is a
 // total order, so the result does not depend on the algorithm.
 // (Measured on the bench batch: 72.7 us against 74.0 us for the bitonic network below -- the kernel is bound by the
-// busiest image's serial passes either way -- so the hand-written network stays the default; -DOPA_SORT_RADIX.)
+// busiest image's serial passes either way -- so the hand-written network stayed; the radix variant predates the block split
+// below and is gone.)
 
 // Images with more than 8192 seeds (wholebody: 133 fields, ~20 000 seeds): every 8192-key block is sorted by a
 // workgroup of its own (kSortBlocksMax per image in the sort kernel's grid), then cifseeds_rankmerge_kernel gives every
@@ -222,11 +222,6 @@ __device__ __forceinline__ void compare_exchange_desc(unsigned long long& a, uns
 constexpr int kSortBlocksMax = 8;
 constexpr int kSortSmallBlock = 2048;
 __host__ __device__ inline int sort_block_size(int n) { return n <= kSortLdsKeys ? kSortSmallBlock : kSortLdsKeys; }
-
-
-#ifdef OPA_SORT_RADIX
-#error "the rocPRIM variant predates the block split (round 2 experiment)"
-#endif
 
 // the sort of one workgroup (block `block` of the grid's sort part); `sk`: 64 KiB of LDS
 __device__ __forceinline__ void cifseeds_sort_body(const SortArgs& g, const DevParams& p, int block, unsigned long long* sk) {
@@ -495,22 +490,6 @@ __global__ __launch_bounds__(1024) void cifseeds_sort_kernel(SortArgs g, DevPara
     cifseeds_sort_body(g, p, blockIdx.x, sk);
 }
 
-// The decode's form: the same launch also builds the CAF lists (CafScored::fill).  Seed sort and list building only
-// share the finished CifHr map; the sort keeps a handful of workgroups busy for ~40 us (its passes are serial), the list
-// building streams 128 MB through all of the chip in about the same time -- side by side instead of one after the other.
-// Blocks [0, n_sort): sort; behind them, two 512-thread groups per workgroup, one (image, CAF field) plane each, list set
-// 0 first, then list set 1 (force complete).
-__global__ __launch_bounds__(1024) void cifseeds_sort_scored_kernel(SortArgs g, DevParams p, int n_sort, ScoredArgs s0, ScoredArgs s1,
-                                                                    int wgs0) {
-    __shared__ unsigned long long sk[kSortLdsKeys];
-    if ((int)blockIdx.x < n_sort) { cifseeds_sort_body(g, p, blockIdx.x, sk); return; }
-    __shared__ int wave_tot[2][2][kScoredThreads / 64];
-    extern __shared__ float bb_dyn[];
-    const int wg = blockIdx.x - n_sort, group = threadIdx.x >> 9, tid = threadIdx.x & (kScoredThreads - 1);
-    if (wg < wgs0) cafscored_plane(s0, 2 * wg + group, tid, wave_tot[group], bb_dyn + group * 2 * s0.nb * 4);
-    else cafscored_plane(s1, 2 * (wg - wgs0) + group, tid, wave_tot[group], bb_dyn + group * 2 * s1.nb * 4);
-}
-
 // final position of every key of a block-sorted image (see kSortBlocksMax) + the decoded seed
 __global__ __launch_bounds__(256) void cifseeds_rankmerge_kernel(
         const unsigned long long* __restrict__ keys, int sort_cap, int cap, const int32_t* __restrict__ seed_count,
@@ -591,9 +570,7 @@ hipError_t launch_cifseeds(const float* cif, int B, int F, int H, int W, int str
                            unsigned long long* keys, int sort_cap, int32_t* seed_count,
                            int32_t* seed_f, float* seed_vxys, hipStream_t st, bool det,
                            int32_t* seed_cell, int occ_h, int occ_w, bool count_is_zero,
-                           const ScoredArgs* scored, int n_scored, const TieScratch* ties, const HrPool* pool, const SeedCandidates* cand,
-                           bool sort_registers) {
-    static_assert(kScoredThreads == 512, "the fused launch packs two cafscored groups into a 1024-thread workgroup");
+                           const TieScratch* ties, const HrPool* pool, const SeedCandidates* cand, bool sort_registers) {
     const int HW = H * W, cap = F * HW, NC = det ? 6 : 5;
     if (!count_is_zero) {                             // (the decode pipeline clears the counters in its first kernel)
         hipError_t e = launch_zero(seed_count, sizeof(int32_t) * B, st);
@@ -627,14 +604,7 @@ hipError_t launch_cifseeds(const float* cif, int B, int F, int H, int W, int str
     g.keys = keys; g.sort_cap = sort_cap; g.cap = cap; g.seed_count = seed_count; g.cif = cif; g.F = F; g.NC = NC; g.HW = HW;
     g.stride = stride; g.seed_f = seed_f; g.seed_vxys = seed_vxys; g.seed_cell = seed_cell; g.occ_h = occ_h; g.occ_w = occ_w;
     const int n_sort = B * kSortBlocksMax;
-    if (scored && n_scored > 0) {
-        const ScoredArgs& s0 = scored[0];
-        const ScoredArgs& s1 = scored[n_scored > 1 ? 1 : 0];
-        const int wgs0 = (s0.planes + 1) / 2, wgs1 = n_scored > 1 ? (s1.planes + 1) / 2 : 0;
-        const int nb_max = s0.nb > s1.nb || n_scored < 2 ? s0.nb : s1.nb;
-        const size_t lds = sizeof(float) * 2 * 2 * nb_max * 4;
-        cifseeds_sort_scored_kernel<<<n_sort + wgs0 + wgs1, 1024, lds, st>>>(g, p, n_sort, s0, s1, wgs0);
-    } else if (sort_registers) {
+    if (sort_registers) {
         cifseeds_sort2k_kernel<<<B * 4, kSort2kThreads, 0, st>>>(g, p);
         if (cap > 4 * kSortSmallBlock) cifseeds_sort_kernel<<<n_sort, 1024, 0, st>>>(g, p, 1);
     } else {
@@ -645,7 +615,7 @@ hipError_t launch_cifseeds(const float* cif, int B, int F, int H, int W, int str
         cifseeds_rankmerge_kernel<<<dim3((most + 255) / 256, B), 256, 0, st>>>(keys, sort_cap, cap, seed_count, cif, F, NC, HW,
                                                                                  stride, seed_f, seed_vxys, seed_cell, occ_h, occ_w, p);
     }
-    prof_mark(st, scored && n_scored > 0 ? "sort_cafscored_kernel" : "cifseeds_sort_kernel");
+    prof_mark(st, "cifseeds_sort_kernel");
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && tie_pass && !ties->defer) {   // cif_seeds.cpp:94: std::sort's order of equal scores
         TieArgs ta; SortArgs tg;

@@ -12,10 +12,7 @@ namespace opa {
 
 constexpr int kWave = 64;                 // CDNA4 wavefront width
 constexpr int kHrTileW = 64;              // CifHr tile width  (one 256-B row segment)
-#ifndef OPA_HR_TILE_H
-#define OPA_HR_TILE_H 32
-#endif
-constexpr int kHrTileH = OPA_HR_TILE_H;   // CifHr tile height
+constexpr int kHrTileH = 32;             // CifHr tile height
 constexpr int kHrLdsPitch = kHrTileW + 16;// LDS row pitch: +16 banks so a 16x4 patch is conflict free
 constexpr int kSortLdsKeys = 8192;        // 64 KiB of u64 keys sorted inside LDS
 
@@ -117,7 +114,6 @@ hipError_t launch_cifhr_gather(const float* pool_image, const int32_t* slot_imag
 // [2] 1 = stored bitmap invalid for this call (written by the first kernel of a call).
 constexpr unsigned long long kWsMagic = 0x6f70615f63696668ull;   // "opa_cifh"
 
-struct ScoredArgs;
 // Scratch of the pass that puts seeds of EQUAL score into libstdc++'s std::sort order (cifseeds.hip); `state` [B]:
 // 0 no equal scores, 1 re-sorted, -1 not reproduced (introsort's heapsort branch).  seed_tie_order(): 1 = libstdc++
 // (the reference, default), 0 = cell index (opa_set_seed_tie_order / OPA_SEED_TIES=index).
@@ -131,10 +127,8 @@ hipError_t launch_cifseeds(const float* cif, int B, int F, int H, int W, int str
                            unsigned long long* keys, int sort_cap, int32_t* seed_count,
                            int32_t* seed_f, float* seed_vxys, hipStream_t st, bool det = false,
                            int32_t* seed_cell = nullptr, int occ_h = 0, int occ_w = 0, bool count_is_zero = false,
-                           const ScoredArgs* scored = nullptr, int n_scored = 0, const TieScratch* ties = nullptr,
-                           const HrPool* pool = nullptr, const SeedCandidates* cand = nullptr, bool sort_registers = true);
-// (`scored`: up to two CafScored list sets built by the SAME launch as the seed sort -- they only share the finished
-// map, and the sort's few workgroups leave the chip to them)
+                           const TieScratch* ties = nullptr, const HrPool* pool = nullptr, const SeedCandidates* cand = nullptr,
+                           bool sort_registers = true);
 
 // CafScored::fill of one list set (cafscored_impl.hpp)
 struct ScoredArgs {
@@ -211,8 +205,7 @@ struct AssocArgs {
     int timing;                 // 1: the coordinator also fills the tick counters of its phases (statistics slots 12, 17-20)
     int collide;                // 1: a growth that assigns a joint inside the same joint's box of an earlier live candidate is stopped (advisory)
     int inherit;                // 1: a candidate inherits the predictions of a growth stopped because of it (advisory; see cifcaf.hip)
-    int help;                   // 1: idle growers evaluate connections of the growth that holds the head seed (scan helpers; exact, see cifcaf.hip)
-    int spec;                   // 1: the growers walk the skeleton level by level in batched scans first and the search takes connection values from that memo (exact; see cifcaf.hip)
+    size_t private_bytes;       // LDS bytes of one grower's private block (association kernel; launch_assoc_nw sizes it)
     int dedup;                  // 1: later seeds of an occupancy cell already seen are dropped at the pool refill (exact; see cifcaf.hip)
     const float* caf_raw; int caf_w; float caf_stride;   // the CAF field tensor itself [B][A][8][list_cap] (predict_pose reads single cells of it)
     int coll_shift;             // collision stops: how close to the centre of the earlier candidate's joint box (extent >> shift; 0 = anywhere inside)

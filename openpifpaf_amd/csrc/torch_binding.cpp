@@ -83,13 +83,13 @@ struct CifCaf : torch::CustomClassHolder {
         opa_debug d;
         check(opa_cifcaf_get_debug(handle, &d), "opa_cifcaf_get_debug");
 #define OPA_DBG_FIELD(F, T) if (name == #F) { d.F = (T)value; check(opa_cifcaf_set_debug(handle, &d), "opa_cifcaf_set_debug"); return; }
-        OPA_DBG_FIELD(stage_worklist, int32_t) OPA_DBG_FIELD(fuse_scored, int32_t) OPA_DBG_FIELD(scored_one_pass, int32_t)
-        OPA_DBG_FIELD(assoc_waves, int32_t) OPA_DBG_FIELD(assoc_growers, int32_t) OPA_DBG_FIELD(assoc_bbox, int32_t)
+        OPA_DBG_FIELD(stage_worklist, int32_t) OPA_DBG_FIELD(scored_one_pass, int32_t)
+        OPA_DBG_FIELD(assoc_growers, int32_t) OPA_DBG_FIELD(assoc_bbox, int32_t)
         OPA_DBG_FIELD(assoc_dedup, int32_t) OPA_DBG_FIELD(assoc_prededup, int32_t) OPA_DBG_FIELD(assoc_predict, int32_t)
         OPA_DBG_FIELD(assoc_predict_min_v, float) OPA_DBG_FIELD(assoc_predict_th, float) OPA_DBG_FIELD(assoc_collide, int32_t)
         OPA_DBG_FIELD(assoc_collide_shift, int32_t) OPA_DBG_FIELD(assoc_inherit, int32_t) OPA_DBG_FIELD(assoc_lookahead, int32_t)
-        OPA_DBG_FIELD(assoc_help, int32_t) OPA_DBG_FIELD(assoc_spec, int32_t) OPA_DBG_FIELD(assoc_timing, int32_t)
-        OPA_DBG_FIELD(assoc_persistent, int32_t) OPA_DBG_FIELD(fc_split, int32_t) OPA_DBG_FIELD(side_stream, int32_t) OPA_DBG_FIELD(assoc_watchdog_ticks, int64_t)
+        OPA_DBG_FIELD(assoc_timing, int32_t)
+        OPA_DBG_FIELD(assoc_persistent, int32_t) OPA_DBG_FIELD(fc_split, int32_t) OPA_DBG_FIELD(assoc_watchdog_ticks, int64_t)
 #undef OPA_DBG_FIELD
         TORCH_CHECK(false, "opa_debug has no field ", name);
     }

@@ -1,6 +1,6 @@
 """Round-6 parity cases: every structural change of the round decodes exactly like the structure it replaced and like the oracle --
 the tile work list / seed candidates against round 5's stage kernels, the image queue of the association kernel (batches of more
-images than compute units), the side stream, the one-pass CAF list sets, and ``opa_debug`` itself (per decoder, no environment)."""
+images than compute units), the one-pass CAF list sets, and ``opa_debug`` itself (per decoder, no environment)."""
 import numpy as np
 import pytest
 
@@ -132,10 +132,9 @@ def test_image_queue_of_large_batches_is_longest_first_and_exact(native, port, c
         assert np.array_equal(small[b], got[b])
 
 
-def test_side_stream_and_list_set_passes_are_bit_identical(native, port, coco_skeleton0):
-    """The CAF lists built on the handle's side stream beside the seed chain (``side_stream``), and both list sets of a
-    force-complete decode from one read of the field or from two passes (``scored_one_pass``): the same annotations, several calls
-    in a row on one decoder (the fork / join events are re-used), default flags and the reference benchmark's setting."""
+def test_list_set_passes_are_bit_identical(native, port, coco_skeleton0):
+    """Both list sets of a force-complete decode from one read of the field or from two passes (``scored_one_pass``): the same
+    annotations, several calls in a row on one decoder, default flags and the reference benchmark's setting."""
     from openpifpaf_amd import _lib, synth
     cifs, cafs = synth.synth_batch(6, seed0=62_000, height=49, width=65)
     for kw in ({}, FC_KW):
@@ -145,15 +144,14 @@ def test_side_stream_and_list_set_passes_are_bit_identical(native, port, coco_sk
             ref, _ = port.decode(cifs[b], 8, cafs[b], 8, coco_skeleton0, params=port.default_params(**kw) if kw else None)
             ok, msg = compare_annotations(want[b], ref)
             assert ok, msg
-        for debug in ({'side_stream': 1}, {'scored_one_pass': 0}, {'side_stream': 1, 'scored_one_pass': 0}):
-            dec = native.CifCaf(17, torch.from_numpy(coco_skeleton0))
-            dec.set_debug(**debug)
-            for rep in range(3):
-                out, ids, counts = dec.call_batch(dev(cifs), 8, dev(cafs), 8, params=params)
-                counts = counts.cpu().numpy()
-                native.check_counts(counts)
-                for b in range(6):
-                    assert np.array_equal(out[b, :native.count_rows(int(counts[b]))].cpu().numpy(), want[b]), (kw, debug, rep, b)
+        dec = native.CifCaf(17, torch.from_numpy(coco_skeleton0))
+        dec.set_debug(scored_one_pass=0)
+        for rep in range(3):
+            out, ids, counts = dec.call_batch(dev(cifs), 8, dev(cafs), 8, params=params)
+            counts = counts.cpu().numpy()
+            native.check_counts(counts)
+            for b in range(6):
+                assert np.array_equal(out[b, :native.count_rows(int(counts[b]))].cpu().numpy(), want[b]), (kw, rep, b)
 
 
 def test_rccl_gather_branch_runs_on_one_gpu(coco_skeleton0, tmp_path):

@@ -1,5 +1,5 @@
 """Statistics of the association kernel on the bench batch (always-on counters, "assoc_stats"):
-    [OPA_ASSOC_WAVES=8|12|16] python tools/gpu/assoc_probe.py [batch]"""
+    python tools/gpu/assoc_probe.py [batch]"""
 import os
 import sys
 
@@ -18,7 +18,7 @@ for _ in range(3):
     out, ids, counts = dec.call_batch(cif, 8, caf, 8)
 torch.cuda.synchronize()
 st = dec.assoc_stats().cpu().numpy()
-print('OPA_ASSOC_WAVES=%s  ticks are 10 ns' % os.environ.get('OPA_ASSOC_WAVES', 'default'))
+print('ticks are 10 ns')
 print('img people poses seeds | started accepted stopped dropped pre-stop mispred refills | growth-us total-us iters '
       'head-wait-us grower-busy-us scans us/scan growers')
 for b in range(min(B, 8)):

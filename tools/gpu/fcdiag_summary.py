@@ -1,4 +1,4 @@
-"""Per-kernel averages of the PMC passes tools/gpu/r5b_fcdiag.sh collected (rocprofv3 counter_collection CSVs)."""
+"""Per-kernel averages of rocprofv3 PMC passes over the force-complete kernel (counter_collection CSVs)."""
 import csv
 import glob
 import os

@@ -23,7 +23,7 @@ WORKLOADS = [('config2', 'COCO-17 (configs 2 / 3 fields), batch 32, default flag
              ('config2_b256', 'COCO-17, 256 images in ONE call_batch (round 6)', 2, 256, False)]
 DECODE_KERNELS = ('zero_kernel', 'cif_active_kernel', 'cifhr_tile_kernel', 'cifhr_worktile_kernel', 'tile_state_roll_kernel',
                   'cifseeds_fill_kernel', 'cifseeds_fill_cand_kernel', 'cifseeds_sort2k_kernel', 'cifseeds_sort_kernel',
-                  'cifseeds_sort_scored_kernel', 'cifseeds_rankmerge_kernel', 'cifseeds_tie_kernel', 'cafscored_kernel',
+                  'cifseeds_rankmerge_kernel', 'cifseeds_tie_kernel', 'cafscored_kernel',
                   'cafscored2_kernel', 'assoc_order_kernel', 'cifcaf_assoc_kernel', 'cifcaf_fc_kernel')
 
 
