@@ -428,10 +428,20 @@ int opa_conv_rows_f32x3(const float* x_dev, const void* w3_dev, const float* bia
  *  x_dev [B, h, w, c_in], u_dev = the filter transformed and laid out by openpifpaf_amd.winograd.transform_filter for
  *  `variant` (0, 2 and 3: 64 output channels per workgroup, c_in % 16 == 0, c_out % 64 == 0 -- 2 runs eight waves in two
  *  shifts on the same operand (the default of the Python side), 3 the same as persistent workgroups; 1: 32 channels, c_in % 8 == 0, c_out % 32 == 0), out_dev [B, h, w, c_out]; bias_dev [c_out] or NULL; relu 0/1; order 0 = workgroups of one tile block
- *  on one XCD, 1 = workgroups of one channel block on one XCD.  B*h*w*c_in < 2^32; pointers 16-B aligned. */
+ *  on one XCD, 1 = workgroups of one channel block on one XCD.  B*h*w*c_in < 2^30; pointers 16-B aligned; any other variant
+ *  is refused. */
 int opa_conv3x3_winograd_f32(const float* x_dev, const float* u_dev, const float* bias_dev, float* out_dev, int32_t batch,
                              int32_t h, int32_t w, int32_t c_in, int32_t c_out, int32_t relu, int32_t variant,
                              int32_t order, void* stream);
+
+/* The same convolution on the bf16 MFMA pipe with exactly split operands (variant 4 of csrc/winograd.hip): every float32
+ * operand is the sum of three bf16 pieces, the six leading piece products are formed (the three left out are below 2^-23 of
+ * a product each), accumulation in float32.  u3_dev = the three bf16 planes of the transformed filter laid out by
+ * openpifpaf_amd.winograd.split_filter ([c_out / 64][c_in / 16][16][2][3][64][8] bf16).  variant must be 4; c_in % 16 == 0,
+ * c_out % 64 == 0, B*h*w*c_in < 2^30; the rest as opa_conv3x3_winograd_f32. */
+int opa_conv3x3_winograd_f32x3(const float* x_dev, const void* u3_dev, const float* bias_dev, float* out_dev, int32_t batch,
+                               int32_t h, int32_t w, int32_t c_in, int32_t c_out, int32_t relu, int32_t variant,
+                               int32_t order, void* stream);
 
 /* Depthwise k x k convolution (k = 3 or 5, stride 1 or 2, padding k/2) of a channels-last activation, with the
  * folded batch-norm bias and optionally ReLU fused (the ShuffleNetV2K unit of the reference,

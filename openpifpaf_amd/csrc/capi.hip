@@ -920,14 +920,32 @@ int opa_conv3x3_winograd_f32(const float* x_dev, const float* u_dev, const float
         return fail(OPA_ERR_INVALID_ARGUMENT, "opa_conv3x3_winograd_f32: bad arguments");
     if (variant != 1 ? (c_in % 16 != 0 || c_out % 64 != 0) : (c_in % 8 != 0 || c_out % 32 != 0))
         return fail(OPA_ERR_INVALID_ARGUMENT, "opa_conv3x3_winograd_f32: channel counts do not fit the variant's tiles");
-    if ((double)batch * h * w * c_in >= 4294967296.0 || (double)batch * ((h + 1) / 2) * ((w + 1) / 2) >= 2147483647.0)
-        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_conv3x3_winograd_f32: the activation needs 32-bit element offsets");
+    if ((double)batch * h * w * c_in >= 1073741824.0 || (double)batch * ((h + 1) / 2) * ((w + 1) / 2) >= 2147483647.0)
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_conv3x3_winograd_f32: the activation needs 32-bit byte offsets (fewer than 2^30 elements)");
     if (((uintptr_t)x_dev | (uintptr_t)u_dev | (uintptr_t)out_dev | (uintptr_t)bias_dev) & 15)
         return fail(OPA_ERR_INVALID_ARGUMENT, "opa_conv3x3_winograd_f32: pointers must be 16-B aligned");
     hipError_t e = launch_winograd_f23(x_dev, u_dev, out_dev, bias_dev, batch, h, w, c_in, c_out, relu, variant, order,
                                        (hipStream_t)stream);
     if (e != hipSuccess) return fail_hip(e, "winograd_f23");
     prof_mark((hipStream_t)stream, "winograd_f23_kernel");
+    return OPA_OK;
+}
+
+int opa_conv3x3_winograd_f32x3(const float* x_dev, const void* u3_dev, const float* bias_dev, float* out_dev, int32_t batch,
+                               int32_t h, int32_t w, int32_t c_in, int32_t c_out, int32_t relu, int32_t variant,
+                               int32_t order, void* stream) {
+    if (!x_dev || !u3_dev || !out_dev || batch <= 0 || h <= 0 || w <= 0 || c_in <= 0 || c_out <= 0 || (variant != 4 && (variant < 21 || variant > 23)))
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_conv3x3_winograd_f32x3: bad arguments");
+    if (c_in % 16 != 0 || c_out % 64 != 0)
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_conv3x3_winograd_f32x3: c_in % 16 and c_out % 64 must be 0");
+    if ((double)batch * h * w * c_in >= 1073741824.0 || (double)batch * ((h + 1) / 2) * ((w + 1) / 2) >= 2147483647.0)
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_conv3x3_winograd_f32x3: the activation needs 32-bit byte offsets (fewer than 2^30 elements)");
+    if (((uintptr_t)x_dev | (uintptr_t)u3_dev | (uintptr_t)out_dev | (uintptr_t)bias_dev) & 15)
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_conv3x3_winograd_f32x3: pointers must be 16-B aligned");
+    hipError_t e = launch_winograd_f23x3(x_dev, (const unsigned short*)u3_dev, out_dev, bias_dev, batch, h, w, c_in, c_out, relu,
+                                         variant, order, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "winograd_f23x3");
+    prof_mark((hipStream_t)stream, "winograd_f23_w8x3_kernel");
     return OPA_OK;
 }
 

@@ -29,6 +29,7 @@
 // not collide: with rows padded to 80 B a third of the LDS cycles were store conflicts; profiles/r6/gemm_x3_swizzle_ab.log:
 // 2-7 % on the reduce shapes); XCD-aware tile order and epilogue as in gemm_f32.hip.
 #include "common.hpp"
+#include "split_bf16.hpp"
 
 namespace opa {
 
@@ -58,23 +59,6 @@ constexpr int kX3BM = 128, kX3BK = OPA_X3_BK, kX3Pitch = OPA_X3_SWIZZLE ? kX3BK 
 __device__ __forceinline__ int x3_lds(int row, int k) {
     if (OPA_X3_SWIZZLE && kX3BK == 32) return row * kX3Pitch + ((((k >> 3) ^ (row >> 2)) & 3) << 3) + (k & 7);
     return row * kX3Pitch + k;
-}
-
-// four float32 -> their three bf16 pieces, packed pairwise (element e in the low half of word e / 2 ... K-major order)
-__device__ __forceinline__ void split4(const f32x4_t a, u32x2_t& p1, u32x2_t& p2, u32x2_t& p3) {
-    unsigned u[4], v[4], w[4];
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-        u[e] = __float_as_uint(a[e]);
-        const float r1 = a[e] - __uint_as_float(u[e] & 0xffff0000u);       // exact: the low 16 significand bits
-        v[e] = __float_as_uint(r1);
-        const float r2 = r1 - __uint_as_float(v[e] & 0xffff0000u);         // exact: at most 8 significant bits are left
-        w[e] = __float_as_uint(r2);
-    }
-    // high halves of two words side by side: bytes {hi.3, hi.2, lo.3, lo.2}
-    p1[0] = __builtin_amdgcn_perm(u[1], u[0], 0x07060302u); p1[1] = __builtin_amdgcn_perm(u[3], u[2], 0x07060302u);
-    p2[0] = __builtin_amdgcn_perm(v[1], v[0], 0x07060302u); p2[1] = __builtin_amdgcn_perm(v[3], v[2], 0x07060302u);
-    p3[0] = __builtin_amdgcn_perm(w[1], w[0], 0x07060302u); p3[1] = __builtin_amdgcn_perm(w[3], w[2], 0x07060302u);
 }
 
 // A SECOND activation behind the first along K (TWO): out = act([A | A2'] * W^T + bias) with A2'[m] = the pixel of A2 that

@@ -21,7 +21,10 @@
 //     group is reloaded for the next chunk right after its last MFMA of this one;
 //   * output transform: A^T m A splits into the nu-sum (inside the owning wave, registers) and the xi-sum across the four
 //     waves through LDS (the staging buffers, reused), then bias / ReLU if asked and 256-B contiguous stores.
+#include <atomic>
+
 #include "common.hpp"
+#include "split_bf16.hpp"
 
 namespace opa {
 
@@ -489,6 +492,269 @@ __global__ __launch_bounds__(512, 1) void winograd_f23_w8_kernel(
     }
 }
 
+// ---- variant 4: variant 2 on the bf16 MFMA pipe with exactly split operands (the scheme of gemm_f32x3.hip).  The float32
+// MFMA runs at 1/16 of the bf16 rate; a float32 number is exactly the sum of three bf16 pieces, and the six leading of the nine
+// piece products (the three left out are below 2^-23 of the product each) cost 6 x v_mfma_f32_32x32x16_bf16 at 32 cycles
+// against 8 x v_mfma_f32_32x32x2f32 at 64 per 32x32x16 block: 0.375 of the MFMA cycles.  Everything but the products is
+// variant 2's (tile, shifts, staging, LDS layout, output transform).  The operand maps fit the bf16 MFMA as they are: lane l
+// (h = l / 32) of a 32x32x16 bf16 fragment holds virtual k' = 8 h + j, j = 0..7; variant 2's lane reads real k = 2 j + h
+// of the chunk (LDS rows 8 kq + 2 m + h) in its j = 4 kq + m-th float32 MFMA -- so the chunk is ONE bf16 K-step under the
+// permutation k' = 8 h + j <-> k = 2 j + h, applied to both operands alike.
+//   * V is split when its fragment is read from LDS (each element is read by one lane of one wave: split once);
+//   * U is split on the host (winograd.split_filter: [nb][chunk][position][j][piece][lane] x 16 B), 48 registers per wave;
+//   * ONE accumulator set: the leading product and then the five corrections (smallest first) go into `acc` -- a second set
+//     for the corrections, as gemm_f32x3.hip keeps, does not fit beside the 48 filter registers (128 more), and adding a zeroed
+//     block of corrections per K-step spilled (the register report of the build: 492 B per lane).  Six roundings per 16 k
+//     against the float32 MFMA's eight; the error against float64 is measured beside variant 2's
+//     (tests/test_gpu_winograd_x3.py, tools/gpu/winograd_x3_probe.py).
+// DIAG (timing experiments, wrong results; OPA_WINO_DIAG builds): 1 no split (the raw bits as every piece), 2 the leading
+// products only, 3 no pixel fetches and no transforms (MFMA + operand reads + split).
+template <int DIAG>
+__global__ __launch_bounds__(512, 1) void winograd_f23_w8x3_kernel(
+        const float* __restrict__ x, const unsigned short* __restrict__ U3, float* __restrict__ y, const float* __restrict__ bias,
+        int H, int W, int Cin, int Cout, int TH, int TW, int T, int relu, int nb_major) {
+    constexpr int KC = kW8KC, P = kW8P, NB = 2, BN = 64;
+    typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
+    typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
+    extern __shared__ __attribute__((aligned(16))) unsigned char wino_smem[];
+    float* const lds = reinterpret_cast<float*>(wino_smem);
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n_nb = Cout / BN;
+    const unsigned nwg = gridDim.x, xcd = blockIdx.x & 7u, in_xcd = blockIdx.x >> 3;
+    const unsigned q8 = nwg >> 3, r8 = nwg & 7u;
+    const unsigned logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + in_xcd;
+    const unsigned n_tb = nwg / (unsigned)n_nb;
+    const int tb = nb_major ? (int)(logical % n_tb) : (int)(logical / (unsigned)n_nb);
+    const int nb = nb_major ? (int)(logical / n_tb) : (int)(logical % (unsigned)n_nb);
+    const int nchunks = Cin / KC;
+
+    const int tile_l = tid >> 3, cg = tid & 7;
+    int t = tb * 64 + tile_l;
+    if (t > T - 1) t = T - 1;
+    const int tx = t % TW, ty = (t / TW) % TH, n = t / (TW * TH);
+    // byte offsets of the tile's four rows and four columns (clamped into the image).  The pixels come through buffer loads:
+    // descriptor and chunk offset in scalar registers, ONE 32-bit register per load, the row + column sum formed in the loop
+    // (kept opaque to the optimiser, which would otherwise hoist sixteen sums -- as 64-bit addresses of global loads they took
+    // 32 registers, which the split filter operand needs)
+    unsigned rowoff[4], coloff[4];
+    unsigned valid = 0u;                               // bit i * 4 + j: pixel (i, j) lies inside the image
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int r = 2 * ty - 1 + i, c = 2 * tx - 1 + i;
+        const int rc = r < 0 ? 0 : (r > H - 1 ? H - 1 : r), cc = c < 0 ? 0 : (c > W - 1 ? W - 1 : c);
+        rowoff[i] = (unsigned)((n * H + rc) * W) * (unsigned)Cin * 4u;
+        coloff[i] = ((unsigned)cc * (unsigned)Cin + (unsigned)(cg * 2)) * 4u;
+        if (r >= 0 && r < H) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int cj = 2 * tx - 1 + j;
+                if (cj >= 0 && cj < W) valid |= 1u << (i * 4 + j);
+            }
+        }
+    }
+    const bool wave_inside = __ballot(valid != 0xffffu) == 0ull;
+    // (the activation is below 2^30 elements -- the launcher checks -- and every offset is clamped into it)
+    const unsigned x_bytes = (unsigned)(T / (TH * TW)) * (unsigned)(H * W) * (unsigned)Cin * 4u;
+    const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, (int)x_bytes, 0x00020000);
+    float d[16][2];
+    auto fetch_x = [&](int chunk) {
+        unsigned ro[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) { ro[i] = rowoff[i]; asm volatile("" : "+v"(ro[i])); }
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+            const u32x2_t v = __builtin_bit_cast(u32x2_t, __builtin_amdgcn_raw_buffer_load_b64(x_rsrc, ro[k >> 2] + coloff[k & 3],
+                                                                                               chunk * KC * 4, 0));
+            d[k][0] = __uint_as_float(v[0]); d[k][1] = __uint_as_float(v[1]);
+        }
+    };
+    auto transform_store = [&](int buf) {
+        float* const vb = lds + buf * kW8VBUF + (cg * 2) * P + tile_l;
+        if (!wave_inside) {
+#pragma unroll
+            for (int k = 0; k < 16; k++)
+                if (!((valid >> k) & 1u)) { d[k][0] = 0.0f; d[k][1] = 0.0f; }
+        }
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            float s[16];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                s[0 * 4 + j] = d[0 * 4 + j][e] - d[2 * 4 + j][e];
+                s[1 * 4 + j] = d[1 * 4 + j][e] + d[2 * 4 + j][e];
+                s[2 * 4 + j] = d[2 * 4 + j][e] - d[1 * 4 + j][e];
+                s[3 * 4 + j] = d[1 * 4 + j][e] - d[3 * 4 + j][e];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                vb[((i * 4 + 0) * KC + e) * P] = s[i * 4 + 0] - s[i * 4 + 2];
+                vb[((i * 4 + 1) * KC + e) * P] = s[i * 4 + 1] + s[i * 4 + 2];
+                vb[((i * 4 + 2) * KC + e) * P] = s[i * 4 + 2] - s[i * 4 + 1];
+                vb[((i * 4 + 3) * KC + e) * P] = s[i * 4 + 1] - s[i * 4 + 3];
+            }
+        }
+    };
+
+    // filter operand: position pl = 0, 1 of this wave (2 * wave + pl), channel half j, piece q; reloaded for the next chunk
+    // behind the position's last MFMA
+    u32x4_t ub[2][NB][3];
+    const __amdgpu_buffer_rsrc_t u_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<unsigned short*>(U3 + (size_t)nb * nchunks * (16 * NB * 3 * 64 * 8)), 0, nchunks * (16 * NB * 3 * 64 * 16), 0x00020000);
+    const unsigned u_lane = (unsigned)lane * 16u;
+    const int wave_s = __builtin_amdgcn_readfirstlane(wave);     // (uniform: the scalar offset of the filter loads)
+    auto u_load = [&](int chunk, int pl, int j, int q) {
+        return __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(
+            u_rsrc, u_lane, ((((chunk * 16 + wave_s * 2 + pl) * NB + j) * 3 + q) * 64) * 16, 0));
+    };
+    wf32x16_t acc[2][2][NB];
+#pragma unroll
+    for (int pl = 0; pl < 2; pl++)
+#pragma unroll
+        for (int i = 0; i < 2; i++)
+#pragma unroll
+            for (int j = 0; j < NB; j++)
+#pragma unroll
+                for (int r = 0; r < 16; r++) acc[pl][i][j][r] = 0.0f;
+
+    const int a_lane = (lane >> 5) * P + (lane & 31) + (wave * 2 * KC) * P;
+    auto mfma_phase = [&](int chunk, int nxt) {
+        const float* const vb = lds + (chunk & 1) * kW8VBUF + a_lane;
+#pragma unroll
+        for (int pl = 0; pl < 2; pl++) {
+            const float* const vp = vb + (pl * KC) * P;
+#pragma unroll
+            for (int i = 0; i < 2; i++) {
+                __builtin_amdgcn_sched_barrier(0);
+                // fragment element j = 4 kq + m <- LDS row 8 kq + 2 m + h (= real k 2 j + h), tile 32 i + lane % 32
+                wf32x4_t lo, hi;
+#pragma unroll
+                for (int m = 0; m < 4; m++) { lo[m] = vp[(2 * m) * P + 32 * i]; hi[m] = vp[(8 + 2 * m) * P + 32 * i]; }
+                u32x2_t l1, l2, l3, h1, h2, h3;
+                if (DIAG == 1) {
+                    l1[0] = __float_as_uint(lo[0]); l1[1] = __float_as_uint(lo[2]); h1[0] = __float_as_uint(hi[0]); h1[1] = __float_as_uint(hi[2]);
+                    l2 = l1; l3 = l1; h2 = h1; h3 = h1;
+                } else {
+                    split4(lo, l1, l2, l3);
+                    split4(hi, h1, h2, h3);
+                }
+                const bf16x8_t a[3] = {__builtin_bit_cast(bf16x8_t, (u32x4_t){l1[0], l1[1], h1[0], h1[1]}),
+                                       __builtin_bit_cast(bf16x8_t, (u32x4_t){l2[0], l2[1], h2[0], h2[1]}),
+                                       __builtin_bit_cast(bf16x8_t, (u32x4_t){l3[0], l3[1], h3[0], h3[1]})};
+#pragma unroll
+                for (int j = 0; j < NB; j++) {
+                    const bf16x8_t b[3] = {__builtin_bit_cast(bf16x8_t, ub[pl][j][0]), __builtin_bit_cast(bf16x8_t, ub[pl][j][1]),
+                                           __builtin_bit_cast(bf16x8_t, ub[pl][j][2])};
+                    // the leading product, then the corrections smallest first, all into `acc` (see the header)
+                    acc[pl][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc[pl][i][j], 0, 0, 0);
+                    if (DIAG == 2) continue;
+                    acc[pl][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], acc[pl][i][j], 0, 0, 0);
+                    acc[pl][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], acc[pl][i][j], 0, 0, 0);
+                    acc[pl][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], acc[pl][i][j], 0, 0, 0);
+                    acc[pl][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], acc[pl][i][j], 0, 0, 0);
+                    acc[pl][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc[pl][i][j], 0, 0, 0);
+                }
+            }
+            if (DIAG != 3) {
+#pragma unroll
+                for (int j = 0; j < NB; j++)
+#pragma unroll
+                    for (int q = 0; q < 3; q++) ub[pl][j][q] = u_load(nxt, pl, j, q);
+            }
+        }
+    };
+
+    // prologue and the two shifts exactly as variant 2
+    const int last = nchunks - 1;
+    fetch_x(0);
+    transform_store(0);
+    __builtin_amdgcn_sched_barrier(0);
+    if (wave >= 4) fetch_x(nchunks > 1 ? 1 : 0);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int pl = 0; pl < 2; pl++)
+#pragma unroll
+        for (int j = 0; j < NB; j++)
+#pragma unroll
+            for (int q = 0; q < 3; q++) ub[pl][j][q] = u_load(0, pl, j, q);
+    __builtin_amdgcn_sched_barrier(0);
+    if (wave < 4) {
+        __syncthreads();
+        for (int chunk = 0; chunk < nchunks; chunk++) {
+            const int nxt = chunk < last ? chunk + 1 : last;
+            if (DIAG != 3) fetch_x(nxt);
+            __builtin_amdgcn_sched_barrier(0);
+            mfma_phase(chunk, nxt);
+            __builtin_amdgcn_sched_barrier(0);
+            if (DIAG != 3) transform_store((chunk + 1) & 1);
+            __syncthreads();
+        }
+    } else {
+        __syncthreads();
+        for (int chunk = 0; chunk < nchunks; chunk++) {
+            const int nxt = chunk < last ? chunk + 1 : last;
+            if (DIAG != 3) transform_store((chunk + 1) & 1);
+            __builtin_amdgcn_sched_barrier(0);
+            if (DIAG != 3) fetch_x(chunk + 2 < nchunks ? chunk + 2 : last);
+            __builtin_amdgcn_sched_barrier(0);
+            mfma_phase(chunk, nxt);
+            __syncthreads();
+        }
+    }
+
+    // ---- output transform (variant 2's)
+    const int h = wave & 1;
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        float* const sw = lds + wave * (2 * 32 * BN);
+#pragma unroll
+        for (int j = 0; j < NB; j++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int tile = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                const int col = j * 32 + (lane & 31);
+                const float ma = acc[0][i][j][r], mb = acc[1][i][j][r];
+                sw[tile * BN + col] = h == 0 ? ma + mb : ma;
+                sw[32 * BN + tile * BN + col] = h == 0 ? mb : -(ma + mb);
+            }
+        __syncthreads();
+        {
+            const int tile = tid >> 4, c4 = (tid & 15) * 4;
+            const int tt = tb * 64 + i * 32 + tile;
+            if (tt < T) {
+                const int ox = tt % TW, oy = (tt / TW) % TH, on = tt / (TW * TH);
+                wf32x4_t pq[4][2];
+#pragma unroll
+                for (int xi = 0; xi < 4; xi++)
+#pragma unroll
+                    for (int jj = 0; jj < 2; jj++)
+                        pq[xi][jj] = *reinterpret_cast<const wf32x4_t*>(lds + ((2 * xi) * 2 + jj) * (32 * BN) + tile * BN + c4) +
+                                     *reinterpret_cast<const wf32x4_t*>(lds + ((2 * xi + 1) * 2 + jj) * (32 * BN) + tile * BN + c4);
+                wf32x4_t bv = {0.f, 0.f, 0.f, 0.f};
+                if (bias) bv = *reinterpret_cast<const wf32x4_t*>(bias + nb * BN + c4);
+#pragma unroll
+                for (int a = 0; a < 2; a++) {
+                    const int oh = 2 * oy + a;
+                    if (oh >= H) continue;
+#pragma unroll
+                    for (int jj = 0; jj < 2; jj++) {
+                        const int ow = 2 * ox + jj;
+                        if (ow >= W) continue;
+                        wf32x4_t v = a == 0 ? (pq[0][jj] + pq[1][jj]) + pq[2][jj] : (pq[1][jj] - pq[2][jj]) - pq[3][jj];
+                        v += bv;
+                        if (relu) {
+#pragma unroll
+                            for (int e = 0; e < 4; e++) v[e] = fmaxf(v[e], 0.0f);
+                        }
+                        *reinterpret_cast<wf32x4_t*>(y + ((size_t)(on * H + oh) * W + ow) * Cout + nb * BN + c4) = v;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
 // ---- variant 3: variant 2 as PERSISTENT workgroups.  With one workgroup per compute unit nothing overlaps a workgroup's
 // prologue (the first pixels come from HBM: 2-3 us) -- a third of a workgroup's time at 64 input channels.  Here a workgroup
 // walks tile blocks tb, tb + G, ... of ONE channel block, and during a block's LAST chunk both shifts fetch the first chunk
@@ -731,26 +997,39 @@ __global__ __launch_bounds__(512, 1) void winograd_f23_w8p_kernel(
     }
 }
 
+// hipFuncSetAttribute holds per device: the 132 KB of dynamic LDS are allowed once per (kernel, device); `done` is the kernel's
+// bit set of devices
+static hipError_t allow_lds(const void* fn, int bytes, std::atomic<unsigned long long>& done) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const unsigned long long bit = dev >= 0 && dev < 64 ? 1ull << dev : 0ull;
+    if (bit && (done.load(std::memory_order_relaxed) & bit)) return hipSuccess;
+    e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) done.fetch_or(bit, std::memory_order_relaxed);
+    return e;
+}
+
 static hipError_t launch_wino_w8p(const float* x, const float* U, float* y, const float* bias, int N, int H, int W, int Cin,
                                   int Cout, int relu, hipStream_t st) {
     const int TH = (H + 1) / 2, TW = (W + 1) / 2, T = N * TH * TW;
     const int n_tb = (T + 63) / 64, n_nb = Cout / 64;
-    static int cus = 0;
+    static std::atomic<int> cus_of[64];                // compute units of each device, asked once
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    int cus = dev >= 0 && dev < 64 ? cus_of[dev].load(std::memory_order_relaxed) : 0;
     if (!cus) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipGetLastError();
-        cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+        int v = 0;
+        cus = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0 ? v : 256;
+        if (dev >= 0 && dev < 64) cus_of[dev].store(cus, std::memory_order_relaxed);
     }
     int G = cus / n_nb;                                // workgroups per channel block: one workgroup per compute unit in all
     if (G < 1) G = 1;
     if (G > n_tb) G = n_tb;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&winograd_f23_w8p_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kW8LdsBytes);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    static std::atomic<unsigned long long> lds_set{0};
+    e = allow_lds(reinterpret_cast<const void*>(&winograd_f23_w8p_kernel), kW8LdsBytes, lds_set);
+    if (e != hipSuccess) return e;
     winograd_f23_w8p_kernel<<<(unsigned)(G * n_nb), 512, kW8LdsBytes, st>>>(x, U, y, bias, H, W, Cin, Cout, TH, TW, T, relu, n_tb, G);
     return hipGetLastError();
 }
@@ -760,14 +1039,23 @@ static hipError_t launch_wino_w8(const float* x, const float* U, float* y, const
                                  int Cout, int relu, int nb_major, hipStream_t st) {
     const int TH = (H + 1) / 2, TW = (W + 1) / 2, T = N * TH * TW;
     const long long blocks = (long long)((T + 63) / 64) * (Cout / 64);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&winograd_f23_w8_kernel<DIAG>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kW8LdsBytes);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    static std::atomic<unsigned long long> lds_set{0};
+    hipError_t e = allow_lds(reinterpret_cast<const void*>(&winograd_f23_w8_kernel<DIAG>), kW8LdsBytes, lds_set);
+    if (e != hipSuccess) return e;
     winograd_f23_w8_kernel<DIAG><<<(unsigned)blocks, 512, kW8LdsBytes, st>>>(x, U, y, bias, H, W, Cin, Cout, TH, TW, T, relu, nb_major);
+    return hipGetLastError();
+}
+
+template <int DIAG>
+static hipError_t launch_wino_w8x3(const float* x, const unsigned short* U3, float* y, const float* bias, int N, int H, int W,
+                                   int Cin, int Cout, int relu, int nb_major, hipStream_t st) {
+    const int TH = (H + 1) / 2, TW = (W + 1) / 2, T = N * TH * TW;
+    const long long blocks = (long long)((T + 63) / 64) * (Cout / 64);
+    static std::atomic<unsigned long long> lds_set{0};
+    hipError_t e = allow_lds(reinterpret_cast<const void*>(&winograd_f23_w8x3_kernel<DIAG>), kW8LdsBytes, lds_set);
+    if (e != hipSuccess) return e;
+    winograd_f23_w8x3_kernel<DIAG><<<(unsigned)blocks, 512, kW8LdsBytes, st>>>(x, U3, y, bias, H, W, Cin, Cout, TH, TW, T, relu,
+                                                                                nb_major);
     return hipGetLastError();
 }
 
@@ -777,13 +1065,9 @@ static hipError_t launch_wino(const float* x, const float* U, float* y, const fl
     using C = WinoCfg<KC, NB>;
     const int TH = (H + 1) / 2, TW = (W + 1) / 2, T = N * TH * TW;
     const long long blocks = (long long)((T + 63) / 64) * (Cout / C::BN);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&winograd_f23_kernel<KC, NB, WGS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    static std::atomic<unsigned long long> lds_set{0};
+    hipError_t e = allow_lds(reinterpret_cast<const void*>(&winograd_f23_kernel<KC, NB, WGS>), C::LDS_BYTES, lds_set);
+    if (e != hipSuccess) return e;
     winograd_f23_kernel<KC, NB, WGS><<<(unsigned)blocks, 256, C::LDS_BYTES, st>>>(x, U, y, bias, H, W, Cin, Cout, TH, TW, T,
                                                                                   relu, nb_major);
     return hipGetLastError();
@@ -791,11 +1075,13 @@ static hipError_t launch_wino(const float* x, const float* U, float* y, const fl
 
 // variant 0: 64 tiles x 64 channels, K-chunks of 16, one workgroup per compute unit (256 accumulator registers per lane);
 // variant 1: 64 tiles x 32 channels, K-chunks of 8, two workgroups per compute unit;
-// variant 2: variant 0's tile and filter layout, eight waves in two shifts (openpifpaf_amd.winograd.DEFAULT_VARIANT);
+// variant 2: variant 0's tile and filter layout, eight waves in two shifts;
 // variant 3: variant 2 as persistent workgroups.  The filter layout depends on the variant (0, 2, 3 share one).
+// Any other variant (variant 4 included: its filter is not float32) is refused.
 hipError_t launch_winograd_f23(const float* x, const float* U, float* y, const float* bias, int N, int H, int W, int Cin,
                                int Cout, int relu, int variant, int nb_major, hipStream_t st) {
     if (variant == 0) return launch_wino<16, 2, 1>(x, U, y, bias, N, H, W, Cin, Cout, relu, nb_major, st);
+    if (variant == 1) return launch_wino<8, 1, 2>(x, U, y, bias, N, H, W, Cin, Cout, relu, nb_major, st);
     if (variant == 2) return launch_wino_w8<0>(x, U, y, bias, N, H, W, Cin, Cout, relu, nb_major, st);
     if (variant == 3) return launch_wino_w8p(x, U, y, bias, N, H, W, Cin, Cout, relu, st);
 #ifdef OPA_WINO_DIAG          // timing experiments (wrong results): without the filter reloads / pixel fetches / transforms
@@ -808,7 +1094,20 @@ hipError_t launch_winograd_f23(const float* x, const float* U, float* y, const f
     if (variant == 17) return launch_wino_w8<7>(x, U, y, bias, N, H, W, Cin, Cout, relu, nb_major, st);
     if (variant == 18) return launch_wino_w8<8>(x, U, y, bias, N, H, W, Cin, Cout, relu, nb_major, st);
 #endif
-    return launch_wino<8, 1, 2>(x, U, y, bias, N, H, W, Cin, Cout, relu, nb_major, st);
+    return hipErrorInvalidValue;
+}
+
+// variant 4: variant 2 on the bf16 MFMA pipe, U3 = the three bf16 planes of the filter (openpifpaf_amd.winograd.split_filter).
+// Any other variant is refused (21-23: variant 4's timing experiments, OPA_WINO_DIAG builds only).
+hipError_t launch_winograd_f23x3(const float* x, const unsigned short* U3, float* y, const float* bias, int N, int H, int W,
+                                 int Cin, int Cout, int relu, int variant, int nb_major, hipStream_t st) {
+    if (variant == 4) return launch_wino_w8x3<0>(x, U3, y, bias, N, H, W, Cin, Cout, relu, nb_major, st);
+#ifdef OPA_WINO_DIAG
+    if (variant == 21) return launch_wino_w8x3<1>(x, U3, y, bias, N, H, W, Cin, Cout, relu, nb_major, st);
+    if (variant == 22) return launch_wino_w8x3<2>(x, U3, y, bias, N, H, W, Cin, Cout, relu, nb_major, st);
+    if (variant == 23) return launch_wino_w8x3<3>(x, U3, y, bias, N, H, W, Cin, Cout, relu, nb_major, st);
+#endif
+    return hipErrorInvalidValue;
 }
 
 }  // namespace opa

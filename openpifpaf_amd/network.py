@@ -69,7 +69,7 @@ class _Bottleneck(nn.Module):
             u = getattr(self, 'wino_u', None)
             wino = winograd.takes(self.conv2, out, u)
             if wino:
-                out = winograd.conv3x3(out, u, self.conv2.out_channels, bias=self.fb2, relu=True, variant=winograd.DEFAULT_VARIANT)
+                out = winograd.run(self.conv2, out, u, bias=self.fb2, relu=True)
             elif fused.conv3x3_x3_supported(self.conv2, out, self.fb2):  # ... float32 strided: implicit GEMM of the split-operand kernel
                 h = out                                                   # (or MIOpen + the epilogue pass, whichever is faster for the shape)
                 s = self.conv2.stride[0]
@@ -127,7 +127,7 @@ class _BasicBlock(nn.Module):
             identity = x if self.downsample is None else self.downsample[0](x)
             u1, u2 = getattr(self, 'wino_u1', None), getattr(self, 'wino_u2', None)
             if winograd.takes(self.conv1, x, u1):             # bias + ReLU in the kernel's output transform
-                out = winograd.conv3x3(x, u1, self.conv1.out_channels, bias=self.fb1, relu=True, variant=winograd.DEFAULT_VARIANT)
+                out = winograd.run(self.conv1, x, u1, bias=self.fb1, relu=True)
             else:
                 out = fused.bias_act_(self.conv1(x), self.fb1)
             return fused.bias_act_(winograd.conv_or_fallback(self.conv2, out, u2), self.fb2, identity)

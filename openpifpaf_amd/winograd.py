@@ -13,8 +13,12 @@ import torch
 from . import _lib
 
 # variant -> (K-chunk, 32-wide channel blocks per workgroup): must match launch_winograd_f23 (csrc/winograd.hip)
-VARIANTS = {0: (16, 2), 1: (8, 1), 2: (16, 2), 3: (16, 2)}     # 2: variant 0's tile and filter layout, eight waves in two shifts
+VARIANTS = {0: (16, 2), 1: (8, 1), 2: (16, 2), 3: (16, 2), 4: (16, 2)}     # 2: variant 0's tile and filter layout, eight waves
 DEFAULT_VARIANT = 2         # eight waves in two shifts (csrc/winograd.hip): 5-8 % faster than variant 0 on every ResNet-50 shape
+X3_VARIANT = 4              # variant 2 on the bf16 MFMA pipe with exactly split operands (opa_conv3x3_winograd_f32x3)
+# OPA_WINO_X3=0: the network's Winograd convolutions stay on variant 2 (float32 MFMA) -- read ONCE, at import; the two round
+# differently, so it is a switch for a whole job, never a per-call choice
+X3 = os.environ.get('OPA_WINO_X3', '1') != '0'
 MIN_WORKGROUPS = 256        # below one workgroup per compute unit the launch does not fill the chip: MIOpen's convolution
 _G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
 
@@ -54,10 +58,18 @@ def takes(conv, x, u, variant=DEFAULT_VARIANT):
             and not (torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad)))
 
 
+def run(conv, x, u, bias=None, relu=False):
+    """``conv(x)`` (+ bias, ReLU) through the kernel, where :func:`takes` holds: variant 4 on the split planes of the CURRENT
+    ``conv.weight`` (:func:`split_filter_of`), or variant 2 on ``u`` with ``OPA_WINO_X3=0``."""
+    if X3:
+        return conv3x3_x3(x, split_filter_of(conv), conv.out_channels, bias=bias, relu=relu)
+    return conv3x3(x, u, conv.out_channels, bias=bias, relu=relu, variant=DEFAULT_VARIANT)
+
+
 def conv_or_fallback(conv, x, u, variant=DEFAULT_VARIANT):
     """``conv(x)``: through the kernel where :func:`takes` says so, else the module itself (MIOpen)."""
     if takes(conv, x, u, variant):
-        return conv3x3(x, u, conv.out_channels, variant=variant)
+        return run(conv, x, u)
     return conv(x)
 
 
@@ -68,7 +80,7 @@ def supported(x, weight, variant=0, stride=(1, 1), padding=(1, 1), groups=1, dil
             and groups == 1 and tuple(dilation) == (1, 1) and weight.shape[1] == x.shape[1]
             and x.is_contiguous(memory_format=torch.channels_last)
             and weight.shape[1] % kc == 0 and weight.shape[0] % (32 * nb) == 0
-            and x.numel() < 2 ** 32 and x.data_ptr() % 16 == 0 and _lib.available())
+            and x.numel() < 2 ** 30 and x.data_ptr() % 16 == 0 and _lib.available())     # (32-bit byte offsets)
 
 
 def transform_filter(weight, variant=0):
@@ -84,6 +96,33 @@ def transform_filter(weight, variant=0):
     u = u.reshape(16, cin // kc, kc // 8, 4, 2, cout // (32 * nb), nb, 32)      # [pos, chunk, kq, e, khalf, block, j, c]
     u = u.permute(5, 1, 0, 6, 2, 4, 7, 3)                                       # [block, chunk, pos, j, kq, khalf, c, e]
     return u.contiguous().float().reshape(-1)
+
+
+def split_filter(weight):
+    """``[C_out, C_in, 3, 3]`` -> the operand of variant 4: ``U = transform_filter(weight, 2)`` (the same float32 numbers variant 2
+    multiplies) cut exactly into three bfloat16 planes (``fused.split_weight``: ``u1 + u2 + u3 == U`` bit for bit), laid out
+    ``[channel block][K-chunk][position 16][j][piece 3][lane 64][8]``: element ``e`` of lane ``l`` is piece ``q`` of
+    ``U[k = 2 e + l // 32][c = 32 j + l % 32]`` of the chunk -- the bf16 fragment of virtual k' = 8 (l // 32) + e, i.e. the chunk's
+    K permutation k' = 8 h + e <-> k = 2 e + h, which the kernel applies to the pixel operand alike.  A wave's load of one piece
+    is 1 KB contiguous."""
+    from . import fused
+    cout, cin = weight.shape[:2]
+    u = transform_filter(weight, DEFAULT_VARIANT)
+    u = u.reshape(cout // 64, cin // 16, 16, 2, 2, 64, 4).permute(0, 1, 2, 3, 5, 4, 6)    # [.., j, kq, lane, e] -> [.., j, lane, kq, e]
+    planes = fused.split_weight(u)                                                       # [3, block, chunk, pos, j, lane, kq, e]
+    return planes.permute(1, 2, 3, 4, 0, 5, 6, 7).contiguous().reshape(-1)
+
+
+def split_filter_of(conv):
+    """``split_filter(conv.weight)``, kept on the module and computed again whenever the weight was replaced, moved or changed in
+    place (``load_state_dict`` into an optimized network): the key is (data pointer, version counter, device)."""
+    w = conv.weight
+    key = (w.data_ptr(), w._version, str(w.device))
+    cached = getattr(conv, '_opa_wino_u3', None)
+    if cached is None or cached[0] != key:
+        cached = (key, split_filter(w))
+        conv._opa_wino_u3 = cached
+    return cached[1]
 
 
 # direct-convolution flops of the launches that went through the kernel since the last reset: a measurement (bench.py) that
@@ -115,6 +154,21 @@ def conv3x3(x, u, c_out, bias=None, relu=False, variant=0, order=0, out=None):
         ctypes.c_void_p(bias.data_ptr()) if bias is not None else None, ctypes.c_void_p(out.data_ptr()),
         B, H, W, cin, c_out, int(bool(relu)), variant, order,
         ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_conv3x3_winograd_f32')
+    return out
+
+
+def conv3x3_x3(x, u3, c_out, bias=None, relu=False, variant=X3_VARIANT, order=0, out=None):
+    """:func:`conv3x3` through variant 4 (bf16 MFMA pipe, exactly split operands) for ``u3 = split_filter(weight)``."""
+    global _direct_flops
+    B, cin, H, W = x.shape
+    _direct_flops += 18.0 * B * H * W * cin * c_out
+    if out is None:
+        out = torch.empty((B, c_out, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    _lib.check(_lib.lib().opa_conv3x3_winograd_f32x3(
+        ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(u3.data_ptr()),
+        ctypes.c_void_p(bias.data_ptr()) if bias is not None else None, ctypes.c_void_p(out.data_ptr()),
+        B, H, W, cin, c_out, int(bool(relu)), variant, order,
+        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_conv3x3_winograd_f32x3')
     return out
 
 
