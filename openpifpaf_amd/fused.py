@@ -142,26 +142,37 @@ def _x3_supported(x, weight):
     return X3_TERMS in (6, 9) and x.dtype == torch.float32 and weight.shape[1] % 64 == 0
 
 
-def _split_weight_of(conv, w2d):
-    """``split_weight(w2d)``, computed once per convolution and kept on the module (inference: the weight does not change; a weight
-    replaced or moved since is split again)."""
-    key = (w2d.data_ptr(), w2d._version, str(w2d.device))
-    cached = getattr(conv, '_opa_w3', None)
+def derived(module, name, sources, make):
+    """``make()`` -- an operand derived from the tensors ``sources`` (parameters, buffers; None where there is none) -- computed
+    once, kept on ``module`` as attribute ``name`` and computed again whenever a source was replaced, moved, converted or changed
+    in place (``load_state_dict``, ``.to()``, an optimizer step): the key is (data pointer, version counter, device, dtype) of each.
+    The entry holds on to the sources' storages, so that no later tensor can be handed the same address while it is the key."""
+    key = tuple(None if t is None else (t.data_ptr(), t._version, str(t.device), t.dtype) for t in sources)
+    cached = getattr(module, name, None)
     if cached is None or cached[0] != key:
-        cached = (key, split_weight(w2d))
-        conv._opa_w3 = cached
+        cached = (key, make(), [t.untyped_storage() for t in sources if t is not None])
+        setattr(module, name, cached)
     return cached[1]
+
+
+def _split_weight_of(conv, w2d):
+    """``split_weight(w2d)`` for ``w2d``, the ``[N, K]`` view of ``conv.weight``: computed once per convolution and kept on the module
+    (inference: the weight does not change; a weight replaced, moved or changed since is split again)."""
+    return derived(conv, '_opa_w3', (conv.weight,), lambda: split_weight(w2d))
 
 
 FORCE_PICK = os.environ.get('OPA_GEMM3_PICK') or None        # 'x3' | 'conv': every pick() takes that side (tests, A/B)
 
 
-def pick(kind, m, k, n, flag_a, flag_b, run_x3, run_other):
+def pick(kind, m, k, n, flag_a, flag_b, run_x3, run_other, written=None):
     """One of two ways to compute the same tensor -- a split-operand kernel (``run_x3``) or what the trunk did before
     (``run_other``: MIOpen's convolution + the fused passes) -- chosen ONCE per shape like ``conv_bias_act`` chooses its GEMM: from
     the shipped table (``conv1x1_pinned.json``, key dtype ``'torch.float32/<kind>'``), else by timing both on the first call; while
     a stream is being captured or in a job of several ranks, where timing is not an option, by size (the split-operand kernels win
-    from ~16 000 output pixels: a batch of one 641-px image keeps MIOpen in layers 3-4).  Returns the chosen function's result."""
+    from ~16 000 output pixels: a batch of one 641-px image keeps MIOpen in layers 3-4).  Returns the chosen function's result.
+    ``written``: an operand that ``run_other`` changes in place (the epilogue its producer left to this consumer); timing calls
+    ``run_other`` several times, so the operand is saved before and put back after -- the winner computes from what the caller
+    passed, whoever wins."""
     if FORCE_PICK in ('x3', 'conv'):
         return run_x3() if FORCE_PICK == 'x3' else run_other()
     key = ('torch.float32/' + kind, int(m), int(k), int(n), bool(flag_a), bool(flag_b))
@@ -170,7 +181,10 @@ def pick(kind, m, k, n, flag_a, flag_b, run_x3, run_other):
         if torch.cuda.is_current_stream_capturing() or _in_multi_rank_job():
             choice = 'x3' if m >= 16384 else 'conv'
         else:
+            saved = written.clone() if written is not None else None
             choice = 'x3' if _time_ms(run_x3) <= _time_ms(run_other) else 'conv'
+            if saved is not None:
+                written.copy_(saved)
         _CHOICE[key] = choice
     return run_x3() if choice == 'x3' else run_other()
 
@@ -201,6 +215,18 @@ def pair_supported(conv, dconv, h, x, bias, a_bias=None):
     return a_bias is None or (a_bias.dtype == torch.float32 and a_bias.numel() == k1 and a_bias.is_contiguous())
 
 
+def _pair_weight_of(conv, dconv, a_bias=None):
+    """The operands of ``conv1x1_pair_bias_act_x3`` derived from the current parameters: ``split_weight([W | Wd])`` and ``a_bias``
+    followed by zeros for ``dconv``'s channels (None without ``a_bias``) -- kept on ``conv`` like ``_split_weight_of``."""
+    k1, k2, n = conv.in_channels, dconv.in_channels, conv.out_channels
+
+    def make():
+        w1, w2 = conv.weight.detach().reshape(n, k1), dconv.weight.detach().reshape(n, k2)
+        ab = None if a_bias is None else torch.cat((a_bias.detach().float(), torch.zeros(k2, device=a_bias.device)))
+        return split_weight(torch.cat((w1, w2), dim=1)), ab
+    return derived(conv, '_opa_w3_pair', (conv.weight, dconv.weight, a_bias), make)
+
+
 def conv1x1_pair_bias_act_x3(conv, dconv, h, x, bias, relu=True, a_bias=None):
     """``act(conv(h) + dconv(x) + bias)`` -- the last 1x1 convolution of a ResNet block and the block's downsampling convolution
     (reference ``network/basenetworks.py:71-150``: torchvision's Bottleneck) -- as ONE product ``[h | x at stride] * [W ; Wd]^T`` of
@@ -208,14 +234,7 @@ def conv1x1_pair_bias_act_x3(conv, dconv, h, x, bias, relu=True, a_bias=None):
     ``a_bias``, ``h`` is the raw output of the preceding convolution and ``relu(h + a_bias)`` is applied while it is staged (``x``
     gets zeros: it is non-negative).  ``pair_supported`` says whether this can run."""
     k1, k2, n = conv.in_channels, dconv.in_channels, conv.out_channels
-    w1, w2 = conv.weight.reshape(n, k1), dconv.weight.reshape(n, k2)
-    key = (w1.data_ptr(), w1._version, w2.data_ptr(), w2._version, str(w1.device), None if a_bias is None else (a_bias.data_ptr(), a_bias._version))
-    cached = getattr(conv, '_opa_w3_pair', None)
-    if cached is None or cached[0] != key:
-        ab = None if a_bias is None else torch.cat((a_bias.detach().float(), torch.zeros(k2, device=a_bias.device)))
-        cached = (key, split_weight(torch.cat((w1.detach(), w2.detach()), dim=1)), ab)
-        conv._opa_w3_pair = cached
-    _, w3, ab = cached
+    w3, ab = _pair_weight_of(conv, dconv, a_bias)
     B, _, H, W = x.shape
     out = torch.empty((B, n, h.shape[2], h.shape[3]), dtype=torch.float32, device=h.device, memory_format=torch.channels_last)
     _lib.check(_lib.lib().opa_gemm2_bias_act_f32x3(
@@ -245,21 +264,21 @@ def conv3x3_x3_supported(conv, x, bias):
             and (x.shape[0] * x.shape[2] * x.shape[3] + x.shape[3] + 1) * x.shape[1] * 4 < 2 ** 31)
 
 
+def _split_weight_3x3_of(conv):
+    """``split_weight_3x3(conv.weight)``, kept on the module like ``_split_weight_of``."""
+    return derived(conv, '_opa_w3_3x3', (conv.weight,), lambda: split_weight_3x3(conv.weight))
+
+
 def conv3x3_bias_act_x3(conv, x, bias, relu=True):
     """``act(conv(x) + bias)`` for a 3x3 convolution with padding 1 and any stride (reference ``network/basenetworks.py:71-150``: the
     strided convolution of a ResNet block) as an implicit GEMM of the split-operand kernel -- float32 in and out."""
-    w = conv.weight
-    key = (w.data_ptr(), w._version, str(w.device))
-    cached = getattr(conv, '_opa_w3_3x3', None)
-    if cached is None or cached[0] != key:
-        cached = (key, split_weight_3x3(w))
-        conv._opa_w3_3x3 = cached
+    w3 = _split_weight_3x3_of(conv)
     B, C, H, W = x.shape
     s = conv.stride[0]
     out = torch.empty((B, conv.out_channels, (H - 1) // s + 1, (W - 1) // s + 1), dtype=torch.float32, device=x.device,
                       memory_format=torch.channels_last)
     _lib.check(_lib.lib().opa_conv3x3_f32x3(
-        ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(cached[1].data_ptr()), ctypes.c_void_p(bias.data_ptr()),
+        ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(w3.data_ptr()), ctypes.c_void_p(bias.data_ptr()),
         ctypes.c_void_p(out.data_ptr()), B, H, W, C, conv.out_channels, s, int(bool(relu)), int(X3_TERMS),
         ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_conv3x3_f32x3')
     return out
@@ -276,25 +295,31 @@ def head_conv_x3_supported(conv, x):
             and conv.weight.dtype == torch.float32 and x.data_ptr() % 16 == 0)
 
 
-def head_conv_x3(conv, x):
-    """``conv(x)`` for a head's biased 1x1 convolution (reference ``network/heads.py:272-378``: ``CompositeField4.conv``) through the
-    split-operand GEMM: the output channels are padded to the next multiple of 64 with zero weights, the product is written with
-    that pitch and the real channels are copied out (0.2 GB for both COCO heads at batch 32)."""
-    w = conv.weight
-    n, k = w.shape[0], w.shape[1]
-    npad = (n + 63) // 64 * 64
-    key = (w.data_ptr(), w._version, str(w.device), None if conv.bias is None else conv.bias._version)
-    cached = getattr(conv, '_opa_w3_head', None)
-    if cached is None or cached[0] != key:
+def _head_weight_of(conv):
+    """The operands of ``head_conv_x3`` derived from the current parameters: ``split_weight`` of the weight padded with zero rows
+    to the next multiple of 64 output channels, and the bias padded alike (zeros without one) -- kept on the module like
+    ``_split_weight_of``; the key holds the bias tensor too (a bias REPLACED by a new Parameter is a new operand)."""
+    def make():
+        w = conv.weight
+        n, k = w.shape[0], w.shape[1]
+        npad = (n + 63) // 64 * 64
         wp = torch.zeros((npad, k), dtype=torch.float32, device=w.device)
         wp[:n] = w.detach().reshape(n, k)
         bp = torch.zeros(npad, dtype=torch.float32, device=w.device)
         if conv.bias is not None:
             bp[:n] = conv.bias.detach()
-        cached = (key, split_weight(wp), bp)
-        conv._opa_w3_head = cached
-    out = conv1x1_bias_act_x3(x, cached[1], cached[2], None, False, None, X3_TERMS)
-    return out[:, :n].contiguous(memory_format=torch.channels_last) if npad != n else out
+        return split_weight(wp), bp
+    return derived(conv, '_opa_w3_head', (conv.weight, conv.bias), make)
+
+
+def head_conv_x3(conv, x):
+    """``conv(x)`` for a head's biased 1x1 convolution (reference ``network/heads.py:272-378``: ``CompositeField4.conv``) through the
+    split-operand GEMM: the output channels are padded to the next multiple of 64 with zero weights, the product is written with
+    that pitch and the real channels are copied out (0.2 GB for both COCO heads at batch 32)."""
+    n = conv.out_channels
+    w3, bp = _head_weight_of(conv)
+    out = conv1x1_bias_act_x3(x, w3, bp, None, False, None, X3_TERMS)
+    return out[:, :n].contiguous(memory_format=torch.channels_last) if w3.shape[1] != n else out
 
 
 # ... and the 7x7 stride-2 stem (OPA_GEMM3_STEM=0: off)
@@ -309,26 +334,30 @@ def stem_x3_supported(conv, x, bias):
             and x.shape[0] * (x.shape[2] + 7) * (x.shape[3] + 7) * 16 < 2 ** 31)
 
 
+def _stem_weight_of(conv):
+    """The weight operand of ``stem7x7_bias_act_x3`` derived from the current ``conv.weight``: ``[N, 7, 7, 3]`` padded with zeros to
+    ``[N, 8, 8, 4]`` and split -- kept on the module like ``_split_weight_of``."""
+    def make():
+        w = conv.weight
+        n = w.shape[0]
+        wp = torch.zeros((n, 8, 8, 4), dtype=torch.float32, device=w.device)
+        wp[:, :7, :7, :3] = w.detach().permute(0, 2, 3, 1)
+        return split_weight(wp.reshape(n, 256))
+    return derived(conv, '_opa_w3_stem', (conv.weight,), make)
+
+
 def stem7x7_bias_act_x3(conv, x, bias, relu=True):
     """``act(conv(x) + bias)`` for the 7x7 stride-2 padding-3 stem of a ResNet on RGB input (reference ``network/basenetworks.py:71-150``)
     as an implicit GEMM of the split-operand kernel: the image is copied once into a zero-padded 4-channel NHWC tensor (3 pixels
     before, 4 behind; ~1 % of the step), a window ROW -- 8 pixels x 4 channels = 32 contiguous floats -- is one K-step, the
     eighth row and column and the fourth channel meet zero weights.  K = 8 x 32 = 256."""
-    w = conv.weight
-    key = (w.data_ptr(), w._version, str(w.device))
-    cached = getattr(conv, '_opa_w3_stem', None)
-    if cached is None or cached[0] != key:
-        n = w.shape[0]
-        wp = torch.zeros((n, 8, 8, 4), dtype=torch.float32, device=w.device)
-        wp[:, :7, :7, :3] = w.detach().permute(0, 2, 3, 1)
-        cached = (key, split_weight(wp.reshape(n, 256)))
-        conv._opa_w3_stem = cached
+    w3 = _stem_weight_of(conv)
     B, _, H, W = x.shape
     xp = torch.nn.functional.pad(x.permute(0, 2, 3, 1), (0, 1, 3, 4, 3, 4)).contiguous()        # [B, H + 7, W + 7, 4]
     ho, wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     out = torch.empty((B, conv.out_channels, ho, wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
     _lib.check(_lib.lib().opa_conv_rows_f32x3(
-        ctypes.c_void_p(xp.data_ptr()), ctypes.c_void_p(cached[1].data_ptr()), ctypes.c_void_p(bias.data_ptr()),
+        ctypes.c_void_p(xp.data_ptr()), ctypes.c_void_p(w3.data_ptr()), ctypes.c_void_p(bias.data_ptr()),
         ctypes.c_void_p(out.data_ptr()), B, H + 7, W + 7, 4, ho, wo, 2, 8, 32, conv.out_channels, int(bool(relu)), int(X3_TERMS),
         ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_conv_rows_f32x3')
     return out

@@ -56,20 +56,25 @@ class _Bottleneck(nn.Module):
 
     def enable_fused_(self):
         _take_biases(self, ('conv1', 'conv2', 'conv3'))
-        if self.conv2.stride == (1, 1):     # the stride-1 3x3: G g G^T once, in the Winograd kernel's operand order
-            self.register_buffer('wino_u', winograd.transform_filter(self.conv2.weight, winograd.DEFAULT_VARIANT),
-                                 persistent=False)
+        self._wino = self.conv2.stride == (1, 1)     # the stride-1 3x3 may go to the Winograd kernel
         self.fused = True
+
+    @property
+    def wino_u(self):
+        """G g G^T of the CURRENT ``conv2.weight`` in the Winograd kernel's operand order (``winograd.filter_of``: derived, cached,
+        no part of a checkpoint); no such attribute before ``enable_fused_`` or on a strided block."""
+        if not self.__dict__.get('_wino'):
+            raise AttributeError('wino_u')
+        return winograd.filter_of(self.conv2)
 
     def forward(self, x):
         if self.fused:      # conv (no bias) -> ONE fused bias(+residual)+ReLU pass each
             out = fused.conv_bias_act(self.conv1, x, self.fb1)            # 1x1: fused MFMA GEMM
             # 3x3: float32 stride 1 -> Winograd F(2x2, 3x3) in one HIP kernel, whose output transform adds the bias and applies
             # the ReLU on the way out (nothing extra to read or write), so the expanding 1x1 is the plain GEMM ...
-            u = getattr(self, 'wino_u', None)
-            wino = winograd.takes(self.conv2, out, u)
+            wino = winograd.takes(self.conv2, out, self._wino)
             if wino:
-                out = winograd.run(self.conv2, out, u, bias=self.fb2, relu=True)
+                out = winograd.run(self.conv2, out, bias=self.fb2, relu=True)
             elif fused.conv3x3_x3_supported(self.conv2, out, self.fb2):  # ... float32 strided: implicit GEMM of the split-operand kernel
                 h = out                                                   # (or MIOpen + the epilogue pass, whichever is faster for the shape)
                 s = self.conv2.stride[0]
@@ -89,10 +94,11 @@ class _Bottleneck(nn.Module):
             # a block WITH a downsampling convolution, float32: conv3(out) + downsample(x) as ONE product (the identity tensor
             # is never written), conv2's bias + ReLU applied to the operand where conv2 left them out -- where that is faster
             if self.downsample is not None and fused.pair_supported(self.conv3, self.downsample[0], out, x, self.fb3, a_bias):
+                # (written: with a_bias, two_launches may apply conv2's epilogue to ``out`` in place -- once, not once per timed call)
                 return fused.pick('pair', out.shape[0] * out.shape[2] * out.shape[3], self.conv3.in_channels + self.downsample[0].in_channels,
                                   self.conv3.out_channels, self.downsample[0].stride[0] > 1, a_bias is not None,
                                   lambda: fused.conv1x1_pair_bias_act_x3(self.conv3, self.downsample[0], out, x, self.fb3, True, a_bias),
-                                  two_launches)
+                                  two_launches, written=out if a_bias is not None else None)
             return two_launches()
         identity = x if self.downsample is None else self.downsample(x)
         out = self.relu(self.bn1(self.conv1(x)))
@@ -116,21 +122,27 @@ class _BasicBlock(nn.Module):
 
     def enable_fused_(self):
         _take_biases(self, ('conv1', 'conv2'))
-        for i, conv in ((1, self.conv1), (2, self.conv2)):   # stride-1 3x3: the Winograd kernel's operand (see _Bottleneck)
-            if conv.stride == (1, 1) and conv.in_channels % 16 == 0 and conv.out_channels % 64 == 0:
-                self.register_buffer('wino_u%d' % i, winograd.transform_filter(conv.weight, winograd.DEFAULT_VARIANT),
-                                     persistent=False)
+        # stride-1 3x3 of the kernel's channel counts: may go to the Winograd kernel (see _Bottleneck)
+        self._wino = tuple(conv.stride == (1, 1) and conv.in_channels % 16 == 0 and conv.out_channels % 64 == 0
+                           for conv in (self.conv1, self.conv2))
         self.fused = True
+
+    def _wino_u(self, i):
+        if not self.__dict__.get('_wino', (False, False))[i - 1]:
+            raise AttributeError('wino_u%d' % i)
+        return winograd.filter_of(getattr(self, 'conv%d' % i))
+
+    wino_u1 = property(lambda self: self._wino_u(1), doc='like ``_Bottleneck.wino_u``, of ``conv1``')
+    wino_u2 = property(lambda self: self._wino_u(2), doc='like ``_Bottleneck.wino_u``, of ``conv2``')
 
     def forward(self, x):
         if self.fused:
             identity = x if self.downsample is None else self.downsample[0](x)
-            u1, u2 = getattr(self, 'wino_u1', None), getattr(self, 'wino_u2', None)
-            if winograd.takes(self.conv1, x, u1):             # bias + ReLU in the kernel's output transform
-                out = winograd.run(self.conv1, x, u1, bias=self.fb1, relu=True)
+            if winograd.takes(self.conv1, x, self._wino[0]):  # bias + ReLU in the kernel's output transform
+                out = winograd.run(self.conv1, x, bias=self.fb1, relu=True)
             else:
                 out = fused.bias_act_(self.conv1(x), self.fb1)
-            return fused.bias_act_(winograd.conv_or_fallback(self.conv2, out, u2), self.fb2, identity)
+            return fused.bias_act_(winograd.conv_or_fallback(self.conv2, out, self._wino[1]), self.fb2, identity)
         identity = x if self.downsample is None else self.downsample(x)
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.bn2(self.conv2(out))
@@ -238,11 +250,22 @@ class _InvertedResidualK(nn.Module):
         self.fused = True
 
     @staticmethod
+    def taps_of(conv):
+        """``w_taps`` of the CURRENT depthwise weight: the buffer (part of the state dict since it was introduced, so it stays one)
+        is written again whenever the weight was replaced, converted or changed in place since."""
+        def make():
+            k = conv.kernel_size[0]
+            conv.w_taps = conv.weight.detach().reshape(conv.out_channels, k * k).t().contiguous()
+            return True
+        fused.derived(conv, '_opa_taps', (conv.weight,), make)
+        return conv.w_taps
+
+    @staticmethod
     def _run(branch, x):
         for m in branch:
-            if isinstance(m, nn.Conv2d) and hasattr(m, 'w_taps') and m.w_taps.dtype == x.dtype \
+            if isinstance(m, nn.Conv2d) and hasattr(m, 'w_taps') and m.weight.dtype == x.dtype \
                     and fused.dwconv_supported(x, m.kernel_size[0], m.stride[0]):
-                x = fused.dwconv_bias_act(x, m.w_taps, m.bias, m.kernel_size[0], m.stride[0])
+                x = fused.dwconv_bias_act(x, _InvertedResidualK.taps_of(m), m.bias, m.kernel_size[0], m.stride[0])
             else:
                 x = m(x)
         return x

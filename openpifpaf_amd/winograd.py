@@ -48,22 +48,24 @@ def workgroups(x_shape, c_out, variant=DEFAULT_VARIANT):
 
 
 def takes(conv, x, u, variant=DEFAULT_VARIANT):
-    """True if the Winograd kernel runs ``conv(x)`` for this bias-free 3x3 ``torch.nn.Conv2d``: ``u`` (its transformed filter)
-    is there, the operands qualify and the launch fills the chip -- a rule on shapes, not a timing, so that every rank of a job
+    """True if the Winograd kernel runs ``conv(x)`` for this bias-free 3x3 ``torch.nn.Conv2d``: ``u`` says that the kernel may (its
+    transformed filter, or True where the operand is derived from ``conv.weight`` at the launch, :func:`filter_of`; None or False:
+    it may not), the operands qualify and the launch fills the chip -- a rule on shapes, not a timing, so that every rank of a job
     and every run take the same path (the two round differently); :func:`set_mode` (default: ``OPA_CONV3X3`` at import) forces one."""
     forced = _mode
-    return (u is not None and forced != 'conv' and u.dtype == torch.float32 and conv.bias is None
+    return (u is not None and u is not False and forced != 'conv' and (u is True or u.dtype == torch.float32) and conv.bias is None
             and supported(x, conv.weight, variant, conv.stride, conv.padding, conv.groups, conv.dilation)
             and (forced == 'winograd' or workgroups(x.shape, conv.out_channels, variant) >= MIN_WORKGROUPS)
             and not (torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad)))
 
 
-def run(conv, x, u, bias=None, relu=False):
+def run(conv, x, u=True, bias=None, relu=False):
     """``conv(x)`` (+ bias, ReLU) through the kernel, where :func:`takes` holds: variant 4 on the split planes of the CURRENT
-    ``conv.weight`` (:func:`split_filter_of`), or variant 2 on ``u`` with ``OPA_WINO_X3=0``."""
+    ``conv.weight`` (:func:`split_filter_of`), or with ``OPA_WINO_X3=0`` variant 2 on its transformed filter (:func:`filter_of`;
+    a tensor passed as ``u`` is taken as that filter instead)."""
     if X3:
         return conv3x3_x3(x, split_filter_of(conv), conv.out_channels, bias=bias, relu=relu)
-    return conv3x3(x, u, conv.out_channels, bias=bias, relu=relu, variant=DEFAULT_VARIANT)
+    return conv3x3(x, filter_of(conv) if u is True else u, conv.out_channels, bias=bias, relu=relu, variant=DEFAULT_VARIANT)
 
 
 def conv_or_fallback(conv, x, u, variant=DEFAULT_VARIANT):
@@ -114,15 +116,19 @@ def split_filter(weight):
 
 
 def split_filter_of(conv):
-    """``split_filter(conv.weight)``, kept on the module and computed again whenever the weight was replaced, moved or changed in
-    place (``load_state_dict`` into an optimized network): the key is (data pointer, version counter, device)."""
-    w = conv.weight
-    key = (w.data_ptr(), w._version, str(w.device))
-    cached = getattr(conv, '_opa_wino_u3', None)
-    if cached is None or cached[0] != key:
-        cached = (key, split_filter(w))
-        conv._opa_wino_u3 = cached
-    return cached[1]
+    """``split_filter(conv.weight)``, kept on the module and computed again whenever the weight was replaced, moved, converted or
+    changed in place (``load_state_dict`` into an optimized network): ``fused.derived``'s key (data pointer, version counter, device,
+    dtype)."""
+    from . import fused
+    return fused.derived(conv, '_opa_wino_u3', (conv.weight,), lambda: split_filter(conv.weight))
+
+
+def filter_of(conv):
+    """``transform_filter(conv.weight, 2)`` in the weight's dtype -- variant 2's operand -- kept on the module and kept current
+    like :func:`split_filter_of` (a snapshot taken when the network was optimized would outlive ``load_state_dict``)."""
+    from . import fused
+    return fused.derived(conv, '_opa_wino_u', (conv.weight,),
+                         lambda: transform_filter(conv.weight, DEFAULT_VARIANT).to(conv.weight.dtype))
 
 
 # direct-convolution flops of the launches that went through the kernel since the last reset: a measurement (bench.py) that
