@@ -421,6 +421,19 @@ int opa_conv_rows_f32x3(const float* x_dev, const void* w3_dev, const float* bia
                         int32_t wp, int32_t pix, int32_t ho, int32_t wo, int32_t stride, int32_t ntaps, int32_t tap_floats,
                         int32_t c_out, int32_t relu, int32_t terms, void* stream);
 
+/* The 1x1 convolutions of a ShuffleNetV2K unit (reference network/basenetworks.py:186-242) through the same kernel: ANY even k
+ * and n, the operand a channel SLICE of a wider channels-last tensor, the result optionally stored into its shuffled position.
+ *     out[m, n] = act(a[m, k; a_pitch floats between rows] * w^T + bias)                                   (partner_dev NULL)
+ *     out[m, 2n]: out[., 2c] = partner[., c; partner_pitch floats between rows] (bit for bit), out[., 2c + 1] = act(...)[c]
+ * -- the latter is channel_shuffle(cat((partner, y), 1), 2) written as contiguous rows.  w3_dev = split_weight of the weight padded
+ * with zeros to [N_pad][K_pad], bias_dev [N_pad] padded alike, N_pad / K_pad = n / k rounded up to multiples of 64
+ * (openpifpaf_amd.fused._unit_weight_of).  Columns of a row of A from k on contribute exactly zero whatever the memory holds,
+ * and nothing behind column k of the last row is read.  a_dev, partner_dev and the pitches on 8 bytes (even), w3_dev, bias_dev and
+ * out_dev on 16; a_pitch >= k (at most 2^21), partner_pitch >= n; m < 2^31; terms 6 or 9 as above.  m == 0: OPA_OK, nothing runs. */
+int opa_gemm_unit_bias_act_f32x3(const float* a_dev, int64_t a_pitch, const void* w3_dev, const float* bias_dev,
+                                 const float* partner_dev, int64_t partner_pitch, float* out_dev,
+                                 int64_t m, int32_t n, int32_t k, int32_t relu, int32_t terms, void* stream);
+
 /* 3x3 convolution, stride 1, padding 1, of an NHWC float32 activation as Winograd F(2x2, 3x3) in ONE kernel (input
  * transform -> sixteen float32 MFMA GEMMs -> output transform; csrc/winograd.hip): the bottleneck convolutions of the
  * ResNet trunk (reference network/basenetworks.py:71-150 runs them through torch.nn.Conv2d), 2.25x fewer multiplications

@@ -913,6 +913,27 @@ int opa_conv3x3_f32x3(const float* x_dev, const void* w3_dev, const float* bias_
     return OPA_OK;
 }
 
+int opa_gemm_unit_bias_act_f32x3(const float* a_dev, int64_t a_pitch, const void* w3_dev, const float* bias_dev,
+                                 const float* partner_dev, int64_t partner_pitch, float* out_dev,
+                                 int64_t m, int32_t n, int32_t k, int32_t relu, int32_t terms, void* stream) {
+    if (!a_dev || !w3_dev || !bias_dev || !out_dev || m < 0 || n <= 0 || k <= 0 || m > 0x7fffffffll || (terms != 6 && terms != 9))
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_gemm_unit_bias_act_f32x3: bad arguments");
+    if (n % 2 != 0 || k % 2 != 0)
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_gemm_unit_bias_act_f32x3: K and N must be even");
+    // (a tile's 128 rows are addressed with 32-bit byte offsets: 2^21 floats per row leave room)
+    if (a_pitch < k || a_pitch % 2 != 0 || a_pitch > (1 << 21) ||
+        (partner_dev && (partner_pitch < n || partner_pitch % 2 != 0 || partner_pitch > 0x7fffffffll)))
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_gemm_unit_bias_act_f32x3: a row pitch is shorter than its row, odd, or too long");
+    if ((((uintptr_t)a_dev | (uintptr_t)partner_dev) & 7) || (((uintptr_t)w3_dev | (uintptr_t)out_dev | (uintptr_t)bias_dev) & 15))
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_gemm_unit_bias_act_f32x3: a_dev / partner_dev must be 8-B, w3_dev / bias_dev / out_dev 16-B aligned");
+    if (m == 0) return OPA_OK;
+    hipError_t e = launch_gemm_unit_f32x3(a_dev, (int)a_pitch, (const unsigned short*)w3_dev, bias_dev, partner_dev,
+                                          partner_dev ? (int)partner_pitch : 0, out_dev, (int)m, n, k, relu, terms, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "gemm_unit_f32x3");
+    prof_mark((hipStream_t)stream, "gemm_unit_f32x3_kernel");
+    return OPA_OK;
+}
+
 int opa_conv3x3_winograd_f32(const float* x_dev, const float* u_dev, const float* bias_dev, float* out_dev, int32_t batch,
                              int32_t h, int32_t w, int32_t c_in, int32_t c_out, int32_t relu, int32_t variant,
                              int32_t order, void* stream) {

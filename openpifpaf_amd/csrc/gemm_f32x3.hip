@@ -38,6 +38,7 @@ typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
+typedef __attribute__((ext_vector_type(2))) float f32x2_t;
 
 #ifndef OPA_X3_BK                  // tuning switches (tools/gpu/gemm_x3_probe.py builds the variants): K-step,
 #define OPA_X3_BK 32               // workgroups per compute unit the registers are budgeted for,
@@ -75,9 +76,80 @@ struct X3Second {
     int hi, C, batch;          // (SRC = 2) input rows, floats per tap (a multiple of the K-step), images
     int pix, taps_x, ntaps, padded;   // (SRC = 2) floats per input pixel; taps per window row; taps; 1: the input is padded in
                                // memory (window origin = (stride oy, stride ox), every tap valid), 0: padding 1 by the tap mask
+    int lda, ldp, n_real, k_real;     // (UNIT) floats between rows of A and of the partner; the columns that exist of N and K
 };
 
-template <int BN, bool RES, bool RELU, bool PRO, int TERMS, int SRC>
+// UNIT: the 1x1 convolutions of a ShuffleNetV2K unit (reference network/basenetworks.py:186-242) -- ANY even K and N, A a channel
+// slice of a wider tensor, the output optionally stored into its shuffled position:
+//     out[M, n] = act(A[M, k; row pitch lda] * W^T + bias)                                    (RES = false)
+//     out[M, 2n]: out[m, 2c] = partner[m, c; row pitch ldp], out[m, 2c + 1] = act(...)[c]     (RES = true: `res` is the partner)
+// = channel_shuffle(cat((partner, y), 1), 2), written as contiguous rows.  The kernel's N and K are the PADDED sizes (W3
+// [3][N][K] and bias [N] are padded with zeros on the host: N to the tile width, K to two K-steps); sec.n_real / sec.k_real are
+// the columns that exist.  Zeros in the weight do not cancel what lies behind column k_real of a row of A (the next pixel, the
+// other half of this one: 0 x Inf is NaN), so those columns are replaced by zeros with a select before the split, and what lies
+// behind the LAST row is never fetched (the buffer's range ends with that row's column k_real).  A slice starts on an 8-byte
+// boundary only (k16 stage 2: 174 floats into a pixel) and so does every row of the output (n_real even): the operand is staged
+// with 8-byte loads, the epilogue works in column pairs -- a pair lies inside k_real / n_real or outside, never across.
+template <int BN, bool PARTNER, bool RELU>
+__device__ __forceinline__ void x3_unit_epilogue(float* smem_f, const f32x16_t (&acc)[2][BN / 64], const f32x16_t (&low)[2][BN / 64],
+                                                 const float* __restrict__ bias, const float* __restrict__ partner,
+                                                 float* __restrict__ out, int M, int m0, int n0, int lane, int wave, int ldp, int n_real) {
+    constexpr int WN = BN / 2, NT = WN / 32;
+    constexpr int PPR = WN / 2;                // column pairs of a patch row
+    constexpr int PPL = 32 * PPR / 64;         // ... per lane (16 | 8)
+    constexpr int PPRE = PPL > 8 ? 8 : PPL;    // partner pairs fetched ahead (16 registers); the rest in the loop
+    const int wm = wave >> 1, wn = wave & 1;
+    float* patch = smem_f + wave * (32 * WN);
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        f32x2_t pv[PPRE];
+        if (PARTNER) {                         // they travel while the patch is written
+#pragma unroll
+            for (int t = 0; t < PPRE; t++) {
+                const int v = t * 64 + lane;
+                const int row = v / PPR, col = n0 + wn * WN + (v % PPR) * 2;
+                const int m = m0 + wm * 64 + i * 32 + row;
+                pv[t] = (f32x2_t){0.f, 0.f};
+                if (m < M && col < n_real) pv[t] = *reinterpret_cast<const f32x2_t*>(partner + (size_t)m * ldp + col);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NT; j++) {
+            const int col = j * 32 + (lane & 31);
+            const float b = bias[n0 + wn * WN + col];
+#pragma unroll
+            for (int r = 0; r < 16; r++) {     // C layout: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+                const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                patch[row * WN + col] = (OPA_X3_ONE_ACC ? acc[i][j][r] : acc[i][j][r] + low[i][j][r]) + b;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int t = 0; t < PPL; t++) {
+            const int v = t * 64 + lane;
+            const int row = v / PPR, c2 = (v % PPR) * 2, col = n0 + wn * WN + c2;
+            const int m = m0 + wm * 64 + i * 32 + row;
+            if (m < M && col < n_real) {       // (n_real is even: the pair is inside or outside)
+                f32x2_t f = *reinterpret_cast<const f32x2_t*>(patch + row * WN + c2);
+                if (RELU) { f[0] = fmaxf(f[0], 0.0f); f[1] = fmaxf(f[1], 0.0f); }
+                if (PARTNER) {                 // the partner's bits pass through untouched
+                    f32x2_t pp;
+                    if (t < PPRE) pp = pv[t < PPRE ? t : 0];
+                    else pp = *reinterpret_cast<const f32x2_t*>(partner + (size_t)m * ldp + col);
+                    *reinterpret_cast<f32x4_t*>(out + (size_t)m * (2 * (size_t)n_real) + 2 * col) = (f32x4_t){pp[0], f[0], pp[1], f[1]};
+                } else {
+                    *reinterpret_cast<f32x2_t*>(out + (size_t)m * n_real + col) = f;
+                }
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        asm volatile("" ::: "memory");
+    }
+}
+
+template <int BN, bool RES, bool RELU, bool PRO, int TERMS, int SRC, bool UNIT = false>
 __global__ __launch_bounds__(256, OPA_X3_WGS) void gemm_f32x3_bias_act_kernel(
         const float* __restrict__ A, const unsigned short* __restrict__ W3, const float* __restrict__ bias,
         const float* __restrict__ res, float* __restrict__ out, int M, int N, int K, const float* __restrict__ a_bias,
@@ -131,12 +203,13 @@ __global__ __launch_bounds__(256, OPA_X3_WGS) void gemm_f32x3_bias_act_kernel(
     // (buffer loads: a descriptor in scalar registers, ONE 32-bit byte offset per load, the K-step as the scalar offset)
     constexpr bool TWO = SRC == 1, TAPS = SRC == 2;
     const int rows_here = M - m0 < kX3BM ? M - m0 : kX3BM;
-    const int KA = TWO ? sec.K1 : TAPS ? sec.C : K;          // row length of the first activation
+    const int KA = TWO ? sec.K1 : TAPS ? sec.C : UNIT ? sec.lda : K;      // row length of the first activation (UNIT: its row pitch)
     // (TAPS: the whole tensor, from wi + 1 pixels BEFORE its start -- the window of output pixel (oy, ox) begins at input pixel
     //  (stride oy - 1, stride ox - 1); what lies before the tensor is only ever asked for by rows whose tap bit is clear)
     const int shift = TAPS && !sec.padded ? (sec.wi + 1) * sec.pix : 0;
     const float* a1_base = TAPS ? A - (size_t)shift : A + (size_t)m0 * KA;
-    const int a1_bytes = TAPS ? (int)(((size_t)sec.batch * sec.hi_wi * sec.pix + shift) * 4) : (int)((size_t)rows_here * KA * 4);
+    const int a1_bytes = TAPS ? (int)(((size_t)sec.batch * sec.hi_wi * sec.pix + shift) * 4)
+                       : UNIT ? (int)(((size_t)(rows_here - 1) * KA + sec.k_real) * 4) : (int)((size_t)rows_here * KA * 4);
     const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a1_base), 0, a1_bytes, 0x00020000);
     // the second activation: its rows are the input pixels the tile's output pixels read (monotonic in m: offsets from the first)
     const int K2 = K - KA;
@@ -200,6 +273,15 @@ __global__ __launch_bounds__(256, OPA_X3_WGS) void gemm_f32x3_bias_act_kernel(
 #pragma unroll
             for (int p = 0; p < NPA; p++)
                 ra[p] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rs, second ? pa2[p] : pa[p], ks, 0));
+        } else if constexpr (UNIT) {           // rows on 8-byte boundaries: two 8-byte loads per vector (where the compiler can prove
+                                               // them adjacent it merges them into one 16-byte load, which needs dword alignment only:
+                                               // tests/test_gpu_unit_gemm.py runs k16's slice, 8 bytes off a 16-byte boundary)
+#pragma unroll
+            for (int p = 0; p < NPA; p++) {
+                const f32x2_t lo = __builtin_bit_cast(f32x2_t, __builtin_amdgcn_raw_buffer_load_b64(a_rsrc, pa[p], k0 * 4, 0));
+                const f32x2_t hi = __builtin_bit_cast(f32x2_t, __builtin_amdgcn_raw_buffer_load_b64(a_rsrc, pa[p] + 8u, k0 * 4, 0));
+                ra[p] = (f32x4_t){lo[0], lo[1], hi[0], hi[1]};
+            }
         } else {
 #pragma unroll
             for (int p = 0; p < NPA; p++) ra[p] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, pa[p], k0 * 4, 0));
@@ -216,11 +298,16 @@ __global__ __launch_bounds__(256, OPA_X3_WGS) void gemm_f32x3_bias_act_kernel(
 #pragma unroll
         for (int t = 0; t < WV; t++) rb[t] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, pb[t], k0 * 2, 0));
     };
-    auto store = [&](const f32x4_t (&ra)[NPA]) {          // registers -> LDS: the activation is split here, once per element and tile
+    auto store = [&](const f32x4_t (&ra)[NPA], int kt) {  // registers -> LDS: the activation (of K-step kt) is split here, once per element and tile
 #pragma unroll
         for (int p = 0; p < NPA; p++) {
             u32x2_t p1, p2, p3;
             if (OPA_X3_DIAG == 1) { p1[0] = __float_as_uint(ra[p][0]); p1[1] = __float_as_uint(ra[p][2]); p2 = p1; p3 = p1; }
+            else if constexpr (UNIT) {         // columns from k_real on are zeros WHATEVER the memory behind the row holds (a select)
+                const bool in0 = kt + s_col < sec.k_real, in1 = kt + s_col + 2 < sec.k_real;
+                const f32x4_t v = {in0 ? ra[p][0] : 0.0f, in0 ? ra[p][1] : 0.0f, in1 ? ra[p][2] : 0.0f, in1 ? ra[p][3] : 0.0f};
+                split4(v, p1, p2, p3);
+            }
             else split4(ra[p], p1, p2, p3);
             unsigned short* d = sA + x3_lds(p * RPP + s_row, s_col);
             *reinterpret_cast<u32x2_t*>(d) = p1;
@@ -278,12 +365,12 @@ __global__ __launch_bounds__(256, OPA_X3_WGS) void gemm_f32x3_bias_act_kernel(
             }
         }
         __syncthreads();                       // every wave is done reading the stage
-        if (more && (OPA_X3_DIAG != 2 || cur[0][0] == 12345.678f)) store(cur);
+        if (more && (OPA_X3_DIAG != 2 || cur[0][0] == 12345.678f)) store(cur, k0 + kX3BK);
         __syncthreads();
     };
     fetch_b(0);
     fetch_a(ra0, 0);
-    store(ra0);
+    store(ra0, 0);
     __syncthreads();
     fetch_a(ra1, kX3BK);                       // (K is a multiple of 2 BK: the launcher checks)
     for (int k0 = 0; k0 < K; k0 += 2 * kX3BK) {
@@ -291,6 +378,10 @@ __global__ __launch_bounds__(256, OPA_X3_WGS) void gemm_f32x3_bias_act_kernel(
         step(k0 + kX3BK, ra0, ra1);
     }
     // (the loop's last barrier: staging LDS is free, reuse it for the epilogue)
+    if constexpr (UNIT) {
+        x3_unit_epilogue<BN, RES, RELU>(reinterpret_cast<float*>(smem), acc, low, bias, res, out, M, m0, n0, lane, wave, sec.ldp, sec.n_real);
+        return;
+    }
 
     // epilogue, one 32-row block of the wave tile at a time through a wave-private f32 patch: the residual load and
     // the output store are row-contiguous 16-B vectors
@@ -383,7 +474,7 @@ static hipError_t launch_x3_terms(const float* A, const unsigned short* W3, cons
 hipError_t launch_gemm_f32x3_bias_act(const float* A, const unsigned short* W3, const float* bias, const float* res, float* out,
                                       int M, int N, int K, int relu, int terms, hipStream_t st, const float* a_bias) {
     X3Second none; none.A2 = nullptr; none.K1 = K; none.ho_wo = none.wo = none.hi_wi = none.wi = none.stride = 1; none.hi = 1; none.C = 0; none.batch = 1;
-    none.pix = 1; none.taps_x = 1; none.ntaps = 1; none.padded = 0;
+    none.pix = 1; none.taps_x = 1; none.ntaps = 1; none.padded = 0; none.lda = none.ldp = none.n_real = none.k_real = 0;
     if (terms == 6) return launch_x3_terms<6>(A, W3, bias, res, out, M, N, K, relu, st, a_bias, none);
     return launch_x3_terms<9>(A, W3, bias, res, out, M, N, K, relu, st, a_bias, none);
 }
@@ -394,10 +485,38 @@ hipError_t launch_gemm2_f32x3_bias_act(const float* A1, int K1, const float* A2,
                                        hipStream_t st, const float* a_bias) {
     const int ho = (hi - 1) / stride + 1, wo = (wi - 1) / stride + 1;
     X3Second sec; sec.A2 = A2; sec.K1 = K1; sec.ho_wo = ho * wo; sec.wo = wo; sec.hi_wi = hi * wi; sec.wi = wi; sec.stride = stride;
-    sec.hi = hi; sec.C = 0; sec.batch = batch; sec.pix = 1; sec.taps_x = 1; sec.ntaps = 1; sec.padded = 0;
+    sec.hi = hi; sec.C = 0; sec.batch = batch; sec.pix = 1; sec.taps_x = 1; sec.ntaps = 1; sec.padded = 0; sec.lda = sec.ldp = sec.n_real = sec.k_real = 0;
     const int M = batch * ho * wo, K = K1 + K2;
     if (terms == 6) return launch_x3_terms<6>(A1, W3, bias, nullptr, out, M, N, K, relu, st, a_bias, sec);
     return launch_x3_terms<9>(A1, W3, bias, nullptr, out, M, N, K, relu, st, a_bias, sec);
+}
+
+template <int BN, int TERMS>
+static hipError_t launch_unit_bn(const float* a, const unsigned short* w, const float* b, const float* partner, float* o,
+                                 int M, int Np, int Kp, int relu, hipStream_t st, const X3Second& sec) {
+    const unsigned blocks = (unsigned)((long long)((M + kX3BM - 1) / kX3BM) * (Np / BN));
+    if (partner) {
+        if (relu) gemm_f32x3_bias_act_kernel<BN, true, true, false, TERMS, 0, true><<<blocks, 256, 0, st>>>(a, w, b, partner, o, M, Np, Kp, nullptr, sec);
+        else gemm_f32x3_bias_act_kernel<BN, true, false, false, TERMS, 0, true><<<blocks, 256, 0, st>>>(a, w, b, partner, o, M, Np, Kp, nullptr, sec);
+    } else {
+        if (relu) gemm_f32x3_bias_act_kernel<BN, false, true, false, TERMS, 0, true><<<blocks, 256, 0, st>>>(a, w, b, nullptr, o, M, Np, Kp, nullptr, sec);
+        else gemm_f32x3_bias_act_kernel<BN, false, false, false, TERMS, 0, true><<<blocks, 256, 0, st>>>(a, w, b, nullptr, o, M, Np, Kp, nullptr, sec);
+    }
+    return hipGetLastError();
+}
+
+// The UNIT mode: A [M, K] with `lda` floats between rows, W3 [3][Np][Kp] and bias [Np] padded with zeros (Np, Kp: N, K rounded up
+// to multiples of 64), partner [M, N] with `ldp` floats between rows or null; out [M, N] dense, or [M, 2N] with a partner.  The tile
+// is 128 wide where Np is a multiple of 128, like launch_gemm_f32x3_bias_act chooses it for N -- with six terms: the 128-wide
+// tile with nine terms does not fit the register file (the existing instantiations spill 8 registers), so nine terms take 64.
+hipError_t launch_gemm_unit_f32x3(const float* A, int lda, const unsigned short* W3, const float* bias, const float* partner, int ldp,
+                                  float* out, int M, int N, int K, int relu, int terms, hipStream_t st) {
+    X3Second sec; sec.A2 = nullptr; sec.K1 = K; sec.ho_wo = sec.wo = sec.hi_wi = sec.wi = sec.stride = 1; sec.hi = 1; sec.C = 0; sec.batch = 1;
+    sec.pix = 1; sec.taps_x = 1; sec.ntaps = 1; sec.padded = 0; sec.lda = lda; sec.ldp = ldp; sec.n_real = N; sec.k_real = K;
+    const int Np = (N + 63) / 64 * 64, Kp = (K + 63) / 64 * 64;
+    if (Np % 128 == 0 && terms == 6) return launch_unit_bn<128, 6>(A, W3, bias, partner, out, M, Np, Kp, relu, st, sec);
+    if (terms == 6) return launch_unit_bn<64, 6>(A, W3, bias, partner, out, M, Np, Kp, relu, st, sec);
+    return launch_unit_bn<64, 9>(A, W3, bias, partner, out, M, Np, Kp, relu, st, sec);
 }
 
 // 3x3 convolution, padding 1, stride s: out[B, ho, wo, N] = act(im2col(x) * W3^T + bias), x [B, hi, wi, C] channels-last,
@@ -406,7 +525,7 @@ hipError_t launch_conv3x3_f32x3(const float* x, int batch, int hi, int wi, int C
                                 const float* bias, float* out, int N, int relu, int terms, hipStream_t st) {
     const int ho = (hi - 1) / stride + 1, wo = (wi - 1) / stride + 1;
     X3Second sec; sec.A2 = nullptr; sec.K1 = C; sec.ho_wo = ho * wo; sec.wo = wo; sec.hi_wi = hi * wi; sec.wi = wi; sec.stride = stride;
-    sec.hi = hi; sec.C = C; sec.batch = batch; sec.pix = C; sec.taps_x = 3; sec.ntaps = 9; sec.padded = 0;
+    sec.hi = hi; sec.C = C; sec.batch = batch; sec.pix = C; sec.taps_x = 3; sec.ntaps = 9; sec.padded = 0; sec.lda = sec.ldp = sec.n_real = sec.k_real = 0;
     const int M = batch * ho * wo, K = 9 * C;
     if (terms == 6) return launch_x3_terms<6>(x, W3, bias, nullptr, out, M, N, K, relu, st, nullptr, sec);
     return launch_x3_terms<9>(x, W3, bias, nullptr, out, M, N, K, relu, st, nullptr, sec);
@@ -419,7 +538,7 @@ hipError_t launch_conv3x3_f32x3(const float* x, int batch, int hi, int wi, int C
 hipError_t launch_convrows_f32x3(const float* x, int batch, int hp, int wp, int pix, int ho, int wo, int stride, int ntaps, int tap_floats,
                                  const unsigned short* W3, const float* bias, float* out, int N, int relu, int terms, hipStream_t st) {
     X3Second sec; sec.A2 = nullptr; sec.K1 = tap_floats; sec.ho_wo = ho * wo; sec.wo = wo; sec.hi_wi = hp * wp; sec.wi = wp; sec.stride = stride;
-    sec.hi = hp; sec.C = tap_floats; sec.batch = batch; sec.pix = pix; sec.taps_x = 1; sec.ntaps = ntaps; sec.padded = 1;
+    sec.hi = hp; sec.C = tap_floats; sec.batch = batch; sec.pix = pix; sec.taps_x = 1; sec.ntaps = ntaps; sec.padded = 1; sec.lda = sec.ldp = sec.n_real = sec.k_real = 0;
     const int M = batch * ho * wo, K = ntaps * tap_floats;
     if (terms == 6) return launch_x3_terms<6>(x, W3, bias, nullptr, out, M, N, K, relu, st, nullptr, sec);
     return launch_x3_terms<9>(x, W3, bias, nullptr, out, M, N, K, relu, st, nullptr, sec);

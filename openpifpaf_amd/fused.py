@@ -164,7 +164,7 @@ def _split_weight_of(conv, w2d):
 FORCE_PICK = os.environ.get('OPA_GEMM3_PICK') or None        # 'x3' | 'conv': every pick() takes that side (tests, A/B)
 
 
-def pick(kind, m, k, n, flag_a, flag_b, run_x3, run_other, written=None):
+def pick(kind, m, k, n, flag_a, flag_b, run_x3, run_other, written=None, timing=True):
     """One of two ways to compute the same tensor -- a split-operand kernel (``run_x3``) or what the trunk did before
     (``run_other``: MIOpen's convolution + the fused passes) -- chosen ONCE per shape like ``conv_bias_act`` chooses its GEMM: from
     the shipped table (``conv1x1_pinned.json``, key dtype ``'torch.float32/<kind>'``), else by timing both on the first call; while
@@ -172,13 +172,14 @@ def pick(kind, m, k, n, flag_a, flag_b, run_x3, run_other, written=None):
     from ~16 000 output pixels: a batch of one 641-px image keeps MIOpen in layers 3-4).  Returns the chosen function's result.
     ``written``: an operand that ``run_other`` changes in place (the epilogue its producer left to this consumer); timing calls
     ``run_other`` several times, so the operand is saved before and put back after -- the winner computes from what the caller
-    passed, whoever wins."""
+    passed, whoever wins.  ``timing=False``: a shape the table does not know is decided by size ALWAYS -- eager or capturing, one
+    rank or many -- and nothing is timed (measurements go into the table: ``tools/gpu/dump_conv_choices.py``)."""
     if FORCE_PICK in ('x3', 'conv'):
         return run_x3() if FORCE_PICK == 'x3' else run_other()
     key = ('torch.float32/' + kind, int(m), int(k), int(n), bool(flag_a), bool(flag_b))
     choice = _CHOICE.get(key)
     if choice is None:
-        if torch.cuda.is_current_stream_capturing() or _in_multi_rank_job():
+        if not timing or torch.cuda.is_current_stream_capturing() or _in_multi_rank_job():
             choice = 'x3' if m >= 16384 else 'conv'
         else:
             saved = written.clone() if written is not None else None
@@ -360,6 +361,77 @@ def stem7x7_bias_act_x3(conv, x, bias, relu=True):
         ctypes.c_void_p(xp.data_ptr()), ctypes.c_void_p(w3.data_ptr()), ctypes.c_void_p(bias.data_ptr()),
         ctypes.c_void_p(out.data_ptr()), B, H + 7, W + 7, 4, ho, wo, 2, 8, 32, conv.out_channels, int(bool(relu)), int(X3_TERMS),
         ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_conv_rows_f32x3')
+    return out
+
+
+# ... and the 1x1 convolutions of the ShuffleNetV2K units and conv5, whose channel counts (k16: 24 / 174 / 348 / 696 / 1392) fit none
+# of the tiles above and whose operand is a channel slice: the kernel's UNIT mode (OPA_GEMM3_UNIT=0: off)
+X3_UNIT = os.environ.get('OPA_GEMM3_UNIT', '1') != '0'
+
+
+def _unit_conv_ok(conv):
+    """The part of ``unit_conv_x3_supported`` that depends on the convolution alone."""
+    return (X3_UNIT and X3_TERMS in (6, 9) and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.in_channels % 2 == 0 and conv.out_channels % 2 == 0
+            and conv.weight.dtype == torch.float32
+            and (conv.bias is None or conv.bias.dtype == torch.float32))
+
+
+def unit_conv_x3_supported(conv, x, partner=None):
+    """Can ``conv1x1_unit_x3(conv, x, partner=partner)`` run?  float32 on the GPU, a 1x1 convolution of stride 1 without padding or
+    groups and with EVEN channel counts, ``x`` (and ``partner``) channels-innermost tensors or channel slices of such, on 8-byte
+    boundaries, nothing that autograd follows; the partner has the output's pixels and ``conv.out_channels`` channels."""
+    if not (x.is_cuda and conv.weight.device == x.device and _unit_conv_ok(conv) and _unit_operand_ok(x, conv.in_channels)
+            and 0 < x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31):
+        return False
+    if partner is not None:
+        return (partner.device == x.device and _unit_operand_ok(partner, conv.out_channels)
+                and (partner.shape[0], partner.shape[2], partner.shape[3]) == (x.shape[0], x.shape[2], x.shape[3]))
+    return True
+
+
+def _unit_operand_ok(t, channels):
+    """Layout of an activation operand of the unit mode (``x`` or the partner), whatever its device: float32, ``channels`` channels
+    innermost with an even pitch between pixels, on an 8-byte boundary, not followed by autograd."""
+    ps = _pixel_stride(t)
+    return (t.dtype == torch.float32 and not t.requires_grad and ps is not None and t.shape[1] == channels
+            and ps % 2 == 0 and ps <= 2 ** 21 and t.data_ptr() % 8 == 0)
+
+
+def _unit_weight_of(conv):
+    """The operands of ``conv1x1_unit_x3`` derived from the current parameters: ``split_weight`` of the ``[N, K]`` weight padded with
+    zeros to ``[N_pad, K_pad]`` (multiples of 64: the kernel's tile width and two of its K-steps) and the bias padded to ``N_pad``
+    (zeros where the convolution has none) -- kept on the module like ``_split_weight_of``; the convolution keeps its parameters."""
+    def make():
+        w = conv.weight
+        n, k = w.shape[0], w.shape[1]
+        npad, kpad = (n + 63) // 64 * 64, (k + 63) // 64 * 64
+        wp = torch.zeros((npad, kpad), dtype=torch.float32, device=w.device)
+        wp[:n, :k] = w.detach().reshape(n, k)
+        bp = torch.zeros(npad, dtype=torch.float32, device=w.device)
+        if conv.bias is not None:
+            bp[:n] = conv.bias.detach()
+        return split_weight(wp), bp
+    return derived(conv, '_opa_w3_unit', (conv.weight, conv.bias), make)
+
+
+def conv1x1_unit_x3(conv, x, relu=True, partner=None):
+    """``act(conv(x))`` for a biased 1x1 convolution of ANY even channel counts on a channels-last tensor or channel slice
+    (reference ``network/basenetworks.py:186-242``: the 1x1 convolutions of a ShuffleNetV2K unit, folded with their batch norms),
+    through the split-operand GEMM's unit mode (``opa_gemm_unit_bias_act_f32x3``).  With ``partner`` (``[B, N, H, W]``, may be a
+    slice) the result is ``channel_shuffle(cat((partner, y), 1), 2)`` -- ``[B, 2N, H, W]``, the partner's channels copied into the
+    even positions by the same kernel.  channels_last float32 out.  ``unit_conv_x3_supported`` says whether this can run."""
+    w3, bp = _unit_weight_of(conv)
+    B, K, H, W = x.shape
+    n = conv.out_channels
+    out = torch.empty((B, n if partner is None else 2 * n, H, W), dtype=torch.float32, device=x.device,
+                      memory_format=torch.channels_last)
+    _lib.check(_lib.lib().opa_gemm_unit_bias_act_f32x3(
+        ctypes.c_void_p(x.data_ptr()), _pixel_stride(x), ctypes.c_void_p(w3.data_ptr()), ctypes.c_void_p(bp.data_ptr()),
+        ctypes.c_void_p(partner.data_ptr()) if partner is not None else None,
+        _pixel_stride(partner) if partner is not None else 0, ctypes.c_void_p(out.data_ptr()),
+        B * H * W, n, K, int(bool(relu)), int(X3_TERMS),
+        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_gemm_unit_bias_act_f32x3')
     return out
 
 

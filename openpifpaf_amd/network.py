@@ -270,12 +270,52 @@ class _InvertedResidualK(nn.Module):
                 x = m(x)
         return x
 
+    def _unit_route_supported(self, x):
+        """Can the WHOLE unit run on the project's kernels alone (``_forward_unit``)?  Every 1x1 convolution through the
+        split-operand GEMM's unit mode, every depthwise convolution through the stencil kernel."""
+        if not (x.dtype == torch.float32 and x.dim() == 4):
+            return False
+        branches = (self.branch2,) if self.branch1 is None else (self.branch1, self.branch2)
+        for branch in branches:
+            for m in branch:
+                if not isinstance(m, nn.Conv2d):
+                    continue
+                if m.groups > 1:
+                    if not (hasattr(m, 'w_taps') and m.weight.dtype == x.dtype and fused.dwconv_supported(x, m.kernel_size[0], m.stride[0])):
+                        return False
+                elif not fused._unit_conv_ok(m):
+                    return False
+        first = x if self.branch1 is not None else x.chunk(2, dim=1)[1]
+        return fused.unit_conv_x3_supported(self.branch2[0], first)
+
+    def _dw(self, m, x):
+        return fused.dwconv_bias_act(x, self.taps_of(m), m.bias, m.kernel_size[0], m.stride[0])
+
+    def _forward_unit(self, x):
+        """Three launches (five in a first unit): GEMM + bias + ReLU on the channel slice, the depthwise stencil, GEMM + bias + ReLU
+        stored into the shuffled position with the pass-through half copied by the same kernel."""
+        b2 = self.branch2
+        if self.branch1 is None:
+            x1, x2 = x.chunk(2, dim=1)
+        else:
+            x1, x2 = fused.conv1x1_unit_x3(self.branch1[2], self._dw(self.branch1[0], x)), x
+        h = self._dw(b2[3], fused.conv1x1_unit_x3(b2[0], x2))
+        return fused.conv1x1_unit_x3(b2[5], h, partner=x1)
+
+    def _forward_fused(self, x):
+        if self.branch1 is None:
+            x1, x2 = x.chunk(2, dim=1)
+            return fused.channel_interleave(x1, self._run(self.branch2, x2))
+        return fused.channel_interleave(self._run(self.branch1, x), self._run(self.branch2, x))
+
     def forward(self, x):
         if self.fused and x.is_cuda:
-            if self.branch1 is None:
-                x1, x2 = x.chunk(2, dim=1)
-                return fused.channel_interleave(x1, self._run(self.branch2, x2))
-            return fused.channel_interleave(self._run(self.branch1, x), self._run(self.branch2, x))
+            if self._unit_route_supported(x):       # ONE decision per unit: its output pixels and its last convolution
+                last, s = self.branch2[5], self.branch2[3].stride[0]
+                pixels = x.shape[0] * ((x.shape[2] - 1) // s + 1) * ((x.shape[3] - 1) // s + 1)
+                return fused.pick('unit', pixels, last.in_channels, last.out_channels, True, False,
+                                  lambda: self._forward_unit(x), lambda: self._forward_fused(x), timing=False)
+            return self._forward_fused(x)
         if self.branch1 is None:
             x1, x2 = x.chunk(2, dim=1)
             out = torch.cat((x1, self.branch2(x2)), dim=1)
@@ -309,8 +349,19 @@ class ShuffleNetV2K(BaseNetwork):
         self.conv5 = nn.Sequential(
             nn.Conv2d(inp, ch[-1], 1, bias=False), nn.BatchNorm2d(ch[-1]), nn.ReLU(inplace=True))
 
+    fused = False
+
+    def enable_fused_(self):
+        """conv5 may run through the split-operand GEMM's unit mode (bias + ReLU inside); no parameter or buffer changes."""
+        self.fused = True
+
     def forward(self, x):
-        return self.conv5(self.stage4(self.stage3(self.stage2(self.input_block(x)))))
+        x = self.stage4(self.stage3(self.stage2(self.input_block(x))))
+        conv = self.conv5[0]
+        if self.fused and x.is_cuda and fused.unit_conv_x3_supported(conv, x):
+            return fused.pick('unit', x.shape[0] * x.shape[2] * x.shape[3], conv.in_channels, conv.out_channels, False, False,
+                              lambda: fused.conv1x1_unit_x3(conv, x), lambda: self.conv5(x), timing=False)
+        return self.conv5(x)
 
 
 BASE_FACTORIES = {
@@ -336,6 +387,12 @@ class CompositeField4(nn.Module):
             conv, x0 = self.conv, x                                                # the split-operand GEMM where that is faster
             x = fused.pick('head', x0.shape[0] * x0.shape[2] * x0.shape[3], conv.in_channels, conv.out_channels, False, False,
                            lambda: fused.head_conv_x3(conv, x0), lambda: conv(x0))
+        elif not self.training and self.conv.in_channels % 64 != 0 and fused.X3_HEAD and fused.unit_conv_x3_supported(self.conv, x):
+            # input channels that are no multiple of 64 (k16: 1392): the unit mode of the same kernel, N tail native (no padded
+            # pitch, no copy-out), decided like the units: the table, else by size, never timed
+            conv, x0 = self.conv, x
+            x = fused.pick('unit', x0.shape[0] * x0.shape[2] * x0.shape[3], conv.in_channels, conv.out_channels, False, False,
+                           lambda: fused.conv1x1_unit_x3(conv, x0, relu=False), lambda: conv(x0), timing=False)
         else:
             x = self.conv(x)
         if self.fused_epilogue and fused.head_epilogue_supported(x, self.meta, self.training):
@@ -438,10 +495,10 @@ def fuse_conv_bn_(model):
 
 def optimize_for_inference_(model):
     """Fold every conv+BN pair, then switch the ResNet blocks to the fused-epilogue forward
-    (conv without bias followed by ONE ``fused.bias_act_`` pass) and the ShuffleNetV2K units to the HIP depthwise /
-    interleave kernels."""
+    (conv without bias followed by ONE ``fused.bias_act_`` pass) and the ShuffleNetV2K units and ``conv5`` to the HIP depthwise /
+    interleave kernels and the split-operand GEMM's unit mode."""
     fuse_conv_bn_(model)
     for m in model.modules():
-        if isinstance(m, (_Bottleneck, _BasicBlock, Resnet, _InvertedResidualK)):
+        if isinstance(m, (_Bottleneck, _BasicBlock, Resnet, _InvertedResidualK, ShuffleNetV2K)):
             m.enable_fused_()
     return model
