@@ -461,7 +461,7 @@ int opa_conv3x3_winograd_f32x3(const float* x_dev, const void* u3_dev, const flo
  * network/basenetworks.py:186-268; MIOpen runs it as a grouped MFMA convolution, ~100x slower).
  *  x_dev [B, h, w, *] with x_pixel_stride elements between pixels (a channel slice of a wider tensor is fine),
  *  w_dev [k*k, channels] (tap-major), bias_dev [channels] or NULL, out_dev [B, ho, wo, *] with out_pixel_stride;
- *  dtype 0 = float32, 2 = bfloat16 (float32 accumulation). */
+ *  dtype 0 = float32, 2 = bfloat16 (float32 accumulation).  batch * ho must not exceed 65535 (OPA_ERR_INVALID_ARGUMENT). */
 int opa_dwconv_bias_act(const void* x_dev, int64_t x_pixel_stride, const void* w_dev, const void* bias_dev,
                         void* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w,
                         int32_t channels, int32_t k, int32_t stride, int32_t dtype, int32_t relu, void* stream);

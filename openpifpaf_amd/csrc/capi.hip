@@ -976,6 +976,8 @@ int opa_dwconv_bias_act(const void* x_dev, int64_t x_pixel_stride, const void* w
     if (!x_dev || !w_dev || !out_dev || batch <= 0 || h <= 0 || w <= 0 || channels <= 0 || x_pixel_stride < channels ||
         out_pixel_stride < channels || (k != 3 && k != 5) || (stride != 1 && stride != 2) || (dtype != 0 && dtype != 2))
         return fail(OPA_ERR_INVALID_ARGUMENT, "opa_dwconv_bias_act: bad arguments");
+    if ((int64_t)batch * (((int64_t)h + 2 * (k / 2) - k) / stride + 1) > 65535)          // grid.y of the stencil kernel (dwconv.hip)
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_dwconv_bias_act: batch * output rows must not exceed 65535");
     hipError_t e = launch_dwconv(x_dev, x_pixel_stride, w_dev, bias_dev, out_dev, out_pixel_stride, batch, h, w, channels,
                                  k, stride, dtype, relu, (hipStream_t)stream);
     if (e != hipSuccess) return fail_hip(e, "depthwise convolution");
