@@ -105,7 +105,7 @@ typedef struct opa_shape {
 /* The structs above are passed by pointer and have grown over time (opa_shape::cifhr_pool_tiles is the latest field): a
  * caller built against another header would make the library read past its struct.  Check once at start-up that
  * opa_abi_version() == OPA_ABI_VERSION and opa_shape_bytes() == sizeof(opa_shape), opa_params_bytes() == sizeof(opa_params). */
-#define OPA_ABI_VERSION 7
+#define OPA_ABI_VERSION 8             /* 8: opa_det_post, opa_cifdet_nms, opa_cifdet_decode_nms */
 int opa_abi_version(void);
 size_t opa_shape_bytes(void);
 size_t opa_params_bytes(void);
@@ -339,7 +339,9 @@ int opa_grow_connection_blend(const float* rows_dev, int32_t n, double x, double
  *  boxes_dev       [B, max_detections, 4]  (x0, y0, x1, y1)
  *  counts_dev      int32 [B]
  * max_detections is the reference's static CifDet::max_detections_before_nms (120, cifdet.cpp:16).
- * The IoU NMS that follows is host-side Python in the reference too (decoder/cifdet.py:62-72). */
+ * These are the reference's PRE-NMS candidates.  The IoU NMS, score filter and box conversion that the reference runs in host
+ * Python behind them (decoder/cifdet.py:60-91) are opa_cifdet_nms / opa_cifdet_decode_nms below: one more kernel on the same
+ * stream, so that only final detections leave the device. */
 typedef struct opa_det_shape {
     int32_t batch, n_fields, field_h, field_w, stride, max_detections;
 } opa_det_shape;
@@ -348,6 +350,54 @@ int opa_cifdet_decode(const opa_det_shape* shape, const opa_params* params, cons
                       void* workspace_dev, size_t workspace_bytes,
                       int64_t* categories_dev, float* scores_dev, float* boxes_dev, int32_t* counts_dev,
                       void* stream);
+
+/* ref: decoder/cifdet.py:16-21,60-91  the class attributes of the reference's Python CifDet and what its __call__ does with
+ * them after the native call: torchvision batched_nms (nms when by_category is 0) at iou_threshold, scores of suppressed
+ * candidates multiplied by `suppression`, candidates kept where the score exceeds instance_threshold, boxes as (x, y, w, h).
+ * Defaults in comments; check opa_det_post_bytes() == sizeof(opa_det_post) once at start-up, like the structs above. */
+typedef struct opa_det_post {
+    double iou_threshold;       /* CifDet.iou_threshold       0.5   compared in double                      */
+    double suppression;         /* CifDet.suppression         0.1   applied as a float32 factor             */
+    double instance_threshold;  /* CifDet.instance_threshold  0.15  compared as a float32                   */
+    int32_t by_category;        /* CifDet.nms_by_category     1     boxes of different categories never suppress each other */
+} opa_det_post;
+size_t opa_det_post_bytes(void);
+void opa_default_det_post(opa_det_post* out);
+
+/* Candidates per image the NMS kernel takes (its suppression matrix lives in LDS: 128 KB of row masks at 1024). */
+#define OPA_CIFDET_NMS_MAX 1024
+
+/* The post-processing alone, from candidate arrays laid out as opa_cifdet_decode writes them (counts_dev int32 [B]: valid
+ * candidates per image, clamped to 0 .. max_detections; any score order) to
+ *  out_categories_dev int64 [B, max_detections], out_scores_dev [B, max_detections],
+ *  out_boxes_dev [B, max_detections, 4] (x, y, w, h), out_counts_dev int32 [B]
+ * -- the surviving candidates of each image in CANDIDATE order (not re-sorted: the reference masks), rows behind
+ * out_counts_dev[b] are not written.  The outputs may be the input arrays.  Greedy NMS in stable descending-score order; IoU
+ * from the float32 corners in double, iou = inter / max(area_a + area_b - inter, 1e-12), suppressed when iou > iou_threshold.
+ * Against the host model (the package's decoder.CifDet._post, i.e. torchvision's nms / batched_nms):
+ *  - by_category 0: the host evaluates the same formula in FLOAT32, threshold included (0.3 becomes 0.30000001).  The kept
+ *    set is the host's wherever no pair's IoU lies within float32 rounding of the formula of the threshold (about 1e-6 * IoU).
+ *  - by_category 1: the host adds category * (largest coordinate + 1) to the corners instead of comparing categories; that
+ *    differs from the category test here by double rounding (1e-13), and where a corner lies below -1, for which the
+ *    host's shifted boxes of neighbouring categories can still overlap.  Here different categories never suppress each other.
+ * One kernel on `stream`; no device memory beyond the arguments.  post NULL = the defaults.  Above 64 KB of LDS (max_detections
+ * beyond about 600) the first call on a device also raises the kernel's LDS limit (hipFuncSetAttribute): make that first call
+ * outside a stream capture; later calls and smaller capacities capture freely.
+ * max_detections > OPA_CIFDET_NMS_MAX: OPA_ERR_INVALID_ARGUMENT, nothing is queued. */
+int opa_cifdet_nms(const opa_det_post* post, int32_t batch, int32_t max_detections,
+                   const int64_t* categories_dev, const float* scores_dev, const float* boxes_dev, const int32_t* counts_dev,
+                   int64_t* out_categories_dev, float* out_scores_dev, float* out_boxes_dev, int32_t* out_counts_dev,
+                   void* stream);
+
+/* opa_cifdet_decode followed by opa_cifdet_nms on the same stream, in the caller's output arrays: on return of the queued work
+ * categories_dev / scores_dev / boxes_dev (x, y, w, h) / counts_dev hold the FINAL detections of every image; rows behind
+ * counts_dev[b] hold leftovers of the candidates.  Same workspace as opa_cifdet_decode.
+ * shape->max_detections > OPA_CIFDET_NMS_MAX: OPA_ERR_INVALID_ARGUMENT, nothing is queued (decode with opa_cifdet_decode and
+ * post-process on the host). */
+int opa_cifdet_decode_nms(const opa_det_shape* shape, const opa_params* params, const opa_det_post* post,
+                          const float* field_dev, void* workspace_dev, size_t workspace_bytes,
+                          int64_t* categories_dev, float* scores_dev, float* boxes_dev, int32_t* counts_dev,
+                          void* stream);
 
 /* ---- producer-side helper ------------------------------------------------ */
 /* Fused convolution epilogue of the field-producing network (no reference counterpart:

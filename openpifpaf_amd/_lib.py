@@ -55,7 +55,7 @@ class Params(ctypes.Structure):
         return other
 
 
-ABI_VERSION = 7                      # OPA_ABI_VERSION of include/openpifpaf_amd.h
+ABI_VERSION = 8                      # OPA_ABI_VERSION of include/openpifpaf_amd.h
 
 
 class Debug(ctypes.Structure):
@@ -76,6 +76,15 @@ class Debug(ctypes.Structure):
 class DetShape(ctypes.Structure):
     """``opa_det_shape``."""
     _fields_ = [(n, ctypes.c_int32) for n in ('batch', 'n_fields', 'field_h', 'field_w', 'stride', 'max_detections')]
+
+
+class DetPost(ctypes.Structure):
+    """``opa_det_post``: what the reference's Python ``CifDet`` does behind its native call (``decoder/cifdet.py:16-21,60-91``)."""
+    _fields_ = [('iou_threshold', ctypes.c_double), ('suppression', ctypes.c_double),
+                ('instance_threshold', ctypes.c_double), ('by_category', ctypes.c_int32)]
+
+
+CIFDET_NMS_MAX = 1024                # OPA_CIFDET_NMS_MAX
 
 
 class Shape(ctypes.Structure):
@@ -130,6 +139,10 @@ SYMBOLS = {
     'opa_grow_connection_blend': (ctypes.c_int, [_vp, _i32, _dbl, _dbl, _dbl, _dbl, _i32, _P(_dbl), _vp]),
     'opa_cifdet_workspace_bytes': (_sz, [_P(DetShape)]),
     'opa_cifdet_decode': (ctypes.c_int, [_P(DetShape), _P(Params), _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    'opa_det_post_bytes': (_sz, []),
+    'opa_default_det_post': (None, [_P(DetPost)]),
+    'opa_cifdet_nms': (ctypes.c_int, [_P(DetPost), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'opa_cifdet_decode_nms': (ctypes.c_int, [_P(DetShape), _P(Params), _P(DetPost), _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     'opa_bias_act': (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     'opa_gemm_bias_act_bf16': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     'opa_gemm_pro_bias_act_bf16': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
@@ -170,11 +183,14 @@ def lib():
             fn.argtypes = argtypes
         # the structs are passed by pointer: a library built from another header would read past (or short of) them
         if handle.opa_abi_version() != ABI_VERSION or handle.opa_shape_bytes() != ctypes.sizeof(Shape) or \
-                handle.opa_params_bytes() != ctypes.sizeof(Params) or handle.opa_debug_bytes() != ctypes.sizeof(Debug):
+                handle.opa_params_bytes() != ctypes.sizeof(Params) or handle.opa_debug_bytes() != ctypes.sizeof(Debug) or \
+                handle.opa_det_post_bytes() != ctypes.sizeof(DetPost):
             raise NativeError('openpifpaf_amd: %s was built from another include/openpifpaf_amd.h (ABI %d, opa_shape %d bytes, '
-                              'opa_params %d bytes; this package: ABI %d, %d, %d): rebuild it' % (
+                              'opa_params %d, opa_debug %d, opa_det_post %d; this package: ABI %d, %d, %d, %d, %d): rebuild it' % (
                                   LIB_PATH, handle.opa_abi_version(), handle.opa_shape_bytes(), handle.opa_params_bytes(),
-                                  ABI_VERSION, ctypes.sizeof(Shape), ctypes.sizeof(Params)))
+                                  handle.opa_debug_bytes(), handle.opa_det_post_bytes(),
+                                  ABI_VERSION, ctypes.sizeof(Shape), ctypes.sizeof(Params), ctypes.sizeof(Debug),
+                                  ctypes.sizeof(DetPost)))
         _lib = handle
     return _lib
 

@@ -771,6 +771,58 @@ int opa_cifdet_decode(const opa_det_shape* shape, const opa_params* params, cons
     return OPA_OK;
 }
 
+size_t opa_det_post_bytes(void) { return sizeof(opa_det_post); }
+
+void opa_default_det_post(opa_det_post* out) {                       // decoder/cifdet.py:17-20
+    if (!out) return;
+    out->iou_threshold = 0.5; out->suppression = 0.1; out->instance_threshold = 0.15; out->by_category = 1;
+}
+
+static int queue_cifdet_nms(const opa_det_post* post, int32_t batch, int32_t max_detections, const int64_t* categories_dev,
+                            const float* scores_dev, const float* boxes_dev, const int32_t* counts_dev,
+                            int64_t* out_categories_dev, float* out_scores_dev, float* out_boxes_dev, int32_t* out_counts_dev,
+                            void* stream) {
+    opa_det_post hp;
+    if (post) hp = *post; else opa_default_det_post(&hp);
+    DetNmsArgs a;
+    a.B = batch; a.max_det = max_detections; a.by_category = hp.by_category != 0;
+    a.iou_threshold = hp.iou_threshold; a.suppression = (float)hp.suppression; a.instance_threshold = (float)hp.instance_threshold;
+    a.categories = categories_dev; a.scores = scores_dev; a.boxes = boxes_dev; a.counts = counts_dev;
+    a.out_categories = out_categories_dev; a.out_scores = out_scores_dev; a.out_boxes = out_boxes_dev; a.out_counts = out_counts_dev;
+    hipError_t e = launch_cifdet_nms(a, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "cifdet nms");
+    return OPA_OK;
+}
+
+int opa_cifdet_nms(const opa_det_post* post, int32_t batch, int32_t max_detections,
+                   const int64_t* categories_dev, const float* scores_dev, const float* boxes_dev, const int32_t* counts_dev,
+                   int64_t* out_categories_dev, float* out_scores_dev, float* out_boxes_dev, int32_t* out_counts_dev,
+                   void* stream) {
+    if (!categories_dev || !scores_dev || !boxes_dev || !counts_dev || !out_categories_dev || !out_scores_dev || !out_boxes_dev ||
+        !out_counts_dev)
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_cifdet_nms: null argument");
+    if (batch <= 0 || max_detections <= 0) return fail(OPA_ERR_INVALID_ARGUMENT, "opa_cifdet_nms: batch and max_detections must be positive");
+    if (max_detections > OPA_CIFDET_NMS_MAX)
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_cifdet_nms: max_detections above OPA_CIFDET_NMS_MAX (the row masks would not fit the LDS)");
+    return queue_cifdet_nms(post, batch, max_detections, categories_dev, scores_dev, boxes_dev, counts_dev, out_categories_dev,
+                            out_scores_dev, out_boxes_dev, out_counts_dev, stream);
+}
+
+int opa_cifdet_decode_nms(const opa_det_shape* shape, const opa_params* params, const opa_det_post* post,
+                          const float* field_dev, void* workspace_dev, size_t workspace_bytes,
+                          int64_t* categories_dev, float* scores_dev, float* boxes_dev, int32_t* counts_dev,
+                          void* stream) {
+    if (!shape) return fail(OPA_ERR_INVALID_ARGUMENT, "opa_cifdet_decode_nms: null argument");
+    if (shape->max_detections > OPA_CIFDET_NMS_MAX)                      // before anything is queued
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_cifdet_decode_nms: max_detections above OPA_CIFDET_NMS_MAX: decode with "
+                                              "opa_cifdet_decode and post-process on the host");
+    const int rc = opa_cifdet_decode(shape, params, field_dev, workspace_dev, workspace_bytes, categories_dev, scores_dev,
+                                     boxes_dev, counts_dev, stream);
+    if (rc != OPA_OK) return rc;
+    return queue_cifdet_nms(post, shape->batch, shape->max_detections, categories_dev, scores_dev, boxes_dev, counts_dev,
+                            categories_dev, scores_dev, boxes_dev, counts_dev, stream);      // in place
+}
+
 int opa_bias_act(void* x_dev, const void* bias_dev, const void* residual_dev, int64_t rows, int32_t channels,
                  int32_t dtype, int32_t relu, void* stream) {
     if (!x_dev || !bias_dev || rows < 0 || channels <= 0 || dtype < 0 || dtype > 2)

@@ -242,6 +242,18 @@ struct DetArgs {
 };
 hipError_t launch_cifdet_collect(const DetArgs& a, const DevParams& p, hipStream_t st);
 
+// IoU NMS + score filter + xywh conversion of the candidates above (cifdet.hip: cifdet_nms_kernel).  The outputs may be the
+// input arrays (every candidate is in registers or LDS before the first result is stored).
+constexpr int kDetNmsMax = 1024;          // OPA_CIFDET_NMS_MAX: candidates per image whose row masks fit the LDS
+struct DetNmsArgs {
+    int B, max_det, by_category;
+    double iou_threshold; float suppression, instance_threshold;
+    const int64_t* categories; const float* scores; const float* boxes; const int32_t* counts;
+    int64_t* out_categories; float* out_scores; float* out_boxes; int32_t* out_counts;
+};
+size_t cifdet_nms_lds_bytes(int max_det);
+hipError_t launch_cifdet_nms(const DetNmsArgs& a, hipStream_t st);
+
 hipError_t launch_bias_act(void* x, const void* bias, const void* res, long long rows, int channels, int dtype,
                            int relu, hipStream_t st);
 

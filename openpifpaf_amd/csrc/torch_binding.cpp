@@ -6,7 +6,7 @@
 // (export_torchscript.py:15-43) and loaded from C++ (cpp/cli_video.cpp:48-64).  This file is the
 // same surface for the HIP path, under the namespaces
 //     torch.ops.openpifpaf_amd.set_quiet
-//     torch.classes.openpifpaf_amd_decoder.{CifCaf,CifDet} (+ call_batch)
+//     torch.classes.openpifpaf_amd_decoder.{CifCaf,CifDet} (+ call_batch; CifDet: + nms, call_batch_nms)
 //     torch.ops.openpifpaf_amd_decoder.grow_connection_blend
 //     torch.classes.openpifpaf_amd_decoder_utils.{CifHr,CifSeeds,CafScored} (stage objects + static tunables),
 //                                               CifDetSeeds, NMSKeypoints (static tunables),
@@ -218,29 +218,85 @@ struct CifDet : torch::CustomClassHolder {
     static int64_t max_detections_before_nms;        // cifdet.cpp:16
     torch::Tensor workspace;
 
-    std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> call_batch(const torch::Tensor& field_in,
-                                                                                       int64_t stride) {
-        torch::Tensor field = to_device_f32(field_in);
-        TORCH_CHECK(field.dim() == 5 && field.size(2) == 6, "expected a CifDet field [B,F,6,H,W]");
+    // what call_batch and call_batch_nms share: the field on the device, the shape, the workspace and the four outputs
+    struct Call {
+        torch::Tensor field, cat, sc, bx, cnt;
         opa_det_shape s;
-        s.batch = (int32_t)field.size(0); s.n_fields = (int32_t)field.size(1);
-        s.field_h = (int32_t)field.size(3); s.field_w = (int32_t)field.size(4);
+    };
+    Call prepare(const torch::Tensor& field_in, int64_t stride) {
+        Call c;
+        c.field = to_device_f32(field_in);
+        TORCH_CHECK(c.field.dim() == 5 && c.field.size(2) == 6, "expected a CifDet field [B,F,6,H,W]");
+        opa_det_shape& s = c.s;
+        s.batch = (int32_t)c.field.size(0); s.n_fields = (int32_t)c.field.size(1);
+        s.field_h = (int32_t)c.field.size(3); s.field_w = (int32_t)c.field.size(4);
         s.stride = (int32_t)stride; s.max_detections = (int32_t)max_detections_before_nms;
         const size_t need = opa_cifdet_workspace_bytes(&s);
         TORCH_CHECK(need > 0, "opa_cifdet_workspace_bytes: ", opa_last_error());
-        if (!workspace.defined() || (size_t)workspace.numel() < need || workspace.device() != field.device())
-            workspace = torch::empty({(int64_t)need}, torch::dtype(torch::kUInt8).device(field.device()));
-        auto opts = torch::TensorOptions().device(field.device());
+        if (!workspace.defined() || (size_t)workspace.numel() < need || workspace.device() != c.field.device())
+            workspace = torch::empty({(int64_t)need}, torch::dtype(torch::kUInt8).device(c.field.device()));
+        auto opts = torch::TensorOptions().device(c.field.device());
         const int64_t M = s.max_detections;
-        torch::Tensor cat = torch::empty({s.batch, M}, opts.dtype(torch::kInt64));
-        torch::Tensor sc = torch::empty({s.batch, M}, opts.dtype(torch::kFloat32));
-        torch::Tensor bx = torch::empty({s.batch, M, 4}, opts.dtype(torch::kFloat32));
-        torch::Tensor cnt = torch::empty({s.batch}, opts.dtype(torch::kInt32));
-        check(opa_cifdet_decode(&s, nullptr, field.data_ptr<float>(), workspace.data_ptr(), (size_t)workspace.numel(),
-                                cat.data_ptr<int64_t>(), sc.data_ptr<float>(), bx.data_ptr<float>(),
-                                cnt.data_ptr<int32_t>(), current_stream(field)),
+        c.cat = torch::empty({s.batch, M}, opts.dtype(torch::kInt64));
+        c.sc = torch::empty({s.batch, M}, opts.dtype(torch::kFloat32));
+        c.bx = torch::empty({s.batch, M, 4}, opts.dtype(torch::kFloat32));
+        c.cnt = torch::empty({s.batch}, opts.dtype(torch::kInt32));
+        return c;
+    }
+
+    std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> call_batch(const torch::Tensor& field_in,
+                                                                                       int64_t stride) {
+        Call c = prepare(field_in, stride);
+        check(opa_cifdet_decode(&c.s, nullptr, c.field.data_ptr<float>(), workspace.data_ptr(), (size_t)workspace.numel(),
+                                c.cat.data_ptr<int64_t>(), c.sc.data_ptr<float>(), c.bx.data_ptr<float>(),
+                                c.cnt.data_ptr<int32_t>(), current_stream(c.field)),
               "opa_cifdet_decode");
-        return std::make_tuple(cat, sc, bx, cnt);
+        return std::make_tuple(c.cat, c.sc, c.bx, c.cnt);
+    }
+
+    static opa_det_post post_of(double iou_threshold, double suppression, double instance_threshold, bool by_category) {
+        opa_det_post p;
+        p.iou_threshold = iou_threshold; p.suppression = suppression; p.instance_threshold = instance_threshold;
+        p.by_category = by_category ? 1 : 0;
+        return p;
+    }
+
+    // decoder/cifdet.py:60-91 on the device (opa_cifdet_nms): candidates as call_batch returns them -> (categories [B,max],
+    // scores [B,max], boxes [B,max,4] as x y w h, counts [B]), the survivors of every image in candidate order
+    std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> nms(
+            const torch::Tensor& categories, const torch::Tensor& scores, const torch::Tensor& boxes, const torch::Tensor& counts,
+            double iou_threshold, double suppression, double instance_threshold, bool by_category) {
+        torch::Tensor sc = to_device_f32(scores), bx = to_device_f32(boxes);
+        torch::Tensor cat = categories.to(sc.device()).to(torch::kInt64).contiguous();
+        torch::Tensor cnt = counts.to(sc.device()).to(torch::kInt32).contiguous();
+        TORCH_CHECK(cat.dim() == 2 && sc.sizes() == cat.sizes() && bx.dim() == 3 && bx.size(0) == cat.size(0) &&
+                    bx.size(1) == cat.size(1) && bx.size(2) == 4 && cnt.dim() == 1 && cnt.size(0) == cat.size(0),
+                    "expected categories / scores [B,max], boxes [B,max,4], counts [B]");
+        torch::Tensor ocat = torch::empty_like(cat), osc = torch::empty_like(sc), obx = torch::empty_like(bx),
+                      ocnt = torch::empty_like(cnt);
+        const opa_det_post p = post_of(iou_threshold, suppression, instance_threshold, by_category);
+        check(opa_cifdet_nms(&p, (int32_t)cat.size(0), (int32_t)cat.size(1), cat.data_ptr<int64_t>(), sc.data_ptr<float>(),
+                             bx.data_ptr<float>(), cnt.data_ptr<int32_t>(), ocat.data_ptr<int64_t>(), osc.data_ptr<float>(),
+                             obx.data_ptr<float>(), ocnt.data_ptr<int32_t>(), current_stream(sc)),
+              "opa_cifdet_nms");
+        if (!scores.is_cuda()) return std::make_tuple(ocat.cpu(), osc.cpu(), obx.cpu(), ocnt.cpu());
+        return std::make_tuple(ocat, osc, obx, ocnt);
+    }
+
+    // call_batch + nms in one native call (opa_cifdet_decode_nms): the final detections of every image
+    std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> call_batch_nms(
+            const torch::Tensor& field_in, int64_t stride, double iou_threshold, double suppression, double instance_threshold,
+            bool by_category) {
+        TORCH_CHECK(max_detections_before_nms <= OPA_CIFDET_NMS_MAX, "max_detections_before_nms above ", OPA_CIFDET_NMS_MAX,
+                    ": use call_batch and post-process on the host");
+        Call c = prepare(field_in, stride);
+        const opa_det_post p = post_of(iou_threshold, suppression, instance_threshold, by_category);
+        check(opa_cifdet_decode_nms(&c.s, nullptr, &p, c.field.data_ptr<float>(), workspace.data_ptr(), (size_t)workspace.numel(),
+                                    c.cat.data_ptr<int64_t>(), c.sc.data_ptr<float>(), c.bx.data_ptr<float>(),
+                                    c.cnt.data_ptr<int32_t>(), current_stream(c.field)),
+              "opa_cifdet_decode_nms");
+        if (!field_in.is_cuda()) return std::make_tuple(c.cat.cpu(), c.sc.cpu(), c.bx.cpu(), c.cnt.cpu());
+        return std::make_tuple(c.cat, c.sc, c.bx, c.cnt);
     }
 
     std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> call(const torch::Tensor& field, int64_t stride) {
@@ -515,7 +571,9 @@ TORCH_LIBRARY(openpifpaf_amd_decoder, m) {
         .def_static("get_max_detections_before_nms", []() { return CifDet::max_detections_before_nms; })
         .def(torch::init<>())
         .def("call", &CifDet::call)
-        .def("call_batch", &CifDet::call_batch);
+        .def("call_batch", &CifDet::call_batch)
+        .def("nms", &CifDet::nms)
+        .def("call_batch_nms", &CifDet::call_batch_nms);
 }
 
 TORCH_LIBRARY(openpifpaf_amd_decoder_utils, m) {

@@ -569,9 +569,59 @@ class CifDet(Decoder):
         return [AnnotationDet(self.metas[0].categories).set(int(c), float(s), b)
                 for c, s, b in zip(categories[mask], scores[mask], boxes)]
 
+    # ---- decode + NMS on the device, ONE copy of the final detections back ------------------------------------------------
+    #: decode lanes of :meth:`batch_async` (native decoder = workspace, stream, output block and pinned host block each), like
+    #: ``CifCaf.decoder_workers``; ``--decoder-workers`` sets both
+    decoder_workers = 2
+
+    def _post_settings(self):
+        return dict(iou_threshold=self.iou_threshold, suppression=self.suppression,
+                    instance_threshold=self.instance_threshold, by_category=self.nms_by_category)
+
+    def _on_device(self):
+        """Does the NMS kernel take the current ``max_detections_before_nms``?  Above its capacity ``_post`` does the work."""
+        return native.CifDet.get_max_detections_before_nms() <= native.CifDet.NMS_MAX
+
+    def _slot(self, slot, batch_size, device):
+        """The device output block and its pinned host twin of ``slot`` ('sync' or a lane index), sized for this batch."""
+        blocks = self.__dict__.setdefault('_blocks', {})
+        key = (batch_size, native.CifDet.get_max_detections_before_nms(), device.index)
+        have = blocks.get(slot)
+        if have is None or have[0] != key:
+            have = (key, native.CifDet.output_block(key[0], key[1], device=device),
+                    native.CifDet.output_block(key[0], key[1], pin_memory=True))
+            blocks[slot] = have
+        return have[1], have[2]
+
+    def _queue(self, cpp_decoder, field, slot):
+        """Decode + NMS + the one D2H copy, queued on the current stream -> the pinned host views (valid once that stream got there)."""
+        field, _ = native._prep(field)
+        (dev_block, dev_views), (host_block, host_views) = self._slot(slot, field.shape[0], field.device)
+        cpp_decoder.call_batch_nms(field, self.metas[0].stride, out=dev_views, **self._post_settings())
+        host_block.copy_(dev_block, non_blocking=True)
+        return host_views
+
+    def _annotations_from_host(self, host_views, n_images):
+        cat, sc, bx, cnt = (v.numpy() for v in host_views)
+        result = []
+        for b in range(n_images):
+            n = int(cnt[b])
+            result.append([AnnotationDet(self.metas[0].categories).set(int(c), float(s), box.copy())
+                           for c, s, box in zip(cat[b, :n], sc[b, :n], bx[b, :n])])
+        return result
+
+    def _decode_fields(self, field):
+        """``field`` [B,F,6,H,W] -> annotations per image, synchronously."""
+        if not self._on_device():
+            cat, sc, bx, cnt = self.cpp_decoder.call_batch(field, self.metas[0].stride)
+            cat, sc, bx, cnt = cat.cpu().numpy(), sc.cpu().numpy(), bx.cpu().numpy(), cnt.cpu().numpy()
+            return [self._post(cat[b, :cnt[b]], sc[b, :cnt[b]], bx[b, :cnt[b]]) for b in range(len(cnt))]
+        host_views = self._queue(self.cpp_decoder, field, 'sync')
+        torch.cuda.current_stream().synchronize()
+        return self._annotations_from_host(host_views, field.shape[0])
+
     def __call__(self, fields, initial_annotations=None):
-        cat, sc, bx = self.cpp_decoder.call(fields[self.metas[0].head_index], self.metas[0].stride)
-        return self._post(cat.cpu().numpy(), sc.cpu().numpy(), bx.cpu().numpy())
+        return self._decode_fields(fields[self.metas[0].head_index].unsqueeze(0))[0]
 
     def batch(self, model, image_batch, *, device=None, gt_anns_batch=None):
         start_nn = time.perf_counter()
@@ -583,11 +633,104 @@ class CifDet(Decoder):
             torch.cuda.current_stream().synchronize()
         self.last_nn_time = time.perf_counter() - start_nn
         start_decoder = time.perf_counter()
-        cat, sc, bx, cnt = self.cpp_decoder.call_batch(heads[self.metas[0].head_index], self.metas[0].stride)
-        cat, sc, bx, cnt = cat.cpu().numpy(), sc.cpu().numpy(), bx.cpu().numpy(), cnt.cpu().numpy()
-        result = [self._post(cat[b, :cnt[b]], sc[b, :cnt[b]], bx[b, :cnt[b]]) for b in range(len(cnt))]
+        result = self._decode_fields(heads[self.metas[0].head_index])
         self.last_decoder_time = time.perf_counter() - start_decoder
         return result
+
+    def __getstate__(self):
+        return {k: v for k, v in self.__dict__.items() if k not in ('worker_pool', '_blocks', '_lanes', '_lane_pending')}
+
+    class Pending:
+        """A batch in flight: ``result()`` waits for ITS lane's event only and builds the annotations."""
+
+        def __init__(self, owner, lane, event, host_views, n_images, t_submit):
+            self.owner, self.lane, self.event, self.host_views, self.n_images, self.t_submit = \
+                owner, lane, event, host_views, n_images, t_submit
+            self._result = None
+            self._error = None
+
+        def done(self):
+            return self._result is not None or self._error is not None or self.event.query()
+
+        def result(self):
+            if self._error is not None:
+                raise self._error                # (the decode failed: every call says so, the lane itself is free again)
+            if self._result is None:
+                try:
+                    self.event.synchronize()
+                    self._result = self.owner._annotations_from_host(self.host_views, self.n_images)
+                    self.owner.last_decoder_time = time.perf_counter() - self.t_submit
+                except Exception as e:           # noqa: BLE001 -- remembered for later calls, raised below
+                    self._error = e
+                    raise
+                finally:
+                    # whatever happened, the ticket is spent: a failed batch is not collected again before later submits
+                    if self.owner._lane_pending.get(self.lane) is self:
+                        del self.owner._lane_pending[self.lane]
+            return self._result
+
+    class _Done:
+        """The ticket of a batch that was decoded synchronously (``max_detections_before_nms`` above the kernel's capacity)."""
+
+        def __init__(self, result):
+            self._result = result
+
+        def done(self):
+            return True
+
+        def result(self):
+            return self._result
+
+    def _decode_lanes(self):
+        n = max(1, int(self.decoder_workers or 1))
+        lanes = getattr(self, '_lanes', None)
+        if lanes is None or len(lanes) != n:
+            for pending in list(getattr(self, '_lane_pending', {}).values()):      # batches in flight on the old lanes first
+                pending.result()
+            native.ensure_hw_queues(n)
+            lanes = [(native.CifDet(), torch.cuda.Stream(priority=-1)) for _ in range(n)]
+            self._lanes, self._lane_pending, self._next_lane = lanes, {}, 0
+        return lanes
+
+    def batch_async(self, model, image_batch, *, device=None, meta_batch=None):
+        """Like :meth:`batch`, but returns at once with a :class:`Pending`: the network is queued on the current stream, decode +
+        NMS + the copy of the detections to pinned host memory on the next lane's stream behind it.  Submit batch *i+1* before
+        asking for batch *i*'s ``result()`` and the two overlap; up to ``decoder_workers`` batches may be in flight (submitting to
+        a lane whose previous batch was not collected yet collects it first: the host block is per lane).  The inverse transform
+        stays with the caller (``AnnotationDet.inverse_transform``): ``meta_batch`` must be None."""
+        if meta_batch is not None:
+            raise ValueError('decoder.CifDet undoes the preprocessing on the host: call AnnotationDet.inverse_transform')
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            if device is not None:
+                image_batch = image_batch.to(device, non_blocking=True)
+            heads = model(image_batch)
+        field = heads[self.metas[0].head_index]
+        if not self._on_device():
+            self.last_nn_time = time.perf_counter() - t0
+            result = self._decode_fields(field)
+            self.last_decoder_time = time.perf_counter() - t0 - self.last_nn_time
+            return CifDet._Done(result)
+        lanes = self._decode_lanes()
+        lane = self._next_lane
+        stale = self._lane_pending.get(lane)
+        if stale is not None:
+            stale.result()
+        self._next_lane = (lane + 1) % len(lanes)
+        cpp_decoder, stream = lanes[lane]
+        field, _ = native._prep(field)
+        ready = torch.cuda.Event()
+        ready.record()                                   # the field is complete on the caller's stream
+        with torch.cuda.stream(stream):
+            stream.wait_event(ready)
+            host_views = self._queue(cpp_decoder, field, lane)
+            field.record_stream(stream)                  # the allocator must not hand the field out before the lane is done
+            done = torch.cuda.Event()
+            done.record(stream)
+        self.last_nn_time = time.perf_counter() - t0               # host time to queue the network (it runs asynchronously)
+        pending = CifDet.Pending(self, lane, done, host_views, field.shape[0], t0)
+        self._lane_pending[lane] = pending
+        return pending
 
 
 class Multi(Decoder):
@@ -694,6 +837,7 @@ def configure(args):
     CifDet.instance_threshold = args.instance_threshold
     if getattr(args, 'decoder_workers', None) is not None:      # reference decoder/factory.py:66-71 sizes its fork pool here
         CifCaf.decoder_workers = max(1, int(args.decoder_workers))
+        CifDet.decoder_workers = CifCaf.decoder_workers
     for dec in _with_tracking():
         dec.configure(args)
     from . import tracking

@@ -622,6 +622,18 @@ class CifDet:
         _device()
         self._workspaces = {}
 
+    def _workspace(self, shape, device):
+        key = (shape.batch, shape.n_fields, shape.field_h, shape.field_w, shape.stride, shape.max_detections, device.index)
+        ws = self._workspaces.get(key)
+        if ws is None:
+            nbytes = _lib.lib().opa_cifdet_workspace_bytes(ctypes.byref(shape))
+            if nbytes == 0:
+                raise _lib.NativeError(_lib.lib().opa_last_error().decode())
+            self._workspaces.clear()
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+            self._workspaces[key] = ws
+        return ws
+
     def call_batch(self, cifdet_field, cifdet_stride, *, params=None):
         """``cifdet_field`` [B,F,6,H,W] -> device tensors (categories [B,max] int64, scores [B,max],
         boxes [B,max,4] (x0,y0,x1,y1), counts [B] int32)."""
@@ -630,15 +642,7 @@ class CifDet:
         if C != 6:
             raise ValueError('expected a CifDet field [B,F,6,H,W], got %s' % (tuple(field.shape),))
         shape = _lib.DetShape(B, F, H, W, int(cifdet_stride), self._max_detections_before_nms)
-        key = (B, F, H, W, int(cifdet_stride), shape.max_detections, field.device.index)
-        ws = self._workspaces.get(key)
-        if ws is None:
-            nbytes = _lib.lib().opa_cifdet_workspace_bytes(ctypes.byref(shape))
-            if nbytes == 0:
-                raise _lib.NativeError(_lib.lib().opa_last_error().decode())
-            self._workspaces.clear()
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=field.device)
-            self._workspaces[key] = ws
+        ws = self._workspace(shape, field.device)
         M = shape.max_detections
         cat = torch.empty((B, M), dtype=torch.int64, device=field.device)
         sc = torch.empty((B, M), dtype=torch.float32, device=field.device)
@@ -656,3 +660,84 @@ class CifDet:
         cat, sc, bx, cnt = self.call_batch(cifdet_field.unsqueeze(0), cifdet_stride)
         n = int(cnt[0])
         return cat[0, :n].clone(), sc[0, :n].clone(), bx[0, :n].clone()
+
+    # ---- the reference's host-side post-processing (decoder/cifdet.py:60-91) on the device ------------------------------
+    NMS_MAX = _lib.CIFDET_NMS_MAX                      #: candidates per image the NMS kernel takes (OPA_CIFDET_NMS_MAX)
+
+    @staticmethod
+    def _post(iou_threshold, suppression, instance_threshold, by_category):
+        return _lib.DetPost(float(iou_threshold), float(suppression), float(instance_threshold), int(bool(by_category)))
+
+    @staticmethod
+    def output_block(batch, max_detections, *, device=None, pin_memory=False):
+        """One byte block holding ``(categories [B,max] int64, scores [B,max], boxes [B,max,4], counts [B] int32)`` as views --
+        on the device the ``out=`` of :meth:`nms` / :meth:`call_batch_nms`, in pinned host memory the target of the ONE copy that
+        brings a batch's detections back.  -> (block, views)."""
+        B, M = int(batch), int(max_detections)
+        sizes = (B * M * 8, B * M * 4, B * M * 16, B * 4)          # (the int64 view first: every view is aligned to its type)
+        if device is None:
+            block = torch.empty(sum(sizes), dtype=torch.uint8)
+            block = block.pin_memory() if pin_memory else block
+        else:
+            block = torch.empty(sum(sizes), dtype=torch.uint8, device=device)
+        o0, o1, o2 = sizes[0], sizes[0] + sizes[1], sizes[0] + sizes[1] + sizes[2]
+        views = (block[:o0].view(torch.int64).view(B, M), block[o0:o1].view(torch.float32).view(B, M),
+                 block[o1:o2].view(torch.float32).view(B, M, 4), block[o2:].view(torch.int32))
+        return block, views
+
+    @staticmethod
+    def _check_out(out, B, M, device):
+        cat, sc, bx, cnt = out
+        want = ((cat, torch.int64, (B, M)), (sc, torch.float32, (B, M)), (bx, torch.float32, (B, M, 4)), (cnt, torch.int32, (B,)))
+        for t, dtype, shape in want:
+            if t.dtype != dtype or tuple(t.shape) != shape or t.device != device or not t.is_contiguous():
+                raise ValueError('out: expected contiguous %s %s on %s, got %s %s on %s' % (
+                    dtype, shape, device, t.dtype, tuple(t.shape), t.device))
+        return out
+
+    def nms(self, categories, scores, boxes, counts, *, iou_threshold=0.5, suppression=0.1, instance_threshold=0.15,
+            by_category=True, out=None):
+        """IoU NMS, score filter and box conversion of candidate arrays laid out as :meth:`call_batch` returns them
+        (``[B,max]`` int64, ``[B,max]``, ``[B,max,4]`` x0 y0 x1 y1, ``[B]`` int32; any score order) -> device tensors
+        ``(categories [B,max], scores [B,max], boxes [B,max,4] as x y w h, counts [B])``: the survivors of every image in
+        candidate order, rows behind ``counts[b]`` not written.  ``out``: four tensors to write into (may be the inputs)."""
+        cat, orig = _prep(categories, torch.int64)
+        sc, bx, cnt = _prep(scores)[0], _prep(boxes)[0], _prep(counts, torch.int32)[0]
+        B, M = cat.shape
+        if tuple(sc.shape) != (B, M) or tuple(bx.shape) != (B, M, 4) or tuple(cnt.shape) != (B,):
+            raise ValueError('expected categories / scores [B,max], boxes [B,max,4], counts [B]')
+        if out is None:
+            out = (torch.empty_like(cat), torch.empty_like(sc), torch.empty_like(bx), torch.empty_like(cnt))
+        ocat, osc, obx, ocnt = self._check_out(out, B, M, cat.device)
+        post = self._post(iou_threshold, suppression, instance_threshold, by_category)
+        _lib.check(_lib.lib().opa_cifdet_nms(ctypes.byref(post), B, M, _ptr(cat), _ptr(sc), _ptr(bx), _ptr(cnt),
+                                             _ptr(ocat), _ptr(osc), _ptr(obx), _ptr(ocnt), _stream()), 'opa_cifdet_nms')
+        if orig.type != 'cuda':
+            return ocat.to(orig), osc.to(orig), obx.to(orig), ocnt.to(orig)
+        return ocat, osc, obx, ocnt
+
+    def call_batch_nms(self, cifdet_field, cifdet_stride, *, iou_threshold=0.5, suppression=0.1, instance_threshold=0.15,
+                       by_category=True, params=None, out=None):
+        """:meth:`call_batch` followed by :meth:`nms` on the same stream (``opa_cifdet_decode_nms``) -> device tensors
+        ``(categories, scores, boxes as x y w h, counts)``: the FINAL detections of every image."""
+        field, orig = _prep(cifdet_field)
+        B, F, C, H, W = field.shape
+        if C != 6:
+            raise ValueError('expected a CifDet field [B,F,6,H,W], got %s' % (tuple(field.shape),))
+        shape = _lib.DetShape(B, F, H, W, int(cifdet_stride), self._max_detections_before_nms)
+        M = shape.max_detections
+        ws = self._workspace(shape, field.device) if M <= self.NMS_MAX else None       # (above it the call is refused below)
+        if out is None:
+            out = (torch.empty((B, M), dtype=torch.int64, device=field.device),
+                   torch.empty((B, M), dtype=torch.float32, device=field.device),
+                   torch.empty((B, M, 4), dtype=torch.float32, device=field.device),
+                   torch.empty((B,), dtype=torch.int32, device=field.device))
+        cat, sc, bx, cnt = self._check_out(out, B, M, field.device)
+        post = self._post(iou_threshold, suppression, instance_threshold, by_category)
+        _lib.check(_lib.lib().opa_cifdet_decode_nms(
+            ctypes.byref(shape), ctypes.byref(params) if params is not None else None, ctypes.byref(post), _ptr(field),
+            _ptr(ws), ws.numel() if ws is not None else 0, _ptr(cat), _ptr(sc), _ptr(bx), _ptr(cnt), _stream()),
+            'opa_cifdet_decode_nms')
+        if orig.type != 'cuda':
+            cat, sc, bx, cnt = cat.to(orig), sc.to(orig), bx.to(orig), cnt.to(orig)
+        return cat, sc, bx, cnt
