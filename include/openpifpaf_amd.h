@@ -105,7 +105,7 @@ typedef struct opa_shape {
 /* The structs above are passed by pointer and have grown over time (opa_shape::cifhr_pool_tiles is the latest field): a
  * caller built against another header would make the library read past its struct.  Check once at start-up that
  * opa_abi_version() == OPA_ABI_VERSION and opa_shape_bytes() == sizeof(opa_shape), opa_params_bytes() == sizeof(opa_params). */
-#define OPA_ABI_VERSION 8             /* 8: opa_det_post, opa_cifdet_nms, opa_cifdet_decode_nms */
+#define OPA_ABI_VERSION 9             /* 9: opa_pre_image, opa_preprocess_u8, opa_preprocess_workspace_bytes */
 int opa_abi_version(void);
 size_t opa_shape_bytes(void);
 size_t opa_params_bytes(void);
@@ -532,6 +532,59 @@ int opa_channel_interleave(const void* a_dev, int64_t a_pixel_stride, const void
 int opa_head_epilogue(const void* conv_dev, int32_t dtype, int32_t batch, int32_t hc, int32_t wc,
                       int32_t n_fields, int32_t n_components, int32_t upsample, int32_t n_confidences,
                       int32_t n_vectors, uint32_t vector_offset_mask, int32_t n_scales, float* out_dev, void* stream);
+
+/* ---- image preprocessing ------------------------------------------------ */
+/* The evaluation pipeline in front of the network (ref: transforms/scale.py:42-63,150-174 RescaleAbsolute,
+ * transforms/pad.py:15-112 CenterPad / CenterPadTight, transforms/__init__.py:26-33 ToTensor + Normalize) for a whole batch of
+ * packed uint8 RGB frames of any sizes, in at most two kernel launches: a horizontal resampling pass into a uint8
+ * intermediate (only for images whose width changes), then vertical pass + centre pad + normalisation + store.
+ *
+ * One opa_pre_image per image.  All sizes in pixels, offsets as stated.  The caller keeps the table twice: on the host (read
+ * here, for the checks and the launch geometry) and on the device (read by the kernels).
+ *  mode 0 (Pillow's 8-bit BILINEAR resampler, the reference's default without OpenCV): x_table / y_table are the offsets, in
+ *    int32 words into tables_dev, of the axis' coefficient table [1 + ksize][out_size]: row 0 the first source sample of every
+ *    output sample, rows 1..ksize its weights with 22 fractional bits (non-negative, summing to ~2^22: the accumulator is
+ *    int32, starts at 2^21, is shifted right by 22 and clamped to 0..255; the horizontal pass rounds to uint8 first, like
+ *    Pillow).  An axis whose size does not change is copied and its table is not read.
+ *  mode 1 (scipy.ndimage.zoom, order 1: --precise-rescaling): the axis table is i0[n], i1[n], outside[n] (int32) and, from the
+ *    next even word on, w0[n], w1[n] (float64), n = out_size; ksize is 2.  The four products (v * wy) * wx are summed in double
+ *    in scipy's order, zeroed where outside, clamped to 0..255 and rounded as floor(t + 0.5).  No intermediate is used.
+ * Table offsets are multiples of 4 words.  Source indices from the tables are clamped to the frame by the kernels. */
+typedef struct opa_pre_image {
+    int64_t src_offset;       /* bytes from frames_dev to the frame: uint8 [h0, w0, 3], dense, any alignment          */
+    int64_t mid_offset;       /* bytes from workspace_dev to the image's intermediate (mode 0, tw != w0 only): uint8
+                               * [h0, pitch] with pitch = 3 * tw rounded up to 16; a multiple of 16                     */
+    int32_t h0, w0;           /* frame size                                                                            */
+    int32_t th, tw;           /* size after the rescale (equal to h0, w0: no rescale)                                  */
+    int32_t top, left;        /* where the rescaled frame is placed on the canvas; the rest gets the fill colour       */
+    int32_t x_table, x_ksize; /* horizontal coefficient table: offset in int32 words, taps per output sample           */
+    int32_t y_table, y_ksize; /* vertical coefficient table                                                            */
+} opa_pre_image;
+size_t opa_pre_image_bytes(void);
+
+/* Bytes of intermediate workspace a batch needs when its images' mid_offset are assigned in order, each region
+ * h0 * pitch bytes rounded up to 256 (mode 1: 0).  0 with opa_last_error() set for a bad argument. */
+size_t opa_preprocess_workspace_bytes(const opa_pre_image* images_host, int32_t batch, int32_t mode);
+
+/* Queue the passes on `stream`.
+ *  frames_dev     packed frames, 16-B aligned, frames_bytes a multiple of 16 (rows are fetched as aligned 16-B vectors)
+ *  tables_dev     int32 [tables_words], 16-B aligned
+ *  workspace_dev  16-B aligned, workspace_bytes >= opa_preprocess_workspace_bytes (may be NULL when that is 0)
+ *  lut_dev        float32 [3][256]: the normalised value of every byte per channel (the caller forms it with the host
+ *                 pipeline's own expression, (float32(v) / 255 - mean) / std, so the kernels divide nothing)
+ *  out_dev        float32 [batch, 3, canvas_h, canvas_w], or with channels_last != 0 [batch, canvas_h, canvas_w, 3]
+ *  fill_rgb       padding colour, r | g << 8 | b << 16 (the reference: 124, 116, 104)
+ * Checked before anything is queued (OPA_ERR_INVALID_ARGUMENT, the text names the field): null pointers, alignment,
+ * batch < 1, canvas sides < 1, h0 / w0 / th / tw < 1, a placement outside the canvas, ksize < 1, offsets outside their
+ * buffers; a workspace that is too small is OPA_ERR_WORKSPACE.  Limits (OPA_ERR_INVALID_ARGUMENT beyond them): batch and
+ * canvas_h at most 65535; h0 * w0 and h0 * tw below 2^30 per image (which also keeps the horizontal pass' grid,
+ * h0 * ceil(tw / 256) workgroups per image, launchable); the source pixels 256 output columns of one row reach must fit
+ * 64 KB of LDS (a horizontal reduction of up to ~80x). */
+int opa_preprocess_u8(const opa_pre_image* images_host, const opa_pre_image* images_dev, int32_t batch,
+                      const uint8_t* frames_dev, size_t frames_bytes, const int32_t* tables_dev, size_t tables_words,
+                      uint8_t* workspace_dev, size_t workspace_bytes, const float* lut_dev, float* out_dev,
+                      int32_t canvas_h, int32_t canvas_w, int32_t mode, int32_t channels_last, uint32_t fill_rgb,
+                      void* stream);
 
 /* ---- measurement -------------------------------------------------------- */
 /* Per-kernel timing with HIP events on the launch stream (no reference

@@ -55,7 +55,7 @@ class Params(ctypes.Structure):
         return other
 
 
-ABI_VERSION = 8                      # OPA_ABI_VERSION of include/openpifpaf_amd.h
+ABI_VERSION = 9                      # OPA_ABI_VERSION of include/openpifpaf_amd.h
 
 
 class Debug(ctypes.Structure):
@@ -85,6 +85,13 @@ class DetPost(ctypes.Structure):
 
 
 CIFDET_NMS_MAX = 1024                # OPA_CIFDET_NMS_MAX
+
+
+class PreImage(ctypes.Structure):
+    """``opa_pre_image``: one image of a preprocessing batch (sizes in pixels, ``src_offset`` / ``mid_offset`` in bytes, the
+    tables' offsets in int32 words)."""
+    _fields_ = [('src_offset', ctypes.c_int64), ('mid_offset', ctypes.c_int64)] + [(n, ctypes.c_int32) for n in (
+        'h0', 'w0', 'th', 'tw', 'top', 'left', 'x_table', 'x_ksize', 'y_table', 'y_ksize')]
 
 
 class Shape(ctypes.Structure):
@@ -157,6 +164,10 @@ SYMBOLS = {
     'opa_dwconv_bias_act': (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     'opa_channel_interleave': (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp]),
     'opa_head_epilogue': (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _i32, _vp, _vp]),
+    'opa_pre_image_bytes': (_sz, []),
+    'opa_preprocess_workspace_bytes': (_sz, [_P(PreImage), _i32, _i32]),
+    'opa_preprocess_u8': (ctypes.c_int, [_P(PreImage), _vp, _i32, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _i32, _i32, _i32, _i32,
+                                         ctypes.c_uint32, _vp]),
     'opa_profile_begin': (ctypes.c_int, [_vp]),
     'opa_profile_end': (ctypes.c_int, [_i32, _P(ctypes.c_char_p), _P(ctypes.c_float), _P(_i32)]),
 }
@@ -184,13 +195,15 @@ def lib():
         # the structs are passed by pointer: a library built from another header would read past (or short of) them
         if handle.opa_abi_version() != ABI_VERSION or handle.opa_shape_bytes() != ctypes.sizeof(Shape) or \
                 handle.opa_params_bytes() != ctypes.sizeof(Params) or handle.opa_debug_bytes() != ctypes.sizeof(Debug) or \
-                handle.opa_det_post_bytes() != ctypes.sizeof(DetPost):
+                handle.opa_det_post_bytes() != ctypes.sizeof(DetPost) or \
+                handle.opa_pre_image_bytes() != ctypes.sizeof(PreImage):
             raise NativeError('openpifpaf_amd: %s was built from another include/openpifpaf_amd.h (ABI %d, opa_shape %d bytes, '
-                              'opa_params %d, opa_debug %d, opa_det_post %d; this package: ABI %d, %d, %d, %d, %d): rebuild it' % (
+                              'opa_params %d, opa_debug %d, opa_det_post %d, opa_pre_image %d; this package: ABI %d, %d, %d, %d, %d, %d): '
+                              'rebuild it' % (
                                   LIB_PATH, handle.opa_abi_version(), handle.opa_shape_bytes(), handle.opa_params_bytes(),
-                                  handle.opa_debug_bytes(), handle.opa_det_post_bytes(),
+                                  handle.opa_debug_bytes(), handle.opa_det_post_bytes(), handle.opa_pre_image_bytes(),
                                   ABI_VERSION, ctypes.sizeof(Shape), ctypes.sizeof(Params), ctypes.sizeof(Debug),
-                                  ctypes.sizeof(DetPost)))
+                                  ctypes.sizeof(DetPost), ctypes.sizeof(PreImage)))
         _lib = handle
     return _lib
 

@@ -2,6 +2,7 @@
 // layout, decoder handle, and the kernel pipeline of one batched decode.
 #include "common.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstdio>
@@ -1057,6 +1058,102 @@ int opa_head_epilogue(const void* conv_dev, int32_t dtype, int32_t batch, int32_
     hipError_t e = launch_head_epilogue(conv_dev, dtype, batch, hc, wc, n_fields, n_components, upsample, n_confidences,
                                         n_vectors, vector_offset_mask, n_scales, out_dev, (hipStream_t)stream);
     if (e != hipSuccess) return fail_hip(e, "head epilogue");
+    return OPA_OK;
+}
+
+size_t opa_pre_image_bytes(void) { return sizeof(opa_pre_image); }
+
+static size_t pre_mid_bytes(const opa_pre_image& d) { return align_up((size_t)d.h0 * (((size_t)d.tw * 3 + 15) & ~(size_t)15)); }
+
+// the sizes of one descriptor row; `why` names the field
+static bool check_pre_sizes(const opa_pre_image* images, int32_t batch, const char* who, std::string* why) {
+    if (!images) { *why = std::string(who) + ": images_host is null"; return false; }
+    if (batch < 1 || batch > 65535) { *why = std::string(who) + ": batch must be 1..65535"; return false; }
+    for (int32_t b = 0; b < batch; b++) {
+        const opa_pre_image& d = images[b];
+        const char* field = d.h0 < 1 ? "h0" : d.w0 < 1 ? "w0" : d.th < 1 ? "th" : d.tw < 1 ? "tw" : nullptr;
+        if (field) { *why = std::string(who) + ": images[" + std::to_string(b) + "]." + field + " must be at least 1"; return false; }
+        if ((int64_t)d.h0 * d.w0 > 0x3fffffff || (int64_t)d.h0 * d.tw > 0x3fffffff) {
+            *why = std::string(who) + ": images[" + std::to_string(b) + "]: h0 * w0 and h0 * tw must stay below 2^30"; return false;
+        }
+    }
+    return true;
+}
+
+size_t opa_preprocess_workspace_bytes(const opa_pre_image* images_host, int32_t batch, int32_t mode) {
+    std::string why;
+    if (!check_pre_sizes(images_host, batch, "opa_preprocess_workspace_bytes", &why)) { g_error = why; return 0; }
+    if (mode != 0 && mode != 1) { g_error = "opa_preprocess_workspace_bytes: mode must be 0 or 1"; return 0; }
+    size_t total = 0;
+    if (mode == 0)
+        for (int32_t b = 0; b < batch; b++)
+            if (images_host[b].tw != images_host[b].w0) total += pre_mid_bytes(images_host[b]);
+    return total;
+}
+
+int opa_preprocess_u8(const opa_pre_image* images_host, const opa_pre_image* images_dev, int32_t batch,
+                      const uint8_t* frames_dev, size_t frames_bytes, const int32_t* tables_dev, size_t tables_words,
+                      uint8_t* workspace_dev, size_t workspace_bytes, const float* lut_dev, float* out_dev,
+                      int32_t canvas_h, int32_t canvas_w, int32_t mode, int32_t channels_last, uint32_t fill_rgb,
+                      void* stream) {
+    const char* who = "opa_preprocess_u8";
+    auto bad = [&](const std::string& what) { return fail(OPA_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what); };
+    if (!images_dev) return bad("images_dev is null");
+    if (!frames_dev) return bad("frames_dev is null");
+    if (!tables_dev) return bad("tables_dev is null");
+    if (!lut_dev) return bad("lut_dev is null");
+    if (!out_dev) return bad("out_dev is null");
+    std::string why;
+    if (!check_pre_sizes(images_host, batch, who, &why)) return fail(OPA_ERR_INVALID_ARGUMENT, why);
+    if (mode != 0 && mode != 1) return bad("mode must be 0 (Pillow) or 1 (zoom)");
+    if (canvas_h < 1 || canvas_h > 65535) return bad("canvas_h must be 1..65535");
+    if (canvas_w < 1) return bad("canvas_w must be at least 1");
+    if (((uintptr_t)frames_dev | (uintptr_t)tables_dev | (uintptr_t)workspace_dev | (uintptr_t)images_dev) & 15)
+        return bad("frames_dev, tables_dev, workspace_dev and images_dev must be 16-B aligned");
+    if (frames_bytes % 16) return bad("frames_bytes must be a multiple of 16");
+    unsigned h_blocks = 0;
+    int in_cap = 1;
+    size_t ws_need = 0;
+    for (int32_t b = 0; b < batch; b++) {
+        const opa_pre_image& d = images_host[b];
+        const std::string at = "images[" + std::to_string(b) + "].";
+        if (d.top < 0 || d.left < 0 || (int64_t)d.top + d.th > canvas_h || (int64_t)d.left + d.tw > canvas_w)
+            return bad(at + "top / left: the placement lies outside the canvas");
+        if (d.x_ksize < 1) return bad(at + "x_ksize must be at least 1");
+        if (d.y_ksize < 1) return bad(at + "y_ksize must be at least 1");
+        if (d.src_offset < 0 || (uint64_t)d.src_offset + (uint64_t)d.h0 * d.w0 * 3 > frames_bytes)
+            return bad(at + "src_offset: the frame lies outside frames_bytes");
+        const size_t x_words = mode ? ((3 * (size_t)d.tw + 1) & ~(size_t)1) + 4 * (size_t)d.tw : (size_t)(1 + d.x_ksize) * d.tw;
+        const size_t y_words = mode ? ((3 * (size_t)d.th + 1) & ~(size_t)1) + 4 * (size_t)d.th : (size_t)(1 + d.y_ksize) * d.th;
+        if (d.x_table < 0 || d.x_table % 4 || (size_t)d.x_table + x_words > tables_words)
+            return bad(at + "x_table: the table lies outside tables_words or is not a multiple of 4 words");
+        if (d.y_table < 0 || d.y_table % 4 || (size_t)d.y_table + y_words > tables_words)
+            return bad(at + "y_table: the table lies outside tables_words or is not a multiple of 4 words");
+        // source pixels of one row that 256 neighbouring output columns reach (sizes the kernels' LDS)
+        double span;
+        if (mode) {
+            if (d.x_ksize != 2 || d.y_ksize != 2) return bad(at + "x_ksize / y_ksize must be 2 in mode 1");
+            span = std::ceil(255.0 * (d.tw > 1 ? (double)(d.w0 - 1) / (d.tw - 1) : 0.0)) + 3.0;
+        } else if (d.tw != d.w0) {
+            const double scale = (double)d.w0 / d.tw;
+            span = std::ceil(255.0 * scale) + 2.0 * std::ceil(std::max(scale, 1.0)) + 4.0;
+            if (d.mid_offset < 0 || d.mid_offset % 16) return bad(at + "mid_offset must be a non-negative multiple of 16");
+            ws_need = std::max(ws_need, (size_t)d.mid_offset + pre_mid_bytes(d));
+            const unsigned chunks = ((unsigned)d.tw + 255u) / 256u;
+            h_blocks = std::max(h_blocks, (unsigned)d.h0 * chunks);
+        } else {
+            span = 1.0;
+        }
+        in_cap = std::max(in_cap, (int)std::min(span, (double)d.w0));
+    }
+    const size_t lds = mode ? preprocess_zoom_lds_bytes(in_cap) : preprocess_h_lds_bytes(in_cap);
+    if (lds > 65536) return bad("w0 / tw: 256 output columns reach more source pixels than 64 KB of LDS hold");
+    if (ws_need > 0 && !workspace_dev) return bad("workspace_dev is null");
+    if (ws_need > workspace_bytes)
+        return fail(OPA_ERR_WORKSPACE, std::string(who) + ": workspace_bytes is " + std::to_string(workspace_bytes) + ", the batch needs " + std::to_string(ws_need));
+    hipError_t e = launch_preprocess(images_dev, batch, frames_dev, tables_dev, workspace_dev, lut_dev, out_dev, canvas_h, canvas_w,
+                                     mode, channels_last, fill_rgb, h_blocks, in_cap, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "image preprocessing");
     return OPA_OK;
 }
 

@@ -286,6 +286,14 @@ hipError_t launch_channel_interleave(const void* a, long long as, const void* b,
 hipError_t launch_head_epilogue(const void* conv, int dtype, int B, int Hc, int Wc, int n_fields, int n_comp, int us,
                                 int n_conf, int n_vec, unsigned offset_mask, int n_scales, float* out, hipStream_t st);
 
+// Image preprocessing (preprocess.hip): pass H (h_blocks workgroups per image; 0: no image needs it) + pass V, or with
+// `precise` the zoom kernel.  in_cap: source pixels of one row that 256 output columns can reach (sizes the dynamic LDS).
+size_t preprocess_h_lds_bytes(int in_cap);
+size_t preprocess_zoom_lds_bytes(int in_cap);
+hipError_t launch_preprocess(const opa_pre_image* images, int batch, const unsigned char* frames, const int32_t* tables,
+                             unsigned char* ws, const float* lut, float* out, int ch, int cw, int precise, int channels_last,
+                             unsigned fill, unsigned h_blocks, int in_cap, hipStream_t st);
+
 hipError_t launch_blend(const float* rows, int n, double x, double y, double s, double filter_sigmas,
                         int only_max, double* out4_dev, hipStream_t st);
 

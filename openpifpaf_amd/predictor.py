@@ -8,19 +8,21 @@ Preprocessing restates the evaluation pipeline without torchvision:
 ``RescaleAbsolute(long_edge, fast=Predictor.fast_rescaling)`` (reference ``transforms/scale.py:42-63,150-174``;
 ``predictor.py:17,88``).  Like the reference's Predictor the DEFAULT is ``fast_rescaling = True``: without OpenCV
 (absent in this image) that is Pillow's antialiased ``BILINEAR`` resize (``scale.py:55-58``) -- on the host Pillow
-itself, on the device :func:`resize_bilinear_u8`, a restatement of Pillow's 8-bit resampler that is pixel-equal to
+itself, on a GPU the kernels of ``csrc/preprocess.hip`` (any other device: :func:`resize_bilinear_u8`), both pixel-equal to
 it; ``--precise-rescaling`` selects ``scipy.ndimage.zoom(order=1)`` (``scale.py:59-67``), restated for host and
 device by :func:`zoom_linear_u8`.  Then ``CenterPad(long_edge)`` for batch > 1 / ``CenterPadTight(16)`` for batch 1
 (reference ``transforms/pad.py:15-112``) and the ImageNet normalisation (reference ``transforms/__init__.py:26-33``).
 """
 import argparse
+import ctypes
+import functools
 import logging
 import math
 
 import numpy as np
 import torch
 
-from . import decoder, network
+from . import _lib, decoder, network
 
 LOG = logging.getLogger(__name__)
 
@@ -175,6 +177,125 @@ def preprocess_image(image, *, long_edge=None, batch_mode=False, fast=True):
     return torch.from_numpy(np.ascontiguousarray(x.transpose(2, 0, 1))), meta
 
 
+FILL_RGB = (124, 116, 104)           # the reference's padding colour (transforms/pad.py)
+
+
+def normalisation_lut():
+    """float32 ``[3, 256]``: what ToTensor + Normalize make of every byte per channel, formed with the very expression of
+    ``preprocess_image`` (``float32(u8) / 255.0``, then ``(x - mean) / std``): the kernels look the value up and divide
+    nothing, so they equal the host path by construction."""
+    x = np.arange(256, dtype=np.uint8).reshape(256, 1).astype(np.float32) / 255.0
+    x = (x - IMAGENET_MEAN) / IMAGENET_STD
+    return np.ascontiguousarray(x.T)
+
+
+@functools.lru_cache(maxsize=256)
+def _axis_table(in_size, out_size, fast):
+    """-> (int32 words, ksize): one axis' table in the layout ``opa_preprocess_u8`` reads (``include/openpifpaf_amd.h``),
+    padded to a multiple of 4 words.  ``fast``: ``_pil_bilinear_coeffs`` as ``[1 + ksize][out_size]`` (row 0 ``first``);
+    else ``zoom_linear_u8``'s ``i0, i1, outside`` (int32) and ``w0, w1`` (float64), formed in float64 exactly as there."""
+    if fast:
+        first, fixed = _pil_bilinear_coeffs(in_size, out_size)
+        ksize = fixed.shape[1]
+        words = np.concatenate([first[None, :], fixed.T]).astype(np.int32).reshape(-1)
+    else:
+        zoom = (in_size - 1) / (out_size - 1) if out_size > 1 else 0.0
+        cc = np.arange(out_size, dtype=np.float64) * zoom
+        start = np.floor(cc)
+        w0 = 1.0 - (cc - start)
+        w1 = 1.0 - ((start + 1.0) - cc)
+        i0 = np.clip(start.astype(np.int64), 0, in_size - 1)
+        i1 = np.minimum(i0 + 1, in_size - 1)
+        outside = cc > (in_size - 1)
+        ints = np.concatenate([i0, i1, outside.astype(np.int64)]).astype(np.int32)
+        if len(ints) % 2:
+            ints = np.concatenate([ints, np.zeros(1, np.int32)])
+        ksize = 2
+        words = np.concatenate([ints, np.concatenate([w0, w1]).view(np.int32)])
+    words = np.concatenate([words, np.zeros(-len(words) % 4, np.int32)])
+    words.setflags(write=False)
+    return words, ksize
+
+
+_PRE_IMAGE = np.dtype(_lib.PreImage)
+
+
+def _align(n, a):
+    return (n + a - 1) // a * a
+
+
+def _copy_meta(m):
+    return dict(m, offset=m['offset'].copy(), scale=m['scale'].copy(), valid_area=m['valid_area'].copy(),
+                width_height=m['width_height'].copy(), rotation=dict(m['rotation']))
+
+
+@functools.lru_cache(maxsize=1024)
+def _image_geometry(h0, w0, long_edge, batch_mode):
+    """-> ((tw, th, left, top), canvas (h, w), meta) of one frame, step for step as ``preprocess_image`` computes them (cached
+    per frame size: datasets and cameras have few; the meta is a template to copy)."""
+    meta = {'offset': np.array((0.0, 0.0)), 'scale': np.array((1.0, 1.0)), 'hflip': False,
+            'rotation': {'angle': 0.0, 'width': None, 'height': None},
+            'valid_area': np.array((0.0, 0.0, w0 - 1, h0 - 1)), 'width_height': np.array((w0, h0))}
+    tw, th = w0, h0
+    if long_edge:
+        tw, th = _target_size(w0, h0, long_edge)
+        if tw < 1 or th < 1:
+            raise ValueError('a %d x %d frame rescaled to long edge %d has a side of 0 pixels' % (w0, h0, long_edge))
+        sx, sy = (tw - 1) / (w0 - 1), (th - 1) / (h0 - 1)
+        meta['offset'] *= (sx, sy)
+        meta['scale'] *= (sx, sy)
+        meta['valid_area'][:2] *= (sx, sy)
+        meta['valid_area'][2:] *= (sx, sy)
+    if batch_mode:
+        cw, ch = long_edge, long_edge
+    else:
+        cw = math.ceil((tw - 1) / 16) * 16 + 1
+        ch = math.ceil((th - 1) / 16) * 16 + 1
+    left, top = max(0, int((cw - tw) / 2.0)), max(0, int((ch - th) / 2.0))
+    meta['offset'] -= (left, top)
+    meta['valid_area'][:2] += (left, top)
+    return (tw, th, left, top), (max(ch, th), max(cw, tw)), meta
+
+
+def preprocess_plan(sizes, *, long_edge=None, batch_mode=False, fast=True):
+    """Everything ``opa_preprocess_u8`` needs to know about a batch of frames of ``sizes`` (``(h0, w0)`` each), on the
+    host and without any device or library call: per image the geometry ``(tw, th, left, top)`` and the meta exactly as
+    ``preprocess_image`` computes them, the canvas (batch mode: ``long_edge x long_edge``; single-image mode:
+    ``ceil((w - 1) / 16) * 16 + 1`` by the same in ``h``, which must agree for all images), the coefficient tables
+    (cached per ``(in_size, out_size)``), the byte offsets of the packed frames and of the intermediates, and the
+    descriptor table (``_lib.PreImage`` rows as a numpy record array)."""
+    if batch_mode:
+        assert long_edge, '--long-edge must be provided for batch size > 1'
+    geometry, metas, canvases = [], [], []
+    for h0, w0 in sizes:
+        g, canvas, meta = _image_geometry(int(h0), int(w0), long_edge, bool(batch_mode))
+        geometry.append(g)
+        canvases.append(canvas)
+        metas.append(_copy_meta(meta))
+    if len(set(canvases)) != 1:
+        raise ValueError('the frames of a batch need one canvas: give long_edge and batch_mode, or frames of one size')
+    tables, table_at, words = [], {}, 0
+    rows, src, mid = [], 0, 0
+    for (h0, w0), (tw, th, left, top) in zip(sizes, geometry):
+        h0, w0 = int(h0), int(w0)
+        entry = []
+        for key in ((w0, tw), (h0, th)):
+            if key not in table_at:
+                t, ksize = _axis_table(key[0], key[1], bool(fast))
+                table_at[key] = (words, ksize)
+                tables.append(t)
+                words += len(t)
+            entry.extend(table_at[key])
+        resample_h = fast and tw != w0                # pass H writes uint8 [h0, pitch], pitch = 3 * tw rounded up to 16
+        rows.append((src, mid if resample_h else 0, h0, w0, th, tw, top, left) + tuple(entry))     # opa_pre_image's field order
+        src += h0 * w0 * 3
+        if resample_h:
+            mid += _align(h0 * _align(3 * tw, 16), 256)
+    images = np.array(rows, dtype=_PRE_IMAGE)
+    return {'canvas': canvases[0], 'geometry': geometry, 'metas': metas, 'images': images,
+            'tables': np.concatenate(tables), 'frames_bytes': _align(src, 16), 'workspace_bytes': mid}
+
+
 def _as_u8_rgb(image):
     """-> contiguous uint8 ``[H, W, 3]`` numpy array (what ``_to_pil(image)`` holds)."""
     if isinstance(image, np.ndarray) and image.dtype == np.uint8 and image.ndim == 3 and image.shape[2] == 3:
@@ -204,8 +325,85 @@ class _Staging:
             ring['events'][k].synchronize()
         return ring, k
 
+    @classmethod
+    def block(cls, device, nbytes):
+        """A ragged block of at least ``nbytes``: the same ring, keyed by a capacity (a power of two, 1 MiB at least) so that
+        batches of other sizes find it again."""
+        return cls.get(device, (max(1 << 20, 1 << (int(nbytes) - 1).bit_length()),))
 
-def preprocess_batch_device(images, *, long_edge, device, fast=True):
+
+_workspaces = {}
+_luts = {}
+_plans = {}
+
+
+def _preprocess_batch_kernels(frames, *, long_edge, device, fast, channels_last, batch_mode):
+    """``preprocess_batch_device`` on a GPU: the plan's descriptor table, its coefficient tables and the frames go up in ONE
+    pinned block with one asynchronous copy, then ``opa_preprocess_u8`` queues its (at most two) kernels on the current
+    stream."""
+    device = torch.device(device)
+    key = (tuple(f.shape[:2] for f in frames), long_edge, bool(batch_mode), bool(fast))
+    plan = _plans.get(key)                            # a video or a camera repeats its sizes: the plan is built once
+    if plan is None:
+        if len(_plans) > 64:
+            _plans.clear()
+        plan = _plans[key] = preprocess_plan(key[0], long_edge=long_edge, batch_mode=batch_mode, fast=fast)
+    metas = [_copy_meta(m) for m in plan['metas']]
+    return _run_plan(frames, plan, device=device, fast=fast, channels_last=channels_last), metas
+
+
+def _run_plan(frames, plan, *, device, fast, channels_last):
+    """Pack ``plan`` (what :func:`preprocess_plan` returns) and ``frames`` into one pinned block, upload it and queue
+    ``opa_preprocess_u8`` on the current stream -> the float32 batch."""
+    images, tables = plan['images'], plan['tables']
+    off_tables = _align(images.nbytes, 256)
+    off_frames = _align(off_tables + tables.nbytes, 256)
+    total = off_frames + plan['frames_bytes']
+    ring, k = _Staging.block(device, total)
+    host = ring['bufs'][k].numpy()
+    host[:images.nbytes] = images.view(np.uint8)
+    host[off_tables:off_tables + tables.nbytes] = tables.view(np.uint8)
+    for d, f in zip(images, frames):
+        at = off_frames + int(d['src_offset'])
+        host[at:at + f.size] = f.reshape(-1)
+    stream = torch.cuda.current_stream(device)
+    lut_key = str(device)
+    if lut_key not in _luts:                          # once per device: the only other upload
+        _luts[lut_key] = torch.from_numpy(normalisation_lut()).to(device)
+    block = ring['bufs'][k][:total].to(device, non_blocking=True)
+    ring['events'][k] = torch.cuda.Event()
+    ring['events'][k].record(stream)
+    ws_key = (lut_key, stream.cuda_stream)            # per stream: work queued on another one may still read its workspace
+    ws = _workspaces.get(ws_key)
+    if plan['workspace_bytes'] and (ws is None or ws.numel() < plan['workspace_bytes']):
+        ws = _workspaces[ws_key] = torch.empty(_align(plan['workspace_bytes'], 1 << 20), dtype=torch.uint8, device=device)
+    ch, cw = plan['canvas']
+    out = torch.empty((len(frames), 3, ch, cw), dtype=torch.float32, device=device,
+                      memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    base = block.data_ptr()
+    _lib.check(_lib.lib().opa_preprocess_u8(
+        images.ctypes.data_as(ctypes.POINTER(_lib.PreImage)), base, len(frames), base + off_frames, plan['frames_bytes'],
+        base + off_tables, len(tables), ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0,
+        _luts[lut_key].data_ptr(), out.data_ptr(), ch, cw, 0 if fast else 1, 1 if channels_last else 0,
+        FILL_RGB[0] | FILL_RGB[1] << 8 | FILL_RGB[2] << 16, stream.cuda_stream), 'opa_preprocess_u8')
+    return out
+
+
+def preprocess_batch_device(images, *, long_edge, device, fast=True, channels_last=False, batch_mode=True):
+    """Device-side form of ``preprocess_image``.  On a GPU: the kernels of ``csrc/preprocess.hip`` (one
+    upload and at most two launches per batch, :func:`_preprocess_batch_kernels`), in batch mode or with
+    ``batch_mode=False`` on the single-image canvas, as NCHW or ``channels_last``.  On any other device the torch-op model
+    below (batch mode).  -> (float32 ``[B,3,H,W]`` on ``device``, metas).  The pixels EQUAL the host path's."""
+    if torch.device(device).type == 'cuda':
+        return _preprocess_batch_kernels([_as_u8_rgb(image) for image in images], long_edge=long_edge, device=device,
+                                         fast=fast, channels_last=channels_last, batch_mode=batch_mode)
+    if not batch_mode:
+        raise ValueError('the single-image canvas is built by the kernels: it needs a GPU')
+    batch, metas = preprocess_batch_torch(images, long_edge=long_edge, device=device, fast=fast)
+    return (batch.contiguous(memory_format=torch.channels_last) if channels_last else batch), metas
+
+
+def preprocess_batch_torch(images, *, long_edge, device, fast=True):
     """Device-side form of ``preprocess_image`` for batch mode: the uint8 frames are
     uploaded as they are (a quarter of the bytes of normalised float32), rescaled to ``long_edge`` with the
     reference's own arithmetic (:func:`resize_bilinear_u8` = Pillow, or with ``fast=False``
@@ -269,7 +467,7 @@ def _device_constants(device):
 
 class Predictor:
     """Predict from various inputs with a common configuration."""
-    device_preprocess = False      #: batch mode: rescale / pad / normalise on the device instead of with PIL
+    device_preprocess = False      #: rescale / pad / normalise on the device (csrc/preprocess.hip) instead of with PIL
     pipelined = True               #: overlap batch i's decode with batch i+1's preprocessing + network (decoder lanes)
     batch_size = 1
     device = torch.device('cuda') if torch.cuda.is_available() else torch.device('cpu')
@@ -307,6 +505,8 @@ class Predictor:
                            help='rescale the long side of the image (aspect ratio maintained)')
         group.add_argument('--precise-rescaling', dest='fast_rescaling', default=True, action='store_false',
                            help='use more exact image rescaling (requires scipy)')      # reference predictor.py:72-74
+        group.add_argument('--device-preprocess', default=False, action='store_true',
+                           help='rescale, pad and normalise the uint8 frames on the GPU instead of with PIL on the host')
         group.add_argument('--basenet', default=cls.base_name, choices=sorted(network.BASE_FACTORIES))
 
     @classmethod
@@ -314,6 +514,7 @@ class Predictor:
         cls.batch_size = args.batch_size
         cls.long_edge = args.long_edge
         cls.fast_rescaling = getattr(args, 'fast_rescaling', cls.fast_rescaling)
+        cls.device_preprocess = getattr(args, 'device_preprocess', cls.device_preprocess)
         cls.base_name = getattr(args, 'basenet', cls.base_name)
         if getattr(args, 'device', None) is not None:
             cls.device = args.device
@@ -376,7 +577,7 @@ class Predictor:
 
     def _preprocess(self, images):
         batch_mode = self.batch_size > 1
-        if batch_mode and self.device_preprocess and self.device.type == 'cuda':
+        if self.device_preprocess and self.device.type == 'cuda' and (batch_mode or len(images) == 1):
             # on a stream of its own: uploads and resizes of batch i+1 do not queue behind the network of batch i (nor does
             # the host behind them); the network's stream waits for the finished batch only
             if getattr(self, '_pre_stream', None) is None:
@@ -384,7 +585,8 @@ class Predictor:
             main = torch.cuda.current_stream(self.device)
             with torch.cuda.stream(self._pre_stream):
                 batch, metas = preprocess_batch_device(images, long_edge=self.long_edge, device=self.device,
-                                                       fast=self.fast_rescaling)
+                                                       fast=self.fast_rescaling, channels_last=self.channels_last,
+                                                       batch_mode=batch_mode)
                 ready = torch.cuda.Event()
                 ready.record(self._pre_stream)
             main.wait_event(ready)
