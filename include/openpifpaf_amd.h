@@ -484,6 +484,15 @@ int opa_gemm_unit_bias_act_f32x3(const float* a_dev, int64_t a_pitch, const void
                                  const float* partner_dev, int64_t partner_pitch, float* out_dev,
                                  int64_t m, int32_t n, int32_t k, int32_t relu, int32_t terms, void* stream);
 
+/* The same with an activation code and optionally a residual -- the 1x1 convolutions of a MobileNetV3 block (reference
+ * network/basenetworks.py:432-446): act 0 none, 1 ReLU, 2 hardswish (x * min(max(x + 3, 0), 6) / 6 in float32);
+ *     out[m, n] = act(a * w^T + bias + residual[m, n; residual_pitch floats between rows])                 (residual_dev not NULL)
+ * the residual read once, on 8 bytes with an even pitch >= n like the partner.  A residual together with a partner is refused
+ * (OPA_ERR_INVALID_ARGUMENT, nothing runs).  act 0 / 1 without a residual are opa_gemm_unit_bias_act_f32x3's own kernels. */
+int opa_gemm_unit_act_f32x3(const float* a_dev, int64_t a_pitch, const void* w3_dev, const float* bias_dev,
+                            const float* partner_dev, int64_t partner_pitch, const float* residual_dev, int64_t residual_pitch,
+                            float* out_dev, int64_t m, int32_t n, int32_t k, int32_t act, int32_t terms, void* stream);
+
 /* 3x3 convolution, stride 1, padding 1, of an NHWC float32 activation as Winograd F(2x2, 3x3) in ONE kernel (input
  * transform -> sixteen float32 MFMA GEMMs -> output transform; csrc/winograd.hip): the bottleneck convolutions of the
  * ResNet trunk (reference network/basenetworks.py:71-150 runs them through torch.nn.Conv2d), 2.25x fewer multiplications
@@ -516,10 +525,38 @@ int opa_dwconv_bias_act(const void* x_dev, int64_t x_pixel_stride, const void* w
                         void* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w,
                         int32_t channels, int32_t k, int32_t stride, int32_t dtype, int32_t relu, void* stream);
 
+/* The same stencil with an activation code: act 0 none, 1 ReLU (both opa_dwconv_bias_act's own kernels, bit for bit),
+ * 2 hardswish in float32 (the depthwise convolution of a MobileNetV3 block); any other code is refused. */
+int opa_dwconv_act(const void* x_dev, int64_t x_pixel_stride, const void* w_dev, const void* bias_dev,
+                   void* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w,
+                   int32_t channels, int32_t k, int32_t stride, int32_t dtype, int32_t act, void* stream);
+
 /* torch.cat((a, b), 1) followed by channel_shuffle(groups = 2) of the same unit, in one pass over channels-last rows:
  * out[r, 2i] = a[r, i], out[r, 2i+1] = b[r, i]; a / b with their own pixel strides, out dense [rows, 2*half]. */
 int opa_channel_interleave(const void* a_dev, int64_t a_pixel_stride, const void* b_dev, int64_t b_pixel_stride,
                            void* out_dev, int64_t rows, int32_t half, int32_t dtype, void* stream);
+
+/* Squeeze-and-excitation of a MobileNetV3 block (torchvision's SqueezeExcitation, which the reference's backbone contains):
+ *     x[b, p, c] *= hardsigmoid(w2 . relu(w1 . mean_p x[b, p, .] + b1) + b2)[c]
+ * on a channels-last float32 activation x_dev [batch, pixels, *] with x_pixel_stride floats between pixels, in three calls:
+ *  opa_se_pool   sums every OPA_SE_POOL_PIXELS pixels of an image into one partial sum per channel (float64, workspace_dev
+ *                [batch][ceil(pixels / OPA_SE_POOL_PIXELS)][channels], opa_se_workspace_bytes bytes);
+ *  opa_se_gate   adds the partial sums, divides by `pixels`, rounds the mean to float32 and computes gate_dev [batch, channels]
+ *                from w1_dev [squeeze, channels], b1_dev [squeeze], w2_dev [channels, squeeze], b2_dev [channels] (float32);
+ *                mean_dev [batch, channels] receives the mean as well, or is NULL;
+ *  opa_se_scale  multiplies x by the gate in place.
+ * The order of every addition depends on the shape alone (no atomics): equal inputs give equal bits.  channels % 4 == 0,
+ * x_pixel_stride % 4 == 0 and >= channels, x_dev / workspace_dev / gate_dev on 16 bytes; batch <= 65535,
+ * pixels <= 65535 * OPA_SE_POOL_PIXELS, channels <= 8192, squeeze <= 4096. */
+#define OPA_SE_POOL_PIXELS 512
+size_t opa_se_workspace_bytes(int32_t batch, int64_t pixels, int32_t channels);
+int opa_se_pool(const float* x_dev, int64_t x_pixel_stride, int32_t batch, int64_t pixels, int32_t channels,
+                void* workspace_dev, size_t workspace_bytes, void* stream);
+int opa_se_gate(const void* workspace_dev, size_t workspace_bytes, int32_t batch, int64_t pixels, int32_t channels, int32_t squeeze,
+                const float* w1_dev, const float* b1_dev, const float* w2_dev, const float* b2_dev, float* gate_dev, float* mean_dev,
+                void* stream);
+int opa_se_scale(float* x_dev, int64_t x_pixel_stride, int32_t batch, int64_t pixels, int32_t channels, const float* gate_dev,
+                 void* stream);
 
 /* The head of the field-producing network after its 1x1 convolution, in one pass (ref: network/heads.py:330-378
  * CompositeField4.forward): PixelShuffle(upsample) -> crop -> [B, n_fields, n_components, H, W] float32 -> sigmoid on

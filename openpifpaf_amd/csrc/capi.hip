@@ -987,6 +987,32 @@ int opa_gemm_unit_bias_act_f32x3(const float* a_dev, int64_t a_pitch, const void
     return OPA_OK;
 }
 
+int opa_gemm_unit_act_f32x3(const float* a_dev, int64_t a_pitch, const void* w3_dev, const float* bias_dev,
+                            const float* partner_dev, int64_t partner_pitch, const float* residual_dev, int64_t residual_pitch,
+                            float* out_dev, int64_t m, int32_t n, int32_t k, int32_t act, int32_t terms, void* stream) {
+    if (!a_dev || !w3_dev || !bias_dev || !out_dev || m < 0 || n <= 0 || k <= 0 || m > 0x7fffffffll || (terms != 6 && terms != 9) ||
+        act < 0 || act > 2)
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_gemm_unit_act_f32x3: bad arguments");
+    if (partner_dev && residual_dev)
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_gemm_unit_act_f32x3: a residual cannot be combined with a partner");
+    if (n % 2 != 0 || k % 2 != 0)
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_gemm_unit_act_f32x3: K and N must be even");
+    if (a_pitch < k || a_pitch % 2 != 0 || a_pitch > (1 << 21) ||
+        (partner_dev && (partner_pitch < n || partner_pitch % 2 != 0 || partner_pitch > 0x7fffffffll)) ||
+        (residual_dev && (residual_pitch < n || residual_pitch % 2 != 0 || residual_pitch > 0x7fffffffll)))
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_gemm_unit_act_f32x3: a row pitch is shorter than its row, odd, or too long");
+    if ((((uintptr_t)a_dev | (uintptr_t)partner_dev | (uintptr_t)residual_dev) & 7) ||
+        (((uintptr_t)w3_dev | (uintptr_t)out_dev | (uintptr_t)bias_dev) & 15))
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_gemm_unit_act_f32x3: a_dev / partner_dev / residual_dev must be 8-B, w3_dev / bias_dev / out_dev 16-B aligned");
+    if (m == 0) return OPA_OK;
+    hipError_t e = launch_gemm_unit_act_f32x3(a_dev, (int)a_pitch, (const unsigned short*)w3_dev, bias_dev, partner_dev,
+                                              partner_dev ? (int)partner_pitch : 0, residual_dev, residual_dev ? (int)residual_pitch : 0,
+                                              out_dev, (int)m, n, k, act, terms, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "gemm_unit_act_f32x3");
+    prof_mark((hipStream_t)stream, "gemm_unit_f32x3_kernel");
+    return OPA_OK;
+}
+
 int opa_conv3x3_winograd_f32(const float* x_dev, const float* u_dev, const float* bias_dev, float* out_dev, int32_t batch,
                              int32_t h, int32_t w, int32_t c_in, int32_t c_out, int32_t relu, int32_t variant,
                              int32_t order, void* stream) {
@@ -1032,8 +1058,73 @@ int opa_dwconv_bias_act(const void* x_dev, int64_t x_pixel_stride, const void* w
     if ((int64_t)batch * (((int64_t)h + 2 * (k / 2) - k) / stride + 1) > 65535)          // grid.y of the stencil kernel (dwconv.hip)
         return fail(OPA_ERR_INVALID_ARGUMENT, "opa_dwconv_bias_act: batch * output rows must not exceed 65535");
     hipError_t e = launch_dwconv(x_dev, x_pixel_stride, w_dev, bias_dev, out_dev, out_pixel_stride, batch, h, w, channels,
-                                 k, stride, dtype, relu, (hipStream_t)stream);
+                                 k, stride, dtype, relu != 0, (hipStream_t)stream);      // (relu: any non-zero)
     if (e != hipSuccess) return fail_hip(e, "depthwise convolution");
+    return OPA_OK;
+}
+
+int opa_dwconv_act(const void* x_dev, int64_t x_pixel_stride, const void* w_dev, const void* bias_dev,
+                   void* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w,
+                   int32_t channels, int32_t k, int32_t stride, int32_t dtype, int32_t act, void* stream) {
+    if (act < 0 || act > 2) return fail(OPA_ERR_INVALID_ARGUMENT, "opa_dwconv_act: act must be 0 (none), 1 (ReLU) or 2 (hardswish)");
+    if (act != 2)
+        return opa_dwconv_bias_act(x_dev, x_pixel_stride, w_dev, bias_dev, out_dev, out_pixel_stride, batch, h, w, channels, k, stride,
+                                   dtype, act, stream);
+    if (!x_dev || !w_dev || !out_dev || batch <= 0 || h <= 0 || w <= 0 || channels <= 0 || x_pixel_stride < channels ||
+        out_pixel_stride < channels || (k != 3 && k != 5) || (stride != 1 && stride != 2) || (dtype != 0 && dtype != 2))
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_dwconv_act: bad arguments");
+    if ((int64_t)batch * (((int64_t)h + 2 * (k / 2) - k) / stride + 1) > 65535)          // grid.y of the stencil kernel (dwconv.hip)
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_dwconv_act: batch * output rows must not exceed 65535");
+    hipError_t e = launch_dwconv(x_dev, x_pixel_stride, w_dev, bias_dev, out_dev, out_pixel_stride, batch, h, w, channels,
+                                 k, stride, dtype, 2, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "depthwise convolution");
+    return OPA_OK;
+}
+
+static const char* se_check(int64_t x_pixel_stride, int32_t batch, int64_t pixels, int32_t channels) {
+    if (batch <= 0 || batch > 65535 || pixels <= 0 || pixels > 65535ll * kSePoolPixels || channels <= 0 || channels > 8192)
+        return "batch, pixels or channels out of range";
+    if (channels % 4 != 0 || x_pixel_stride % 4 != 0 || x_pixel_stride < channels) return "channels and the pixel stride must be multiples of 4, the stride >= channels";
+    return nullptr;
+}
+
+size_t opa_se_workspace_bytes(int32_t batch, int64_t pixels, int32_t channels) {
+    if (batch <= 0 || pixels <= 0 || channels <= 0) return 0;
+    return (size_t)batch * (size_t)se_pool_chunks(pixels) * (size_t)channels * sizeof(double);
+}
+
+int opa_se_pool(const float* x_dev, int64_t x_pixel_stride, int32_t batch, int64_t pixels, int32_t channels,
+                void* workspace_dev, size_t workspace_bytes, void* stream) {
+    if (!x_dev || !workspace_dev) return fail(OPA_ERR_INVALID_ARGUMENT, "opa_se_pool: bad arguments");
+    if (const char* why = se_check(x_pixel_stride, batch, pixels, channels)) return fail(OPA_ERR_INVALID_ARGUMENT, std::string("opa_se_pool: ") + why);
+    if (((uintptr_t)x_dev | (uintptr_t)workspace_dev) & 15) return fail(OPA_ERR_INVALID_ARGUMENT, "opa_se_pool: pointers must be 16-B aligned");
+    if (workspace_bytes < opa_se_workspace_bytes(batch, pixels, channels)) return fail(OPA_ERR_WORKSPACE, "opa_se_pool: the workspace is too small");
+    hipError_t e = launch_se_pool(x_dev, x_pixel_stride, batch, pixels, channels, (double*)workspace_dev, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "se pool");
+    return OPA_OK;
+}
+
+int opa_se_gate(const void* workspace_dev, size_t workspace_bytes, int32_t batch, int64_t pixels, int32_t channels, int32_t squeeze,
+                const float* w1_dev, const float* b1_dev, const float* w2_dev, const float* b2_dev, float* gate_dev, float* mean_dev,
+                void* stream) {
+    if (!workspace_dev || !w1_dev || !b1_dev || !w2_dev || !b2_dev || !gate_dev || squeeze <= 0 || squeeze > 4096)
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_se_gate: bad arguments");
+    if (const char* why = se_check(channels, batch, pixels, channels)) return fail(OPA_ERR_INVALID_ARGUMENT, std::string("opa_se_gate: ") + why);
+    if ((uintptr_t)workspace_dev & 15) return fail(OPA_ERR_INVALID_ARGUMENT, "opa_se_gate: workspace_dev must be 16-B aligned");
+    if (workspace_bytes < opa_se_workspace_bytes(batch, pixels, channels)) return fail(OPA_ERR_WORKSPACE, "opa_se_gate: the workspace is too small");
+    hipError_t e = launch_se_gate((const double*)workspace_dev, batch, pixels, channels, squeeze, w1_dev, b1_dev, w2_dev, b2_dev, gate_dev,
+                                  mean_dev, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "se gate");
+    return OPA_OK;
+}
+
+int opa_se_scale(float* x_dev, int64_t x_pixel_stride, int32_t batch, int64_t pixels, int32_t channels, const float* gate_dev,
+                 void* stream) {
+    if (!x_dev || !gate_dev) return fail(OPA_ERR_INVALID_ARGUMENT, "opa_se_scale: bad arguments");
+    if (const char* why = se_check(x_pixel_stride, batch, pixels, channels)) return fail(OPA_ERR_INVALID_ARGUMENT, std::string("opa_se_scale: ") + why);
+    if (((uintptr_t)x_dev | (uintptr_t)gate_dev) & 15) return fail(OPA_ERR_INVALID_ARGUMENT, "opa_se_scale: pointers must be 16-B aligned");
+    hipError_t e = launch_se_scale(x_dev, x_pixel_stride, batch, pixels, channels, gate_dev, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "se scale");
     return OPA_OK;
 }
 

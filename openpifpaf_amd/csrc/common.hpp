@@ -271,6 +271,10 @@ hipError_t launch_conv3x3_f32x3(const float* x, int batch, int hi, int wi, int C
                                 const float* bias, float* out, int N, int relu, int terms, hipStream_t st);
 hipError_t launch_gemm_unit_f32x3(const float* A, int lda, const unsigned short* W3, const float* bias, const float* partner, int ldp,
                                   float* out, int M, int N, int K, int relu, int terms, hipStream_t st);
+// ... with an activation code (0 none, 1 ReLU, 2 hardswish) and optionally a residual [M, N] with `ldr` floats between rows
+// (added before the activation; not together with a partner)
+hipError_t launch_gemm_unit_act_f32x3(const float* A, int lda, const unsigned short* W3, const float* bias, const float* partner, int ldp,
+                                      const float* residual, int ldr, float* out, int M, int N, int K, int act, int terms, hipStream_t st);
 hipError_t launch_gemm_f32_bias_act(const float* A, const float* W, const float* bias, const float* res, float* out,
                                     int M, int N, int K, int relu, hipStream_t st, const float* a_bias = nullptr);
 hipError_t launch_winograd_f23(const float* x, const float* U, float* y, const float* bias, int N, int H, int W, int Cin,
@@ -278,10 +282,20 @@ hipError_t launch_winograd_f23(const float* x, const float* U, float* y, const f
 hipError_t launch_winograd_f23x3(const float* x, const unsigned short* U3, float* y, const float* bias, int N, int H, int W,
                                  int Cin, int Cout, int relu, int variant, int nb_major, hipStream_t st);
 
+// act: 0 none, 1 ReLU, 2 hardswish
 hipError_t launch_dwconv(const void* x, long long xs, const void* w, const void* bias, void* out, long long os,
-                         int B, int H, int W, int C, int K, int S, int dtype, int relu, hipStream_t st);
+                         int B, int H, int W, int C, int K, int S, int dtype, int act, hipStream_t st);
 hipError_t launch_channel_interleave(const void* a, long long as, const void* b, long long bs, void* out,
                                      long long rows, int half, int dtype, hipStream_t st);
+
+// Squeeze-and-excitation of a MobileNetV3 block (se.hip) on a channels-last float32 tensor [B, HW, C] with pixel stride xs:
+// pool (partial sums [B][se_pool_chunks(HW)][C] in float64), gate (g [B, C]), apply (x *= g in place).
+constexpr int kSePoolPixels = 512;        // OPA_SE_POOL_PIXELS: pixels of one partial sum
+inline long long se_pool_chunks(long long hw) { return (hw + kSePoolPixels - 1) / kSePoolPixels; }
+hipError_t launch_se_pool(const float* x, long long xs, int B, long long HW, int C, double* partial, hipStream_t st);
+hipError_t launch_se_gate(const double* partial, int B, long long HW, int C, int S, const float* w1, const float* b1,
+                          const float* w2, const float* b2, float* gate, float* mean_out, hipStream_t st);
+hipError_t launch_se_scale(float* x, long long xs, int B, long long HW, int C, const float* gate, hipStream_t st);
 
 hipError_t launch_head_epilogue(const void* conv, int dtype, int B, int Hc, int Wc, int n_fields, int n_comp, int us,
                                 int n_conf, int n_vec, unsigned offset_mask, int n_scales, float* out, hipStream_t st);
@@ -323,6 +337,10 @@ __device__ __forceinline__ void sync_global() {
 __device__ __forceinline__ int seed_cell_pack(const DevParams& p, int occ_h, int occ_w, double x, double y, double sigma);
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (kWave - 1); }
+
+// MobileNetV3's activations in float32 (torch.nn.Hardswish / Hardsigmoid): x * min(max(x + 3, 0), 6) / 6 and the factor alone
+__device__ __forceinline__ float hardsigmoid_f32(float x) { return fminf(fmaxf(x + 3.0f, 0.0f), 6.0f) / 6.0f; }
+__device__ __forceinline__ float hardswish_f32(float x) { return x * fminf(fmaxf(x + 3.0f, 0.0f), 6.0f) / 6.0f; }
 
 __device__ __forceinline__ long long clampll(long long v, long long lo, long long hi) {
     return v < lo ? lo : (v > hi ? hi : v);

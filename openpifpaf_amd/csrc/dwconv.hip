@@ -7,10 +7,15 @@
 // margin -- so it gets a plain stencil kernel: channels-last, one thread per channel and strip of four output
 // pixels (a wave reads 64 consecutive channels: coalesced), the k rows of the window slide through registers,
 // float32 accumulation, the folded batch-norm bias (and optionally ReLU) applied before the single store.
+// The MobileNetV3 blocks (reference network/basenetworks.py:432-446) use the same stencil with hardswish behind it: the
+// activation is then a template parameter (ACT = 2), so that the kernels with the run-time `relu` flag (ACT = -1) stay as they are.
+// That variant also keeps its 9 or 25 products in float64 and rounds once, behind the bias: a chain of 25 float32
+// multiply-adds came out at 1.5-3 times the error of torch's depthwise convolution + hardswish against float64.
 //
 // channel_interleave_kernel fuses the unit's torch.cat + channel_shuffle(groups = 2): out[.., 2i] = a[.., i],
 // out[.., 2i+1] = b[.., i].
 #include "common.hpp"
+#include <type_traits>
 
 namespace opa {
 
@@ -56,7 +61,7 @@ template <int V> struct DwVec<unsigned short, V> {               // bfloat16
 // x: [B, H, W, *] with pixel stride xs (a channel slice of a wider tensor is fine), w: [K*K, C] (tap-major),
 // out: [B, Ho, Wo, *] with pixel stride os.  A work item = V channels x a strip of kDwStrip output pixels of one
 // output row; the items of a row are dealt to the threads channel-vector first (coalesced within a pixel).
-template <typename T, int K, int S, int V>
+template <typename T, int K, int S, int V, int ACT = -1>
 __global__ __launch_bounds__(256) void dwconv_kernel(const T* __restrict__ x, long long xs, const T* __restrict__ w,
                                                      const T* __restrict__ bias, T* __restrict__ out, long long os,
                                                      int H, int W, int C, int Ho, int Wo, int relu) {
@@ -68,7 +73,8 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const T* __restrict__ x, lo
     const int strip = item / cvecs, c = (item - strip * cvecs) * V;
     const int x0 = strip * kDwStrip;
     const int by = blockIdx.y, b = by / Ho, y = by - b * Ho;
-    float acc[kDwStrip][V];
+    using Acc = typename std::conditional<ACT == 2, double, float>::type;
+    Acc acc[kDwStrip][V];
     DwVec<T, V> bv;
 #pragma unroll
     for (int q = 0; q < V; q++) bv.v[q] = 0.0f;
@@ -76,7 +82,7 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const T* __restrict__ x, lo
 #pragma unroll
     for (int i = 0; i < kDwStrip; i++)
 #pragma unroll
-        for (int q = 0; q < V; q++) acc[i][q] = 0.0f;
+        for (int q = 0; q < V; q++) acc[i][q] = (Acc)0.0f;
 #pragma unroll
     for (int ky = 0; ky < K; ky++) {
         const int yy = y * S - P + ky;
@@ -97,7 +103,10 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const T* __restrict__ x, lo
 #pragma unroll
             for (int i = 0; i < kDwStrip; i++)
 #pragma unroll
-                for (int q = 0; q < V; q++) acc[i][q] = fmaf(in[i * S + kx].v[q], wv.v[q], acc[i][q]);
+                for (int q = 0; q < V; q++) {
+                    if constexpr (ACT == 2) acc[i][q] = fma((double)in[i * S + kx].v[q], (double)wv.v[q], acc[i][q]);
+                    else acc[i][q] = fmaf(in[i * S + kx].v[q], wv.v[q], acc[i][q]);
+                }
         }
     }
 #pragma unroll
@@ -106,7 +115,11 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const T* __restrict__ x, lo
         if (xo >= Wo) break;
         DwVec<T, V> o;
 #pragma unroll
-        for (int q = 0; q < V; q++) { o.v[q] = acc[i][q] + bv.v[q]; if (relu) o.v[q] = fmaxf(o.v[q], 0.0f); }
+        for (int q = 0; q < V; q++) {
+            o.v[q] = (float)(acc[i][q] + (Acc)bv.v[q]);
+            if constexpr (ACT == 2) o.v[q] = hardswish_f32(o.v[q]);
+            else if (relu) o.v[q] = fmaxf(o.v[q], 0.0f);
+        }
         o.store(out + (((size_t)b * Ho + y) * Wo + xo) * os + c);
     }
 }
@@ -129,15 +142,19 @@ __global__ __launch_bounds__(256) void channel_interleave_kernel(const T* __rest
     __builtin_memcpy(out + r * 2 * half + 2 * c, vo, sizeof(vo));
 }
 
+// act: 0 none, 1 ReLU (both the kernel with the run-time flag), 2 hardswish
 template <typename T, int V>
 static hipError_t launch_dw_v(const void* x, long long xs, const void* w, const void* bias, void* out, long long os,
-                              int B, int H, int W, int C, int K, int S, int relu, hipStream_t st) {
+                              int B, int H, int W, int C, int K, int S, int act, hipStream_t st) {
     const int P = K / 2;
     const int Ho = (H + 2 * P - K) / S + 1, Wo = (W + 2 * P - K) / S + 1;
     const long long items = (long long)(C / V) * ((Wo + kDwStrip - 1) / kDwStrip);
     dim3 grid((unsigned)((items + 255) / 256), B * Ho);
-#define OPA_DW(KK, SS) dwconv_kernel<T, KK, SS, V><<<grid, 256, 0, st>>>((const T*)x, xs, (const T*)w, (const T*)bias, \
-                                                                         (T*)out, os, H, W, C, Ho, Wo, relu)
+#define OPA_DW(KK, SS) do { \
+        if (act == 2) dwconv_kernel<T, KK, SS, V, 2><<<grid, 256, 0, st>>>((const T*)x, xs, (const T*)w, (const T*)bias, \
+                                                                           (T*)out, os, H, W, C, Ho, Wo, 0); \
+        else dwconv_kernel<T, KK, SS, V><<<grid, 256, 0, st>>>((const T*)x, xs, (const T*)w, (const T*)bias, \
+                                                               (T*)out, os, H, W, C, Ho, Wo, act); } while (0)
     if (K == 5 && S == 1) OPA_DW(5, 1);
     else if (K == 5 && S == 2) OPA_DW(5, 2);
     else if (K == 3 && S == 1) OPA_DW(3, 1);
@@ -151,21 +168,21 @@ static hipError_t launch_dw_v(const void* x, long long xs, const void* w, const 
 // the widest channel vector the shapes and addresses allow
 template <typename T>
 static hipError_t launch_dw_t(const void* x, long long xs, const void* w, const void* bias, void* out, long long os,
-                              int B, int H, int W, int C, int K, int S, int relu, hipStream_t st) {
+                              int B, int H, int W, int C, int K, int S, int act, hipStream_t st) {
     auto ok = [&](int v) {
         const size_t a = v * sizeof(T);
         return C % v == 0 && xs % v == 0 && os % v == 0 && (uintptr_t)x % a == 0 && (uintptr_t)out % a == 0 &&
                (uintptr_t)w % a == 0 && (!bias || (uintptr_t)bias % a == 0);
     };
-    if (ok(4)) return launch_dw_v<T, 4>(x, xs, w, bias, out, os, B, H, W, C, K, S, relu, st);
-    if (ok(2)) return launch_dw_v<T, 2>(x, xs, w, bias, out, os, B, H, W, C, K, S, relu, st);
-    return launch_dw_v<T, 1>(x, xs, w, bias, out, os, B, H, W, C, K, S, relu, st);
+    if (ok(4)) return launch_dw_v<T, 4>(x, xs, w, bias, out, os, B, H, W, C, K, S, act, st);
+    if (ok(2)) return launch_dw_v<T, 2>(x, xs, w, bias, out, os, B, H, W, C, K, S, act, st);
+    return launch_dw_v<T, 1>(x, xs, w, bias, out, os, B, H, W, C, K, S, act, st);
 }
 
 hipError_t launch_dwconv(const void* x, long long xs, const void* w, const void* bias, void* out, long long os,
-                         int B, int H, int W, int C, int K, int S, int dtype, int relu, hipStream_t st) {
-    if (dtype == 0) return launch_dw_t<float>(x, xs, w, bias, out, os, B, H, W, C, K, S, relu, st);
-    if (dtype == 2) return launch_dw_t<unsigned short>(x, xs, w, bias, out, os, B, H, W, C, K, S, relu, st);
+                         int B, int H, int W, int C, int K, int S, int dtype, int act, hipStream_t st) {
+    if (dtype == 0) return launch_dw_t<float>(x, xs, w, bias, out, os, B, H, W, C, K, S, act, st);
+    if (dtype == 2) return launch_dw_t<unsigned short>(x, xs, w, bias, out, os, B, H, W, C, K, S, act, st);
     return hipErrorInvalidValue;
 }
 

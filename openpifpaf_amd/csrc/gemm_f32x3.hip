@@ -90,7 +90,9 @@ struct X3Second {
 // behind the LAST row is never fetched (the buffer's range ends with that row's column k_real).  A slice starts on an 8-byte
 // boundary only (k16 stage 2: 174 floats into a pixel) and so does every row of the output (n_real even): the operand is staged
 // with 8-byte loads, the epilogue works in column pairs -- a pair lies inside k_real / n_real or outside, never across.
-template <int BN, bool PARTNER, bool RELU>
+// UX (MobileNetV3's blocks, reference network/basenetworks.py:432-446; 0 for everything above): UX & 3 == 2 -- the activation is
+// hardswish (RELU false); UX & 4 -- `partner` is a RESIDUAL [M, n; row pitch ldp]: out[M, n] = act(A * W^T + bias + residual), dense rows.
+template <int BN, bool PARTNER, bool RELU, int UX = 0>
 __device__ __forceinline__ void x3_unit_epilogue(float* smem_f, const f32x16_t (&acc)[2][BN / 64], const f32x16_t (&low)[2][BN / 64],
                                                  const float* __restrict__ bias, const float* __restrict__ partner,
                                                  float* __restrict__ out, int M, int m0, int n0, int lane, int wave, int ldp, int n_real) {
@@ -132,8 +134,15 @@ __device__ __forceinline__ void x3_unit_epilogue(float* smem_f, const f32x16_t (
             const int m = m0 + wm * 64 + i * 32 + row;
             if (m < M && col < n_real) {       // (n_real is even: the pair is inside or outside)
                 f32x2_t f = *reinterpret_cast<const f32x2_t*>(patch + row * WN + c2);
+                if constexpr (PARTNER && (UX & 4) != 0) {
+                    f32x2_t pp;
+                    if (t < PPRE) pp = pv[t < PPRE ? t : 0];
+                    else pp = *reinterpret_cast<const f32x2_t*>(partner + (size_t)m * ldp + col);
+                    f[0] += pp[0]; f[1] += pp[1];
+                }
                 if (RELU) { f[0] = fmaxf(f[0], 0.0f); f[1] = fmaxf(f[1], 0.0f); }
-                if (PARTNER) {                 // the partner's bits pass through untouched
+                if constexpr ((UX & 3) == 2) { f[0] = hardswish_f32(f[0]); f[1] = hardswish_f32(f[1]); }
+                if (PARTNER && (UX & 4) == 0) { // the partner's bits pass through untouched
                     f32x2_t pp;
                     if (t < PPRE) pp = pv[t < PPRE ? t : 0];
                     else pp = *reinterpret_cast<const f32x2_t*>(partner + (size_t)m * ldp + col);
@@ -149,7 +158,7 @@ __device__ __forceinline__ void x3_unit_epilogue(float* smem_f, const f32x16_t (
     }
 }
 
-template <int BN, bool RES, bool RELU, bool PRO, int TERMS, int SRC, bool UNIT = false>
+template <int BN, bool RES, bool RELU, bool PRO, int TERMS, int SRC, bool UNIT = false, int UX = 0>
 __global__ __launch_bounds__(256, OPA_X3_WGS) void gemm_f32x3_bias_act_kernel(
         const float* __restrict__ A, const unsigned short* __restrict__ W3, const float* __restrict__ bias,
         const float* __restrict__ res, float* __restrict__ out, int M, int N, int K, const float* __restrict__ a_bias,
@@ -379,7 +388,7 @@ __global__ __launch_bounds__(256, OPA_X3_WGS) void gemm_f32x3_bias_act_kernel(
     }
     // (the loop's last barrier: staging LDS is free, reuse it for the epilogue)
     if constexpr (UNIT) {
-        x3_unit_epilogue<BN, RES, RELU>(reinterpret_cast<float*>(smem), acc, low, bias, res, out, M, m0, n0, lane, wave, sec.ldp, sec.n_real);
+        x3_unit_epilogue<BN, RES, RELU, UX>(reinterpret_cast<float*>(smem), acc, low, bias, res, out, M, m0, n0, lane, wave, sec.ldp, sec.n_real);
         return;
     }
 
@@ -509,14 +518,63 @@ static hipError_t launch_unit_bn(const float* a, const unsigned short* w, const 
 // to multiples of 64), partner [M, N] with `ldp` floats between rows or null; out [M, N] dense, or [M, 2N] with a partner.  The tile
 // is 128 wide where Np is a multiple of 128, like launch_gemm_f32x3_bias_act chooses it for N -- with six terms: the 128-wide
 // tile with nine terms does not fit the register file (the existing instantiations spill 8 registers), so nine terms take 64.
-hipError_t launch_gemm_unit_f32x3(const float* A, int lda, const unsigned short* W3, const float* bias, const float* partner, int ldp,
-                                  float* out, int M, int N, int K, int relu, int terms, hipStream_t st) {
+static X3Second unit_sec(int lda, int ldp, int N, int K) {
     X3Second sec; sec.A2 = nullptr; sec.K1 = K; sec.ho_wo = sec.wo = sec.hi_wi = sec.wi = sec.stride = 1; sec.hi = 1; sec.C = 0; sec.batch = 1;
     sec.pix = 1; sec.taps_x = 1; sec.ntaps = 1; sec.padded = 0; sec.lda = lda; sec.ldp = ldp; sec.n_real = N; sec.k_real = K;
+    return sec;
+}
+
+// f.template operator()<BN, TERMS>(Np, Kp) with the unit mode's tile width and term count for these sizes
+template <typename F>
+static hipError_t unit_dispatch(int N, int K, int terms, F f) {
     const int Np = (N + 63) / 64 * 64, Kp = (K + 63) / 64 * 64;
-    if (Np % 128 == 0 && terms == 6) return launch_unit_bn<128, 6>(A, W3, bias, partner, out, M, Np, Kp, relu, st, sec);
-    if (terms == 6) return launch_unit_bn<64, 6>(A, W3, bias, partner, out, M, Np, Kp, relu, st, sec);
-    return launch_unit_bn<64, 9>(A, W3, bias, partner, out, M, Np, Kp, relu, st, sec);
+    if (Np % 128 == 0 && terms == 6) return f.template operator()<128, 6>(Np, Kp);
+    if (terms == 6) return f.template operator()<64, 6>(Np, Kp);
+    return f.template operator()<64, 9>(Np, Kp);
+}
+
+struct UnitLaunch {
+    const float* a; const unsigned short* w; const float* b; const float* third; bool residual; float* o;
+    int M, act; hipStream_t st; X3Second sec;
+    template <int BN, int TERMS> hipError_t operator()(int Np, int Kp) const;
+};
+
+hipError_t launch_gemm_unit_f32x3(const float* A, int lda, const unsigned short* W3, const float* bias, const float* partner, int ldp,
+                                  float* out, int M, int N, int K, int relu, int terms, hipStream_t st) {
+    return unit_dispatch(N, K, terms, UnitLaunch{A, W3, bias, partner, false, out, M, relu ? 1 : 0, st, unit_sec(lda, ldp, N, K)});
+}
+
+// The unit mode's instantiations with hardswish or a residual (see x3_unit_epilogue's UX); `third` is the partner or the residual.
+template <int BN, int TERMS>
+static hipError_t launch_unit_act_bn(const float* a, const unsigned short* w, const float* b, const float* third, bool residual, float* o,
+                                     int M, int Np, int Kp, int act, hipStream_t st, const X3Second& sec) {
+    const unsigned blocks = (unsigned)((long long)((M + kX3BM - 1) / kX3BM) * (Np / BN));
+#define OPA_UNIT_ACT(RES_, RELU_, UX_) gemm_f32x3_bias_act_kernel<BN, RES_, RELU_, false, TERMS, 0, true, UX_><<<blocks, 256, 0, st>>>(a, w, b, third, o, M, Np, Kp, nullptr, sec)
+    if (residual) {
+        if (act == 2) OPA_UNIT_ACT(true, false, 6);
+        else if (act == 1) OPA_UNIT_ACT(true, true, 4);
+        else OPA_UNIT_ACT(true, false, 4);
+    } else if (third) {
+        OPA_UNIT_ACT(true, false, 2);
+    } else {
+        OPA_UNIT_ACT(false, false, 2);
+    }
+#undef OPA_UNIT_ACT
+    return hipGetLastError();
+}
+
+hipError_t launch_gemm_unit_act_f32x3(const float* A, int lda, const unsigned short* W3, const float* bias, const float* partner, int ldp,
+                                      const float* residual, int ldr, float* out, int M, int N, int K, int act, int terms, hipStream_t st) {
+    if (partner && residual) return hipErrorInvalidValue;
+    return unit_dispatch(N, K, terms, UnitLaunch{A, W3, bias, residual ? residual : partner, residual != nullptr, out, M, act, st,
+                                                 unit_sec(lda, residual ? ldr : ldp, N, K)});
+}
+
+// act 0 / 1 without a residual: the instantiations the ShuffleNetV2K units use (launch_unit_bn)
+template <int BN, int TERMS>
+hipError_t UnitLaunch::operator()(int Np, int Kp) const {
+    if (!residual && act != 2) return launch_unit_bn<BN, TERMS>(a, w, b, third, o, M, Np, Kp, act, st, sec);
+    return launch_unit_act_bn<BN, TERMS>(a, w, b, third, residual, o, M, Np, Kp, act, st, sec);
 }
 
 // 3x3 convolution, padding 1, stride s: out[B, ho, wo, N] = act(im2col(x) * W3^T + bias), x [B, hi, wi, C] channels-last,

@@ -377,16 +377,20 @@ def _unit_conv_ok(conv):
             and (conv.bias is None or conv.bias.dtype == torch.float32))
 
 
-def unit_conv_x3_supported(conv, x, partner=None):
-    """Can ``conv1x1_unit_x3(conv, x, partner=partner)`` run?  float32 on the GPU, a 1x1 convolution of stride 1 without padding or
-    groups and with EVEN channel counts, ``x`` (and ``partner``) channels-innermost tensors or channel slices of such, on 8-byte
-    boundaries, nothing that autograd follows; the partner has the output's pixels and ``conv.out_channels`` channels."""
+def unit_conv_x3_supported(conv, x, partner=None, residual=None):
+    """Can ``conv1x1_unit_x3(conv, x, partner=partner, residual=residual)`` run?  float32 on the GPU, a 1x1 convolution of stride 1
+    without padding or groups and with EVEN channel counts, ``x`` (and ``partner`` or ``residual``, never both) channels-innermost
+    tensors or channel slices of such, on 8-byte boundaries, nothing that autograd follows; the partner and the residual have the
+    output's pixels and ``conv.out_channels`` channels."""
     if not (x.is_cuda and conv.weight.device == x.device and _unit_conv_ok(conv) and _unit_operand_ok(x, conv.in_channels)
             and 0 < x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31):
         return False
-    if partner is not None:
-        return (partner.device == x.device and _unit_operand_ok(partner, conv.out_channels)
-                and (partner.shape[0], partner.shape[2], partner.shape[3]) == (x.shape[0], x.shape[2], x.shape[3]))
+    if partner is not None and residual is not None:
+        return False
+    for third in (partner, residual):
+        if third is not None and not (third.device == x.device and _unit_operand_ok(third, conv.out_channels)
+                                      and (third.shape[0], third.shape[2], third.shape[3]) == (x.shape[0], x.shape[2], x.shape[3])):
+            return False
     return True
 
 
@@ -415,17 +419,34 @@ def _unit_weight_of(conv):
     return derived(conv, '_opa_w3_unit', (conv.weight, conv.bias), make)
 
 
-def conv1x1_unit_x3(conv, x, relu=True, partner=None):
+ACT_NONE, ACT_RELU, ACT_HARDSWISH = 0, 1, 2      # the activation codes of opa_dwconv_act and opa_gemm_unit_act_f32x3
+
+
+def conv1x1_unit_x3(conv, x, relu=True, partner=None, residual=None, act=None):
     """``act(conv(x))`` for a biased 1x1 convolution of ANY even channel counts on a channels-last tensor or channel slice
     (reference ``network/basenetworks.py:186-242``: the 1x1 convolutions of a ShuffleNetV2K unit, folded with their batch norms),
     through the split-operand GEMM's unit mode (``opa_gemm_unit_bias_act_f32x3``).  With ``partner`` (``[B, N, H, W]``, may be a
     slice) the result is ``channel_shuffle(cat((partner, y), 1), 2)`` -- ``[B, 2N, H, W]``, the partner's channels copied into the
-    even positions by the same kernel.  channels_last float32 out.  ``unit_conv_x3_supported`` says whether this can run."""
+    even positions by the same kernel.  channels_last float32 out.  ``unit_conv_x3_supported`` says whether this can run.
+
+    ``act`` (``ACT_NONE`` / ``ACT_RELU`` / ``ACT_HARDSWISH``) instead of ``relu``, and ``residual`` (``[B, N, H, W]``, may be a slice,
+    never together with a partner): ``act(conv(x) + residual)`` in the same launch -- the 1x1 convolutions of a MobileNetV3 block
+    (``opa_gemm_unit_act_f32x3``).  ``act=None`` without a residual is the call above, entry point and all."""
     w3, bp = _unit_weight_of(conv)
     B, K, H, W = x.shape
     n = conv.out_channels
     out = torch.empty((B, n if partner is None else 2 * n, H, W), dtype=torch.float32, device=x.device,
                       memory_format=torch.channels_last)
+    if act is not None or residual is not None:
+        _lib.check(_lib.lib().opa_gemm_unit_act_f32x3(
+            ctypes.c_void_p(x.data_ptr()), _pixel_stride(x), ctypes.c_void_p(w3.data_ptr()), ctypes.c_void_p(bp.data_ptr()),
+            ctypes.c_void_p(partner.data_ptr()) if partner is not None else None,
+            _pixel_stride(partner) if partner is not None else 0,
+            ctypes.c_void_p(residual.data_ptr()) if residual is not None else None,
+            _pixel_stride(residual) if residual is not None else 0, ctypes.c_void_p(out.data_ptr()),
+            B * H * W, n, K, int(bool(relu)) if act is None else int(act), int(X3_TERMS),
+            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_gemm_unit_act_f32x3')
+        return out
     _lib.check(_lib.lib().opa_gemm_unit_bias_act_f32x3(
         ctypes.c_void_p(x.data_ptr()), _pixel_stride(x), ctypes.c_void_p(w3.data_ptr()), ctypes.c_void_p(bp.data_ptr()),
         ctypes.c_void_p(partner.data_ptr()) if partner is not None else None,
@@ -600,19 +621,98 @@ def dwconv_supported(x, kernel_size, stride):
             and _pixel_stride(x) is not None and _lib.available())
 
 
-def dwconv_bias_act(x, w_taps, bias, kernel_size, stride, relu=False):
+def dwconv_bias_act(x, w_taps, bias, kernel_size, stride, relu=False, act=None):
     """Depthwise ``kernel_size`` x ``kernel_size`` convolution (padding k//2) + bias (+ ReLU) of a channels-last
-    activation or channel slice, one HIP stencil kernel.  ``w_taps``: ``[k*k, C]`` (tap-major) in ``x``'s dtype."""
+    activation or channel slice, one HIP stencil kernel.  ``w_taps``: ``[k*k, C]`` (tap-major) in ``x``'s dtype.
+    ``act`` (``ACT_NONE`` / ``ACT_RELU`` / ``ACT_HARDSWISH``) instead of ``relu``: ``opa_dwconv_act``."""
     B, C, H, W = x.shape
     pad = kernel_size // 2
     Ho, Wo = (H + 2 * pad - kernel_size) // stride + 1, (W + 2 * pad - kernel_size) // stride + 1
     out = torch.empty((B, C, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    if act is not None:
+        _lib.check(_lib.lib().opa_dwconv_act(
+            ctypes.c_void_p(x.data_ptr()), _pixel_stride(x), ctypes.c_void_p(w_taps.data_ptr()),
+            ctypes.c_void_p(bias.data_ptr()) if bias is not None else None, ctypes.c_void_p(out.data_ptr()), C,
+            B, H, W, C, kernel_size, stride, _DTYPES[x.dtype], int(act),
+            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_dwconv_act')
+        return out
     _lib.check(_lib.lib().opa_dwconv_bias_act(
         ctypes.c_void_p(x.data_ptr()), _pixel_stride(x), ctypes.c_void_p(w_taps.data_ptr()),
         ctypes.c_void_p(bias.data_ptr()) if bias is not None else None, ctypes.c_void_p(out.data_ptr()), C,
         B, H, W, C, kernel_size, stride, _DTYPES[x.dtype], int(bool(relu)),
         ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_dwconv_bias_act')
     return out
+
+
+# The MobileNetV3 blocks on the project's kernels (network._MBV3Block._forward_unit): OPA_MBV3=1 (or fused.MBV3 = True) switches the
+# route on.  It stays OFF by default -- the plain torch forward -- until both trunks have been timed against that forward at 641 px,
+# batch 32 (tools/gpu/mobilenetv3_times.py): no speed is claimed for a route nobody has measured.
+MBV3 = os.environ.get('OPA_MBV3', '0') != '0'
+
+
+def _se_convs_ok(fc1, fc2):
+    """The part of ``se_gate_supported`` that depends on the two convolutions alone."""
+    def ok(conv):
+        return (conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.groups == 1
+                and conv.bias is not None and conv.weight.dtype == torch.float32 and conv.bias.dtype == torch.float32
+                and conv.weight.is_contiguous() and conv.bias.is_contiguous() and conv.bias.device == conv.weight.device)
+    return (ok(fc1) and ok(fc2) and fc1.weight.device == fc2.weight.device and fc2.in_channels == fc1.out_channels
+            and fc2.out_channels == fc1.in_channels and fc1.in_channels % 4 == 0 and fc1.in_channels <= 8192
+            and fc1.out_channels <= 4096)
+
+
+SE_MAX_PIXELS = 65535 * 512          # grid.y of the pool kernel x OPA_SE_POOL_PIXELS
+
+
+def _se_operand_ok(x, channels):
+    """Layout and size of the activation of ``se_gate`` / ``scale_channels_``: float32 on the GPU, ``channels`` channels innermost with
+    a pitch between pixels that is a multiple of 4, on a 16-byte boundary, not followed by autograd."""
+    ps = _pixel_stride(x) if x.dim() == 4 else None
+    return (x.is_cuda and x.dtype == torch.float32 and not x.requires_grad and ps is not None and x.shape[1] == channels
+            and channels % 4 == 0 and ps % 4 == 0 and x.data_ptr() % 16 == 0 and 0 < x.shape[0] <= 65535
+            and 0 < x.shape[2] * x.shape[3] <= SE_MAX_PIXELS and _lib.available())
+
+
+def se_gate_supported(x, fc1, fc2):
+    """Can ``se_gate(x, fc1, fc2)`` run?  Two biased float32 1x1 convolutions C -> S -> C (C a multiple of 4, at most 8192; S at most
+    4096) on ``x``'s device, ``x`` as ``_se_operand_ok`` says."""
+    return _se_convs_ok(fc1, fc2) and _se_operand_ok(x, fc1.in_channels) and fc1.weight.device == x.device
+
+
+def se_gate(x, fc1, fc2, mean_out=None):
+    """The gate of a squeeze-and-excitation block: ``hardsigmoid(fc2(relu(fc1(mean of x over its pixels))))`` -> ``[B, C]`` float32
+    (torchvision's ``SqueezeExcitation`` inside the reference's MobileNetV3, ``network/basenetworks.py:432-446``).  ``x``: channels-last
+    float32 or a channel slice.  Two launches (``csrc/se.hip``): partial sums of 512 pixels each into a workspace, then the sums'
+    reduction and the two matrix-vector products per image; the order of every addition depends on the shape alone.
+    ``mean_out``: a contiguous float32 ``[B, C]`` tensor that receives the pooled mean as well (tests)."""
+    B, C, H, W = x.shape
+    lib = _lib.lib()
+    nbytes = lib.opa_se_workspace_bytes(B, H * W, C)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
+    gate = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _lib.check(lib.opa_se_pool(ctypes.c_void_p(x.data_ptr()), _pixel_stride(x), B, H * W, C, ctypes.c_void_p(ws.data_ptr()), nbytes,
+                               stream), 'opa_se_pool')
+    _lib.check(lib.opa_se_gate(ctypes.c_void_p(ws.data_ptr()), nbytes, B, H * W, C, fc1.out_channels,
+                               ctypes.c_void_p(fc1.weight.data_ptr()), ctypes.c_void_p(fc1.bias.data_ptr()),
+                               ctypes.c_void_p(fc2.weight.data_ptr()), ctypes.c_void_p(fc2.bias.data_ptr()),
+                               ctypes.c_void_p(gate.data_ptr()),
+                               ctypes.c_void_p(mean_out.data_ptr()) if mean_out is not None else None, stream), 'opa_se_gate')
+    return gate
+
+
+def scale_channels_supported(x, gate):
+    """Can ``scale_channels_(x, gate)`` run?  ``x`` as ``_se_operand_ok`` says, ``gate`` ``[B, C]`` float32, contiguous, on ``x``'s device."""
+    return (x.dim() == 4 and _se_operand_ok(x, x.shape[1]) and gate.dtype == torch.float32 and gate.device == x.device
+            and tuple(gate.shape) == (x.shape[0], x.shape[1]) and gate.is_contiguous() and gate.data_ptr() % 16 == 0)
+
+
+def scale_channels_(x, gate):
+    """In place ``x[b, c] *= gate[b, c]`` for a channels-last float32 activation or channel slice: one vectorised pass."""
+    B, C, H, W = x.shape
+    _lib.check(_lib.lib().opa_se_scale(ctypes.c_void_p(x.data_ptr()), _pixel_stride(x), B, H * W, C, ctypes.c_void_p(gate.data_ptr()),
+                                       ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_se_scale')
+    return x
 
 
 def channel_interleave(a, b):

@@ -10,6 +10,8 @@ follows the reference so that the field tensors have the reference's shapes:
   factories ``network/factory.py:51-57``).
 * ``ShuffleNetV2K``: reference ``network/basenetworks.py:186-355`` (k16: stages
   [4,8,4], channels [24,348,696,1392,1392]; k30: [8,16,6], [32,512,1024,2048,2048]).
+* ``MobileNetV3``: torchvision's ``mobilenet_v3_large`` / ``mobilenet_v3_small`` feature extractors with the stride of the first
+  convolution set to 1, stride 16 (reference ``network/basenetworks.py:432-446``, ``network/factory.py:53-56``).
 * ``CompositeField4``: 1x1 conv -> PixelShuffle(2) -> crop last row/col -> view
   ``[B, F, C, H, W]`` -> sigmoid / index-add / softplus (reference
   ``network/heads.py:272-378``); 641 px -> 41 -> 82 -> 81.
@@ -364,9 +366,169 @@ class ShuffleNetV2K(BaseNetwork):
         return self.conv5(x)
 
 
+def _make_divisible(v, divisor=8):
+    new_v = max(divisor, int(v + divisor / 2) // divisor * divisor)
+    if new_v < 0.9 * v:
+        new_v += divisor
+    return new_v
+
+
+def _conv_bn_act(inp, oup, kernel_size, stride, groups, act):
+    layers = [nn.Conv2d(inp, oup, kernel_size, stride, kernel_size // 2, groups=groups, bias=False),
+              nn.BatchNorm2d(oup, eps=1e-3, momentum=0.01)]       # (the reference forces eps >= 1e-3, ``network/nets.py:78``)
+    if act is not None:
+        layers.append(act(inplace=True))
+    return nn.Sequential(*layers)
+
+
+class _SqueezeExcitation(nn.Module):
+    """``x * hardsigmoid(fc2(relu(fc1(mean(x)))))`` (torchvision's ``SqueezeExcitation``: the same attribute names)."""
+
+    def __init__(self, channels, squeeze):
+        super().__init__()
+        self.avgpool = nn.AdaptiveAvgPool2d(1)
+        self.fc1 = nn.Conv2d(channels, squeeze, 1)
+        self.fc2 = nn.Conv2d(squeeze, channels, 1)
+        self.activation = nn.ReLU()
+        self.scale_activation = nn.Hardsigmoid()
+
+    def forward(self, x):
+        return x * self.scale_activation(self.fc2(self.activation(self.fc1(self.avgpool(x)))))
+
+
+class _MBV3Block(nn.Module):
+    """MobileNetV3's inverted residual (torchvision's ``InvertedResidual``: ``.block`` = [expand,] depthwise, [se,] project)."""
+
+    def __init__(self, inp, kernel_size, exp, oup, use_se, use_hs, stride):
+        super().__init__()
+        act = nn.Hardswish if use_hs else nn.ReLU
+        layers = []
+        if exp != inp:
+            layers.append(_conv_bn_act(inp, exp, 1, 1, 1, act))
+        layers.append(_conv_bn_act(exp, exp, kernel_size, stride, exp, act))
+        if use_se:
+            layers.append(_SqueezeExcitation(exp, _make_divisible(exp // 4, 8)))
+        layers.append(_conv_bn_act(exp, oup, 1, 1, 1, None))
+        self.block = nn.Sequential(*layers)
+        self.use_res_connect = stride == 1 and inp == oup
+        self._has_expand, self._has_se = exp != inp, use_se
+        self._act = fused.ACT_HARDSWISH if use_hs else fused.ACT_RELU
+
+    fused = False
+
+    expand = property(lambda self: self.block[0][0] if self._has_expand else None, doc='the expanding 1x1 convolution, or None')
+    depthwise = property(lambda self: self.block[1 if self._has_expand else 0][0], doc='the depthwise convolution')
+    se = property(lambda self: self.block[-2] if self._has_se else None, doc='the squeeze-and-excitation module, or None')
+    project = property(lambda self: self.block[-1][0], doc='the projecting 1x1 convolution')
+
+    def enable_fused_(self):
+        """After conv+BN folding: the block may run on the project's kernels alone (``_forward_unit``); no parameter or buffer changes."""
+        assert not any(isinstance(m, nn.BatchNorm2d) for m in self.modules()), 'fold the batch norms first (fuse_conv_bn_)'
+        self.fused = True
+
+    @staticmethod
+    def taps_of(conv):
+        """The CURRENT depthwise weight tap-major, ``[k * k, C]`` (derived and cached, no part of a checkpoint)."""
+        def make():
+            k = conv.kernel_size[0]
+            return conv.weight.detach().reshape(conv.out_channels, k * k).t().contiguous()
+        return fused.derived(conv, '_opa_taps', (conv.weight,), make)
+
+    def _route_supported(self, x):
+        """Can the WHOLE block run on the project's kernels (``_forward_unit``)?  float32 outside autocast; every intermediate tensor is
+        a dense channels-last one this module allocates, so its layout is known and its sizes follow from ``x``'s."""
+        if not (fused.MBV3 and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and not torch.is_autocast_enabled()):
+            return False
+        dw, project = self.depthwise, self.project
+        k, s = dw.kernel_size[0], dw.stride[0]
+        if self._has_expand and not fused.unit_conv_x3_supported(self.expand, x):
+            return False
+        # (the stencil's limits are on the batch and the rows, which the expanding convolution keeps)
+        if not (dw.weight.dtype == torch.float32 and dw.bias is not None and dw.bias.dtype == torch.float32
+                and dw.weight.device == x.device and dw.padding == (k // 2, k // 2) and fused.dwconv_supported(x, k, s)):
+            return False
+        pixels = ((x.shape[2] - 1) // s + 1) * ((x.shape[3] - 1) // s + 1)          # of the depthwise output, which the SE kernels read
+        if self._has_se and not (fused._se_convs_ok(self.se.fc1, self.se.fc2) and self.se.fc1.weight.device == x.device
+                                 and x.shape[0] <= 65535 and pixels <= fused.SE_MAX_PIXELS and fused._lib.available()):
+            return False
+        if not (fused._unit_conv_ok(project) and project.weight.device == x.device):
+            return False
+        return not self.use_res_connect or fused._unit_operand_ok(x, project.out_channels)
+
+    def _forward_unit(self, x):
+        """Two to six launches: [GEMM + bias + activation,] the depthwise stencil + bias + activation, [the SE pool, its gate, the
+        scale in place,] GEMM + bias (+ the block's input as the residual)."""
+        h = x if not self._has_expand else fused.conv1x1_unit_x3(self.expand, x, act=self._act)
+        dw = self.depthwise
+        h = fused.dwconv_bias_act(h, self.taps_of(dw), dw.bias, dw.kernel_size[0], dw.stride[0], act=self._act)
+        if self._has_se:
+            fused.scale_channels_(h, fused.se_gate(h, self.se.fc1, self.se.fc2))
+        return fused.conv1x1_unit_x3(self.project, h, residual=x if self.use_res_connect else None, act=fused.ACT_NONE)
+
+    def forward(self, x):
+        if self.fused and self._route_supported(x):
+            return self._forward_unit(x)
+        out = self.block(x)
+        return out + x if self.use_res_connect else out
+
+
+class MobileNetV3(BaseNetwork):
+    """MobileNetV3 large / small as the reference uses them: torchvision's ``features`` with the stride of the first convolution set
+    to 1, so the overall stride is 16 (reference ``network/basenetworks.py:432-446``, ``network/factory.py:53-56``), restated from the
+    paper's tables with torchvision's module tree (``backbone.<i>.block.<j>...``), so that the ``base_net.backbone.*`` keys of a
+    reference checkpoint fit.  No checkpoint can be loaded offline: the fit is checked by key names and shapes only
+    (``tests/test_mobilenetv3_host.py``), never against real weights."""
+    # in, kernel, expanded, out, SE, hardswish, stride
+    CONFIGS = {
+        'mobilenetv3large': ([
+            (16, 3, 16, 16, False, False, 1), (16, 3, 64, 24, False, False, 2), (24, 3, 72, 24, False, False, 1),
+            (24, 5, 72, 40, True, False, 2), (40, 5, 120, 40, True, False, 1), (40, 5, 120, 40, True, False, 1),
+            (40, 3, 240, 80, False, True, 2), (80, 3, 200, 80, False, True, 1), (80, 3, 184, 80, False, True, 1),
+            (80, 3, 184, 80, False, True, 1), (80, 3, 480, 112, True, True, 1), (112, 3, 672, 112, True, True, 1),
+            (112, 5, 672, 160, True, True, 2), (160, 5, 960, 160, True, True, 1), (160, 5, 960, 160, True, True, 1)], 960),
+        'mobilenetv3small': ([
+            (16, 3, 16, 16, True, False, 2), (16, 3, 72, 24, False, False, 2), (24, 3, 88, 24, False, False, 1),
+            (24, 5, 96, 40, True, True, 2), (40, 5, 240, 40, True, True, 1), (40, 5, 240, 40, True, True, 1),
+            (40, 5, 120, 48, True, True, 1), (48, 5, 144, 48, True, True, 1), (48, 5, 288, 96, True, True, 2),
+            (96, 5, 576, 96, True, True, 1), (96, 5, 576, 96, True, True, 1)], 576),
+    }
+
+    def __init__(self, name='mobilenetv3large'):
+        blocks, out_features = self.CONFIGS[name]
+        super().__init__(name, stride=16, out_features=out_features)
+        layers = [_conv_bn_act(3, 16, 3, 1, 1, nn.Hardswish)]              # (torchvision: stride 2; the reference sets it to 1)
+        layers += [_MBV3Block(*cfg) for cfg in blocks]
+        layers.append(_conv_bn_act(blocks[-1][3], out_features, 1, 1, 1, nn.Hardswish))
+        self.backbone = nn.Sequential(*layers)
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode='fan_out')
+                if m.bias is not None:
+                    nn.init.zeros_(m.bias)
+
+    fused = False
+
+    def enable_fused_(self):
+        """The last 1x1 convolution may run through the split-operand GEMM's unit mode (bias + hardswish inside); the stem stays
+        with ``torch.nn.Conv2d`` like ShuffleNetV2K's ``input_block``.  No parameter or buffer changes."""
+        assert not any(isinstance(m, nn.BatchNorm2d) for m in self.modules()), 'fold the batch norms first (fuse_conv_bn_)'
+        self.fused = True
+
+    def forward(self, x):
+        *front, last = self.backbone
+        for m in front:
+            x = m(x)
+        conv = last[0]
+        if (self.fused and fused.MBV3 and x.is_cuda and not torch.is_autocast_enabled() and conv.bias is not None
+                and fused.unit_conv_x3_supported(conv, x)):
+            return fused.conv1x1_unit_x3(conv, x, act=fused.ACT_HARDSWISH)
+        return last(x)
+
+
 BASE_FACTORIES = {
     **{n: (lambda n=n: Resnet(n)) for n in Resnet.CONFIGS},
     **{n: (lambda n=n: ShuffleNetV2K(n)) for n in ShuffleNetV2K.CONFIGS},
+    **{n: (lambda n=n: MobileNetV3(n)) for n in MobileNetV3.CONFIGS},
 }
 
 
@@ -495,10 +657,11 @@ def fuse_conv_bn_(model):
 
 def optimize_for_inference_(model):
     """Fold every conv+BN pair, then switch the ResNet blocks to the fused-epilogue forward
-    (conv without bias followed by ONE ``fused.bias_act_`` pass) and the ShuffleNetV2K units and ``conv5`` to the HIP depthwise /
-    interleave kernels and the split-operand GEMM's unit mode."""
+    (conv without bias followed by ONE ``fused.bias_act_`` pass), the ShuffleNetV2K units and ``conv5`` to the HIP depthwise /
+    interleave kernels and the split-operand GEMM's unit mode, and the MobileNetV3 blocks and last convolution to the same GEMM,
+    the depthwise stencil and the squeeze-and-excitation kernels."""
     fuse_conv_bn_(model)
     for m in model.modules():
-        if isinstance(m, (_Bottleneck, _BasicBlock, Resnet, _InvertedResidualK, ShuffleNetV2K)):
+        if isinstance(m, (_Bottleneck, _BasicBlock, Resnet, _InvertedResidualK, ShuffleNetV2K, _MBV3Block, MobileNetV3)):
             m.enable_fused_()
     return model
