@@ -531,6 +531,21 @@ int opa_dwconv_act(const void* x_dev, int64_t x_pixel_stride, const void* w_dev,
                    void* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w,
                    int32_t channels, int32_t k, int32_t stride, int32_t dtype, int32_t act, void* stream);
 
+/* Grouped 3x3 convolution, padding 1, dilation 1, stride 1 or 2, as many output as input channels, float32, channels innermost,
+ * with the folded batch-norm bias and optionally ReLU (fmaxf) applied before the single store: the middle convolution of a
+ * ResNeXt bottleneck (reference network/basenetworks.py:71-150 with torchvision's grouped Bottleneck).
+ *     out[b, y, x, co] = act(bias[co] + sum_{t, ci} x[b, y*s - 1 + ky, x*s - 1 + kx, (co / cg) * cg + ci] * wt[t][ci][co])
+ *  x_dev [B, h, w, *] with x_pixel_stride floats between pixels (a channel slice of a wider tensor is fine),
+ *  wt_dev [9][group_width][channels]: wt[ky*3 + kx][ci][co] = weight[co][ci][ky][kx] of the [channels, group_width, 3, 3] weight,
+ *  bias_dev [channels] or NULL, out_dev [B, ho, wo, *] with out_pixel_stride, ho = (h - 1) / stride + 1 (likewise wo).
+ * group_width 4, 8, 16, 32 or 64; channels a multiple of it; pixel strides multiples of 4 and >= channels; every pointer on 16
+ * bytes; batch <= 65535 (grid.y) and tiles * ceil(channels / 64) of one image < 2^31 (grid.x); offsets are 64-bit, so the
+ * tensors may hold 2^31 elements or more.  Anything else: OPA_ERR_INVALID_ARGUMENT before any launch.  batch, h or w == 0:
+ * OPA_OK, nothing runs.  The order of every addition depends on group_width alone (no atomics): equal inputs give equal bits. */
+int opa_gconv3x3_bias_act_f32(const float* x_dev, int64_t x_pixel_stride, const float* wt_dev, const float* bias_dev,
+                              float* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w, int32_t channels,
+                              int32_t group_width, int32_t stride, int32_t relu, void* stream);
+
 /* torch.cat((a, b), 1) followed by channel_shuffle(groups = 2) of the same unit, in one pass over channels-last rows:
  * out[r, 2i] = a[r, i], out[r, 2i+1] = b[r, i]; a / b with their own pixel strides, out dense [rows, 2*half]. */
 int opa_channel_interleave(const void* a_dev, int64_t a_pixel_stride, const void* b_dev, int64_t b_pixel_stride,

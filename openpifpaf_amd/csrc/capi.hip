@@ -1081,6 +1081,31 @@ int opa_dwconv_act(const void* x_dev, int64_t x_pixel_stride, const void* w_dev,
     return OPA_OK;
 }
 
+int opa_gconv3x3_bias_act_f32(const float* x_dev, int64_t x_pixel_stride, const float* wt_dev, const float* bias_dev,
+                              float* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w, int32_t channels,
+                              int32_t group_width, int32_t stride, int32_t relu, void* stream) {
+    const char* const me = "opa_gconv3x3_bias_act_f32: ";
+    if (!x_dev || !wt_dev || !out_dev) return fail(OPA_ERR_INVALID_ARGUMENT, std::string(me) + "x, wt and out must not be NULL");
+    if (group_width != 4 && group_width != 8 && group_width != 16 && group_width != 32 && group_width != 64)
+        return fail(OPA_ERR_INVALID_ARGUMENT, std::string(me) + "group_width must be 4, 8, 16, 32 or 64");
+    if (channels <= 0 || channels % group_width != 0)
+        return fail(OPA_ERR_INVALID_ARGUMENT, std::string(me) + "channels must be a positive multiple of group_width");
+    if (stride != 1 && stride != 2) return fail(OPA_ERR_INVALID_ARGUMENT, std::string(me) + "stride must be 1 or 2");
+    if (x_pixel_stride < channels || out_pixel_stride < channels || x_pixel_stride % 4 != 0 || out_pixel_stride % 4 != 0)
+        return fail(OPA_ERR_INVALID_ARGUMENT, std::string(me) + "pixel strides must be multiples of 4 and at least channels");
+    if (((uintptr_t)x_dev | (uintptr_t)wt_dev | (uintptr_t)out_dev | (uintptr_t)bias_dev) & 15)
+        return fail(OPA_ERR_INVALID_ARGUMENT, std::string(me) + "pointers must be 16-B aligned");
+    if (batch < 0 || h < 0 || w < 0) return fail(OPA_ERR_INVALID_ARGUMENT, std::string(me) + "negative batch, h or w");
+    if (batch == 0 || h == 0 || w == 0) return OPA_OK;                                   // nothing to compute
+    if (batch > 65535) return fail(OPA_ERR_INVALID_ARGUMENT, std::string(me) + "batch must not exceed 65535 (grid.y)");
+    if (gconv3x3_workgroups(h, w, channels, stride) > 2147483647ll)                      // (offsets are 64-bit: no limit on the elements)
+        return fail(OPA_ERR_INVALID_ARGUMENT, std::string(me) + "tiles * channel chunks of one image must not exceed 2^31 - 1 (grid.x)");
+    hipError_t e = launch_gconv3x3(x_dev, x_pixel_stride, wt_dev, bias_dev, out_dev, out_pixel_stride, batch, h, w, channels,
+                                   group_width, stride, relu != 0, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "grouped 3x3 convolution");
+    return OPA_OK;
+}
+
 static const char* se_check(int64_t x_pixel_stride, int32_t batch, int64_t pixels, int32_t channels) {
     if (batch <= 0 || batch > 65535 || pixels <= 0 || pixels > 65535ll * kSePoolPixels || channels <= 0 || channels > 8192)
         return "batch, pixels or channels out of range";

@@ -288,6 +288,13 @@ hipError_t launch_dwconv(const void* x, long long xs, const void* w, const void*
 hipError_t launch_channel_interleave(const void* a, long long as, const void* b, long long bs, void* out,
                                      long long rows, int half, int dtype, hipStream_t st);
 
+// Grouped 3x3 convolution, padding 1, C channels in groups of CG (4, 8, 16, 32, 64), stride S (1, 2), float32 (gconv.hip):
+// x [B, H, W, *] with pixel stride xs, wt [9][CG][C], out [B, Ho, Wo, *] with pixel stride os.  grid.y = B;
+// gconv3x3_workgroups = grid.x of the launch for one image.
+long long gconv3x3_workgroups(int H, int W, int C, int S);
+hipError_t launch_gconv3x3(const float* x, long long xs, const float* wt, const float* bias, float* out, long long os,
+                           int B, int H, int W, int C, int CG, int S, int relu, hipStream_t st);
+
 // Squeeze-and-excitation of a MobileNetV3 block (se.hip) on a channels-last float32 tensor [B, HW, C] with pixel stride xs:
 // pool (partial sums [B][se_pool_chunks(HW)][C] in float64), gate (g [B, C]), apply (x *= g in place).
 constexpr int kSePoolPixels = 512;        // OPA_SE_POOL_PIXELS: pixels of one partial sum

@@ -285,6 +285,60 @@ def conv3x3_bias_act_x3(conv, x, bias, relu=True):
     return out
 
 
+# The GROUPED 3x3 convolution of a ResNeXt bottleneck (32 groups of 4 ... 64 channels) as one HIP kernel with the bias and the ReLU
+# inside (csrc/gconv.hip); OPA_GCONV=1 (or fused.GCONV = True) switches the route on.  It is never timed and makes no choice-table
+# entry: where it is supported it runs.  It stays OFF by default -- torch's grouped convolution + the epilogue pass -- until the
+# kernel has been timed against that route on every (group width, stride) class at 641 px (tools/gpu/gconv_times.py): no speed is
+# claimed for a route nobody has measured.
+GCONV = os.environ.get('OPA_GCONV', '0') != '0'
+GCONV_WIDTHS = (4, 8, 16, 32, 64)            # channels per group the kernel is instantiated for
+
+
+def gconv3x3_supported(conv, x, bias):
+    """Can ``gconv3x3_bias_act(conv, x, bias)`` run?  A grouped 3x3 convolution (padding 1, dilation 1, square stride 1 or 2, as many
+    output as input channels, a group width of ``GCONV_WIDTHS``, no bias of its own: the folded one arrives separately) of a dense
+    channels-last float32 tensor on the GPU, outside autocast, not followed by autograd."""
+    if not (GCONV and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and not torch.is_autocast_enabled()):
+        return False
+    if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad or (bias is not None and bias.requires_grad)):
+        return False
+    c = conv.in_channels
+    return (conv.groups > 1 and conv.kernel_size == (3, 3) and conv.padding == (1, 1) and conv.dilation == (1, 1)
+            and conv.stride in ((1, 1), (2, 2)) and c == conv.out_channels and c % conv.groups == 0
+            and c // conv.groups in GCONV_WIDTHS and conv.bias is None and conv.weight.dtype == torch.float32
+            and conv.weight.device == x.device and x.shape[1] == c and x.is_contiguous(memory_format=torch.channels_last)
+            and x.data_ptr() % 16 == 0 and 0 < x.shape[0] <= 65535                     # (grid.y of the kernel)
+            and (bias is None or (bias.dtype == torch.float32 and bias.device == x.device and bias.is_contiguous()
+                                  and bias.numel() == c and bias.data_ptr() % 16 == 0))
+            and _lib.available())
+
+
+def gconv_weight_of(conv):
+    """The operand of ``opa_gconv3x3_bias_act_f32`` derived from the CURRENT ``conv.weight`` (``[C, cg, 3, 3]``): tap-major with the
+    output channel innermost, ``[9, cg, C]`` with ``wt[ky * 3 + kx][ci][co] = weight[co][ci][ky][kx]``.  Derived and cached
+    (``derived``): no buffer, no part of a state dict, computed again whenever the weight was replaced, moved or changed in place."""
+    def make():
+        w = conv.weight.detach()
+        return w.permute(2, 3, 1, 0).reshape(9, w.shape[1], w.shape[0]).contiguous()
+    return derived(conv, '_opa_gconv_wt', (conv.weight,), make)
+
+
+def gconv3x3_bias_act(conv, x, bias, relu=True):
+    """``act(conv(x) + bias)`` for a grouped 3x3 convolution (reference ``network/basenetworks.py:71-150`` with torchvision's grouped
+    Bottleneck: ResNeXt) in one HIP kernel, float32 in and out.  ``gconv3x3_supported`` says whether this can run."""
+    wt = gconv_weight_of(conv)
+    B, C, H, W = x.shape
+    s = conv.stride[0]
+    out = torch.empty((B, C, (H - 1) // s + 1, (W - 1) // s + 1), dtype=torch.float32, device=x.device,
+                      memory_format=torch.channels_last)
+    _lib.check(_lib.lib().opa_gconv3x3_bias_act_f32(
+        ctypes.c_void_p(x.data_ptr()), C, ctypes.c_void_p(wt.data_ptr()),
+        ctypes.c_void_p(bias.data_ptr()) if bias is not None else None, ctypes.c_void_p(out.data_ptr()), C,
+        B, H, W, C, C // conv.groups, s, int(bool(relu)),
+        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_gconv3x3_bias_act_f32')
+    return out
+
+
 # ... and the heads' 1x1 convolutions, whose output channels are no multiple of the kernel's 64-wide tile (OPA_GEMM3_HEAD=0: off)
 X3_HEAD = os.environ.get('OPA_GEMM3_HEAD', '1') != '0'
 

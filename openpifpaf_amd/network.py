@@ -44,13 +44,14 @@ def _take_biases(block, conv_names):
 class _Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, base_width=64):
         super().__init__()
-        self.conv1 = nn.Conv2d(inplanes, planes, 1, bias=False)
-        self.bn1 = nn.BatchNorm2d(planes)
-        self.conv2 = nn.Conv2d(planes, planes, 3, stride, 1, bias=False)
-        self.bn2 = nn.BatchNorm2d(planes)
-        self.conv3 = nn.Conv2d(planes, planes * 4, 1, bias=False)
+        width = int(planes * base_width / 64) * groups       # torchvision's rule (ResNeXt: 32 groups of base_width * planes / 64)
+        self.conv1 = nn.Conv2d(inplanes, width, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(width)
+        self.conv2 = nn.Conv2d(width, width, 3, stride, 1, groups=groups, bias=False)
+        self.bn2 = nn.BatchNorm2d(width)
+        self.conv3 = nn.Conv2d(width, planes * 4, 1, bias=False)
         self.bn3 = nn.BatchNorm2d(planes * 4)
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
@@ -85,6 +86,9 @@ class _Bottleneck(nn.Module):
                                  lambda: fused.conv3x3_bias_act_x3(self.conv2, h, self.fb2, True),
                                  lambda: fused.bias_act_(self.conv2(h), self.fb2))
                 wino = True                                               # (bias + ReLU applied: nothing left for the next operand)
+            elif fused.gconv3x3_supported(self.conv2, out, self.fb2):    # ... float32 grouped (ResNeXt): one stencil kernel,
+                out = fused.gconv3x3_bias_act(self.conv2, out, self.fb2, True)        # bias + ReLU inside
+                wino = True
             else:
                 out = self.conv2(out)                                     # ... bfloat16: MIOpen, raw output ...
             a_bias = None if wino else self.fb2
@@ -160,17 +164,22 @@ class BaseNetwork(nn.Module):
 
 
 class Resnet(BaseNetwork):
-    """ResNet-18/34/50/101 without the input max-pool: stride 16."""
+    """ResNet-18/34/50/101/152 and ResNeXt-50 (32x4d) / -101 (32x8d) without the input max-pool: stride 16 (reference
+    ``network/factory.py:51-79``)."""
     CONFIGS = {
         'resnet18': (_BasicBlock, [2, 2, 2, 2]),
         'resnet34': (_BasicBlock, [3, 4, 6, 3]),
         'resnet50': (_Bottleneck, [3, 4, 6, 3]),
         'resnet101': (_Bottleneck, [3, 4, 23, 3]),
+        'resnet152': (_Bottleneck, [3, 8, 36, 3]),
+        'resnext50': (_Bottleneck, [3, 4, 6, 3], 32, 4),          # (..., groups, base width)
+        'resnext101': (_Bottleneck, [3, 4, 23, 3], 32, 8),
     }
 
     def __init__(self, name='resnet50'):
-        block, layers = self.CONFIGS[name]
+        block, layers, *grouped = self.CONFIGS[name]
         super().__init__(name, stride=16, out_features=512 * block.expansion)
+        self._block_args = dict(zip(('groups', 'base_width'), grouped))
         self.inplanes = 64
         self.input_block = nn.Sequential(
             nn.Conv2d(3, 64, 7, 2, 3, bias=False), nn.BatchNorm2d(64), nn.ReLU(inplace=True))
@@ -188,9 +197,9 @@ class Resnet(BaseNetwork):
             downsample = nn.Sequential(
                 nn.Conv2d(self.inplanes, planes * block.expansion, 1, stride, bias=False),
                 nn.BatchNorm2d(planes * block.expansion))
-        layers = [block(self.inplanes, planes, stride, downsample)]
+        layers = [block(self.inplanes, planes, stride, downsample, **self._block_args)]
         self.inplanes = planes * block.expansion
-        layers += [block(self.inplanes, planes) for _ in range(1, blocks)]
+        layers += [block(self.inplanes, planes, **self._block_args) for _ in range(1, blocks)]
         return nn.Sequential(*layers)
 
     def enable_fused_(self):
