@@ -1,133 +1,40 @@
-"""Fused inference epilogues for the field-producing network (HIP, ``csrc/epilogue.hip``)."""
-import ctypes
+"""The route layer of the trunk: everything between the ``torch.nn`` modules of ``network.py`` and the HIP kernels under ``csrc/``.
+
+For every kernel family it holds the predicate that says whether the kernel can run for given operands (``*_supported``: the
+kernel's contract), the operands derived from the module's parameters (split, padded, transposed copies, cached on the module:
+``derived``) and the launcher that hands them to the C ABI.  Where a kernel competes with another way to compute the same tensor,
+the choice is made once per shape and remembered in one table (``_CHOICE``, shipped as ``conv1x1_pinned.json``): ``conv_bias_act``
+and ``pick`` say what the candidates are, ``_decide`` makes the choice.  In this order: the launcher, the switches, the choice
+table and the decision, the derived operands, then the routes by kernel family -- the epilogue passes, the 1x1 GEMMs, the
+split-operand convolutions (pair, 3x3, stem, heads, unit mode), the grouped and the depthwise stencils, squeeze-and-excitation."""
 import os
 
 import torch
 
 from . import _lib
+from .native import _ptr, _stream
 
 _DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+ACT_NONE, ACT_RELU, ACT_HARDSWISH = 0, 1, 2      # the activation codes of opa_dwconv_act and opa_gemm_unit_act_f32x3
 
 
-def _nhwc_rows(x):
-    """(rows, channels) if ``x`` is physically [rows, channels]-contiguous, else None."""
-    if x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last):
-        return x.shape[0] * x.shape[2] * x.shape[3], x.shape[1]
-    if x.dim() == 2 and x.is_contiguous():
-        return x.shape[0], x.shape[1]
-    return None
+# ---- the launcher ---------------------------------------------------------------------------------------------------------------
+
+def _launch(symbol, *args):
+    """Calls ``symbol`` of the library with ``args`` followed by the current stream; any status but OK raises under that name.
+    ``_lib.SYMBOLS`` declares every argument's type: an address goes in as a plain integer or None (``_ptr``)."""
+    _lib.check(getattr(_lib.lib(), symbol)(*args, _stream()), symbol)
 
 
-def bias_act_(x, bias, residual=None, relu=True):
-    """In place ``x = act(x + bias[c] (+ residual))`` for a channels_last activation.
-
-    One HIP kernel on the GPU; the equivalent PyTorch ops elsewhere (CPU tests, odd layouts)."""
-    rc = _nhwc_rows(x) if x.is_cuda else None
-    per_vec = 4 if x.dtype == torch.float32 else 8
-    ok = (rc is not None and x.dtype in _DTYPES and rc[1] % per_vec == 0 and bias.dtype == x.dtype
-          and bias.is_contiguous() and x.data_ptr() % 16 == 0 and bias.data_ptr() % 16 == 0
-          and (residual is None or (residual.dtype == x.dtype and residual.shape == x.shape
-                                    and _nhwc_rows(residual) is not None and residual.data_ptr() % 16 == 0)))
-    if not ok:
-        x.add_(bias.view(1, -1, 1, 1) if x.dim() == 4 else bias)
-        if residual is not None:
-            x.add_(residual)
-        return torch.relu_(x) if relu else x
-    _lib.check(_lib.lib().opa_bias_act(
-        ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(bias.data_ptr()),
-        ctypes.c_void_p(residual.data_ptr()) if residual is not None else None,
-        rc[0], rc[1], _DTYPES[x.dtype], int(bool(relu)),
-        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_bias_act')
-    return x
+def _act_code(relu, act):
+    """The activation code of a launcher that takes ``relu=`` and ``act=``: ``act`` where it is given."""
+    return int(bool(relu)) if act is None else int(act)
 
 
-def conv1x1_supported(x, weight, bias=None, residual=None, a_bias=None):
-    """True if ``conv1x1_bias_act`` can run the HIP GEMM for these operands.  The kernels read raw buffers:
-    EVERY operand must have the activation's dtype, bfloat16 or float32 (autocast keeps parameters in float32
-    next to bfloat16 activations -- those take the PyTorch path), the activation channels_last, the residual
-    channels_last of the output's shape."""
-    dt = x.dtype
-    if not (x.is_cuda and dt in (torch.bfloat16, torch.float32) and x.dim() == 4
-            and x.is_contiguous(memory_format=torch.channels_last)
-            and weight.dtype == dt and weight.is_cuda
-            and weight.shape[1] % (64 if dt == torch.bfloat16 else 32) == 0 and weight.shape[0] % 64 == 0
-            and weight.shape[1] == x.shape[1]):
-        return False
-    for vec, n in ((bias, weight.shape[0]), (a_bias, weight.shape[1])):
-        if vec is not None and not (vec.dtype == dt and vec.is_cuda and vec.is_contiguous()
-                                    and vec.numel() == n and vec.data_ptr() % 16 == 0):
-            return False
-    if residual is not None:
-        if not (residual.dtype == dt and residual.is_cuda
-                and tuple(residual.shape) == (x.shape[0], weight.shape[0], x.shape[2], x.shape[3])
-                and residual.is_contiguous(memory_format=torch.channels_last) and residual.data_ptr() % 16 == 0):
-            return False
-    return x.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0
+# ---- the switches (read ONCE, at import; the attributes can be set afterwards) ---------------------------------------------------
 
-
-def conv1x1_bias_act(x, weight2d, bias, residual=None, relu=True, a_bias=None):
-    """``act(conv1x1(x, weight) + bias (+ residual))`` as ONE MFMA GEMM kernel with fused epilogue.
-
-    :param x: ``[B, C_in, H, W]`` bfloat16 or float32, channels_last
-    :param weight2d: ``[C_out, C_in]`` of the same dtype, contiguous
-    :param a_bias: ``[C_in]``: ``x`` is the RAW output of the preceding convolution and
-        ``relu(x + a_bias)`` -- that convolution's epilogue -- is applied while the operand is staged
-    :returns: ``[B, C_out, H, W]`` of that dtype, channels_last
-    """
-    B, K, H, W = x.shape
-    N = weight2d.shape[0]
-    out = torch.empty((B, N, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    if x.dtype == torch.float32:
-        _lib.check(_lib.lib().opa_gemm_bias_act_f32(
-            ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(a_bias.data_ptr()) if a_bias is not None else None,
-            ctypes.c_void_p(weight2d.data_ptr()), ctypes.c_void_p(bias.data_ptr()),
-            ctypes.c_void_p(residual.data_ptr()) if residual is not None else None,
-            ctypes.c_void_p(out.data_ptr()), B * H * W, N, K, int(bool(relu)),
-            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_gemm_bias_act_f32')
-        return out
-    if a_bias is not None:
-        _lib.check(_lib.lib().opa_gemm_pro_bias_act_bf16(
-            ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(a_bias.data_ptr()), ctypes.c_void_p(weight2d.data_ptr()),
-            ctypes.c_void_p(bias.data_ptr()), ctypes.c_void_p(residual.data_ptr()) if residual is not None else None,
-            ctypes.c_void_p(out.data_ptr()), B * H * W, N, K, int(bool(relu)),
-            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_gemm_pro_bias_act_bf16')
-        return out
-    _lib.check(_lib.lib().opa_gemm_bias_act_bf16(
-        ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(weight2d.data_ptr()), ctypes.c_void_p(bias.data_ptr()),
-        ctypes.c_void_p(residual.data_ptr()) if residual is not None else None,
-        ctypes.c_void_p(out.data_ptr()), B * H * W, N, K, int(bool(relu)),
-        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_gemm_bias_act_bf16')
-    return out
-
-
-def split_weight(weight2d):
-    """``[N, K]`` float32 -> ``[3, N, K]`` bfloat16: the three pieces of every weight (its 24-bit significand cut into 8 + 8 + 8
-    bits: ``w1`` = ``w`` with the low 16 bits cleared, ``r = w - w1``, ``w2`` = ``r`` with the low 16 bits cleared, ``w3 = r - w2``;
-    every step is exact and ``w1 + w2 + w3 == w`` bit for bit) -- the operand of ``opa_gemm_bias_act_f32x3`` (``csrc/gemm_f32x3.hip``)."""
-    w = weight2d.detach().to(torch.float32).contiguous()
-
-    def top(x):
-        return (x.view(torch.int32) & -65536).view(torch.float32)
-    w1 = top(w)
-    r1 = w - w1
-    w2 = top(r1)
-    w3 = r1 - w2
-    out = torch.stack((w1, w2, w3)).to(torch.bfloat16)          # (exact: each piece has at most 8 significant bits)
-    return out.contiguous()
-
-
-def conv1x1_bias_act_x3(x, w3, bias, residual=None, relu=True, a_bias=None, terms=9):
-    """``conv1x1_bias_act`` for float32 through the split-operand kernel: ``w3`` = ``split_weight(weight2d)``; ``terms`` 9 or 6."""
-    B, K, H, W = x.shape
-    N = w3.shape[1]
-    out = torch.empty((B, N, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    _lib.check(_lib.lib().opa_gemm_bias_act_f32x3(
-        ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(a_bias.data_ptr()) if a_bias is not None else None,
-        ctypes.c_void_p(w3.data_ptr()), ctypes.c_void_p(bias.data_ptr()),
-        ctypes.c_void_p(residual.data_ptr()) if residual is not None else None,
-        ctypes.c_void_p(out.data_ptr()), B * H * W, N, K, int(bool(relu)), int(terms),
-        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_gemm_bias_act_f32x3')
-    return out
+def _switch(name, default):
+    return os.environ.get(name, default) != '0'
 
 
 # float32 1x1 convolutions may take the split-operand kernel (choice 'gemm3'): float32 in and out, every product formed from
@@ -136,381 +43,34 @@ def conv1x1_bias_act_x3(x, w3, bias, residual=None, relu=True, a_bias=None, term
 # torch's own float32 convolution on every ResNet-50 shape (tools/gpu/gemm_x3_probe.py, tests/test_gpu_gemm_x3.py).
 # OPA_GEMM3=0 (or fused.X3_TERMS = 0) takes the choice away.
 X3_TERMS = {'0': 0, '6': 6, '9': 9}.get(os.environ.get('OPA_GEMM3', '6'), 6)
-
-
-def _x3_supported(x, weight):
-    return X3_TERMS in (6, 9) and x.dtype == torch.float32 and weight.shape[1] % 64 == 0
-
-
-def derived(module, name, sources, make):
-    """``make()`` -- an operand derived from the tensors ``sources`` (parameters, buffers; None where there is none) -- computed
-    once, kept on ``module`` as attribute ``name`` and computed again whenever a source was replaced, moved, converted or changed
-    in place (``load_state_dict``, ``.to()``, an optimizer step): the key is (data pointer, version counter, device, dtype) of each.
-    The entry holds on to the sources' storages, so that no later tensor can be handed the same address while it is the key."""
-    key = tuple(None if t is None else (t.data_ptr(), t._version, str(t.device), t.dtype) for t in sources)
-    cached = getattr(module, name, None)
-    if cached is None or cached[0] != key:
-        cached = (key, make(), [t.untyped_storage() for t in sources if t is not None])
-        setattr(module, name, cached)
-    return cached[1]
-
-
-def _split_weight_of(conv, w2d):
-    """``split_weight(w2d)`` for ``w2d``, the ``[N, K]`` view of ``conv.weight``: computed once per convolution and kept on the module
-    (inference: the weight does not change; a weight replaced, moved or changed since is split again)."""
-    return derived(conv, '_opa_w3', (conv.weight,), lambda: split_weight(w2d))
-
-
 FORCE_PICK = os.environ.get('OPA_GEMM3_PICK') or None        # 'x3' | 'conv': every pick() takes that side (tests, A/B)
-
-
-def pick(kind, m, k, n, flag_a, flag_b, run_x3, run_other, written=None, timing=True):
-    """One of two ways to compute the same tensor -- a split-operand kernel (``run_x3``) or what the trunk did before
-    (``run_other``: MIOpen's convolution + the fused passes) -- chosen ONCE per shape like ``conv_bias_act`` chooses its GEMM: from
-    the shipped table (``conv1x1_pinned.json``, key dtype ``'torch.float32/<kind>'``), else by timing both on the first call; while
-    a stream is being captured or in a job of several ranks, where timing is not an option, by size (the split-operand kernels win
-    from ~16 000 output pixels: a batch of one 641-px image keeps MIOpen in layers 3-4).  Returns the chosen function's result.
-    ``written``: an operand that ``run_other`` changes in place (the epilogue its producer left to this consumer); timing calls
-    ``run_other`` several times, so the operand is saved before and put back after -- the winner computes from what the caller
-    passed, whoever wins.  ``timing=False``: a shape the table does not know is decided by size ALWAYS -- eager or capturing, one
-    rank or many -- and nothing is timed (measurements go into the table: ``tools/gpu/dump_conv_choices.py``)."""
-    if FORCE_PICK in ('x3', 'conv'):
-        return run_x3() if FORCE_PICK == 'x3' else run_other()
-    key = ('torch.float32/' + kind, int(m), int(k), int(n), bool(flag_a), bool(flag_b))
-    choice = _CHOICE.get(key)
-    if choice is None:
-        if not timing or torch.cuda.is_current_stream_capturing() or _in_multi_rank_job():
-            choice = 'x3' if m >= 16384 else 'conv'
-        else:
-            saved = written.clone() if written is not None else None
-            choice = 'x3' if _time_ms(run_x3) <= _time_ms(run_other) else 'conv'
-            if saved is not None:
-                written.copy_(saved)
-        _CHOICE[key] = choice
-    return run_x3() if choice == 'x3' else run_other()
-
-
 # ... and the block's LAST 1x1 convolution together with its downsampling convolution as one product (OPA_GEMM3_PAIR=0: off)
-X3_PAIR = os.environ.get('OPA_GEMM3_PAIR', '1') != '0'
-
-
-def pair_supported(conv, dconv, h, x, bias, a_bias=None):
-    """Can ``conv(h) + dconv(x)`` run as ONE split-operand product (``conv1x1_pair_bias_act_x3``)?  float32, channels_last,
-    both 1x1 without bias / groups / padding, ``conv`` of stride 1, ``dconv`` of any stride."""
-    k1, k2 = conv.in_channels, dconv.in_channels
-    ok = (X3_PAIR and X3_TERMS in (6, 9) and h.is_cuda and h.dtype == torch.float32 and x.dtype == torch.float32
-          and conv.kernel_size == (1, 1) and dconv.kernel_size == (1, 1) and conv.stride == (1, 1) and dconv.stride[0] == dconv.stride[1]
-          and conv.groups == 1 and dconv.groups == 1 and conv.padding == (0, 0) and dconv.padding == (0, 0)
-          and conv.bias is None and dconv.bias is None and conv.out_channels == dconv.out_channels
-          and k1 % 32 == 0 and (k1 + k2) % 64 == 0 and k2 % 4 == 0 and conv.out_channels % 64 == 0
-          and h.dim() == 4 and x.dim() == 4 and h.is_contiguous(memory_format=torch.channels_last)
-          and x.is_contiguous(memory_format=torch.channels_last) and h.shape[1] == k1 and x.shape[1] == k2
-          and h.shape[0] == x.shape[0] and h.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0
-          and bias.dtype == torch.float32 and bias.is_contiguous() and bias.data_ptr() % 16 == 0
-          and x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31)
-    if not ok:
-        return False
-    s = dconv.stride[0]
-    if (h.shape[2], h.shape[3]) != ((x.shape[2] - 1) // s + 1, (x.shape[3] - 1) // s + 1):
-        return False
-    return a_bias is None or (a_bias.dtype == torch.float32 and a_bias.numel() == k1 and a_bias.is_contiguous())
-
-
-def _pair_weight_of(conv, dconv, a_bias=None):
-    """The operands of ``conv1x1_pair_bias_act_x3`` derived from the current parameters: ``split_weight([W | Wd])`` and ``a_bias``
-    followed by zeros for ``dconv``'s channels (None without ``a_bias``) -- kept on ``conv`` like ``_split_weight_of``."""
-    k1, k2, n = conv.in_channels, dconv.in_channels, conv.out_channels
-
-    def make():
-        w1, w2 = conv.weight.detach().reshape(n, k1), dconv.weight.detach().reshape(n, k2)
-        ab = None if a_bias is None else torch.cat((a_bias.detach().float(), torch.zeros(k2, device=a_bias.device)))
-        return split_weight(torch.cat((w1, w2), dim=1)), ab
-    return derived(conv, '_opa_w3_pair', (conv.weight, dconv.weight, a_bias), make)
-
-
-def conv1x1_pair_bias_act_x3(conv, dconv, h, x, bias, relu=True, a_bias=None):
-    """``act(conv(h) + dconv(x) + bias)`` -- the last 1x1 convolution of a ResNet block and the block's downsampling convolution
-    (reference ``network/basenetworks.py:71-150``: torchvision's Bottleneck) -- as ONE product ``[h | x at stride] * [W ; Wd]^T`` of
-    the split-operand kernel (``opa_gemm2_bias_act_f32x3``): the identity tensor is neither written nor read back.  With
-    ``a_bias``, ``h`` is the raw output of the preceding convolution and ``relu(h + a_bias)`` is applied while it is staged (``x``
-    gets zeros: it is non-negative).  ``pair_supported`` says whether this can run."""
-    k1, k2, n = conv.in_channels, dconv.in_channels, conv.out_channels
-    w3, ab = _pair_weight_of(conv, dconv, a_bias)
-    B, _, H, W = x.shape
-    out = torch.empty((B, n, h.shape[2], h.shape[3]), dtype=torch.float32, device=h.device, memory_format=torch.channels_last)
-    _lib.check(_lib.lib().opa_gemm2_bias_act_f32x3(
-        ctypes.c_void_p(h.data_ptr()), k1, ctypes.c_void_p(x.data_ptr()), k2, B, H, W, dconv.stride[0],
-        ctypes.c_void_p(ab.data_ptr()) if ab is not None else None, ctypes.c_void_p(w3.data_ptr()), ctypes.c_void_p(bias.data_ptr()),
-        ctypes.c_void_p(out.data_ptr()), n, int(bool(relu)), int(X3_TERMS),
-        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_gemm2_bias_act_f32x3')
-    return out
-
-
+X3_PAIR = _switch('OPA_GEMM3_PAIR', '1')
 # ... and the STRIDED 3x3 convolutions (the head of ResNet layers 2-4) as an implicit GEMM of the same kernel (OPA_GEMM3_3X3=0: off)
-X3_CONV3 = os.environ.get('OPA_GEMM3_3X3', '1') != '0'
-
-
-def split_weight_3x3(weight):
-    """``[N, C, 3, 3]`` float32 -> ``split_weight`` of ``[N, (ky, kx, c)]``: the operand of ``opa_conv3x3_f32x3``."""
-    n, c = weight.shape[0], weight.shape[1]
-    return split_weight(weight.detach().permute(0, 2, 3, 1).reshape(n, 9 * c))
-
-
-def conv3x3_x3_supported(conv, x, bias):
-    return (X3_CONV3 and X3_TERMS in (6, 9) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
-            and x.is_contiguous(memory_format=torch.channels_last) and conv.kernel_size == (3, 3) and conv.padding == (1, 1)
-            and conv.stride[0] == conv.stride[1] and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
-            and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0 and x.shape[1] == conv.in_channels
-            and x.data_ptr() % 16 == 0 and bias.dtype == torch.float32 and bias.is_contiguous() and bias.data_ptr() % 16 == 0
-            and (x.shape[0] * x.shape[2] * x.shape[3] + x.shape[3] + 1) * x.shape[1] * 4 < 2 ** 31)
-
-
-def _split_weight_3x3_of(conv):
-    """``split_weight_3x3(conv.weight)``, kept on the module like ``_split_weight_of``."""
-    return derived(conv, '_opa_w3_3x3', (conv.weight,), lambda: split_weight_3x3(conv.weight))
-
-
-def conv3x3_bias_act_x3(conv, x, bias, relu=True):
-    """``act(conv(x) + bias)`` for a 3x3 convolution with padding 1 and any stride (reference ``network/basenetworks.py:71-150``: the
-    strided convolution of a ResNet block) as an implicit GEMM of the split-operand kernel -- float32 in and out."""
-    w3 = _split_weight_3x3_of(conv)
-    B, C, H, W = x.shape
-    s = conv.stride[0]
-    out = torch.empty((B, conv.out_channels, (H - 1) // s + 1, (W - 1) // s + 1), dtype=torch.float32, device=x.device,
-                      memory_format=torch.channels_last)
-    _lib.check(_lib.lib().opa_conv3x3_f32x3(
-        ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(w3.data_ptr()), ctypes.c_void_p(bias.data_ptr()),
-        ctypes.c_void_p(out.data_ptr()), B, H, W, C, conv.out_channels, s, int(bool(relu)), int(X3_TERMS),
-        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_conv3x3_f32x3')
-    return out
-
-
+X3_CONV3 = _switch('OPA_GEMM3_3X3', '1')
+# ... and the heads' 1x1 convolutions, whose output channels are no multiple of the kernel's 64-wide tile (OPA_GEMM3_HEAD=0: off)
+X3_HEAD = _switch('OPA_GEMM3_HEAD', '1')
+# ... and the 7x7 stride-2 stem (OPA_GEMM3_STEM=0: off)
+X3_STEM = _switch('OPA_GEMM3_STEM', '1')
+# ... and the 1x1 convolutions of the ShuffleNetV2K units and conv5, whose channel counts (k16: 24 / 174 / 348 / 696 / 1392) fit none
+# of the tiles above and whose operand is a channel slice: the kernel's UNIT mode (OPA_GEMM3_UNIT=0: off)
+X3_UNIT = _switch('OPA_GEMM3_UNIT', '1')
 # The GROUPED 3x3 convolution of a ResNeXt bottleneck (32 groups of 4 ... 64 channels) as one HIP kernel with the bias and the ReLU
 # inside (csrc/gconv.hip); OPA_GCONV=1 (or fused.GCONV = True) switches the route on.  It is never timed and makes no choice-table
 # entry: where it is supported it runs.  It stays OFF by default -- torch's grouped convolution + the epilogue pass -- until the
 # kernel has been timed against that route on every (group width, stride) class at 641 px (tools/gpu/gconv_times.py): no speed is
 # claimed for a route nobody has measured.
-GCONV = os.environ.get('OPA_GCONV', '0') != '0'
-GCONV_WIDTHS = (4, 8, 16, 32, 64)            # channels per group the kernel is instantiated for
+GCONV = _switch('OPA_GCONV', '0')
+# The MobileNetV3 blocks on the project's kernels (network._MBV3Block._forward_unit): OPA_MBV3=1 (or fused.MBV3 = True) switches the
+# route on.  It stays OFF by default -- the plain torch forward -- until both trunks have been timed against that forward at 641 px,
+# batch 32 (tools/gpu/mobilenetv3_times.py): no speed is claimed for a route nobody has measured.
+MBV3 = _switch('OPA_MBV3', '0')
 
 
-def gconv3x3_supported(conv, x, bias):
-    """Can ``gconv3x3_bias_act(conv, x, bias)`` run?  A grouped 3x3 convolution (padding 1, dilation 1, square stride 1 or 2, as many
-    output as input channels, a group width of ``GCONV_WIDTHS``, no bias of its own: the folded one arrives separately) of a dense
-    channels-last float32 tensor on the GPU, outside autocast, not followed by autograd."""
-    if not (GCONV and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and not torch.is_autocast_enabled()):
-        return False
-    if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad or (bias is not None and bias.requires_grad)):
-        return False
-    c = conv.in_channels
-    return (conv.groups > 1 and conv.kernel_size == (3, 3) and conv.padding == (1, 1) and conv.dilation == (1, 1)
-            and conv.stride in ((1, 1), (2, 2)) and c == conv.out_channels and c % conv.groups == 0
-            and c // conv.groups in GCONV_WIDTHS and conv.bias is None and conv.weight.dtype == torch.float32
-            and conv.weight.device == x.device and x.shape[1] == c and x.is_contiguous(memory_format=torch.channels_last)
-            and x.data_ptr() % 16 == 0 and 0 < x.shape[0] <= 65535                     # (grid.y of the kernel)
-            and (bias is None or (bias.dtype == torch.float32 and bias.device == x.device and bias.is_contiguous()
-                                  and bias.numel() == c and bias.data_ptr() % 16 == 0))
-            and _lib.available())
+# ---- the choice table and the decision ---------------------------------------------------------------------------------------------
 
-
-def gconv_weight_of(conv):
-    """The operand of ``opa_gconv3x3_bias_act_f32`` derived from the CURRENT ``conv.weight`` (``[C, cg, 3, 3]``): tap-major with the
-    output channel innermost, ``[9, cg, C]`` with ``wt[ky * 3 + kx][ci][co] = weight[co][ci][ky][kx]``.  Derived and cached
-    (``derived``): no buffer, no part of a state dict, computed again whenever the weight was replaced, moved or changed in place."""
-    def make():
-        w = conv.weight.detach()
-        return w.permute(2, 3, 1, 0).reshape(9, w.shape[1], w.shape[0]).contiguous()
-    return derived(conv, '_opa_gconv_wt', (conv.weight,), make)
-
-
-def gconv3x3_bias_act(conv, x, bias, relu=True):
-    """``act(conv(x) + bias)`` for a grouped 3x3 convolution (reference ``network/basenetworks.py:71-150`` with torchvision's grouped
-    Bottleneck: ResNeXt) in one HIP kernel, float32 in and out.  ``gconv3x3_supported`` says whether this can run."""
-    wt = gconv_weight_of(conv)
-    B, C, H, W = x.shape
-    s = conv.stride[0]
-    out = torch.empty((B, C, (H - 1) // s + 1, (W - 1) // s + 1), dtype=torch.float32, device=x.device,
-                      memory_format=torch.channels_last)
-    _lib.check(_lib.lib().opa_gconv3x3_bias_act_f32(
-        ctypes.c_void_p(x.data_ptr()), C, ctypes.c_void_p(wt.data_ptr()),
-        ctypes.c_void_p(bias.data_ptr()) if bias is not None else None, ctypes.c_void_p(out.data_ptr()), C,
-        B, H, W, C, C // conv.groups, s, int(bool(relu)),
-        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_gconv3x3_bias_act_f32')
-    return out
-
-
-# ... and the heads' 1x1 convolutions, whose output channels are no multiple of the kernel's 64-wide tile (OPA_GEMM3_HEAD=0: off)
-X3_HEAD = os.environ.get('OPA_GEMM3_HEAD', '1') != '0'
-
-
-def head_conv_x3_supported(conv, x):
-    return (X3_HEAD and X3_TERMS in (6, 9) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and not x.requires_grad
-            and x.is_contiguous(memory_format=torch.channels_last) and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
-            and conv.padding == (0, 0) and conv.groups == 1 and conv.in_channels % 64 == 0 and x.shape[1] == conv.in_channels
-            and conv.weight.dtype == torch.float32 and x.data_ptr() % 16 == 0)
-
-
-def _head_weight_of(conv):
-    """The operands of ``head_conv_x3`` derived from the current parameters: ``split_weight`` of the weight padded with zero rows
-    to the next multiple of 64 output channels, and the bias padded alike (zeros without one) -- kept on the module like
-    ``_split_weight_of``; the key holds the bias tensor too (a bias REPLACED by a new Parameter is a new operand)."""
-    def make():
-        w = conv.weight
-        n, k = w.shape[0], w.shape[1]
-        npad = (n + 63) // 64 * 64
-        wp = torch.zeros((npad, k), dtype=torch.float32, device=w.device)
-        wp[:n] = w.detach().reshape(n, k)
-        bp = torch.zeros(npad, dtype=torch.float32, device=w.device)
-        if conv.bias is not None:
-            bp[:n] = conv.bias.detach()
-        return split_weight(wp), bp
-    return derived(conv, '_opa_w3_head', (conv.weight, conv.bias), make)
-
-
-def head_conv_x3(conv, x):
-    """``conv(x)`` for a head's biased 1x1 convolution (reference ``network/heads.py:272-378``: ``CompositeField4.conv``) through the
-    split-operand GEMM: the output channels are padded to the next multiple of 64 with zero weights, the product is written with
-    that pitch and the real channels are copied out (0.2 GB for both COCO heads at batch 32)."""
-    n = conv.out_channels
-    w3, bp = _head_weight_of(conv)
-    out = conv1x1_bias_act_x3(x, w3, bp, None, False, None, X3_TERMS)
-    return out[:, :n].contiguous(memory_format=torch.channels_last) if w3.shape[1] != n else out
-
-
-# ... and the 7x7 stride-2 stem (OPA_GEMM3_STEM=0: off)
-X3_STEM = os.environ.get('OPA_GEMM3_STEM', '1') != '0'
-
-
-def stem_x3_supported(conv, x, bias):
-    return (X3_STEM and X3_TERMS in (6, 9) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and conv.kernel_size == (7, 7)
-            and conv.stride == (2, 2) and conv.padding == (3, 3) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
-            and conv.in_channels == 3 and x.shape[1] == 3 and conv.out_channels % 64 == 0
-            and bias.dtype == torch.float32 and bias.is_contiguous() and bias.data_ptr() % 16 == 0
-            and x.shape[0] * (x.shape[2] + 7) * (x.shape[3] + 7) * 16 < 2 ** 31)
-
-
-def _stem_weight_of(conv):
-    """The weight operand of ``stem7x7_bias_act_x3`` derived from the current ``conv.weight``: ``[N, 7, 7, 3]`` padded with zeros to
-    ``[N, 8, 8, 4]`` and split -- kept on the module like ``_split_weight_of``."""
-    def make():
-        w = conv.weight
-        n = w.shape[0]
-        wp = torch.zeros((n, 8, 8, 4), dtype=torch.float32, device=w.device)
-        wp[:, :7, :7, :3] = w.detach().permute(0, 2, 3, 1)
-        return split_weight(wp.reshape(n, 256))
-    return derived(conv, '_opa_w3_stem', (conv.weight,), make)
-
-
-def stem7x7_bias_act_x3(conv, x, bias, relu=True):
-    """``act(conv(x) + bias)`` for the 7x7 stride-2 padding-3 stem of a ResNet on RGB input (reference ``network/basenetworks.py:71-150``)
-    as an implicit GEMM of the split-operand kernel: the image is copied once into a zero-padded 4-channel NHWC tensor (3 pixels
-    before, 4 behind; ~1 % of the step), a window ROW -- 8 pixels x 4 channels = 32 contiguous floats -- is one K-step, the
-    eighth row and column and the fourth channel meet zero weights.  K = 8 x 32 = 256."""
-    w3 = _stem_weight_of(conv)
-    B, _, H, W = x.shape
-    xp = torch.nn.functional.pad(x.permute(0, 2, 3, 1), (0, 1, 3, 4, 3, 4)).contiguous()        # [B, H + 7, W + 7, 4]
-    ho, wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    out = torch.empty((B, conv.out_channels, ho, wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    _lib.check(_lib.lib().opa_conv_rows_f32x3(
-        ctypes.c_void_p(xp.data_ptr()), ctypes.c_void_p(w3.data_ptr()), ctypes.c_void_p(bias.data_ptr()),
-        ctypes.c_void_p(out.data_ptr()), B, H + 7, W + 7, 4, ho, wo, 2, 8, 32, conv.out_channels, int(bool(relu)), int(X3_TERMS),
-        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_conv_rows_f32x3')
-    return out
-
-
-# ... and the 1x1 convolutions of the ShuffleNetV2K units and conv5, whose channel counts (k16: 24 / 174 / 348 / 696 / 1392) fit none
-# of the tiles above and whose operand is a channel slice: the kernel's UNIT mode (OPA_GEMM3_UNIT=0: off)
-X3_UNIT = os.environ.get('OPA_GEMM3_UNIT', '1') != '0'
-
-
-def _unit_conv_ok(conv):
-    """The part of ``unit_conv_x3_supported`` that depends on the convolution alone."""
-    return (X3_UNIT and X3_TERMS in (6, 9) and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
-            and conv.dilation == (1, 1) and conv.groups == 1 and conv.in_channels % 2 == 0 and conv.out_channels % 2 == 0
-            and conv.weight.dtype == torch.float32
-            and (conv.bias is None or conv.bias.dtype == torch.float32))
-
-
-def unit_conv_x3_supported(conv, x, partner=None, residual=None):
-    """Can ``conv1x1_unit_x3(conv, x, partner=partner, residual=residual)`` run?  float32 on the GPU, a 1x1 convolution of stride 1
-    without padding or groups and with EVEN channel counts, ``x`` (and ``partner`` or ``residual``, never both) channels-innermost
-    tensors or channel slices of such, on 8-byte boundaries, nothing that autograd follows; the partner and the residual have the
-    output's pixels and ``conv.out_channels`` channels."""
-    if not (x.is_cuda and conv.weight.device == x.device and _unit_conv_ok(conv) and _unit_operand_ok(x, conv.in_channels)
-            and 0 < x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31):
-        return False
-    if partner is not None and residual is not None:
-        return False
-    for third in (partner, residual):
-        if third is not None and not (third.device == x.device and _unit_operand_ok(third, conv.out_channels)
-                                      and (third.shape[0], third.shape[2], third.shape[3]) == (x.shape[0], x.shape[2], x.shape[3])):
-            return False
-    return True
-
-
-def _unit_operand_ok(t, channels):
-    """Layout of an activation operand of the unit mode (``x`` or the partner), whatever its device: float32, ``channels`` channels
-    innermost with an even pitch between pixels, on an 8-byte boundary, not followed by autograd."""
-    ps = _pixel_stride(t)
-    return (t.dtype == torch.float32 and not t.requires_grad and ps is not None and t.shape[1] == channels
-            and ps % 2 == 0 and ps <= 2 ** 21 and t.data_ptr() % 8 == 0)
-
-
-def _unit_weight_of(conv):
-    """The operands of ``conv1x1_unit_x3`` derived from the current parameters: ``split_weight`` of the ``[N, K]`` weight padded with
-    zeros to ``[N_pad, K_pad]`` (multiples of 64: the kernel's tile width and two of its K-steps) and the bias padded to ``N_pad``
-    (zeros where the convolution has none) -- kept on the module like ``_split_weight_of``; the convolution keeps its parameters."""
-    def make():
-        w = conv.weight
-        n, k = w.shape[0], w.shape[1]
-        npad, kpad = (n + 63) // 64 * 64, (k + 63) // 64 * 64
-        wp = torch.zeros((npad, kpad), dtype=torch.float32, device=w.device)
-        wp[:n, :k] = w.detach().reshape(n, k)
-        bp = torch.zeros(npad, dtype=torch.float32, device=w.device)
-        if conv.bias is not None:
-            bp[:n] = conv.bias.detach()
-        return split_weight(wp), bp
-    return derived(conv, '_opa_w3_unit', (conv.weight, conv.bias), make)
-
-
-ACT_NONE, ACT_RELU, ACT_HARDSWISH = 0, 1, 2      # the activation codes of opa_dwconv_act and opa_gemm_unit_act_f32x3
-
-
-def conv1x1_unit_x3(conv, x, relu=True, partner=None, residual=None, act=None):
-    """``act(conv(x))`` for a biased 1x1 convolution of ANY even channel counts on a channels-last tensor or channel slice
-    (reference ``network/basenetworks.py:186-242``: the 1x1 convolutions of a ShuffleNetV2K unit, folded with their batch norms),
-    through the split-operand GEMM's unit mode (``opa_gemm_unit_bias_act_f32x3``).  With ``partner`` (``[B, N, H, W]``, may be a
-    slice) the result is ``channel_shuffle(cat((partner, y), 1), 2)`` -- ``[B, 2N, H, W]``, the partner's channels copied into the
-    even positions by the same kernel.  channels_last float32 out.  ``unit_conv_x3_supported`` says whether this can run.
-
-    ``act`` (``ACT_NONE`` / ``ACT_RELU`` / ``ACT_HARDSWISH``) instead of ``relu``, and ``residual`` (``[B, N, H, W]``, may be a slice,
-    never together with a partner): ``act(conv(x) + residual)`` in the same launch -- the 1x1 convolutions of a MobileNetV3 block
-    (``opa_gemm_unit_act_f32x3``).  ``act=None`` without a residual is the call above, entry point and all."""
-    w3, bp = _unit_weight_of(conv)
-    B, K, H, W = x.shape
-    n = conv.out_channels
-    out = torch.empty((B, n if partner is None else 2 * n, H, W), dtype=torch.float32, device=x.device,
-                      memory_format=torch.channels_last)
-    if act is not None or residual is not None:
-        _lib.check(_lib.lib().opa_gemm_unit_act_f32x3(
-            ctypes.c_void_p(x.data_ptr()), _pixel_stride(x), ctypes.c_void_p(w3.data_ptr()), ctypes.c_void_p(bp.data_ptr()),
-            ctypes.c_void_p(partner.data_ptr()) if partner is not None else None,
-            _pixel_stride(partner) if partner is not None else 0,
-            ctypes.c_void_p(residual.data_ptr()) if residual is not None else None,
-            _pixel_stride(residual) if residual is not None else 0, ctypes.c_void_p(out.data_ptr()),
-            B * H * W, n, K, int(bool(relu)) if act is None else int(act), int(X3_TERMS),
-            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_gemm_unit_act_f32x3')
-        return out
-    _lib.check(_lib.lib().opa_gemm_unit_bias_act_f32x3(
-        ctypes.c_void_p(x.data_ptr()), _pixel_stride(x), ctypes.c_void_p(w3.data_ptr()), ctypes.c_void_p(bp.data_ptr()),
-        ctypes.c_void_p(partner.data_ptr()) if partner is not None else None,
-        _pixel_stride(partner) if partner is not None else 0, ctypes.c_void_p(out.data_ptr()),
-        B * H * W, n, K, int(bool(relu)), int(X3_TERMS),
-        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_gemm_unit_bias_act_f32x3')
-    return out
-
-
-# (dtype, M, K, N, has_residual, has_a_bias) -> 'gemm' | 'gemm3' | 'pass+gemm' | 'conv'.  The three paths round
+# (dtype, M, K, N, has_residual, has_a_bias) -> 'gemm' | 'gemm3' | 'pass+gemm' | 'conv', and for ``pick``
+# ('torch.float32/<kind>', M, K, N, flag, flag) -> 'x3' | 'conv'.  The paths round
 # differently, so the choice is part of the result: it is made once per shape (the key holds no device index: a
 # table exported on rank 0 must match the lookups of every other rank), never by timing while a stream is being
 # captured (timing synchronises; the capture-time default is remembered, so a captured graph and a later eager
@@ -571,57 +131,224 @@ def _time_ms(fn, reps=3):
     return best
 
 
-def conv_bias_act(conv, x, bias, residual=None, relu=True, a_bias=None):
-    """``act(conv(x) + bias (+ residual))`` for a bias-free ``conv`` module: 1x1 stride-1 convolutions go
-    to the fused MFMA GEMM when it is faster than MIOpen's convolution + the fused epilogue pass
-    (decided once per shape by timing both on the first call); everything else is conv + ``bias_act_``.
+def _decide(key, default, timed, may_time=True):
+    """The choice for ``key``: the table's entry; else ``default`` where timing is not an option -- ``may_time`` is false, a stream is
+    being captured (timing synchronises), or the job has several ranks (wall clocks differ from rank to rank and the candidates
+    round differently: every rank takes the SAME default, no collective needed) -- else the fastest of ``timed()``, a callable that
+    times every candidate once and returns ``{name: ms}`` (the first listed wins a tie).  Whatever was chosen is remembered, so
+    that a captured graph and a later eager run use the same kernel."""
+    choice = _CHOICE.get(key)
+    if choice is None:
+        if not may_time or torch.cuda.is_current_stream_capturing() or _in_multi_rank_job():
+            choice = default
+        else:
+            times = timed()
+            choice = min(times, key=times.get)
+        _CHOICE[key] = choice
+    return choice
 
-    With ``a_bias``, ``x`` is the raw output of the preceding convolution whose epilogue
-    ``relu(x + a_bias[c])`` has not been applied yet: the GEMM applies it to its operand on the fly, the
-    fallback applies it in place first."""
-    w = conv.weight
-    if (conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.groups == 1 and conv.padding == (0, 0)
-            and conv1x1_supported(x, w, bias, residual, a_bias)):
-        M = x.shape[0] * x.shape[2] * x.shape[3]
-        key = (str(x.dtype), M, w.shape[1], w.shape[0], residual is not None, a_bias is not None)
-        w2d = w.reshape(w.shape[0], w.shape[1])
-        if not w2d.is_contiguous():
-            w2d = w2d.contiguous()
-        choice = _CHOICE.get(key)
-        if choice is None:
-            forced = os.environ.get('OPA_CONV1X1', 'auto')
-            if forced in ('gemm', 'conv'):
-                choice = _CHOICE[key] = forced
-            elif torch.cuda.is_current_stream_capturing():
-                choice = _CHOICE[key] = 'gemm'   # no timing inside a capture; remembered, so eager runs agree with the graph
-            elif _in_multi_rank_job():
-                # a shape the shipped table does not know, in a job of several ranks: every rank takes the SAME default instead of
-                # timing (wall clocks differ from rank to rank, and the three paths round differently) -- no collective needed
-                choice = _CHOICE[key] = 'gemm'
-        if choice is None:
-            times = {'gemm': _time_ms(lambda: conv1x1_bias_act(x, w2d, bias, residual, relu, a_bias))}
-            if _x3_supported(x, w):
-                w3 = _split_weight_of(conv, w2d)
-                times['gemm3'] = _time_ms(lambda: conv1x1_bias_act_x3(x, w3, bias, residual, relu, a_bias, X3_TERMS))
-            if a_bias is None:
-                times['conv'] = _time_ms(lambda: bias_act_(conv(x), bias, residual, relu))
-            else:       # timing only: the separate epilogue pass runs on a scratch copy
-                scratch = x.clone()
-                times['pass+gemm'] = _time_ms(
-                    lambda: conv1x1_bias_act(bias_act_(scratch, a_bias), w2d, bias, residual, relu))
-                times['conv'] = _time_ms(lambda: bias_act_(conv(bias_act_(scratch, a_bias)), bias, residual, relu))
-            choice = _CHOICE[key] = min(times, key=times.get)
-        if choice == 'gemm3' and not _x3_supported(x, w):
-            choice = 'gemm'                  # (switched off after the table was made: the float32 MFMA kernel)
-        if choice == 'gemm3':
-            return conv1x1_bias_act_x3(x, _split_weight_of(conv, w2d), bias, residual, relu, a_bias, X3_TERMS)
-        if choice == 'gemm':
-            return conv1x1_bias_act(x, w2d, bias, residual, relu, a_bias)
-        if choice == 'pass+gemm':     # the prologue's VALU work is repeated per N-tile: cheaper as its own pass here
-            return conv1x1_bias_act(bias_act_(x, a_bias), w2d, bias, residual, relu)
-    if a_bias is not None:
-        x = bias_act_(x, a_bias)
-    return bias_act_(conv(x), bias, residual, relu)
+
+def pick(kind, m, k, n, flag_a, flag_b, run_x3, run_other, written=None, timing=True):
+    """One of two ways to compute the same tensor -- a split-operand kernel (``run_x3``) or what the trunk did before
+    (``run_other``: MIOpen's convolution + the fused passes) -- chosen ONCE per shape like ``conv_bias_act`` chooses its GEMM: from
+    the shipped table (``conv1x1_pinned.json``, key dtype ``'torch.float32/<kind>'``), else by timing both on the first call; while
+    a stream is being captured or in a job of several ranks, where timing is not an option, by size (the split-operand kernels win
+    from ~16 000 output pixels: a batch of one 641-px image keeps MIOpen in layers 3-4).  Returns the chosen function's result.
+    ``written``: an operand that ``run_other`` changes in place (the epilogue its producer left to this consumer); timing calls
+    ``run_other`` several times, so the operand is saved before and put back after -- the winner computes from what the caller
+    passed, whoever wins.  ``timing=False``: a shape the table does not know is decided by size ALWAYS -- eager or capturing, one
+    rank or many -- and nothing is timed (measurements go into the table: ``tools/gpu/dump_conv_choices.py``)."""
+    if FORCE_PICK in ('x3', 'conv'):
+        return run_x3() if FORCE_PICK == 'x3' else run_other()
+
+    def timed():
+        saved = written.clone() if written is not None else None
+        times = {'x3': _time_ms(run_x3), 'conv': _time_ms(run_other)}
+        if saved is not None:
+            written.copy_(saved)
+        return times
+    key = ('torch.float32/' + kind, int(m), int(k), int(n), bool(flag_a), bool(flag_b))
+    choice = _decide(key, 'x3' if m >= 16384 else 'conv', timed, may_time=timing)
+    return run_x3() if choice == 'x3' else run_other()
+
+
+# ---- layouts and sizes --------------------------------------------------------------------------------------------------------------
+
+def _nhwc_rows(x):
+    """(rows, channels) if ``x`` is physically [rows, channels]-contiguous, else None."""
+    if x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last):
+        return x.shape[0] * x.shape[2] * x.shape[3], x.shape[1]
+    if x.dim() == 2 and x.is_contiguous():
+        return x.shape[0], x.shape[1]
+    return None
+
+
+def _pixel_stride(x):
+    """Elements between neighbouring pixels of a channels-innermost (NHWC in memory) 4-d tensor or channel slice of
+    one; None if ``x`` is laid out differently."""
+    if x.dim() != 4 or x.stride(1) != 1:
+        return None
+    B, C, H, W = x.shape
+    ps = x.stride(3) if W > 1 else (x.stride(2) if H > 1 else C)
+    if ps < C or (H > 1 and x.stride(2) != W * ps) or (B > 1 and x.stride(0) != H * W * ps):
+        return None
+    return ps
+
+
+def _out_hw(x, stride=1):
+    return (x.shape[2] - 1) // stride + 1, (x.shape[3] - 1) // stride + 1
+
+
+def out_pixels(x, stride=1):
+    """Pixels of the whole batch behind a convolution of ``x`` with "same" padding and this stride: the M of the choice table's keys."""
+    ho, wo = _out_hw(x, stride)
+    return x.shape[0] * ho * wo
+
+
+def _empty_nhwc(x, channels, hw=None, dtype=None):
+    """An uninitialised channels-last ``[B, channels, *hw]`` on ``x``'s device (``hw``: ``x``'s own where not given)."""
+    h, w = hw or x.shape[2:]
+    return torch.empty((x.shape[0], channels, h, w), dtype=dtype or x.dtype, device=x.device, memory_format=torch.channels_last)
+
+
+# ---- derived operands -----------------------------------------------------------------------------------------------------------------
+
+def derived(module, name, sources, make):
+    """``make()`` -- an operand derived from the tensors ``sources`` (parameters, buffers; None where there is none) -- computed
+    once, kept on ``module`` as attribute ``name`` and computed again whenever a source was replaced, moved, converted or changed
+    in place (``load_state_dict``, ``.to()``, an optimizer step): the key is (data pointer, version counter, device, dtype) of each.
+    The entry holds on to the sources' storages, so that no later tensor can be handed the same address while it is the key."""
+    key = tuple(None if t is None else (t.data_ptr(), t._version, str(t.device), t.dtype) for t in sources)
+    cached = getattr(module, name, None)
+    if cached is None or cached[0] != key:
+        cached = (key, make(), [t.untyped_storage() for t in sources if t is not None])
+        setattr(module, name, cached)
+    return cached[1]
+
+
+def split_weight(weight2d):
+    """``[N, K]`` float32 -> ``[3, N, K]`` bfloat16: the three pieces of every weight (its 24-bit significand cut into 8 + 8 + 8
+    bits: ``w1`` = ``w`` with the low 16 bits cleared, ``r = w - w1``, ``w2`` = ``r`` with the low 16 bits cleared, ``w3 = r - w2``;
+    every step is exact and ``w1 + w2 + w3 == w`` bit for bit) -- the operand of ``opa_gemm_bias_act_f32x3`` (``csrc/gemm_f32x3.hip``)."""
+    w = weight2d.detach().to(torch.float32).contiguous()
+
+    def top(x):
+        return (x.view(torch.int32) & -65536).view(torch.float32)
+    w1 = top(w)
+    r1 = w - w1
+    w2 = top(r1)
+    w3 = r1 - w2
+    out = torch.stack((w1, w2, w3)).to(torch.bfloat16)          # (exact: each piece has at most 8 significant bits)
+    return out.contiguous()
+
+
+def split_weight_3x3(weight):
+    """``[N, C, 3, 3]`` float32 -> ``split_weight`` of ``[N, (ky, kx, c)]``: the operand of ``opa_conv3x3_f32x3``."""
+    n, c = weight.shape[0], weight.shape[1]
+    return split_weight(weight.detach().permute(0, 2, 3, 1).reshape(n, 9 * c))
+
+
+def _split_weight_of(conv, w2d):
+    """``split_weight(w2d)`` for ``w2d``, the ``[N, K]`` view of ``conv.weight``: computed once per convolution and kept on the module
+    (inference: the weight does not change; a weight replaced, moved or changed since is split again)."""
+    return derived(conv, '_opa_w3', (conv.weight,), lambda: split_weight(w2d))
+
+
+def _split_weight_3x3_of(conv):
+    """``split_weight_3x3(conv.weight)``, kept on the module like ``_split_weight_of``."""
+    return derived(conv, '_opa_w3_3x3', (conv.weight,), lambda: split_weight_3x3(conv.weight))
+
+
+def _pair_weight_of(conv, dconv, a_bias=None):
+    """The operands of ``conv1x1_pair_bias_act_x3`` derived from the current parameters: ``split_weight([W | Wd])`` and ``a_bias``
+    followed by zeros for ``dconv``'s channels (None without ``a_bias``) -- kept on ``conv`` like ``_split_weight_of``."""
+    k1, k2, n = conv.in_channels, dconv.in_channels, conv.out_channels
+
+    def make():
+        w1, w2 = conv.weight.detach().reshape(n, k1), dconv.weight.detach().reshape(n, k2)
+        ab = None if a_bias is None else torch.cat((a_bias.detach().float(), torch.zeros(k2, device=a_bias.device)))
+        return split_weight(torch.cat((w1, w2), dim=1)), ab
+    return derived(conv, '_opa_w3_pair', (conv.weight, dconv.weight, a_bias), make)
+
+
+def _stem_weight_of(conv):
+    """The weight operand of ``stem7x7_bias_act_x3`` derived from the current ``conv.weight``: ``[N, 7, 7, 3]`` padded with zeros to
+    ``[N, 8, 8, 4]`` and split -- kept on the module like ``_split_weight_of``."""
+    def make():
+        w = conv.weight
+        n = w.shape[0]
+        wp = torch.zeros((n, 8, 8, 4), dtype=torch.float32, device=w.device)
+        wp[:, :7, :7, :3] = w.detach().permute(0, 2, 3, 1)
+        return split_weight(wp.reshape(n, 256))
+    return derived(conv, '_opa_w3_stem', (conv.weight,), make)
+
+
+def _unit_weight_of(conv):
+    """The operands of ``conv1x1_unit_x3`` and ``head_conv_x3`` derived from the current parameters: ``split_weight`` of the
+    ``[N, K]`` weight padded with zeros to ``[N_pad, K_pad]`` (multiples of 64: the kernel's tile width and two of its K-steps) and
+    the bias padded to ``N_pad`` (zeros where the convolution has none) -- kept on the module like ``_split_weight_of``; the
+    convolution keeps its parameters, and the key holds the bias tensor too (a bias REPLACED by a new Parameter is a new operand)."""
+    def make():
+        w = conv.weight
+        n, k = w.shape[0], w.shape[1]
+        npad, kpad = (n + 63) // 64 * 64, (k + 63) // 64 * 64
+        wp = torch.zeros((npad, kpad), dtype=torch.float32, device=w.device)
+        wp[:n, :k] = w.detach().reshape(n, k)
+        bp = torch.zeros(npad, dtype=torch.float32, device=w.device)
+        if conv.bias is not None:
+            bp[:n] = conv.bias.detach()
+        return split_weight(wp), bp
+    return derived(conv, '_opa_w3_unit', (conv.weight, conv.bias), make)
+
+
+def gconv_weight_of(conv):
+    """The operand of ``opa_gconv3x3_bias_act_f32`` derived from the CURRENT ``conv.weight`` (``[C, cg, 3, 3]``): tap-major with the
+    output channel innermost, ``[9, cg, C]`` with ``wt[ky * 3 + kx][ci][co] = weight[co][ci][ky][kx]``.  Derived and cached
+    (``derived``): no buffer, no part of a state dict, computed again whenever the weight was replaced, moved or changed in place."""
+    def make():
+        w = conv.weight.detach()
+        return w.permute(2, 3, 1, 0).reshape(9, w.shape[1], w.shape[0]).contiguous()
+    return derived(conv, '_opa_gconv_wt', (conv.weight,), make)
+
+
+def depthwise_taps(weight):
+    """``[C, 1, k, k]`` -> ``[k * k, C]``, tap-major: the weight operand of ``dwconv_bias_act``."""
+    return weight.detach().reshape(weight.shape[0], -1).t().contiguous()
+
+
+# ---- the epilogue passes --------------------------------------------------------------------------------------------------------------
+
+def bias_act_(x, bias, residual=None, relu=True):
+    """In place ``x = act(x + bias[c] (+ residual))`` for a channels_last activation.
+
+    One HIP kernel on the GPU; the equivalent PyTorch ops elsewhere (CPU tests, odd layouts)."""
+    rc = _nhwc_rows(x) if x.is_cuda else None
+    per_vec = 4 if x.dtype == torch.float32 else 8
+    ok = (rc is not None and x.dtype in _DTYPES and rc[1] % per_vec == 0 and bias.dtype == x.dtype
+          and bias.is_contiguous() and x.data_ptr() % 16 == 0 and bias.data_ptr() % 16 == 0
+          and (residual is None or (residual.dtype == x.dtype and residual.shape == x.shape
+                                    and _nhwc_rows(residual) is not None and residual.data_ptr() % 16 == 0)))
+    if not ok:
+        x.add_(bias.view(1, -1, 1, 1) if x.dim() == 4 else bias)
+        if residual is not None:
+            x.add_(residual)
+        return torch.relu_(x) if relu else x
+    _launch('opa_bias_act', _ptr(x), _ptr(bias), _ptr(residual), rc[0], rc[1], _DTYPES[x.dtype], int(bool(relu)))
+    return x
+
+
+def channel_interleave(a, b):
+    """``channel_shuffle(torch.cat((a, b), 1), groups=2)`` in one pass: out[:, 2i] = a[:, i], out[:, 2i+1] = b[:, i]."""
+    pa, pb = _pixel_stride(a), _pixel_stride(b)
+    if not (a.is_cuda and a.dtype in _DTYPES and a.dtype == b.dtype and a.shape == b.shape and pa and pb
+            and _lib.available()):
+        x = torch.cat((a, b), dim=1)
+        n, c, h, w = x.shape
+        return x.view(n, 2, c // 2, h, w).transpose(1, 2).reshape(n, c, h, w)
+    B, half, H, W = a.shape
+    out = _empty_nhwc(a, 2 * half)
+    _launch('opa_channel_interleave', _ptr(a), pa, _ptr(b), pb, _ptr(out), B * H * W, half, _DTYPES[a.dtype])
+    return out
 
 
 def head_epilogue_supported(x, meta, training=False):
@@ -647,23 +374,303 @@ def head_epilogue(x, meta):
     H, W = hc * us - low_cut - high_cut, wc * us - low_cut - high_cut
     out = torch.empty((B, n_fields, n_comp, H, W), dtype=torch.float32, device=x.device)
     mask = sum(1 << i for i, on in enumerate(meta.vector_offsets) if on)
-    _lib.check(_lib.lib().opa_head_epilogue(
-        ctypes.c_void_p(x.data_ptr()), _DTYPES[x.dtype], B, hc, wc, n_fields, n_comp, us, meta.n_confidences,
-        meta.n_vectors, mask, meta.n_scales, ctypes.c_void_p(out.data_ptr()),
-        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_head_epilogue')
+    _launch('opa_head_epilogue', _ptr(x), _DTYPES[x.dtype], B, hc, wc, n_fields, n_comp, us, meta.n_confidences,
+            meta.n_vectors, mask, meta.n_scales, _ptr(out))
     return out
 
 
-def _pixel_stride(x):
-    """Elements between neighbouring pixels of a channels-innermost (NHWC in memory) 4-d tensor or channel slice of
-    one; None if ``x`` is laid out differently."""
-    if x.dim() != 4 or x.stride(1) != 1:
-        return None
+# ---- the 1x1 GEMMs --------------------------------------------------------------------------------------------------------------------
+
+def conv1x1_supported(x, weight, bias=None, residual=None, a_bias=None):
+    """True if ``conv1x1_bias_act`` can run the HIP GEMM for these operands.  The kernels read raw buffers:
+    EVERY operand must have the activation's dtype, bfloat16 or float32 (autocast keeps parameters in float32
+    next to bfloat16 activations -- those take the PyTorch path), the activation channels_last, the residual
+    channels_last of the output's shape."""
+    dt = x.dtype
+    if not (x.is_cuda and dt in (torch.bfloat16, torch.float32) and x.dim() == 4
+            and x.is_contiguous(memory_format=torch.channels_last)
+            and weight.dtype == dt and weight.is_cuda
+            and weight.shape[1] % (64 if dt == torch.bfloat16 else 32) == 0 and weight.shape[0] % 64 == 0
+            and weight.shape[1] == x.shape[1]):
+        return False
+    for vec, n in ((bias, weight.shape[0]), (a_bias, weight.shape[1])):
+        if vec is not None and not (vec.dtype == dt and vec.is_cuda and vec.is_contiguous()
+                                    and vec.numel() == n and vec.data_ptr() % 16 == 0):
+            return False
+    if residual is not None:
+        if not (residual.dtype == dt and residual.is_cuda
+                and tuple(residual.shape) == (x.shape[0], weight.shape[0], x.shape[2], x.shape[3])
+                and residual.is_contiguous(memory_format=torch.channels_last) and residual.data_ptr() % 16 == 0):
+            return False
+    return x.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0
+
+
+def conv1x1_bias_act(x, weight2d, bias, residual=None, relu=True, a_bias=None):
+    """``act(conv1x1(x, weight) + bias (+ residual))`` as ONE MFMA GEMM kernel with fused epilogue.
+
+    :param x: ``[B, C_in, H, W]`` bfloat16 or float32, channels_last
+    :param weight2d: ``[C_out, C_in]`` of the same dtype, contiguous
+    :param a_bias: ``[C_in]``: ``x`` is the RAW output of the preceding convolution and
+        ``relu(x + a_bias)`` -- that convolution's epilogue -- is applied while the operand is staged
+    :returns: ``[B, C_out, H, W]`` of that dtype, channels_last
+    """
+    N, K = weight2d.shape[0], x.shape[1]
+    out = _empty_nhwc(x, N)
+    rest = (_ptr(weight2d), _ptr(bias), _ptr(residual), _ptr(out), out_pixels(x), N, K, int(bool(relu)))
+    if x.dtype == torch.float32:
+        _launch('opa_gemm_bias_act_f32', _ptr(x), _ptr(a_bias), *rest)
+    elif a_bias is not None:
+        _launch('opa_gemm_pro_bias_act_bf16', _ptr(x), _ptr(a_bias), *rest)
+    else:
+        _launch('opa_gemm_bias_act_bf16', _ptr(x), *rest)
+    return out
+
+
+def conv1x1_bias_act_x3(x, w3, bias, residual=None, relu=True, a_bias=None, terms=9):
+    """``conv1x1_bias_act`` for float32 through the split-operand kernel: ``w3`` = ``split_weight(weight2d)``; ``terms`` 9 or 6."""
+    N, K = w3.shape[1], x.shape[1]
+    out = _empty_nhwc(x, N)
+    _launch('opa_gemm_bias_act_f32x3', _ptr(x), _ptr(a_bias), _ptr(w3), _ptr(bias), _ptr(residual), _ptr(out),
+            out_pixels(x), N, K, int(bool(relu)), int(terms))
+    return out
+
+
+def _x3_supported(x, weight):
+    return X3_TERMS in (6, 9) and x.dtype == torch.float32 and weight.shape[1] % 64 == 0
+
+
+def conv_bias_act(conv, x, bias, residual=None, relu=True, a_bias=None):
+    """``act(conv(x) + bias (+ residual))`` for a bias-free ``conv`` module: 1x1 stride-1 convolutions go
+    to the fused MFMA GEMM when it is faster than MIOpen's convolution + the fused epilogue pass
+    (decided once per shape by timing both on the first call); everything else is conv + ``bias_act_``.
+
+    With ``a_bias``, ``x`` is the raw output of the preceding convolution whose epilogue
+    ``relu(x + a_bias[c])`` has not been applied yet: the GEMM applies it to its operand on the fly, the
+    fallback applies it in place first."""
+    w = conv.weight
+    if (conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.groups == 1 and conv.padding == (0, 0)
+            and conv1x1_supported(x, w, bias, residual, a_bias)):
+        key = (str(x.dtype), out_pixels(x), w.shape[1], w.shape[0], residual is not None, a_bias is not None)
+        w2d = w.reshape(w.shape[0], w.shape[1])
+        if not w2d.is_contiguous():
+            w2d = w2d.contiguous()
+
+        def timed():
+            times = {'gemm': _time_ms(lambda: conv1x1_bias_act(x, w2d, bias, residual, relu, a_bias))}
+            if _x3_supported(x, w):
+                w3 = _split_weight_of(conv, w2d)
+                times['gemm3'] = _time_ms(lambda: conv1x1_bias_act_x3(x, w3, bias, residual, relu, a_bias, X3_TERMS))
+            if a_bias is None:
+                times['conv'] = _time_ms(lambda: bias_act_(conv(x), bias, residual, relu))
+            else:       # timing only: the separate epilogue pass runs on a scratch copy
+                scratch = x.clone()
+                times['pass+gemm'] = _time_ms(
+                    lambda: conv1x1_bias_act(bias_act_(scratch, a_bias), w2d, bias, residual, relu))
+                times['conv'] = _time_ms(lambda: bias_act_(conv(bias_act_(scratch, a_bias)), bias, residual, relu))
+            return times
+        # OPA_CONV1X1=gemm|conv (read at the call) pins a shape the table does not know; the default where nothing may be timed: 'gemm'
+        forced = os.environ.get('OPA_CONV1X1', 'auto')
+        pinned = forced in ('gemm', 'conv')
+        choice = _decide(key, forced if pinned else 'gemm', timed, may_time=not pinned)
+        if choice == 'gemm3' and not _x3_supported(x, w):
+            choice = 'gemm'                  # (switched off after the table was made: the float32 MFMA kernel)
+        if choice == 'gemm3':
+            return conv1x1_bias_act_x3(x, _split_weight_of(conv, w2d), bias, residual, relu, a_bias, X3_TERMS)
+        if choice == 'gemm':
+            return conv1x1_bias_act(x, w2d, bias, residual, relu, a_bias)
+        if choice == 'pass+gemm':     # the prologue's VALU work is repeated per N-tile: cheaper as its own pass here
+            return conv1x1_bias_act(bias_act_(x, a_bias), w2d, bias, residual, relu)
+    if a_bias is not None:
+        x = bias_act_(x, a_bias)
+    return bias_act_(conv(x), bias, residual, relu)
+
+
+# ---- the split-operand convolutions: pair, strided 3x3, stem, heads, unit mode ----------------------------------------------------------
+
+def pair_supported(conv, dconv, h, x, bias, a_bias=None):
+    """Can ``conv(h) + dconv(x)`` run as ONE split-operand product (``conv1x1_pair_bias_act_x3``)?  float32, channels_last,
+    both 1x1 without bias / groups / padding, ``conv`` of stride 1, ``dconv`` of any stride."""
+    k1, k2 = conv.in_channels, dconv.in_channels
+    ok = (X3_PAIR and X3_TERMS in (6, 9) and h.is_cuda and h.dtype == torch.float32 and x.dtype == torch.float32
+          and conv.kernel_size == (1, 1) and dconv.kernel_size == (1, 1) and conv.stride == (1, 1) and dconv.stride[0] == dconv.stride[1]
+          and conv.groups == 1 and dconv.groups == 1 and conv.padding == (0, 0) and dconv.padding == (0, 0)
+          and conv.bias is None and dconv.bias is None and conv.out_channels == dconv.out_channels
+          and k1 % 32 == 0 and (k1 + k2) % 64 == 0 and k2 % 4 == 0 and conv.out_channels % 64 == 0
+          and h.dim() == 4 and x.dim() == 4 and h.is_contiguous(memory_format=torch.channels_last)
+          and x.is_contiguous(memory_format=torch.channels_last) and h.shape[1] == k1 and x.shape[1] == k2
+          and h.shape[0] == x.shape[0] and h.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0
+          and bias.dtype == torch.float32 and bias.is_contiguous() and bias.data_ptr() % 16 == 0
+          and x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31)
+    if not ok:
+        return False
+    if (h.shape[2], h.shape[3]) != _out_hw(x, dconv.stride[0]):
+        return False
+    return a_bias is None or (a_bias.dtype == torch.float32 and a_bias.numel() == k1 and a_bias.is_contiguous())
+
+
+def conv1x1_pair_bias_act_x3(conv, dconv, h, x, bias, relu=True, a_bias=None):
+    """``act(conv(h) + dconv(x) + bias)`` -- the last 1x1 convolution of a ResNet block and the block's downsampling convolution
+    (reference ``network/basenetworks.py:71-150``: torchvision's Bottleneck) -- as ONE product ``[h | x at stride] * [W ; Wd]^T`` of
+    the split-operand kernel (``opa_gemm2_bias_act_f32x3``): the identity tensor is neither written nor read back.  With
+    ``a_bias``, ``h`` is the raw output of the preceding convolution and ``relu(h + a_bias)`` is applied while it is staged (``x``
+    gets zeros: it is non-negative).  ``pair_supported`` says whether this can run."""
+    k1, k2, n = conv.in_channels, dconv.in_channels, conv.out_channels
+    w3, ab = _pair_weight_of(conv, dconv, a_bias)
+    B, _, H, W = x.shape
+    out = _empty_nhwc(h, n, dtype=torch.float32)
+    _launch('opa_gemm2_bias_act_f32x3', _ptr(h), k1, _ptr(x), k2, B, H, W, dconv.stride[0], _ptr(ab), _ptr(w3), _ptr(bias),
+            _ptr(out), n, int(bool(relu)), int(X3_TERMS))
+    return out
+
+
+def conv3x3_x3_supported(conv, x, bias):
+    return (X3_CONV3 and X3_TERMS in (6, 9) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and x.is_contiguous(memory_format=torch.channels_last) and conv.kernel_size == (3, 3) and conv.padding == (1, 1)
+            and conv.stride[0] == conv.stride[1] and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
+            and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0 and x.shape[1] == conv.in_channels
+            and x.data_ptr() % 16 == 0 and bias.dtype == torch.float32 and bias.is_contiguous() and bias.data_ptr() % 16 == 0
+            and (x.shape[0] * x.shape[2] * x.shape[3] + x.shape[3] + 1) * x.shape[1] * 4 < 2 ** 31)
+
+
+def conv3x3_bias_act_x3(conv, x, bias, relu=True):
+    """``act(conv(x) + bias)`` for a 3x3 convolution with padding 1 and any stride (reference ``network/basenetworks.py:71-150``: the
+    strided convolution of a ResNet block) as an implicit GEMM of the split-operand kernel -- float32 in and out."""
+    w3 = _split_weight_3x3_of(conv)
     B, C, H, W = x.shape
-    ps = x.stride(3) if W > 1 else (x.stride(2) if H > 1 else C)
-    if ps < C or (H > 1 and x.stride(2) != W * ps) or (B > 1 and x.stride(0) != H * W * ps):
-        return None
-    return ps
+    s = conv.stride[0]
+    out = _empty_nhwc(x, conv.out_channels, _out_hw(x, s), torch.float32)
+    _launch('opa_conv3x3_f32x3', _ptr(x), _ptr(w3), _ptr(bias), _ptr(out), B, H, W, C, conv.out_channels, s,
+            int(bool(relu)), int(X3_TERMS))
+    return out
+
+
+def stem_x3_supported(conv, x, bias):
+    return (X3_STEM and X3_TERMS in (6, 9) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and conv.kernel_size == (7, 7)
+            and conv.stride == (2, 2) and conv.padding == (3, 3) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
+            and conv.in_channels == 3 and x.shape[1] == 3 and conv.out_channels % 64 == 0
+            and bias.dtype == torch.float32 and bias.is_contiguous() and bias.data_ptr() % 16 == 0
+            and x.shape[0] * (x.shape[2] + 7) * (x.shape[3] + 7) * 16 < 2 ** 31)
+
+
+def stem7x7_bias_act_x3(conv, x, bias, relu=True):
+    """``act(conv(x) + bias)`` for the 7x7 stride-2 padding-3 stem of a ResNet on RGB input (reference ``network/basenetworks.py:71-150``)
+    as an implicit GEMM of the split-operand kernel: the image is copied once into a zero-padded 4-channel NHWC tensor (3 pixels
+    before, 4 behind; ~1 % of the step), a window ROW -- 8 pixels x 4 channels = 32 contiguous floats -- is one K-step, the
+    eighth row and column and the fourth channel meet zero weights.  K = 8 x 32 = 256."""
+    w3 = _stem_weight_of(conv)
+    B, _, H, W = x.shape
+    xp = torch.nn.functional.pad(x.permute(0, 2, 3, 1), (0, 1, 3, 4, 3, 4)).contiguous()        # [B, H + 7, W + 7, 4]
+    ho, wo = _out_hw(x, 2)
+    out = _empty_nhwc(x, conv.out_channels, (ho, wo), torch.float32)
+    _launch('opa_conv_rows_f32x3', _ptr(xp), _ptr(w3), _ptr(bias), _ptr(out), B, H + 7, W + 7, 4, ho, wo, 2, 8, 32,
+            conv.out_channels, int(bool(relu)), int(X3_TERMS))
+    return out
+
+
+def head_conv_x3_supported(conv, x):
+    return (X3_HEAD and X3_TERMS in (6, 9) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and not x.requires_grad
+            and x.is_contiguous(memory_format=torch.channels_last) and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
+            and conv.padding == (0, 0) and conv.groups == 1 and conv.in_channels % 64 == 0 and x.shape[1] == conv.in_channels
+            and conv.weight.dtype == torch.float32 and x.data_ptr() % 16 == 0)
+
+
+def head_conv_x3(conv, x):
+    """``conv(x)`` for a head's biased 1x1 convolution (reference ``network/heads.py:272-378``: ``CompositeField4.conv``) through the
+    split-operand GEMM: the output channels are padded to the next multiple of 64 with zero weights (``_unit_weight_of``: the input
+    channels are a multiple of 64 here and get no padding), the product is written with that pitch and the real channels are
+    copied out (0.2 GB for both COCO heads at batch 32)."""
+    n = conv.out_channels
+    w3, bp = _unit_weight_of(conv)
+    out = conv1x1_bias_act_x3(x, w3, bp, None, False, None, X3_TERMS)
+    return out[:, :n].contiguous(memory_format=torch.channels_last) if w3.shape[1] != n else out
+
+
+def _unit_conv_ok(conv):
+    """The part of ``unit_conv_x3_supported`` that depends on the convolution alone."""
+    return (X3_UNIT and X3_TERMS in (6, 9) and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.in_channels % 2 == 0 and conv.out_channels % 2 == 0
+            and conv.weight.dtype == torch.float32
+            and (conv.bias is None or conv.bias.dtype == torch.float32))
+
+
+def _unit_operand_ok(t, channels):
+    """Layout of an activation operand of the unit mode (``x`` or the partner), whatever its device: float32, ``channels`` channels
+    innermost with an even pitch between pixels, on an 8-byte boundary, not followed by autograd."""
+    ps = _pixel_stride(t)
+    return (t.dtype == torch.float32 and not t.requires_grad and ps is not None and t.shape[1] == channels
+            and ps % 2 == 0 and ps <= 2 ** 21 and t.data_ptr() % 8 == 0)
+
+
+def unit_conv_x3_supported(conv, x, partner=None, residual=None):
+    """Can ``conv1x1_unit_x3(conv, x, partner=partner, residual=residual)`` run?  float32 on the GPU, a 1x1 convolution of stride 1
+    without padding or groups and with EVEN channel counts, ``x`` (and ``partner`` or ``residual``, never both) channels-innermost
+    tensors or channel slices of such, on 8-byte boundaries, nothing that autograd follows; the partner and the residual have the
+    output's pixels and ``conv.out_channels`` channels."""
+    if not (x.is_cuda and conv.weight.device == x.device and _unit_conv_ok(conv) and _unit_operand_ok(x, conv.in_channels)
+            and 0 < x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31):
+        return False
+    if partner is not None and residual is not None:
+        return False
+    for third in (partner, residual):
+        if third is not None and not (third.device == x.device and _unit_operand_ok(third, conv.out_channels)
+                                      and (third.shape[0], third.shape[2], third.shape[3]) == (x.shape[0], x.shape[2], x.shape[3])):
+            return False
+    return True
+
+
+def conv1x1_unit_x3(conv, x, relu=True, partner=None, residual=None, act=None):
+    """``act(conv(x))`` for a biased 1x1 convolution of ANY even channel counts on a channels-last tensor or channel slice
+    (reference ``network/basenetworks.py:186-242``: the 1x1 convolutions of a ShuffleNetV2K unit, folded with their batch norms),
+    through the split-operand GEMM's unit mode (``opa_gemm_unit_act_f32x3``).  With ``partner`` (``[B, N, H, W]``, may be a
+    slice) the result is ``channel_shuffle(cat((partner, y), 1), 2)`` -- ``[B, 2N, H, W]``, the partner's channels copied into the
+    even positions by the same kernel.  channels_last float32 out.  ``unit_conv_x3_supported`` says whether this can run.
+
+    ``act`` (``ACT_NONE`` / ``ACT_RELU`` / ``ACT_HARDSWISH``) instead of ``relu``, and ``residual`` (``[B, N, H, W]``, may be a slice,
+    never together with a partner): ``act(conv(x) + residual)`` in the same launch -- the 1x1 convolutions of a MobileNetV3 block."""
+    w3, bp = _unit_weight_of(conv)
+    n = conv.out_channels
+    out = _empty_nhwc(x, n if partner is None else 2 * n, dtype=torch.float32)
+    _launch('opa_gemm_unit_act_f32x3', _ptr(x), _pixel_stride(x), _ptr(w3), _ptr(bp),
+            _ptr(partner), _pixel_stride(partner) if partner is not None else 0,
+            _ptr(residual), _pixel_stride(residual) if residual is not None else 0,
+            _ptr(out), out_pixels(x), n, x.shape[1], _act_code(relu, act), int(X3_TERMS))
+    return out
+
+
+# ---- the grouped and the depthwise stencils ---------------------------------------------------------------------------------------------
+
+GCONV_WIDTHS = (4, 8, 16, 32, 64)            # channels per group the kernel is instantiated for
+
+
+def gconv3x3_supported(conv, x, bias):
+    """Can ``gconv3x3_bias_act(conv, x, bias)`` run?  A grouped 3x3 convolution (padding 1, dilation 1, square stride 1 or 2, as many
+    output as input channels, a group width of ``GCONV_WIDTHS``, no bias of its own: the folded one arrives separately) of a dense
+    channels-last float32 tensor on the GPU, outside autocast, not followed by autograd."""
+    if not (GCONV and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and not torch.is_autocast_enabled()):
+        return False
+    if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad or (bias is not None and bias.requires_grad)):
+        return False
+    c = conv.in_channels
+    return (conv.groups > 1 and conv.kernel_size == (3, 3) and conv.padding == (1, 1) and conv.dilation == (1, 1)
+            and conv.stride in ((1, 1), (2, 2)) and c == conv.out_channels and c % conv.groups == 0
+            and c // conv.groups in GCONV_WIDTHS and conv.bias is None and conv.weight.dtype == torch.float32
+            and conv.weight.device == x.device and x.shape[1] == c and x.is_contiguous(memory_format=torch.channels_last)
+            and x.data_ptr() % 16 == 0 and 0 < x.shape[0] <= 65535                     # (grid.y of the kernel)
+            and (bias is None or (bias.dtype == torch.float32 and bias.device == x.device and bias.is_contiguous()
+                                  and bias.numel() == c and bias.data_ptr() % 16 == 0))
+            and _lib.available())
+
+
+def gconv3x3_bias_act(conv, x, bias, relu=True):
+    """``act(conv(x) + bias)`` for a grouped 3x3 convolution (reference ``network/basenetworks.py:71-150`` with torchvision's grouped
+    Bottleneck: ResNeXt) in one HIP kernel, float32 in and out.  ``gconv3x3_supported`` says whether this can run."""
+    wt = gconv_weight_of(conv)
+    B, C, H, W = x.shape
+    s = conv.stride[0]
+    out = _empty_nhwc(x, C, _out_hw(x, s), torch.float32)
+    _launch('opa_gconv3x3_bias_act_f32', _ptr(x), C, _ptr(wt), _ptr(bias), _ptr(out), C, B, H, W, C, C // conv.groups, s,
+            int(bool(relu)))
+    return out
 
 
 def dwconv_supported(x, kernel_size, stride):
@@ -676,33 +683,19 @@ def dwconv_supported(x, kernel_size, stride):
 
 
 def dwconv_bias_act(x, w_taps, bias, kernel_size, stride, relu=False, act=None):
-    """Depthwise ``kernel_size`` x ``kernel_size`` convolution (padding k//2) + bias (+ ReLU) of a channels-last
-    activation or channel slice, one HIP stencil kernel.  ``w_taps``: ``[k*k, C]`` (tap-major) in ``x``'s dtype.
-    ``act`` (``ACT_NONE`` / ``ACT_RELU`` / ``ACT_HARDSWISH``) instead of ``relu``: ``opa_dwconv_act``."""
+    """Depthwise ``kernel_size`` x ``kernel_size`` convolution (padding k//2) + bias (+ activation) of a channels-last
+    activation or channel slice, one HIP stencil kernel (``opa_dwconv_act``).  ``w_taps``: ``[k*k, C]`` (tap-major,
+    ``depthwise_taps``) in ``x``'s dtype.  ``act`` (``ACT_NONE`` / ``ACT_RELU`` / ``ACT_HARDSWISH``) instead of ``relu``."""
     B, C, H, W = x.shape
     pad = kernel_size // 2
     Ho, Wo = (H + 2 * pad - kernel_size) // stride + 1, (W + 2 * pad - kernel_size) // stride + 1
-    out = torch.empty((B, C, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    if act is not None:
-        _lib.check(_lib.lib().opa_dwconv_act(
-            ctypes.c_void_p(x.data_ptr()), _pixel_stride(x), ctypes.c_void_p(w_taps.data_ptr()),
-            ctypes.c_void_p(bias.data_ptr()) if bias is not None else None, ctypes.c_void_p(out.data_ptr()), C,
-            B, H, W, C, kernel_size, stride, _DTYPES[x.dtype], int(act),
-            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_dwconv_act')
-        return out
-    _lib.check(_lib.lib().opa_dwconv_bias_act(
-        ctypes.c_void_p(x.data_ptr()), _pixel_stride(x), ctypes.c_void_p(w_taps.data_ptr()),
-        ctypes.c_void_p(bias.data_ptr()) if bias is not None else None, ctypes.c_void_p(out.data_ptr()), C,
-        B, H, W, C, kernel_size, stride, _DTYPES[x.dtype], int(bool(relu)),
-        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_dwconv_bias_act')
+    out = _empty_nhwc(x, C, (Ho, Wo))
+    _launch('opa_dwconv_act', _ptr(x), _pixel_stride(x), _ptr(w_taps), _ptr(bias), _ptr(out), C, B, H, W, C, kernel_size, stride,
+            _DTYPES[x.dtype], _act_code(relu, act))
     return out
 
 
-# The MobileNetV3 blocks on the project's kernels (network._MBV3Block._forward_unit): OPA_MBV3=1 (or fused.MBV3 = True) switches the
-# route on.  It stays OFF by default -- the plain torch forward -- until both trunks have been timed against that forward at 641 px,
-# batch 32 (tools/gpu/mobilenetv3_times.py): no speed is claimed for a route nobody has measured.
-MBV3 = os.environ.get('OPA_MBV3', '0') != '0'
-
+# ---- squeeze-and-excitation ---------------------------------------------------------------------------------------------------------------
 
 def _se_convs_ok(fc1, fc2):
     """The part of ``se_gate_supported`` that depends on the two convolutions alone."""
@@ -740,18 +733,12 @@ def se_gate(x, fc1, fc2, mean_out=None):
     reduction and the two matrix-vector products per image; the order of every addition depends on the shape alone.
     ``mean_out``: a contiguous float32 ``[B, C]`` tensor that receives the pooled mean as well (tests)."""
     B, C, H, W = x.shape
-    lib = _lib.lib()
-    nbytes = lib.opa_se_workspace_bytes(B, H * W, C)
+    nbytes = _lib.lib().opa_se_workspace_bytes(B, H * W, C)
     ws = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
     gate = torch.empty((B, C), dtype=torch.float32, device=x.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    _lib.check(lib.opa_se_pool(ctypes.c_void_p(x.data_ptr()), _pixel_stride(x), B, H * W, C, ctypes.c_void_p(ws.data_ptr()), nbytes,
-                               stream), 'opa_se_pool')
-    _lib.check(lib.opa_se_gate(ctypes.c_void_p(ws.data_ptr()), nbytes, B, H * W, C, fc1.out_channels,
-                               ctypes.c_void_p(fc1.weight.data_ptr()), ctypes.c_void_p(fc1.bias.data_ptr()),
-                               ctypes.c_void_p(fc2.weight.data_ptr()), ctypes.c_void_p(fc2.bias.data_ptr()),
-                               ctypes.c_void_p(gate.data_ptr()),
-                               ctypes.c_void_p(mean_out.data_ptr()) if mean_out is not None else None, stream), 'opa_se_gate')
+    _launch('opa_se_pool', _ptr(x), _pixel_stride(x), B, H * W, C, _ptr(ws), nbytes)
+    _launch('opa_se_gate', _ptr(ws), nbytes, B, H * W, C, fc1.out_channels, _ptr(fc1.weight), _ptr(fc1.bias),
+            _ptr(fc2.weight), _ptr(fc2.bias), _ptr(gate), _ptr(mean_out))
     return gate
 
 
@@ -764,26 +751,8 @@ def scale_channels_supported(x, gate):
 def scale_channels_(x, gate):
     """In place ``x[b, c] *= gate[b, c]`` for a channels-last float32 activation or channel slice: one vectorised pass."""
     B, C, H, W = x.shape
-    _lib.check(_lib.lib().opa_se_scale(ctypes.c_void_p(x.data_ptr()), _pixel_stride(x), B, H * W, C, ctypes.c_void_p(gate.data_ptr()),
-                                       ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_se_scale')
+    _launch('opa_se_scale', _ptr(x), _pixel_stride(x), B, H * W, C, _ptr(gate))
     return x
-
-
-def channel_interleave(a, b):
-    """``channel_shuffle(torch.cat((a, b), 1), groups=2)`` in one pass: out[:, 2i] = a[:, i], out[:, 2i+1] = b[:, i]."""
-    pa, pb = _pixel_stride(a), _pixel_stride(b)
-    if not (a.is_cuda and a.dtype in _DTYPES and a.dtype == b.dtype and a.shape == b.shape and pa and pb
-            and _lib.available()):
-        x = torch.cat((a, b), dim=1)
-        n, c, h, w = x.shape
-        return x.view(n, 2, c // 2, h, w).transpose(1, 2).reshape(n, c, h, w)
-    B, half, H, W = a.shape
-    out = torch.empty((B, 2 * half, H, W), dtype=a.dtype, device=a.device, memory_format=torch.channels_last)
-    _lib.check(_lib.lib().opa_channel_interleave(
-        ctypes.c_void_p(a.data_ptr()), pa, ctypes.c_void_p(b.data_ptr()), pb, ctypes.c_void_p(out.data_ptr()),
-        B * H * W, half, _DTYPES[a.dtype], ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
-        'opa_channel_interleave')
-    return out
 
 
 load_pinned()

@@ -96,11 +96,14 @@ def _prep(t, dtype=torch.float32):
 
 
 def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    """The current stream's handle.  Like ``_ptr`` a plain integer: ``_lib.SYMBOLS`` declares every argument's type, so ctypes
+    converts an integer or None to ``void*`` itself."""
+    return torch.cuda.current_stream().cuda_stream
 
 
 def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+    """tensor or None -> address or None."""
+    return t.data_ptr() if t is not None else None
 
 
 def _static_getset(field, cast=float):

@@ -75,23 +75,21 @@ class _Bottleneck(nn.Module):
             out = fused.conv_bias_act(self.conv1, x, self.fb1)            # 1x1: fused MFMA GEMM
             # 3x3: float32 stride 1 -> Winograd F(2x2, 3x3) in one HIP kernel, whose output transform adds the bias and applies
             # the ReLU on the way out (nothing extra to read or write), so the expanding 1x1 is the plain GEMM ...
-            wino = winograd.takes(self.conv2, out, self._wino)
-            if wino:
+            epilogue_done = True        # conv2's bias + ReLU applied by whatever ran it: nothing left for the next operand
+            if winograd.takes(self.conv2, out, self._wino):
                 out = winograd.run(self.conv2, out, bias=self.fb2, relu=True)
             elif fused.conv3x3_x3_supported(self.conv2, out, self.fb2):  # ... float32 strided: implicit GEMM of the split-operand kernel
                 h = out                                                   # (or MIOpen + the epilogue pass, whichever is faster for the shape)
                 s = self.conv2.stride[0]
-                out = fused.pick('conv3', h.shape[0] * ((h.shape[2] - 1) // s + 1) * ((h.shape[3] - 1) // s + 1), 9 * h.shape[1],
-                                 self.conv2.out_channels, s > 1, False,
+                out = fused.pick('conv3', fused.out_pixels(h, s), 9 * h.shape[1], self.conv2.out_channels, s > 1, False,
                                  lambda: fused.conv3x3_bias_act_x3(self.conv2, h, self.fb2, True),
                                  lambda: fused.bias_act_(self.conv2(h), self.fb2))
-                wino = True                                               # (bias + ReLU applied: nothing left for the next operand)
             elif fused.gconv3x3_supported(self.conv2, out, self.fb2):    # ... float32 grouped (ResNeXt): one stencil kernel,
                 out = fused.gconv3x3_bias_act(self.conv2, out, self.fb2, True)        # bias + ReLU inside
-                wino = True
             else:
                 out = self.conv2(out)                                     # ... bfloat16: MIOpen, raw output ...
-            a_bias = None if wino else self.fb2
+                epilogue_done = False
+            a_bias = None if epilogue_done else self.fb2
 
             def two_launches():
                 identity = x if self.downsample is None else self.downsample[0](x)
@@ -101,7 +99,7 @@ class _Bottleneck(nn.Module):
             # is never written), conv2's bias + ReLU applied to the operand where conv2 left them out -- where that is faster
             if self.downsample is not None and fused.pair_supported(self.conv3, self.downsample[0], out, x, self.fb3, a_bias):
                 # (written: with a_bias, two_launches may apply conv2's epilogue to ``out`` in place -- once, not once per timed call)
-                return fused.pick('pair', out.shape[0] * out.shape[2] * out.shape[3], self.conv3.in_channels + self.downsample[0].in_channels,
+                return fused.pick('pair', fused.out_pixels(out), self.conv3.in_channels + self.downsample[0].in_channels,
                                   self.conv3.out_channels, self.downsample[0].stride[0] > 1, a_bias is not None,
                                   lambda: fused.conv1x1_pair_bias_act_x3(self.conv3, self.downsample[0], out, x, self.fb3, True, a_bias),
                                   two_launches, written=out if a_bias is not None else None)
@@ -212,7 +210,7 @@ class Resnet(BaseNetwork):
         if getattr(self, 'fused', False):
             if fused.stem_x3_supported(self.input_block[0], x, self.fb0):     # float32: the stem as an implicit GEMM, bias + ReLU inside
                 conv, x0 = self.input_block[0], x
-                x = fused.pick('stem', x0.shape[0] * ((x0.shape[2] - 1) // 2 + 1) * ((x0.shape[3] - 1) // 2 + 1), 256, conv.out_channels,
+                x = fused.pick('stem', fused.out_pixels(x0, 2), 256, conv.out_channels,
                                True, False, lambda: fused.stem7x7_bias_act_x3(conv, x0, self.fb0),
                                lambda: fused.bias_act_(conv(x0), self.fb0))
             else:
@@ -256,8 +254,7 @@ class _InvertedResidualK(nn.Module):
                 continue
             for m in branch:
                 if isinstance(m, nn.Conv2d) and m.groups == m.in_channels and m.groups > 1:
-                    k = m.kernel_size[0]
-                    m.register_buffer('w_taps', m.weight.detach().reshape(m.out_channels, k * k).t().contiguous())
+                    m.register_buffer('w_taps', fused.depthwise_taps(m.weight))
         self.fused = True
 
     @staticmethod
@@ -265,17 +262,20 @@ class _InvertedResidualK(nn.Module):
         """``w_taps`` of the CURRENT depthwise weight: the buffer (part of the state dict since it was introduced, so it stays one)
         is written again whenever the weight was replaced, converted or changed in place since."""
         def make():
-            k = conv.kernel_size[0]
-            conv.w_taps = conv.weight.detach().reshape(conv.out_channels, k * k).t().contiguous()
+            conv.w_taps = fused.depthwise_taps(conv.weight)
             return True
         fused.derived(conv, '_opa_taps', (conv.weight,), make)
         return conv.w_taps
 
     @staticmethod
+    def _dw_ok(m, x):
+        """Can the convolution ``m`` of a branch run through the stencil kernel on ``x``?"""
+        return hasattr(m, 'w_taps') and m.weight.dtype == x.dtype and fused.dwconv_supported(x, m.kernel_size[0], m.stride[0])
+
+    @staticmethod
     def _run(branch, x):
         for m in branch:
-            if isinstance(m, nn.Conv2d) and hasattr(m, 'w_taps') and m.weight.dtype == x.dtype \
-                    and fused.dwconv_supported(x, m.kernel_size[0], m.stride[0]):
+            if isinstance(m, nn.Conv2d) and _InvertedResidualK._dw_ok(m, x):
                 x = fused.dwconv_bias_act(x, _InvertedResidualK.taps_of(m), m.bias, m.kernel_size[0], m.stride[0])
             else:
                 x = m(x)
@@ -292,7 +292,7 @@ class _InvertedResidualK(nn.Module):
                 if not isinstance(m, nn.Conv2d):
                     continue
                 if m.groups > 1:
-                    if not (hasattr(m, 'w_taps') and m.weight.dtype == x.dtype and fused.dwconv_supported(x, m.kernel_size[0], m.stride[0])):
+                    if not self._dw_ok(m, x):
                         return False
                 elif not fused._unit_conv_ok(m):
                     return False
@@ -322,9 +322,8 @@ class _InvertedResidualK(nn.Module):
     def forward(self, x):
         if self.fused and x.is_cuda:
             if self._unit_route_supported(x):       # ONE decision per unit: its output pixels and its last convolution
-                last, s = self.branch2[5], self.branch2[3].stride[0]
-                pixels = x.shape[0] * ((x.shape[2] - 1) // s + 1) * ((x.shape[3] - 1) // s + 1)
-                return fused.pick('unit', pixels, last.in_channels, last.out_channels, True, False,
+                last = self.branch2[5]
+                return fused.pick('unit', fused.out_pixels(x, self.branch2[3].stride[0]), last.in_channels, last.out_channels, True, False,
                                   lambda: self._forward_unit(x), lambda: self._forward_fused(x), timing=False)
             return self._forward_fused(x)
         if self.branch1 is None:
@@ -370,7 +369,7 @@ class ShuffleNetV2K(BaseNetwork):
         x = self.stage4(self.stage3(self.stage2(self.input_block(x))))
         conv = self.conv5[0]
         if self.fused and x.is_cuda and fused.unit_conv_x3_supported(conv, x):
-            return fused.pick('unit', x.shape[0] * x.shape[2] * x.shape[3], conv.in_channels, conv.out_channels, False, False,
+            return fused.pick('unit', fused.out_pixels(x), conv.in_channels, conv.out_channels, False, False,
                               lambda: fused.conv1x1_unit_x3(conv, x), lambda: self.conv5(x), timing=False)
         return self.conv5(x)
 
@@ -438,10 +437,7 @@ class _MBV3Block(nn.Module):
     @staticmethod
     def taps_of(conv):
         """The CURRENT depthwise weight tap-major, ``[k * k, C]`` (derived and cached, no part of a checkpoint)."""
-        def make():
-            k = conv.kernel_size[0]
-            return conv.weight.detach().reshape(conv.out_channels, k * k).t().contiguous()
-        return fused.derived(conv, '_opa_taps', (conv.weight,), make)
+        return fused.derived(conv, '_opa_taps', (conv.weight,), lambda: fused.depthwise_taps(conv.weight))
 
     def _route_supported(self, x):
         """Can the WHOLE block run on the project's kernels (``_forward_unit``)?  float32 outside autocast; every intermediate tensor is
@@ -556,13 +552,13 @@ class CompositeField4(nn.Module):
     def forward(self, x):
         if not self.training and fused.head_conv_x3_supported(self.conv, x):     # float32 inference: the head's 1x1 convolution through
             conv, x0 = self.conv, x                                                # the split-operand GEMM where that is faster
-            x = fused.pick('head', x0.shape[0] * x0.shape[2] * x0.shape[3], conv.in_channels, conv.out_channels, False, False,
+            x = fused.pick('head', fused.out_pixels(x0), conv.in_channels, conv.out_channels, False, False,
                            lambda: fused.head_conv_x3(conv, x0), lambda: conv(x0))
         elif not self.training and self.conv.in_channels % 64 != 0 and fused.X3_HEAD and fused.unit_conv_x3_supported(self.conv, x):
             # input channels that are no multiple of 64 (k16: 1392): the unit mode of the same kernel, N tail native (no padded
             # pitch, no copy-out), decided like the units: the table, else by size, never timed
             conv, x0 = self.conv, x
-            x = fused.pick('unit', x0.shape[0] * x0.shape[2] * x0.shape[3], conv.in_channels, conv.out_channels, False, False,
+            x = fused.pick('unit', fused.out_pixels(x0), conv.in_channels, conv.out_channels, False, False,
                            lambda: fused.conv1x1_unit_x3(conv, x0, relu=False), lambda: conv(x0), timing=False)
         else:
             x = self.conv(x)

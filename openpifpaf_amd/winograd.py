@@ -5,12 +5,11 @@ thirteen stride-1 3x3 convolutions of ResNet-50 are half of the float32 step.  `
 with 16 instead of 36 multiplications per 2x2 outputs, in float32 throughout; the filter side ``G g G^T`` is computed once
 per weight, in float64, and stored in the order the kernel's lanes read it.
 """
-import ctypes
 import os
 
 import torch
 
-from . import _lib
+from . import _lib, fused
 
 # variant -> (K-chunk, 32-wide channel blocks per workgroup): must match launch_winograd_f23 (csrc/winograd.hip)
 VARIANTS = {0: (16, 2), 1: (8, 1), 2: (16, 2), 3: (16, 2), 4: (16, 2)}     # 2: variant 0's tile and filter layout, eight waves
@@ -18,7 +17,7 @@ DEFAULT_VARIANT = 2         # eight waves in two shifts (csrc/winograd.hip): 5-8
 X3_VARIANT = 4              # variant 2 on the bf16 MFMA pipe with exactly split operands (opa_conv3x3_winograd_f32x3)
 # OPA_WINO_X3=0: the network's Winograd convolutions stay on variant 2 (float32 MFMA) -- read ONCE, at import; the two round
 # differently, so it is a switch for a whole job, never a per-call choice
-X3 = os.environ.get('OPA_WINO_X3', '1') != '0'
+X3 = fused._switch('OPA_WINO_X3', '1')
 MIN_WORKGROUPS = 256        # below one workgroup per compute unit the launch does not fill the chip: MIOpen's convolution
 _G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
 
@@ -107,7 +106,6 @@ def split_filter(weight):
     ``U[k = 2 e + l // 32][c = 32 j + l % 32]`` of the chunk -- the bf16 fragment of virtual k' = 8 (l // 32) + e, i.e. the chunk's
     K permutation k' = 8 h + e <-> k = 2 e + h, which the kernel applies to the pixel operand alike.  A wave's load of one piece
     is 1 KB contiguous."""
-    from . import fused
     cout, cin = weight.shape[:2]
     u = transform_filter(weight, DEFAULT_VARIANT)
     u = u.reshape(cout // 64, cin // 16, 16, 2, 2, 64, 4).permute(0, 1, 2, 3, 5, 4, 6)    # [.., j, kq, lane, e] -> [.., j, lane, kq, e]
@@ -119,14 +117,12 @@ def split_filter_of(conv):
     """``split_filter(conv.weight)``, kept on the module and computed again whenever the weight was replaced, moved, converted or
     changed in place (``load_state_dict`` into an optimized network): ``fused.derived``'s key (data pointer, version counter, device,
     dtype)."""
-    from . import fused
     return fused.derived(conv, '_opa_wino_u3', (conv.weight,), lambda: split_filter(conv.weight))
 
 
 def filter_of(conv):
     """``transform_filter(conv.weight, 2)`` in the weight's dtype -- variant 2's operand -- kept on the module and kept current
     like :func:`split_filter_of` (a snapshot taken when the network was optimized would outlive ``load_state_dict``)."""
-    from . import fused
     return fused.derived(conv, '_opa_wino_u', (conv.weight,),
                          lambda: transform_filter(conv.weight, DEFAULT_VARIANT).to(conv.weight.dtype))
 
@@ -147,35 +143,27 @@ def direct_flops():
     return _direct_flops
 
 
-def conv3x3(x, u, c_out, bias=None, relu=False, variant=0, order=0, out=None):
-    """``conv2d(x, weight, padding=1)`` (+ bias, ReLU) for the ``u = transform_filter(weight, variant)`` of a 3x3 weight.
-    ``x``: ``[B, C_in, H, W]`` float32 channels_last on the GPU -> ``[B, c_out, H, W]`` channels_last."""
+def _run_kernel(symbol, x, u, c_out, bias, relu, variant, order, out):
+    """One launch of either entry point (they take the same arguments), counted in ``direct_flops``."""
     global _direct_flops
     B, cin, H, W = x.shape
     _direct_flops += 18.0 * B * H * W * cin * c_out
     if out is None:
-        out = torch.empty((B, c_out, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    _lib.check(_lib.lib().opa_conv3x3_winograd_f32(
-        ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(u.data_ptr()),
-        ctypes.c_void_p(bias.data_ptr()) if bias is not None else None, ctypes.c_void_p(out.data_ptr()),
-        B, H, W, cin, c_out, int(bool(relu)), variant, order,
-        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_conv3x3_winograd_f32')
+        out = fused._empty_nhwc(x, c_out, dtype=torch.float32)
+    fused._launch(symbol, fused._ptr(x), fused._ptr(u), fused._ptr(bias), fused._ptr(out), B, H, W, cin, c_out, int(bool(relu)),
+                  variant, order)
     return out
+
+
+def conv3x3(x, u, c_out, bias=None, relu=False, variant=0, order=0, out=None):
+    """``conv2d(x, weight, padding=1)`` (+ bias, ReLU) for the ``u = transform_filter(weight, variant)`` of a 3x3 weight.
+    ``x``: ``[B, C_in, H, W]`` float32 channels_last on the GPU -> ``[B, c_out, H, W]`` channels_last."""
+    return _run_kernel('opa_conv3x3_winograd_f32', x, u, c_out, bias, relu, variant, order, out)
 
 
 def conv3x3_x3(x, u3, c_out, bias=None, relu=False, variant=X3_VARIANT, order=0, out=None):
     """:func:`conv3x3` through variant 4 (bf16 MFMA pipe, exactly split operands) for ``u3 = split_filter(weight)``."""
-    global _direct_flops
-    B, cin, H, W = x.shape
-    _direct_flops += 18.0 * B * H * W * cin * c_out
-    if out is None:
-        out = torch.empty((B, c_out, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    _lib.check(_lib.lib().opa_conv3x3_winograd_f32x3(
-        ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(u3.data_ptr()),
-        ctypes.c_void_p(bias.data_ptr()) if bias is not None else None, ctypes.c_void_p(out.data_ptr()),
-        B, H, W, cin, c_out, int(bool(relu)), variant, order,
-        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), 'opa_conv3x3_winograd_f32x3')
-    return out
+    return _run_kernel('opa_conv3x3_winograd_f32x3', x, u3, c_out, bias, relu, variant, order, out)
 
 
 def reference_f23(x, weight):

@@ -245,9 +245,61 @@ def test_unit_gemm_with_hardswish_and_with_residual(K, N):
         ok &= _report('unit+residual+hardswish K %d N %d' % (K, N), tc.errors(got, ref64), _e0(lambda: F.hardswish(conv(x) + res), ref64))
         assert torch.equal(fused.conv1x1_unit_x3(conv, x, residual=res, act=fused.ACT_RELU),
                            F.relu(fused.conv1x1_unit_x3(conv, x, residual=res, act=fused.ACT_NONE)))
-        assert torch.equal(fused.conv1x1_unit_x3(conv, x, act=fused.ACT_RELU), fused.conv1x1_unit_x3(conv, x, relu=True))
-        assert torch.equal(fused.conv1x1_unit_x3(conv, x, act=fused.ACT_NONE), fused.conv1x1_unit_x3(conv, x, relu=False))
-    assert ok
+    assert ok        # (act= and relu= are one call of one entry point; the C twins: test_unit_gemm_entry_points_are_one_kernel)
+
+
+SENTINEL = 12345.5
+
+
+@pytest.mark.parametrize('partner', [False, True], ids=['alone', 'partner'])
+@pytest.mark.parametrize('act', [0, 1])
+@pytest.mark.parametrize('N,terms', [(40, 6), (128, 6), (40, 9)])
+def test_unit_gemm_entry_points_are_one_kernel(N, terms, act, partner, monkeypatch):
+    """``opa_gemm_unit_bias_act_f32x3(relu=a)`` against ``opa_gemm_unit_act_f32x3(residual NULL, act=a)``, raw, each into its own
+    sentinel-filled output: bit for bit.  K = 72 (a K tail), M = 286 (two full 128-row tiles and a tail); N = 40: the 64-wide tile
+    with an N tail, N = 128: the 128-wide tile.  The launcher calls the second one only."""
+    K, shape = 72, (2, 13, 11)
+    conv = tc.randomize_(nn.Conv2d(K, N, 1), K + N).cuda()
+    x = torch.randn((2, K, 13, 11), generator=_gen(K)).cuda().contiguous(memory_format=CL)
+    third = torch.randn((2, N, 13, 11), generator=_gen(N)).cuda().contiguous(memory_format=CL) if partner else None
+    w3, bp = fused._unit_weight_of(conv)
+    outs = [torch.full((2, 2 * N if partner else N, 13, 11), SENTINEL, device='cuda').contiguous(memory_format=CL) for _ in range(2)]
+    lib, vp = _lib.lib(), ctypes.c_void_p
+    head = (vp(x.data_ptr()), K, vp(w3.data_ptr()), vp(bp.data_ptr()), vp(third.data_ptr()) if partner else None, N if partner else 0)
+    tail = (shape[0] * shape[1] * shape[2], N, K, act, terms, None)
+    assert lib.opa_gemm_unit_bias_act_f32x3(*head, vp(outs[0].data_ptr()), *tail) == 0
+    assert lib.opa_gemm_unit_act_f32x3(*head, None, 0, vp(outs[1].data_ptr()), *tail) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(outs[0], outs[1]) and outs[0].isfinite().all() and not bool((outs[0] == SENTINEL).any())
+    assert bool((outs[0][:, 1::2] if partner else outs[0]).lt(0).any()) == (act == 0)      # (the product's channels: the odd ones next to a partner)
+    monkeypatch.setattr(fused, 'X3_TERMS', terms)
+    assert torch.equal(fused.conv1x1_unit_x3(conv, x, relu=bool(act), partner=third), outs[1])
+    assert torch.equal(fused.conv1x1_unit_x3(conv, x, act=act, partner=third), outs[1])
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16], ids=['float32', 'bfloat16'])
+@pytest.mark.parametrize('act', [0, 1])
+@pytest.mark.parametrize('stride', [1, 2])
+@pytest.mark.parametrize('k', [3, 5])
+def test_depthwise_entry_points_are_one_kernel(k, stride, act, dtype):
+    """``opa_dwconv_bias_act(relu=a)`` against ``opa_dwconv_act(act=a)``, raw, with a bias, each into its own sentinel-filled
+    output: bit for bit.  The launcher calls the second one only."""
+    C, g = 8, _gen(10 * k + stride)
+    x = torch.randn((2, C, 7, 5), generator=g).to(dtype).cuda().contiguous(memory_format=CL)
+    taps = (torch.randn((k * k, C), generator=g) * (2.0 / (k * k)) ** 0.5).to(dtype).cuda()
+    b = (torch.randn(C, generator=g) * 0.5).to(dtype).cuda()
+    ho, wo = (7 + 2 * (k // 2) - k) // stride + 1, (5 + 2 * (k // 2) - k) // stride + 1
+    outs = [torch.full((2, C, ho, wo), SENTINEL, dtype=dtype, device='cuda').contiguous(memory_format=CL) for _ in range(2)]
+    sentinel = outs[0].flatten()[0].clone()
+    lib, vp = _lib.lib(), ctypes.c_void_p
+    for fn, out in ((lib.opa_dwconv_bias_act, outs[0]), (lib.opa_dwconv_act, outs[1])):
+        assert fn(vp(x.data_ptr()), C, vp(taps.data_ptr()), vp(b.data_ptr()), vp(out.data_ptr()), C, 2, 7, 5, C, k, stride,
+                  fused._DTYPES[dtype], act, None) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(outs[0], outs[1]) and outs[0].isfinite().all() and not bool((outs[0] == sentinel).any())
+    assert bool((outs[0] < 0).any()) == (act == 0)
+    assert torch.equal(fused.dwconv_bias_act(x, taps, b, k, stride, relu=bool(act)), outs[1])
+    assert torch.equal(fused.dwconv_bias_act(x, taps, b, k, stride, act=act), outs[1])
 
 
 def test_residual_with_partner_is_refused():

@@ -54,10 +54,12 @@ def _operands(net):
             wp[:, :7, :7, :3] = w.permute(0, 2, 3, 1)
             out.append((name + '/stem', fused._stem_weight_of(m.input_block[0]), fused.split_weight(wp.reshape(w.shape[0], 256))))
         if isinstance(m, network.CompositeField4) and m.conv.weight.dtype == torch.float32:
-            n = m.conv.out_channels
-            npad = (n + 63) // 64 * 64
-            w3, bp = fused._head_weight_of(m.conv)
-            out.append((name + '/head w3', w3, fused.split_weight(_pad_rows(m.conv.weight.detach().flatten(1), npad))))
+            n, k = m.conv.out_channels, m.conv.in_channels
+            npad, kpad = (n + 63) // 64 * 64, (k + 63) // 64 * 64       # (k16's heads have 1392 input channels: the unit mode's K tail)
+            w3, bp = fused._unit_weight_of(m.conv)
+            wp = torch.zeros((npad, kpad))
+            wp[:n, :k] = m.conv.weight.detach().flatten(1)
+            out.append((name + '/head w3', w3, fused.split_weight(wp)))
             out.append((name + '/head bias', bp, _pad_rows(m.conv.bias.detach(), npad)))
         if isinstance(m, nn.Conv2d) and hasattr(m, 'w_taps'):
             k = m.kernel_size[0]

@@ -33,9 +33,8 @@ def time_units(path):
         x = args[0]
         if not mod._unit_route_supported(x):
             return
-        last, s = mod.branch2[5], mod.branch2[3].stride[0]
-        key = ('torch.float32/unit', x.shape[0] * ((x.shape[2] - 1) // s + 1) * ((x.shape[3] - 1) // s + 1), last.in_channels,
-               last.out_channels, True, False)
+        last = mod.branch2[5]
+        key = ('torch.float32/unit', fused.out_pixels(x, mod.branch2[3].stride[0]), last.in_channels, last.out_channels, True, False)
         t = ms.setdefault(key, [0.0, 0.0])
         t[0] += fused._time_ms(lambda: mod._forward_fused(x))
         t[1] += fused._time_ms(lambda: mod._forward_unit(x))
@@ -44,7 +43,7 @@ def time_units(path):
         x, conv = args[0], mod[0]
         if not fused.unit_conv_x3_supported(conv, x):
             return
-        t = ms.setdefault(('torch.float32/unit', x.shape[0] * x.shape[2] * x.shape[3], conv.in_channels, conv.out_channels, False, False),
+        t = ms.setdefault(('torch.float32/unit', fused.out_pixels(x), conv.in_channels, conv.out_channels, False, False),
                           [0.0, 0.0])
         t[0] += fused._time_ms(lambda: mod[2](mod[0](x)))
         t[1] += fused._time_ms(lambda: fused.conv1x1_unit_x3(conv, x))
