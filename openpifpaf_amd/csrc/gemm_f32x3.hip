@@ -4,7 +4,9 @@
 // dense), so the compute-bound 1x1 convolutions of ResNet layers 3-4 sit at 115-118 TFLOP/s however the kernel around them
 // is built (gemm_f32.hip).  A float32 number is, exactly, the sum of three bfloat16 numbers: its 24-bit
 // significand cut into 8 + 8 + 8 bits (a1 = a with the low 16 bits cleared, r = a - a1, a2 = r with the low 16 bits cleared,
-// a3 = r - a2: every step exact, every piece representable -- bf16 has float32's exponent range).  So
+// a3 = r - a2: every step exact, every piece representable -- bf16 has float32's exponent range -- from |a| = 2^-110 up; what
+// becomes of smaller numbers, of +-Inf (NaN: the split's Inf - Inf) and of NaN is stated in split_bf16.hpp and at the end of this
+// header).  So
 //     a * b = sum over i, j of a_i * b_j                                       (nine products, each EXACT in float32:
 // 8 x 8 significand bits), and v_mfma_f32_32x32x16_bf16 forms and accumulates them in float32 like the float32 MFMA
 // accumulates its own exact products.  TERMS = 9: all of them -- the GEMM's only rounding is the accumulation's, as in
@@ -28,6 +30,14 @@
 // (ds_read_b128 fragments of 16 consecutive rows fall on 16 different bank groups AND the 8-byte plane stores of the split do
 // not collide: with rows padded to 80 B a third of the LDS cycles were store conflicts; profiles/r6/gemm_x3_swizzle_ab.log:
 // 2-7 % on the reduce shapes); XCD-aware tile order and epilogue as in gemm_f32.hip.
+//
+// Non-finite and tiny operands (tests/test_gpu_x3_edges.py): a NaN or +-Inf element of A makes its output ROW
+// NaN, one of W its output COLUMN (a float32 GEMM gives +-Inf for an Inf operand: the split turns Inf into (Inf, NaN, NaN));
+// Inf in the bias or the residual arrives as Inf.  Every other element of the tile is bit for bit what it is without that
+// value.  fmaxf returns its other argument for a NaN: ReLU stores NaN, +0 or +Inf there, and the prologue turns a NaN (or -Inf)
+// activation into 0 before the split.  The stem's eighth window row and column meet zero weights, so a non-finite pixel
+// reaches every output whose 8x8 window holds it (0 x Inf), not the 7x7 ones alone: written down and pinned by a test.  Operands below 2^-110: see split_bf16.hpp; an element loses less than
+// 2^-125 sum_k (|a_mk| + |w_nk|).
 #include "common.hpp"
 #include "split_bf16.hpp"
 

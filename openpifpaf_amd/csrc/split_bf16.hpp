@@ -1,6 +1,14 @@
 // A float32 number as the exact sum of three bfloat16 pieces (csrc/gemm_f32x3.hip, csrc/winograd.hip variant 4): its 24-bit
 // significand cut into 8 + 8 + 8 bits by truncation -- a1 = a with the low 16 bits cleared, r = a - a1, a2 = r with the low 16
-// bits cleared, a3 = r - a2; every step exact, every piece representable (bf16 has float32's exponent range).
+// bits cleared, a3 = r - a2; every step exact, every piece representable (bf16 has float32's exponent range) for every finite
+// |a| >= 2^-110 and for zero.  Below 2^-110 the low pieces are subnormal bf16 numbers and a has bits under 2^-133, the smallest
+// of them: taking the high halves truncates those (a subnormal float32 a has an empty second piece and up to 16 bits in the
+// third).  Measured (profiles/x3_edges/errors.log): v_mfma_f32_32x32x16_bf16 KEEPS subnormal bf16 inputs -- the elements of
+// tests/test_gpu_x3_edges.py::test_subnormal_pieces that tell come out at 3-8e-8 of sum |a||w|, where a pipe that flushed them
+// would leave 1e-6 and more (tests/test_x3_cases.py); an element loses less than 2^-125 sum_k (|a_mk| + |w_nk|) to the bits
+// under 2^-133.
+// +-Inf leaves as (+-Inf, NaN, NaN) -- a - a1 is Inf - Inf -- and NaN as NaN in every piece: a non-finite operand makes every
+// product it enters NaN (its output row; for a weight its output channel), and only those (tests/test_gpu_x3_edges.py).
 #pragma once
 
 #include <hip/hip_runtime.h>

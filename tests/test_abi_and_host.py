@@ -405,7 +405,8 @@ def test_seed_tie_order_setting_and_workspace_view():
 
 def test_split_weight_is_exact_on_the_cpu():
     """``fused.split_weight``: every float32 weight is, bit for bit, the sum of its three bfloat16 pieces (the operand of the
-    split-operand GEMM, csrc/gemm_f32x3.hip) -- including denormal-free extremes, zeros and negative numbers."""
+    split-operand GEMM, csrc/gemm_f32x3.hip) -- including extremes, zeros and negative numbers; what becomes of non-finite weights
+    and of weights below 2^-110 is pinned at the end."""
     torch = pytest.importorskip('torch')
     from openpifpaf_amd import fused
     torch.manual_seed(0)
@@ -416,6 +417,22 @@ def test_split_weight_is_exact_on_the_cpu():
     assert w3.dtype == torch.bfloat16 and tuple(w3.shape) == (3, 64, 128)
     assert torch.equal((w3[0].float() + w3[1].float()) + w3[2].float(), w)
     assert float(w3[1].float().abs().max() / w.abs().max()) < 2.0 ** -7 and float((w3[2].float().abs() / w.abs().clamp_min(1e-30)).max()) < 2.0 ** -15
+    # where "exact" ends (tests/test_x3_cases.py pins the same through the CPU model of the kernels' split):
+    #  * +-Inf -> (+-Inf, NaN, NaN) -- Inf - Inf -- and NaN -> NaN in every piece: a non-finite weight makes its output channel NaN;
+    #  * -0.0 -> (-0.0, +0.0, +0.0);
+    #  * from |w| = 2^-110 up all three pieces are bfloat16 numbers, subnormal ones below 2^-126; smaller numbers (subnormal
+    #    float32 among them) have bits under 2^-133, the smallest subnormal bfloat16, which the conversion rounds away
+    inf, nan = float('inf'), float('nan')
+    s3 = fused.split_weight(torch.tensor([[inf, -inf, nan, -0.0]])).float()
+    assert s3[0, 0, 0] == inf and s3[0, 0, 1] == -inf and bool(s3[1:, 0, :3].isnan().all()) and bool(s3[0, 0, 2].isnan())
+    assert s3[:, 0, 3].view(torch.int32).tolist() == [-2 ** 31, 0, 0]
+    small = torch.tensor([[2.0 ** -110 * (1 + 2.0 ** -23), -(2.0 ** -104) * (2 - 2.0 ** -23), 2.0 ** -126 * (1 + 2.0 ** -7)]])
+    p3 = fused.split_weight(small).float()
+    assert torch.equal((p3[0] + p3[1]) + p3[2], small) and 0 < float(p3[1, 0, 0]) < 2.0 ** -126       # exact, subnormal pieces
+    sub = torch.tensor([[2.0 ** -127 + 2.0 ** -149, 2.0 ** -120 * (1 + 2.0 ** -23)]])                  # bits below 2^-133
+    q3 = fused.split_weight(sub).double()
+    lost = (q3.sum(0) - sub.double()).abs()
+    assert bool((lost > 0).all()) and bool((lost <= 2.0 ** -134).all())
 
 
 def test_pick_takes_the_pinned_choice_without_timing(monkeypatch):
