@@ -460,6 +460,29 @@ int opa_gemm2_bias_act_f32x3(const float* a1_dev, int32_t k1, const float* a2_de
 int opa_conv3x3_f32x3(const float* x_dev, const void* w3_dev, const float* bias_dev, float* out_dev, int32_t batch, int32_t h_in,
                       int32_t w_in, int32_t c_in, int32_t c_out, int32_t stride, int32_t relu, int32_t terms, void* stream);
 
+/* The same convolution with a DILATION d >= 1 and padding d (the same kernel: opa_conv3x3_f32x3 is its d = 1 call, bit for bit) --
+ * the 3x3 convolutions of a ResNet's block 5 under --resnet-block5-dilation (reference network/basenetworks.py:121-135).  Column
+ * block t = 3 ky + kx of K holds the channels of input pixel (stride*y - d + d*ky, stride*x - d + d*kx); pixels in the padding are
+ * zeros (a dilation beyond the image leaves the centre tap alone).  w3_dev as above (split_weight_3x3: the layout does not depend
+ * on d); out_dev [B, ho, wo, c_out], ho = (h_in - 1) / stride + 1.  c_in % 64 == 0, c_out % 64 == 0, pointers 16-B aligned,
+ * dilation >= 1, stride >= 1, terms 6 or 9, (batch * h_in * w_in + dilation * (w_in + 1)) * c_in * 4 < 2^31; anything else:
+ * OPA_ERR_INVALID_ARGUMENT before any launch.  batch, h_in or w_in == 0: OPA_OK, nothing runs. */
+int opa_conv3x3_dilated_f32x3(const float* x_dev, const void* w3_dev, const float* bias_dev, float* out_dev, int32_t batch, int32_t h_in,
+                              int32_t w_in, int32_t c_in, int32_t c_out, int32_t stride, int32_t dilation, int32_t relu, int32_t terms,
+                              void* stream);
+
+/* The input max-pool of a ResNet (reference network/basenetworks.py:85-93: MaxPool2d(3, 2, 1) behind the stem) together with the
+ * stem's epilogue, one pass over a channels-last activation (csrc/pool.hip):
+ *     out[b, y, x, c] = max over the 3x3 window at (2y - 1, 2x - 1) of act(x[b, iy, ix, c] + bias[c])
+ * computed as act(max(x) + bias) -- both steps are non-decreasing, so this equals max_pool2d(relu(x + bias), 3, 2, 1) as numbers
+ * (the sign of a zero result may differ; without bias and relu the bits are torch's); float32 arithmetic, one rounding to the storage type.  Pixels in the padding never win (the window always holds its centre); a
+ * NaN in the window gives NaN.  x_dev [B, h, w, c], out_dev [B, ho, wo, c], ho = (h - 1) / 2 + 1; bias_dev [c] of the same dtype
+ * or NULL; dtype 0 = float32, 2 = bfloat16; relu 0/1.  c % 8 == 0, pointers 16-B aligned, stride == 2 (any other is refused),
+ * batch * h * w * c elements < 2 GB (32-bit offsets, one thread per output vector); anything else: OPA_ERR_INVALID_ARGUMENT before
+ * any launch.  batch, h or w == 0: OPA_OK, nothing runs. */
+int opa_maxpool3x3_bias_act(const void* x_dev, const void* bias_dev, void* out_dev, int32_t dtype, int32_t batch, int32_t h, int32_t w,
+                            int32_t c, int32_t stride, int32_t relu, void* stream);
+
 /* A convolution whose window ROWS are the taps of the same implicit GEMM, on an input that is padded IN MEMORY: the 7x7 stride-2
  * stem of a ResNet (reference network/basenetworks.py:71-150) on a 4-channel, zero-padded copy of the image.  x_dev [B, hp, wp, pix]
  * (pix floats per pixel); output pixel (y, x) reads for tap t the tap_floats contiguous floats that begin at input pixel

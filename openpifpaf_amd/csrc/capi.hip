@@ -948,21 +948,60 @@ int opa_conv_rows_f32x3(const float* x_dev, const void* w3_dev, const float* bia
     return OPA_OK;
 }
 
-int opa_conv3x3_f32x3(const float* x_dev, const void* w3_dev, const float* bias_dev, float* out_dev, int32_t batch, int32_t h_in,
-                      int32_t w_in, int32_t c_in, int32_t c_out, int32_t stride, int32_t relu, int32_t terms, void* stream) {
-    if (!x_dev || !w3_dev || !bias_dev || !out_dev || batch <= 0 || h_in <= 0 || w_in <= 0 || stride < 1 || c_in <= 0 || c_out <= 0 ||
-        (terms != 6 && terms != 9))
-        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_conv3x3_f32x3: bad arguments");
-    if (c_in % 64 != 0 || c_out % 64 != 0)
-        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_conv3x3_f32x3: c_in and c_out must be multiples of 64");
-    if (((uintptr_t)x_dev | (uintptr_t)w3_dev | (uintptr_t)out_dev | (uintptr_t)bias_dev) & 15)
-        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_conv3x3_f32x3: pointers must be 16-B aligned");
-    if (((long long)batch * h_in * w_in + w_in + 1) * c_in * 4 > 0x7fffffffll)
-        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_conv3x3_f32x3: the activation must be smaller than 2 GB");
-    hipError_t e = launch_conv3x3_f32x3(x_dev, batch, h_in, w_in, c_in, stride, (const unsigned short*)w3_dev, bias_dev, out_dev, c_out,
-                                        relu, terms, (hipStream_t)stream);
+// opa_conv3x3_f32x3 and opa_conv3x3_dilated_f32x3: one set of checks, one launcher (`fn`: the entry point's name in the messages)
+static int conv3x3_f32x3(const char* fn, const float* x_dev, const void* w3_dev, const float* bias_dev, float* out_dev, int32_t batch,
+                         int32_t h_in, int32_t w_in, int32_t c_in, int32_t c_out, int32_t stride, int32_t dilation, int32_t relu,
+                         int32_t terms, void* stream) {
+    auto refuse = [&](const char* what) { return fail(OPA_ERR_INVALID_ARGUMENT, std::string(fn) + ": " + what); };
+    if (!x_dev || !w3_dev || !bias_dev || !out_dev || batch < 0 || h_in < 0 || w_in < 0 || stride < 1 || dilation < 1 || c_in <= 0 ||
+        c_out <= 0 || (terms != 6 && terms != 9))
+        return refuse("bad arguments");
+    if (c_in % 64 != 0 || c_out % 64 != 0) return refuse("c_in and c_out must be multiples of 64");
+    if (((uintptr_t)x_dev | (uintptr_t)w3_dev | (uintptr_t)out_dev | (uintptr_t)bias_dev) & 15) return refuse("pointers must be 16-B aligned");
+    // (the buffer the kernel reads through begins dilation * (w_in + 1) pixels before the tensor: its size is a 32-bit count of bytes)
+    // (in double: exact up to 2^53, and no product of four 32-bit arguments overflows it)
+    if (((double)batch * h_in * w_in + (double)dilation * ((double)w_in + 1.0)) * c_in * 4.0 >= 2147483648.0)
+        return refuse("the activation must be smaller than 2 GB");
+    if (batch == 0 || h_in == 0 || w_in == 0) return OPA_OK;
+    hipError_t e = launch_conv3x3_f32x3(x_dev, batch, h_in, w_in, c_in, stride, dilation, (const unsigned short*)w3_dev, bias_dev, out_dev,
+                                        c_out, relu, terms, (hipStream_t)stream);
     if (e != hipSuccess) return fail_hip(e, "conv3x3_f32x3");
     prof_mark((hipStream_t)stream, "conv3x3_f32x3_kernel");
+    return OPA_OK;
+}
+
+int opa_conv3x3_f32x3(const float* x_dev, const void* w3_dev, const float* bias_dev, float* out_dev, int32_t batch, int32_t h_in,
+                      int32_t w_in, int32_t c_in, int32_t c_out, int32_t stride, int32_t relu, int32_t terms, void* stream) {
+    if (batch <= 0 || h_in <= 0 || w_in <= 0)        // (this entry point has always refused an empty tensor)
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_conv3x3_f32x3: bad arguments");
+    return conv3x3_f32x3("opa_conv3x3_f32x3", x_dev, w3_dev, bias_dev, out_dev, batch, h_in, w_in, c_in, c_out, stride, 1, relu, terms, stream);
+}
+
+int opa_conv3x3_dilated_f32x3(const float* x_dev, const void* w3_dev, const float* bias_dev, float* out_dev, int32_t batch, int32_t h_in,
+                              int32_t w_in, int32_t c_in, int32_t c_out, int32_t stride, int32_t dilation, int32_t relu, int32_t terms,
+                              void* stream) {
+    return conv3x3_f32x3("opa_conv3x3_dilated_f32x3", x_dev, w3_dev, bias_dev, out_dev, batch, h_in, w_in, c_in, c_out, stride, dilation,
+                         relu, terms, stream);
+}
+
+int opa_maxpool3x3_bias_act(const void* x_dev, const void* bias_dev, void* out_dev, int32_t dtype, int32_t batch, int32_t h, int32_t w,
+                            int32_t c, int32_t stride, int32_t relu, void* stream) {
+    if (!x_dev || !out_dev || batch < 0 || h < 0 || w < 0 || c <= 0)
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_maxpool3x3_bias_act: bad arguments");
+    if (dtype != 0 && dtype != 2) return fail(OPA_ERR_INVALID_ARGUMENT, "opa_maxpool3x3_bias_act: dtype must be 0 (float32) or 2 (bfloat16)");
+    if (stride != 2) return fail(OPA_ERR_INVALID_ARGUMENT, "opa_maxpool3x3_bias_act: the stride must be 2");
+    if (c % 8 != 0) return fail(OPA_ERR_INVALID_ARGUMENT, "opa_maxpool3x3_bias_act: c must be a multiple of 8");
+    if (((uintptr_t)x_dev | (uintptr_t)out_dev | (uintptr_t)bias_dev) & 15)
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_maxpool3x3_bias_act: pointers must be 16-B aligned");
+    // 32-bit vector indices in the kernel, one thread per output vector
+    if ((double)batch * h * w * c * (dtype == 0 ? 4.0 : 2.0) >= 2147483648.0)
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_maxpool3x3_bias_act: the activation must be smaller than 2 GB (32-bit offsets)");
+    if (batch == 0 || h == 0 || w == 0) return OPA_OK;
+    if (maxpool3x3_blocks(batch, h, w, c) > 0x7fffffffll)
+        return fail(OPA_ERR_INVALID_ARGUMENT, "opa_maxpool3x3_bias_act: too many output vectors for grid.x");
+    hipError_t e = launch_maxpool3x3(x_dev, bias_dev, out_dev, dtype, batch, h, w, c, relu, (hipStream_t)stream);
+    if (e != hipSuccess) return fail_hip(e, "maxpool3x3_bias_act");
+    prof_mark((hipStream_t)stream, "maxpool3x3s2_kernel");
     return OPA_OK;
 }
 

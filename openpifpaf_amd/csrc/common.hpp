@@ -267,8 +267,12 @@ hipError_t launch_gemm2_f32x3_bias_act(const float* A1, int K1, const float* A2,
                                        hipStream_t st, const float* a_bias);
 hipError_t launch_convrows_f32x3(const float* x, int batch, int hp, int wp, int pix, int ho, int wo, int stride, int ntaps, int tap_floats,
                                  const unsigned short* W3, const float* bias, float* out, int N, int relu, int terms, hipStream_t st);
-hipError_t launch_conv3x3_f32x3(const float* x, int batch, int hi, int wi, int C, int stride, const unsigned short* W3,
+hipError_t launch_conv3x3_f32x3(const float* x, int batch, int hi, int wi, int C, int stride, int dilation, const unsigned short* W3,
                                 const float* bias, float* out, int N, int relu, int terms, hipStream_t st);
+// out = maxpool3x3(act(x + bias)), stride 2, padding 1, channels-last [B, H, W, C] -> [B, ho, wo, C] (pool.hip); dtype 0 float32,
+// 2 bfloat16; bias null or [C] of that dtype; C % 8 == 0.  The caller checks the sizes (maxpool3x3_blocks < 2^31, 32-bit offsets).
+long long maxpool3x3_blocks(int B, int H, int W, int C);
+hipError_t launch_maxpool3x3(const void* x, const void* bias, void* out, int dtype, int B, int H, int W, int C, int relu, hipStream_t st);
 hipError_t launch_gemm_unit_f32x3(const float* A, int lda, const unsigned short* W3, const float* bias, const float* partner, int ldp,
                                   float* out, int M, int N, int K, int relu, int terms, hipStream_t st);
 // ... with an activation code (0 none, 1 ReLU, 2 hardswish) and optionally a residual [M, N] with `ldr` floats between rows

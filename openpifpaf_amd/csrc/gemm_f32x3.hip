@@ -78,14 +78,16 @@ __device__ __forceinline__ int x3_lds(int row, int k) {
 // is neither written nor read back.  Columns [0, K1) come from A (row length K1), [K1, K) from A2 (row length K - K1).
 // NINE activations along K (SRC = 2): a 3x3 convolution with padding 1 and any stride as an implicit GEMM -- column block
 // t = 3 ky + kx of K holds the C channels of input pixel (stride * oy - 1 + ky, stride * ox - 1 + kx); a pixel in the padding is
-// requested beyond the end of the buffer, which a buffer load answers with zeros (one bit per row and tap decides).
+// requested beyond the end of the buffer, which a buffer load answers with zeros (one bit per row and tap decides).  With a
+// dilation d (padding d) the pixel is (stride * oy - d + d ky, stride * ox - d + d kx): the same three expressions times d.
 struct X3Second {
     const float* A2;           // [B, hi, wi, K - K1] channels-last, or null
     int K1;                    // columns of the first activation (a multiple of the K-step)
     int ho_wo, wo, hi_wi, wi, stride;
     int hi, C, batch;          // (SRC = 2) input rows, floats per tap (a multiple of the K-step), images
     int pix, taps_x, ntaps, padded;   // (SRC = 2) floats per input pixel; taps per window row; taps; 1: the input is padded in
-                               // memory (window origin = (stride oy, stride ox), every tap valid), 0: padding 1 by the tap mask
+                               // memory (window origin = (stride oy, stride ox), every tap valid), 0: padding `dil` by the tap mask
+    int dil;                   // (SRC = 2, not padded) dilation d: tap (ky, kx) reads input pixel (stride oy - d + d ky, stride ox - d + d kx)
     int lda, ldp, n_real, k_real;     // (UNIT) floats between rows of A and of the partner; the columns that exist of N and K
 };
 
@@ -223,9 +225,9 @@ __global__ __launch_bounds__(256, OPA_X3_WGS) void gemm_f32x3_bias_act_kernel(
     constexpr bool TWO = SRC == 1, TAPS = SRC == 2;
     const int rows_here = M - m0 < kX3BM ? M - m0 : kX3BM;
     const int KA = TWO ? sec.K1 : TAPS ? sec.C : UNIT ? sec.lda : K;      // row length of the first activation (UNIT: its row pitch)
-    // (TAPS: the whole tensor, from wi + 1 pixels BEFORE its start -- the window of output pixel (oy, ox) begins at input pixel
-    //  (stride oy - 1, stride ox - 1); what lies before the tensor is only ever asked for by rows whose tap bit is clear)
-    const int shift = TAPS && !sec.padded ? (sec.wi + 1) * sec.pix : 0;
+    // (TAPS: the whole tensor, from d (wi + 1) pixels BEFORE its start -- the window of output pixel (oy, ox) begins at input pixel
+    //  (stride oy - d, stride ox - d); what lies before the tensor is only ever asked for by rows whose tap bit is clear)
+    const int shift = TAPS && !sec.padded ? sec.dil * (sec.wi + 1) * sec.pix : 0;
     const float* a1_base = TAPS ? A - (size_t)shift : A + (size_t)m0 * KA;
     const int a1_bytes = TAPS ? (int)(((size_t)sec.batch * sec.hi_wi * sec.pix + shift) * 4)
                        : UNIT ? (int)(((size_t)(rows_here - 1) * KA + sec.k_real) * 4) : (int)((size_t)rows_here * KA * 4);
@@ -264,7 +266,7 @@ __global__ __launch_bounds__(256, OPA_X3_WGS) void gemm_f32x3_bias_act_kernel(
             if (sec.padded) vmask[p] = 0xffffffffu;
             else
                 for (int t = 0; t < sec.ntaps; t++) {
-                    const int iy = oy * sec.stride - 1 + t / sec.taps_x, ix = ox * sec.stride - 1 + t % sec.taps_x;
+                    const int iy = oy * sec.stride - sec.dil + sec.dil * (t / sec.taps_x), ix = ox * sec.stride - sec.dil + sec.dil * (t % sec.taps_x);
                     if (iy >= 0 && iy < sec.hi && ix >= 0 && ix < sec.wi) vmask[p] |= 1u << t;
                 }
         }
@@ -280,7 +282,8 @@ __global__ __launch_bounds__(256, OPA_X3_WGS) void gemm_f32x3_bias_act_kernel(
     auto fetch_a = [&](f32x4_t (&ra)[NPA], int k0) {      // global -> registers for K-step k0 (with the operand prologue)
         if constexpr (TAPS) {                  // tap t = k0 / C: a uniform shift of every row's window origin
             const int t = k0 / KA, kc = k0 - t * KA;
-            const int soff = (((t / sec.taps_x) * sec.wi + t % sec.taps_x) * sec.pix + kc) * 4;
+            // (unsigned: the offset of a tap that no row can reach -- a dilation beyond the image -- may wrap; its bit is clear in every row)
+            const int soff = (int)((((unsigned)(sec.dil * (t / sec.taps_x)) * (unsigned)sec.wi + (unsigned)(sec.dil * (t % sec.taps_x))) * (unsigned)sec.pix + (unsigned)kc) * 4u);
 #pragma unroll
             for (int p = 0; p < NPA; p++)
                 ra[p] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, (vmask[p] >> t) & 1u ? pa[p] : 0xFFFFFFF0u, soff, 0));
@@ -493,7 +496,7 @@ static hipError_t launch_x3_terms(const float* A, const unsigned short* W3, cons
 hipError_t launch_gemm_f32x3_bias_act(const float* A, const unsigned short* W3, const float* bias, const float* res, float* out,
                                       int M, int N, int K, int relu, int terms, hipStream_t st, const float* a_bias) {
     X3Second none; none.A2 = nullptr; none.K1 = K; none.ho_wo = none.wo = none.hi_wi = none.wi = none.stride = 1; none.hi = 1; none.C = 0; none.batch = 1;
-    none.pix = 1; none.taps_x = 1; none.ntaps = 1; none.padded = 0; none.lda = none.ldp = none.n_real = none.k_real = 0;
+    none.pix = 1; none.taps_x = 1; none.ntaps = 1; none.padded = 0; none.dil = 1; none.lda = none.ldp = none.n_real = none.k_real = 0;
     if (terms == 6) return launch_x3_terms<6>(A, W3, bias, res, out, M, N, K, relu, st, a_bias, none);
     return launch_x3_terms<9>(A, W3, bias, res, out, M, N, K, relu, st, a_bias, none);
 }
@@ -504,7 +507,7 @@ hipError_t launch_gemm2_f32x3_bias_act(const float* A1, int K1, const float* A2,
                                        hipStream_t st, const float* a_bias) {
     const int ho = (hi - 1) / stride + 1, wo = (wi - 1) / stride + 1;
     X3Second sec; sec.A2 = A2; sec.K1 = K1; sec.ho_wo = ho * wo; sec.wo = wo; sec.hi_wi = hi * wi; sec.wi = wi; sec.stride = stride;
-    sec.hi = hi; sec.C = 0; sec.batch = batch; sec.pix = 1; sec.taps_x = 1; sec.ntaps = 1; sec.padded = 0; sec.lda = sec.ldp = sec.n_real = sec.k_real = 0;
+    sec.hi = hi; sec.C = 0; sec.batch = batch; sec.pix = 1; sec.taps_x = 1; sec.ntaps = 1; sec.padded = 0; sec.dil = 1; sec.lda = sec.ldp = sec.n_real = sec.k_real = 0;
     const int M = batch * ho * wo, K = K1 + K2;
     if (terms == 6) return launch_x3_terms<6>(A1, W3, bias, nullptr, out, M, N, K, relu, st, a_bias, sec);
     return launch_x3_terms<9>(A1, W3, bias, nullptr, out, M, N, K, relu, st, a_bias, sec);
@@ -530,7 +533,7 @@ static hipError_t launch_unit_bn(const float* a, const unsigned short* w, const 
 // tile with nine terms does not fit the register file (the existing instantiations spill 8 registers), so nine terms take 64.
 static X3Second unit_sec(int lda, int ldp, int N, int K) {
     X3Second sec; sec.A2 = nullptr; sec.K1 = K; sec.ho_wo = sec.wo = sec.hi_wi = sec.wi = sec.stride = 1; sec.hi = 1; sec.C = 0; sec.batch = 1;
-    sec.pix = 1; sec.taps_x = 1; sec.ntaps = 1; sec.padded = 0; sec.lda = lda; sec.ldp = ldp; sec.n_real = N; sec.k_real = K;
+    sec.pix = 1; sec.taps_x = 1; sec.ntaps = 1; sec.padded = 0; sec.dil = 1; sec.lda = lda; sec.ldp = ldp; sec.n_real = N; sec.k_real = K;
     return sec;
 }
 
@@ -587,13 +590,13 @@ hipError_t UnitLaunch::operator()(int Np, int Kp) const {
     return launch_unit_act_bn<BN, TERMS>(a, w, b, third, residual, o, M, Np, Kp, act, st, sec);
 }
 
-// 3x3 convolution, padding 1, stride s: out[B, ho, wo, N] = act(im2col(x) * W3^T + bias), x [B, hi, wi, C] channels-last,
-// W3 = split_weight of the weight as [N, (ky, kx, c)] ([3][N][9 C]); C % 32 == 0, 9 C % 64 == 0, tensor < 2 GB
-hipError_t launch_conv3x3_f32x3(const float* x, int batch, int hi, int wi, int C, int stride, const unsigned short* W3,
+// 3x3 convolution, dilation d, padding d, stride s: out[B, ho, wo, N] = act(im2col(x) * W3^T + bias), x [B, hi, wi, C] channels-last,
+// W3 = split_weight of the weight as [N, (ky, kx, c)] ([3][N][9 C]); C % 32 == 0, 9 C % 64 == 0, tensor + d (wi + 1) pixels < 2 GB
+hipError_t launch_conv3x3_f32x3(const float* x, int batch, int hi, int wi, int C, int stride, int dilation, const unsigned short* W3,
                                 const float* bias, float* out, int N, int relu, int terms, hipStream_t st) {
     const int ho = (hi - 1) / stride + 1, wo = (wi - 1) / stride + 1;
     X3Second sec; sec.A2 = nullptr; sec.K1 = C; sec.ho_wo = ho * wo; sec.wo = wo; sec.hi_wi = hi * wi; sec.wi = wi; sec.stride = stride;
-    sec.hi = hi; sec.C = C; sec.batch = batch; sec.pix = C; sec.taps_x = 3; sec.ntaps = 9; sec.padded = 0; sec.lda = sec.ldp = sec.n_real = sec.k_real = 0;
+    sec.hi = hi; sec.C = C; sec.batch = batch; sec.pix = C; sec.taps_x = 3; sec.ntaps = 9; sec.padded = 0; sec.dil = dilation; sec.lda = sec.ldp = sec.n_real = sec.k_real = 0;
     const int M = batch * ho * wo, K = 9 * C;
     if (terms == 6) return launch_x3_terms<6>(x, W3, bias, nullptr, out, M, N, K, relu, st, nullptr, sec);
     return launch_x3_terms<9>(x, W3, bias, nullptr, out, M, N, K, relu, st, nullptr, sec);
@@ -606,7 +609,7 @@ hipError_t launch_conv3x3_f32x3(const float* x, int batch, int hi, int wi, int C
 hipError_t launch_convrows_f32x3(const float* x, int batch, int hp, int wp, int pix, int ho, int wo, int stride, int ntaps, int tap_floats,
                                  const unsigned short* W3, const float* bias, float* out, int N, int relu, int terms, hipStream_t st) {
     X3Second sec; sec.A2 = nullptr; sec.K1 = tap_floats; sec.ho_wo = ho * wo; sec.wo = wo; sec.hi_wi = hp * wp; sec.wi = wp; sec.stride = stride;
-    sec.hi = hp; sec.C = tap_floats; sec.batch = batch; sec.pix = pix; sec.taps_x = 1; sec.ntaps = ntaps; sec.padded = 1; sec.lda = sec.ldp = sec.n_real = sec.k_real = 0;
+    sec.hi = hp; sec.C = tap_floats; sec.batch = batch; sec.pix = pix; sec.taps_x = 1; sec.ntaps = ntaps; sec.padded = 1; sec.dil = 1; sec.lda = sec.ldp = sec.n_real = sec.k_real = 0;
     const int M = batch * ho * wo, K = ntaps * tap_floats;
     if (terms == 6) return launch_x3_terms<6>(x, W3, bias, nullptr, out, M, N, K, relu, st, nullptr, sec);
     return launch_x3_terms<9>(x, W3, bias, nullptr, out, M, N, K, relu, st, nullptr, sec);

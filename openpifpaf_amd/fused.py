@@ -6,7 +6,8 @@ kernel's contract), the operands derived from the module's parameters (split, pa
 the choice is made once per shape and remembered in one table (``_CHOICE``, shipped as ``conv1x1_pinned.json``): ``conv_bias_act``
 and ``pick`` say what the candidates are, ``_decide`` makes the choice.  In this order: the launcher, the switches, the choice
 table and the decision, the derived operands, then the routes by kernel family -- the epilogue passes, the 1x1 GEMMs, the
-split-operand convolutions (pair, 3x3, stem, heads, unit mode), the grouped and the depthwise stencils, squeeze-and-excitation."""
+split-operand convolutions (pair, 3x3 and dilated 3x3, stem, heads, unit mode), the input max-pool, the grouped and the depthwise
+stencils, squeeze-and-excitation."""
 import os
 
 import torch
@@ -544,6 +545,33 @@ def conv3x3_bias_act_x3(conv, x, bias, relu=True):
     return out
 
 
+def conv3x3_dilated_x3_supported(conv, x, bias):
+    """Can ``conv3x3_dilated_bias_act_x3(conv, x, bias)`` run?  As ``conv3x3_x3_supported``, for a 3x3 convolution with a square
+    dilation d >= 1 and padding d (the kernel's buffer begins d rows + d pixels before the tensor: that share counts towards 2 GB)."""
+    d = conv.dilation[0]
+    return (X3_CONV3 and X3_TERMS in (6, 9) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and x.is_contiguous(memory_format=torch.channels_last) and conv.kernel_size == (3, 3) and d >= 1
+            and conv.dilation == (d, d) and conv.padding == (d, d)
+            and conv.stride[0] == conv.stride[1] and conv.groups == 1 and conv.bias is None
+            and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0 and x.shape[1] == conv.in_channels
+            and conv.weight.dtype == torch.float32 and conv.weight.device == x.device
+            and x.data_ptr() % 16 == 0 and bias.dtype == torch.float32 and bias.is_contiguous() and bias.data_ptr() % 16 == 0
+            and x.numel() > 0 and (x.shape[0] * x.shape[2] * x.shape[3] + d * (x.shape[3] + 1)) * x.shape[1] * 4 < 2 ** 31)
+
+
+def conv3x3_dilated_bias_act_x3(conv, x, bias, relu=True):
+    """``act(conv(x) + bias)`` for a 3x3 convolution with dilation d, padding d and any stride (reference
+    ``network/basenetworks.py:121-135``: the convolutions of block 5 under ``--resnet-block5-dilation``) as an implicit GEMM of the
+    split-operand kernel (``opa_conv3x3_dilated_f32x3``: ``conv3x3_bias_act_x3``'s kernel, whose taps step by d) -- float32 in and out."""
+    w3 = _split_weight_3x3_of(conv)
+    B, C, H, W = x.shape
+    s = conv.stride[0]
+    out = _empty_nhwc(x, conv.out_channels, _out_hw(x, s), torch.float32)
+    _launch('opa_conv3x3_dilated_f32x3', _ptr(x), _ptr(w3), _ptr(bias), _ptr(out), B, H, W, C, conv.out_channels, s,
+            conv.dilation[0], int(bool(relu)), int(X3_TERMS))
+    return out
+
+
 def stem_x3_supported(conv, x, bias):
     return (X3_STEM and X3_TERMS in (6, 9) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and conv.kernel_size == (7, 7)
             and conv.stride == (2, 2) and conv.padding == (3, 3) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
@@ -637,7 +665,7 @@ def conv1x1_unit_x3(conv, x, relu=True, partner=None, residual=None, act=None):
     return out
 
 
-# ---- the grouped and the depthwise stencils ---------------------------------------------------------------------------------------------
+# ---- the input max-pool, the grouped and the depthwise stencils ---------------------------------------------------------------------------------------------
 
 GCONV_WIDTHS = (4, 8, 16, 32, 64)            # channels per group the kernel is instantiated for
 
@@ -670,6 +698,29 @@ def gconv3x3_bias_act(conv, x, bias, relu=True):
     out = _empty_nhwc(x, C, _out_hw(x, s), torch.float32)
     _launch('opa_gconv3x3_bias_act_f32', _ptr(x), C, _ptr(wt), _ptr(bias), _ptr(out), C, B, H, W, C, C // conv.groups, s,
             int(bool(relu)))
+    return out
+
+
+def maxpool3x3_supported(x, bias=None):
+    """Can ``maxpool3x3_bias_act_(x, bias)`` run?  A dense channels-last float32 or bfloat16 tensor on the GPU with a multiple of 8
+    channels, smaller than 2 GB, not followed by autograd; ``bias`` of ``x``'s dtype, one element per channel."""
+    return (x.is_cuda and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16) and not (torch.is_grad_enabled() and x.requires_grad)
+            and x.is_contiguous(memory_format=torch.channels_last) and x.shape[1] % 8 == 0 and x.data_ptr() % 16 == 0
+            and 0 < x.numel() * x.element_size() < 2 ** 31
+            and (bias is None or (bias.dtype == x.dtype and bias.device == x.device and bias.is_contiguous()
+                                  and bias.numel() == x.shape[1] and bias.data_ptr() % 16 == 0))
+            and _lib.available())
+
+
+def maxpool3x3_bias_act_(x, bias=None, relu=False, out=None):
+    """``max_pool2d(act(x + bias), 3, 2, 1)`` -- the input max-pool of a ResNet (reference ``network/basenetworks.py:85-93``) with the
+    stem's bias and ReLU in front of it -- in one HIP kernel (``opa_maxpool3x3_bias_act``): ``torch.equal`` to what the torch ops compute.
+    ``bias`` None: no addition.  ``x`` is read only; ``out``: a dense channels-last tensor to write into (tests).
+    ``maxpool3x3_supported`` says whether this can run."""
+    B, C, H, W = x.shape
+    if out is None:
+        out = _empty_nhwc(x, C, _out_hw(x, 2))
+    _launch('opa_maxpool3x3_bias_act', _ptr(x), _ptr(bias), _ptr(out), _DTYPES[x.dtype], B, H, W, C, 2, int(bool(relu)))
     return out
 
 

@@ -7,7 +7,9 @@ follows the reference so that the field tensors have the reference's shapes:
 
 * ``Resnet``: torchvision ResNet topology with the input max-pool removed, so
   the overall stride is 16 (reference ``network/basenetworks.py:71-150``,
-  factories ``network/factory.py:51-57``).
+  factories ``network/factory.py:51-57``); the reference's options put the pool
+  back, change the stem's stride, add a second input convolution, dilate
+  block 5 or drop it (``network/basenetworks.py:79-142``).
 * ``ShuffleNetV2K``: reference ``network/basenetworks.py:186-355`` (k16: stages
   [4,8,4], channels [24,348,696,1392,1392]; k30: [8,16,6], [32,512,1024,2048,2048]).
 * ``MobileNetV3``: torchvision's ``mobilenet_v3_large`` / ``mobilenet_v3_small`` feature extractors with the stride of the first
@@ -84,6 +86,12 @@ class _Bottleneck(nn.Module):
                 out = fused.pick('conv3', fused.out_pixels(h, s), 9 * h.shape[1], self.conv2.out_channels, s > 1, False,
                                  lambda: fused.conv3x3_bias_act_x3(self.conv2, h, self.fb2, True),
                                  lambda: fused.bias_act_(self.conv2(h), self.fb2))
+            elif self.conv2.dilation != (1, 1) and fused.conv3x3_dilated_x3_supported(self.conv2, out, self.fb2):
+                h = out                                                   # ... float32 dilated (block 5 under block5_dilation): the same
+                s, d = self.conv2.stride[0], self.conv2.dilation[0]      # implicit GEMM with its taps d apart, against MIOpen + the pass
+                out = fused.pick('conv3d%d' % d, fused.out_pixels(h, s), 9 * h.shape[1], self.conv2.out_channels, s > 1, False,
+                                 lambda: fused.conv3x3_dilated_bias_act_x3(self.conv2, h, self.fb2, True),
+                                 lambda: fused.bias_act_(self.conv2(h), self.fb2))
             elif fused.gconv3x3_supported(self.conv2, out, self.fb2):    # ... float32 grouped (ResNeXt): one stencil kernel,
                 out = fused.gconv3x3_bias_act(self.conv2, out, self.fb2, True)        # bias + ReLU inside
             else:
@@ -139,13 +147,36 @@ class _BasicBlock(nn.Module):
     wino_u1 = property(lambda self: self._wino_u(1), doc='like ``_Bottleneck.wino_u``, of ``conv1``')
     wino_u2 = property(lambda self: self._wino_u(2), doc='like ``_Bottleneck.wino_u``, of ``conv2``')
 
+    def _dilated(self, conv, x, bias, identity=None):
+        """``relu(conv(x) + bias (+ identity))`` for a dilated 3x3 convolution the split-operand kernel takes, else None.  The kernel
+        has no residual operand: with an identity it adds a zero bias and the epilogue pass adds the rest, as behind MIOpen."""
+        if conv.dilation == (1, 1) or not fused.conv3x3_dilated_x3_supported(conv, x, bias):
+            return None
+        s, d = conv.stride[0], conv.dilation[0]
+        if identity is None:
+            def run_x3():
+                return fused.conv3x3_dilated_bias_act_x3(conv, x, bias, True)
+        else:
+            zero = fused.derived(conv, '_opa_zero_bias', (conv.weight,), lambda: torch.zeros_like(bias))
+
+            def run_x3():
+                return fused.bias_act_(fused.conv3x3_dilated_bias_act_x3(conv, x, zero, False), bias, identity)
+        return fused.pick('conv3d%d' % d, fused.out_pixels(x, s), 9 * x.shape[1], conv.out_channels, s > 1, identity is not None,
+                          run_x3, lambda: fused.bias_act_(conv(x), bias, identity))
+
     def forward(self, x):
         if self.fused:
             identity = x if self.downsample is None else self.downsample[0](x)
-            if winograd.takes(self.conv1, x, self._wino[0]):  # bias + ReLU in the kernel's output transform
+            out = self._dilated(self.conv1, x, self.fb1)                  # (block 5 under block5_dilation)
+            if out is not None:
+                pass
+            elif winograd.takes(self.conv1, x, self._wino[0]):  # bias + ReLU in the kernel's output transform
                 out = winograd.run(self.conv1, x, bias=self.fb1, relu=True)
             else:
                 out = fused.bias_act_(self.conv1(x), self.fb1)
+            last = self._dilated(self.conv2, out, self.fb2, identity)
+            if last is not None:
+                return last
             return fused.bias_act_(winograd.conv_or_fallback(self.conv2, out, self._wino[1]), self.fb2, identity)
         identity = x if self.downsample is None else self.downsample(x)
         out = self.relu(self.bn1(self.conv1(x)))
@@ -161,9 +192,36 @@ class BaseNetwork(nn.Module):
         self.out_features = out_features
 
 
+def _dilate_(block5, dilation):
+    """Block 5 with dilated convolutions instead of a stride (reference ``network/basenetworks.py:121-135``): every convolution gets
+    stride 1, the downsampling 1x1 included, every other one dilation = padding = ``dilation`` (k x k: (k - 1) / 2 times that)."""
+    for m in block5.modules():
+        if not isinstance(m, nn.Conv2d):
+            continue
+        m.stride = (1, 1)
+        if m.kernel_size[0] == 1:
+            continue
+        m.dilation = (dilation, dilation)
+        m.padding = ((m.kernel_size[0] - 1) // 2 * dilation,) * 2
+    return block5
+
+
 class Resnet(BaseNetwork):
-    """ResNet-18/34/50/101/152 and ResNeXt-50 (32x4d) / -101 (32x8d) without the input max-pool: stride 16 (reference
-    ``network/factory.py:51-79``)."""
+    """ResNet-18/34/50/101/152 and ResNeXt-50 (32x4d) / -101 (32x8d) (reference ``network/factory.py:51-79``) with the reference's
+    five options (``network/basenetworks.py:71-183``); each keyword defaults to the class attribute of its name, which
+    ``configure`` sets from the command line.  The defaults give stride 16: no input max-pool, stem of stride 2, no dilation.
+
+    * ``pool0_stride``: 0 removes the input max-pool; else ``input_block.3 = MaxPool2d(3, pool0_stride, 1)``, the overall stride
+      times 2 (``int(stride * 2 / pool0_stride)`` for a stride other than 2, as the reference counts).
+    * ``input_conv_stride`` s: the stem's stride; the overall stride follows it, ``stride * s / 2`` (8 for s = 1: what the network
+      does.  The reference writes ``int(stride * 2 / s)`` here, 32 for s = 1, which no head could decode with).
+    * ``input_conv2_stride`` s: ``input_block.3 = Sequential(Conv2d(64, 64, 3, s, 1), BatchNorm2d, ReLU)`` in place of the pool (refused
+      together with ``pool0_stride``), the overall stride times s (the reference builds this convolution with stride 2 whatever s
+      is and counts 2: the same for s = 2, the one value it documents).
+    * ``block5_dilation`` d != 1: see ``_dilate_``; the overall stride is halved.
+    * ``remove_last_block``: no block 5; the stride and ``out_features`` are halved.  The reference's own ``forward`` would call
+      ``None`` here: this one skips the block, the evident intent.  (With ``block5_dilation`` the reference fails on the missing
+      block when it is built; here the combination is refused.)"""
     CONFIGS = {
         'resnet18': (_BasicBlock, [2, 2, 2, 2]),
         'resnet34': (_BasicBlock, [3, 4, 6, 3]),
@@ -173,21 +231,77 @@ class Resnet(BaseNetwork):
         'resnext50': (_Bottleneck, [3, 4, 6, 3], 32, 4),          # (..., groups, base width)
         'resnext101': (_Bottleneck, [3, 4, 23, 3], 32, 8),
     }
+    pool0_stride = 0
+    input_conv_stride = 2
+    input_conv2_stride = 0
+    block5_dilation = 1
+    remove_last_block = False
+    OPTIONS = ('pool0_stride', 'input_conv_stride', 'input_conv2_stride', 'block5_dilation', 'remove_last_block')
 
-    def __init__(self, name='resnet50'):
+    def __init__(self, name='resnet50', *, pool0_stride=None, input_conv_stride=None, input_conv2_stride=None, block5_dilation=None,
+                 remove_last_block=None):
+        given = dict(zip(self.OPTIONS, (pool0_stride, input_conv_stride, input_conv2_stride, block5_dilation, remove_last_block)))
+        pool0_stride, input_conv_stride, input_conv2_stride, block5_dilation, remove_last_block = (
+            getattr(type(self), k) if v is None else v for k, v in given.items())
         block, layers, *grouped = self.CONFIGS[name]
-        super().__init__(name, stride=16, out_features=512 * block.expansion)
+        stride, out_features = 32, 512 * block.expansion             # (the reference's arithmetic, step by step)
+        if pool0_stride:
+            if pool0_stride != 2:
+                stride = int(stride * 2 / pool0_stride)
+        else:
+            stride //= 2
+        if input_conv_stride != 2:
+            stride = stride * input_conv_stride // 2
+        if input_conv2_stride:
+            assert not pool0_stride, 'the second input convolution is a replacement for the input max-pool'
+            stride *= input_conv2_stride
+        if remove_last_block:
+            assert block5_dilation == 1, 'there is no block 5 to dilate'
+            stride //= 2
+            out_features //= 2
+        if block5_dilation != 1:
+            stride //= 2
+        super().__init__(name, stride=stride, out_features=out_features)
+        self.pool0_stride, self.input_conv_stride, self.input_conv2_stride = pool0_stride, input_conv_stride, input_conv2_stride
+        self.block5_dilation, self.remove_last_block = block5_dilation, remove_last_block
         self._block_args = dict(zip(('groups', 'base_width'), grouped))
         self.inplanes = 64
-        self.input_block = nn.Sequential(
-            nn.Conv2d(3, 64, 7, 2, 3, bias=False), nn.BatchNorm2d(64), nn.ReLU(inplace=True))
+        input_modules = [nn.Conv2d(3, 64, 7, input_conv_stride, 3, bias=False), nn.BatchNorm2d(64), nn.ReLU(inplace=True)]
+        if pool0_stride:
+            input_modules.append(nn.MaxPool2d(3, pool0_stride, 1))
+        if input_conv2_stride:
+            input_modules.append(nn.Sequential(
+                nn.Conv2d(64, 64, 3, input_conv2_stride, 1, bias=False), nn.BatchNorm2d(64), nn.ReLU(inplace=True)))
+        self.input_block = nn.Sequential(*input_modules)
         self.block2 = self._make_layer(block, 64, layers[0], 1)
         self.block3 = self._make_layer(block, 128, layers[1], 2)
         self.block4 = self._make_layer(block, 256, layers[2], 2)
-        self.block5 = self._make_layer(block, 512, layers[3], 2)
+        self.block5 = None if remove_last_block else self._make_layer(block, 512, layers[3], 2)
+        if block5_dilation != 1:
+            _dilate_(self.block5, block5_dilation)
         for m in self.modules():
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
+
+    @classmethod
+    def cli(cls, parser):
+        """The reference's flags (``network/basenetworks.py:152-174``; nothing is pretrained here, so no ``--resnet-no-pretrain``)."""
+        group = parser.add_argument_group('ResNet')
+        group.add_argument('--resnet-pool0-stride', default=cls.pool0_stride, type=int,
+                           help='stride of zero removes the pooling op')
+        group.add_argument('--resnet-input-conv-stride', default=cls.input_conv_stride, type=int,
+                           help='stride of the input convolution')
+        group.add_argument('--resnet-input-conv2-stride', default=cls.input_conv2_stride, type=int,
+                           help='stride of the optional 2nd input convolution')
+        group.add_argument('--resnet-block5-dilation', default=cls.block5_dilation, type=int,
+                           help='use dilated convs in block5')
+        group.add_argument('--resnet-remove-last-block', default=False, action='store_true',
+                           help='create a network without the last block')
+
+    @classmethod
+    def configure(cls, args):
+        for option in cls.OPTIONS:             # (a namespace from a parser without these flags leaves the attributes as they are)
+            setattr(cls, option, getattr(args, 'resnet_' + option, getattr(cls, option)))
 
     def _make_layer(self, block, planes, blocks, stride):
         downsample = None
@@ -201,23 +315,55 @@ class Resnet(BaseNetwork):
         return nn.Sequential(*layers)
 
     def enable_fused_(self):
-        conv = self.input_block[0]
-        self.register_buffer('fb0', conv.bias.detach().clone())
-        conv.bias = None
+        """The folded biases of the stem and of the second input convolution become buffers (``fb0``, ``fb0_2``) that the fused
+        forward hands to whatever kernel applies them."""
+        convs = [('fb0', self.input_block[0])]
+        if self.input_conv2_stride:
+            convs.append(('fb0_2', self.input_block[3][0]))
+        for name, conv in convs:
+            self.register_buffer(name, conv.bias.detach().clone())
+            conv.bias = None
         self.fused = True
 
-    def forward(self, x):
-        if getattr(self, 'fused', False):
-            if fused.stem_x3_supported(self.input_block[0], x, self.fb0):     # float32: the stem as an implicit GEMM, bias + ReLU inside
-                conv, x0 = self.input_block[0], x
+    def _pooled(self, x, bias=None):
+        """The input max-pool of ``relu(x + bias)`` (``bias`` None: of ``x`` as it is): one HIP kernel for stride 2 where it takes the
+        tensor -- with a bias it REPLACES the epilogue pass -- else that pass and ``F.max_pool2d``."""
+        if self.pool0_stride == 2 and fused.maxpool3x3_supported(x, bias):
+            return fused.maxpool3x3_bias_act_(x, bias, relu=bias is not None)
+        return self.input_block[3](x if bias is None else fused.bias_act_(x, bias))
+
+    def _input_block_fused(self, x):
+        conv = self.input_block[0]
+        pool = bool(self.pool0_stride)
+        if fused.stem_x3_supported(conv, x, self.fb0):     # float32: the stem as an implicit GEMM, bias + ReLU inside
+            x0 = x
+            if pool:                                        # ... and the pool behind either side: torch's raw convolution hands its
+                x = fused.pick('stempool', fused.out_pixels(x0, 2), 256, conv.out_channels, True, False,       # epilogue to the pool kernel
+                               lambda: self._pooled(fused.stem7x7_bias_act_x3(conv, x0, self.fb0)),
+                               lambda: self._pooled(conv(x0), self.fb0))
+            else:
                 x = fused.pick('stem', fused.out_pixels(x0, 2), 256, conv.out_channels,
                                True, False, lambda: fused.stem7x7_bias_act_x3(conv, x0, self.fb0),
                                lambda: fused.bias_act_(conv(x0), self.fb0))
-            else:
-                x = fused.bias_act_(self.input_block[0](x), self.fb0)
+        elif pool:                                          # torch's raw convolution (bfloat16, a stem stride other than 2)
+            x = self._pooled(conv(x), self.fb0)
         else:
-            x = self.input_block(x)
-        return self.block5(self.block4(self.block3(self.block2(x))))
+            x = fused.bias_act_(conv(x), self.fb0)
+        if self.input_conv2_stride:
+            conv2, h = self.input_block[3][0], x
+            if fused.conv3x3_x3_supported(conv2, h, self.fb0_2):
+                s = conv2.stride[0]
+                x = fused.pick('conv3', fused.out_pixels(h, s), 9 * h.shape[1], conv2.out_channels, s > 1, False,
+                               lambda: fused.conv3x3_bias_act_x3(conv2, h, self.fb0_2, True),
+                               lambda: fused.bias_act_(conv2(h), self.fb0_2))
+            else:
+                x = fused.bias_act_(conv2(h), self.fb0_2)
+        return x
+
+    def forward(self, x):
+        x = self._input_block_fused(x) if getattr(self, 'fused', False) else self.input_block(x)
+        x = self.block4(self.block3(self.block2(x)))
+        return x if self.block5 is None else self.block5(x)
 
 
 def _channel_shuffle(x, groups=2):

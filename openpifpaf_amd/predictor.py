@@ -508,6 +508,7 @@ class Predictor:
         group.add_argument('--device-preprocess', default=False, action='store_true',
                            help='rescale, pad and normalise the uint8 frames on the GPU instead of with PIL on the host')
         group.add_argument('--basenet', default=cls.base_name, choices=sorted(network.BASE_FACTORIES))
+        network.Resnet.cli(parser)
 
     @classmethod
     def configure(cls, args: argparse.Namespace):
@@ -516,6 +517,7 @@ class Predictor:
         cls.fast_rescaling = getattr(args, 'fast_rescaling', cls.fast_rescaling)
         cls.device_preprocess = getattr(args, 'device_preprocess', cls.device_preprocess)
         cls.base_name = getattr(args, 'basenet', cls.base_name)
+        network.Resnet.configure(args)
         if getattr(args, 'device', None) is not None:
             cls.device = args.device
 
