@@ -273,10 +273,8 @@ hipError_t launch_conv3x3_f32x3(const float* x, int batch, int hi, int wi, int C
 // 2 bfloat16; bias null or [C] of that dtype; C % 8 == 0.  The caller checks the sizes (maxpool3x3_blocks < 2^31, 32-bit offsets).
 long long maxpool3x3_blocks(int B, int H, int W, int C);
 hipError_t launch_maxpool3x3(const void* x, const void* bias, void* out, int dtype, int B, int H, int W, int C, int relu, hipStream_t st);
-hipError_t launch_gemm_unit_f32x3(const float* A, int lda, const unsigned short* W3, const float* bias, const float* partner, int ldp,
-                                  float* out, int M, int N, int K, int relu, int terms, hipStream_t st);
-// ... with an activation code (0 none, 1 ReLU, 2 hardswish) and optionally a residual [M, N] with `ldr` floats between rows
-// (added before the activation; not together with a partner)
+// the unit mode (gemm_f32x3.hip) with an activation code (0 none, 1 ReLU, 2 hardswish) and optionally a residual [M, N] with `ldr`
+// floats between rows (added before the activation; not together with a partner)
 hipError_t launch_gemm_unit_act_f32x3(const float* A, int lda, const unsigned short* W3, const float* bias, const float* partner, int ldp,
                                       const float* residual, int ldr, float* out, int M, int N, int K, int act, int terms, hipStream_t st);
 hipError_t launch_gemm_f32_bias_act(const float* A, const float* W, const float* bias, const float* res, float* out,

@@ -552,11 +552,6 @@ struct UnitLaunch {
     template <int BN, int TERMS> hipError_t operator()(int Np, int Kp) const;
 };
 
-hipError_t launch_gemm_unit_f32x3(const float* A, int lda, const unsigned short* W3, const float* bias, const float* partner, int ldp,
-                                  float* out, int M, int N, int K, int relu, int terms, hipStream_t st) {
-    return unit_dispatch(N, K, terms, UnitLaunch{A, W3, bias, partner, false, out, M, relu ? 1 : 0, st, unit_sec(lda, ldp, N, K)});
-}
-
 // The unit mode's instantiations with hardswish or a residual (see x3_unit_epilogue's UX); `third` is the partner or the residual.
 template <int BN, int TERMS>
 static hipError_t launch_unit_act_bn(const float* a, const unsigned short* w, const float* b, const float* third, bool residual, float* o,

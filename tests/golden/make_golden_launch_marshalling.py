@@ -5,7 +5,7 @@ layer was rearranged (one launcher, one activation code): the test passes there 
 
 Two symbols are written under another name than that commit called them by, on purpose.  ``conv1x1_unit_x3`` called
 ``opa_gemm_unit_bias_act_f32x3`` where it had neither ``act`` nor a residual, and ``dwconv_bias_act`` called ``opa_dwconv_bias_act``
-without ``act``; both now always call the supersets ``opa_gemm_unit_act_f32x3`` / ``opa_dwconv_act``, which ``csrc/capi.hip``
+without ``act``; both now always call the supersets ``opa_gemm_unit_act_f32x3`` / ``opa_dwconv_act``, which ``csrc/capi_trunk.hip``
 forwards the old entry points to literally.  Those entries are generated from the supersets' argument lists (a null residual with
 pitch 0 put in; the activation code is ``int(bool(relu))``): ``test_launch_marshalling.canonical``, applied to whatever was recorded.
 

@@ -69,7 +69,7 @@ def recording():
 
 def canonical(name, row):
     """``opa_gemm_unit_bias_act_f32x3`` and ``opa_dwconv_bias_act`` are the calls of ``opa_gemm_unit_act_f32x3`` without a residual
-    and of ``opa_dwconv_act`` with the activation codes 0 / 1 (``csrc/capi.hip`` forwards them literally): a record of either
+    and of ``opa_dwconv_act`` with the activation codes 0 / 1 (``csrc/capi_trunk.hip`` forwards them literally): a record of either
     is read as the record of its superset, so that the golden file holds ONE spelling of these launches."""
     if name == 'opa_gemm_unit_bias_act_f32x3':
         return ['opa_gemm_unit_act_f32x3', row[:6] + ['null', 0] + row[6:]]
