@@ -483,6 +483,26 @@ int opa_conv3x3_dilated_f32x3(const float* x_dev, const void* w3_dev, const floa
 int opa_maxpool3x3_bias_act(const void* x_dev, const void* bias_dev, void* out_dev, int32_t dtype, int32_t batch, int32_t h, int32_t w,
                             int32_t c, int32_t stride, int32_t relu, void* stream);
 
+/* The same pass with torch's ceil_mode=True output sizes -- the three max-pools of SqueezeNet (reference
+ * network/basenetworks.py:461-487: MaxPool2d(3, 2, padding 1, ceil_mode=True)): ho = ceil((h - 1) / 2) + 1, one less if
+ * (ho - 1) * 2 >= h + 1 (never for this kernel size, stride and padding), i.e. the size above for odd h and one more for even h,
+ * whose last window holds row h - 1 alone; wo likewise.  Same kernel, same arguments, same checks in the same order. */
+int opa_maxpool3x3_ceil_bias_act(const void* x_dev, const void* bias_dev, void* out_dev, int32_t dtype, int32_t batch, int32_t h, int32_t w,
+                                 int32_t c, int32_t stride, int32_t relu, void* stream);
+
+/* Both expand convolutions of a SqueezeNet Fire module (reference network/basenetworks.py:461-487: torchvision's Fire) with their
+ * biases, ReLUs and the concatenation, one launch (csrc/fire.hip):
+ *     out[b, y, x, n]         = relu(bias[n]        + sum_c       h[b, y, x, c]           * W1[n, c])            n < c_e1
+ *     out[b, y, x, c_e1 + n]  = relu(bias[c_e1 + n] + sum_ky,kx,c h[b, y+ky-1, x+kx-1, c] * W3[n, c, ky, kx])    n < c_e3
+ * (outside the image: 0).  h_dev [batch, h, w, c_squeeze] and out_dev [batch, h, w, c_e1 + c_e3] channels-last float32; w_dev the
+ * split weights in the kernel's fragment order, 3 * (c_e1 + 9 * c_e3) * c_squeeze bfloat16 (openpifpaf_amd.fused.fire_weight_of);
+ * bias_dev [c_e1 + c_e3] float32.  Split-operand arithmetic as opa_gemm_bias_act_f32x3 (terms 6 or 9).  c_squeeze 16, 32, 48 or
+ * 64; c_e1 and c_e3 multiples of 64; pointers 16-B aligned; both tensors smaller than 2 GB (32-bit byte offsets); anything else:
+ * OPA_ERR_INVALID_ARGUMENT before any launch.  batch, h or w == 0: OPA_OK, nothing runs.  A NaN or +-Inf at pixel p of h gives NaN
+ * in every c_e1 channel at p and in every c_e3 channel at the pixels whose 3x3 window holds p, and changes no other output. */
+int opa_fire_expand_f32x3(const float* h_dev, const void* w_dev, const float* bias_dev, float* out_dev, int32_t batch, int32_t h, int32_t w,
+                          int32_t c_squeeze, int32_t c_e1, int32_t c_e3, int32_t terms, void* stream);
+
 /* A convolution whose window ROWS are the taps of the same implicit GEMM, on an input that is padded IN MEMORY: the 7x7 stride-2
  * stem of a ResNet (reference network/basenetworks.py:71-150) on a 4-channel, zero-padded copy of the image.  x_dev [B, hp, wp, pix]
  * (pix floats per pixel); output pixel (y, x) reads for tap t the tap_floats contiguous floats that begin at input pixel

@@ -7,11 +7,13 @@
 // ABI decision of its own.  What differs:
 //   null / alignment   opa_gemm_bias_act_bf16 and opa_gemm_pro_bias_act_bf16 do not test bias_dev's alignment, the float32 GEMMs do.
 //                      The Winograd entry points, opa_dwconv_*, opa_gconv3x3_* and opa_maxpool3x3_* accept a null bias.
+//                      opa_fire_expand_f32x3 tests all four pointers.
 //                      opa_dwconv_*, opa_channel_interleave and opa_head_epilogue test no alignment at all.  The unit mode asks
 //                      8 bytes of a_dev, partner_dev and residual_dev, 16 of the rest.  A null pointer is aligned everywhere.
 //   empty calls        m == 0 (opa_bias_act: rows == 0) is OPA_OK for the GEMMs; an empty batch, h or w is OPA_OK for
-//                      opa_conv3x3_dilated_f32x3, opa_maxpool3x3_bias_act and opa_gconv3x3_bias_act_f32, after every check that does
-//                      not need a size (the last two test their grid only behind it).  opa_conv3x3_f32x3, opa_gemm2_*,
+//                      opa_conv3x3_dilated_f32x3, opa_maxpool3x3_bias_act, opa_maxpool3x3_ceil_bias_act, opa_fire_expand_f32x3 and
+//                      opa_gconv3x3_bias_act_f32, after every check that does not need a size (all but the first test their grid
+//                      only behind it).  opa_conv3x3_f32x3, opa_gemm2_*,
 //                      opa_conv_rows_*, Winograd, dwconv, squeeze-excite, interleave and the head epilogue refuse empties.
 //   last error         a call that succeeds leaves opa_last_error's text as it was.
 //   marks              the entry points that pass a kernel's name to Entry::launched mark the profile here; the launchers of the
@@ -179,9 +181,10 @@ int opa_conv3x3_dilated_f32x3(const float* x_dev, const void* w3_dev, const floa
                          relu, terms, stream);
 }
 
-int opa_maxpool3x3_bias_act(const void* x_dev, const void* bias_dev, void* out_dev, int32_t dtype, int32_t batch, int32_t h, int32_t w,
-                            int32_t c, int32_t stride, int32_t relu, void* stream) {
-    const Entry E("opa_maxpool3x3_bias_act", stream);
+// opa_maxpool3x3_bias_act and opa_maxpool3x3_ceil_bias_act (`ceil_mode`: torch's ceil_mode=True output sizes, SqueezeNet's pools)
+static int maxpool3x3(const char* fn, const char* where, int ceil_mode, const void* x_dev, const void* bias_dev, void* out_dev, int32_t dtype,
+                      int32_t batch, int32_t h, int32_t w, int32_t c, int32_t stride, int32_t relu, void* stream) {
+    const Entry E(fn, stream);
     if (!x_dev || !out_dev || batch < 0 || h < 0 || w < 0 || c <= 0) return E.refuse("bad arguments");
     if (dtype != 0 && dtype != 2) return E.refuse("dtype must be 0 (float32) or 2 (bfloat16)");
     if (stride != 2) return E.refuse("the stride must be 2");
@@ -191,8 +194,36 @@ int opa_maxpool3x3_bias_act(const void* x_dev, const void* bias_dev, void* out_d
     if ((double)batch * h * w * c * (dtype == 0 ? 4.0 : 2.0) >= 2147483648.0)
         return E.refuse("the activation must be smaller than 2 GB (32-bit offsets)");
     if (batch == 0 || h == 0 || w == 0) return OPA_OK;
-    if (maxpool3x3_blocks(batch, h, w, c) > 0x7fffffffll) return E.refuse("too many output vectors for grid.x");
-    return E.launched(launch_maxpool3x3(x_dev, bias_dev, out_dev, dtype, batch, h, w, c, relu, E.st), "maxpool3x3_bias_act", "maxpool3x3s2_kernel");
+    if (maxpool3x3_blocks(batch, h, w, c, ceil_mode) > 0x7fffffffll) return E.refuse("too many output vectors for grid.x");
+    return E.launched(launch_maxpool3x3(x_dev, bias_dev, out_dev, dtype, batch, h, w, c, relu, E.st, ceil_mode), where, "maxpool3x3s2_kernel");
+}
+
+int opa_maxpool3x3_bias_act(const void* x_dev, const void* bias_dev, void* out_dev, int32_t dtype, int32_t batch, int32_t h, int32_t w,
+                            int32_t c, int32_t stride, int32_t relu, void* stream) {
+    return maxpool3x3("opa_maxpool3x3_bias_act", "maxpool3x3_bias_act", 0, x_dev, bias_dev, out_dev, dtype, batch, h, w, c, stride, relu, stream);
+}
+
+int opa_maxpool3x3_ceil_bias_act(const void* x_dev, const void* bias_dev, void* out_dev, int32_t dtype, int32_t batch, int32_t h, int32_t w,
+                                 int32_t c, int32_t stride, int32_t relu, void* stream) {
+    return maxpool3x3("opa_maxpool3x3_ceil_bias_act", "maxpool3x3_ceil_bias_act", 1, x_dev, bias_dev, out_dev, dtype, batch, h, w, c, stride, relu,
+                      stream);
+}
+
+int opa_fire_expand_f32x3(const float* h_dev, const void* w_dev, const float* bias_dev, float* out_dev, int32_t batch, int32_t h, int32_t w,
+                          int32_t c_squeeze, int32_t c_e1, int32_t c_e3, int32_t terms, void* stream) {
+    const Entry E("opa_fire_expand_f32x3", stream);
+    if (!h_dev || !w_dev || !bias_dev || !out_dev || batch < 0 || h < 0 || w < 0 || c_squeeze <= 0 || c_e1 <= 0 || c_e3 <= 0 || bad_terms(terms))
+        return E.refuse("bad arguments");
+    if (c_squeeze % 16 != 0 || c_squeeze > 64) return E.refuse("c_squeeze must be 16, 32, 48 or 64");
+    if (c_e1 % 64 != 0 || c_e3 % 64 != 0) return E.refuse("c_e1 and c_e3 must be multiples of 64");
+    if (misaligned(15, {h_dev, w_dev, bias_dev, out_dev})) return E.refuse("pointers must be 16-B aligned");
+    // 32-bit byte offsets into both tensors (in double: no product of 32-bit arguments overflows it)
+    if ((double)batch * h * w * ((double)c_e1 + c_e3) * 4.0 >= 2147483648.0 || (double)batch * h * w * c_squeeze * 4.0 >= 2147483648.0)
+        return E.refuse("the tensors must be smaller than 2 GB (32-bit offsets)");
+    if (batch == 0 || h == 0 || w == 0) return OPA_OK;
+    if (fire_expand_workgroups(batch, h, w) > 0x7fffffffll) return E.refuse("too many pixel tiles for grid.x");
+    return E.launched(launch_fire_expand(h_dev, (const unsigned short*)w_dev, bias_dev, out_dev, batch, h, w, c_squeeze, c_e1, c_e3, terms,
+                                         E.st), "fire_expand_f32x3", "fire_expand_kernel");
 }
 
 // opa_gemm_unit_act_f32x3, and opa_gemm_unit_bias_act_f32x3 as its call without a residual and with act 0 / 1 (`eight`: the

@@ -271,8 +271,18 @@ hipError_t launch_conv3x3_f32x3(const float* x, int batch, int hi, int wi, int C
                                 const float* bias, float* out, int N, int relu, int terms, hipStream_t st);
 // out = maxpool3x3(act(x + bias)), stride 2, padding 1, channels-last [B, H, W, C] -> [B, ho, wo, C] (pool.hip); dtype 0 float32,
 // 2 bfloat16; bias null or [C] of that dtype; C % 8 == 0.  The caller checks the sizes (maxpool3x3_blocks < 2^31, 32-bit offsets).
-long long maxpool3x3_blocks(int B, int H, int W, int C);
-hipError_t launch_maxpool3x3(const void* x, const void* bias, void* out, int dtype, int B, int H, int W, int C, int relu, hipStream_t st);
+// ceil_mode 1: torch's ceil_mode=True output sizes (maxpool3x3_out: one more row / column for an even H / W), the same kernel.
+int maxpool3x3_out(int h, int ceil_mode);
+long long maxpool3x3_blocks(int B, int H, int W, int C, int ceil_mode = 0);
+hipError_t launch_maxpool3x3(const void* x, const void* bias, void* out, int dtype, int B, int H, int W, int C, int relu, hipStream_t st,
+                             int ceil_mode = 0);
+// Both expand convolutions of a SqueezeNet Fire module, bias, ReLU and the concatenation in one launch (fire.hip): h [B, H, W, S]
+// channels-last float32, w3 the fragment-ordered split weight block (openpifpaf_amd.fused.fire_weight_of), bias [E1 + E3],
+// out [B, H, W, E1 + E3].  S % 16 == 0, S <= 64, E1 % 64 == 0, E3 % 64 == 0; both tensors smaller than 2 GB (32-bit byte offsets);
+// fire_expand_workgroups = grid.x of the launch.
+long long fire_expand_workgroups(int B, int H, int W);
+hipError_t launch_fire_expand(const float* h, const unsigned short* w3, const float* bias, float* out, int B, int H, int W, int S,
+                              int E1, int E3, int terms, hipStream_t st);
 // the unit mode (gemm_f32x3.hip) with an activation code (0 none, 1 ReLU, 2 hardswish) and optionally a residual [M, N] with `ldr`
 // floats between rows (added before the activation; not together with a partner)
 hipError_t launch_gemm_unit_act_f32x3(const float* A, int lda, const unsigned short* W3, const float* bias, const float* partner, int ldp,

@@ -8,7 +8,10 @@
 // scanned in torch's order from -inf with a strict comparison, so the first of two equal values -- +0.0 and -0.0 -- stays.
 // The largest activation of the network (64 channels at half resolution) is read once and a quarter of it written, where the
 // epilogue pass + torch's pool read it twice and write 1.25 of it.
-// Padding never wins: only pixels inside the image are compared, and the window's centre (2 oy, 2 ox) always is one.  A NaN in the
+// Padding never wins: only pixels inside the image are compared, and every window holds at least one.  In floor mode that is its
+// centre (2 oy, 2 ox); in ceil mode (SqueezeNet's pools, reference network/basenetworks.py:461-487: MaxPool2d(3, 2, 1,
+// ceil_mode=True); the launcher passes ho, wo) an even H has one more output row whose window holds row H - 1 alone -- its first
+// row, the centre lies outside -- and likewise column W - 1 for an even W.  A NaN in the
 // window gives NaN, as in torch (fmaxf would drop it: the comparison is written out), and ReLU keeps it (v < 0 ? 0 : v).
 // One thread per output pixel and 16-byte vector of channels (4 float32 | 8 bfloat16); 32-bit vector indices (the host checks).
 #include "common.hpp"
@@ -35,7 +38,7 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const Vec16* __restri
     }
     float m[N];
 #pragma unroll
-    for (int k = 0; k < N; k++) m[k] = -INFINITY;      // (the centre, t = 4, is inside for every output pixel)
+    for (int k = 0; k < N; k++) m[k] = -INFINITY;      // (at least one pixel of every window is inside: see the header)
 #pragma unroll
     for (int t = 0; t < 9; t++) {              // torch's scan: rows, then columns, the first of equal values stays
         if (!in[t]) continue;
@@ -61,15 +64,25 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const Vec16* __restri
 
 static int pool_per_vec(int dtype) { return dtype == 0 ? 4 : 8; }
 
+// output rows of kernel 3, stride 2, padding 1 for h >= 1 input rows.  Floor mode: (h - 1) / 2 + 1.  Ceil mode is torch's rule:
+// ceil((h - 1) / 2) + 1, one less where the last window would begin behind the input and its left padding ((o - 1) * 2 >= h + 1:
+// never the case for this kernel, stride and padding; kept as torch states it) -- the floor-mode size for odd h, one more for even h
+int maxpool3x3_out(int h, int ceil_mode) {
+    if (!ceil_mode) return (h - 1) / 2 + 1;
+    int o = h / 2 + 1;
+    if ((o - 1) * 2 >= h + 1) o--;
+    return o;
+}
+
 // workgroups of the launch (one thread per output pixel and vector)
-long long maxpool3x3_blocks(int B, int H, int W, int C) {
-    const long long ho = (H - 1) / 2 + 1, wo = (W - 1) / 2 + 1;
+long long maxpool3x3_blocks(int B, int H, int W, int C, int ceil_mode) {
+    const long long ho = maxpool3x3_out(H, ceil_mode), wo = maxpool3x3_out(W, ceil_mode);
     return ((long long)B * ho * wo * (C / 4) + 255) / 256;      // (float32's vector count: the larger of the two)
 }
 
 template <int DT>
-static hipError_t launch_pool_dt(const void* x, const void* bias, void* out, int B, int H, int W, int C, int relu, hipStream_t st) {
-    const int ho = (H - 1) / 2 + 1, wo = (W - 1) / 2 + 1, vpp = C / Elem<DT>::kPerVec;
+static hipError_t launch_pool_dt(const void* x, const void* bias, void* out, int B, int H, int W, int C, int relu, int ceil_mode, hipStream_t st) {
+    const int ho = maxpool3x3_out(H, ceil_mode), wo = maxpool3x3_out(W, ceil_mode), vpp = C / Elem<DT>::kPerVec;
     const unsigned n_vec = (unsigned)((long long)B * ho * wo * vpp);
     const unsigned blocks = (n_vec + 255u) / 256u;
     const Vec16* xv = (const Vec16*)x; const Vec16* bv = (const Vec16*)bias; Vec16* ov = (Vec16*)out;
@@ -80,11 +93,12 @@ static hipError_t launch_pool_dt(const void* x, const void* bias, void* out, int
     return hipGetLastError();
 }
 
-hipError_t launch_maxpool3x3(const void* x, const void* bias, void* out, int dtype, int B, int H, int W, int C, int relu, hipStream_t st) {
+hipError_t launch_maxpool3x3(const void* x, const void* bias, void* out, int dtype, int B, int H, int W, int C, int relu, hipStream_t st,
+                             int ceil_mode) {
     if (C % pool_per_vec(dtype) != 0) return hipErrorInvalidValue;
     switch (dtype) {
-        case 0: return launch_pool_dt<0>(x, bias, out, B, H, W, C, relu, st);
-        case 2: return launch_pool_dt<2>(x, bias, out, B, H, W, C, relu, st);
+        case 0: return launch_pool_dt<0>(x, bias, out, B, H, W, C, relu, ceil_mode, st);
+        case 2: return launch_pool_dt<2>(x, bias, out, B, H, W, C, relu, ceil_mode, st);
         default: return hipErrorInvalidValue;
     }
 }

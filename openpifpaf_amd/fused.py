@@ -6,8 +6,8 @@ kernel's contract), the operands derived from the module's parameters (split, pa
 the choice is made once per shape and remembered in one table (``_CHOICE``, shipped as ``conv1x1_pinned.json``): ``conv_bias_act``
 and ``pick`` say what the candidates are, ``_decide`` makes the choice.  In this order: the launcher, the switches, the choice
 table and the decision, the derived operands, then the routes by kernel family -- the epilogue passes, the 1x1 GEMMs, the
-split-operand convolutions (pair, 3x3 and dilated 3x3, stem, heads, unit mode), the input max-pool, the grouped and the depthwise
-stencils, squeeze-and-excitation."""
+split-operand convolutions (pair, 3x3 and dilated 3x3, stem, heads, unit mode), the Fire expand, the max-pools, the grouped and
+the depthwise stencils, squeeze-and-excitation."""
 import os
 
 import torch
@@ -66,6 +66,21 @@ GCONV = _switch('OPA_GCONV', '0')
 # route on.  It stays OFF by default -- the plain torch forward -- until both trunks have been timed against that forward at 641 px,
 # batch 32 (tools/gpu/mobilenetv3_times.py): no speed is claimed for a route nobody has measured.
 MBV3 = _switch('OPA_MBV3', '0')
+# The SqueezeNet Fire modules and max-pools on the project's kernels (network._Fire._forward_unit: the unit-mode GEMM for the squeeze,
+# csrc/fire.hip for both expands, their ReLUs and the concatenation; csrc/pool.hip in ceil mode): OPA_FIRE=1 (or fused.FIRE = True)
+# switches the route on.  It ships OFF -- the plain torch forward.  Timed once against that forward at 641 px
+# (tools/gpu/squeezenet_times.py, profiles/squeezenet/times.log: 3.5 against 6.7 ms at batch 32, 0.50 against 1.00 ms at batch 1,
+# trunk + heads); switching the default is a change of its own that rests on that log.
+FIRE = _switch('OPA_FIRE', '0')
+# ... with NINE terms in both of a Fire's launches, whatever X3_TERMS says (0 still switches the route off: the squeeze is the unit
+# mode's).  Nine terms are 1.5 times the MFMA work of six, which counts in the 41 x 41 layers; the times of
+# profiles/squeezenet/times.log are of the route as it runs, with nine -- six terms have not been timed.  The pieces of the split
+# are truncations, so they have their number's sign and the three products the six-term variant leaves out have the product's: every
+# six-term layer shrinks its output by ~3e-8 of its size, and where a float32 rounding error grows with the square root of the
+# depth this adds up in proportion to it.  SqueezeNet is 17 such layers in series with K as small as 16: measured
+# (tools/gpu/squeezenet_terms.py, profiles/squeezenet/terms.log) the field outputs are 4e-7 ... 6e-7 of their size too small with six
+# terms -- 0.9 ... 2.4 times the largest error of torch's own float32 forward -- and 0.4 ... 1.0 times that error with nine.
+FIRE_TERMS = 9
 
 
 # ---- the choice table and the decision ---------------------------------------------------------------------------------------------
@@ -646,7 +661,7 @@ def unit_conv_x3_supported(conv, x, partner=None, residual=None):
     return True
 
 
-def conv1x1_unit_x3(conv, x, relu=True, partner=None, residual=None, act=None):
+def conv1x1_unit_x3(conv, x, relu=True, partner=None, residual=None, act=None, terms=None):
     """``act(conv(x))`` for a biased 1x1 convolution of ANY even channel counts on a channels-last tensor or channel slice
     (reference ``network/basenetworks.py:186-242``: the 1x1 convolutions of a ShuffleNetV2K unit, folded with their batch norms),
     through the split-operand GEMM's unit mode (``opa_gemm_unit_act_f32x3``).  With ``partner`` (``[B, N, H, W]``, may be a
@@ -654,18 +669,89 @@ def conv1x1_unit_x3(conv, x, relu=True, partner=None, residual=None, act=None):
     even positions by the same kernel.  channels_last float32 out.  ``unit_conv_x3_supported`` says whether this can run.
 
     ``act`` (``ACT_NONE`` / ``ACT_RELU`` / ``ACT_HARDSWISH``) instead of ``relu``, and ``residual`` (``[B, N, H, W]``, may be a slice,
-    never together with a partner): ``act(conv(x) + residual)`` in the same launch -- the 1x1 convolutions of a MobileNetV3 block."""
+    never together with a partner): ``act(conv(x) + residual)`` in the same launch -- the 1x1 convolutions of a MobileNetV3 block.
+    ``terms``: 6 or 9 instead of ``X3_TERMS`` (the squeeze of a SqueezeNet Fire: ``FIRE_TERMS``)."""
     w3, bp = _unit_weight_of(conv)
     n = conv.out_channels
     out = _empty_nhwc(x, n if partner is None else 2 * n, dtype=torch.float32)
     _launch('opa_gemm_unit_act_f32x3', _ptr(x), _pixel_stride(x), _ptr(w3), _ptr(bp),
             _ptr(partner), _pixel_stride(partner) if partner is not None else 0,
             _ptr(residual), _pixel_stride(residual) if residual is not None else 0,
-            _ptr(out), out_pixels(x), n, x.shape[1], _act_code(relu, act), int(X3_TERMS))
+            _ptr(out), out_pixels(x), n, x.shape[1], _act_code(relu, act), int(X3_TERMS if terms is None else terms))
     return out
 
 
-# ---- the input max-pool, the grouped and the depthwise stencils ---------------------------------------------------------------------------------------------
+# ---- the Fire expand ------------------------------------------------------------------------------------------------------------------
+
+def _fragment_order(w3):
+    """``[3, N, K]`` (``split_weight``; N a multiple of 32, K of 16) -> ``[3, N * K]`` in the order ``csrc/fire.hip`` loads it: per
+    32-row block and K-step of 16 one fragment of 64 lanes x 8 elements, lane ``l`` holding row ``l % 32``, columns
+    ``8 * (l // 32) ... + 8`` -- the B operand of ``v_mfma_f32_32x32x16_bf16`` as consecutive bytes."""
+    n, k = w3.shape[1], w3.shape[2]
+    return w3.reshape(3, n // 32, 32, k // 16, 2, 8).permute(0, 1, 3, 4, 2, 5).reshape(3, n * k)
+
+
+def fire_weight_of(expand1x1, expand3x3):
+    """The operands of ``fire_expand_bias_relu`` derived from the CURRENT parameters of both convolutions: the split weights in the
+    kernel's fragment order, ``[3, (e1 + 9 e3) * s]`` bfloat16 (the 1x1's blocks, then the 3x3's with K = (ky, kx, c)), and both
+    biases concatenated (zeros where a convolution has none).  Kept on ``expand1x1`` (``derived``): the key holds both weights and
+    both biases, so ``load_state_dict``, ``.to()`` or an in-place update of any of them makes a new operand."""
+    def make():
+        w1, w3 = expand1x1.weight.detach(), expand3x3.weight.detach()
+        blocks = (_fragment_order(split_weight(w1.reshape(w1.shape[0], w1.shape[1]))), _fragment_order(split_weight_3x3(w3)))
+        biases = [torch.zeros(c.out_channels, dtype=torch.float32, device=w1.device) if c.bias is None else c.bias.detach().float()
+                  for c in (expand1x1, expand3x3)]
+        return torch.cat(blocks, dim=1).contiguous(), torch.cat(biases).contiguous()
+    return derived(expand1x1, '_opa_w3_fire', (expand1x1.weight, expand1x1.bias, expand3x3.weight, expand3x3.bias), make)
+
+
+def _fire_convs_ok(expand1x1, expand3x3):
+    """The part of ``fire_expand_supported`` that depends on the two convolutions alone."""
+    def ok(conv, k):
+        return (conv.kernel_size == (k, k) and conv.stride == (1, 1) and conv.padding == (k // 2, k // 2) and conv.dilation == (1, 1)
+                and conv.groups == 1 and conv.padding_mode == 'zeros' and conv.weight.dtype == torch.float32
+                and (conv.bias is None or (conv.bias.dtype == torch.float32 and conv.bias.device == conv.weight.device)))
+    s = expand1x1.in_channels
+    return (ok(expand1x1, 1) and ok(expand3x3, 3) and expand3x3.in_channels == s and s % 16 == 0 and s <= 64
+            and expand1x1.out_channels % 64 == 0 and expand3x3.out_channels % 64 == 0
+            and expand1x1.weight.device == expand3x3.weight.device)
+
+
+def fire_expand_supported(expand1x1, expand3x3, h, terms=None):
+    """Can ``fire_expand_bias_relu(expand1x1, expand3x3, h, terms)`` run?  ``terms`` (``FIRE_TERMS`` where not given) 6 or 9;  A 1x1 and a 3x3 (padding 1) float32 convolution of stride 1 on the
+    same 16 / 32 / 48 / 64 input channels with multiples of 64 output channels each; ``h`` a dense channels-last float32 tensor on
+    their device, input and output smaller than 2 GB, outside autocast, not followed by autograd."""
+    if not (h.is_cuda and h.dim() == 4 and h.dtype == torch.float32 and not torch.is_autocast_enabled() and _fire_convs_ok(expand1x1, expand3x3)):
+        return False
+    if torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for c in (expand1x1, expand3x3) for p in c.parameters())):
+        return False
+    return (h.shape[1] == expand1x1.in_channels and h.is_contiguous(memory_format=torch.channels_last) and h.data_ptr() % 16 == 0
+            and fire_expand_shape_supported(expand1x1, expand3x3, h.device, h.shape[0] * h.shape[2] * h.shape[3], terms))
+
+
+def fire_expand_shape_supported(expand1x1, expand3x3, device, pixels, terms=None):
+    """The part of ``fire_expand_supported`` that needs no tensor: the convolutions, their device and the size of a dense channels-last
+    float32 operand of ``pixels`` pixels (batch x rows x columns) that the caller is about to allocate (``network._Fire``)."""
+    n = expand1x1.out_channels + expand3x3.out_channels
+    return ((FIRE_TERMS if terms is None else terms) in (6, 9)          # (the value the launcher passes)
+            and _fire_convs_ok(expand1x1, expand3x3) and expand1x1.weight.device == device and 0 < pixels
+            and pixels * n * 4 < 2 ** 31 and _lib.available())
+
+
+def fire_expand_bias_relu(expand1x1, expand3x3, h, terms=None):
+    """``cat((relu(expand1x1(h)), relu(expand3x3(h))), 1)`` -- the second half of a SqueezeNet Fire module (reference
+    ``network/basenetworks.py:461-487``: torchvision's ``Fire``) -- in one HIP kernel (``opa_fire_expand_f32x3``, ``csrc/fire.hip``):
+    split-operand arithmetic with ``terms`` (6 or 9; ``FIRE_TERMS`` where not given) terms, float32 channels-last in and out.
+    ``fire_expand_supported`` says whether this can run."""
+    w3, bias = fire_weight_of(expand1x1, expand3x3)
+    B, S, H, W = h.shape
+    out = _empty_nhwc(h, expand1x1.out_channels + expand3x3.out_channels, dtype=torch.float32)
+    _launch('opa_fire_expand_f32x3', _ptr(h), _ptr(w3), _ptr(bias), _ptr(out), B, H, W, S, expand1x1.out_channels,
+            expand3x3.out_channels, int(FIRE_TERMS if terms is None else terms))
+    return out
+
+
+# ---- the max-pools, the grouped and the depthwise stencils ---------------------------------------------------------------------------------------------
 
 GCONV_WIDTHS = (4, 8, 16, 32, 64)            # channels per group the kernel is instantiated for
 
@@ -712,15 +798,30 @@ def maxpool3x3_supported(x, bias=None):
             and _lib.available())
 
 
-def maxpool3x3_bias_act_(x, bias=None, relu=False, out=None):
+def maxpool3x3_out_hw(h, w, ceil_mode=False):
+    """Output rows and columns of ``max_pool2d(kernel 3, stride 2, padding 1, ceil_mode)`` for an ``h`` x ``w`` input: floor mode
+    ``(h - 1) // 2 + 1``; ceil mode torch's ``ceil((h - 1) / 2) + 1``, one less if the last window would begin behind the input and its
+    left padding (``(o - 1) * 2 >= h + 1``) -- the floor-mode size for odd ``h``, one more for even ``h``."""
+    def one(n):
+        if not ceil_mode:
+            return (n - 1) // 2 + 1
+        o = -((n - 1) // -2) + 1
+        return o - 1 if (o - 1) * 2 >= n + 1 else o
+    return one(h), one(w)
+
+
+def maxpool3x3_bias_act_(x, bias=None, relu=False, out=None, ceil_mode=False):
     """``max_pool2d(act(x + bias), 3, 2, 1)`` -- the input max-pool of a ResNet (reference ``network/basenetworks.py:85-93``) with the
     stem's bias and ReLU in front of it -- in one HIP kernel (``opa_maxpool3x3_bias_act``): ``torch.equal`` to what the torch ops compute.
     ``bias`` None: no addition.  ``x`` is read only; ``out``: a dense channels-last tensor to write into (tests).
+    ``ceil_mode``: torch's ``ceil_mode=True`` output sizes (``maxpool3x3_out_hw``) -- SqueezeNet's pools (reference
+    ``network/basenetworks.py:461-487``) -- through ``opa_maxpool3x3_ceil_bias_act``, the same kernel.
     ``maxpool3x3_supported`` says whether this can run."""
     B, C, H, W = x.shape
     if out is None:
-        out = _empty_nhwc(x, C, _out_hw(x, 2))
-    _launch('opa_maxpool3x3_bias_act', _ptr(x), _ptr(bias), _ptr(out), _DTYPES[x.dtype], B, H, W, C, 2, int(bool(relu)))
+        out = _empty_nhwc(x, C, maxpool3x3_out_hw(H, W, ceil_mode))
+    _launch('opa_maxpool3x3_ceil_bias_act' if ceil_mode else 'opa_maxpool3x3_bias_act', _ptr(x), _ptr(bias), _ptr(out),
+            _DTYPES[x.dtype], B, H, W, C, 2, int(bool(relu)))
     return out
 
 

@@ -14,6 +14,8 @@ follows the reference so that the field tensors have the reference's shapes:
   [4,8,4], channels [24,348,696,1392,1392]; k30: [8,16,6], [32,512,1024,2048,2048]).
 * ``MobileNetV3``: torchvision's ``mobilenet_v3_large`` / ``mobilenet_v3_small`` feature extractors with the stride of the first
   convolution set to 1, stride 16 (reference ``network/basenetworks.py:432-446``, ``network/factory.py:53-56``).
+* ``SqueezeNet``: torchvision's ``squeezenet1_1`` features with padding 1 on the stem and on the ceil-mode max-pools, stride 16
+  (reference ``network/basenetworks.py:461-487``).
 * ``CompositeField4``: 1x1 conv -> PixelShuffle(2) -> crop last row/col -> view
   ``[B, F, C, H, W]`` -> sigmoid / index-add / softplus (reference
   ``network/heads.py:272-378``); 641 px -> 41 -> 82 -> 81.
@@ -676,10 +678,106 @@ class MobileNetV3(BaseNetwork):
         return last(x)
 
 
+class _Fire(nn.Module):
+    """SqueezeNet's Fire module (torchvision's ``Fire``: the same attribute names): a 1x1 squeeze, then a 1x1 and a 3x3 expand of the
+    squeezed tensor, concatenated; every convolution biased and followed by a ReLU."""
+
+    def __init__(self, inplanes, squeeze_planes, expand1x1_planes, expand3x3_planes):
+        super().__init__()
+        self.squeeze = nn.Conv2d(inplanes, squeeze_planes, 1)
+        self.squeeze_activation = nn.ReLU(inplace=True)
+        self.expand1x1 = nn.Conv2d(squeeze_planes, expand1x1_planes, 1)
+        self.expand1x1_activation = nn.ReLU(inplace=True)
+        self.expand3x3 = nn.Conv2d(squeeze_planes, expand3x3_planes, 3, padding=1)
+        self.expand3x3_activation = nn.ReLU(inplace=True)
+
+    fused = False
+
+    def enable_fused_(self):
+        """The module may run on the project's kernels alone (``_forward_unit``); no parameter or buffer changes."""
+        self.fused = True
+
+    def _route_supported(self, x):
+        """Can the WHOLE module run on the project's kernels (``_forward_unit``)?  A float32 channels-last tensor on the GPU, outside
+        autocast, nothing that autograd follows; the squeezed tensor is a dense channels-last one this module allocates, so its
+        layout is known and its size follows from ``x``'s."""
+        if not (fused.FIRE and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and not torch.is_autocast_enabled()
+                and x.is_contiguous(memory_format=torch.channels_last)):
+            return False
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return False
+        return (self.squeeze.bias is not None and fused.FIRE_TERMS in (6, 9) and fused.unit_conv_x3_supported(self.squeeze, x)
+                and fused.fire_expand_shape_supported(self.expand1x1, self.expand3x3, x.device, x.shape[0] * x.shape[2] * x.shape[3]))
+
+    def _forward_unit(self, x):
+        """Two launches: the squeeze as GEMM + bias + ReLU (unit mode), then both expands, their biases and ReLUs and the
+        concatenation (``csrc/fire.hip``); both with ``fused.FIRE_TERMS`` terms."""
+        h = fused.conv1x1_unit_x3(self.squeeze, x, relu=True, terms=fused.FIRE_TERMS)
+        return fused.fire_expand_bias_relu(self.expand1x1, self.expand3x3, h)
+
+    def forward(self, x):
+        if self.fused and self._route_supported(x):
+            return self._forward_unit(x)
+        x = self.squeeze_activation(self.squeeze(x))
+        return torch.cat([self.expand1x1_activation(self.expand1x1(x)), self.expand3x3_activation(self.expand3x3(x))], 1)
+
+
+class SqueezeNet(BaseNetwork):
+    """SqueezeNet 1.1 as the reference uses it: torchvision's ``squeezenet1_1().features`` with the padding of the stem and of every
+    max-pool set to 1 (the pools keep ``ceil_mode=True``), stride 16, 512 features (reference ``network/basenetworks.py:461-487``,
+    ``network/factory.py:52-78``), restated with torchvision's module tree (``backbone.<i>.squeeze`` ...), so that the
+    ``base_net.backbone.*`` keys of a reference checkpoint fit.  No checkpoint can be loaded offline: the fit is checked by key
+    names and shapes only (``tests/test_squeezenet_host.py``), never against real weights."""
+    # in, squeeze, expand 1x1, expand 3x3; None: a max-pool
+    CONFIGS = {'squeezenet': ((64, 16, 64, 64), (128, 16, 64, 64), None, (128, 32, 128, 128), (256, 32, 128, 128), None,
+                              (256, 48, 192, 192), (384, 48, 192, 192), (384, 64, 256, 256), (512, 64, 256, 256))}
+
+    def __init__(self, name='squeezenet'):
+        super().__init__(name, stride=16, out_features=512)
+
+        def pool():
+            return nn.MaxPool2d(kernel_size=3, stride=2, padding=1, ceil_mode=True)     # (torchvision: padding 0)
+        layers = [nn.Conv2d(3, 64, 3, stride=2, padding=1), nn.ReLU(inplace=True), pool()]          # (torchvision: padding 0)
+        layers += [pool() if cfg is None else _Fire(*cfg) for cfg in self.CONFIGS[name]]
+        self.backbone = nn.Sequential(*layers)
+        for m in self.modules():               # torchvision's initialisation (its last, classifying convolution aside)
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_uniform_(m.weight)
+                nn.init.zeros_(m.bias)
+
+    fused = False
+
+    def enable_fused_(self):
+        """The max-pools may run through the ceil-mode entry point of ``csrc/pool.hip`` (the first with the stem's ReLU inside); the
+        stem stays with ``torch.nn.Conv2d`` like MobileNetV3's and ShuffleNetV2K's.  No parameter or buffer changes."""
+        self.fused = True
+
+    @staticmethod
+    def _pool_route_supported(pool, x):
+        return (isinstance(pool, nn.MaxPool2d) and pool.kernel_size == 3 and pool.stride == 2 and pool.padding == 1 and pool.dilation == 1
+                and pool.ceil_mode and not pool.return_indices and fused.maxpool3x3_supported(x))
+
+    def forward(self, x):
+        if not (self.fused and fused.FIRE and x.is_cuda and not torch.is_autocast_enabled()):
+            return self.backbone(x)
+        modules = list(self.backbone)
+        i = 0
+        while i < len(modules):
+            m = modules[i]
+            if isinstance(m, nn.ReLU) and i + 1 < len(modules) and self._pool_route_supported(modules[i + 1], x):
+                x = fused.maxpool3x3_bias_act_(x, relu=True, ceil_mode=True)        # the stem's ReLU goes into the pool (max and ReLU commute)
+                i += 2
+                continue
+            x = fused.maxpool3x3_bias_act_(x, ceil_mode=True) if self._pool_route_supported(m, x) else m(x)
+            i += 1
+        return x
+
+
 BASE_FACTORIES = {
     **{n: (lambda n=n: Resnet(n)) for n in Resnet.CONFIGS},
     **{n: (lambda n=n: ShuffleNetV2K(n)) for n in ShuffleNetV2K.CONFIGS},
     **{n: (lambda n=n: MobileNetV3(n)) for n in MobileNetV3.CONFIGS},
+    **{n: (lambda n=n: SqueezeNet(n)) for n in SqueezeNet.CONFIGS},
 }
 
 
@@ -809,10 +907,12 @@ def fuse_conv_bn_(model):
 def optimize_for_inference_(model):
     """Fold every conv+BN pair, then switch the ResNet blocks to the fused-epilogue forward
     (conv without bias followed by ONE ``fused.bias_act_`` pass), the ShuffleNetV2K units and ``conv5`` to the HIP depthwise /
-    interleave kernels and the split-operand GEMM's unit mode, and the MobileNetV3 blocks and last convolution to the same GEMM,
-    the depthwise stencil and the squeeze-and-excitation kernels."""
+    interleave kernels and the split-operand GEMM's unit mode, the MobileNetV3 blocks and last convolution to the same GEMM,
+    the depthwise stencil and the squeeze-and-excitation kernels, and the SqueezeNet Fire modules and max-pools to that GEMM, the
+    Fire expand kernel and the ceil-mode pool (behind ``fused.FIRE``)."""
     fuse_conv_bn_(model)
     for m in model.modules():
-        if isinstance(m, (_Bottleneck, _BasicBlock, Resnet, _InvertedResidualK, ShuffleNetV2K, _MBV3Block, MobileNetV3)):
+        if isinstance(m, (_Bottleneck, _BasicBlock, Resnet, _InvertedResidualK, ShuffleNetV2K, _MBV3Block, MobileNetV3, _Fire,
+                          SqueezeNet)):
             m.enable_fused_()
     return model
