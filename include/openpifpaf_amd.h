@@ -574,6 +574,15 @@ int opa_dwconv_act(const void* x_dev, int64_t x_pixel_stride, const void* w_dev,
                    void* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w,
                    int32_t channels, int32_t k, int32_t stride, int32_t dtype, int32_t act, void* stream);
 
+/* The same stencil with a 7 x 7 window and a dilation (the ShuffleNetV2K options of the reference, network/basenetworks.py:245-400:
+ * --shufflenetv2k-kernel, --shufflenetv2k-stage4-dilation): tap (ky, kx) of output (y, x) reads input
+ * (y * stride - p + ky * dilation, x * stride - p + kx * dilation), p = (k / 2) * dilation, zeros outside; w_dev [k*k, channels].
+ * k 3, 5 or 7; stride 1 or 2; dilation 1, 2 or 4, stride 1 where it is above 1; dtype and act as opa_dwconv_act, whose results it
+ * gives bit for bit where both accept the call.  Everything else is refused like there, and nothing is launched. */
+int opa_dwconv_dilated_act(const void* x_dev, int64_t x_pixel_stride, const void* w_dev, const void* bias_dev,
+                           void* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w,
+                           int32_t channels, int32_t k, int32_t stride, int32_t dilation, int32_t dtype, int32_t act, void* stream);
+
 /* Grouped 3x3 convolution, padding 1, dilation 1, stride 1 or 2, as many output as input channels, float32, channels innermost,
  * with the folded batch-norm bias and optionally ReLU (fmaxf) applied before the single store: the middle convolution of a
  * ResNeXt bottleneck (reference network/basenetworks.py:71-150 with torchvision's grouped Bottleneck).

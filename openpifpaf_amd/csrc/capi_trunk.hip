@@ -297,33 +297,44 @@ int opa_conv3x3_winograd_f32x3(const float* x_dev, const void* u3_dev, const flo
                             order, stream);
 }
 
-// opa_dwconv_act, and opa_dwconv_bias_act as its call with act 0 / 1
-static int dwconv(const char* fn, const void* x_dev, int64_t x_pixel_stride, const void* w_dev, const void* bias_dev, void* out_dev,
-                  int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w, int32_t channels, int32_t k, int32_t stride,
-                  int32_t dtype, int32_t act, void* stream) {
+// opa_dwconv_act, opa_dwconv_bias_act as its call with act 0 / 1, and opa_dwconv_dilated_act (`dilated`: k = 7 and a dilation of 2
+// or 4 at stride 1 are accepted too; the other two pass dilation 1)
+static int dwconv(const char* fn, bool dilated, const void* x_dev, int64_t x_pixel_stride, const void* w_dev, const void* bias_dev,
+                  void* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w, int32_t channels, int32_t k, int32_t stride,
+                  int32_t dilation, int32_t dtype, int32_t act, void* stream) {
     const Entry E(fn, stream);
     if (act < 0 || act > 2) return E.refuse("act must be 0 (none), 1 (ReLU) or 2 (hardswish)");
+    const bool k_ok = k == 3 || k == 5 || (dilated && k == 7);
+    const bool d_ok = dilation == 1 || (dilated && (dilation == 2 || dilation == 4) && stride == 1);
     if (!x_dev || !w_dev || !out_dev || batch <= 0 || h <= 0 || w <= 0 || channels <= 0 || x_pixel_stride < channels ||
-        out_pixel_stride < channels || (k != 3 && k != 5) || (stride != 1 && stride != 2) || (dtype != 0 && dtype != 2))
+        out_pixel_stride < channels || !k_ok || (stride != 1 && stride != 2) || !d_ok || (dtype != 0 && dtype != 2))
         return E.refuse("bad arguments");
-    if ((int64_t)batch * (((int64_t)h + 2 * (k / 2) - k) / stride + 1) > 65535)          // grid.y of the stencil kernel (dwconv.hip)
+    // grid.y of the stencil kernel (dwconv.hip); the padding is (k / 2) * dilation, so the window takes dilation * (k - 1) rows off
+    if ((int64_t)batch * (((int64_t)h + 2 * (k / 2) * dilation - dilation * (k - 1) - 1) / stride + 1) > 65535)
         return E.refuse("batch * output rows must not exceed 65535");
     return E.launched(launch_dwconv(x_dev, x_pixel_stride, w_dev, bias_dev, out_dev, out_pixel_stride, batch, h, w, channels, k, stride,
-                                    dtype, act, E.st), "depthwise convolution");
+                                    dilation, dtype, act, E.st), "depthwise convolution");
 }
 
 int opa_dwconv_bias_act(const void* x_dev, int64_t x_pixel_stride, const void* w_dev, const void* bias_dev,
                         void* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w,
                         int32_t channels, int32_t k, int32_t stride, int32_t dtype, int32_t relu, void* stream) {
-    return dwconv("opa_dwconv_bias_act", x_dev, x_pixel_stride, w_dev, bias_dev, out_dev, out_pixel_stride, batch, h, w, channels, k, stride,
-                  dtype, relu != 0, stream);                                              // (relu: any non-zero)
+    return dwconv("opa_dwconv_bias_act", false, x_dev, x_pixel_stride, w_dev, bias_dev, out_dev, out_pixel_stride, batch, h, w, channels, k,
+                  stride, 1, dtype, relu != 0, stream);                                   // (relu: any non-zero)
 }
 
 int opa_dwconv_act(const void* x_dev, int64_t x_pixel_stride, const void* w_dev, const void* bias_dev,
                    void* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w,
                    int32_t channels, int32_t k, int32_t stride, int32_t dtype, int32_t act, void* stream) {
-    return dwconv("opa_dwconv_act", x_dev, x_pixel_stride, w_dev, bias_dev, out_dev, out_pixel_stride, batch, h, w, channels, k, stride,
-                  dtype, act, stream);
+    return dwconv("opa_dwconv_act", false, x_dev, x_pixel_stride, w_dev, bias_dev, out_dev, out_pixel_stride, batch, h, w, channels, k,
+                  stride, 1, dtype, act, stream);
+}
+
+int opa_dwconv_dilated_act(const void* x_dev, int64_t x_pixel_stride, const void* w_dev, const void* bias_dev,
+                           void* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w,
+                           int32_t channels, int32_t k, int32_t stride, int32_t dilation, int32_t dtype, int32_t act, void* stream) {
+    return dwconv("opa_dwconv_dilated_act", true, x_dev, x_pixel_stride, w_dev, bias_dev, out_dev, out_pixel_stride, batch, h, w, channels,
+                  k, stride, dilation, dtype, act, stream);
 }
 
 int opa_gconv3x3_bias_act_f32(const float* x_dev, int64_t x_pixel_stride, const float* wt_dev, const float* bias_dev,

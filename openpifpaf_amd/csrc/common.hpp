@@ -294,9 +294,9 @@ hipError_t launch_winograd_f23(const float* x, const float* U, float* y, const f
 hipError_t launch_winograd_f23x3(const float* x, const unsigned short* U3, float* y, const float* bias, int N, int H, int W,
                                  int Cin, int Cout, int relu, int variant, int nb_major, hipStream_t st);
 
-// act: 0 none, 1 ReLU, 2 hardswish
+// act: 0 none, 1 ReLU, 2 hardswish; K 3, 5 or 7, S 1 or 2, dilation D 1, or 2 or 4 with S = 1 (anything else: hipErrorInvalidValue)
 hipError_t launch_dwconv(const void* x, long long xs, const void* w, const void* bias, void* out, long long os,
-                         int B, int H, int W, int C, int K, int S, int dtype, int act, hipStream_t st);
+                         int B, int H, int W, int C, int K, int S, int D, int dtype, int act, hipStream_t st);
 hipError_t launch_channel_interleave(const void* a, long long as, const void* b, long long bs, void* out,
                                      long long rows, int half, int dtype, hipStream_t st);
 

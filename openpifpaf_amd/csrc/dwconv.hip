@@ -14,6 +14,16 @@
 //
 // channel_interleave_kernel fuses the unit's torch.cat + channel_shuffle(groups = 2): out[.., 2i] = a[.., i],
 // out[.., 2i+1] = b[.., i].
+//
+// The ShuffleNetV2K options (reference network/basenetworks.py:245-400) add a 7 x 7 window (--shufflenetv2k-kernel) and a dilation
+// D of 2 or 4 at stride 1 (--shufflenetv2k-stage4-dilation; the reference never builds a strided dilated unit).  D is a template
+// parameter: tap (ky, kx) of output (y, x) reads input (y - P D + ky D, x - P D + kx D), P = K / 2, zeros outside.  The sliding window
+// of a strip would then be 3 + (K - 1) D + 1 columns -- 28 columns x 4 channels at K = 7, D = 4, and at D = 4 no column is used by
+// more than one tap anyway -- so a dilated instantiation holds no window: per tap column it loads the strip's four consecutive
+// pixels (K x 4 loads per row, neighbouring taps' loads hit in L1/L2).  The compiler hoists the independent loads of the unrolled
+// window in front of the multiply-adds, so these instantiations still take 92 - 172 registers at V = 4 (no scratch; a rolled row
+// loop took more): profiles/shufflenetv2k_options/resource_usage.md.  Measured at 696 channels, 81 x 81, batch 32: 0.87 ms for the
+// dilated 5 x 5 against 0.64 undilated and 4.15 for MIOpen (profiles/shufflenetv2k_options/times.log).
 #include "common.hpp"
 #include <type_traits>
 
@@ -61,12 +71,11 @@ template <int V> struct DwVec<unsigned short, V> {               // bfloat16
 // x: [B, H, W, *] with pixel stride xs (a channel slice of a wider tensor is fine), w: [K*K, C] (tap-major),
 // out: [B, Ho, Wo, *] with pixel stride os.  A work item = V channels x a strip of kDwStrip output pixels of one
 // output row; the items of a row are dealt to the threads channel-vector first (coalesced within a pixel).
-template <typename T, int K, int S, int V, int ACT = -1>
+template <typename T, int K, int S, int V, int ACT = -1, int D = 1>
 __global__ __launch_bounds__(256) void dwconv_kernel(const T* __restrict__ x, long long xs, const T* __restrict__ w,
                                                      const T* __restrict__ bias, T* __restrict__ out, long long os,
                                                      int H, int W, int C, int Ho, int Wo, int relu) {
     constexpr int P = K / 2;
-    constexpr int NIN = (kDwStrip - 1) * S + K;          // input columns a strip of outputs needs
     const int cvecs = C / V, strips = (Wo + kDwStrip - 1) / kDwStrip;
     const int item = blockIdx.x * 256 + threadIdx.x;
     if (item >= cvecs * strips) return;
@@ -83,30 +92,59 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const T* __restrict__ x, lo
     for (int i = 0; i < kDwStrip; i++)
 #pragma unroll
         for (int q = 0; q < V; q++) acc[i][q] = (Acc)0.0f;
+    if constexpr (D == 1) {
+        constexpr int NIN = (kDwStrip - 1) * S + K;      // input columns a strip of outputs needs
 #pragma unroll
-    for (int ky = 0; ky < K; ky++) {
-        const int yy = y * S - P + ky;
-        if (yy < 0 || yy >= H) continue;
-        const T* row = x + ((size_t)b * H + yy) * W * xs + c;
-        DwVec<T, V> in[NIN];
+        for (int ky = 0; ky < K; ky++) {
+            const int yy = y * S - P + ky;
+            if (yy < 0 || yy >= H) continue;
+            const T* row = x + ((size_t)b * H + yy) * W * xs + c;
+            DwVec<T, V> in[NIN];
 #pragma unroll
-        for (int j = 0; j < NIN; j++) {
-            const int xx = x0 * S - P + j;
+            for (int j = 0; j < NIN; j++) {
+                const int xx = x0 * S - P + j;
 #pragma unroll
-            for (int q = 0; q < V; q++) in[j].v[q] = 0.0f;
-            if (xx >= 0 && xx < W) in[j].load(row + (size_t)xx * xs);
+                for (int q = 0; q < V; q++) in[j].v[q] = 0.0f;
+                if (xx >= 0 && xx < W) in[j].load(row + (size_t)xx * xs);
+            }
+#pragma unroll
+            for (int kx = 0; kx < K; kx++) {
+                DwVec<T, V> wv;
+                wv.load(w + (size_t)(ky * K + kx) * C + c);
+#pragma unroll
+                for (int i = 0; i < kDwStrip; i++)
+#pragma unroll
+                    for (int q = 0; q < V; q++) {
+                        if constexpr (ACT == 2) acc[i][q] = fma((double)in[i * S + kx].v[q], (double)wv.v[q], acc[i][q]);
+                        else acc[i][q] = fmaf(in[i * S + kx].v[q], wv.v[q], acc[i][q]);
+                    }
+            }
         }
+    } else {
+        static_assert(S == 1, "a dilated stencil has stride 1");
 #pragma unroll
-        for (int kx = 0; kx < K; kx++) {
-            DwVec<T, V> wv;
-            wv.load(w + (size_t)(ky * K + kx) * C + c);
+        for (int ky = 0; ky < K; ky++) {
+            const int yy = y + (ky - P) * D;
+            if (yy < 0 || yy >= H) continue;
+            const T* row = x + ((size_t)b * H + yy) * W * xs + c;
 #pragma unroll
-            for (int i = 0; i < kDwStrip; i++)
+            for (int kx = 0; kx < K; kx++) {
+                DwVec<T, V> wv;
+                wv.load(w + (size_t)(ky * K + kx) * C + c);
 #pragma unroll
-                for (int q = 0; q < V; q++) {
-                    if constexpr (ACT == 2) acc[i][q] = fma((double)in[i * S + kx].v[q], (double)wv.v[q], acc[i][q]);
-                    else acc[i][q] = fmaf(in[i * S + kx].v[q], wv.v[q], acc[i][q]);
+                for (int i = 0; i < kDwStrip; i++) {
+                    const int xx = x0 + i + (kx - P) * D;
+                    DwVec<T, V> in;
+#pragma unroll
+                    for (int q = 0; q < V; q++) in.v[q] = 0.0f;
+                    if (xx >= 0 && xx < W) in.load(row + (size_t)xx * xs);
+#pragma unroll
+                    for (int q = 0; q < V; q++) {
+                        if constexpr (ACT == 2) acc[i][q] = fma((double)in.v[q], (double)wv.v[q], acc[i][q]);
+                        else acc[i][q] = fmaf(in.v[q], wv.v[q], acc[i][q]);
+                    }
                 }
+            }
         }
     }
 #pragma unroll
@@ -142,24 +180,30 @@ __global__ __launch_bounds__(256) void channel_interleave_kernel(const T* __rest
     __builtin_memcpy(out + r * 2 * half + 2 * c, vo, sizeof(vo));
 }
 
-// act: 0 none, 1 ReLU (both the kernel with the run-time flag), 2 hardswish
+// act: 0 none, 1 ReLU (both the kernel with the run-time flag), 2 hardswish.  (K, S, D): 3, 5 or 7; 1 or 2; 1, or 2 or 4 at S = 1
 template <typename T, int V>
 static hipError_t launch_dw_v(const void* x, long long xs, const void* w, const void* bias, void* out, long long os,
-                              int B, int H, int W, int C, int K, int S, int act, hipStream_t st) {
+                              int B, int H, int W, int C, int K, int S, int D, int act, hipStream_t st) {
     const int P = K / 2;
-    const int Ho = (H + 2 * P - K) / S + 1, Wo = (W + 2 * P - K) / S + 1;
+    const int Ho = (H + 2 * P * D - D * (K - 1) - 1) / S + 1, Wo = (W + 2 * P * D - D * (K - 1) - 1) / S + 1;
     const long long items = (long long)(C / V) * ((Wo + kDwStrip - 1) / kDwStrip);
     dim3 grid((unsigned)((items + 255) / 256), B * Ho);
-#define OPA_DW(KK, SS) do { \
-        if (act == 2) dwconv_kernel<T, KK, SS, V, 2><<<grid, 256, 0, st>>>((const T*)x, xs, (const T*)w, (const T*)bias, \
-                                                                           (T*)out, os, H, W, C, Ho, Wo, 0); \
-        else dwconv_kernel<T, KK, SS, V><<<grid, 256, 0, st>>>((const T*)x, xs, (const T*)w, (const T*)bias, \
-                                                               (T*)out, os, H, W, C, Ho, Wo, act); } while (0)
-    if (K == 5 && S == 1) OPA_DW(5, 1);
-    else if (K == 5 && S == 2) OPA_DW(5, 2);
-    else if (K == 3 && S == 1) OPA_DW(3, 1);
-    else if (K == 3 && S == 2) OPA_DW(3, 2);
+#define OPA_DW(KK, SS, DD) do { \
+        if (act == 2) dwconv_kernel<T, KK, SS, V, 2, DD><<<grid, 256, 0, st>>>((const T*)x, xs, (const T*)w, (const T*)bias, \
+                                                                               (T*)out, os, H, W, C, Ho, Wo, 0); \
+        else dwconv_kernel<T, KK, SS, V, -1, DD><<<grid, 256, 0, st>>>((const T*)x, xs, (const T*)w, (const T*)bias, \
+                                                                       (T*)out, os, H, W, C, Ho, Wo, act); } while (0)
+#define OPA_DW_K(KK) do { \
+        if (S == 1 && D == 1) OPA_DW(KK, 1, 1); \
+        else if (S == 2 && D == 1) OPA_DW(KK, 2, 1); \
+        else if (S == 1 && D == 2) OPA_DW(KK, 1, 2); \
+        else if (S == 1 && D == 4) OPA_DW(KK, 1, 4); \
+        else return hipErrorInvalidValue; } while (0)
+    if (K == 5) OPA_DW_K(5);
+    else if (K == 3) OPA_DW_K(3);
+    else if (K == 7) OPA_DW_K(7);
     else return hipErrorInvalidValue;
+#undef OPA_DW_K
 #undef OPA_DW
     prof_mark(st, "dwconv_kernel");
     return hipGetLastError();
@@ -168,21 +212,21 @@ static hipError_t launch_dw_v(const void* x, long long xs, const void* w, const 
 // the widest channel vector the shapes and addresses allow
 template <typename T>
 static hipError_t launch_dw_t(const void* x, long long xs, const void* w, const void* bias, void* out, long long os,
-                              int B, int H, int W, int C, int K, int S, int act, hipStream_t st) {
+                              int B, int H, int W, int C, int K, int S, int D, int act, hipStream_t st) {
     auto ok = [&](int v) {
         const size_t a = v * sizeof(T);
         return C % v == 0 && xs % v == 0 && os % v == 0 && (uintptr_t)x % a == 0 && (uintptr_t)out % a == 0 &&
                (uintptr_t)w % a == 0 && (!bias || (uintptr_t)bias % a == 0);
     };
-    if (ok(4)) return launch_dw_v<T, 4>(x, xs, w, bias, out, os, B, H, W, C, K, S, act, st);
-    if (ok(2)) return launch_dw_v<T, 2>(x, xs, w, bias, out, os, B, H, W, C, K, S, act, st);
-    return launch_dw_v<T, 1>(x, xs, w, bias, out, os, B, H, W, C, K, S, act, st);
+    if (ok(4)) return launch_dw_v<T, 4>(x, xs, w, bias, out, os, B, H, W, C, K, S, D, act, st);
+    if (ok(2)) return launch_dw_v<T, 2>(x, xs, w, bias, out, os, B, H, W, C, K, S, D, act, st);
+    return launch_dw_v<T, 1>(x, xs, w, bias, out, os, B, H, W, C, K, S, D, act, st);
 }
 
 hipError_t launch_dwconv(const void* x, long long xs, const void* w, const void* bias, void* out, long long os,
-                         int B, int H, int W, int C, int K, int S, int dtype, int act, hipStream_t st) {
-    if (dtype == 0) return launch_dw_t<float>(x, xs, w, bias, out, os, B, H, W, C, K, S, act, st);
-    if (dtype == 2) return launch_dw_t<unsigned short>(x, xs, w, bias, out, os, B, H, W, C, K, S, act, st);
+                         int B, int H, int W, int C, int K, int S, int D, int dtype, int act, hipStream_t st) {
+    if (dtype == 0) return launch_dw_t<float>(x, xs, w, bias, out, os, B, H, W, C, K, S, D, act, st);
+    if (dtype == 2) return launch_dw_t<unsigned short>(x, xs, w, bias, out, os, B, H, W, C, K, S, D, act, st);
     return hipErrorInvalidValue;
 }
 

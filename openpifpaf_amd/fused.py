@@ -825,25 +825,46 @@ def maxpool3x3_bias_act_(x, bias=None, relu=False, out=None, ceil_mode=False):
     return out
 
 
-def dwconv_supported(x, kernel_size, stride):
+# (kernel_size, dilation) combinations the stencil can run but that came out SLOWER than torch's convolution of the same layer
+# (tools/gpu/shufflenetv2k_option_times.py, profiles/shufflenetv2k_options/times.log): ``dwconv_supported`` declines them.
+DW_DECLINED = frozenset()
+
+
+def dwconv_out_hw(h, w, kernel_size, stride, dilation=1):
+    """Output rows and columns of the depthwise convolution with padding ``(kernel_size // 2) * dilation``."""
+    cut = dilation * (kernel_size - 1) - 2 * (kernel_size // 2) * dilation + 1          # (1 for an odd kernel)
+    return (h - cut) // stride + 1, (w - cut) // stride + 1
+
+
+def dwconv_supported(x, kernel_size, stride, dilation=1):
+    """Can ``dwconv_bias_act(x, ..., kernel_size, stride, dilation=dilation)`` run?  A float32 or bfloat16 channels-innermost tensor
+    or channel slice on the GPU; a 3 x 3, 5 x 5 or 7 x 7 window; stride 1 or 2; dilation 1, or 2 or 4 at stride 1."""
     if not (x.is_cuda and x.dim() == 4):
         return False
-    rows_out = (x.shape[2] + 2 * (kernel_size // 2) - kernel_size) // stride + 1
-    return (x.dtype in (torch.float32, torch.bfloat16) and kernel_size in (3, 5) and stride in (1, 2)
+    if not (kernel_size in (3, 5, 7) and stride in (1, 2) and (dilation == 1 or (dilation in (2, 4) and stride == 1))):
+        return False
+    if DW_DECLINED and (kernel_size, dilation) in DW_DECLINED:
+        return False
+    rows_out = dwconv_out_hw(x.shape[2], x.shape[3], kernel_size, stride, dilation)[0]
+    return (x.dtype in (torch.float32, torch.bfloat16)
             and x.shape[0] * rows_out <= 65535                              # grid.y of the stencil kernel (dwconv.hip)
             and _pixel_stride(x) is not None and _lib.available())
 
 
-def dwconv_bias_act(x, w_taps, bias, kernel_size, stride, relu=False, act=None):
-    """Depthwise ``kernel_size`` x ``kernel_size`` convolution (padding k//2) + bias (+ activation) of a channels-last
-    activation or channel slice, one HIP stencil kernel (``opa_dwconv_act``).  ``w_taps``: ``[k*k, C]`` (tap-major,
-    ``depthwise_taps``) in ``x``'s dtype.  ``act`` (``ACT_NONE`` / ``ACT_RELU`` / ``ACT_HARDSWISH``) instead of ``relu``."""
+def dwconv_bias_act(x, w_taps, bias, kernel_size, stride, relu=False, act=None, dilation=1):
+    """Depthwise ``kernel_size`` x ``kernel_size`` convolution (padding k//2 times the dilation) + bias (+ activation) of a
+    channels-last activation or channel slice, one HIP stencil kernel.  ``w_taps``: ``[k*k, C]`` (tap-major,
+    ``depthwise_taps``) in ``x``'s dtype.  ``act`` (``ACT_NONE`` / ``ACT_RELU`` / ``ACT_HARDSWISH``) instead of ``relu``.
+    A 3 x 3 or 5 x 5 window without dilation goes to ``opa_dwconv_act``, a 7 x 7 window or a dilation of 2 or 4 (stride 1) to
+    ``opa_dwconv_dilated_act``: the same kernel template."""
     B, C, H, W = x.shape
-    pad = kernel_size // 2
-    Ho, Wo = (H + 2 * pad - kernel_size) // stride + 1, (W + 2 * pad - kernel_size) // stride + 1
-    out = _empty_nhwc(x, C, (Ho, Wo))
-    _launch('opa_dwconv_act', _ptr(x), _pixel_stride(x), _ptr(w_taps), _ptr(bias), _ptr(out), C, B, H, W, C, kernel_size, stride,
-            _DTYPES[x.dtype], _act_code(relu, act))
+    out = _empty_nhwc(x, C, dwconv_out_hw(H, W, kernel_size, stride, dilation))
+    if kernel_size in (3, 5) and dilation == 1:
+        _launch('opa_dwconv_act', _ptr(x), _pixel_stride(x), _ptr(w_taps), _ptr(bias), _ptr(out), C, B, H, W, C, kernel_size, stride,
+                _DTYPES[x.dtype], _act_code(relu, act))
+    else:
+        _launch('opa_dwconv_dilated_act', _ptr(x), _pixel_stride(x), _ptr(w_taps), _ptr(bias), _ptr(out), C, B, H, W, C, kernel_size,
+                stride, dilation, _DTYPES[x.dtype], _act_code(relu, act))
     return out
 
 

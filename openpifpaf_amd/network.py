@@ -11,7 +11,9 @@ follows the reference so that the field tensors have the reference's shapes:
   back, change the stem's stride, add a second input convolution, dilate
   block 5 or drop it (``network/basenetworks.py:79-142``).
 * ``ShuffleNetV2K``: reference ``network/basenetworks.py:186-355`` (k16: stages
-  [4,8,4], channels [24,348,696,1392,1392]; k30: [8,16,6], [32,512,1024,2048,2048]).
+  [4,8,4], channels [24,348,696,1392,1392]; k30: [8,16,6], [32,512,1024,2048,2048]); the reference's options add a second
+  input convolution, dilate stage 4, change the depthwise kernel's width, make ``conv5`` two units or put a LeakyReLU in
+  place of every ReLU (``network/basenetworks.py:245-400``).
 * ``MobileNetV3``: torchvision's ``mobilenet_v3_large`` / ``mobilenet_v3_small`` feature extractors with the stride of the first
   convolution set to 1, stride 16 (reference ``network/basenetworks.py:432-446``, ``network/factory.py:53-56``).
 * ``SqueezeNet``: torchvision's ``squeezenet1_1`` features with padding 1 on the stem and on the ceil-mode max-pools, stride 16
@@ -374,23 +376,26 @@ def _channel_shuffle(x, groups=2):
 
 
 class _InvertedResidualK(nn.Module):
-    """ShuffleNetV2 unit with a k x k depthwise conv (reference ``basenetworks.py:186-268``)."""
+    """ShuffleNetV2 unit with a k x k depthwise conv (reference ``basenetworks.py:186-268``), optionally dilated (padding
+    ``(k - 1) // 2 * dilation``) and with ``nn.LeakyReLU`` (slope 0.01) in place of its ReLUs."""
 
-    def __init__(self, inp, oup, first_in_stage, *, stride=1, kernel_size=5):
+    def __init__(self, inp, oup, first_in_stage, *, stride=1, kernel_size=5, dilation=1, leaky_relu=False):
         super().__init__()
-        assert stride in (1, 2) and (stride != 1 or inp == oup)
+        assert stride in (1, 2) and (stride != 1 or inp == oup or first_in_stage)
         self.first_in_stage = first_in_stage
+        self.leaky_relu = bool(leaky_relu)
         bf = oup // 2
-        pad = (kernel_size - 1) // 2
+        pad = (kernel_size - 1) // 2 * dilation
+        act = nn.LeakyReLU if leaky_relu else nn.ReLU
         self.branch1 = None
         if first_in_stage:
             self.branch1 = nn.Sequential(
-                nn.Conv2d(inp, inp, kernel_size, stride, pad, groups=inp, bias=False), nn.BatchNorm2d(inp),
-                nn.Conv2d(inp, bf, 1, bias=False), nn.BatchNorm2d(bf), nn.ReLU(inplace=True))
+                nn.Conv2d(inp, inp, kernel_size, stride, pad, dilation, groups=inp, bias=False), nn.BatchNorm2d(inp),
+                nn.Conv2d(inp, bf, 1, bias=False), nn.BatchNorm2d(bf), act(inplace=True))
         self.branch2 = nn.Sequential(
-            nn.Conv2d(inp if first_in_stage else bf, bf, 1, bias=False), nn.BatchNorm2d(bf), nn.ReLU(inplace=True),
-            nn.Conv2d(bf, bf, kernel_size, stride, pad, groups=bf, bias=False), nn.BatchNorm2d(bf),
-            nn.Conv2d(bf, bf, 1, bias=False), nn.BatchNorm2d(bf), nn.ReLU(inplace=True))
+            nn.Conv2d(inp if first_in_stage else bf, bf, 1, bias=False), nn.BatchNorm2d(bf), act(inplace=True),
+            nn.Conv2d(bf, bf, kernel_size, stride, pad, dilation, groups=bf, bias=False), nn.BatchNorm2d(bf),
+            nn.Conv2d(bf, bf, 1, bias=False), nn.BatchNorm2d(bf), act(inplace=True))
 
     fused = False
 
@@ -418,21 +423,27 @@ class _InvertedResidualK(nn.Module):
     @staticmethod
     def _dw_ok(m, x):
         """Can the convolution ``m`` of a branch run through the stencil kernel on ``x``?"""
-        return hasattr(m, 'w_taps') and m.weight.dtype == x.dtype and fused.dwconv_supported(x, m.kernel_size[0], m.stride[0])
+        k, d = m.kernel_size[0], m.dilation[0]
+        return (hasattr(m, 'w_taps') and m.weight.dtype == x.dtype and m.padding[0] == m.padding[1] == k // 2 * d
+                and fused.dwconv_supported(x, k, m.stride[0], d))
 
     @staticmethod
     def _run(branch, x):
         for m in branch:
             if isinstance(m, nn.Conv2d) and _InvertedResidualK._dw_ok(m, x):
-                x = fused.dwconv_bias_act(x, _InvertedResidualK.taps_of(m), m.bias, m.kernel_size[0], m.stride[0])
+                x = fused.dwconv_bias_act(x, _InvertedResidualK.taps_of(m), m.bias, m.kernel_size[0], m.stride[0],
+                                          dilation=m.dilation[0])
             else:
                 x = m(x)
         return x
 
     def _unit_route_supported(self, x):
         """Can the WHOLE unit run on the project's kernels alone (``_forward_unit``)?  Every 1x1 convolution through the
-        split-operand GEMM's unit mode, every depthwise convolution through the stencil kernel."""
+        split-operand GEMM's unit mode, every depthwise convolution through the stencil kernel.  The GEMM's epilogue applies a ReLU:
+        a unit with another non-linearity (``leaky_relu``) takes ``_forward_fused``."""
         if not (x.dtype == torch.float32 and x.dim() == 4):
+            return False
+        if self.leaky_relu:
             return False
         branches = (self.branch2,) if self.branch1 is None else (self.branch1, self.branch2)
         for branch in branches:
@@ -448,7 +459,7 @@ class _InvertedResidualK(nn.Module):
         return fused.unit_conv_x3_supported(self.branch2[0], first)
 
     def _dw(self, m, x):
-        return fused.dwconv_bias_act(x, self.taps_of(m), m.bias, m.kernel_size[0], m.stride[0])
+        return fused.dwconv_bias_act(x, self.taps_of(m), m.bias, m.kernel_size[0], m.stride[0], dilation=m.dilation[0])
 
     def _forward_unit(self, x):
         """Three launches (five in a first unit): GEMM + bias + ReLU on the channel slice, the depthwise stencil, GEMM + bias + ReLU
@@ -483,29 +494,96 @@ class _InvertedResidualK(nn.Module):
 
 
 class ShuffleNetV2K(BaseNetwork):
-    """ShuffleNetV2 with 5x5 depthwise kernels, stride 16 (reference ``basenetworks.py:271-355``)."""
+    """ShuffleNetV2 with 5x5 depthwise kernels, stride 16 (reference ``basenetworks.py:271-355``), with the reference's options
+    (``network/basenetworks.py:245-400``); each keyword defaults to the class attribute of its name, which ``configure`` sets from
+    the command line.  The reference's quirks are kept:
+
+    * ``input_conv2_stride`` != 0: ``input_block.3 = Sequential(Conv2d(c0, out, 3, 2, 1), BatchNorm2d, non-linearity)`` with
+      ``out = input_conv2_outchannels or c0``; the convolution's stride is 2 WHATEVER the option's value, and the overall stride
+      doubles.
+    * ``stage4_dilation`` d > 1: the first unit of stage 4 has stride 1 and every depthwise convolution of the stage dilation d;
+      the overall stride is halved.
+    * ``kernel_width`` k (odd): the depthwise kernel of every unit, padding ``(k - 1) // 2 * dilation``.
+    * ``conv5_as_stage``: ``conv5`` is two units with dilation ``stage4_dilation``, the first a first-in-stage unit if and only if
+      the widths differ.
+    * ``leaky_relu``: ``nn.LeakyReLU(inplace=True)`` wherever the network has a ReLU.
+
+    The reference's instance and group norms are not offered: neither folds into a convolution."""
     CONFIGS = {
         'shufflenetv2k16': ([4, 8, 4], [24, 348, 696, 1392, 1392]),
         'shufflenetv2k20': ([5, 10, 5], [32, 512, 1024, 2048, 2048]),
         'shufflenetv2k30': ([8, 16, 6], [32, 512, 1024, 2048, 2048]),
         'shufflenetv2k44': ([12, 24, 8], [32, 512, 1024, 2048, 2048]),
+        'shufflenetv2kx5': ([6, 13, 6], [42, 640, 1280, 2560, 2560]),
     }
+    input_conv2_stride = 0
+    input_conv2_outchannels = None
+    stage4_dilation = 1
+    kernel_width = 5
+    conv5_as_stage = False
+    leaky_relu = False
+    OPTIONS = ('input_conv2_stride', 'input_conv2_outchannels', 'stage4_dilation', 'kernel_width', 'conv5_as_stage', 'leaky_relu')
 
-    def __init__(self, name='shufflenetv2k16'):
-        repeats, ch = self.CONFIGS[name]
-        super().__init__(name, stride=16, out_features=ch[-1])
-        self.input_block = nn.Sequential(
-            nn.Conv2d(3, ch[0], 3, 2, 1, bias=False), nn.BatchNorm2d(ch[0]), nn.ReLU(inplace=True))
-        stages, inp = [], ch[0]
-        for rep, oup in zip(repeats, ch[1:4]):
+    def __init__(self, name='shufflenetv2k16', *, input_conv2_stride=None, input_conv2_outchannels=None, stage4_dilation=None,
+                 kernel_width=None, conv5_as_stage=None, leaky_relu=None, config=None):
+        given = dict(zip(self.OPTIONS, (input_conv2_stride, input_conv2_outchannels, stage4_dilation, kernel_width, conv5_as_stage,
+                                        leaky_relu)))
+        input_conv2_stride, input_conv2_outchannels, stage4_dilation, kernel_width, conv5_as_stage, leaky_relu = (
+            getattr(type(self), k) if v is None else v for k, v in given.items())
+        assert kernel_width % 2 == 1 and stage4_dilation >= 1
+        repeats, ch = config or self.CONFIGS[name]          # (``config``: (stage repeats, five channel counts) of a network of one's own)
+        stride = 16
+        if input_conv2_stride:
+            stride *= 2
+        if stage4_dilation != 1:
+            stride //= 2
+        super().__init__(name, stride=stride, out_features=ch[-1])
+        for option in self.OPTIONS:
+            setattr(self, option, locals()[option])
+        act = nn.LeakyReLU if leaky_relu else nn.ReLU
+        unit = dict(kernel_size=kernel_width, leaky_relu=leaky_relu)
+        input_modules = [nn.Conv2d(3, ch[0], 3, 2, 1, bias=False), nn.BatchNorm2d(ch[0]), act(inplace=True)]
+        inp = ch[0]
+        if input_conv2_stride:
+            out = input_conv2_outchannels or inp
+            input_modules.append(nn.Sequential(nn.Conv2d(inp, out, 3, 2, 1, bias=False), nn.BatchNorm2d(out), act(inplace=True)))
+            inp = out
+        self.input_block = nn.Sequential(*input_modules)
+        stages = []
+        for rep, oup, dilation in zip(repeats, ch[1:4], (1, 1, stage4_dilation)):
             # the first stage keeps resolution (the reference drops the max-pool and uses stride 16)
-            seq = [_InvertedResidualK(inp, oup, True, stride=2)]
-            seq += [_InvertedResidualK(oup, oup, False) for _ in range(rep - 1)]
+            seq = [_InvertedResidualK(inp, oup, True, stride=2 if dilation == 1 else 1, dilation=dilation, **unit)]
+            seq += [_InvertedResidualK(oup, oup, False, dilation=dilation, **unit) for _ in range(rep - 1)]
             stages.append(nn.Sequential(*seq))
             inp = oup
         self.stage2, self.stage3, self.stage4 = stages
-        self.conv5 = nn.Sequential(
-            nn.Conv2d(inp, ch[-1], 1, bias=False), nn.BatchNorm2d(ch[-1]), nn.ReLU(inplace=True))
+        if conv5_as_stage:
+            self.conv5 = nn.Sequential(_InvertedResidualK(inp, ch[-1], inp != ch[-1], dilation=stage4_dilation, **unit),
+                                       _InvertedResidualK(ch[-1], ch[-1], False, dilation=stage4_dilation, **unit))
+        else:
+            self.conv5 = nn.Sequential(
+                nn.Conv2d(inp, ch[-1], 1, bias=False), nn.BatchNorm2d(ch[-1]), act(inplace=True))
+
+    @classmethod
+    def cli(cls, parser):
+        """The reference's flags (``network/basenetworks.py:357-384``) but ``--shufflenetv2k-instance-norm`` and
+        ``--shufflenetv2k-group-norm``: those norms do not fold into a convolution."""
+        group = parser.add_argument_group('shufflenetv2k')
+        group.add_argument('--shufflenetv2k-input-conv2-stride', default=cls.input_conv2_stride, type=int,
+                           help='stride of the optional 2nd input convolution')
+        group.add_argument('--shufflenetv2k-input-conv2-outchannels', default=cls.input_conv2_outchannels, type=int,
+                           help='out channels of the optional 2nd input convolution')
+        group.add_argument('--shufflenetv2k-stage4-dilation', default=cls.stage4_dilation, type=int,
+                           help='dilation factor of stage 4')
+        group.add_argument('--shufflenetv2k-kernel', default=cls.kernel_width, type=int, help='kernel width')
+        group.add_argument('--shufflenetv2k-conv5-as-stage', default=False, action='store_true')
+        group.add_argument('--shufflenetv2k-leaky-relu', default=False, action='store_true')
+
+    @classmethod
+    def configure(cls, args):
+        for option in cls.OPTIONS:             # (a namespace from a parser without these flags leaves the attributes as they are)
+            flag = 'shufflenetv2k_' + ('kernel' if option == 'kernel_width' else option)
+            setattr(cls, option, getattr(args, flag, getattr(cls, option)))
 
     fused = False
 
@@ -516,7 +594,9 @@ class ShuffleNetV2K(BaseNetwork):
     def forward(self, x):
         x = self.stage4(self.stage3(self.stage2(self.input_block(x))))
         conv = self.conv5[0]
-        if self.fused and x.is_cuda and fused.unit_conv_x3_supported(conv, x):
+        # (a stage ``conv5`` routes itself, unit by unit; the GEMM's epilogue applies a ReLU, so a LeakyReLU stays with torch)
+        if (self.fused and x.is_cuda and isinstance(conv, nn.Conv2d) and isinstance(self.conv5[2], nn.ReLU)
+                and fused.unit_conv_x3_supported(conv, x)):
             return fused.pick('unit', fused.out_pixels(x), conv.in_channels, conv.out_channels, False, False,
                               lambda: fused.conv1x1_unit_x3(conv, x), lambda: self.conv5(x), timing=False)
         return self.conv5(x)

@@ -509,6 +509,7 @@ class Predictor:
                            help='rescale, pad and normalise the uint8 frames on the GPU instead of with PIL on the host')
         group.add_argument('--basenet', default=cls.base_name, choices=sorted(network.BASE_FACTORIES))
         network.Resnet.cli(parser)
+        network.ShuffleNetV2K.cli(parser)
 
     @classmethod
     def configure(cls, args: argparse.Namespace):
@@ -518,6 +519,7 @@ class Predictor:
         cls.device_preprocess = getattr(args, 'device_preprocess', cls.device_preprocess)
         cls.base_name = getattr(args, 'basenet', cls.base_name)
         network.Resnet.configure(args)
+        network.ShuffleNetV2K.configure(args)
         if getattr(args, 'device', None) is not None:
             cls.device = args.device
 
