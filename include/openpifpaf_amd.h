@@ -536,6 +536,18 @@ int opa_gemm_unit_act_f32x3(const float* a_dev, int64_t a_pitch, const void* w3_
                             const float* partner_dev, int64_t partner_pitch, const float* residual_dev, int64_t residual_pitch,
                             float* out_dev, int64_t m, int32_t n, int32_t k, int32_t act, int32_t terms, void* stream);
 
+/* The same with two more activation codes, each with one parameter -- MobileNetV2's ReLU6 (reference network/basenetworks.py:407-430)
+ * and the LeakyReLU of a ShuffleNetV2K unit (network/basenetworks.py:186-268):
+ *     act 3 LeakyReLU:    x < 0 ? x * act_param : x                               (act_param: the slope, finite and >= 0)
+ *     act 4 clipped ReLU: x < 0 ? 0 : (x > act_param ? act_param : x)             (act_param: the cap, finite and > 0; ReLU6 is 6)
+ * both selects in float32 behind the bias, the last operation before the store: NaN stays NaN, and the result is that function of
+ * the act 0 result bit for bit.  With a partner the partner's bits pass through as above.  act 0 .. 2 ignore act_param (which must
+ * still be finite) and run opa_gemm_unit_act_f32x3's kernels.  A residual together with act 3 or 4 is refused, like everything
+ * opa_gemm_unit_act_f32x3 refuses. */
+int opa_gemm_unit_actp_f32x3(const float* a_dev, int64_t a_pitch, const void* w3_dev, const float* bias_dev,
+                             const float* partner_dev, int64_t partner_pitch, const float* residual_dev, int64_t residual_pitch,
+                             float* out_dev, int64_t m, int32_t n, int32_t k, int32_t act, float act_param, int32_t terms, void* stream);
+
 /* 3x3 convolution, stride 1, padding 1, of an NHWC float32 activation as Winograd F(2x2, 3x3) in ONE kernel (input
  * transform -> sixteen float32 MFMA GEMMs -> output transform; csrc/winograd.hip): the bottleneck convolutions of the
  * ResNet trunk (reference network/basenetworks.py:71-150 runs them through torch.nn.Conv2d), 2.25x fewer multiplications
@@ -582,6 +594,14 @@ int opa_dwconv_act(const void* x_dev, int64_t x_pixel_stride, const void* w_dev,
 int opa_dwconv_dilated_act(const void* x_dev, int64_t x_pixel_stride, const void* w_dev, const void* bias_dev,
                            void* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w,
                            int32_t channels, int32_t k, int32_t stride, int32_t dilation, int32_t dtype, int32_t act, void* stream);
+
+/* The same stencil with one more activation code -- the depthwise convolutions of a MobileNetV2 block (reference
+ * network/basenetworks.py:407-430): act 4, the ReLU clipped at act_param (x < 0 ? 0 : (x > act_param ? act_param : x) in float32,
+ * in bfloat16 before the rounding; act_param finite and > 0, ReLU6 is 6).  act 0 .. 2 ignore act_param (which must still be finite)
+ * and give opa_dwconv_dilated_act's results bit for bit; act 3 and everything opa_dwconv_dilated_act refuses are refused. */
+int opa_dwconv_actp(const void* x_dev, int64_t x_pixel_stride, const void* w_dev, const void* bias_dev,
+                    void* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w,
+                    int32_t channels, int32_t k, int32_t stride, int32_t dilation, int32_t dtype, int32_t act, float act_param, void* stream);
 
 /* Grouped 3x3 convolution, padding 1, dilation 1, stride 1 or 2, as many output as input channels, float32, channels innermost,
  * with the folded batch-norm bias and optionally ReLU (fmaxf) applied before the single store: the middle convolution of a

@@ -157,6 +157,8 @@ SYMBOLS = {
     'opa_gemm_bias_act_f32x3': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     'opa_gemm_unit_bias_act_f32x3': (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     'opa_gemm_unit_act_f32x3': (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
+    'opa_gemm_unit_actp_f32x3': (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, ctypes.c_float, _i32,
+                                                _vp]),
     'opa_conv_rows_f32x3': (ctypes.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 12 + [_vp]),
     'opa_conv3x3_f32x3': (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     'opa_conv3x3_dilated_f32x3': (ctypes.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 9 + [_vp]),
@@ -169,6 +171,8 @@ SYMBOLS = {
     'opa_dwconv_bias_act': (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     'opa_dwconv_act': (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     'opa_dwconv_dilated_act': (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    'opa_dwconv_actp': (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.c_float,
+                                       _vp]),
     'opa_gconv3x3_bias_act_f32': (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     'opa_se_workspace_bytes': (_sz, [_i32, _i64, _i32]),
     'opa_se_pool': (ctypes.c_int, [_vp, _i64, _i32, _i64, _i32, _vp, _sz, _vp]),

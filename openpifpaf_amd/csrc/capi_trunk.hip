@@ -226,16 +226,21 @@ int opa_fire_expand_f32x3(const float* h_dev, const void* w_dev, const float* bi
                                          E.st), "fire_expand_f32x3", "fire_expand_kernel");
 }
 
-// opa_gemm_unit_act_f32x3, and opa_gemm_unit_bias_act_f32x3 as its call without a residual and with act 0 / 1 (`eight`: the
-// pointers the alignment message names, `where`: the launch in a HIP error's text)
-static int gemm_unit_f32x3(const char* fn, const char* eight, const char* where, const float* a_dev, int64_t a_pitch, const void* w3_dev,
+// opa_gemm_unit_actp_f32x3; opa_gemm_unit_act_f32x3 as its call with act 0 .. 2 (`act_max`) and no parameter, and
+// opa_gemm_unit_bias_act_f32x3 as that one's call without a residual and with act 0 / 1 (`eight`: the pointers the alignment
+// message names, `where`: the launch in a HIP error's text).  act 3 (LeakyReLU) and 4 (clipped ReLU) read act_param.
+static int gemm_unit_f32x3(const char* fn, const char* eight, const char* where, int32_t act_max, float act_param, const float* a_dev, int64_t a_pitch, const void* w3_dev,
                            const float* bias_dev, const float* partner_dev, int64_t partner_pitch, const float* residual_dev,
                            int64_t residual_pitch, float* out_dev, int64_t m, int32_t n, int32_t k, int32_t act, int32_t terms,
                            void* stream) {
     const Entry E(fn, stream);
-    if (!a_dev || !w3_dev || !bias_dev || !out_dev || m < 0 || n <= 0 || k <= 0 || m > 0x7fffffffll || bad_terms(terms) || act < 0 || act > 2)
+    if (!a_dev || !w3_dev || !bias_dev || !out_dev || m < 0 || n <= 0 || k <= 0 || m > 0x7fffffffll || bad_terms(terms) || act < 0 || act > act_max)
         return E.refuse("bad arguments");
+    if (!std::isfinite(act_param)) return E.refuse("act_param must be finite");
+    if (act == 3 && act_param < 0.0f) return E.refuse("act_param must not be negative with act 3 (the LeakyReLU's slope)");
+    if (act == 4 && act_param <= 0.0f) return E.refuse("act_param must be positive with act 4 (the clipped ReLU's cap)");
     if (partner_dev && residual_dev) return E.refuse("a residual cannot be combined with a partner");
+    if (residual_dev && act > 2) return E.refuse("a residual cannot be combined with act 3 or 4");
     if (n % 2 != 0 || k % 2 != 0) return E.refuse("K and N must be even");
     // (a tile's 128 rows are addressed with 32-bit byte offsets: 2^21 floats per row leave room)
     if (a_pitch < k || a_pitch % 2 != 0 || a_pitch > (1 << 21) ||
@@ -247,21 +252,29 @@ static int gemm_unit_f32x3(const char* fn, const char* eight, const char* where,
     if (m == 0) return OPA_OK;
     return E.launched(launch_gemm_unit_act_f32x3(a_dev, (int)a_pitch, (const unsigned short*)w3_dev, bias_dev, partner_dev,
                                                  partner_dev ? (int)partner_pitch : 0, residual_dev, residual_dev ? (int)residual_pitch : 0,
-                                                 out_dev, (int)m, n, k, act, terms, E.st), where, "gemm_unit_f32x3_kernel");
+                                                 out_dev, (int)m, n, k, act, terms, E.st, act_param), where, "gemm_unit_f32x3_kernel");
 }
 
 int opa_gemm_unit_bias_act_f32x3(const float* a_dev, int64_t a_pitch, const void* w3_dev, const float* bias_dev,
                                  const float* partner_dev, int64_t partner_pitch, float* out_dev,
                                  int64_t m, int32_t n, int32_t k, int32_t relu, int32_t terms, void* stream) {
-    return gemm_unit_f32x3("opa_gemm_unit_bias_act_f32x3", "a_dev / partner_dev", "gemm_unit_f32x3", a_dev, a_pitch, w3_dev, bias_dev,
+    return gemm_unit_f32x3("opa_gemm_unit_bias_act_f32x3", "a_dev / partner_dev", "gemm_unit_f32x3", 2, 0.0f, a_dev, a_pitch, w3_dev, bias_dev,
                            partner_dev, partner_pitch, nullptr, 0, out_dev, m, n, k, relu ? 1 : 0, terms, stream);
 }
 
 int opa_gemm_unit_act_f32x3(const float* a_dev, int64_t a_pitch, const void* w3_dev, const float* bias_dev,
                             const float* partner_dev, int64_t partner_pitch, const float* residual_dev, int64_t residual_pitch,
                             float* out_dev, int64_t m, int32_t n, int32_t k, int32_t act, int32_t terms, void* stream) {
-    return gemm_unit_f32x3("opa_gemm_unit_act_f32x3", "a_dev / partner_dev / residual_dev", "gemm_unit_act_f32x3", a_dev, a_pitch, w3_dev,
-                           bias_dev, partner_dev, partner_pitch, residual_dev, residual_pitch, out_dev, m, n, k, act, terms, stream);
+    return gemm_unit_f32x3("opa_gemm_unit_act_f32x3", "a_dev / partner_dev / residual_dev", "gemm_unit_act_f32x3", 2, 0.0f, a_dev, a_pitch,
+                           w3_dev, bias_dev, partner_dev, partner_pitch, residual_dev, residual_pitch, out_dev, m, n, k, act, terms, stream);
+}
+
+int opa_gemm_unit_actp_f32x3(const float* a_dev, int64_t a_pitch, const void* w3_dev, const float* bias_dev,
+                             const float* partner_dev, int64_t partner_pitch, const float* residual_dev, int64_t residual_pitch,
+                             float* out_dev, int64_t m, int32_t n, int32_t k, int32_t act, float act_param, int32_t terms, void* stream) {
+    return gemm_unit_f32x3("opa_gemm_unit_actp_f32x3", "a_dev / partner_dev / residual_dev", "gemm_unit_actp_f32x3", 4, act_param, a_dev,
+                           a_pitch, w3_dev, bias_dev, partner_dev, partner_pitch, residual_dev, residual_pitch, out_dev, m, n, k, act,
+                           terms, stream);
 }
 
 // opa_conv3x3_winograd_f32 and opa_conv3x3_winograd_f32x3 (`x3`: u_dev holds the three bf16 planes of the filter)
@@ -297,13 +310,17 @@ int opa_conv3x3_winograd_f32x3(const float* x_dev, const void* u3_dev, const flo
                             order, stream);
 }
 
-// opa_dwconv_act, opa_dwconv_bias_act as its call with act 0 / 1, and opa_dwconv_dilated_act (`dilated`: k = 7 and a dilation of 2
-// or 4 at stride 1 are accepted too; the other two pass dilation 1)
-static int dwconv(const char* fn, bool dilated, const void* x_dev, int64_t x_pixel_stride, const void* w_dev, const void* bias_dev,
+// opa_dwconv_act, opa_dwconv_bias_act as its call with act 0 / 1, opa_dwconv_dilated_act (`dilated`: k = 7 and a dilation of 2
+// or 4 at stride 1 are accepted too; the other two pass dilation 1) and opa_dwconv_actp (`actp`: act 4, the ReLU clipped at
+// act_param, is accepted too; the others pass no parameter)
+static int dwconv(const char* fn, bool dilated, bool actp, float act_param, const void* x_dev, int64_t x_pixel_stride, const void* w_dev, const void* bias_dev,
                   void* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w, int32_t channels, int32_t k, int32_t stride,
                   int32_t dilation, int32_t dtype, int32_t act, void* stream) {
     const Entry E(fn, stream);
-    if (act < 0 || act > 2) return E.refuse("act must be 0 (none), 1 (ReLU) or 2 (hardswish)");
+    if (actp ? (act < 0 || act > 4 || act == 3) : (act < 0 || act > 2))
+        return E.refuse(actp ? "act must be 0 (none), 1 (ReLU), 2 (hardswish) or 4 (clipped ReLU)" : "act must be 0 (none), 1 (ReLU) or 2 (hardswish)");
+    if (!std::isfinite(act_param)) return E.refuse("act_param must be finite");
+    if (act == 4 && act_param <= 0.0f) return E.refuse("act_param must be positive with act 4 (the clipped ReLU's cap)");
     const bool k_ok = k == 3 || k == 5 || (dilated && k == 7);
     const bool d_ok = dilation == 1 || (dilated && (dilation == 2 || dilation == 4) && stride == 1);
     if (!x_dev || !w_dev || !out_dev || batch <= 0 || h <= 0 || w <= 0 || channels <= 0 || x_pixel_stride < channels ||
@@ -313,27 +330,34 @@ static int dwconv(const char* fn, bool dilated, const void* x_dev, int64_t x_pix
     if ((int64_t)batch * (((int64_t)h + 2 * (k / 2) * dilation - dilation * (k - 1) - 1) / stride + 1) > 65535)
         return E.refuse("batch * output rows must not exceed 65535");
     return E.launched(launch_dwconv(x_dev, x_pixel_stride, w_dev, bias_dev, out_dev, out_pixel_stride, batch, h, w, channels, k, stride,
-                                    dilation, dtype, act, E.st), "depthwise convolution");
+                                    dilation, dtype, act, E.st, act_param), "depthwise convolution");
 }
 
 int opa_dwconv_bias_act(const void* x_dev, int64_t x_pixel_stride, const void* w_dev, const void* bias_dev,
                         void* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w,
                         int32_t channels, int32_t k, int32_t stride, int32_t dtype, int32_t relu, void* stream) {
-    return dwconv("opa_dwconv_bias_act", false, x_dev, x_pixel_stride, w_dev, bias_dev, out_dev, out_pixel_stride, batch, h, w, channels, k,
+    return dwconv("opa_dwconv_bias_act", false, false, 0.0f, x_dev, x_pixel_stride, w_dev, bias_dev, out_dev, out_pixel_stride, batch, h, w, channels, k,
                   stride, 1, dtype, relu != 0, stream);                                   // (relu: any non-zero)
 }
 
 int opa_dwconv_act(const void* x_dev, int64_t x_pixel_stride, const void* w_dev, const void* bias_dev,
                    void* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w,
                    int32_t channels, int32_t k, int32_t stride, int32_t dtype, int32_t act, void* stream) {
-    return dwconv("opa_dwconv_act", false, x_dev, x_pixel_stride, w_dev, bias_dev, out_dev, out_pixel_stride, batch, h, w, channels, k,
+    return dwconv("opa_dwconv_act", false, false, 0.0f, x_dev, x_pixel_stride, w_dev, bias_dev, out_dev, out_pixel_stride, batch, h, w, channels, k,
                   stride, 1, dtype, act, stream);
 }
 
 int opa_dwconv_dilated_act(const void* x_dev, int64_t x_pixel_stride, const void* w_dev, const void* bias_dev,
                            void* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w,
                            int32_t channels, int32_t k, int32_t stride, int32_t dilation, int32_t dtype, int32_t act, void* stream) {
-    return dwconv("opa_dwconv_dilated_act", true, x_dev, x_pixel_stride, w_dev, bias_dev, out_dev, out_pixel_stride, batch, h, w, channels,
+    return dwconv("opa_dwconv_dilated_act", true, false, 0.0f, x_dev, x_pixel_stride, w_dev, bias_dev, out_dev, out_pixel_stride, batch, h, w, channels,
+                  k, stride, dilation, dtype, act, stream);
+}
+
+int opa_dwconv_actp(const void* x_dev, int64_t x_pixel_stride, const void* w_dev, const void* bias_dev,
+                    void* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w,
+                    int32_t channels, int32_t k, int32_t stride, int32_t dilation, int32_t dtype, int32_t act, float act_param, void* stream) {
+    return dwconv("opa_dwconv_actp", true, true, act_param, x_dev, x_pixel_stride, w_dev, bias_dev, out_dev, out_pixel_stride, batch, h, w, channels,
                   k, stride, dilation, dtype, act, stream);
 }
 

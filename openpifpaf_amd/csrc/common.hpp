@@ -283,10 +283,12 @@ hipError_t launch_maxpool3x3(const void* x, const void* bias, void* out, int dty
 long long fire_expand_workgroups(int B, int H, int W);
 hipError_t launch_fire_expand(const float* h, const unsigned short* w3, const float* bias, float* out, int B, int H, int W, int S,
                               int E1, int E3, int terms, hipStream_t st);
-// the unit mode (gemm_f32x3.hip) with an activation code (0 none, 1 ReLU, 2 hardswish) and optionally a residual [M, N] with `ldr`
-// floats between rows (added before the activation; not together with a partner)
+// the unit mode (gemm_f32x3.hip) with an activation code (0 none, 1 ReLU, 2 hardswish, 3 LeakyReLU with slope `act_param`, 4 ReLU
+// clipped at `act_param`) and optionally a residual [M, N] with `ldr` floats between rows (added before the activation; not together
+// with a partner, nor with act 3 / 4)
 hipError_t launch_gemm_unit_act_f32x3(const float* A, int lda, const unsigned short* W3, const float* bias, const float* partner, int ldp,
-                                      const float* residual, int ldr, float* out, int M, int N, int K, int act, int terms, hipStream_t st);
+                                      const float* residual, int ldr, float* out, int M, int N, int K, int act, int terms, hipStream_t st,
+                                      float act_param = 0.0f);
 hipError_t launch_gemm_f32_bias_act(const float* A, const float* W, const float* bias, const float* res, float* out,
                                     int M, int N, int K, int relu, hipStream_t st, const float* a_bias = nullptr);
 hipError_t launch_winograd_f23(const float* x, const float* U, float* y, const float* bias, int N, int H, int W, int Cin,
@@ -294,9 +296,9 @@ hipError_t launch_winograd_f23(const float* x, const float* U, float* y, const f
 hipError_t launch_winograd_f23x3(const float* x, const unsigned short* U3, float* y, const float* bias, int N, int H, int W,
                                  int Cin, int Cout, int relu, int variant, int nb_major, hipStream_t st);
 
-// act: 0 none, 1 ReLU, 2 hardswish; K 3, 5 or 7, S 1 or 2, dilation D 1, or 2 or 4 with S = 1 (anything else: hipErrorInvalidValue)
+// act: 0 none, 1 ReLU, 2 hardswish, 4 ReLU clipped at `cap`; K 3, 5 or 7, S 1 or 2, dilation D 1, or 2 or 4 with S = 1 (anything else: hipErrorInvalidValue)
 hipError_t launch_dwconv(const void* x, long long xs, const void* w, const void* bias, void* out, long long os,
-                         int B, int H, int W, int C, int K, int S, int D, int dtype, int act, hipStream_t st);
+                         int B, int H, int W, int C, int K, int S, int D, int dtype, int act, hipStream_t st, float cap = 0.0f);
 hipError_t launch_channel_interleave(const void* a, long long as, const void* b, long long bs, void* out,
                                      long long rows, int half, int dtype, hipStream_t st);
 

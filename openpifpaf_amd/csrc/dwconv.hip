@@ -9,6 +9,8 @@
 // float32 accumulation, the folded batch-norm bias (and optionally ReLU) applied before the single store.
 // The MobileNetV3 blocks (reference network/basenetworks.py:432-446) use the same stencil with hardswish behind it: the
 // activation is then a template parameter (ACT = 2), so that the kernels with the run-time `relu` flag (ACT = -1) stay as they are.
+// MobileNetV2's ReLU6 (reference network/basenetworks.py:407-430) is a value of that run-time flag: 4 clips at `cap` with two selects
+// (x < 0 ? 0 : (x > cap ? cap : x): NaN stays NaN), the last float32 operation before the store -- in bfloat16 before the rounding.
 // That variant also keeps its 9 or 25 products in float64 and rounds once, behind the bias: a chain of 25 float32
 // multiply-adds came out at 1.5-3 times the error of torch's depthwise convolution + hardswish against float64.
 //
@@ -74,7 +76,7 @@ template <int V> struct DwVec<unsigned short, V> {               // bfloat16
 template <typename T, int K, int S, int V, int ACT = -1, int D = 1>
 __global__ __launch_bounds__(256) void dwconv_kernel(const T* __restrict__ x, long long xs, const T* __restrict__ w,
                                                      const T* __restrict__ bias, T* __restrict__ out, long long os,
-                                                     int H, int W, int C, int Ho, int Wo, int relu) {
+                                                     int H, int W, int C, int Ho, int Wo, int relu, float cap) {
     constexpr int P = K / 2;
     const int cvecs = C / V, strips = (Wo + kDwStrip - 1) / kDwStrip;
     const int item = blockIdx.x * 256 + threadIdx.x;
@@ -156,6 +158,7 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const T* __restrict__ x, lo
         for (int q = 0; q < V; q++) {
             o.v[q] = (float)(acc[i][q] + (Acc)bv.v[q]);
             if constexpr (ACT == 2) o.v[q] = hardswish_f32(o.v[q]);
+            else if (relu == 4) o.v[q] = o.v[q] < 0.0f ? 0.0f : (o.v[q] > cap ? cap : o.v[q]);
             else if (relu) o.v[q] = fmaxf(o.v[q], 0.0f);
         }
         o.store(out + (((size_t)b * Ho + y) * Wo + xo) * os + c);
@@ -180,19 +183,19 @@ __global__ __launch_bounds__(256) void channel_interleave_kernel(const T* __rest
     __builtin_memcpy(out + r * 2 * half + 2 * c, vo, sizeof(vo));
 }
 
-// act: 0 none, 1 ReLU (both the kernel with the run-time flag), 2 hardswish.  (K, S, D): 3, 5 or 7; 1 or 2; 1, or 2 or 4 at S = 1
+// act: 0 none, 1 ReLU, 4 ReLU clipped at `cap` (all three the kernel with the run-time flag), 2 hardswish.  (K, S, D): 3, 5 or 7; 1 or 2; 1, or 2 or 4 at S = 1
 template <typename T, int V>
 static hipError_t launch_dw_v(const void* x, long long xs, const void* w, const void* bias, void* out, long long os,
-                              int B, int H, int W, int C, int K, int S, int D, int act, hipStream_t st) {
+                              int B, int H, int W, int C, int K, int S, int D, int act, hipStream_t st, float cap) {
     const int P = K / 2;
     const int Ho = (H + 2 * P * D - D * (K - 1) - 1) / S + 1, Wo = (W + 2 * P * D - D * (K - 1) - 1) / S + 1;
     const long long items = (long long)(C / V) * ((Wo + kDwStrip - 1) / kDwStrip);
     dim3 grid((unsigned)((items + 255) / 256), B * Ho);
 #define OPA_DW(KK, SS, DD) do { \
         if (act == 2) dwconv_kernel<T, KK, SS, V, 2, DD><<<grid, 256, 0, st>>>((const T*)x, xs, (const T*)w, (const T*)bias, \
-                                                                               (T*)out, os, H, W, C, Ho, Wo, 0); \
+                                                                               (T*)out, os, H, W, C, Ho, Wo, 0, 0.0f); \
         else dwconv_kernel<T, KK, SS, V, -1, DD><<<grid, 256, 0, st>>>((const T*)x, xs, (const T*)w, (const T*)bias, \
-                                                                       (T*)out, os, H, W, C, Ho, Wo, act); } while (0)
+                                                                       (T*)out, os, H, W, C, Ho, Wo, act, cap); } while (0)
 #define OPA_DW_K(KK) do { \
         if (S == 1 && D == 1) OPA_DW(KK, 1, 1); \
         else if (S == 2 && D == 1) OPA_DW(KK, 2, 1); \
@@ -212,21 +215,21 @@ static hipError_t launch_dw_v(const void* x, long long xs, const void* w, const 
 // the widest channel vector the shapes and addresses allow
 template <typename T>
 static hipError_t launch_dw_t(const void* x, long long xs, const void* w, const void* bias, void* out, long long os,
-                              int B, int H, int W, int C, int K, int S, int D, int act, hipStream_t st) {
+                              int B, int H, int W, int C, int K, int S, int D, int act, hipStream_t st, float cap) {
     auto ok = [&](int v) {
         const size_t a = v * sizeof(T);
         return C % v == 0 && xs % v == 0 && os % v == 0 && (uintptr_t)x % a == 0 && (uintptr_t)out % a == 0 &&
                (uintptr_t)w % a == 0 && (!bias || (uintptr_t)bias % a == 0);
     };
-    if (ok(4)) return launch_dw_v<T, 4>(x, xs, w, bias, out, os, B, H, W, C, K, S, D, act, st);
-    if (ok(2)) return launch_dw_v<T, 2>(x, xs, w, bias, out, os, B, H, W, C, K, S, D, act, st);
-    return launch_dw_v<T, 1>(x, xs, w, bias, out, os, B, H, W, C, K, S, D, act, st);
+    if (ok(4)) return launch_dw_v<T, 4>(x, xs, w, bias, out, os, B, H, W, C, K, S, D, act, st, cap);
+    if (ok(2)) return launch_dw_v<T, 2>(x, xs, w, bias, out, os, B, H, W, C, K, S, D, act, st, cap);
+    return launch_dw_v<T, 1>(x, xs, w, bias, out, os, B, H, W, C, K, S, D, act, st, cap);
 }
 
 hipError_t launch_dwconv(const void* x, long long xs, const void* w, const void* bias, void* out, long long os,
-                         int B, int H, int W, int C, int K, int S, int D, int dtype, int act, hipStream_t st) {
-    if (dtype == 0) return launch_dw_t<float>(x, xs, w, bias, out, os, B, H, W, C, K, S, D, act, st);
-    if (dtype == 2) return launch_dw_t<unsigned short>(x, xs, w, bias, out, os, B, H, W, C, K, S, D, act, st);
+                         int B, int H, int W, int C, int K, int S, int D, int dtype, int act, hipStream_t st, float cap) {
+    if (dtype == 0) return launch_dw_t<float>(x, xs, w, bias, out, os, B, H, W, C, K, S, D, act, st, cap);
+    if (dtype == 2) return launch_dw_t<unsigned short>(x, xs, w, bias, out, os, B, H, W, C, K, S, D, act, st, cap);
     return hipErrorInvalidValue;
 }
 

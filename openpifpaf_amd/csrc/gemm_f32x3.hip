@@ -89,6 +89,7 @@ struct X3Second {
                                // memory (window origin = (stride oy, stride ox), every tap valid), 0: padding `dil` by the tap mask
     int dil;                   // (SRC = 2, not padded) dilation d: tap (ky, kx) reads input pixel (stride oy - d + d ky, stride ox - d + d kx)
     int lda, ldp, n_real, k_real;     // (UNIT) floats between rows of A and of the partner; the columns that exist of N and K
+    int act; float act_param;        // (UNIT, UX & 8) the activation read at run time: 3 LeakyReLU(slope), 4 clipped ReLU(cap)
 };
 
 // UNIT: the 1x1 convolutions of a ShuffleNetV2K unit (reference network/basenetworks.py:186-242) -- ANY even K and N, A a channel
@@ -104,10 +105,19 @@ struct X3Second {
 // with 8-byte loads, the epilogue works in column pairs -- a pair lies inside k_real / n_real or outside, never across.
 // UX (MobileNetV3's blocks, reference network/basenetworks.py:432-446; 0 for everything above): UX & 3 == 2 -- the activation is
 // hardswish (RELU false); UX & 4 -- `partner` is a RESIDUAL [M, n; row pitch ldp]: out[M, n] = act(A * W^T + bias + residual), dense rows.
+// UX & 8 (MobileNetV2's ReLU6, reference network/basenetworks.py:407-430, and the LeakyReLU of a ShuffleNetV2K unit, :186-268; RELU
+// false, never with a residual): the activation is read at run time -- `act` 3: x < 0 ? x * p : x, 4: x < 0 ? 0 : (x > p ? p : x),
+// p = `act_param` -- both selects, so that NaN stays NaN; one pair of instantiations serves both, the epilogue is not where the time goes.
+__device__ __forceinline__ float x3_act_param(float x, int act, float p) {
+    if (act == 3) return x < 0.0f ? x * p : x;
+    return x < 0.0f ? 0.0f : (x > p ? p : x);
+}
+
 template <int BN, bool PARTNER, bool RELU, int UX = 0>
 __device__ __forceinline__ void x3_unit_epilogue(float* smem_f, const f32x16_t (&acc)[2][BN / 64], const f32x16_t (&low)[2][BN / 64],
                                                  const float* __restrict__ bias, const float* __restrict__ partner,
-                                                 float* __restrict__ out, int M, int m0, int n0, int lane, int wave, int ldp, int n_real) {
+                                                 float* __restrict__ out, int M, int m0, int n0, int lane, int wave, int ldp, int n_real,
+                                                 int act, float act_param) {
     constexpr int WN = BN / 2, NT = WN / 32;
     constexpr int PPR = WN / 2;                // column pairs of a patch row
     constexpr int PPL = 32 * PPR / 64;         // ... per lane (16 | 8)
@@ -154,6 +164,7 @@ __device__ __forceinline__ void x3_unit_epilogue(float* smem_f, const f32x16_t (
                 }
                 if (RELU) { f[0] = fmaxf(f[0], 0.0f); f[1] = fmaxf(f[1], 0.0f); }
                 if constexpr ((UX & 3) == 2) { f[0] = hardswish_f32(f[0]); f[1] = hardswish_f32(f[1]); }
+                if constexpr ((UX & 8) != 0) { f[0] = x3_act_param(f[0], act, act_param); f[1] = x3_act_param(f[1], act, act_param); }
                 if (PARTNER && (UX & 4) == 0) { // the partner's bits pass through untouched
                     f32x2_t pp;
                     if (t < PPRE) pp = pv[t < PPRE ? t : 0];
@@ -401,7 +412,8 @@ __global__ __launch_bounds__(256, OPA_X3_WGS) void gemm_f32x3_bias_act_kernel(
     }
     // (the loop's last barrier: staging LDS is free, reuse it for the epilogue)
     if constexpr (UNIT) {
-        x3_unit_epilogue<BN, RES, RELU, UX>(reinterpret_cast<float*>(smem), acc, low, bias, res, out, M, m0, n0, lane, wave, sec.ldp, sec.n_real);
+        x3_unit_epilogue<BN, RES, RELU, UX>(reinterpret_cast<float*>(smem), acc, low, bias, res, out, M, m0, n0, lane, wave, sec.ldp, sec.n_real,
+                                            sec.act, sec.act_param);
         return;
     }
 
@@ -496,7 +508,7 @@ static hipError_t launch_x3_terms(const float* A, const unsigned short* W3, cons
 hipError_t launch_gemm_f32x3_bias_act(const float* A, const unsigned short* W3, const float* bias, const float* res, float* out,
                                       int M, int N, int K, int relu, int terms, hipStream_t st, const float* a_bias) {
     X3Second none; none.A2 = nullptr; none.K1 = K; none.ho_wo = none.wo = none.hi_wi = none.wi = none.stride = 1; none.hi = 1; none.C = 0; none.batch = 1;
-    none.pix = 1; none.taps_x = 1; none.ntaps = 1; none.padded = 0; none.dil = 1; none.lda = none.ldp = none.n_real = none.k_real = 0;
+    none.pix = 1; none.taps_x = 1; none.ntaps = 1; none.padded = 0; none.dil = 1; none.lda = none.ldp = none.n_real = none.k_real = 0; none.act = 0; none.act_param = 0.0f;
     if (terms == 6) return launch_x3_terms<6>(A, W3, bias, res, out, M, N, K, relu, st, a_bias, none);
     return launch_x3_terms<9>(A, W3, bias, res, out, M, N, K, relu, st, a_bias, none);
 }
@@ -507,7 +519,7 @@ hipError_t launch_gemm2_f32x3_bias_act(const float* A1, int K1, const float* A2,
                                        hipStream_t st, const float* a_bias) {
     const int ho = (hi - 1) / stride + 1, wo = (wi - 1) / stride + 1;
     X3Second sec; sec.A2 = A2; sec.K1 = K1; sec.ho_wo = ho * wo; sec.wo = wo; sec.hi_wi = hi * wi; sec.wi = wi; sec.stride = stride;
-    sec.hi = hi; sec.C = 0; sec.batch = batch; sec.pix = 1; sec.taps_x = 1; sec.ntaps = 1; sec.padded = 0; sec.dil = 1; sec.lda = sec.ldp = sec.n_real = sec.k_real = 0;
+    sec.hi = hi; sec.C = 0; sec.batch = batch; sec.pix = 1; sec.taps_x = 1; sec.ntaps = 1; sec.padded = 0; sec.dil = 1; sec.lda = sec.ldp = sec.n_real = sec.k_real = 0; sec.act = 0; sec.act_param = 0.0f;
     const int M = batch * ho * wo, K = K1 + K2;
     if (terms == 6) return launch_x3_terms<6>(A1, W3, bias, nullptr, out, M, N, K, relu, st, a_bias, sec);
     return launch_x3_terms<9>(A1, W3, bias, nullptr, out, M, N, K, relu, st, a_bias, sec);
@@ -534,6 +546,7 @@ static hipError_t launch_unit_bn(const float* a, const unsigned short* w, const 
 static X3Second unit_sec(int lda, int ldp, int N, int K) {
     X3Second sec; sec.A2 = nullptr; sec.K1 = K; sec.ho_wo = sec.wo = sec.hi_wi = sec.wi = sec.stride = 1; sec.hi = 1; sec.C = 0; sec.batch = 1;
     sec.pix = 1; sec.taps_x = 1; sec.ntaps = 1; sec.padded = 0; sec.dil = 1; sec.lda = lda; sec.ldp = ldp; sec.n_real = N; sec.k_real = K;
+    sec.act = 0; sec.act_param = 0.0f;
     return sec;
 }
 
@@ -552,13 +565,18 @@ struct UnitLaunch {
     template <int BN, int TERMS> hipError_t operator()(int Np, int Kp) const;
 };
 
-// The unit mode's instantiations with hardswish or a residual (see x3_unit_epilogue's UX); `third` is the partner or the residual.
+// The unit mode's instantiations with hardswish, a residual or a run-time activation (see x3_unit_epilogue's UX; act 3 / 4 are read
+// from `sec`); `third` is the partner or the residual.
 template <int BN, int TERMS>
 static hipError_t launch_unit_act_bn(const float* a, const unsigned short* w, const float* b, const float* third, bool residual, float* o,
                                      int M, int Np, int Kp, int act, hipStream_t st, const X3Second& sec) {
     const unsigned blocks = (unsigned)((long long)((M + kX3BM - 1) / kX3BM) * (Np / BN));
 #define OPA_UNIT_ACT(RES_, RELU_, UX_) gemm_f32x3_bias_act_kernel<BN, RES_, RELU_, false, TERMS, 0, true, UX_><<<blocks, 256, 0, st>>>(a, w, b, third, o, M, Np, Kp, nullptr, sec)
-    if (residual) {
+    if (act == 3 || act == 4) {
+        if (residual) return hipErrorInvalidValue;
+        if (third) OPA_UNIT_ACT(true, false, 8);
+        else OPA_UNIT_ACT(false, false, 8);
+    } else if (residual) {
         if (act == 2) OPA_UNIT_ACT(true, false, 6);
         else if (act == 1) OPA_UNIT_ACT(true, true, 4);
         else OPA_UNIT_ACT(true, false, 4);
@@ -572,16 +590,18 @@ static hipError_t launch_unit_act_bn(const float* a, const unsigned short* w, co
 }
 
 hipError_t launch_gemm_unit_act_f32x3(const float* A, int lda, const unsigned short* W3, const float* bias, const float* partner, int ldp,
-                                      const float* residual, int ldr, float* out, int M, int N, int K, int act, int terms, hipStream_t st) {
+                                      const float* residual, int ldr, float* out, int M, int N, int K, int act, int terms, hipStream_t st,
+                                      float act_param) {
     if (partner && residual) return hipErrorInvalidValue;
-    return unit_dispatch(N, K, terms, UnitLaunch{A, W3, bias, residual ? residual : partner, residual != nullptr, out, M, act, st,
-                                                 unit_sec(lda, residual ? ldr : ldp, N, K)});
+    X3Second sec = unit_sec(lda, residual ? ldr : ldp, N, K);
+    if (act == 3 || act == 4) { sec.act = act; sec.act_param = act_param; }
+    return unit_dispatch(N, K, terms, UnitLaunch{A, W3, bias, residual ? residual : partner, residual != nullptr, out, M, act, st, sec});
 }
 
 // act 0 / 1 without a residual: the instantiations the ShuffleNetV2K units use (launch_unit_bn)
 template <int BN, int TERMS>
 hipError_t UnitLaunch::operator()(int Np, int Kp) const {
-    if (!residual && act != 2) return launch_unit_bn<BN, TERMS>(a, w, b, third, o, M, Np, Kp, act, st, sec);
+    if (!residual && (act == 0 || act == 1)) return launch_unit_bn<BN, TERMS>(a, w, b, third, o, M, Np, Kp, act, st, sec);
     return launch_unit_act_bn<BN, TERMS>(a, w, b, third, residual, o, M, Np, Kp, act, st, sec);
 }
 
@@ -591,7 +611,7 @@ hipError_t launch_conv3x3_f32x3(const float* x, int batch, int hi, int wi, int C
                                 const float* bias, float* out, int N, int relu, int terms, hipStream_t st) {
     const int ho = (hi - 1) / stride + 1, wo = (wi - 1) / stride + 1;
     X3Second sec; sec.A2 = nullptr; sec.K1 = C; sec.ho_wo = ho * wo; sec.wo = wo; sec.hi_wi = hi * wi; sec.wi = wi; sec.stride = stride;
-    sec.hi = hi; sec.C = C; sec.batch = batch; sec.pix = C; sec.taps_x = 3; sec.ntaps = 9; sec.padded = 0; sec.dil = dilation; sec.lda = sec.ldp = sec.n_real = sec.k_real = 0;
+    sec.hi = hi; sec.C = C; sec.batch = batch; sec.pix = C; sec.taps_x = 3; sec.ntaps = 9; sec.padded = 0; sec.dil = dilation; sec.lda = sec.ldp = sec.n_real = sec.k_real = 0; sec.act = 0; sec.act_param = 0.0f;
     const int M = batch * ho * wo, K = 9 * C;
     if (terms == 6) return launch_x3_terms<6>(x, W3, bias, nullptr, out, M, N, K, relu, st, nullptr, sec);
     return launch_x3_terms<9>(x, W3, bias, nullptr, out, M, N, K, relu, st, nullptr, sec);
@@ -604,7 +624,7 @@ hipError_t launch_conv3x3_f32x3(const float* x, int batch, int hi, int wi, int C
 hipError_t launch_convrows_f32x3(const float* x, int batch, int hp, int wp, int pix, int ho, int wo, int stride, int ntaps, int tap_floats,
                                  const unsigned short* W3, const float* bias, float* out, int N, int relu, int terms, hipStream_t st) {
     X3Second sec; sec.A2 = nullptr; sec.K1 = tap_floats; sec.ho_wo = ho * wo; sec.wo = wo; sec.hi_wi = hp * wp; sec.wi = wp; sec.stride = stride;
-    sec.hi = hp; sec.C = tap_floats; sec.batch = batch; sec.pix = pix; sec.taps_x = 1; sec.ntaps = ntaps; sec.padded = 1; sec.dil = 1; sec.lda = sec.ldp = sec.n_real = sec.k_real = 0;
+    sec.hi = hp; sec.C = tap_floats; sec.batch = batch; sec.pix = pix; sec.taps_x = 1; sec.ntaps = ntaps; sec.padded = 1; sec.dil = 1; sec.lda = sec.ldp = sec.n_real = sec.k_real = 0; sec.act = 0; sec.act_param = 0.0f;
     const int M = batch * ho * wo, K = ntaps * tap_floats;
     if (terms == 6) return launch_x3_terms<6>(x, W3, bias, nullptr, out, M, N, K, relu, st, nullptr, sec);
     return launch_x3_terms<9>(x, W3, bias, nullptr, out, M, N, K, relu, st, nullptr, sec);

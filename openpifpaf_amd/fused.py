@@ -17,6 +17,9 @@ from .native import _ptr, _stream
 
 _DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 ACT_NONE, ACT_RELU, ACT_HARDSWISH = 0, 1, 2      # the activation codes of opa_dwconv_act and opa_gemm_unit_act_f32x3
+# ... and the two with a parameter (``act_param``), which only opa_gemm_unit_actp_f32x3 and opa_dwconv_actp take: LeakyReLU(slope)
+# (the GEMM alone) and the ReLU clipped at a cap (ReLU6: 6)
+ACT_LEAKY_RELU, ACT_RELU6 = 3, 4
 
 
 # ---- the launcher ---------------------------------------------------------------------------------------------------------------
@@ -81,6 +84,14 @@ FIRE = _switch('OPA_FIRE', '0')
 # (tools/gpu/squeezenet_terms.py, profiles/squeezenet/terms.log) the field outputs are 4e-7 ... 6e-7 of their size too small with six
 # terms -- 0.9 ... 2.4 times the largest error of torch's own float32 forward -- and 0.4 ... 1.0 times that error with nine.
 FIRE_TERMS = 9
+# The MobileNetV2 blocks and last convolution on the project's kernels (network._MBV2Block._forward_unit: the unit-mode GEMM with
+# ReLU6 for the expanding convolution, the depthwise stencil with ReLU6, the unit-mode GEMM with the block's input as the residual):
+# OPA_MBV2=1 (or fused.MBV2 = True) switches the route on.  It ships OFF -- the plain torch forward; the one timing is
+# tools/gpu/mobilenetv2_times.py, profiles/mobilenetv2/times.log, and switching the default is a change of its own that rests on it.
+MBV2 = _switch('OPA_MBV2', '0')
+# The 1x1 convolutions of a LeakyReLU ShuffleNetV2K unit and a LeakyReLU conv5 through the unit-mode GEMM (the LeakyReLU in its
+# epilogue) instead of torch: OPA_UNIT_LEAKY=1 (or fused.UNIT_LEAKY = True).  Off by default, timed by the same tool into the same log.
+UNIT_LEAKY = _switch('OPA_UNIT_LEAKY', '0')
 
 
 # ---- the choice table and the decision ---------------------------------------------------------------------------------------------
@@ -661,7 +672,7 @@ def unit_conv_x3_supported(conv, x, partner=None, residual=None):
     return True
 
 
-def conv1x1_unit_x3(conv, x, relu=True, partner=None, residual=None, act=None, terms=None):
+def conv1x1_unit_x3(conv, x, relu=True, partner=None, residual=None, act=None, terms=None, act_param=0.0):
     """``act(conv(x))`` for a biased 1x1 convolution of ANY even channel counts on a channels-last tensor or channel slice
     (reference ``network/basenetworks.py:186-242``: the 1x1 convolutions of a ShuffleNetV2K unit, folded with their batch norms),
     through the split-operand GEMM's unit mode (``opa_gemm_unit_act_f32x3``).  With ``partner`` (``[B, N, H, W]``, may be a
@@ -670,14 +681,23 @@ def conv1x1_unit_x3(conv, x, relu=True, partner=None, residual=None, act=None, t
 
     ``act`` (``ACT_NONE`` / ``ACT_RELU`` / ``ACT_HARDSWISH``) instead of ``relu``, and ``residual`` (``[B, N, H, W]``, may be a slice,
     never together with a partner): ``act(conv(x) + residual)`` in the same launch -- the 1x1 convolutions of a MobileNetV3 block.
-    ``terms``: 6 or 9 instead of ``X3_TERMS`` (the squeeze of a SqueezeNet Fire: ``FIRE_TERMS``)."""
+    ``terms``: 6 or 9 instead of ``X3_TERMS`` (the squeeze of a SqueezeNet Fire: ``FIRE_TERMS``).
+    ``act`` ``ACT_LEAKY_RELU`` / ``ACT_RELU6`` with ``act_param`` (the slope / the cap; never with a residual) -- a LeakyReLU unit, the
+    expanding and the last convolution of MobileNetV2 -- go to ``opa_gemm_unit_actp_f32x3``, the same kernel; every other code to the
+    symbol it has always gone to."""
     w3, bp = _unit_weight_of(conv)
     n = conv.out_channels
     out = _empty_nhwc(x, n if partner is None else 2 * n, dtype=torch.float32)
-    _launch('opa_gemm_unit_act_f32x3', _ptr(x), _pixel_stride(x), _ptr(w3), _ptr(bp),
-            _ptr(partner), _pixel_stride(partner) if partner is not None else 0,
-            _ptr(residual), _pixel_stride(residual) if residual is not None else 0,
-            _ptr(out), out_pixels(x), n, x.shape[1], _act_code(relu, act), int(X3_TERMS if terms is None else terms))
+    code = _act_code(relu, act)
+    operands = (_ptr(x), _pixel_stride(x), _ptr(w3), _ptr(bp),
+                _ptr(partner), _pixel_stride(partner) if partner is not None else 0,
+                _ptr(residual), _pixel_stride(residual) if residual is not None else 0,
+                _ptr(out), out_pixels(x), n, x.shape[1], code)
+    terms = int(X3_TERMS if terms is None else terms)
+    if code in (ACT_LEAKY_RELU, ACT_RELU6):
+        _launch('opa_gemm_unit_actp_f32x3', *operands, float(act_param), terms)
+    else:
+        _launch('opa_gemm_unit_act_f32x3', *operands, terms)
     return out
 
 
@@ -851,15 +871,19 @@ def dwconv_supported(x, kernel_size, stride, dilation=1):
             and _pixel_stride(x) is not None and _lib.available())
 
 
-def dwconv_bias_act(x, w_taps, bias, kernel_size, stride, relu=False, act=None, dilation=1):
+def dwconv_bias_act(x, w_taps, bias, kernel_size, stride, relu=False, act=None, dilation=1, act_param=0.0):
     """Depthwise ``kernel_size`` x ``kernel_size`` convolution (padding k//2 times the dilation) + bias (+ activation) of a
     channels-last activation or channel slice, one HIP stencil kernel.  ``w_taps``: ``[k*k, C]`` (tap-major,
     ``depthwise_taps``) in ``x``'s dtype.  ``act`` (``ACT_NONE`` / ``ACT_RELU`` / ``ACT_HARDSWISH``) instead of ``relu``.
     A 3 x 3 or 5 x 5 window without dilation goes to ``opa_dwconv_act``, a 7 x 7 window or a dilation of 2 or 4 (stride 1) to
-    ``opa_dwconv_dilated_act``: the same kernel template."""
+    ``opa_dwconv_dilated_act``: the same kernel template; ``act`` ``ACT_RELU6`` with ``act_param`` (the cap) -- the depthwise
+    convolution of a MobileNetV2 block -- to ``opa_dwconv_actp``, whatever the window."""
     B, C, H, W = x.shape
     out = _empty_nhwc(x, C, dwconv_out_hw(H, W, kernel_size, stride, dilation))
-    if kernel_size in (3, 5) and dilation == 1:
+    if _act_code(relu, act) == ACT_RELU6:
+        _launch('opa_dwconv_actp', _ptr(x), _pixel_stride(x), _ptr(w_taps), _ptr(bias), _ptr(out), C, B, H, W, C, kernel_size,
+                stride, dilation, _DTYPES[x.dtype], ACT_RELU6, float(act_param))
+    elif kernel_size in (3, 5) and dilation == 1:
         _launch('opa_dwconv_act', _ptr(x), _pixel_stride(x), _ptr(w_taps), _ptr(bias), _ptr(out), C, B, H, W, C, kernel_size, stride,
                 _DTYPES[x.dtype], _act_code(relu, act))
     else:

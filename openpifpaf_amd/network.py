@@ -14,6 +14,9 @@ follows the reference so that the field tensors have the reference's shapes:
   [4,8,4], channels [24,348,696,1392,1392]; k30: [8,16,6], [32,512,1024,2048,2048]); the reference's options add a second
   input convolution, dilate stage 4, change the depthwise kernel's width, make ``conv5`` two units or put a LeakyReLU in
   place of every ReLU (``network/basenetworks.py:245-400``).
+* ``ShuffleNetV2``: torchvision's ``shufflenet_v2_x1_0`` / ``_x2_0`` without the max-pool and the classifier, stride 16 (reference
+  ``network/basenetworks.py:36-69``): the K unit with a 3x3 window under torchvision's names.
+* ``MobileNetV2``: torchvision's ``mobilenet_v2`` features, stride 32 (reference ``network/basenetworks.py:407-430``).
 * ``MobileNetV3``: torchvision's ``mobilenet_v3_large`` / ``mobilenet_v3_small`` feature extractors with the stride of the first
   convolution set to 1, stride 16 (reference ``network/basenetworks.py:432-446``, ``network/factory.py:53-56``).
 * ``SqueezeNet``: torchvision's ``squeezenet1_1`` features with padding 1 on the stem and on the ceil-mode max-pools, stride 16
@@ -439,11 +442,12 @@ class _InvertedResidualK(nn.Module):
 
     def _unit_route_supported(self, x):
         """Can the WHOLE unit run on the project's kernels alone (``_forward_unit``)?  Every 1x1 convolution through the
-        split-operand GEMM's unit mode, every depthwise convolution through the stencil kernel.  The GEMM's epilogue applies a ReLU:
-        a unit with another non-linearity (``leaky_relu``) takes ``_forward_fused``."""
+        split-operand GEMM's unit mode, every depthwise convolution through the stencil kernel.  The GEMM's epilogue applies the
+        ReLU, or the LeakyReLU of a ``leaky_relu`` unit where ``fused.UNIT_LEAKY`` is on and outside autocast: otherwise such a unit
+        takes ``_forward_fused``."""
         if not (x.dtype == torch.float32 and x.dim() == 4):
             return False
-        if self.leaky_relu:
+        if self.leaky_relu and not (fused.UNIT_LEAKY and not torch.is_autocast_enabled()):
             return False
         branches = (self.branch2,) if self.branch1 is None else (self.branch1, self.branch2)
         for branch in branches:
@@ -463,14 +467,16 @@ class _InvertedResidualK(nn.Module):
 
     def _forward_unit(self, x):
         """Three launches (five in a first unit): GEMM + bias + ReLU on the channel slice, the depthwise stencil, GEMM + bias + ReLU
-        stored into the shuffled position with the pass-through half copied by the same kernel."""
+        stored into the shuffled position with the pass-through half copied by the same kernel.  A ``leaky_relu`` unit: the same
+        launches with the module's LeakyReLU in the GEMM's epilogue."""
         b2 = self.branch2
+        act = dict(act=fused.ACT_LEAKY_RELU, act_param=b2[2].negative_slope) if self.leaky_relu else {}
         if self.branch1 is None:
             x1, x2 = x.chunk(2, dim=1)
         else:
-            x1, x2 = fused.conv1x1_unit_x3(self.branch1[2], self._dw(self.branch1[0], x)), x
-        h = self._dw(b2[3], fused.conv1x1_unit_x3(b2[0], x2))
-        return fused.conv1x1_unit_x3(b2[5], h, partner=x1)
+            x1, x2 = fused.conv1x1_unit_x3(self.branch1[2], self._dw(self.branch1[0], x), **act), x
+        h = self._dw(b2[3], fused.conv1x1_unit_x3(b2[0], x2, **act))
+        return fused.conv1x1_unit_x3(b2[5], h, partner=x1, **act)
 
     def _forward_fused(self, x):
         if self.branch1 is None:
@@ -592,14 +598,62 @@ class ShuffleNetV2K(BaseNetwork):
         self.fused = True
 
     def forward(self, x):
-        x = self.stage4(self.stage3(self.stage2(self.input_block(x))))
-        conv = self.conv5[0]
-        # (a stage ``conv5`` routes itself, unit by unit; the GEMM's epilogue applies a ReLU, so a LeakyReLU stays with torch)
-        if (self.fused and x.is_cuda and isinstance(conv, nn.Conv2d) and isinstance(self.conv5[2], nn.ReLU)
-                and fused.unit_conv_x3_supported(conv, x)):
+        return _conv5_forward(self, self.stage4(self.stage3(self.stage2(self.input_block(x)))))
+
+
+def _conv5_forward(net, x):
+    """``net.conv5(x)`` of a ShuffleNetV2K or a ShuffleNetV2: ``Sequential(Conv2d 1x1, BatchNorm2d, non-linearity)`` through the
+    split-operand GEMM's unit mode where that takes it, decided like the units (the table, else by size, never timed).  A stage
+    ``conv5`` routes itself, unit by unit.  The GEMM's epilogue applies a ReLU, or a LeakyReLU where ``fused.UNIT_LEAKY`` is on (outside
+    autocast); with the switch off a LeakyReLU ``conv5`` stays with torch."""
+    conv = net.conv5[0]
+    if net.fused and x.is_cuda and isinstance(conv, nn.Conv2d) and fused.unit_conv_x3_supported(conv, x):
+        act = net.conv5[2]
+        if isinstance(act, nn.ReLU):
             return fused.pick('unit', fused.out_pixels(x), conv.in_channels, conv.out_channels, False, False,
-                              lambda: fused.conv1x1_unit_x3(conv, x), lambda: self.conv5(x), timing=False)
-        return self.conv5(x)
+                              lambda: fused.conv1x1_unit_x3(conv, x), lambda: net.conv5(x), timing=False)
+        if isinstance(act, nn.LeakyReLU) and fused.UNIT_LEAKY and not torch.is_autocast_enabled():
+            return fused.pick('unit', fused.out_pixels(x), conv.in_channels, conv.out_channels, False, False,
+                              lambda: fused.conv1x1_unit_x3(conv, x, act=fused.ACT_LEAKY_RELU, act_param=act.negative_slope),
+                              lambda: net.conv5(x), timing=False)
+    return net.conv5(x)
+
+
+class ShuffleNetV2(BaseNetwork):
+    """ShuffleNetV2 x1.0 / x2.0 as the reference uses them: torchvision's ``shufflenet_v2_x1_0`` / ``shufflenet_v2_x2_0`` without the
+    max-pool behind ``conv1`` and without the classifier, stride 16 (reference ``network/basenetworks.py:36-69``,
+    ``network/factory.py:63-67``), restated with torchvision's module tree (``conv1``, ``stage2..4.<i>.branch1|branch2.<j>``, ``conv5``),
+    so that the ``base_net.*`` keys of a reference checkpoint fit.  The unit is ``_InvertedResidualK`` with a 3x3 window -- the
+    same indices inside ``branch1`` / ``branch2`` as torchvision's ``InvertedResidual`` -- so the units and ``conv5`` take the routes
+    ShuffleNetV2K's take.  No checkpoint can be loaded offline: the fit is checked by key names and shapes only
+    (``tests/test_mobilenetv2_host.py``), never against real weights."""
+    # stage repeats, [conv1, stage2, stage3, stage4, conv5] channels
+    CONFIGS = {
+        'shufflenetv2x1': ([4, 8, 4], [24, 116, 232, 464, 1024]),
+        'shufflenetv2x2': ([4, 8, 4], [24, 244, 488, 976, 2048]),
+    }
+
+    def __init__(self, name='shufflenetv2x2'):
+        repeats, ch = self.CONFIGS[name]
+        super().__init__(name, stride=16, out_features=ch[-1])
+        self.conv1 = nn.Sequential(nn.Conv2d(3, ch[0], 3, 2, 1, bias=False), nn.BatchNorm2d(ch[0]), nn.ReLU(inplace=True))
+        inp, stages = ch[0], []
+        for rep, oup in zip(repeats, ch[1:4]):
+            seq = [_InvertedResidualK(inp, oup, True, stride=2, kernel_size=3)]
+            seq += [_InvertedResidualK(oup, oup, False, kernel_size=3) for _ in range(rep - 1)]
+            stages.append(nn.Sequential(*seq))
+            inp = oup
+        self.stage2, self.stage3, self.stage4 = stages
+        self.conv5 = nn.Sequential(nn.Conv2d(inp, ch[-1], 1, bias=False), nn.BatchNorm2d(ch[-1]), nn.ReLU(inplace=True))
+
+    fused = False
+
+    def enable_fused_(self):
+        """conv5 may run through the split-operand GEMM's unit mode (bias + ReLU inside); no parameter or buffer changes."""
+        self.fused = True
+
+    def forward(self, x):
+        return _conv5_forward(self, self.stage4(self.stage3(self.stage2(self.conv1(x)))))
 
 
 def _make_divisible(v, divisor=8):
@@ -758,6 +812,109 @@ class MobileNetV3(BaseNetwork):
         return last(x)
 
 
+class _MBV2Block(nn.Module):
+    """MobileNetV2's inverted residual (torchvision's ``InvertedResidual``: ``.conv`` = [expand + BN + ReLU6,] depthwise + BN + ReLU6,
+    the projecting ``Conv2d``, its ``BatchNorm2d``; no expanding convolution where the expansion ratio is 1)."""
+
+    def __init__(self, inp, oup, stride, expand_ratio):
+        super().__init__()
+        hidden = inp * expand_ratio
+        layers = []
+        if expand_ratio != 1:
+            layers.append(_conv_bn_act(inp, hidden, 1, 1, 1, nn.ReLU6))
+        layers += [_conv_bn_act(hidden, hidden, 3, stride, hidden, nn.ReLU6),
+                   nn.Conv2d(hidden, oup, 1, bias=False), nn.BatchNorm2d(oup, eps=1e-3, momentum=0.01)]
+        self.conv = nn.Sequential(*layers)
+        self.use_res_connect = stride == 1 and inp == oup
+        self._has_expand = expand_ratio != 1
+
+    fused = False
+
+    expand = property(lambda self: self.conv[0][0] if self._has_expand else None, doc='the expanding 1x1 convolution, or None')
+    depthwise = property(lambda self: self.conv[1 if self._has_expand else 0][0], doc='the depthwise convolution')
+    project = property(lambda self: self.conv[-2], doc='the projecting 1x1 convolution')
+
+    def enable_fused_(self):
+        """After conv+BN folding: the block may run on the project's kernels alone (``_forward_unit``); no parameter or buffer changes."""
+        assert not any(isinstance(m, nn.BatchNorm2d) for m in self.modules()), 'fold the batch norms first (fuse_conv_bn_)'
+        self.fused = True
+
+    def _route_supported(self, x):
+        """Can the WHOLE block run on the project's kernels (``_forward_unit``)?  float32 outside autocast; every intermediate tensor is
+        a dense channels-last one this module allocates, so its layout is known and its sizes follow from ``x``'s."""
+        if not (fused.MBV2 and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and not torch.is_autocast_enabled()):
+            return False
+        dw, project = self.depthwise, self.project
+        k, s = dw.kernel_size[0], dw.stride[0]
+        if self._has_expand and not (self.expand.bias is not None and fused.unit_conv_x3_supported(self.expand, x)):
+            return False
+        # (the stencil's limits are on the batch and the rows, which the expanding convolution keeps; without one the stencil reads
+        #  ``x`` itself, whose layout ``dwconv_supported`` tests)
+        if not (dw.weight.dtype == torch.float32 and dw.bias is not None and dw.bias.dtype == torch.float32 and not x.requires_grad
+                and dw.weight.device == x.device and dw.padding == (k // 2, k // 2) and dw.dilation == (1, 1)
+                and fused.dwconv_supported(x, k, s)):
+            return False
+        if not (project.bias is not None and fused._unit_conv_ok(project) and project.weight.device == x.device):
+            return False
+        return not self.use_res_connect or fused._unit_operand_ok(x, project.out_channels)
+
+    def _forward_unit(self, x):
+        """Two or three launches: [GEMM + bias + ReLU6,] the depthwise stencil + bias + ReLU6, GEMM + bias (+ the block's input as the
+        residual: the projecting convolution is linear)."""
+        h = x if not self._has_expand else fused.conv1x1_unit_x3(self.expand, x, act=fused.ACT_RELU6, act_param=6.0)
+        dw = self.depthwise
+        h = fused.dwconv_bias_act(h, _MBV3Block.taps_of(dw), dw.bias, dw.kernel_size[0], dw.stride[0], act=fused.ACT_RELU6, act_param=6.0)
+        return fused.conv1x1_unit_x3(self.project, h, residual=x if self.use_res_connect else None, act=fused.ACT_NONE)
+
+    def forward(self, x):
+        if self.fused and self._route_supported(x):
+            return self._forward_unit(x)
+        out = self.conv(x)
+        return out + x if self.use_res_connect else out
+
+
+class MobileNetV2(BaseNetwork):
+    """MobileNetV2 as the reference uses it: torchvision's ``mobilenet_v2().features``, stride 32, 1280 features (reference
+    ``network/basenetworks.py:407-430``, ``network/factory.py:52``), restated from the paper's table with torchvision's module tree
+    (``backbone.0`` the stem, ``backbone.<i>.conv.<j>...`` the inverted residuals, ``backbone.18`` the last convolution), so that the
+    ``base_net.backbone.*`` keys of a reference checkpoint fit.  No checkpoint can be loaded offline: the fit is checked by key
+    names and shapes only (``tests/test_mobilenetv2_host.py``), never against real weights."""
+    # expansion ratio t, output channels c, repeats n, stride of the first repeat s
+    CONFIGS = {'mobilenetv2': ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1))}
+
+    def __init__(self, name='mobilenetv2'):
+        super().__init__(name, stride=32, out_features=1280)
+        layers = [_conv_bn_act(3, 32, 3, 2, 1, nn.ReLU6)]
+        inp = 32
+        for t, c, n, s in self.CONFIGS[name]:
+            for i in range(n):
+                layers.append(_MBV2Block(inp, c, s if i == 0 else 1, t))
+                inp = c
+        layers.append(_conv_bn_act(inp, self.out_features, 1, 1, 1, nn.ReLU6))
+        self.backbone = nn.Sequential(*layers)
+        for m in self.modules():               # torchvision's initialisation
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode='fan_out')
+
+    fused = False
+
+    def enable_fused_(self):
+        """The last 1x1 convolution may run through the split-operand GEMM's unit mode (bias + ReLU6 inside); the stem stays with
+        ``torch.nn.Conv2d`` like every non-ResNet stem.  No parameter or buffer changes."""
+        assert not any(isinstance(m, nn.BatchNorm2d) for m in self.modules()), 'fold the batch norms first (fuse_conv_bn_)'
+        self.fused = True
+
+    def forward(self, x):
+        *front, last = self.backbone
+        for m in front:
+            x = m(x)
+        conv = last[0]
+        if (self.fused and fused.MBV2 and x.is_cuda and not torch.is_autocast_enabled() and conv.bias is not None
+                and fused.unit_conv_x3_supported(conv, x)):
+            return fused.conv1x1_unit_x3(conv, x, act=fused.ACT_RELU6, act_param=6.0)
+        return last(x)
+
+
 class _Fire(nn.Module):
     """SqueezeNet's Fire module (torchvision's ``Fire``: the same attribute names): a 1x1 squeeze, then a 1x1 and a 3x3 expand of the
     squeezed tensor, concatenated; every convolution biased and followed by a ReLU."""
@@ -856,6 +1013,8 @@ class SqueezeNet(BaseNetwork):
 BASE_FACTORIES = {
     **{n: (lambda n=n: Resnet(n)) for n in Resnet.CONFIGS},
     **{n: (lambda n=n: ShuffleNetV2K(n)) for n in ShuffleNetV2K.CONFIGS},
+    **{n: (lambda n=n: ShuffleNetV2(n)) for n in ShuffleNetV2.CONFIGS},
+    **{n: (lambda n=n: MobileNetV2(n)) for n in MobileNetV2.CONFIGS},
     **{n: (lambda n=n: MobileNetV3(n)) for n in MobileNetV3.CONFIGS},
     **{n: (lambda n=n: SqueezeNet(n)) for n in SqueezeNet.CONFIGS},
 }
@@ -985,14 +1144,18 @@ def fuse_conv_bn_(model):
 
 
 def optimize_for_inference_(model):
-    """Fold every conv+BN pair, then switch the ResNet blocks to the fused-epilogue forward
-    (conv without bias followed by ONE ``fused.bias_act_`` pass), the ShuffleNetV2K units and ``conv5`` to the HIP depthwise /
-    interleave kernels and the split-operand GEMM's unit mode, the MobileNetV3 blocks and last convolution to the same GEMM,
-    the depthwise stencil and the squeeze-and-excitation kernels, and the SqueezeNet Fire modules and max-pools to that GEMM, the
-    Fire expand kernel and the ceil-mode pool (behind ``fused.FIRE``)."""
+    """Fold every conv+BN pair, then switch each family to its kernels:
+
+    * the ResNet and ResNeXt blocks to the fused-epilogue forward (conv without bias followed by ONE ``fused.bias_act_`` pass);
+    * the ShuffleNetV2K and ShuffleNetV2 units and ``conv5`` to the HIP depthwise / interleave kernels and the split-operand GEMM's
+      unit mode (a LeakyReLU unit's 1x1 convolutions behind ``fused.UNIT_LEAKY``);
+    * the MobileNetV3 blocks and last convolution to the same GEMM, the depthwise stencil and the squeeze-and-excitation kernels
+      (behind ``fused.MBV3``);
+    * the MobileNetV2 blocks and last convolution to that GEMM and that stencil with ReLU6 (behind ``fused.MBV2``);
+    * the SqueezeNet Fire modules and max-pools to that GEMM, the Fire expand kernel and the ceil-mode pool (behind ``fused.FIRE``)."""
     fuse_conv_bn_(model)
     for m in model.modules():
-        if isinstance(m, (_Bottleneck, _BasicBlock, Resnet, _InvertedResidualK, ShuffleNetV2K, _MBV3Block, MobileNetV3, _Fire,
-                          SqueezeNet)):
+        if isinstance(m, (_Bottleneck, _BasicBlock, Resnet, _InvertedResidualK, ShuffleNetV2K, ShuffleNetV2, _MBV2Block, MobileNetV2,
+                          _MBV3Block, MobileNetV3, _Fire, SqueezeNet)):
             m.enable_fused_()
     return model
