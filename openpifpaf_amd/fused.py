@@ -65,7 +65,7 @@ X3_UNIT = _switch('OPA_GEMM3_UNIT', '1')
 # kernel has been timed against that route on every (group width, stride) class at 641 px (tools/gpu/gconv_times.py): no speed is
 # claimed for a route nobody has measured.
 GCONV = _switch('OPA_GCONV', '0')
-# The MobileNetV3 blocks on the project's kernels (network._MBV3Block._forward_unit): OPA_MBV3=1 (or fused.MBV3 = True) switches the
+# The MobileNetV3 blocks on the project's kernels (network._InvertedResidual._forward_unit): OPA_MBV3=1 (or fused.MBV3 = True) switches the
 # route on.  It stays OFF by default -- the plain torch forward -- until both trunks have been timed against that forward at 641 px,
 # batch 32 (tools/gpu/mobilenetv3_times.py): no speed is claimed for a route nobody has measured.
 MBV3 = _switch('OPA_MBV3', '0')
@@ -84,7 +84,7 @@ FIRE = _switch('OPA_FIRE', '0')
 # (tools/gpu/squeezenet_terms.py, profiles/squeezenet/terms.log) the field outputs are 4e-7 ... 6e-7 of their size too small with six
 # terms -- 0.9 ... 2.4 times the largest error of torch's own float32 forward -- and 0.4 ... 1.0 times that error with nine.
 FIRE_TERMS = 9
-# The MobileNetV2 blocks and last convolution on the project's kernels (network._MBV2Block._forward_unit: the unit-mode GEMM with
+# The MobileNetV2 blocks and last convolution on the project's kernels (network._InvertedResidual._forward_unit: the unit-mode GEMM with
 # ReLU6 for the expanding convolution, the depthwise stencil with ReLU6, the unit-mode GEMM with the block's input as the residual):
 # OPA_MBV2=1 (or fused.MBV2 = True) switches the route on.  It ships OFF -- the plain torch forward; the one timing is
 # tools/gpu/mobilenetv2_times.py, profiles/mobilenetv2/times.log, and switching the default is a change of its own that rests on it.

@@ -198,6 +198,12 @@ class BaseNetwork(nn.Module):
         self.stride = stride
         self.out_features = out_features
 
+    fused = False
+
+    def enable_fused_(self):
+        """After conv+BN folding: ``forward`` may take the project's kernels; no parameter or buffer changes."""
+        self.fused = True
+
 
 def _dilate_(block5, dilation):
     """Block 5 with dilated convolutions instead of a stride (reference ``network/basenetworks.py:121-135``): every convolution gets
@@ -431,13 +437,13 @@ class _InvertedResidualK(nn.Module):
                 and fused.dwconv_supported(x, k, m.stride[0], d))
 
     @staticmethod
+    def _dw(m, x):
+        return fused.dwconv_bias_act(x, _InvertedResidualK.taps_of(m), m.bias, m.kernel_size[0], m.stride[0], dilation=m.dilation[0])
+
+    @staticmethod
     def _run(branch, x):
         for m in branch:
-            if isinstance(m, nn.Conv2d) and _InvertedResidualK._dw_ok(m, x):
-                x = fused.dwconv_bias_act(x, _InvertedResidualK.taps_of(m), m.bias, m.kernel_size[0], m.stride[0],
-                                          dilation=m.dilation[0])
-            else:
-                x = m(x)
+            x = _InvertedResidualK._dw(m, x) if isinstance(m, nn.Conv2d) and _InvertedResidualK._dw_ok(m, x) else m(x)
         return x
 
     def _unit_route_supported(self, x):
@@ -461,9 +467,6 @@ class _InvertedResidualK(nn.Module):
                     return False
         first = x if self.branch1 is not None else x.chunk(2, dim=1)[1]
         return fused.unit_conv_x3_supported(self.branch2[0], first)
-
-    def _dw(self, m, x):
-        return fused.dwconv_bias_act(x, self.taps_of(m), m.bias, m.kernel_size[0], m.stride[0], dilation=m.dilation[0])
 
     def _forward_unit(self, x):
         """Three launches (five in a first unit): GEMM + bias + ReLU on the channel slice, the depthwise stencil, GEMM + bias + ReLU
@@ -591,12 +594,6 @@ class ShuffleNetV2K(BaseNetwork):
             flag = 'shufflenetv2k_' + ('kernel' if option == 'kernel_width' else option)
             setattr(cls, option, getattr(args, flag, getattr(cls, option)))
 
-    fused = False
-
-    def enable_fused_(self):
-        """conv5 may run through the split-operand GEMM's unit mode (bias + ReLU inside); no parameter or buffer changes."""
-        self.fused = True
-
     def forward(self, x):
         return _conv5_forward(self, self.stage4(self.stage3(self.stage2(self.input_block(x)))))
 
@@ -608,14 +605,14 @@ def _conv5_forward(net, x):
     autocast); with the switch off a LeakyReLU ``conv5`` stays with torch."""
     conv = net.conv5[0]
     if net.fused and x.is_cuda and isinstance(conv, nn.Conv2d) and fused.unit_conv_x3_supported(conv, x):
-        act = net.conv5[2]
-        if isinstance(act, nn.ReLU):
+        nonlin, act = net.conv5[2], None
+        if isinstance(nonlin, nn.ReLU):
+            act = {}
+        elif isinstance(nonlin, nn.LeakyReLU) and fused.UNIT_LEAKY and not torch.is_autocast_enabled():
+            act = dict(act=fused.ACT_LEAKY_RELU, act_param=nonlin.negative_slope)
+        if act is not None:
             return fused.pick('unit', fused.out_pixels(x), conv.in_channels, conv.out_channels, False, False,
-                              lambda: fused.conv1x1_unit_x3(conv, x), lambda: net.conv5(x), timing=False)
-        if isinstance(act, nn.LeakyReLU) and fused.UNIT_LEAKY and not torch.is_autocast_enabled():
-            return fused.pick('unit', fused.out_pixels(x), conv.in_channels, conv.out_channels, False, False,
-                              lambda: fused.conv1x1_unit_x3(conv, x, act=fused.ACT_LEAKY_RELU, act_param=act.negative_slope),
-                              lambda: net.conv5(x), timing=False)
+                              lambda: fused.conv1x1_unit_x3(conv, x, **act), lambda: net.conv5(x), timing=False)
     return net.conv5(x)
 
 
@@ -645,12 +642,6 @@ class ShuffleNetV2(BaseNetwork):
             inp = oup
         self.stage2, self.stage3, self.stage4 = stages
         self.conv5 = nn.Sequential(nn.Conv2d(inp, ch[-1], 1, bias=False), nn.BatchNorm2d(ch[-1]), nn.ReLU(inplace=True))
-
-    fused = False
-
-    def enable_fused_(self):
-        """conv5 may run through the split-operand GEMM's unit mode (bias + ReLU inside); no parameter or buffer changes."""
-        self.fused = True
 
     def forward(self, x):
         return _conv5_forward(self, self.stage4(self.stage3(self.stage2(self.conv1(x)))))
@@ -686,8 +677,73 @@ class _SqueezeExcitation(nn.Module):
         return x * self.scale_activation(self.fc2(self.activation(self.fc1(self.avgpool(x)))))
 
 
-class _MBV3Block(nn.Module):
+def _assert_folded(module):
+    assert not any(isinstance(m, nn.BatchNorm2d) for m in module.modules()), 'fold the batch norms first (fuse_conv_bn_)'
+
+
+class _InvertedResidual(nn.Module):
+    """What the inverted residuals of MobileNetV3 and MobileNetV2 share: [expand,] depthwise, [se,] project, the block's input added
+    under ``use_res_connect``, and the route that runs all of it on the project's kernels.  A subclass builds its layers and states
+    ``_body`` (the attribute that holds them), ``_switch`` (the name of its switch in ``fused``), ``_act`` (code and parameter of its
+    activation) and, as properties, where ``expand``, ``depthwise``, ``se`` and ``project`` sit in the body."""
+    fused = False
+
+    def enable_fused_(self):
+        """After conv+BN folding: the block may run on the project's kernels alone (``_forward_unit``); no parameter or buffer changes."""
+        _assert_folded(self)
+        self.fused = True
+
+    @staticmethod
+    def taps_of(conv):
+        """The CURRENT depthwise weight tap-major, ``[k * k, C]`` (derived and cached, no part of a checkpoint)."""
+        return fused.derived(conv, '_opa_taps', (conv.weight,), lambda: fused.depthwise_taps(conv.weight))
+
+    def _route_supported(self, x):
+        """Can the WHOLE block run on the project's kernels (``_forward_unit``)?  float32 outside autocast, nothing that autograd
+        follows; every intermediate tensor is a dense channels-last one this module allocates, so its layout is known and its sizes
+        follow from ``x``'s."""
+        if not (getattr(fused, self._switch) and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32
+                and not torch.is_autocast_enabled() and not x.requires_grad):
+            return False
+        expand, dw, se, project = self.expand, self.depthwise, self.se, self.project
+        k, s = dw.kernel_size[0], dw.stride[0]
+        if expand is not None and not (expand.bias is not None and fused.unit_conv_x3_supported(expand, x)):
+            return False
+        # (the stencil's limits are on the batch and the rows, which the expanding convolution keeps; without one the stencil reads
+        #  ``x`` itself, whose layout ``dwconv_supported`` tests)
+        if not (dw.weight.dtype == torch.float32 and dw.bias is not None and dw.bias.dtype == torch.float32
+                and dw.weight.device == x.device and dw.padding == (k // 2, k // 2) and dw.dilation == (1, 1)
+                and fused.dwconv_supported(x, k, s)):
+            return False
+        pixels = ((x.shape[2] - 1) // s + 1) * ((x.shape[3] - 1) // s + 1)          # of the depthwise output, which the SE kernels read
+        if se is not None and not (fused._se_convs_ok(se.fc1, se.fc2) and se.fc1.weight.device == x.device
+                                   and x.shape[0] <= 65535 and pixels <= fused.SE_MAX_PIXELS and fused._lib.available()):
+            return False
+        if not (project.bias is not None and fused._unit_conv_ok(project) and project.weight.device == x.device):
+            return False
+        return not self.use_res_connect or fused._unit_operand_ok(x, project.out_channels)
+
+    def _forward_unit(self, x):
+        """Two to six launches: [GEMM + bias + activation,] the depthwise stencil + bias + activation, [the SE pool, its gate, the
+        scale in place,] GEMM + bias (+ the block's input as the residual: the projecting convolution is linear)."""
+        act = dict(act=self._act[0], act_param=self._act[1])
+        expand, dw, se = self.expand, self.depthwise, self.se
+        h = x if expand is None else fused.conv1x1_unit_x3(expand, x, **act)
+        h = fused.dwconv_bias_act(h, self.taps_of(dw), dw.bias, dw.kernel_size[0], dw.stride[0], **act)
+        if se is not None:
+            fused.scale_channels_(h, fused.se_gate(h, se.fc1, se.fc2))
+        return fused.conv1x1_unit_x3(self.project, h, residual=x if self.use_res_connect else None, act=fused.ACT_NONE)
+
+    def forward(self, x):
+        if self.fused and self._route_supported(x):
+            return self._forward_unit(x)
+        out = getattr(self, self._body)(x)
+        return out + x if self.use_res_connect else out
+
+
+class _MBV3Block(_InvertedResidual):
     """MobileNetV3's inverted residual (torchvision's ``InvertedResidual``: ``.block`` = [expand,] depthwise, [se,] project)."""
+    _body, _switch = 'block', 'MBV3'
 
     def __init__(self, inp, kernel_size, exp, oup, use_se, use_hs, stride):
         super().__init__()
@@ -702,69 +758,42 @@ class _MBV3Block(nn.Module):
         self.block = nn.Sequential(*layers)
         self.use_res_connect = stride == 1 and inp == oup
         self._has_expand, self._has_se = exp != inp, use_se
-        self._act = fused.ACT_HARDSWISH if use_hs else fused.ACT_RELU
-
-    fused = False
+        self._act = (fused.ACT_HARDSWISH if use_hs else fused.ACT_RELU, 0.0)
 
     expand = property(lambda self: self.block[0][0] if self._has_expand else None, doc='the expanding 1x1 convolution, or None')
     depthwise = property(lambda self: self.block[1 if self._has_expand else 0][0], doc='the depthwise convolution')
     se = property(lambda self: self.block[-2] if self._has_se else None, doc='the squeeze-and-excitation module, or None')
     project = property(lambda self: self.block[-1][0], doc='the projecting 1x1 convolution')
 
+
+class _MobileNet(BaseNetwork):
+    """What MobileNetV3 and MobileNetV2 share: ``backbone``, whose last module is a 1x1 convolution with the network's activation.  A
+    subclass states ``_switch`` and ``_act`` as its blocks do."""
+
     def enable_fused_(self):
-        """After conv+BN folding: the block may run on the project's kernels alone (``_forward_unit``); no parameter or buffer changes."""
-        assert not any(isinstance(m, nn.BatchNorm2d) for m in self.modules()), 'fold the batch norms first (fuse_conv_bn_)'
-        self.fused = True
-
-    @staticmethod
-    def taps_of(conv):
-        """The CURRENT depthwise weight tap-major, ``[k * k, C]`` (derived and cached, no part of a checkpoint)."""
-        return fused.derived(conv, '_opa_taps', (conv.weight,), lambda: fused.depthwise_taps(conv.weight))
-
-    def _route_supported(self, x):
-        """Can the WHOLE block run on the project's kernels (``_forward_unit``)?  float32 outside autocast; every intermediate tensor is
-        a dense channels-last one this module allocates, so its layout is known and its sizes follow from ``x``'s."""
-        if not (fused.MBV3 and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and not torch.is_autocast_enabled()):
-            return False
-        dw, project = self.depthwise, self.project
-        k, s = dw.kernel_size[0], dw.stride[0]
-        if self._has_expand and not fused.unit_conv_x3_supported(self.expand, x):
-            return False
-        # (the stencil's limits are on the batch and the rows, which the expanding convolution keeps)
-        if not (dw.weight.dtype == torch.float32 and dw.bias is not None and dw.bias.dtype == torch.float32
-                and dw.weight.device == x.device and dw.padding == (k // 2, k // 2) and fused.dwconv_supported(x, k, s)):
-            return False
-        pixels = ((x.shape[2] - 1) // s + 1) * ((x.shape[3] - 1) // s + 1)          # of the depthwise output, which the SE kernels read
-        if self._has_se and not (fused._se_convs_ok(self.se.fc1, self.se.fc2) and self.se.fc1.weight.device == x.device
-                                 and x.shape[0] <= 65535 and pixels <= fused.SE_MAX_PIXELS and fused._lib.available()):
-            return False
-        if not (fused._unit_conv_ok(project) and project.weight.device == x.device):
-            return False
-        return not self.use_res_connect or fused._unit_operand_ok(x, project.out_channels)
-
-    def _forward_unit(self, x):
-        """Two to six launches: [GEMM + bias + activation,] the depthwise stencil + bias + activation, [the SE pool, its gate, the
-        scale in place,] GEMM + bias (+ the block's input as the residual)."""
-        h = x if not self._has_expand else fused.conv1x1_unit_x3(self.expand, x, act=self._act)
-        dw = self.depthwise
-        h = fused.dwconv_bias_act(h, self.taps_of(dw), dw.bias, dw.kernel_size[0], dw.stride[0], act=self._act)
-        if self._has_se:
-            fused.scale_channels_(h, fused.se_gate(h, self.se.fc1, self.se.fc2))
-        return fused.conv1x1_unit_x3(self.project, h, residual=x if self.use_res_connect else None, act=fused.ACT_NONE)
+        """The last 1x1 convolution may run through the split-operand GEMM's unit mode (bias + activation inside); the stem stays
+        with ``torch.nn.Conv2d`` like every non-ResNet stem.  No parameter or buffer changes."""
+        _assert_folded(self)
+        super().enable_fused_()
 
     def forward(self, x):
-        if self.fused and self._route_supported(x):
-            return self._forward_unit(x)
-        out = self.block(x)
-        return out + x if self.use_res_connect else out
+        *front, last = self.backbone
+        for m in front:
+            x = m(x)
+        conv = last[0]
+        if (self.fused and getattr(fused, self._switch) and x.is_cuda and not torch.is_autocast_enabled() and conv.bias is not None
+                and fused.unit_conv_x3_supported(conv, x)):
+            return fused.conv1x1_unit_x3(conv, x, act=self._act[0], act_param=self._act[1])
+        return last(x)
 
 
-class MobileNetV3(BaseNetwork):
+class MobileNetV3(_MobileNet):
     """MobileNetV3 large / small as the reference uses them: torchvision's ``features`` with the stride of the first convolution set
     to 1, so the overall stride is 16 (reference ``network/basenetworks.py:432-446``, ``network/factory.py:53-56``), restated from the
     paper's tables with torchvision's module tree (``backbone.<i>.block.<j>...``), so that the ``base_net.backbone.*`` keys of a
     reference checkpoint fit.  No checkpoint can be loaded offline: the fit is checked by key names and shapes only
     (``tests/test_mobilenetv3_host.py``), never against real weights."""
+    _switch, _act = 'MBV3', (fused.ACT_HARDSWISH, 0.0)
     # in, kernel, expanded, out, SE, hardswish, stride
     CONFIGS = {
         'mobilenetv3large': ([
@@ -793,28 +822,11 @@ class MobileNetV3(BaseNetwork):
                 if m.bias is not None:
                     nn.init.zeros_(m.bias)
 
-    fused = False
 
-    def enable_fused_(self):
-        """The last 1x1 convolution may run through the split-operand GEMM's unit mode (bias + hardswish inside); the stem stays
-        with ``torch.nn.Conv2d`` like ShuffleNetV2K's ``input_block``.  No parameter or buffer changes."""
-        assert not any(isinstance(m, nn.BatchNorm2d) for m in self.modules()), 'fold the batch norms first (fuse_conv_bn_)'
-        self.fused = True
-
-    def forward(self, x):
-        *front, last = self.backbone
-        for m in front:
-            x = m(x)
-        conv = last[0]
-        if (self.fused and fused.MBV3 and x.is_cuda and not torch.is_autocast_enabled() and conv.bias is not None
-                and fused.unit_conv_x3_supported(conv, x)):
-            return fused.conv1x1_unit_x3(conv, x, act=fused.ACT_HARDSWISH)
-        return last(x)
-
-
-class _MBV2Block(nn.Module):
+class _MBV2Block(_InvertedResidual):
     """MobileNetV2's inverted residual (torchvision's ``InvertedResidual``: ``.conv`` = [expand + BN + ReLU6,] depthwise + BN + ReLU6,
     the projecting ``Conv2d``, its ``BatchNorm2d``; no expanding convolution where the expansion ratio is 1)."""
+    _body, _switch, _act = 'conv', 'MBV2', (fused.ACT_RELU6, 6.0)
 
     def __init__(self, inp, oup, stride, expand_ratio):
         super().__init__()
@@ -828,57 +840,19 @@ class _MBV2Block(nn.Module):
         self.use_res_connect = stride == 1 and inp == oup
         self._has_expand = expand_ratio != 1
 
-    fused = False
-
     expand = property(lambda self: self.conv[0][0] if self._has_expand else None, doc='the expanding 1x1 convolution, or None')
     depthwise = property(lambda self: self.conv[1 if self._has_expand else 0][0], doc='the depthwise convolution')
+    se = None
     project = property(lambda self: self.conv[-2], doc='the projecting 1x1 convolution')
 
-    def enable_fused_(self):
-        """After conv+BN folding: the block may run on the project's kernels alone (``_forward_unit``); no parameter or buffer changes."""
-        assert not any(isinstance(m, nn.BatchNorm2d) for m in self.modules()), 'fold the batch norms first (fuse_conv_bn_)'
-        self.fused = True
 
-    def _route_supported(self, x):
-        """Can the WHOLE block run on the project's kernels (``_forward_unit``)?  float32 outside autocast; every intermediate tensor is
-        a dense channels-last one this module allocates, so its layout is known and its sizes follow from ``x``'s."""
-        if not (fused.MBV2 and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and not torch.is_autocast_enabled()):
-            return False
-        dw, project = self.depthwise, self.project
-        k, s = dw.kernel_size[0], dw.stride[0]
-        if self._has_expand and not (self.expand.bias is not None and fused.unit_conv_x3_supported(self.expand, x)):
-            return False
-        # (the stencil's limits are on the batch and the rows, which the expanding convolution keeps; without one the stencil reads
-        #  ``x`` itself, whose layout ``dwconv_supported`` tests)
-        if not (dw.weight.dtype == torch.float32 and dw.bias is not None and dw.bias.dtype == torch.float32 and not x.requires_grad
-                and dw.weight.device == x.device and dw.padding == (k // 2, k // 2) and dw.dilation == (1, 1)
-                and fused.dwconv_supported(x, k, s)):
-            return False
-        if not (project.bias is not None and fused._unit_conv_ok(project) and project.weight.device == x.device):
-            return False
-        return not self.use_res_connect or fused._unit_operand_ok(x, project.out_channels)
-
-    def _forward_unit(self, x):
-        """Two or three launches: [GEMM + bias + ReLU6,] the depthwise stencil + bias + ReLU6, GEMM + bias (+ the block's input as the
-        residual: the projecting convolution is linear)."""
-        h = x if not self._has_expand else fused.conv1x1_unit_x3(self.expand, x, act=fused.ACT_RELU6, act_param=6.0)
-        dw = self.depthwise
-        h = fused.dwconv_bias_act(h, _MBV3Block.taps_of(dw), dw.bias, dw.kernel_size[0], dw.stride[0], act=fused.ACT_RELU6, act_param=6.0)
-        return fused.conv1x1_unit_x3(self.project, h, residual=x if self.use_res_connect else None, act=fused.ACT_NONE)
-
-    def forward(self, x):
-        if self.fused and self._route_supported(x):
-            return self._forward_unit(x)
-        out = self.conv(x)
-        return out + x if self.use_res_connect else out
-
-
-class MobileNetV2(BaseNetwork):
+class MobileNetV2(_MobileNet):
     """MobileNetV2 as the reference uses it: torchvision's ``mobilenet_v2().features``, stride 32, 1280 features (reference
     ``network/basenetworks.py:407-430``, ``network/factory.py:52``), restated from the paper's table with torchvision's module tree
     (``backbone.0`` the stem, ``backbone.<i>.conv.<j>...`` the inverted residuals, ``backbone.18`` the last convolution), so that the
     ``base_net.backbone.*`` keys of a reference checkpoint fit.  No checkpoint can be loaded offline: the fit is checked by key
     names and shapes only (``tests/test_mobilenetv2_host.py``), never against real weights."""
+    _switch, _act = _MBV2Block._switch, _MBV2Block._act
     # expansion ratio t, output channels c, repeats n, stride of the first repeat s
     CONFIGS = {'mobilenetv2': ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1))}
 
@@ -895,24 +869,6 @@ class MobileNetV2(BaseNetwork):
         for m in self.modules():               # torchvision's initialisation
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode='fan_out')
-
-    fused = False
-
-    def enable_fused_(self):
-        """The last 1x1 convolution may run through the split-operand GEMM's unit mode (bias + ReLU6 inside); the stem stays with
-        ``torch.nn.Conv2d`` like every non-ResNet stem.  No parameter or buffer changes."""
-        assert not any(isinstance(m, nn.BatchNorm2d) for m in self.modules()), 'fold the batch norms first (fuse_conv_bn_)'
-        self.fused = True
-
-    def forward(self, x):
-        *front, last = self.backbone
-        for m in front:
-            x = m(x)
-        conv = last[0]
-        if (self.fused and fused.MBV2 and x.is_cuda and not torch.is_autocast_enabled() and conv.bias is not None
-                and fused.unit_conv_x3_supported(conv, x)):
-            return fused.conv1x1_unit_x3(conv, x, act=fused.ACT_RELU6, act_param=6.0)
-        return last(x)
 
 
 class _Fire(nn.Module):
@@ -982,19 +938,14 @@ class SqueezeNet(BaseNetwork):
                 nn.init.kaiming_uniform_(m.weight)
                 nn.init.zeros_(m.bias)
 
-    fused = False
-
-    def enable_fused_(self):
-        """The max-pools may run through the ceil-mode entry point of ``csrc/pool.hip`` (the first with the stem's ReLU inside); the
-        stem stays with ``torch.nn.Conv2d`` like MobileNetV3's and ShuffleNetV2K's.  No parameter or buffer changes."""
-        self.fused = True
-
     @staticmethod
     def _pool_route_supported(pool, x):
         return (isinstance(pool, nn.MaxPool2d) and pool.kernel_size == 3 and pool.stride == 2 and pool.padding == 1 and pool.dilation == 1
                 and pool.ceil_mode and not pool.return_indices and fused.maxpool3x3_supported(x))
 
     def forward(self, x):
+        """Fused: the max-pools through the ceil-mode entry point of ``csrc/pool.hip`` (the first with the stem's ReLU inside); the stem
+        stays with ``torch.nn.Conv2d`` like MobileNetV3's and ShuffleNetV2K's."""
         if not (self.fused and fused.FIRE and x.is_cuda and not torch.is_autocast_enabled()):
             return self.backbone(x)
         modules = list(self.backbone)
@@ -1155,7 +1106,6 @@ def optimize_for_inference_(model):
     * the SqueezeNet Fire modules and max-pools to that GEMM, the Fire expand kernel and the ceil-mode pool (behind ``fused.FIRE``)."""
     fuse_conv_bn_(model)
     for m in model.modules():
-        if isinstance(m, (_Bottleneck, _BasicBlock, Resnet, _InvertedResidualK, ShuffleNetV2K, ShuffleNetV2, _MBV2Block, MobileNetV2,
-                          _MBV3Block, MobileNetV3, _Fire, SqueezeNet)):
+        if isinstance(m, (_Bottleneck, _BasicBlock, _InvertedResidualK, _InvertedResidual, _Fire, BaseNetwork)):
             m.enable_fused_()
     return model

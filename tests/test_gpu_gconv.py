@@ -43,31 +43,7 @@ _LAUNCHERS = {'gconv3x3_bias_act': 'gconv', 'conv1x1_bias_act': 'gemm', 'conv1x1
               'head_epilogue': 'head_epilogue'}
 
 
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _e0(fn, ref64):
-    """(max, rms) error of the float32 torch computation ``fn`` against ``ref64``: the median of nine calls."""
-    errs = [tc.errors(fn(), ref64) for _ in range(9)]
-    return tuple(sorted(e[i] for e in errs)[4] for i in (0, 1))
-
-
-def _report(what, err, e0):
-    print('GCONV %s | e0 max %.3e rms %.3e | err max %.3e rms %.3e | err/e0 max %.2f rms %.2f'
-          % (what, e0[0], e0[1], err[0], err[1], err[0] / max(e0[0], 1e-30), err[1] / max(e0[1], 1e-30)))
-    return err[0] <= 2 * e0[0] and err[1] <= 2 * e0[1]
-
-
-class _Recorder:
-    def __init__(self):
-        self.trace = []
-
-    def watch(self, module):
-        for name, m in module.named_modules():
-            if isinstance(m, nn.Conv2d):
-                m.register_forward_hook(lambda mod, args, out, name=name: self.trace.append('miopen:' + name))
-        return module
+_report = functools.partial(tc.report, 'GCONV')
 
 
 @pytest.fixture
@@ -78,31 +54,9 @@ def rec(monkeypatch):
     K = 2048 of block ``cg64`` that chain alone is 2.3 - 2.6 e0 of the block (measured on an MI355X: err max 9.1e-7 - 9.4e-7 against
     e0 3.6e-7 - 4.0e-7; a float32 replay of the block on the CPU with everything else in float64 puts 7.6e-7 on the two GEMMs and
     1.3e-7, the float64 baseline's level, on the grouped convolution) -- an error of a kernel this file does not test."""
-    r = _Recorder()
-    for attr, label in _LAUNCHERS.items():
-        real = getattr(fused, attr)
-
-        def wrapper(*args, _real=real, _label=label, **kwargs):
-            r.trace.append(_label)
-            return _real(*args, **kwargs)
-        monkeypatch.setattr(fused, attr, wrapper)
-
-    def time_ms(fn, reps=3):
-        raise AssertionError('the grouped route timed something')
-    monkeypatch.setattr(fused, '_time_ms', time_ms)
-    monkeypatch.setattr(fused, 'FORCE_PICK', 'x3')
-    monkeypatch.setattr(fused, 'X3_TERMS', 6)
-    for attr in ('X3_PAIR', 'X3_CONV3', 'X3_STEM', 'X3_HEAD', 'GCONV'):
-        monkeypatch.setattr(fused, attr, True)
     monkeypatch.setenv('OPA_CONV1X1', 'gemm')                 # (bfloat16, where no split-operand kernel exists: decided without timing too)
-
-    class Pinned(dict):
-        def get(self, key, default=None):
-            if len(key) == 6 and key[0] == 'torch.float32':      # a key of conv_bias_act
-                return 'gemm3'
-            return super().get(key, default)
-    monkeypatch.setattr(fused, '_CHOICE', Pinned())
-    yield r
+    return tc.recorder(monkeypatch, _LAUNCHERS, ('X3_PAIR', 'X3_CONV3', 'X3_STEM', 'X3_HEAD', 'GCONV'), force_pick='x3',
+                       table=tc.PinnedGemm3())
 
 
 # ---- 1. the kernel -------------------------------------------------------------------------------------------------------------
@@ -152,13 +106,13 @@ def test_kernel(monkeypatch, cg, groups, stride):
     monkeypatch.setattr(fused, 'GCONV', True)
     C = cg * groups
     conv = _conv(cg, groups, stride, 1000 * cg + 10 * groups + stride)
-    bias = (torch.randn(C, generator=_gen(cg + groups)) * 0.5).cuda()
+    bias = (torch.randn(C, generator=tc.gen(cg + groups)) * 0.5).cuda()
     wt = fused.gconv_weight_of(conv)
     combos = [(True, True), (False, False), (True, False), (False, True)]
     ok = True
     for i, (H, W) in enumerate(SHAPES + (WIDE_SHAPES if groups == 2 else [])):
         big = torch.full((4, H, W, C + 4), float('nan'), device='cuda')
-        big[1:3, :, :, :C] = torch.randn((2, H, W, C), generator=_gen(H * W + C)).cuda()
+        big[1:3, :, :, :C] = torch.randn((2, H, W, C), generator=tc.gen(H * W + C)).cuda()
         xv = big[1:3, :, :, :C].permute(0, 3, 1, 2)                      # [2, C, H, W], pixel stride C + 4
         x = xv.contiguous(memory_format=CL)
         assert fused.gconv3x3_supported(conv, x, bias) and not fused.gconv3x3_supported(conv, xv, bias)
@@ -170,7 +124,7 @@ def test_kernel(monkeypatch, cg, groups, stride):
                 t = t if b is None else t + b.to(t.dtype).view(1, -1, 1, 1)
                 return F.relu(t) if relu else t
             ref64 = post(lin64)
-            e0 = _e0(lambda: post(conv(x)), ref64)
+            e0 = tc.e0(lambda: post(conv(x)), ref64)
             x0 = x.clone()
             got = fused.gconv3x3_bias_act(conv, x, b, relu=relu)
             assert torch.equal(x, x0) and got.is_contiguous(memory_format=CL) and got.shape == ref64.shape
@@ -194,7 +148,7 @@ def test_writes_stay_inside_the_channel_slice(cg, groups, stride):
     wt = fused.gconv_weight_of(conv)
     for H, W in ((9, 7), (8, 23)):
         Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-        x = torch.randn((2, C, H, W), generator=_gen(H)).cuda().contiguous(memory_format=CL)
+        x = torch.randn((2, C, H, W), generator=tc.gen(H)).cuda().contiguous(memory_format=CL)
         wide = torch.full((3, Ho + 1, Wo, C + 8), 7.0, device='cuda')            # a guard image behind, a guard row, guard channels
         out = wide[:2, :Ho, :, 4:4 + C].permute(0, 3, 1, 2)
         # (the guard row makes the image stride differ from Ho * Wo * pitch: one image per call)
@@ -215,7 +169,7 @@ def test_nan_and_inf_go_where_the_window_and_the_group_say(monkeypatch, cg, grou
     C = cg * groups
     conv = _conv(cg, groups, stride, cg + 7)
     H, W = 9, 11
-    x = torch.randn((2, C, H, W), generator=_gen(3)).cuda().contiguous(memory_format=CL)
+    x = torch.randn((2, C, H, W), generator=tc.gen(3)).cuda().contiguous(memory_format=CL)
     clean = fused.gconv3x3_bias_act(conv, x, None, relu=False)
     for value, (b, c, y, xx) in ((float('nan'), (1, cg + 1, 4, 6)), (float('inf'), (0, 0, 0, 10))):
         xp = x.clone(memory_format=torch.preserve_format)
@@ -250,29 +204,13 @@ def _reference(block, seed):
     """-> (the unfused block on the CPU, x, ref64, e0)."""
     spec = BLOCKS[block]
     module = _make(spec, seed)
-    x = torch.randn((2, spec[0]) + spec[6], generator=_gen(1000 + seed)).abs().cuda().contiguous(memory_format=CL)
+    x = torch.randn((2, spec[0]) + spec[6], generator=tc.gen(1000 + seed)).abs().cuda().contiguous(memory_format=CL)
     with torch.no_grad():
         ref64 = copy.deepcopy(module).double().cuda()(x.double())
         plain = copy.deepcopy(module).cuda().to(memory_format=CL)
-        e0 = _e0(lambda: plain(x), ref64)
+        e0 = tc.e0(lambda: plain(x), ref64)
     assert e0[0] > 0 and ref64.isfinite().all()
     return module, x, ref64, e0
-
-
-def _forward_checks(opt, x, rec):
-    """-> (output of the first call, launch trace of the second); first == second == fresh clone, bit for bit; x unchanged."""
-    x0 = x.clone()
-    with torch.no_grad():
-        first = opt(x)
-        rec.trace.clear()
-        second = opt(x)
-        trace = list(rec.trace)
-        assert torch.equal(x, x0), 'the forward wrote into its input'
-        third = opt(x0.clone(memory_format=torch.preserve_format))
-    assert first.isfinite().all()
-    if not any(t.startswith('miopen:') for t in trace):
-        assert torch.equal(first, second) and torch.equal(first, third)
-    return first, trace
 
 
 @pytest.mark.parametrize('block', list(BLOCKS))
@@ -281,14 +219,14 @@ def test_block_route(rec, block):
     for seed in SEEDS:
         module, x, ref64, e0 = _reference(block, seed)
         opt = rec.watch(tc.optimized(module).cuda().to(memory_format=CL))
-        got, trace = _forward_checks(opt, x, rec)
+        got, trace = tc.forward_checks(opt, x, rec)
         assert trace.count('gconv') == 1 and 'miopen:conv2' not in trace, trace
         assert trace == (['gemm3', 'gconv', 'pair'] if BLOCKS[block][3] else ['gemm3', 'gconv', 'gemm3']), trace
         assert fused.choices() == {}, 'the route made a choice-table entry'
         assert got.is_contiguous(memory_format=CL) and got.shape == ref64.shape
         ok &= _report('block %s | %s | seed %d' % (block, ' '.join(trace), seed), tc.errors(got, ref64), e0)
         fused.GCONV = False                                 # switched off: conv2 is torch's again
-        off, trace = _forward_checks(opt, x, rec)
+        off, trace = tc.forward_checks(opt, x, rec)
         assert 'gconv' not in trace and trace.count('miopen:conv2') == 1, trace
         assert float((off - got).abs().max()) <= 1e-4 * float(off.abs().max())
         fused.GCONV = True
@@ -339,12 +277,12 @@ def test_forward_after_load_state_dict(rec):
 def test_whole_network(rec):
     """resnext50 with the cocokp heads on [2, 3, 65, 49]: the optimized channels-last model against the double model."""
     net = tc.randomize_(network.factory('resnext50'), 7)
-    x = torch.randn((2, 3, 65, 49), generator=_gen(8)).cuda().contiguous(memory_format=CL)
+    x = torch.randn((2, 3, 65, 49), generator=tc.gen(8)).cuda().contiguous(memory_format=CL)
     with torch.no_grad():
         ref64 = copy.deepcopy(net).double().cuda()(x.double())
         plain = copy.deepcopy(net).cuda().to(memory_format=CL)
         fused.FORCE_PICK = 'conv'                                      # e0: torch's own convolutions, the heads' too
-        e0s = [_e0(lambda: plain(x)[i], r) for i, r in enumerate(ref64)]
+        e0s = [tc.e0(lambda: plain(x)[i], r) for i, r in enumerate(ref64)]
         fused.FORCE_PICK = 'x3'
         opt = rec.watch(network.optimize_for_inference_(copy.deepcopy(net)).cuda().to(memory_format=CL))
         rec.trace.clear()

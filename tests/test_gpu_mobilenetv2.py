@@ -34,20 +34,7 @@ _LAUNCHERS = {'conv1x1_unit_x3': 'unit', 'dwconv_bias_act': 'dwconv', 'channel_i
               'conv1x1_bias_act': 'gemm', 'conv1x1_bias_act_x3': 'gemm3', 'head_conv_x3': 'head_x3', 'head_epilogue': 'head_epilogue'}
 
 
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _e0(fn, ref64):
-    """(max, rms) error of the float32 torch computation ``fn`` against ``ref64``: the median of nine calls."""
-    errs = [tc.errors(fn(), ref64) for _ in range(9)]
-    return tuple(sorted(e[i] for e in errs)[4] for i in (0, 1))
-
-
-def _report(what, err, e0):
-    print('MBV2 %s | e0 max %.3e rms %.3e | err max %.3e rms %.3e | err/e0 max %.2f rms %.2f'
-          % (what, e0[0], e0[1], err[0], err[1], err[0] / max(e0[0], 1e-30), err[1] / max(e0[1], 1e-30)))
-    return err[0] <= 2 * e0[0] and err[1] <= 2 * e0[1]
+_report = functools.partial(tc.report, 'MBV2')
 
 
 def _same(got, want):
@@ -68,42 +55,11 @@ def _pieces(y, act, param):
     return bool((y < 0).any()) and bool((y > param).any()) and bool(((y > 0) & (y < param)).any())
 
 
-class _Recorder:
-    def __init__(self):
-        self.trace = []
-
-    def watch(self, module):
-        for name, m in module.named_modules():
-            if isinstance(m, nn.Conv2d):
-                m.register_forward_hook(lambda mod, args, out, name=name: self.trace.append('miopen:' + name))
-        return module
-
-
 @pytest.fixture
 def rec(monkeypatch):
     """Launch recorder; nothing may be timed; both new routes switched on, every ``pick`` forced to the project's kernel (the shapes
     here are far below the size from which it is chosen); the switches and the choice table restored after."""
-    r = _Recorder()
-    for attr, label in _LAUNCHERS.items():
-        real = getattr(fused, attr)
-
-        def wrapper(*args, _real=real, _label=label, **kwargs):
-            r.trace.append(_label)
-            return _real(*args, **kwargs)
-        monkeypatch.setattr(fused, attr, wrapper)
-
-    def time_ms(fn, reps=3):
-        raise AssertionError('a route timed something')
-    monkeypatch.setattr(fused, '_time_ms', time_ms)
-    monkeypatch.setattr(fused, 'FORCE_PICK', 'x3')
-    monkeypatch.setattr(fused, 'X3_TERMS', 6)
-    monkeypatch.setattr(fused, 'X3_UNIT', True)
-    monkeypatch.setattr(fused, 'MBV2', True)
-    monkeypatch.setattr(fused, 'UNIT_LEAKY', True)
-    saved = fused.choices()
-    fused.set_choices({}, replace=True)
-    yield r
-    fused.set_choices(saved, replace=True)
+    return tc.recorder(monkeypatch, _LAUNCHERS, ('X3_UNIT', 'MBV2', 'UNIT_LEAKY'), force_pick='x3')
 
 
 # ---- 1. the unit GEMM with the two new codes -------------------------------------------------------------------------------------
@@ -133,7 +89,7 @@ UNIT_SHAPES = {'126x16x96': ((2, 9, 7), 16, 96, 'dense'), '144x16x96': ((2, 9, 8
 def _unit_operands(shape, seed, non_finite=False):
     (B, H, W), K, N, layout = UNIT_SHAPES[shape]
     conv = tc.randomize_(nn.Conv2d(K, N, 1), seed).cuda()
-    wide = (torch.randn((B, 2 * K if layout == 'half' else K, H, W), generator=_gen(seed + 1)) * 3.0).cuda().contiguous(memory_format=CL)
+    wide = (torch.randn((B, 2 * K if layout == 'half' else K, H, W), generator=tc.gen(seed + 1)) * 3.0).cuda().contiguous(memory_format=CL)
     if non_finite:                       # a +Inf row and a NaN row of x (pixels 3 and 5): their output rows are NaN, no other is touched
         wide[0, :, 0, 3] = float('inf')
         wide[0, :, 0, 5] = float('nan')
@@ -218,7 +174,7 @@ def _dw_actp(x, taps, bias, k, stride, dilation, act, param, symbol='opa_dwconv_
 
 
 def _dw_operands(C, H, W, k, dtype, seed):
-    g = _gen(seed)
+    g = tc.gen(seed)
     x = (torch.randn((2, C, H, W), generator=g) * 4.0).to(dtype).cuda().contiguous(memory_format=CL)
     taps = (torch.randn((k * k, C), generator=g) * (2.0 / (k * k)) ** 0.5).to(dtype).cuda()
     bias = (torch.randn(C, generator=g) * 0.5).to(dtype).cuda()
@@ -284,8 +240,8 @@ def test_unit_gemm_entry_points_are_one_kernel(N, terms, act, third):
     with an N tail, N = 128: the 128-wide tile."""
     K = 72
     conv = tc.randomize_(nn.Conv2d(K, N, 1), K + N).cuda()
-    x = torch.randn((2, K, 13, 11), generator=_gen(K)).cuda().contiguous(memory_format=CL)
-    t = torch.randn((2, N, 13, 11), generator=_gen(N)).cuda().contiguous(memory_format=CL)
+    x = torch.randn((2, K, 13, 11), generator=tc.gen(K)).cuda().contiguous(memory_format=CL)
+    t = torch.randn((2, N, 13, 11), generator=tc.gen(N)).cuda().contiguous(memory_format=CL)
     partner, residual = (t if third == 'partner' else None), (t if third == 'residual' else None)
     w3, bp = fused._unit_weight_of(conv)
     old = torch.full((2, 2 * N if partner is not None else N, 13, 11), SENTINEL, device='cuda').contiguous(memory_format=CL)
@@ -347,7 +303,7 @@ def _trace_of(name):
 def _reference(name, seed):
     """-> (the unfused module on the CPU, x, ref64, e0, the largest input of a ReLU6)."""
     module = _make(name, seed)
-    x = (torch.randn((2, MODULES[name][1][0], 9, 7), generator=_gen(1000 + seed)) * 2.0).cuda().contiguous(memory_format=CL)
+    x = (torch.randn((2, MODULES[name][1][0], 9, 7), generator=tc.gen(1000 + seed)) * 2.0).cuda().contiguous(memory_format=CL)
     seen = []
     with torch.no_grad():
         m64 = copy.deepcopy(module).double().cuda()
@@ -356,25 +312,9 @@ def _reference(name, seed):
                 m.register_forward_pre_hook(lambda mod, args: seen.append(float(args[0].max())))
         ref64 = m64(x.double())
         plain = copy.deepcopy(module).cuda().to(memory_format=CL)
-        e0 = _e0(lambda: plain(x), ref64)
+        e0 = tc.e0(lambda: plain(x), ref64)
     assert e0[0] > 0 and ref64.isfinite().all()
     return module, x, ref64, e0, max(seen, default=0.0)
-
-
-def _forward_checks(opt, x, rec):
-    """-> (output of the first call, launch trace of the second); first == second == fresh clone, bit for bit; x unchanged."""
-    x0 = x.clone()
-    with torch.no_grad():
-        first = opt(x)
-        rec.trace.clear()
-        second = opt(x)
-        trace = list(rec.trace)
-        assert torch.equal(x, x0), 'the forward wrote into its input'
-        third = opt(x0.clone(memory_format=torch.preserve_format))
-    assert first.isfinite().all()
-    if not any(t.startswith('miopen:') for t in trace):
-        assert torch.equal(first, second) and torch.equal(first, third)
-    return first, trace
 
 
 @pytest.mark.parametrize('name', list(MODULES))
@@ -387,7 +327,7 @@ def test_route(rec, name):
         elif MODULES[name][1][5]:
             assert bool((ref64 < 0).any()), 'no negative output: the LeakyReLU is not exercised'
         opt = rec.watch(tc.optimized(module).cuda().to(memory_format=CL))
-        got, trace = _forward_checks(opt, x, rec)
+        got, trace = tc.forward_checks(opt, x, rec)
         assert trace == _trace_of(name), trace
         assert fused.choices() == {}, 'the route made a choice-table entry'
         assert got.is_contiguous(memory_format=CL) and got.shape == ref64.shape
@@ -401,11 +341,11 @@ def test_mbv2_route_selection(rec, name):
     channels-last take torch's forward."""
     module, x, _, _, _ = _reference(name, 0)
     opt = rec.watch(tc.optimized(module).cuda().to(memory_format=CL))
-    got, trace = _forward_checks(opt, x, rec)
+    got, trace = tc.forward_checks(opt, x, rec)
     assert trace == _trace_of(name) and opt._route_supported(x), trace
     convs = ['miopen:' + n for n, m in opt.named_modules() if isinstance(m, nn.Conv2d)]
     fused.MBV2 = False
-    off, trace = _forward_checks(opt, x, rec)
+    off, trace = tc.forward_checks(opt, x, rec)
     assert trace == convs and not opt._route_supported(x), trace
     assert float((off - got).abs().max()) <= 1e-4 * float(off.abs().max())
     fused.MBV2 = True
@@ -428,15 +368,15 @@ def test_leaky_unit_route_selection(rec, name):
     first = MODULES[name][1][2]
     module, x, _, _, _ = _reference(name, 0)
     opt = rec.watch(tc.optimized(module).cuda().to(memory_format=CL))
-    got, trace = _forward_checks(opt, x, rec)
+    got, trace = tc.forward_checks(opt, x, rec)
     assert trace == UNIT_NEW[first], trace
     fused.UNIT_LEAKY = False                                       # today's route, launch for launch, even with the pick forced
-    off, trace = _forward_checks(opt, x, rec)
+    off, trace = tc.forward_checks(opt, x, rec)
     assert trace == UNIT_OLD[first], trace
     assert float((off - got).abs().max()) <= 1e-4 * float(off.abs().max()) and bool((off < 0).any())
     fused.UNIT_LEAKY = True
     opt16 = rec.watch(tc.optimized(module).cuda().to(torch.bfloat16).to(memory_format=CL))
-    _, trace = _forward_checks(opt16, x.bfloat16().contiguous(memory_format=CL), rec)
+    _, trace = tc.forward_checks(opt16, x.bfloat16().contiguous(memory_format=CL), rec)
     assert trace == UNIT_OLD[first], trace
     with torch.no_grad(), torch.autocast('cuda', dtype=torch.bfloat16):
         rec.trace.clear()
@@ -452,7 +392,7 @@ def test_leaky_network_with_the_switch_off_launches_what_it_launches_today(rec):
     net = tc.randomize_(network.Shell(network.ShuffleNetV2K('shufflenetv2k16', leaky_relu=True),
                                       [network.CompositeField4(m, 1392) for m in headmeta.cocokp_metas()]), 3)
     opt = rec.watch(network.optimize_for_inference_(net).cuda().to(memory_format=CL))
-    x = torch.randn((2, 3, 65, 97), generator=_gen(9)).cuda().contiguous(memory_format=CL)
+    x = torch.randn((2, 3, 65, 97), generator=tc.gen(9)).cuda().contiguous(memory_format=CL)
     with torch.no_grad():
         fused.UNIT_LEAKY = False
         rec.trace.clear()
@@ -479,7 +419,7 @@ def _plain_e0(net, x, ref64):
     plain = copy.deepcopy(net).cuda().to(memory_format=CL)
     saved, fused.FORCE_PICK = fused.FORCE_PICK, 'conv'                 # e0: torch's own convolutions, the heads' too
     try:
-        return [_e0(lambda: plain(x)[i], r) for i, r in enumerate(ref64)]
+        return [tc.e0(lambda: plain(x)[i], r) for i, r in enumerate(ref64)]
     finally:
         fused.FORCE_PICK = saved
 
@@ -489,7 +429,7 @@ def test_whole_network(rec, name):
     """cocokp heads on [2, 3, 65, 97]: the optimized channels-last model against the double model, both head outputs; then the same
     after ``load_state_dict`` of other weights into the optimised network, against THEIR double model."""
     net, net2 = tc.randomize_(network.factory(name), 7), tc.randomize_(network.factory(name), 11)
-    x = torch.randn((2, 3, 65, 97), generator=_gen(8)).cuda().contiguous(memory_format=CL)
+    x = torch.randn((2, 3, 65, 97), generator=tc.gen(8)).cuda().contiguous(memory_format=CL)
     with torch.no_grad():
         ref64 = copy.deepcopy(net).double().cuda()(x.double())
         e0s = _plain_e0(net, x, ref64)

@@ -1,6 +1,6 @@
 """MobileNetV3 on the project's kernels (real kernels, MI355X): the depthwise stencil with hardswish, the squeeze-and-excitation
 kernels (``csrc/se.hip``), the unit-mode GEMM with hardswish and with a residual, the block route built from them
-(``network._MBV3Block._forward_unit``) and the two whole networks.
+(``network._InvertedResidual._forward_unit``) and the two whole networks.
 
 The error criterion is the one of ``test_gpu_unit_routes.py``: ``ref64`` the unfused module or op in ``double()``; ``e0`` the error
 against ``ref64`` of the SAME unfused float32 torch module or op (the median of nine calls), not of the code under test;
@@ -30,65 +30,22 @@ _LAUNCHERS = {'conv1x1_unit_x3': 'unit', 'dwconv_bias_act': 'dwconv', 'se_gate':
               'head_conv_x3': 'head_x3', 'head_epilogue': 'head_epilogue'}
 
 
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _e0(fn, ref64):
-    """(max, rms) error of the float32 torch computation ``fn`` against ``ref64``: the median of nine calls."""
-    errs = [tc.errors(fn(), ref64) for _ in range(9)]
-    return tuple(sorted(e[i] for e in errs)[4] for i in (0, 1))
-
-
-def _report(what, err, e0, extra=(0.0, 0.0)):
-    print('MBV3 %s | e0 max %.3e rms %.3e | err max %.3e rms %.3e | err/e0 max %.2f rms %.2f'
-          % (what, e0[0], e0[1], err[0], err[1], err[0] / max(e0[0], 1e-30), err[1] / max(e0[1], 1e-30)))
-    return err[0] <= 2 * e0[0] + extra[0] and err[1] <= 2 * e0[1] + extra[1]
-
-
-class _Recorder:
-    def __init__(self):
-        self.trace = []
-
-    def watch(self, module):
-        for name, m in module.named_modules():
-            if isinstance(m, nn.Conv2d):
-                m.register_forward_hook(lambda mod, args, out, name=name: self.trace.append('miopen:' + name))
-        return module
+_report = functools.partial(tc.report, 'MBV3')
 
 
 @pytest.fixture
 def rec(monkeypatch):
     """Launch recorder; nothing may be timed; the switches at their defaults and the choice table empty, both restored after."""
-    r = _Recorder()
-    for attr, label in _LAUNCHERS.items():
-        real = getattr(fused, attr)
-
-        def wrapper(*args, _real=real, _label=label, **kwargs):
-            r.trace.append(_label)
-            return _real(*args, **kwargs)
-        monkeypatch.setattr(fused, attr, wrapper)
-
-    def time_ms(fn, reps=3):
-        raise AssertionError('the MobileNetV3 route timed something')
-    monkeypatch.setattr(fused, '_time_ms', time_ms)
-    monkeypatch.setattr(fused, 'FORCE_PICK', None)
-    monkeypatch.setattr(fused, 'X3_TERMS', 6)
-    monkeypatch.setattr(fused, 'X3_UNIT', True)
-    monkeypatch.setattr(fused, 'MBV3', True)
-    saved = fused.choices()
-    fused.set_choices({}, replace=True)
-    yield r
-    fused.set_choices(saved, replace=True)
+    return tc.recorder(monkeypatch, _LAUNCHERS, ('X3_UNIT', 'MBV3'))
 
 
 # ---- 1. depthwise + hardswish ------------------------------------------------------------------------------------------------
 
 def _views(C, seed):
     """A dense tensor, a slice on an 8-byte boundary (channel vectors of 2) and one on a 4-byte boundary (of 1)."""
-    dense = torch.randn((2, C, 9, 7), generator=_gen(seed)).cuda().contiguous(memory_format=CL)
-    wide2 = torch.randn((2, C + 6, 9, 7), generator=_gen(seed + 1)).cuda().contiguous(memory_format=CL)
-    wide1 = torch.randn((2, C + 5, 9, 7), generator=_gen(seed + 2)).cuda().contiguous(memory_format=CL)
+    dense = torch.randn((2, C, 9, 7), generator=tc.gen(seed)).cuda().contiguous(memory_format=CL)
+    wide2 = torch.randn((2, C + 6, 9, 7), generator=tc.gen(seed + 1)).cuda().contiguous(memory_format=CL)
+    wide1 = torch.randn((2, C + 5, 9, 7), generator=tc.gen(seed + 2)).cuda().contiguous(memory_format=CL)
     return {'dense': dense, 'slice2': wide2[:, 2:2 + C], 'slice1': wide1[:, 1:1 + C]}
 
 
@@ -96,7 +53,7 @@ def _views(C, seed):
 @pytest.mark.parametrize('k', [3, 5])
 @pytest.mark.parametrize('C', [16, 72, 88, 200])
 def test_depthwise_with_hardswish(C, k, stride):
-    g = _gen(100 * C + 10 * k + stride)
+    g = tc.gen(100 * C + 10 * k + stride)
     w = (torch.randn((C, 1, k, k), generator=g) * (2.0 / (k * k)) ** 0.5).cuda()
     b = (torch.randn(C, generator=g) * 0.5).cuda()
     taps = w.reshape(C, k * k).t().contiguous()
@@ -104,7 +61,7 @@ def test_depthwise_with_hardswish(C, k, stride):
     for layout, x in _views(C, C + k + stride).items():
         assert fused.dwconv_supported(x, k, stride)
         ref64 = F.hardswish(F.conv2d(x.double(), w.double(), b.double(), stride, k // 2, groups=C))
-        e0 = _e0(lambda: F.hardswish(F.conv2d(x, w, b, stride, k // 2, groups=C)), ref64)
+        e0 = tc.e0(lambda: F.hardswish(F.conv2d(x, w, b, stride, k // 2, groups=C)), ref64)
         x0 = x.clone()
         got = fused.dwconv_bias_act(x, taps, b, k, stride, act=fused.ACT_HARDSWISH)
         assert torch.equal(x, x0) and got.is_contiguous(memory_format=CL) and got.isfinite().all()
@@ -128,7 +85,7 @@ def test_depthwise_act_code_is_checked():
 # ---- 2. the pool -------------------------------------------------------------------------------------------------------------
 
 def _se_convs(C, S, seed, w1_scale=1.0, w2_scale=1.0):
-    g = _gen(seed)
+    g = tc.gen(seed)
     fc1, fc2 = nn.Conv2d(C, S, 1), nn.Conv2d(S, C, 1)
     with torch.no_grad():
         fc1.weight.copy_(torch.randn(fc1.weight.shape, generator=g) * w1_scale / C ** 0.5)
@@ -163,7 +120,7 @@ def test_pool(shape, pitch):
     pixels are split over 51 workgroups per image.  The extra 2^-24 is one rounding of the result: torch's mean may be exact."""
     B, C, H, W = shape
     extra = 8 if pitch == 'strided' else 0
-    wide = F.hardswish(torch.randn((B, C + extra, H, W), generator=_gen(H + C)) * 2.0).cuda().contiguous(memory_format=CL)
+    wide = F.hardswish(torch.randn((B, C + extra, H, W), generator=tc.gen(H + C)) * 2.0).cuda().contiguous(memory_format=CL)
     x = wide[:, 4:4 + C] if extra else wide
     fc1, fc2 = _se_convs(C, 8, 1)
     x0 = x.clone()
@@ -175,7 +132,7 @@ def test_pool(shape, pitch):
         assert torch.equal(mean, means[0])
     assert torch.equal(means[0], means[1]) and torch.equal(x, x0) and means[0].isfinite().all()
     ref64 = x.double().mean((2, 3))
-    e0 = _e0(lambda: x.mean((2, 3)), ref64)
+    e0 = tc.e0(lambda: x.mean((2, 3)), ref64)
     one = 2.0 ** -24
     assert _report('pool %s %s' % ('x'.join(map(str, shape)), pitch), tc.errors(means[0], ref64), e0, extra=(one, one))
 
@@ -189,13 +146,13 @@ def test_gate_and_apply(C, S):
     fc1, fc2 = _se_convs(C, S, C + S, w1_scale=2.0, w2_scale=4.0)
     se.fc1, se.fc2 = fc1, fc2
     se = se.cuda()
-    x = (F.hardswish(torch.randn((B, C, 5, 5), generator=_gen(C)) * 2.0) * 3.0).cuda().contiguous(memory_format=CL)
+    x = (F.hardswish(torch.randn((B, C, 5, 5), generator=tc.gen(C)) * 2.0) * 3.0).cuda().contiguous(memory_format=CL)
 
     def gate_of(module, t):
         return module.scale_activation(module.fc2(module.activation(module.fc1(module.avgpool(t))))).flatten(1)
     with torch.no_grad():
         ref64 = gate_of(copy.deepcopy(se).double(), x.double())
-        e0 = _e0(lambda: gate_of(se, x), ref64)
+        e0 = tc.e0(lambda: gate_of(se, x), ref64)
         # all three pieces of the hardsigmoid occur (told by its argument: 6 * (1 / 6) need not be 1 to the last bit)
         m64 = copy.deepcopy(se).double()
         z = m64.fc2(m64.activation(m64.fc1(m64.avgpool(x.double())))).flatten(1)
@@ -221,9 +178,9 @@ def test_gate_and_apply(C, S):
 @pytest.mark.parametrize('K,N', [(16, 64), (72, 40), (672, 112), (960, 160)])
 def test_unit_gemm_with_hardswish_and_with_residual(K, N):
     conv = tc.randomize_(nn.Conv2d(K, N, 1), K + N).cuda()
-    x = torch.randn((2, K, 13, 11), generator=_gen(K)).cuda().contiguous(memory_format=CL)
-    res = torch.randn((2, N, 13, 11), generator=_gen(N)).cuda().contiguous(memory_format=CL)
-    wide = torch.randn((2, N + 6, 13, 11), generator=_gen(N + 1)).cuda().contiguous(memory_format=CL)
+    x = torch.randn((2, K, 13, 11), generator=tc.gen(K)).cuda().contiguous(memory_format=CL)
+    res = torch.randn((2, N, 13, 11), generator=tc.gen(N)).cuda().contiguous(memory_format=CL)
+    wide = torch.randn((2, N + 6, 13, 11), generator=tc.gen(N + 1)).cuda().contiguous(memory_format=CL)
     ok = True
     with torch.no_grad():
         conv64 = copy.deepcopy(conv).double()
@@ -231,18 +188,18 @@ def test_unit_gemm_with_hardswish_and_with_residual(K, N):
         assert fused.unit_conv_x3_supported(conv, x)
         got = fused.conv1x1_unit_x3(conv, x, act=fused.ACT_HARDSWISH)
         ref64 = F.hardswish(lin64)
-        ok &= _report('unit+hardswish K %d N %d' % (K, N), tc.errors(got, ref64), _e0(lambda: F.hardswish(conv(x)), ref64))
+        ok &= _report('unit+hardswish K %d N %d' % (K, N), tc.errors(got, ref64), tc.e0(lambda: F.hardswish(conv(x)), ref64))
         for layout, r in (('dense', res), ('slice', wide[:, 2:2 + N])):
             assert fused.unit_conv_x3_supported(conv, x, residual=r)
             r0 = r.clone()
             got = fused.conv1x1_unit_x3(conv, x, residual=r, act=fused.ACT_NONE)
             assert torch.equal(r, r0) and got.is_contiguous(memory_format=CL)
             ref64 = lin64 + r.double()
-            ok &= _report('unit+residual K %d N %d %s' % (K, N, layout), tc.errors(got, ref64), _e0(lambda: conv(x) + r, ref64))
+            ok &= _report('unit+residual K %d N %d %s' % (K, N, layout), tc.errors(got, ref64), tc.e0(lambda: conv(x) + r, ref64))
         # the activation behind the residual, and the codes that are the existing kernels
         got = fused.conv1x1_unit_x3(conv, x, residual=res, act=fused.ACT_HARDSWISH)
         ref64 = F.hardswish(lin64 + res.double())
-        ok &= _report('unit+residual+hardswish K %d N %d' % (K, N), tc.errors(got, ref64), _e0(lambda: F.hardswish(conv(x) + res), ref64))
+        ok &= _report('unit+residual+hardswish K %d N %d' % (K, N), tc.errors(got, ref64), tc.e0(lambda: F.hardswish(conv(x) + res), ref64))
         assert torch.equal(fused.conv1x1_unit_x3(conv, x, residual=res, act=fused.ACT_RELU),
                            F.relu(fused.conv1x1_unit_x3(conv, x, residual=res, act=fused.ACT_NONE)))
     assert ok        # (act= and relu= are one call of one entry point; the C twins: test_unit_gemm_entry_points_are_one_kernel)
@@ -260,8 +217,8 @@ def test_unit_gemm_entry_points_are_one_kernel(N, terms, act, partner, monkeypat
     with an N tail, N = 128: the 128-wide tile.  The launcher calls the second one only."""
     K, shape = 72, (2, 13, 11)
     conv = tc.randomize_(nn.Conv2d(K, N, 1), K + N).cuda()
-    x = torch.randn((2, K, 13, 11), generator=_gen(K)).cuda().contiguous(memory_format=CL)
-    third = torch.randn((2, N, 13, 11), generator=_gen(N)).cuda().contiguous(memory_format=CL) if partner else None
+    x = torch.randn((2, K, 13, 11), generator=tc.gen(K)).cuda().contiguous(memory_format=CL)
+    third = torch.randn((2, N, 13, 11), generator=tc.gen(N)).cuda().contiguous(memory_format=CL) if partner else None
     w3, bp = fused._unit_weight_of(conv)
     outs = [torch.full((2, 2 * N if partner else N, 13, 11), SENTINEL, device='cuda').contiguous(memory_format=CL) for _ in range(2)]
     lib, vp = _lib.lib(), ctypes.c_void_p
@@ -284,7 +241,7 @@ def test_unit_gemm_entry_points_are_one_kernel(N, terms, act, partner, monkeypat
 def test_depthwise_entry_points_are_one_kernel(k, stride, act, dtype):
     """``opa_dwconv_bias_act(relu=a)`` against ``opa_dwconv_act(act=a)``, raw, with a bias, each into its own sentinel-filled
     output: bit for bit.  The launcher calls the second one only."""
-    C, g = 8, _gen(10 * k + stride)
+    C, g = 8, tc.gen(10 * k + stride)
     x = torch.randn((2, C, 7, 5), generator=g).to(dtype).cuda().contiguous(memory_format=CL)
     taps = (torch.randn((k * k, C), generator=g) * (2.0 / (k * k)) ** 0.5).to(dtype).cuda()
     b = (torch.randn(C, generator=g) * 0.5).to(dtype).cuda()
@@ -339,29 +296,13 @@ def _make(spec, seed):
 def _reference(spec, seed):
     """-> (the unfused block on the CPU, x, ref64, e0)."""
     module = _make(spec, seed)
-    x = torch.randn((2, spec[0], 13, 11), generator=_gen(1000 + seed)).cuda().contiguous(memory_format=CL)
+    x = torch.randn((2, spec[0], 13, 11), generator=tc.gen(1000 + seed)).cuda().contiguous(memory_format=CL)
     with torch.no_grad():
         ref64 = copy.deepcopy(module).double().cuda()(x.double())
         plain = copy.deepcopy(module).cuda().to(memory_format=CL)
-        e0 = _e0(lambda: plain(x), ref64)
+        e0 = tc.e0(lambda: plain(x), ref64)
     assert e0[0] > 0 and ref64.isfinite().all()
     return module, x, ref64, e0
-
-
-def _forward_checks(opt, x, rec):
-    """-> (output of the first call, launch trace of the second); first == second == fresh clone, bit for bit; x unchanged."""
-    x0 = x.clone()
-    with torch.no_grad():
-        first = opt(x)
-        rec.trace.clear()
-        second = opt(x)
-        trace = list(rec.trace)
-        assert torch.equal(x, x0), 'the forward wrote into its input'
-        third = opt(x0.clone(memory_format=torch.preserve_format))
-    assert first.isfinite().all()
-    if not any(t.startswith('miopen:') for t in trace):
-        assert torch.equal(first, second) and torch.equal(first, third)
-    return first, trace
 
 
 @pytest.mark.parametrize('block', list(BLOCKS))
@@ -371,14 +312,14 @@ def test_block_route(rec, block):
     for seed in SEEDS:
         module, x, ref64, e0 = _reference(spec, seed)
         opt = rec.watch(tc.optimized(module).cuda().to(memory_format=CL))
-        got, trace = _forward_checks(opt, x, rec)
+        got, trace = tc.forward_checks(opt, x, rec)
         assert trace == _trace_of(spec), trace
         assert fused.choices() == {}, 'the route made a choice-table entry'
         assert got.is_contiguous(memory_format=CL) and got.shape == ref64.shape
         ok &= _report('block %s | %s | seed %d' % (block, ' '.join(trace), seed), tc.errors(got, ref64), e0)
         # switched off: torch's forward, convolution for convolution
         fused.MBV3 = False
-        off, trace = _forward_checks(opt, x, rec)
+        off, trace = tc.forward_checks(opt, x, rec)
         convs = [name for name, m in opt.named_modules() if isinstance(m, nn.Conv2d)]
         assert trace == ['miopen:' + name for name in convs], trace
         assert float((off - got).abs().max()) <= 1e-4 * float(off.abs().max())
@@ -400,6 +341,26 @@ def test_block_route_declines(rec):
     assert rec.trace and all(t.startswith('miopen:') for t in rec.trace), rec.trace
 
 
+def test_block_route_declines_a_tensor_autograd_follows(rec):
+    """A block without an expanding convolution hands ``x`` itself to the stencil: a tensor that autograd follows takes the torch
+    forward and keeps its graph; detached and under ``no_grad`` the same block takes the route.  Stride 1: the block's input is
+    also the residual operand of the projecting GEMM; stride 2: the stencil is the only kernel that reads ``x``."""
+    for stride in (1, 2):
+        opt = rec.watch(tc.optimized(_make((16, 3, 16, 16, False, False, stride), 0)).cuda().to(memory_format=CL))
+        with torch.enable_grad():
+            x = torch.randn((1, 16, 5, 5), generator=tc.gen(3)).cuda().contiguous(memory_format=CL).requires_grad_(True)
+            assert not opt._route_supported(x), stride
+            rec.trace.clear()
+            out = opt(x)
+        assert rec.trace and all(t.startswith('miopen:') for t in rec.trace), rec.trace
+        assert out.grad_fn is not None
+        with torch.no_grad():
+            assert opt._route_supported(x.detach())
+            rec.trace.clear()
+            opt(x.detach())
+        assert rec.trace == ['dwconv', 'unit'], rec.trace
+
+
 # ---- 6. operands follow the parameters ---------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize('block', ['large12', 'small1'])
@@ -417,7 +378,7 @@ def test_forward_after_load_state_dict(rec, block):
         assert rec.trace == _trace_of(spec), rec.trace
         ref64 = copy.deepcopy(module1).double().cuda()(x.double())
         plain = copy.deepcopy(module1).cuda().to(memory_format=CL)
-        e0 = _e0(lambda: plain(x), ref64)
+        e0 = tc.e0(lambda: plain(x), ref64)
         assert not torch.equal(before, after)
         assert torch.equal(after, other(x)), 'stale operand: max |delta| %.3g' % (after - other(x)).abs().max().item()
     assert _report('block %s after load_state_dict' % block, tc.errors(after, ref64), e0)
@@ -430,12 +391,12 @@ def test_whole_network(rec, name):
     """cocokp heads on [2, 3, 65, 49]: the optimized channels-last model against the double model, both head outputs.  The heads'
     1x1 convolutions are pinned to the split-operand kernel (960 and 576 input channels: ``head_conv_x3``), so nothing is timed."""
     net = tc.randomize_(network.factory(name), 7)
-    x = torch.randn((2, 3, 65, 49), generator=_gen(8)).cuda().contiguous(memory_format=CL)
+    x = torch.randn((2, 3, 65, 49), generator=tc.gen(8)).cuda().contiguous(memory_format=CL)
     with torch.no_grad():
         ref64 = copy.deepcopy(net).double().cuda()(x.double())
         plain = copy.deepcopy(net).cuda().to(memory_format=CL)
         fused.FORCE_PICK = 'conv'                                      # e0: torch's own convolutions, the heads' too
-        e0s = [_e0(lambda: plain(x)[i], r) for i, r in enumerate(ref64)]
+        e0s = [tc.e0(lambda: plain(x)[i], r) for i, r in enumerate(ref64)]
         fused.FORCE_PICK = 'x3'
         opt = rec.watch(network.optimize_for_inference_(copy.deepcopy(net)).cuda().to(memory_format=CL))
         rec.trace.clear()

@@ -48,62 +48,17 @@ _LAUNCHERS = {'conv3x3_dilated_bias_act_x3': 'conv3x3_d', 'maxpool3x3_bias_act_'
               'head_epilogue': 'head_epilogue'}
 
 
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _e0(fn, ref64):
-    """(max, rms) error of torch's own computation ``fn`` against ``ref64``: the median of nine calls."""
-    errs = [tc.errors(fn(), ref64) for _ in range(9)]
-    return tuple(sorted(e[i] for e in errs)[4] for i in (0, 1))
-
-
 def _report(family, what, err, e0):
-    print('RESNETV %s %s | e0 max %.3e rms %.3e | err max %.3e rms %.3e | err/e0 max %.2f rms %.2f | k=%d'
-          % (family, what, e0[0], e0[1], err[0], err[1], err[0] / max(e0[0], 1e-30), err[1] / max(e0[1], 1e-30), K[family]))
-    return err[0] <= K[family] * e0[0] and err[1] <= K[family] * e0[1]
-
-
-class _Recorder:
-    def __init__(self):
-        self.trace = []
-
-    def watch(self, module):
-        for name, m in module.named_modules():
-            if isinstance(m, nn.Conv2d):
-                m.register_forward_hook(lambda mod, args, out, name=name: self.trace.append('miopen:' + name))
-        return module
+    return tc.report('RESNETV', '%s %s' % (family, what), err, e0, K[family], show_k=True)
 
 
 @pytest.fixture
 def rec(monkeypatch):
     """Launch recorder; nothing may be timed: ``FORCE_PICK = 'x3'``, and every float32 1x1 convolution of ``conv_bias_act`` is answered
     'gemm3' by a choice table that stays empty (``test_gpu_gconv.py``'s recipe and its reason)."""
-    r = _Recorder()
-    for attr, label in _LAUNCHERS.items():
-        real = getattr(fused, attr)
-
-        def wrapper(*args, _real=real, _label=label, **kwargs):
-            r.trace.append(_label)
-            return _real(*args, **kwargs)
-        monkeypatch.setattr(fused, attr, wrapper)
-
-    def time_ms(fn, reps=3):
-        raise AssertionError('a route timed something')
-    monkeypatch.setattr(fused, '_time_ms', time_ms)
-    monkeypatch.setattr(fused, 'FORCE_PICK', 'x3')
-    monkeypatch.setattr(fused, 'X3_TERMS', 6)
-    for attr in ('X3_PAIR', 'X3_CONV3', 'X3_STEM', 'X3_HEAD', 'GCONV'):
-        monkeypatch.setattr(fused, attr, True)
     monkeypatch.setenv('OPA_CONV1X1', 'gemm')                 # (bfloat16: decided without timing too)
-
-    class Pinned(dict):
-        def get(self, key, default=None):
-            if len(key) == 6 and key[0] == 'torch.float32':      # a key of conv_bias_act
-                return 'gemm3'
-            return super().get(key, default)
-    monkeypatch.setattr(fused, '_CHOICE', Pinned())
-    yield r
+    return tc.recorder(monkeypatch, _LAUNCHERS, ('X3_PAIR', 'X3_CONV3', 'X3_STEM', 'X3_HEAD', 'GCONV'), force_pick='x3',
+                       table=tc.PinnedGemm3())
 
 
 # ---- 1. the dilated kernel -----------------------------------------------------------------------------------------------------
@@ -115,7 +70,7 @@ def _conv(c_in, c_out, stride, d, seed):
 def _poisoned(H, W, C, seed):
     """-> (x, big): ``x`` is images 1-2 of the four-image channels-last ``big`` whose images 0 and 3 are NaN."""
     big = torch.full((4, H, W, C), float('nan'), device='cuda')
-    big[1:3] = torch.randn((2, H, W, C), generator=_gen(seed)).cuda()
+    big[1:3] = torch.randn((2, H, W, C), generator=tc.gen(seed)).cuda()
     return big[1:3].permute(0, 3, 1, 2), big
 
 
@@ -128,7 +83,7 @@ def test_dilated_kernel(monkeypatch, d, s, terms):
     ok = True
     for c_in, c_out in ((64, 64), (64, 128), (128, 64)):
         conv = _conv(c_in, c_out, s, d, 100 * d + 10 * s + c_in // 64 + c_out // 64)
-        bias = (torch.randn(c_out, generator=_gen(c_in + c_out)) * 0.5).cuda()
+        bias = (torch.randn(c_out, generator=tc.gen(c_in + c_out)) * 0.5).cuda()
         zero = torch.zeros_like(bias)
         for i, (H, W) in enumerate(SHAPES if c_in == 64 else [(9, 7)]):
             x, big = _poisoned(H, W, c_in, H * W + c_in)
@@ -143,7 +98,7 @@ def test_dilated_kernel(monkeypatch, d, s, terms):
                     t = t + b.to(t.dtype).view(1, -1, 1, 1)
                     return F.relu(t) if relu else t
                 ref64 = post(lin64)
-                e0 = _e0(lambda: post(conv(x)), ref64)
+                e0 = tc.e0(lambda: post(conv(x)), ref64)
                 big0 = big.clone()
                 got = fused.conv3x3_dilated_bias_act_x3(conv, x, b, relu=relu)
                 assert got.isfinite().all(), 'a tap left its image'
@@ -166,7 +121,7 @@ def test_nan_and_inf_go_where_the_window_says(monkeypatch, s):
     conv = _conv(C, 64, s, d, 17 + s)
     zero = torch.zeros(64, device='cuda')
     H, W = 9, 11
-    x = torch.randn((2, C, H, W), generator=_gen(3)).cuda().contiguous(memory_format=CL)
+    x = torch.randn((2, C, H, W), generator=tc.gen(3)).cuda().contiguous(memory_format=CL)
     clean = fused.conv3x3_dilated_bias_act_x3(conv, x, zero, relu=False)
     for value, (b, c, y, xx) in ((float('nan'), (1, 5, 4, 6)), (float('inf'), (0, 0, 0, 10))):
         xp = x.clone(memory_format=torch.preserve_format)
@@ -192,8 +147,8 @@ def _same_with_nans(a, b):
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16], ids=['float32', 'bfloat16'])
 def test_pool_kernel(dtype, C):
     for H, W in SHAPES:
-        x = (torch.randn((2, C, H, W), generator=_gen(H * W + C)) * 3).to(dtype).cuda().contiguous(memory_format=CL)
-        bias = torch.randn(C, generator=_gen(C)).to(dtype).cuda()
+        x = (torch.randn((2, C, H, W), generator=tc.gen(H * W + C)) * 3).to(dtype).cuda().contiguous(memory_format=CL)
+        bias = torch.randn(C, generator=tc.gen(C)).to(dtype).cuda()
         assert fused.maxpool3x3_supported(x) and fused.maxpool3x3_supported(x, bias)
         assert not fused.maxpool3x3_supported(x.contiguous()) or H * W == 1 or C == 1
         assert not fused.maxpool3x3_supported(x, bias.float() if dtype == torch.bfloat16 else bias.bfloat16())
@@ -233,7 +188,7 @@ def test_pool_writes_stay_inside_its_output(dtype):
     C = 64
     for H, W in ((9, 7), (8, 23)):
         ho, wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-        x = torch.randn((2, C, H, W), generator=_gen(H)).to(dtype).cuda().contiguous(memory_format=CL)
+        x = torch.randn((2, C, H, W), generator=tc.gen(H)).to(dtype).cuda().contiguous(memory_format=CL)
         wide = torch.full((4, ho, wo, C), 7.0, dtype=dtype, device='cuda')
         out = wide[1:3].permute(0, 3, 1, 2)                    # the two images in the middle
         fused.maxpool3x3_bias_act_(x, out=out)
@@ -246,7 +201,7 @@ def test_pool_writes_stay_inside_its_output(dtype):
 def test_pool_without_epilogue_keeps_the_sign_of_a_zero(dtype):
     """Windows of +0.0 and -0.0 alone: the first of equal values in torch's scan order stays, so the BITS are torch's."""
     x = torch.zeros((2, 8, 9, 7), dtype=dtype)
-    x[torch.rand(x.shape, generator=_gen(21)) < 0.5] = -0.0
+    x[torch.rand(x.shape, generator=tc.gen(21)) < 0.5] = -0.0
     x[0, :, :4] = -0.0                                            # whole windows of -0.0 too
     x = x.cuda().contiguous(memory_format=CL)
     got, want = fused.maxpool3x3_bias_act_(x), F.max_pool2d(x, 3, 2, 1)
@@ -285,30 +240,13 @@ BLOCKS = {'bottleneck': (_bottleneck, (2, 256, 13, 11), ['gemm3', 'conv3x3_d', '
 def _reference(make, shape, seed, dtype=torch.float32):
     """-> (the unfused module on the CPU, x, ref64, e0)."""
     module = make(seed)
-    x = torch.randn(shape, generator=_gen(1000 + seed)).abs().cuda().to(dtype).contiguous(memory_format=CL)
+    x = torch.randn(shape, generator=tc.gen(1000 + seed)).abs().cuda().to(dtype).contiguous(memory_format=CL)
     with torch.no_grad():
         ref64 = copy.deepcopy(module).double().cuda()(x.double())
         plain = copy.deepcopy(module).cuda().to(dtype).to(memory_format=CL)
-        e0 = _e0(lambda: plain(x), ref64)
+        e0 = tc.e0(lambda: plain(x), ref64)
     assert e0[0] > 0 and ref64.isfinite().all()
     return module, x, ref64, e0
-
-
-def _forward_checks(opt, x, rec):
-    """-> (output of the first call, launch trace of the second); first == second == fresh clone, bit for bit, where no MIOpen step
-    is on the route; x unchanged."""
-    x0 = x.clone()
-    with torch.no_grad():
-        first = opt(x)
-        rec.trace.clear()
-        second = opt(x)
-        trace = list(rec.trace)
-        assert torch.equal(x, x0), 'the forward wrote into its input'
-        third = opt(x0.clone(memory_format=torch.preserve_format))
-    assert first.isfinite().all()
-    if not any(t.startswith('miopen:') for t in trace):
-        assert torch.equal(first, second) and torch.equal(first, third)
-    return first, trace
 
 
 @pytest.mark.parametrize('block', list(BLOCKS))
@@ -320,14 +258,14 @@ def test_block_route(rec, block):
         convs = [m for m in module.modules() if isinstance(m, nn.Conv2d)]
         assert all(m.stride == (1, 1) for m in convs) and sum(m.dilation == (2, 2) for m in convs) == (1 if block == 'bottleneck' else 2)
         opt = rec.watch(tc.optimized(module).cuda().to(memory_format=CL))
-        got, trace = _forward_checks(opt, x, rec)
+        got, trace = tc.forward_checks(opt, x, rec)
         assert trace == route, trace
         assert not [t for t in trace if t.startswith('miopen:')], trace
         assert fused.choices() == {}, 'the route made a choice-table entry'
         assert got.is_contiguous(memory_format=CL) and got.shape == ref64.shape == x.shape[:1] + (ref64.shape[1],) + x.shape[2:]
         ok &= _report('block', '%s | %s | seed %d' % (block, ' '.join(trace), seed), tc.errors(got, ref64), e0)
         fused.FORCE_PICK = 'conv'                           # the other side of every pick: torch's convolution + the epilogue pass
-        off, trace = _forward_checks(opt, x, rec)
+        off, trace = tc.forward_checks(opt, x, rec)
         assert 'conv3x3_d' not in trace and 'miopen:conv2' in trace, trace
         assert float((off - got).abs().max()) <= 1e-4 * float(off.abs().max())
         _report('block', '%s | %s | seed %d' % (block, ' '.join(trace), seed), tc.errors(off, ref64), e0)       # (printed, not judged here)
@@ -396,12 +334,12 @@ def _net(name, seed, **options):
 
 def _whole(rec, what, net):
     """The optimized channels-last net against the double net, per head -> (launch trace, every head within the bound)."""
-    x = torch.randn((2, 3, 65, 49), generator=_gen(8)).cuda().contiguous(memory_format=CL)
+    x = torch.randn((2, 3, 65, 49), generator=tc.gen(8)).cuda().contiguous(memory_format=CL)
     with torch.no_grad():
         ref64 = copy.deepcopy(net).double().cuda()(x.double())
         plain = copy.deepcopy(net).cuda().to(memory_format=CL)
         fused.FORCE_PICK = 'conv'                                      # e0: torch's own convolutions, the heads' too
-        e0s = [_e0(lambda: plain(x)[i], r) for i, r in enumerate(ref64)]
+        e0s = [tc.e0(lambda: plain(x)[i], r) for i, r in enumerate(ref64)]
         fused.FORCE_PICK = 'x3'
         opt = rec.watch(network.optimize_for_inference_(copy.deepcopy(net)).cuda().to(memory_format=CL))
         rec.trace.clear()
@@ -440,7 +378,7 @@ def test_the_pool_takes_the_epilogue_of_a_raw_stem(rec):
     the pass followed by torch's pool, bit for bit."""
     base = tc.randomize_(network.Resnet('resnet18', pool0_stride=2), 5)
     opt = network.optimize_for_inference_(copy.deepcopy(base)).cuda().bfloat16().to(memory_format=CL)
-    x = torch.randn((2, 3, 65, 49), generator=_gen(6)).cuda().bfloat16().contiguous(memory_format=CL)
+    x = torch.randn((2, 3, 65, 49), generator=tc.gen(6)).cuda().bfloat16().contiguous(memory_format=CL)
     raws = []
     opt.input_block[0].register_forward_hook(lambda mod, args, out: raws.append(out.clone()))      # (the kernel only reads it)
     with torch.no_grad():
@@ -455,7 +393,7 @@ def test_the_pool_takes_the_epilogue_of_a_float32_stem_that_ran_as_torchs_convol
     """``pick('stempool')`` on its 'conv' side: the raw convolution, then ONE pass (bias + ReLU + pool), equal to torch's three ops."""
     base = tc.randomize_(network.Resnet('resnet18', pool0_stride=2), 5)
     opt = network.optimize_for_inference_(copy.deepcopy(base)).cuda().to(memory_format=CL)
-    x = torch.randn((2, 3, 65, 49), generator=_gen(6)).cuda().contiguous(memory_format=CL)
+    x = torch.randn((2, 3, 65, 49), generator=tc.gen(6)).cuda().contiguous(memory_format=CL)
     raws = []
     opt.input_block[0].register_forward_hook(lambda mod, args, out: raws.append(out.clone()))
     with torch.no_grad():

@@ -46,54 +46,14 @@ _LAUNCHERS = {'conv1x1_unit_x3': 'unit', 'dwconv_bias_act': 'dwconv', 'channel_i
 _vp = ctypes.c_void_p
 
 
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _e0(fn, ref64):
-    """(max, rms) error of torch's own computation ``fn`` against ``ref64``: the median of nine calls."""
-    errs = [tc.errors(fn(), ref64) for _ in range(9)]
-    return tuple(sorted(e[i] for e in errs)[4] for i in (0, 1))
-
-
 def _report(family, what, err, e0):
-    print('SHUFFLEOPT %s %s | e0 max %.3e rms %.3e | err max %.3e rms %.3e | err/e0 max %.2f rms %.2f | k=%d'
-          % (family, what, e0[0], e0[1], err[0], err[1], err[0] / max(e0[0], 1e-30), err[1] / max(e0[1], 1e-30), K[family]))
-    return err[0] <= K[family] * e0[0] and err[1] <= K[family] * e0[1]
-
-
-class _Recorder:
-    def __init__(self):
-        self.trace = []
-
-    def watch(self, module):
-        for name, m in module.named_modules():
-            if isinstance(m, nn.Conv2d):
-                m.register_forward_hook(lambda mod, args, out, name=name: self.trace.append('miopen:' + name))
-        return module
+    return tc.report('SHUFFLEOPT', '%s %s' % (family, what), err, e0, K[family], show_k=True)
 
 
 @pytest.fixture
 def rec(monkeypatch):
     """Launch recorder (``test_gpu_resnet_variants.py``'s recipe); nothing may be timed: ``FORCE_PICK = 'x3'``, an empty choice table."""
-    r = _Recorder()
-    for attr, label in _LAUNCHERS.items():
-        real = getattr(fused, attr)
-
-        def wrapper(*args, _real=real, _label=label, **kwargs):
-            r.trace.append(_label)
-            return _real(*args, **kwargs)
-        monkeypatch.setattr(fused, attr, wrapper)
-
-    def time_ms(fn, reps=3):
-        raise AssertionError('a route timed something')
-    monkeypatch.setattr(fused, '_time_ms', time_ms)
-    monkeypatch.setattr(fused, 'FORCE_PICK', 'x3')
-    monkeypatch.setattr(fused, 'X3_TERMS', 6)
-    for attr in ('X3_UNIT', 'X3_HEAD'):
-        monkeypatch.setattr(fused, attr, True)
-    monkeypatch.setattr(fused, '_CHOICE', {})
-    yield r
+    return tc.recorder(monkeypatch, _LAUNCHERS, ('X3_UNIT', 'X3_HEAD'), force_pick='x3')
 
 
 # ---- 1. the stencil kernel ---------------------------------------------------------------------------------------------------------
@@ -254,30 +214,13 @@ def _reference(make, shape, seed):
     """-> (the unfused module on the CPU, x, ref64, e0).  ``x`` has both signs: the unit's first 1x1 convolution sees negative inputs
     and, behind the random batch norms, negative pre-activations."""
     module = make(seed)
-    x = torch.randn(shape, generator=_gen(1000 + seed)).cuda().contiguous(memory_format=CL)
+    x = torch.randn(shape, generator=tc.gen(1000 + seed)).cuda().contiguous(memory_format=CL)
     with torch.no_grad():
         ref64 = copy.deepcopy(module).double().cuda()(x.double())
         plain = copy.deepcopy(module).cuda().to(memory_format=CL)
-        e0 = _e0(lambda: plain(x), ref64)
+        e0 = tc.e0(lambda: plain(x), ref64)
     assert e0[0] > 0 and ref64.isfinite().all()
     return module, x, ref64, e0
-
-
-def _forward_checks(opt, x, rec):
-    """-> (output of the first call, launch trace of the second); first == second == fresh clone, bit for bit, where no MIOpen step
-    is on the route; x unchanged."""
-    x0 = x.clone()
-    with torch.no_grad():
-        first = opt(x)
-        rec.trace.clear()
-        second = opt(x)
-        trace = list(rec.trace)
-        assert torch.equal(x, x0), 'the forward wrote into its input'
-        third = opt(x0.clone(memory_format=torch.preserve_format))
-    assert first.isfinite().all()
-    if not any(t.startswith('miopen:') for t in trace):
-        assert torch.equal(first, second) and torch.equal(first, third)
-    return first, trace
 
 
 @pytest.mark.parametrize('unit', list(UNITS))
@@ -288,14 +231,14 @@ def test_unit_route(rec, unit):
     for seed in SEEDS:
         module, x, ref64, e0 = _reference(make, shape, seed)
         opt = rec.watch(tc.optimized(module).cuda().to(memory_format=CL))
-        got, trace = _forward_checks(opt, x, rec)
+        got, trace = tc.forward_checks(opt, x, rec)
         assert trace == route, trace
         assert not [t for t in trace if t.startswith('miopen:')], trace
         assert fused.choices() == {}, 'the route made a choice-table entry'
         assert got.is_contiguous(memory_format=CL) and got.shape == ref64.shape
         ok &= _report('unit', '%s | %s | seed %d' % (unit, ' '.join(trace), seed), tc.errors(got, ref64), e0)
         fused.FORCE_PICK = 'conv'               # the other side of the pick: the stencil, torch's 1x1 convolutions, the interleave
-        off, trace = _forward_checks(opt, x, rec)
+        off, trace = tc.forward_checks(opt, x, rec)
         assert 'unit' not in trace and 'dwconv' in trace and not [t for t in trace if t.endswith('branch2.3') or t.endswith('branch1.0')], trace
         assert float((off - got).abs().max()) <= 1e-4 * float(off.abs().max())
         _report('unit', '%s | %s | seed %d' % (unit, ' '.join(trace), seed), tc.errors(off, ref64), e0)          # (printed, not judged here)
@@ -314,7 +257,7 @@ def test_leaky_relu_unit(rec):
             assert all(isinstance(m, nn.LeakyReLU) for m in (module.branch2[2], module.branch2[7]))
             opt = rec.watch(tc.optimized(module).cuda().to(memory_format=CL))
             assert not opt._unit_route_supported(x)
-            got, trace = _forward_checks(opt, x, rec)
+            got, trace = tc.forward_checks(opt, x, rec)
             assert trace.count('dwconv') == (2 if first else 1) and 'unit' not in trace and 'interleave' in trace, trace
             assert not [t for t in trace if t.endswith('branch2.3') or t.endswith('branch1.0')], trace
             err = tc.errors(got, ref64)
@@ -380,12 +323,12 @@ def _net(seed, **options):
 
 def _whole(rec, what, net):
     """The optimized channels-last net against the double net, per head -> (launch trace, every head within the bound)."""
-    x = torch.randn((2, 3, 65, 49), generator=_gen(8)).cuda().contiguous(memory_format=CL)
+    x = torch.randn((2, 3, 65, 49), generator=tc.gen(8)).cuda().contiguous(memory_format=CL)
     with torch.no_grad():
         ref64 = copy.deepcopy(net).double().cuda()(x.double())
         plain = copy.deepcopy(net).cuda().to(memory_format=CL)
         fused.FORCE_PICK = 'conv'                                      # e0: torch's own convolutions, the heads' too
-        e0s = [_e0(lambda: plain(x)[i], r) for i, r in enumerate(ref64)]
+        e0s = [tc.e0(lambda: plain(x)[i], r) for i, r in enumerate(ref64)]
         fused.FORCE_PICK = 'x3'
         opt = rec.watch(network.optimize_for_inference_(copy.deepcopy(net)).cuda().to(memory_format=CL))
         rec.trace.clear()

@@ -16,7 +16,6 @@ import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
-from torch import nn
 
 from openpifpaf_amd import fused, network
 
@@ -35,57 +34,14 @@ PAIRS = [(16, 64), (32, 128), (48, 192), (64, 256)]
 SIZES = [(1, 1), (9, 7), (17, 35)]
 
 
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _e0(fn, ref64):
-    """(max, rms) error of the float32 torch computation ``fn`` against ``ref64``: the median of nine calls."""
-    errs = [tc.errors(fn(), ref64) for _ in range(9)]
-    return tuple(sorted(e[i] for e in errs)[4] for i in (0, 1))
-
-
-def _report(what, err, e0):
-    print('SQZ %s | e0 max %.3e rms %.3e | err max %.3e rms %.3e | err/e0 max %.2f rms %.2f'
-          % (what, e0[0], e0[1], err[0], err[1], err[0] / max(e0[0], 1e-30), err[1] / max(e0[1], 1e-30)))
-    return err[0] <= 2 * e0[0] and err[1] <= 2 * e0[1]
-
-
-class _Recorder:
-    def __init__(self):
-        self.trace = []
-
-    def watch(self, module):
-        for name, m in module.named_modules():
-            if isinstance(m, nn.Conv2d):
-                m.register_forward_hook(lambda mod, args, out, name=name: self.trace.append('miopen:' + name))
-        return module
+_report = functools.partial(tc.report, 'SQZ')
 
 
 @pytest.fixture
 def rec(monkeypatch):
     """Launch recorder; nothing may be timed; the route switched on, the other switches at their defaults and the choice table
     empty, all restored after."""
-    r = _Recorder()
-    for attr, label in _LAUNCHERS.items():
-        real = getattr(fused, attr)
-
-        def wrapper(*args, _real=real, _label=label, **kwargs):
-            r.trace.append(_label)
-            return _real(*args, **kwargs)
-        monkeypatch.setattr(fused, attr, wrapper)
-
-    def time_ms(fn, reps=3):
-        raise AssertionError('the SqueezeNet route timed something')
-    monkeypatch.setattr(fused, '_time_ms', time_ms)
-    monkeypatch.setattr(fused, 'FORCE_PICK', None)
-    monkeypatch.setattr(fused, 'X3_TERMS', 6)
-    monkeypatch.setattr(fused, 'X3_UNIT', True)
-    monkeypatch.setattr(fused, 'FIRE', True)
-    saved = fused.choices()
-    fused.set_choices({}, replace=True)
-    yield r
-    fused.set_choices(saved, replace=True)
+    return tc.recorder(monkeypatch, _LAUNCHERS, ('X3_UNIT', 'FIRE'))
 
 
 # ---- 1. the pool in ceil mode ------------------------------------------------------------------------------------------------
@@ -97,7 +53,7 @@ def test_pool_ceil_mode(dtype, relu):
     that an index error across images shows."""
     for H, W in [(1, 1), (2, 2), (7, 8), (8, 7), (8, 8), (16, 17)]:
         for C in (8, 64, 128):
-            x = torch.randn((2, C, H, W), generator=_gen(100 * H + W + C)).to(dtype).cuda().contiguous(memory_format=CL)
+            x = torch.randn((2, C, H, W), generator=tc.gen(100 * H + W + C)).to(dtype).cuda().contiguous(memory_format=CL)
             assert fused.maxpool3x3_supported(x)
             want = F.max_pool2d(F.relu(x) if relu else x, 3, 2, 1, ceil_mode=True)
             x0 = x.clone()
@@ -126,7 +82,7 @@ def _expand_torch(e1, e3, h):
 @pytest.mark.parametrize('s,e', PAIRS)
 def test_fire_expand(s, e, size, terms):
     e1, e3 = _expands(s, e, s + e)
-    h = F.relu(torch.randn((2, s) + size, generator=_gen(s + size[0]))).cuda().contiguous(memory_format=CL)     # (a squeezed tensor is >= 0)
+    h = F.relu(torch.randn((2, s) + size, generator=tc.gen(s + size[0]))).cuda().contiguous(memory_format=CL)     # (a squeezed tensor is >= 0)
     with torch.no_grad():
         ref64 = _expand_torch(copy.deepcopy(e1).double(), copy.deepcopy(e3).double(), h.double())
         assert fused.fire_expand_supported(e1, e3, h)
@@ -140,7 +96,7 @@ def test_fire_expand(s, e, size, terms):
         what = 's %d e %d %dx%d terms %d' % (s, e, size[0], size[1], terms)
         # both halves alone as well as whole: a wrong half cannot hide behind the other's scale
         for part, sl in (('whole', slice(None)), ('1x1', slice(0, e)), ('3x3', slice(e, 2 * e))):
-            e0 = _e0(lambda: _expand_torch(e1, e3, h)[:, sl], ref64[:, sl])
+            e0 = tc.e0(lambda: _expand_torch(e1, e3, h)[:, sl], ref64[:, sl])
             ok &= _report('fire expand %s %s' % (what, part), tc.errors(got[:, sl], ref64[:, sl]), e0)
     assert ok
 
@@ -153,7 +109,7 @@ def test_fire_expand_non_finite(pixel, value, terms):
     holds it (of its image only); every other output bit for bit the clean run's."""
     s, e, H, W = 16, 64, 9, 7
     e1, e3 = _expands(s, e, 5)
-    h = F.relu(torch.randn((2, s, H, W), generator=_gen(6))).cuda().contiguous(memory_format=CL)
+    h = F.relu(torch.randn((2, s, H, W), generator=tc.gen(6))).cuda().contiguous(memory_format=CL)
     b, y, x = pixel
     with torch.no_grad():
         clean = fused.fire_expand_bias_relu(e1, e3, h, terms=terms)
@@ -173,11 +129,11 @@ def test_fire_expand_non_finite(pixel, value, terms):
 def _reference(cfg, seed):
     """-> (the unfused Fire on the CPU, x, ref64, e0)."""
     module = tc.randomize_(network._Fire(*cfg), seed)
-    x = F.relu(torch.randn((2, cfg[0], 9, 7), generator=_gen(1000 + seed))).cuda().contiguous(memory_format=CL)
+    x = F.relu(torch.randn((2, cfg[0], 9, 7), generator=tc.gen(1000 + seed))).cuda().contiguous(memory_format=CL)
     with torch.no_grad():
         ref64 = copy.deepcopy(module).double().cuda()(x.double())
         plain = copy.deepcopy(module).cuda().to(memory_format=CL)
-        e0 = _e0(lambda: plain(x), ref64)
+        e0 = tc.e0(lambda: plain(x), ref64)
     assert e0[0] > 0 and ref64.isfinite().all()
     return module, x, ref64, e0
 
@@ -239,7 +195,7 @@ def test_forward_after_load_state_dict(rec):
         assert rec.trace == ['unit', 'fire_expand'], rec.trace
         ref64 = copy.deepcopy(module1).double().cuda()(x.double())
         plain = copy.deepcopy(module1).cuda().to(memory_format=CL)
-        e0 = _e0(lambda: plain(x), ref64)
+        e0 = tc.e0(lambda: plain(x), ref64)
         assert not torch.equal(before, after)
         assert torch.equal(after, other(x)), 'stale operand: max |delta| %.3g' % (after - other(x)).abs().max().item()
     assert _report('block %s after load_state_dict' % '-'.join(map(str, cfg)), tc.errors(after, ref64), e0)
@@ -253,12 +209,12 @@ def test_whole_network(rec, shape):
     1x1 convolutions are pinned to the split-operand kernel (512 input channels: ``head_conv_x3``), so nothing is timed.  The even
     input makes every pool's input even: 32 x 25 -> 17 x 13 -> 9 x 7 -> 5 x 4."""
     net = tc.randomize_(network.factory('squeezenet'), 7)
-    x = torch.randn(shape, generator=_gen(8)).cuda().contiguous(memory_format=CL)
+    x = torch.randn(shape, generator=tc.gen(8)).cuda().contiguous(memory_format=CL)
     with torch.no_grad():
         ref64 = copy.deepcopy(net).double().cuda()(x.double())
         plain = copy.deepcopy(net).cuda().to(memory_format=CL)
         fused.FORCE_PICK = 'conv'                                      # e0: torch's own convolutions, the heads' too
-        e0s = [_e0(lambda: plain(x)[i], r) for i, r in enumerate(ref64)]
+        e0s = [tc.e0(lambda: plain(x)[i], r) for i, r in enumerate(ref64)]
         fused.FORCE_PICK = 'x3'
         opt = rec.watch(network.optimize_for_inference_(copy.deepcopy(net)).cuda().to(memory_format=CL))
         rec.trace.clear()

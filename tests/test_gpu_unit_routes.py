@@ -28,40 +28,10 @@ _LAUNCHERS = {'conv1x1_unit_x3': 'unit', 'dwconv_bias_act': 'dwconv', 'channel_i
               'conv1x1_bias_act': 'gemm', 'conv1x1_bias_act_x3': 'gemm3', 'head_conv_x3': 'head_x3', 'head_epilogue': 'head_epilogue'}
 
 
-class _Recorder:
-    def __init__(self):
-        self.trace, self.timed = [], 0
-
-    def watch(self, module):
-        for name, m in module.named_modules():
-            if isinstance(m, nn.Conv2d):
-                m.register_forward_hook(lambda mod, args, out, name=name: self.trace.append('miopen:' + name))
-        return module
-
-
 @pytest.fixture
 def rec(monkeypatch):
     """Launch recorder; the switches and the choice table saved and restored; the table starts EMPTY, nothing forced."""
-    r = _Recorder()
-    for attr, label in _LAUNCHERS.items():
-        real = getattr(fused, attr)
-
-        def wrapper(*args, _real=real, _label=label, **kwargs):
-            r.trace.append(_label)
-            return _real(*args, **kwargs)
-        monkeypatch.setattr(fused, attr, wrapper)
-
-    def time_ms(fn, reps=3):
-        r.timed += 1
-        raise AssertionError('the unit route timed something')
-    monkeypatch.setattr(fused, '_time_ms', time_ms)
-    monkeypatch.setattr(fused, 'FORCE_PICK', None)
-    monkeypatch.setattr(fused, 'X3_TERMS', 6)
-    monkeypatch.setattr(fused, 'X3_UNIT', True)
-    saved = fused.choices()
-    fused.set_choices({}, replace=True)
-    yield r
-    fused.set_choices(saved, replace=True)
+    return tc.recorder(monkeypatch, _LAUNCHERS, ('X3_UNIT',))
 
 
 def _make(inp, oup, first, stride, seed):
@@ -90,30 +60,13 @@ def _reference(spec, shape, seed):
     with torch.no_grad():
         ref64 = copy.deepcopy(module).double().cuda()(x.double())
         plain = copy.deepcopy(module).cuda().to(memory_format=CL)
-        errs = [tc.errors(plain(x), ref64) for _ in range(9)]
-    e0 = tuple(sorted(e[i] for e in errs)[4] for i in (0, 1))
+        e0 = tc.e0(lambda: plain(x), ref64)
     assert e0[0] > 0 and ref64.isfinite().all()
     return module, x, ref64, e0
 
 
 def _optimized(module, rec, dtype=torch.float32):
     return rec.watch(tc.optimized(module).cuda().to(dtype).to(memory_format=CL))
-
-
-def _forward_checks(opt, x, rec):
-    """-> (output of the first call, launch trace of the second); first == second == fresh clone, bit for bit; x unchanged."""
-    x0 = x.clone()
-    with torch.no_grad():
-        first = opt(x)
-        rec.trace.clear()
-        second = opt(x)
-        trace = list(rec.trace)
-        assert torch.equal(x, x0), 'the forward wrote into its input'
-        third = opt(x0.clone(memory_format=torch.preserve_format))
-    assert first.isfinite().all()
-    if not any(t.startswith('miopen:') for t in trace):            # (a route of the project's kernels alone repeats bit for bit)
-        assert torch.equal(first, second) and torch.equal(first, third)
-    return first, trace
 
 
 @pytest.mark.parametrize('unit', list(UNITS))
@@ -126,7 +79,7 @@ def test_unit_on_the_split_operand_gemm(rec, unit):
         opt = _optimized(module, rec)
         table = {_key(spec, shape): 'x3'}
         fused.set_choices(table, replace=True)
-        got, trace = _forward_checks(opt, x, rec)
+        got, trace = tc.forward_checks(opt, x, rec)
         assert trace == NEW[spec[2]], trace
         assert fused.choices() == table and rec.timed == 0
         assert got.is_contiguous(memory_format=CL) and got.shape == ref64.shape
@@ -136,7 +89,7 @@ def test_unit_on_the_split_operand_gemm(rec, unit):
         rows.append((seed, err, e0))
         # ... and the table's other side IS today's route, launch for launch
         fused.set_choices({_key(spec, shape): 'conv'}, replace=True)
-        _, trace = _forward_checks(opt, x, rec)
+        _, trace = tc.forward_checks(opt, x, rec)
         assert trace == OLD[spec[2]], trace
     bad = [(seed, err, e0) for seed, err, e0 in rows if err[0] > 2 * e0[0] or err[1] > 2 * e0[1]]
     assert not bad, bad
@@ -149,14 +102,14 @@ def test_default_decision_is_by_size_and_never_timed(rec):
     large = torch.randn((2, 348, 96, 96), generator=torch.Generator().manual_seed(2)).relu().cuda().contiguous(memory_format=CL)
     assert 2 * 96 * 96 == 18432
     opt = _optimized(module, rec)
-    _, trace = _forward_checks(opt, small, rec)
+    _, trace = tc.forward_checks(opt, small, rec)
     assert trace == OLD[False] and fused.choices() == {_key(spec, small.shape): 'conv'}, (trace, fused.choices())
-    got, trace = _forward_checks(opt, large, rec)
+    got, trace = tc.forward_checks(opt, large, rec)
     assert trace == NEW[False] and fused.choices()[_key(spec, large.shape)] == 'x3' and rec.timed == 0, trace
     # X3_UNIT off: today's trace at any size, no decision asked for
     fused.set_choices({}, replace=True)
     fused.X3_UNIT = False
-    off, trace = _forward_checks(opt, large, rec)
+    off, trace = tc.forward_checks(opt, large, rec)
     assert trace == OLD[False] and fused.choices() == {} and rec.timed == 0
     assert float((off - got).abs().max()) <= 1e-4 * float(off.abs().max()) and not torch.equal(off, got)
     fused.X3_UNIT = True
@@ -170,7 +123,7 @@ def test_default_decision_is_by_size_and_never_timed(rec):
     # bfloat16: today's trace even with the route forced
     fused.FORCE_PICK = 'x3'
     opt16 = _optimized(module, rec, torch.bfloat16)
-    _, trace = _forward_checks(opt16, large.bfloat16().contiguous(memory_format=CL), rec)
+    _, trace = tc.forward_checks(opt16, large.bfloat16().contiguous(memory_format=CL), rec)
     assert trace == OLD[False] and rec.timed == 0, trace
 
 
@@ -283,10 +236,10 @@ def test_head_with_1392_input_channels(rec, which):
             e0 = tuple(sorted(e[i] for e in errs)[4] for i in (0, 1))
             fused.FORCE_PICK = None
             fused.set_choices({}, replace=True)
-            _, trace = _forward_checks(opt, x, rec)
+            _, trace = tc.forward_checks(opt, x, rec)
             assert trace == ['miopen:conv'] and rec.timed == 0, trace              # 1197 pixels: by size
             fused.set_choices({('torch.float32/unit', 3 * 21 * 19, 1392, head.conv.out_channels, False, False): 'x3'}, replace=True)
-            got, trace = _forward_checks(opt, x, rec)
+            got, trace = tc.forward_checks(opt, x, rec)
         assert trace == ['unit'] and rec.timed == 0, trace
         err = tc.errors(got, ref64)
         print('UNITROUTE head-%s float32 forced | %s | seed %d | e0 max %.3e rms %.3e | err max %.3e rms %.3e | err/e0 max %.2f rms %.2f'
