@@ -13,6 +13,9 @@
 // 144-B LDS pitch); 4 waves as 2(M) x 2(N); XCD-aware tile order; epilogue through a wave-private LDS patch.
 // Measured (tools/gpu/gemm_f32_probe.py, batch 32 at 641 px): layer-1 expand 64->256 + residual 1.70 ms against 3.3 ms
 // for MIOpen's convolution + the epilogue pass; 105-119 TFLOP/s on the compute-bound shapes (dense f32 MFMA peak 157).
+// With a residual the last K-step, which has no operands to request, requests the residual of epilogue block 0; block 1's follows at
+// the epilogue's entry and the bias waits in LDS (as in gemm_f32x3.hip): layer-1 tail 1.68 -> 1.44 ms (profiles/tail_prefetch/).
+#include <type_traits>
 #include "common.hpp"
 
 namespace opa {
@@ -44,7 +47,10 @@ __global__ __launch_bounds__(256, BN == 128 ? OPA_F32_WGS : 3) void gemm_f32_bia
     constexpr int LDS_A = kF32BM * kF32Pitch, LDS_B = BN * kF32Pitch;
     constexpr int STAGE_BYTES = kF32Stages * (LDS_A + LDS_B) * 4;
     constexpr int EPI_BYTES = 4 * 32 * WN * 4; // per wave a 32 x WN f32 patch
-    __shared__ __attribute__((aligned(16))) unsigned char smem[STAGE_BYTES > EPI_BYTES ? STAGE_BYTES : EPI_BYTES];
+    // (with a residual the BN bias values wait behind the stages: read with ds_read in the epilogue they do not share a counter with
+    //  the residual vectors in flight)
+    constexpr int SMEM_BYTES = STAGE_BYTES > EPI_BYTES ? STAGE_BYTES : EPI_BYTES;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM_BYTES + (RES ? BN * 4 : 0)];
     float* stage0 = reinterpret_cast<float*>(smem);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -104,13 +110,41 @@ __global__ __launch_bounds__(256, BN == 128 ? OPA_F32_WGS : 3) void gemm_f32_bia
         for (int p = 0; p < BN / 32; p++)
             *reinterpret_cast<f32x4_t*>(sB + (p * 32 + s_row) * kF32Pitch + s_col) = rb[p];
     };
+    // The residual, in the epilogue's own layout: vector t of 32-row block i of the wave tile is row t * 64 / VEC_PER_ROW +
+    // lane / VEC_PER_ROW, 4 floats.  A descriptor over the tile's rows that exist; a row past M gets an offset beyond every
+    // buffer (a select, no branch): the load answers with zeros and requests nothing.
+    constexpr int VEC_PER_ROW = WN / 4;
+    constexpr int VPL = 32 * VEC_PER_ROW / 64; // vectors per lane and block (8 | 4)
+    f32x4_t rres[2][RES ? VPL : 1];
+    auto fetch_res = [&](int i) {
+        if constexpr (RES) {
+            const int rows_here = M - m0 < kF32BM ? M - m0 : kF32BM;
+            const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<float*>(res + (size_t)m0 * N + n0), 0, (int)(((size_t)(rows_here - 1) * N + BN) * 4), 0x00020000);
+            const int lrow = wm * 64 + lane / VEC_PER_ROW;
+            const unsigned off = ((unsigned)lrow * (unsigned)N + (unsigned)(wn * WN + (lane % VEC_PER_ROW) * 4)) * 4u;
+#pragma unroll
+            for (int t = 0; t < VPL; t++) {
+                const int urow = i * 32 + t * (64 / VEC_PER_ROW);      // uniform part of the row
+                rres[i][t] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(
+                    r_rsrc, lrow < rows_here - urow ? off : 0xFFFFFFF0u, urow * N * 4, 0));
+            }
+            __builtin_amdgcn_sched_barrier(0); // (keeps the requests where they are written)
+        }
+    };
     fetch(0);
+    if constexpr (RES) {
+        if (tid < BN) reinterpret_cast<float*>(smem + SMEM_BYTES)[tid] = bias[n0 + tid];
+    }
     store(0);
     __syncthreads();
-    int buf = 0;
-    for (int k0 = 0; k0 < K; k0 += kF32BK, buf ^= (kF32Stages - 1)) {
-        const bool more = k0 + kF32BK < K;
+    // one K-step.  `last` (with a residual only): the final one, peeled at compile time -- it has no operands to request, so the
+    // residual of epilogue block 0 travels in its place and has this step's multiplications to arrive in.
+    auto kstep = [&](auto last, int k0, int buf) {
+        constexpr bool LAST = decltype(last)::value;
+        const bool more = !LAST && k0 + kF32BK < K;
         if (more && OPA_GEMM_DIAG == 0) fetch(k0 + kF32BK);          // the next K-step's operands travel while this one multiplies
+        if constexpr (LAST) fetch_res(0);
         const float* sA = stage0 + buf * (LDS_A + LDS_B);
         const float* sB = sA + LDS_A;
 #pragma unroll
@@ -135,32 +169,28 @@ __global__ __launch_bounds__(256, BN == 128 ? OPA_F32_WGS : 3) void gemm_f32_bia
         if (kF32Stages == 1) __syncthreads(); // one stage: every wave is done reading it
         if (more && OPA_GEMM_DIAG < 2) store(buf ^ (kF32Stages - 1)); // (two stages: the other one, whose readers passed the previous step's barrier)
         __syncthreads();
+    };
+    if constexpr (RES) {
+        int k0 = 0, buf = 0;
+        for (; k0 < K - kF32BK; k0 += kF32BK, buf ^= (kF32Stages - 1)) kstep(std::false_type{}, k0, buf);
+        kstep(std::true_type{}, k0, buf);
+    } else {
+        int buf = 0;
+        for (int k0 = 0; k0 < K; k0 += kF32BK, buf ^= (kF32Stages - 1)) kstep(std::false_type{}, k0, buf);
     }
     // (the loop's last barrier: staging LDS is free, reuse it for the epilogue)
 
     // epilogue, one 32-row block of the wave tile at a time through a wave-private f32 patch: the residual load and
-    // the output store are row-contiguous 16-B vectors
-    constexpr int VEC_PER_ROW = WN / 4;
-    constexpr int VPL = 32 * VEC_PER_ROW / 64;
+    // the output store are row-contiguous 16-B vectors.  The residual of block 0 has been on its way since the last K-step;
+    // block 1's is requested here, where the fragment and staging registers are dead, and travels while block 0 is written out.
     float* patch = reinterpret_cast<float*>(smem) + wave * (32 * WN);
+    fetch_res(1);
 #pragma unroll
     for (int i = 0; i < 2; i++) {
-        constexpr int VPRE = VPL > 4 ? 4 : VPL; // residual vectors fetched ahead (16 registers); the rest in the loop
-        f32x4_t rv[VPRE];
-        if (RES) {                             // they travel while the patch is written
-#pragma unroll
-            for (int t = 0; t < VPRE; t++) {
-                const int v = t * 64 + lane;
-                const int row = v / VEC_PER_ROW, c4 = (v % VEC_PER_ROW) * 4;
-                const int m = m0 + wm * 64 + i * 32 + row;
-                rv[t] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-                if (m < M) rv[t] = *reinterpret_cast<const f32x4_t*>(res + (size_t)m * N + n0 + wn * WN + c4);
-            }
-        }
 #pragma unroll
         for (int j = 0; j < NT; j++) {
             const int col = j * 32 + (lane & 31);
-            const float b = bias[n0 + wn * WN + col];
+            const float b = RES ? reinterpret_cast<const float*>(smem + SMEM_BYTES)[wn * WN + col] : bias[n0 + wn * WN + col];
 #pragma unroll
             for (int r = 0; r < 16; r++) {     // C layout: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
                 const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
@@ -176,10 +206,7 @@ __global__ __launch_bounds__(256, BN == 128 ? OPA_F32_WGS : 3) void gemm_f32_bia
             const int m = m0 + wm * 64 + i * 32 + row;
             if (m < M) {
                 f32x4_t f = *reinterpret_cast<const f32x4_t*>(patch + row * WN + c4);
-                if (RES) {
-                    if (t < VPRE) f += rv[t < VPRE ? t : 0];
-                    else f += *reinterpret_cast<const f32x4_t*>(res + (size_t)m * N + n0 + wn * WN + c4);
-                }
+                if constexpr (RES) f += rres[i][t];
                 if (RELU) {
 #pragma unroll
                     for (int e = 0; e < 4; e++) f[e] = fmaxf(f[e], 0.0f);
@@ -189,7 +216,7 @@ __global__ __launch_bounds__(256, BN == 128 ? OPA_F32_WGS : 3) void gemm_f32_bia
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        asm volatile("" ::: "memory");         // (keeps the second block's residual loads -- 32 registers -- behind this block)
+        asm volatile("" ::: "memory");
     }
 }
 

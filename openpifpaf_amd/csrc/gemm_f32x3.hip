@@ -30,6 +30,8 @@
 // (ds_read_b128 fragments of 16 consecutive rows fall on 16 different bank groups AND the 8-byte plane stores of the split do
 // not collide: with rows padded to 80 B a third of the LDS cycles were store conflicts; profiles/r6/gemm_x3_swizzle_ab.log:
 // 2-7 % on the reduce shapes); XCD-aware tile order and epilogue as in gemm_f32.hip.
+// Block tails (RES): the last two K-steps used to request the last tile again (unconditional loads, nothing read them); the residual
+// of epilogue block 0 travels in those slots, block 1's from the epilogue's entry, the bias waits in LDS: layer-3 tail 0.81 -> 0.66 ms.
 //
 // Non-finite and tiny operands (tests/test_gpu_x3_edges.py): a NaN or +-Inf element of A makes its output ROW
 // NaN, one of W its output COLUMN (a float32 GEMM gives +-Inf for an Inf operand: the split turns Inf into (Inf, NaN, NaN));
@@ -38,6 +40,7 @@
 // activation into 0 before the split.  The stem's eighth window row and column meet zero weights, so a non-finite pixel
 // reaches every output whose 8x8 window holds it (0 x Inf), not the 7x7 ones alone: written down and pinned by a test.  Operands below 2^-110: see split_bf16.hpp; an element loses less than
 // 2^-125 sum_k (|a_mk| + |w_nk|).
+#include <type_traits>
 #include "common.hpp"
 #include "split_bf16.hpp"
 
@@ -194,7 +197,10 @@ __global__ __launch_bounds__(256, OPA_X3_WGS) void gemm_f32x3_bias_act_kernel(
 #endif
     constexpr int STAGE_BYTES = 3 * (LDS_A + LDS_B) * 2 + OPA_X3_PAD_LDS;
     constexpr int EPI_BYTES = 4 * 32 * WN * 4; // per wave a 32 x WN f32 patch
-    __shared__ __attribute__((aligned(16))) unsigned char smem[STAGE_BYTES > EPI_BYTES ? STAGE_BYTES : EPI_BYTES];
+    // (a block tail keeps its BN bias values behind the stages: read with ds_read in the epilogue they do not share a counter with
+    //  the residual vectors in flight -- as a global load there, the wait for the bias was a wait for every residual vector requested before it)
+    constexpr int SMEM_BYTES = STAGE_BYTES > EPI_BYTES ? STAGE_BYTES : EPI_BYTES;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM_BYTES + (RES && !UNIT ? BN * 4 : 0)];
     unsigned short* sA = reinterpret_cast<unsigned short*>(smem);          // [3][128][pitch]
     unsigned short* sB = sA + 3 * LDS_A;                                    // [3][BN][pitch]
 
@@ -351,29 +357,81 @@ __global__ __launch_bounds__(256, OPA_X3_WGS) void gemm_f32x3_bias_act_kernel(
         for (int t = 0; t < WV; t++)
             if (WTOT % 256 == 0 || t * 256 + tid < WTOT) *reinterpret_cast<u32x4_t*>(sB + sb_off[t]) = rb[t];
     };
+    // The residual of a block tail (RES, not UNIT), in the epilogue's own layout: vector t of 32-row block i of the wave tile is
+    // row t * 64 / VEC_PER_ROW + lane / VEC_PER_ROW, 4 floats.  A descriptor over the tile's rows that exist; a row past M gets
+    // an offset beyond every buffer (a select, no branch): the load answers with zeros and requests nothing.
+    constexpr int VEC_PER_ROW = WN / 4;
+    constexpr int VPL = 32 * VEC_PER_ROW / 64; // vectors per lane and block (8 | 4)
+    // ... of block 0 that travel in K-step k_last - BK; the rest in K-step k_last, where both staging sets and the weight's registers
+    // are dead.  One: with two (four) the 128-wide six-term tail spills 3 (7) registers, and a scratch reload counts in vmcnt
+    // like the loads it would have to overtake (profiles/tail_prefetch/resource_usage.md)
+    constexpr int VRA = 1;
+    constexpr bool TAIL_RES = RES && !UNIT;
+    f32x4_t rres[2][TAIL_RES ? VPL : 1];
+    auto fetch_res = [&](int i, int t_begin, int t_end) {
+        if constexpr (TAIL_RES) {
+            const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<float*>(res + (size_t)m0 * N + n0), 0, (int)(((size_t)(rows_here - 1) * N + BN) * 4), 0x00020000);
+            // (ONE offset register per lane, the block and the vector as the load's scalar offset: eight offsets would stay live through the K loop)
+            const int lrow = wm * 64 + lane / VEC_PER_ROW;
+            const unsigned off = ((unsigned)lrow * (unsigned)N + (unsigned)(wn * WN + (lane % VEC_PER_ROW) * 4)) * 4u;
+#pragma unroll
+            for (int t = t_begin; t < t_end; t++) {
+                const int urow = i * 32 + t * (64 / VEC_PER_ROW);      // uniform part of the row
+                rres[i][t] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(
+                    r_rsrc, lrow < rows_here - urow ? off : 0xFFFFFFF0u, urow * N * 4, 0));
+            }
+        }
+    };
+    // fragment BYTE offsets of the wave's first A and B rows for the two halves of a K-step (32 rows further: 32 pitches further, the
+    // swizzle has a period of 16 rows).  In a block tail the peeled steps are copies of the step's code: the offsets are made
+    // opaque there, or every copy puts them together again from pieces that then stay live, and spill, across the K loop.
+    int frag_a[kX3BK / 16], frag_b[kX3BK / 16];
+    if constexpr (TAIL_RES) {
+#pragma unroll
+        for (int h = 0; h < kX3BK / 16; h++) {
+            frag_a[h] = 2 * x3_lds(wm * 64 + (lane & 31), h * 16 + (lane >> 5) * 8);
+            frag_b[h] = 2 * x3_lds(wn * WN + (lane & 31), h * 16 + (lane >> 5) * 8);
+            asm volatile("" : "+v"(frag_a[h]), "+v"(frag_b[h]));
+        }
+    }
     // one K-step: LDS holds tile k0, `cur` the activation of tile k0 + BK (requested a step ago), `nxt` is free.  The weight's
     // loads are issued BEFORE the activation's: vmcnt counts in order, so the wait for the weight of tile k0 + BK (behind this
-    // step's MFMAs) leaves the activation of tile k0 + 2 BK in flight
-    auto step = [&](int k0, f32x4_t (&cur)[NPA], f32x4_t (&nxt)[NPA]) {
+    // step's MFMAs) leaves the activation of tile k0 + 2 BK in flight.
+    // `tail` 0: any step.  1 | 2 (block tails only): the steps k_last - BK and k_last, peeled at compile time -- what `tail` 0 would
+    // request there AGAIN (the activation of tile k_last; then that and the weight of tile k_last) nothing ever reads: the residual
+    // of epilogue block 0 travels in those slots, behind the step's real weight fetch, so that the wait for the weight leaves it in flight.
+    auto step = [&](auto tail, int k0, f32x4_t (&cur)[NPA], f32x4_t (&nxt)[NPA]) {
+        constexpr int TAIL = decltype(tail)::value;
         // (no branch around a load: past the end the last tile is requested again -- behind a conditional load the compiler's
         // wait counts assume the worst path, i.e. they wait for everything in flight, which is what two steps ahead is there to avoid)
-        const bool more = k0 + kX3BK < K;
+        const bool more = TAIL == 1 || (TAIL == 0 && k0 + kX3BK < K);
         const int k_last = K - kX3BK;
-        fetch_b(k0 + kX3BK < k_last ? k0 + kX3BK : k_last);
-        fetch_a(nxt, k0 + 2 * kX3BK < k_last ? k0 + 2 * kX3BK : k_last);
+        if constexpr (TAIL == 0) {
+            fetch_b(k0 + kX3BK < k_last ? k0 + kX3BK : k_last);
+            fetch_a(nxt, k0 + 2 * kX3BK < k_last ? k0 + 2 * kX3BK : k_last);
+        } else if constexpr (TAIL == 1) {
+            fetch_b(k_last);
+            fetch_res(0, 0, VRA);
+        } else {
+            fetch_res(0, VRA, VPL);
+        }
         __builtin_amdgcn_sched_barrier(0);     // (the scheduler otherwise sinks the loads behind the MFMAs and lets fragments share their registers)
 #pragma unroll
         for (int kk = 0; kk < kX3BK; kk += 16) {
             bf16x8_t fa[3][2], fb[3][NT];
-            const int kof = (OPA_X3_DIAG == 4 ? 0 : kk) + (lane >> 5) * 8;
+            const int kh = OPA_X3_DIAG == 4 ? 0 : kk / 16;
+            const int kof = kh * 16 + (lane >> 5) * 8;
 #pragma unroll
             for (int pl = 0; pl < 3; pl++) {
 #pragma unroll
                 for (int i = 0; i < 2; i++)
-                    fa[pl][i] = *reinterpret_cast<const bf16x8_t*>(sA + pl * LDS_A + x3_lds(wm * 64 + i * 32 + (lane & 31), kof));
+                    fa[pl][i] = *reinterpret_cast<const bf16x8_t*>(TAIL_RES ? reinterpret_cast<const unsigned short*>(smem + frag_a[kh]) + (pl * LDS_A + i * 32 * kX3Pitch)
+                                                                       : sA + pl * LDS_A + x3_lds(wm * 64 + i * 32 + (lane & 31), kof));
 #pragma unroll
                 for (int j = 0; j < NT; j++)
-                    fb[pl][j] = *reinterpret_cast<const bf16x8_t*>(sB + pl * LDS_B + x3_lds(wn * WN + j * 32 + (lane & 31), kof));
+                    fb[pl][j] = *reinterpret_cast<const bf16x8_t*>(TAIL_RES ? reinterpret_cast<const unsigned short*>(smem + frag_b[kh]) + (3 * LDS_A + pl * LDS_B + j * 32 * kX3Pitch)
+                                                                       : sB + pl * LDS_B + x3_lds(wn * WN + j * 32 + (lane & 31), kof));
             }
             // consecutive MFMAs go to different accumulators (a dependent MFMA waits for its predecessor's passes)
 #pragma unroll
@@ -403,12 +461,26 @@ __global__ __launch_bounds__(256, OPA_X3_WGS) void gemm_f32x3_bias_act_kernel(
     };
     fetch_b(0);
     fetch_a(ra0, 0);
+    if constexpr (TAIL_RES) {
+        if (tid < BN) reinterpret_cast<float*>(smem + SMEM_BYTES)[tid] = bias[n0 + tid];
+    }
     store(ra0, 0);
     __syncthreads();
     fetch_a(ra1, kX3BK);                       // (K is a multiple of 2 BK: the launcher checks)
-    for (int k0 = 0; k0 < K; k0 += 2 * kX3BK) {
-        step(k0, ra1, ra0);
-        step(k0 + kX3BK, ra0, ra1);
+    constexpr std::integral_constant<int, 0> any_step{};
+    if constexpr (TAIL_RES) {
+        int k0 = 0;
+        for (; k0 < K - 2 * kX3BK; k0 += 2 * kX3BK) {
+            step(any_step, k0, ra1, ra0);
+            step(any_step, k0 + kX3BK, ra0, ra1);
+        }
+        step(std::integral_constant<int, 1>{}, k0, ra1, ra0);
+        step(std::integral_constant<int, 2>{}, k0 + kX3BK, ra0, ra1);
+    } else {
+        for (int k0 = 0; k0 < K; k0 += 2 * kX3BK) {
+            step(any_step, k0, ra1, ra0);
+            step(any_step, k0 + kX3BK, ra0, ra1);
+        }
     }
     // (the loop's last barrier: staging LDS is free, reuse it for the epilogue)
     if constexpr (UNIT) {
@@ -418,28 +490,19 @@ __global__ __launch_bounds__(256, OPA_X3_WGS) void gemm_f32x3_bias_act_kernel(
     }
 
     // epilogue, one 32-row block of the wave tile at a time through a wave-private f32 patch: the residual load and
-    // the output store are row-contiguous 16-B vectors
-    constexpr int VEC_PER_ROW = WN / 4;
-    constexpr int VPL = 32 * VEC_PER_ROW / 64;
+    // the output store are row-contiguous 16-B vectors.  The residual of block 0 has been on its way since the last two K-steps;
+    // block 1's is requested here, where fragments and staging registers are dead, and travels while block 0 is written out.
     float* patch = reinterpret_cast<float*>(smem) + wave * (32 * WN);
+    if constexpr (TAIL_RES) {
+        fetch_res(1, 0, VPL);
+        __builtin_amdgcn_sched_barrier(0);
+    }
 #pragma unroll
     for (int i = 0; i < 2; i++) {
-        constexpr int VPRE = VPL > 4 ? 4 : VPL; // residual vectors fetched ahead (16 registers); the rest in the loop
-        f32x4_t rv[VPRE];
-        if (RES) {                             // they travel while the patch is written
-#pragma unroll
-            for (int t = 0; t < VPRE; t++) {
-                const int v = t * 64 + lane;
-                const int row = v / VEC_PER_ROW, c4 = (v % VEC_PER_ROW) * 4;
-                const int m = m0 + wm * 64 + i * 32 + row;
-                rv[t] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-                if (m < M) rv[t] = *reinterpret_cast<const f32x4_t*>(res + (size_t)m * N + n0 + wn * WN + c4);
-            }
-        }
 #pragma unroll
         for (int j = 0; j < NT; j++) {
             const int col = j * 32 + (lane & 31);
-            const float b = bias[n0 + wn * WN + col];
+            const float b = TAIL_RES ? reinterpret_cast<const float*>(smem + SMEM_BYTES)[wn * WN + col] : bias[n0 + wn * WN + col];
 #pragma unroll
             for (int r = 0; r < 16; r++) {     // C layout: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
                 const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
@@ -455,10 +518,7 @@ __global__ __launch_bounds__(256, OPA_X3_WGS) void gemm_f32x3_bias_act_kernel(
             const int m = m0 + wm * 64 + i * 32 + row;
             if (m < M) {
                 f32x4_t f = *reinterpret_cast<const f32x4_t*>(patch + row * WN + c4);
-                if (RES) {
-                    if (t < VPRE) f += rv[t < VPRE ? t : 0];
-                    else f += *reinterpret_cast<const f32x4_t*>(res + (size_t)m * N + n0 + wn * WN + c4);
-                }
+                if constexpr (TAIL_RES) f += rres[i][t];
                 if (RELU) {
 #pragma unroll
                     for (int e = 0; e < 4; e++) f[e] = fmaxf(f[e], 0.0f);
@@ -468,7 +528,7 @@ __global__ __launch_bounds__(256, OPA_X3_WGS) void gemm_f32x3_bias_act_kernel(
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        asm volatile("" ::: "memory");         // (keeps the second block's residual loads behind this block)
+        asm volatile("" ::: "memory");
     }
 }
 
