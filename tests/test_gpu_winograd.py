@@ -1,6 +1,8 @@
 """csrc/winograd.hip on the GPU: F(2x2, 3x3) against a float64 convolution (tolerance: 2e-5 of the output's largest
-magnitude; torch's own float32 convolution is printed beside it by tools/gpu/winograd_probe.py), every variant / workgroup
-order, ragged sizes (odd H / W, a last tile block of one tile), bias + ReLU, and the ResNet trunk with and without it."""
+magnitude; torch's own float32 convolution is printed beside it by tools/gpu/winograd_probe.py) for variants 0-3 in both
+workgroup orders at seven shapes, bias + ReLU, and the ResNet trunk with and without it.  This max-norm sees an O(1) mistake only;
+the launch regimes (XCD remap, last tile block, image sizes, K-chunk counts, variant 3's walk) are reached and checked bit for bit
+by tests/test_gpu_winograd_regimes.py, which says which shape reaches which regime."""
 import pytest
 import torch
 
