@@ -603,6 +603,27 @@ int opa_dwconv_actp(const void* x_dev, int64_t x_pixel_stride, const void* w_dev
                     void* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w,
                     int32_t channels, int32_t k, int32_t stride, int32_t dilation, int32_t dtype, int32_t act, float act_param, void* stream);
 
+/* The RGB stem of the non-ResNet backbones (reference network/basenetworks.py: ShuffleNetV2K, ShuffleNetV2, MobileNetV2 / V3,
+ * SqueezeNet): a direct 3x3 convolution from 3 input channels, padding 1, dilation 1, stride 1 or 2, float32, with the folded bias
+ * and the activation applied before the single store (csrc/stem.hip):
+ *     out[b, oy, ox, co] = act(sum_t x[b, ci, oy*s - 1 + ky, ox*s - 1 + kx] * w[t][co] + bias[co]),   t = (ky*3 + kx)*3 + ci
+ *  x_dev   [batch, 3, h, w] given by four element strides (batch, channel, row, pixel), all positive: NCHW-contiguous,
+ *          channels-last (3 floats per pixel) or a cropped view of either; on a 4-byte boundary; read only, never copied;
+ *  w_dev   [27][channels_out] tap-major: row t = (ky*3 + kx)*3 + ci holds weight[co][ci][ky][kx] of the [channels_out, 3, 3, 3]
+ *          weight (openpifpaf_amd.fused.stem_weight_of);  bias_dev [channels_out] or NULL;  both and out_dev on 16 bytes;
+ *  out_dev dense channels-last [batch, ho, wo, channels_out], ho = (h - 1) / stride + 1 (likewise wo).
+ * channels_out 16, 24, 32, 42 or 64 (the stems the networks have).  act 0 none, 1 ReLU (x < 0 ? 0 : x), 2 hardswish, 3 LeakyReLU
+ * with the slope act_param (>= 0), 4 ReLU clipped at act_param (> 0; ReLU6 is 6); act_param finite whatever the code; a NaN stays
+ * a NaN under every code.  A padded tap contributes nothing: an Inf or NaN in x reaches the windows that hold it and no other.
+ * Each output is one chain of 27 float64 fma in the order of t, then + bias in float64, one rounding to float32, then act in
+ * float32, whatever the sizes: equal inputs give equal bits, and the sum is as good as correctly rounded.
+ * x must span fewer than 2^31 elements (first to last addressed) and out hold fewer than 2^31; batch <= 65535 (grid.y).  Anything
+ * else: OPA_ERR_INVALID_ARGUMENT before any launch.  batch == 0: OPA_OK, nothing runs. */
+int opa_stem3x3_actp(const float* x_dev, int64_t x_batch_stride, int64_t x_channel_stride, int64_t x_row_stride,
+                     int64_t x_pixel_stride, const float* w_dev, const float* bias_dev, float* out_dev,
+                     int32_t batch, int32_t h, int32_t w, int32_t channels_out, int32_t stride,
+                     int32_t act, float act_param, void* stream);
+
 /* Grouped 3x3 convolution, padding 1, dilation 1, stride 1 or 2, as many output as input channels, float32, channels innermost,
  * with the folded batch-norm bias and optionally ReLU (fmaxf) applied before the single store: the middle convolution of a
  * ResNeXt bottleneck (reference network/basenetworks.py:71-150 with torchvision's grouped Bottleneck).

@@ -13,7 +13,8 @@
 //   empty calls        m == 0 (opa_bias_act: rows == 0) is OPA_OK for the GEMMs; an empty batch, h or w is OPA_OK for
 //                      opa_conv3x3_dilated_f32x3, opa_maxpool3x3_bias_act, opa_maxpool3x3_ceil_bias_act, opa_fire_expand_f32x3 and
 //                      opa_gconv3x3_bias_act_f32, after every check that does not need a size (all but the first test their grid
-//                      only behind it).  opa_conv3x3_f32x3, opa_gemm2_*,
+//                      only behind it); an empty batch alone (h and w must be positive) for opa_stem3x3_actp, after every check
+//                      but those of the sizes' products.  opa_conv3x3_f32x3, opa_gemm2_*,
 //                      opa_conv_rows_*, Winograd, dwconv, squeeze-excite, interleave and the head epilogue refuse empties.
 //   last error         a call that succeeds leaves opa_last_error's text as it was.
 //   marks              the entry points that pass a kernel's name to Entry::launched mark the profile here; the launchers of the
@@ -380,6 +381,36 @@ int opa_gconv3x3_bias_act_f32(const float* x_dev, int64_t x_pixel_stride, const 
         return E.refuse("tiles * channel chunks of one image must not exceed 2^31 - 1 (grid.x)");
     return E.launched(launch_gconv3x3(x_dev, x_pixel_stride, wt_dev, bias_dev, out_dev, out_pixel_stride, batch, h, w, channels,
                                       group_width, stride, relu != 0, E.st), "grouped 3x3 convolution");
+}
+
+int opa_stem3x3_actp(const float* x_dev, int64_t x_batch_stride, int64_t x_channel_stride, int64_t x_row_stride,
+                     int64_t x_pixel_stride, const float* w_dev, const float* bias_dev, float* out_dev,
+                     int32_t batch, int32_t h, int32_t w, int32_t channels_out, int32_t stride,
+                     int32_t act, float act_param, void* stream) {
+    const Entry E("opa_stem3x3_actp", stream);
+    if (!x_dev || !w_dev || !out_dev) return E.refuse("x_dev, w_dev and out_dev must not be NULL");
+    if (misaligned(3, {x_dev}) || misaligned(15, {w_dev, bias_dev, out_dev}))
+        return E.refuse("x_dev must be 4-B, w_dev / bias_dev / out_dev 16-B aligned");
+    if (batch < 0 || h <= 0 || w <= 0) return E.refuse("batch must not be negative, h and w must be positive");
+    if (x_batch_stride <= 0 || x_channel_stride <= 0 || x_row_stride <= 0 || x_pixel_stride <= 0)
+        return E.refuse("the four strides of x must be positive");
+    if (stride != 1 && stride != 2) return E.refuse("stride must be 1 or 2");
+    if (!stem3x3_channels_ok(channels_out)) return E.refuse("channels_out must be 16, 24, 32, 42 or 64");
+    if (act < 0 || act > 4) return E.refuse("act must be 0 (none), 1 (ReLU), 2 (hardswish), 3 (LeakyReLU) or 4 (clipped ReLU)");
+    if (!std::isfinite(act_param)) return E.refuse("act_param must be finite");
+    if (act == 3 && act_param < 0.0f) return E.refuse("act_param must not be negative with act 3 (the LeakyReLU's slope)");
+    if (act == 4 && act_param <= 0.0f) return E.refuse("act_param must be positive with act 4 (the clipped ReLU's cap)");
+    if (batch == 0) return OPA_OK;
+    // 32-bit element indices in the kernel (in double: exact up to 2^53, and no product of these arguments overflows it); the
+    // stride of a dimension of one element addresses nothing
+    const double last = ((double)batch - 1.0) * (double)x_batch_stride + 2.0 * (double)x_channel_stride +
+                        ((double)h - 1.0) * (double)x_row_stride + ((double)w - 1.0) * (double)x_pixel_stride;
+    if (last >= 2147483648.0) return E.refuse("x must span fewer than 2^31 elements (32-bit indices)");
+    const double ho = (h - 1) / stride + 1, wo = (w - 1) / stride + 1;
+    if ((double)batch * ho * wo * channels_out >= 2147483648.0) return E.refuse("out must hold fewer than 2^31 elements (32-bit indices)");
+    if (batch > 65535) return E.refuse("batch must not exceed 65535 (grid.y)");
+    return E.launched(launch_stem3x3(x_dev, x_batch_stride, x_channel_stride, x_row_stride, x_pixel_stride, w_dev, bias_dev, out_dev, batch,
+                                     h, w, channels_out, stride, act, act_param, E.st), "stem3x3", "stem3x3_kernel");
 }
 
 static const char* se_check(int64_t x_pixel_stride, int32_t batch, int64_t pixels, int32_t channels) {

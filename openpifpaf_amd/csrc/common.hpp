@@ -276,6 +276,15 @@ int maxpool3x3_out(int h, int ceil_mode);
 long long maxpool3x3_blocks(int B, int H, int W, int C, int ceil_mode = 0);
 hipError_t launch_maxpool3x3(const void* x, const void* bias, void* out, int dtype, int B, int H, int W, int C, int relu, hipStream_t st,
                              int ceil_mode = 0);
+// The RGB stem of the non-ResNet backbones (stem.hip): out = act(conv3x3(x, padding 1, stride S) + bias), x [B, 3, H, W] float32 with
+// the element strides xb, xc, xr, xp (batch, channel, row, pixel), w [27][C] tap-major (t = (ky * 3 + kx) * 3 + ci), bias null or [C],
+// out dense channels-last [B, Ho, Wo, C]; C as stem3x3_channels_ok says, S 1 or 2, act 0 .. 4 with act_param (act_f32 below).  The
+// caller checks the sizes: the input's extent and the output's element count below 2^31 (32-bit indices), B <= 65535 (grid.y);
+// stem3x3_tiles = grid.x of the launch.
+bool stem3x3_channels_ok(int C);
+long long stem3x3_tiles(int H, int W, int S);
+hipError_t launch_stem3x3(const float* x, long long xb, long long xc, long long xr, long long xp, const float* w, const float* bias,
+                          float* out, int B, int H, int W, int C, int S, int act, float act_param, hipStream_t st);
 // Both expand convolutions of a SqueezeNet Fire module, bias, ReLU and the concatenation in one launch (fire.hip): h [B, H, W, S]
 // channels-last float32, w3 the fragment-ordered split weight block (openpifpaf_amd.fused.fire_weight_of), bias [E1 + E3],
 // out [B, H, W, E1 + E3].  S % 16 == 0, S <= 64, E1 % 64 == 0, E3 % 64 == 0; both tensors smaller than 2 GB (32-bit byte offsets);
@@ -362,6 +371,22 @@ __device__ __forceinline__ int lane_id() { return threadIdx.x & (kWave - 1); }
 // MobileNetV3's activations in float32 (torch.nn.Hardswish / Hardsigmoid): x * min(max(x + 3, 0), 6) / 6 and the factor alone
 __device__ __forceinline__ float hardsigmoid_f32(float x) { return fminf(fmaxf(x + 3.0f, 0.0f), 6.0f) / 6.0f; }
 __device__ __forceinline__ float hardswish_f32(float x) { return x * fminf(fmaxf(x + 3.0f, 0.0f), 6.0f) / 6.0f; }
+
+// The two activation codes with a parameter p (`act_param` of the C ABI), read at run time: `act` 3 LeakyReLU, x < 0 ? x * p : x
+// (MobileNetV2's ReLU6 is code 4, reference network/basenetworks.py:407-430; the LeakyReLU of a ShuffleNetV2K unit, :186-268), else
+// code 4, the ReLU clipped at p, x < 0 ? 0 : (x > p ? p : x) -- both selects, so that NaN stays NaN.
+__device__ __forceinline__ float x3_act_param(float x, int act, float p) {
+    if (act == 3) return x < 0.0f ? x * p : x;
+    return x < 0.0f ? 0.0f : (x > p ? p : x);
+}
+
+// Every activation code of the trunk's C ABI, read at run time: 0 none, 1 ReLU (a select: NaN stays), 2 hardswish, 3 and 4 as above
+__device__ __forceinline__ float act_f32(float x, int act, float p) {
+    if (act == 0) return x;
+    if (act == 1) return x < 0.0f ? 0.0f : x;
+    if (act == 2) return hardswish_f32(x);
+    return x3_act_param(x, act, p);
+}
 
 __device__ __forceinline__ long long clampll(long long v, long long lo, long long hi) {
     return v < lo ? lo : (v > hi ? hi : v);

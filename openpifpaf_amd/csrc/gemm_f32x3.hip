@@ -110,11 +110,8 @@ struct X3Second {
 // hardswish (RELU false); UX & 4 -- `partner` is a RESIDUAL [M, n; row pitch ldp]: out[M, n] = act(A * W^T + bias + residual), dense rows.
 // UX & 8 (MobileNetV2's ReLU6, reference network/basenetworks.py:407-430, and the LeakyReLU of a ShuffleNetV2K unit, :186-268; RELU
 // false, never with a residual): the activation is read at run time -- `act` 3: x < 0 ? x * p : x, 4: x < 0 ? 0 : (x > p ? p : x),
-// p = `act_param` -- both selects, so that NaN stays NaN; one pair of instantiations serves both, the epilogue is not where the time goes.
-__device__ __forceinline__ float x3_act_param(float x, int act, float p) {
-    if (act == 3) return x < 0.0f ? x * p : x;
-    return x < 0.0f ? 0.0f : (x > p ? p : x);
-}
+// p = `act_param` -- both selects, so that NaN stays NaN (x3_act_param of common.hpp, which csrc/stem.hip shares); one pair of
+// instantiations serves both, the epilogue is not where the time goes.
 
 template <int BN, bool PARTNER, bool RELU, int UX = 0>
 __device__ __forceinline__ void x3_unit_epilogue(float* smem_f, const f32x16_t (&acc)[2][BN / 64], const f32x16_t (&low)[2][BN / 64],

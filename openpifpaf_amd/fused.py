@@ -7,7 +7,7 @@ the choice is made once per shape and remembered in one table (``_CHOICE``, ship
 and ``pick`` say what the candidates are, ``_decide`` makes the choice.  In this order: the launcher, the switches, the choice
 table and the decision, the derived operands, then the routes by kernel family -- the epilogue passes, the 1x1 GEMMs, the
 split-operand convolutions (pair, 3x3 and dilated 3x3, stem, heads, unit mode), the Fire expand, the max-pools, the grouped and
-the depthwise stencils, squeeze-and-excitation."""
+the depthwise stencils, the RGB stem, squeeze-and-excitation."""
 import os
 
 import torch
@@ -18,7 +18,7 @@ from .native import _ptr, _stream
 _DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 ACT_NONE, ACT_RELU, ACT_HARDSWISH = 0, 1, 2      # the activation codes of opa_dwconv_act and opa_gemm_unit_act_f32x3
 # ... and the two with a parameter (``act_param``), which only opa_gemm_unit_actp_f32x3 and opa_dwconv_actp take: LeakyReLU(slope)
-# (the GEMM alone) and the ReLU clipped at a cap (ReLU6: 6)
+# (the GEMM alone) and the ReLU clipped at a cap (ReLU6: 6); opa_stem3x3_actp takes all five
 ACT_LEAKY_RELU, ACT_RELU6 = 3, 4
 
 
@@ -92,6 +92,12 @@ MBV2 = _switch('OPA_MBV2', '0')
 # The 1x1 convolutions of a LeakyReLU ShuffleNetV2K unit and a LeakyReLU conv5 through the unit-mode GEMM (the LeakyReLU in its
 # epilogue) instead of torch: OPA_UNIT_LEAKY=1 (or fused.UNIT_LEAKY = True).  Off by default, timed by the same tool into the same log.
 UNIT_LEAKY = _switch('OPA_UNIT_LEAKY', '0')
+# The RGB stem of ShuffleNetV2K, ShuffleNetV2, MobileNetV2, MobileNetV3 and SqueezeNet -- a 3x3 convolution from 3 channels, its folded
+# bias and its activation -- as one HIP kernel (csrc/stem.hip, network._stem_forward) instead of torch's convolution + activation:
+# OPA_STEM=1 (or fused.STEM = True).  Independent of MBV2 / MBV3 / FIRE / UNIT_LEAKY; never timed, no choice-table entry: where the
+# switch is on and ``stem_conv3x3_supported`` the kernel runs.  It ships OFF; the one timing is tools/gpu/stem_times.py,
+# profiles/stem/times.log, and switching the default is a change of its own that rests on it.
+STEM = _switch('OPA_STEM', '0')
 
 
 # ---- the choice table and the decision ---------------------------------------------------------------------------------------------
@@ -889,6 +895,69 @@ def dwconv_bias_act(x, w_taps, bias, kernel_size, stride, relu=False, act=None, 
     else:
         _launch('opa_dwconv_dilated_act', _ptr(x), _pixel_stride(x), _ptr(w_taps), _ptr(bias), _ptr(out), C, B, H, W, C, kernel_size,
                 stride, dilation, _DTYPES[x.dtype], _act_code(relu, act))
+    return out
+
+
+# ---- the RGB stem -----------------------------------------------------------------------------------------------------------------------
+
+STEM_CHANNELS = (16, 24, 32, 42, 64)         # output channels the kernel is instantiated for: the stems the networks have
+# output channel counts the kernel can run but that came out NO FASTER than torch's convolution + activation of the same layer
+# (tools/gpu/stem_times.py, profiles/stem/times.log): ``stem_conv3x3_supported`` declines them.
+STEM_DECLINED = frozenset()
+
+
+def stem_weight_of(conv):
+    """The weight operand of ``stem_conv3x3_bias_act`` derived from the CURRENT ``conv.weight`` (``[C, 3, 3, 3]``): ``[27, C]`` float32,
+    tap-major with the output channel innermost, ``w[(ky * 3 + kx) * 3 + ci][co] = weight[co][ci][ky][kx]``.  Derived and cached
+    (``derived``): no buffer, no part of a state dict, computed again whenever the weight was replaced, moved or changed in place."""
+    def make():
+        w = conv.weight.detach().to(torch.float32)
+        return w.permute(2, 3, 1, 0).reshape(27, w.shape[0]).contiguous()
+    return derived(conv, '_opa_stem3x3_w', (conv.weight,), make)
+
+
+def stem_conv_out_hw(h, w, stride):
+    """Output rows and columns of the 3x3 stem (padding 1) for an ``h`` x ``w`` input."""
+    return (h - 1) // stride + 1, (w - 1) // stride + 1
+
+
+def stem_conv3x3_supported(conv, x):
+    """Can ``stem_conv3x3_bias_act(conv, x)`` run?  ``x``: a float32 ``[B, 3, H, W]`` tensor on the GPU in ANY layout with positive
+    strides (NCHW, channels-last, a cropped view), outside autocast, nothing that autograd follows; ``conv``: a 3x3 convolution of
+    stride 1 or 2, padding 1, no dilation, no groups, float32 weights on ``x``'s device, ``STEM_CHANNELS`` output channels (but
+    ``STEM_DECLINED``), a float32 bias or none; sizes that ``opa_stem3x3_actp`` takes (32-bit indices, the batch in grid.y)."""
+    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.shape[1] == 3 and not torch.is_autocast_enabled()):
+        return False
+    if x.requires_grad or (torch.is_grad_enabled() and any(p.requires_grad for p in conv.parameters())):
+        return False
+    if not (isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (3, 3) and conv.stride in ((1, 1), (2, 2)) and conv.padding == (1, 1)
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == 'zeros' and conv.in_channels == 3
+            and conv.out_channels in STEM_CHANNELS and conv.out_channels not in STEM_DECLINED
+            and conv.weight.dtype == torch.float32 and conv.weight.device == x.device):
+        return False
+    bias = conv.bias
+    if bias is not None and not (bias.dtype == torch.float32 and bias.device == x.device and bias.is_contiguous()
+                                 and bias.data_ptr() % 16 == 0):
+        return False
+    B, _, H, W = x.shape
+    ho, wo = stem_conv_out_hw(H, W, conv.stride[0])
+    last = sum((n - 1) * s for n, s in zip(x.shape, x.stride()))                 # the last element addressed
+    return (min(x.shape) > 0 and min(x.stride()) > 0 and x.data_ptr() % 4 == 0 and last < 2 ** 31
+            and B * ho * wo * conv.out_channels < 2 ** 31 and B <= 65535 and _lib.available())
+
+
+def stem_conv3x3_bias_act(conv, x, act=ACT_NONE, act_param=0.0):
+    """``act(conv(x))`` for the 3x3 RGB stem of a ShuffleNetV2K, ShuffleNetV2, MobileNetV2, MobileNetV3 or SqueezeNet (folded with its
+    batch norm: the bias is ``conv.bias``, or none) in one HIP kernel (``opa_stem3x3_actp``, ``csrc/stem.hip``): ``x`` is read through
+    its own four strides, whatever its layout -- no copy --, the result is a dense channels-last float32 tensor.  ``act``:
+    ``ACT_NONE`` / ``ACT_RELU`` / ``ACT_HARDSWISH`` / ``ACT_LEAKY_RELU`` / ``ACT_RELU6``, the last two with ``act_param`` (the slope / the
+    cap).  ``stem_conv3x3_supported`` says whether this can run."""
+    w = stem_weight_of(conv)
+    B, _, H, W = x.shape
+    s = conv.stride[0]
+    out = _empty_nhwc(x, conv.out_channels, stem_conv_out_hw(H, W, s), torch.float32)
+    _launch('opa_stem3x3_actp', _ptr(x), x.stride(0), x.stride(1), x.stride(2), x.stride(3), _ptr(w), _ptr(conv.bias), _ptr(out),
+            B, H, W, conv.out_channels, s, int(act), float(act_param))
     return out
 
 

@@ -379,6 +379,33 @@ class Resnet(BaseNetwork):
         return x if self.block5 is None else self.block5(x)
 
 
+def _stem_act(nonlin):
+    """The activation code and parameter of ``fused.stem_conv3x3_bias_act`` for a stem's non-linearity, or None."""
+    kind = type(nonlin)
+    if kind is nn.ReLU:
+        return fused.ACT_RELU, 0.0
+    if kind is nn.Hardswish:
+        return fused.ACT_HARDSWISH, 0.0
+    if kind is nn.LeakyReLU:
+        return fused.ACT_LEAKY_RELU, nonlin.negative_slope
+    if kind is nn.ReLU6:
+        return fused.ACT_RELU6, 6.0
+    return None
+
+
+def _stem_route(net, conv, nonlin, x):
+    """``nonlin(conv(x))`` for the 3x3 RGB stem of an optimized ShuffleNetV2K, ShuffleNetV2, MobileNetV2, MobileNetV3 or SqueezeNet (``conv``
+    folded with its batch norm: the bias is ``conv.bias``) in one HIP kernel, or None where the route is not taken: ``fused.STEM`` off
+    (the default), a network that is not optimized, or a call ``fused.stem_conv3x3_supported`` declines (bfloat16, autocast, the CPU).
+    One route for the five families, independent of their own switches; ``x`` in any layout, the result channels-last."""
+    if not (net.fused and fused.STEM and x.is_cuda and isinstance(conv, nn.Conv2d)):
+        return None
+    act = _stem_act(nonlin)
+    if act is None or not fused.stem_conv3x3_supported(conv, x):
+        return None
+    return fused.stem_conv3x3_bias_act(conv, x, act=act[0], act_param=act[1])
+
+
 def _channel_shuffle(x, groups=2):
     b, c, h, w = x.shape
     return x.view(b, groups, c // groups, h, w).transpose(1, 2).reshape(b, c, h, w)
@@ -594,8 +621,18 @@ class ShuffleNetV2K(BaseNetwork):
             flag = 'shufflenetv2k_' + ('kernel' if option == 'kernel_width' else option)
             setattr(cls, option, getattr(args, flag, getattr(cls, option)))
 
+    def _input_block_forward(self, x):
+        """``input_block(x)``, the stem through ``_stem_route`` where that takes it (the second input convolution stays with torch)."""
+        modules = list(self.input_block)
+        y = _stem_route(self, modules[0], modules[2], x)
+        if y is None:
+            return self.input_block(x)
+        for m in modules[3:]:
+            y = m(y)
+        return y
+
     def forward(self, x):
-        return _conv5_forward(self, self.stage4(self.stage3(self.stage2(self.input_block(x)))))
+        return _conv5_forward(self, self.stage4(self.stage3(self.stage2(self._input_block_forward(x)))))
 
 
 def _conv5_forward(net, x):
@@ -644,7 +681,8 @@ class ShuffleNetV2(BaseNetwork):
         self.conv5 = nn.Sequential(nn.Conv2d(inp, ch[-1], 1, bias=False), nn.BatchNorm2d(ch[-1]), nn.ReLU(inplace=True))
 
     def forward(self, x):
-        return _conv5_forward(self, self.stage4(self.stage3(self.stage2(self.conv1(x)))))
+        y = _stem_route(self, self.conv1[0], self.conv1[2], x)
+        return _conv5_forward(self, self.stage4(self.stage3(self.stage2(self.conv1(x) if y is None else y))))
 
 
 def _make_divisible(v, divisor=8):
@@ -772,13 +810,16 @@ class _MobileNet(BaseNetwork):
 
     def enable_fused_(self):
         """The last 1x1 convolution may run through the split-operand GEMM's unit mode (bias + activation inside); the stem stays
-        with ``torch.nn.Conv2d`` like every non-ResNet stem.  No parameter or buffer changes."""
+        with ``torch.nn.Conv2d`` like every non-ResNet stem unless ``fused.STEM`` is on (``_stem_route``).  No parameter or buffer
+        changes."""
         _assert_folded(self)
         super().enable_fused_()
 
     def forward(self, x):
-        *front, last = self.backbone
-        for m in front:
+        stem, *blocks, last = self.backbone
+        y = _stem_route(self, stem[0], stem[2], x)
+        x = stem(x) if y is None else y
+        for m in blocks:
             x = m(x)
         conv = last[0]
         if (self.fused and getattr(fused, self._switch) and x.is_cuda and not torch.is_autocast_enabled() and conv.bias is not None
@@ -944,19 +985,24 @@ class SqueezeNet(BaseNetwork):
                 and pool.ceil_mode and not pool.return_indices and fused.maxpool3x3_supported(x))
 
     def forward(self, x):
-        """Fused: the max-pools through the ceil-mode entry point of ``csrc/pool.hip`` (the first with the stem's ReLU inside); the stem
-        stays with ``torch.nn.Conv2d`` like MobileNetV3's and ShuffleNetV2K's."""
-        if not (self.fused and fused.FIRE and x.is_cuda and not torch.is_autocast_enabled()):
-            return self.backbone(x)
+        """Fused (``fused.FIRE``): the max-pools through the ceil-mode entry point of ``csrc/pool.hip`` (the first with the stem's ReLU
+        inside); the stem stays with ``torch.nn.Conv2d`` like MobileNetV3's and ShuffleNetV2K's unless ``fused.STEM`` is on -- then it
+        is ``_stem_route``'s with the ReLU applied there, once, and the first max-pool runs without it."""
         modules = list(self.backbone)
         i = 0
+        y = _stem_route(self, modules[0], modules[1], x)
+        if y is not None:
+            x, i = y, 2
+        pools = self.fused and fused.FIRE and x.is_cuda and not torch.is_autocast_enabled()
+        if not pools and i == 0:
+            return self.backbone(x)
         while i < len(modules):
             m = modules[i]
-            if isinstance(m, nn.ReLU) and i + 1 < len(modules) and self._pool_route_supported(modules[i + 1], x):
+            if pools and isinstance(m, nn.ReLU) and i + 1 < len(modules) and self._pool_route_supported(modules[i + 1], x):
                 x = fused.maxpool3x3_bias_act_(x, relu=True, ceil_mode=True)        # the stem's ReLU goes into the pool (max and ReLU commute)
                 i += 2
                 continue
-            x = fused.maxpool3x3_bias_act_(x, ceil_mode=True) if self._pool_route_supported(m, x) else m(x)
+            x = fused.maxpool3x3_bias_act_(x, ceil_mode=True) if pools and self._pool_route_supported(m, x) else m(x)
             i += 1
         return x
 
@@ -1103,7 +1149,8 @@ def optimize_for_inference_(model):
     * the MobileNetV3 blocks and last convolution to the same GEMM, the depthwise stencil and the squeeze-and-excitation kernels
       (behind ``fused.MBV3``);
     * the MobileNetV2 blocks and last convolution to that GEMM and that stencil with ReLU6 (behind ``fused.MBV2``);
-    * the SqueezeNet Fire modules and max-pools to that GEMM, the Fire expand kernel and the ceil-mode pool (behind ``fused.FIRE``)."""
+    * the SqueezeNet Fire modules and max-pools to that GEMM, the Fire expand kernel and the ceil-mode pool (behind ``fused.FIRE``);
+    * the 3x3 RGB stem of these five families to the stem kernel with the bias and the activation inside (behind ``fused.STEM``)."""
     fuse_conv_bn_(model)
     for m in model.modules():
         if isinstance(m, (_Bottleneck, _BasicBlock, _InvertedResidualK, _InvertedResidual, _Fire, BaseNetwork)):
