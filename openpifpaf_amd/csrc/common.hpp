@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <type_traits>
 
 #include "../../include/openpifpaf_amd.h"
 
@@ -256,6 +257,18 @@ hipError_t launch_cifdet_nms(const DetNmsArgs& a, hipStream_t st);
 
 hipError_t launch_bias_act(void* x, const void* bias, const void* res, long long rows, int channels, int dtype,
                            int relu, hipStream_t st);
+
+// A run-time value as a compile-time constant, for a launcher that picks a kernel template's instantiation: f is called with the
+// std::integral_constant of the listed value that equals v, e.g. with_value<64, 128>(bn, [&](auto BN) { ... kernel<BN> ... });
+// a value that is not listed calls nothing: hipErrorInvalidValue.  with_flag: a bool.
+template <auto... Vs, typename T, typename F>
+hipError_t with_value(T v, F&& f) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)((v == Vs && (e = f(std::integral_constant<decltype(Vs), Vs>{}), true)) || ...);
+    return e;
+}
+template <typename F>
+hipError_t with_flag(bool v, F&& f) { return with_value<false, true>(v, f); }
 
 hipError_t launch_gemm_bias_act(const void* A, const void* W, const void* bias, const void* res, void* out,
                                 int M, int N, int K, int relu, hipStream_t st, const void* a_bias = nullptr);

@@ -191,32 +191,20 @@ __global__ __launch_bounds__(256, 3) void gemm_bias_act_kernel(
     }
 }
 
-template <int BN, bool PRO>
-static hipError_t launch_bn(const void* A, const void* W, const void* bias, const void* res, void* out,
-                            int M, int N, int K, int relu, const void* a_bias, hipStream_t st) {
-    const long long blocks = (long long)((M + kGemmBM - 1) / kGemmBM) * (N / BN);
-    const unsigned short *a = (const unsigned short*)A, *w = (const unsigned short*)W,
-                         *b = (const unsigned short*)bias, *r = (const unsigned short*)res,
-                         *ab = (const unsigned short*)a_bias;
-    unsigned short* o = (unsigned short*)out;
-    if (res) {
-        if (relu) gemm_bias_act_kernel<BN, true, true, PRO><<<(unsigned)blocks, 256, 0, st>>>(a, w, b, r, o, M, N, K, ab);
-        else gemm_bias_act_kernel<BN, true, false, PRO><<<(unsigned)blocks, 256, 0, st>>>(a, w, b, r, o, M, N, K, ab);
-    } else {
-        if (relu) gemm_bias_act_kernel<BN, false, true, PRO><<<(unsigned)blocks, 256, 0, st>>>(a, w, b, r, o, M, N, K, ab);
-        else gemm_bias_act_kernel<BN, false, false, PRO><<<(unsigned)blocks, 256, 0, st>>>(a, w, b, r, o, M, N, K, ab);
-    }
-    return hipGetLastError();
-}
-
 hipError_t launch_gemm_bias_act(const void* A, const void* W, const void* bias, const void* res, void* out,
                                 int M, int N, int K, int relu, hipStream_t st, const void* a_bias) {
-    if (a_bias) {
-        if (N % 128 == 0) return launch_bn<128, true>(A, W, bias, res, out, M, N, K, relu, a_bias, st);
-        return launch_bn<64, true>(A, W, bias, res, out, M, N, K, relu, a_bias, st);
-    }
-    if (N % 128 == 0) return launch_bn<128, false>(A, W, bias, res, out, M, N, K, relu, nullptr, st);
-    return launch_bn<64, false>(A, W, bias, res, out, M, N, K, relu, nullptr, st);
+    const unsigned short *a = (const unsigned short*)A, *w = (const unsigned short*)W, *b = (const unsigned short*)bias,
+                         *r = (const unsigned short*)res, *ab = (const unsigned short*)a_bias;
+    unsigned short* o = (unsigned short*)out;
+    const int bn = N % 128 == 0 ? 128 : 64;
+    const long long blocks = (long long)((M + kGemmBM - 1) / kGemmBM) * (N / bn);
+    return with_value<64, 128>(bn, [&](auto BN) {
+    return with_flag(res != nullptr, [&](auto RES) {
+    return with_flag(relu != 0, [&](auto RELU) {
+    return with_flag(a_bias != nullptr, [&](auto PRO) {
+        gemm_bias_act_kernel<BN, RES, RELU, PRO><<<(unsigned)blocks, 256, 0, st>>>(a, w, b, r, o, M, N, K, ab);
+        return hipGetLastError();
+    }); }); }); });
 }
 
 }  // namespace opa

@@ -220,28 +220,17 @@ __global__ __launch_bounds__(256, BN == 128 ? OPA_F32_WGS : 3) void gemm_f32_bia
     }
 }
 
-template <int BN, bool PRO>
-static hipError_t launch_f32_bn(const float* a, const float* w, const float* b, const float* r, float* o,
-                                int M, int N, int K, int relu, const float* ab, hipStream_t st) {
-    const long long blocks = (long long)((M + kF32BM - 1) / kF32BM) * (N / BN);
-    if (r) {
-        if (relu) gemm_f32_bias_act_kernel<BN, true, true, PRO><<<(unsigned)blocks, 256, 0, st>>>(a, w, b, r, o, M, N, K, ab);
-        else gemm_f32_bias_act_kernel<BN, true, false, PRO><<<(unsigned)blocks, 256, 0, st>>>(a, w, b, r, o, M, N, K, ab);
-    } else {
-        if (relu) gemm_f32_bias_act_kernel<BN, false, true, PRO><<<(unsigned)blocks, 256, 0, st>>>(a, w, b, r, o, M, N, K, ab);
-        else gemm_f32_bias_act_kernel<BN, false, false, PRO><<<(unsigned)blocks, 256, 0, st>>>(a, w, b, r, o, M, N, K, ab);
-    }
-    return hipGetLastError();
-}
-
 hipError_t launch_gemm_f32_bias_act(const float* A, const float* W, const float* bias, const float* res, float* out,
                                     int M, int N, int K, int relu, hipStream_t st, const float* a_bias) {
-    if (a_bias) {
-        if (N % 128 == 0) return launch_f32_bn<128, true>(A, W, bias, res, out, M, N, K, relu, a_bias, st);
-        return launch_f32_bn<64, true>(A, W, bias, res, out, M, N, K, relu, a_bias, st);
-    }
-    if (N % 128 == 0) return launch_f32_bn<128, false>(A, W, bias, res, out, M, N, K, relu, nullptr, st);
-    return launch_f32_bn<64, false>(A, W, bias, res, out, M, N, K, relu, nullptr, st);
+    const int bn = N % 128 == 0 ? 128 : 64;
+    const long long blocks = (long long)((M + kF32BM - 1) / kF32BM) * (N / bn);
+    return with_value<64, 128>(bn, [&](auto BN) {
+    return with_flag(res != nullptr, [&](auto RES) {
+    return with_flag(relu != 0, [&](auto RELU) {
+    return with_flag(a_bias != nullptr, [&](auto PRO) {
+        gemm_f32_bias_act_kernel<BN, RES, RELU, PRO><<<(unsigned)blocks, 256, 0, st>>>(A, W, bias, res, out, M, N, K, a_bias);
+        return hipGetLastError();
+    }); }); }); });
 }
 
 }  // namespace opa

@@ -83,16 +83,17 @@ __device__ __forceinline__ int x3_lds(int row, int k) {
 // t = 3 ky + kx of K holds the C channels of input pixel (stride * oy - 1 + ky, stride * ox - 1 + kx); a pixel in the padding is
 // requested beyond the end of the buffer, which a buffer load answers with zeros (one bit per row and tap decides).  With a
 // dilation d (padding d) the pixel is (stride * oy - d + d ky, stride * ox - d + d kx): the same three expressions times d.
+// The defaults are what a mode that does not read a field passes: a launcher sets the fields of its own mode, nothing else.
 struct X3Second {
-    const float* A2;           // [B, hi, wi, K - K1] channels-last, or null
-    int K1;                    // columns of the first activation (a multiple of the K-step)
-    int ho_wo, wo, hi_wi, wi, stride;
-    int hi, C, batch;          // (SRC = 2) input rows, floats per tap (a multiple of the K-step), images
-    int pix, taps_x, ntaps, padded;   // (SRC = 2) floats per input pixel; taps per window row; taps; 1: the input is padded in
+    const float* A2 = nullptr; // (SRC = 1) [B, hi, wi, K - K1] channels-last
+    int K1 = 0;                // (SRC = 1) columns of the first activation (a multiple of the K-step)
+    int ho_wo = 1, wo = 1, hi_wi = 1, wi = 1, stride = 1;        // (SRC = 1, 2) output pixels per image and row, input ones, the stride
+    int hi = 1, C = 0, batch = 1;     // (SRC = 2) input rows, floats per tap (a multiple of the K-step), images
+    int pix = 1, taps_x = 1, ntaps = 1, padded = 0;   // (SRC = 2) floats per input pixel; taps per window row; taps; 1: the input is padded in
                                // memory (window origin = (stride oy, stride ox), every tap valid), 0: padding `dil` by the tap mask
-    int dil;                   // (SRC = 2, not padded) dilation d: tap (ky, kx) reads input pixel (stride oy - d + d ky, stride ox - d + d kx)
-    int lda, ldp, n_real, k_real;     // (UNIT) floats between rows of A and of the partner; the columns that exist of N and K
-    int act; float act_param;        // (UNIT, UX & 8) the activation read at run time: 3 LeakyReLU(slope), 4 clipped ReLU(cap)
+    int dil = 1;               // (SRC = 2, not padded) dilation d: tap (ky, kx) reads input pixel (stride oy - d + d ky, stride ox - d + d kx)
+    int lda = 0, ldp = 0, n_real = 0, k_real = 0;     // (UNIT) floats between rows of A and of the partner; the columns that exist of N and K
+    int act = 0; float act_param = 0.0f;     // (UNIT, kUxActParam) the activation read at run time: 3 LeakyReLU(slope), 4 clipped ReLU(cap)
 };
 
 // UNIT: the 1x1 convolutions of a ShuffleNetV2K unit (reference network/basenetworks.py:186-242) -- ANY even K and N, A a channel
@@ -106,12 +107,14 @@ struct X3Second {
 // behind the LAST row is never fetched (the buffer's range ends with that row's column k_real).  A slice starts on an 8-byte
 // boundary only (k16 stage 2: 174 floats into a pixel) and so does every row of the output (n_real even): the operand is staged
 // with 8-byte loads, the epilogue works in column pairs -- a pair lies inside k_real / n_real or outside, never across.
-// UX (MobileNetV3's blocks, reference network/basenetworks.py:432-446; 0 for everything above): UX & 3 == 2 -- the activation is
-// hardswish (RELU false); UX & 4 -- `partner` is a RESIDUAL [M, n; row pitch ldp]: out[M, n] = act(A * W^T + bias + residual), dense rows.
-// UX & 8 (MobileNetV2's ReLU6, reference network/basenetworks.py:407-430, and the LeakyReLU of a ShuffleNetV2K unit, :186-268; RELU
+// UX (MobileNetV3's blocks, reference network/basenetworks.py:432-446; 0 for everything above): (UX & kUxAct) == kUxHardswish -- the
+// activation is hardswish (RELU false); UX & kUxResidual -- `partner` is a RESIDUAL [M, n; row pitch ldp]:
+// out[M, n] = act(A * W^T + bias + residual), dense rows.
+// UX & kUxActParam (MobileNetV2's ReLU6, reference network/basenetworks.py:407-430, and the LeakyReLU of a ShuffleNetV2K unit, :186-268; RELU
 // false, never with a residual): the activation is read at run time -- `act` 3: x < 0 ? x * p : x, 4: x < 0 ? 0 : (x > p ? p : x),
 // p = `act_param` -- both selects, so that NaN stays NaN (x3_act_param of common.hpp, which csrc/stem.hip shares); one pair of
 // instantiations serves both, the epilogue is not where the time goes.
+constexpr int kUxAct = 3, kUxHardswish = 2, kUxResidual = 4, kUxActParam = 8;      // (the values are part of the kernels' names)
 
 template <int BN, bool PARTNER, bool RELU, int UX = 0>
 __device__ __forceinline__ void x3_unit_epilogue(float* smem_f, const f32x16_t (&acc)[2][BN / 64], const f32x16_t (&low)[2][BN / 64],
@@ -156,16 +159,16 @@ __device__ __forceinline__ void x3_unit_epilogue(float* smem_f, const f32x16_t (
             const int m = m0 + wm * 64 + i * 32 + row;
             if (m < M && col < n_real) {       // (n_real is even: the pair is inside or outside)
                 f32x2_t f = *reinterpret_cast<const f32x2_t*>(patch + row * WN + c2);
-                if constexpr (PARTNER && (UX & 4) != 0) {
+                if constexpr (PARTNER && (UX & kUxResidual) != 0) {
                     f32x2_t pp;
                     if (t < PPRE) pp = pv[t < PPRE ? t : 0];
                     else pp = *reinterpret_cast<const f32x2_t*>(partner + (size_t)m * ldp + col);
                     f[0] += pp[0]; f[1] += pp[1];
                 }
                 if (RELU) { f[0] = fmaxf(f[0], 0.0f); f[1] = fmaxf(f[1], 0.0f); }
-                if constexpr ((UX & 3) == 2) { f[0] = hardswish_f32(f[0]); f[1] = hardswish_f32(f[1]); }
-                if constexpr ((UX & 8) != 0) { f[0] = x3_act_param(f[0], act, act_param); f[1] = x3_act_param(f[1], act, act_param); }
-                if (PARTNER && (UX & 4) == 0) { // the partner's bits pass through untouched
+                if constexpr ((UX & kUxAct) == kUxHardswish) { f[0] = hardswish_f32(f[0]); f[1] = hardswish_f32(f[1]); }
+                if constexpr ((UX & kUxActParam) != 0) { f[0] = x3_act_param(f[0], act, act_param); f[1] = x3_act_param(f[1], act, act_param); }
+                if (PARTNER && (UX & kUxResidual) == 0) { // the partner's bits pass through untouched
                     f32x2_t pp;
                     if (t < PPRE) pp = pv[t < PPRE ? t : 0];
                     else pp = *reinterpret_cast<const f32x2_t*>(partner + (size_t)m * ldp + col);
@@ -529,45 +532,47 @@ __global__ __launch_bounds__(256, OPA_X3_WGS) void gemm_f32x3_bias_act_kernel(
     }
 }
 
-template <int BN, bool PRO, int TERMS>
-static hipError_t launch_x3_bn(const float* a, const unsigned short* w, const float* b, const float* r, float* o,
-                               int M, int N, int K, int relu, const float* ab, hipStream_t st, const X3Second& sec) {
-    const long long blocks = (long long)((M + kX3BM - 1) / kX3BM) * (N / BN);
-    if (sec.C > 0) {                           // 3x3 implicit GEMM: no operand prologue, no residual
-        if constexpr (!PRO) {
-            if (relu) gemm_f32x3_bias_act_kernel<BN, false, true, false, TERMS, 2><<<(unsigned)blocks, 256, 0, st>>>(a, w, b, nullptr, o, M, N, K, nullptr, sec);
-            else gemm_f32x3_bias_act_kernel<BN, false, false, false, TERMS, 2><<<(unsigned)blocks, 256, 0, st>>>(a, w, b, nullptr, o, M, N, K, nullptr, sec);
-        }
-    } else if (sec.A2) {                       // (the pair has no residual: the second activation IS the identity branch)
-        if (relu) gemm_f32x3_bias_act_kernel<BN, false, true, PRO, TERMS, 1><<<(unsigned)blocks, 256, 0, st>>>(a, w, b, nullptr, o, M, N, K, ab, sec);
-        else gemm_f32x3_bias_act_kernel<BN, false, false, PRO, TERMS, 1><<<(unsigned)blocks, 256, 0, st>>>(a, w, b, nullptr, o, M, N, K, ab, sec);
-    } else if (r) {
-        if (relu) gemm_f32x3_bias_act_kernel<BN, true, true, PRO, TERMS, 0><<<(unsigned)blocks, 256, 0, st>>>(a, w, b, r, o, M, N, K, ab, sec);
-        else gemm_f32x3_bias_act_kernel<BN, true, false, PRO, TERMS, 0><<<(unsigned)blocks, 256, 0, st>>>(a, w, b, r, o, M, N, K, ab, sec);
-    } else {
-        if (relu) gemm_f32x3_bias_act_kernel<BN, false, true, PRO, TERMS, 0><<<(unsigned)blocks, 256, 0, st>>>(a, w, b, r, o, M, N, K, ab, sec);
-        else gemm_f32x3_bias_act_kernel<BN, false, false, PRO, TERMS, 0><<<(unsigned)blocks, 256, 0, st>>>(a, w, b, r, o, M, N, K, ab, sec);
-    }
-    return hipGetLastError();
+enum X3Mode { kX3Plain = 0, kX3Pair = 1, kX3Taps = 2, kX3Unit = 3 };      // SRC 0, 1, 2; UNIT (whose SRC is 0)
+
+// The instantiations that exist, 89: launch_x3 launches these and refuses everything else.
+// Not UNIT, 56: BN x TERMS x RELU, x PRO except with taps (no operand prologue there), x RES with one activation alone (the pair's
+// second activation IS the identity branch).  UNIT, 11 for each (BN, TERMS) but (128, 9), which does not fit the register file: one
+// activation, no prologue, RES = a third operand; five epilogues, RELU only where UX names no activation, a residual only as RES.
+constexpr bool x3_exists(int BN, bool RES, bool RELU, bool PRO, int TERMS, int SRC, bool UNIT, int UX) {
+    if (!UNIT) return UX == 0 && !(SRC != 0 && RES) && !(SRC == 2 && PRO);
+    if (SRC != 0 || PRO || (BN == 128 && TERMS == 9)) return false;
+    const bool known = UX == 0 || UX == kUxHardswish || UX == kUxResidual || UX == (kUxResidual | kUxHardswish) || UX == kUxActParam;
+    return known && !(RELU && (UX & ~kUxResidual) != 0) && !((UX & kUxResidual) != 0 && !RES);
 }
 
-template <int TERMS>
-static hipError_t launch_x3_terms(const float* A, const unsigned short* W3, const float* bias, const float* res, float* out,
-                                  int M, int N, int K, int relu, hipStream_t st, const float* a_bias, const X3Second& sec) {
-    if (a_bias) {
-        if (N % 128 == 0) return launch_x3_bn<128, true, TERMS>(A, W3, bias, res, out, M, N, K, relu, a_bias, st, sec);
-        return launch_x3_bn<64, true, TERMS>(A, W3, bias, res, out, M, N, K, relu, a_bias, st, sec);
-    }
-    if (N % 128 == 0) return launch_x3_bn<128, false, TERMS>(A, W3, bias, res, out, M, N, K, relu, nullptr, st, sec);
-    return launch_x3_bn<64, false, TERMS>(A, W3, bias, res, out, M, N, K, relu, nullptr, st, sec);
+// Every launch of this file.  N and K are the kernel's (UNIT: the padded sizes), `third` the residual, or UNIT's partner or residual.
+static hipError_t launch_x3(X3Mode mode, const float* A, const unsigned short* W3, const float* bias, const float* third, float* out,
+                            int M, int N, int K, bool relu, int ux, int terms, const float* a_bias, hipStream_t st, const X3Second& sec) {
+    // (the 128-wide tile with nine terms does not fit the register file -- its instantiations spill 8 registers -- so the unit mode has none)
+    const int bn = mode != kX3Unit ? (N % 128 == 0 ? 128 : 64)
+                                   : (N % 128 == 0 && terms == 6 ? 128 : 64);
+    const unsigned blocks = (unsigned)((long long)((M + kX3BM - 1) / kX3BM) * (N / bn));
+    return with_value<64, 128>(bn, [&](auto BN) {
+    return with_value<6, 9>(terms == 6 ? 6 : 9, [&](auto TERMS) {
+    return with_value<kX3Plain, kX3Pair, kX3Taps, kX3Unit>(mode, [&](auto MODE) {
+    return with_value<0, kUxHardswish, kUxResidual, kUxResidual | kUxHardswish, kUxActParam>(ux, [&](auto UX) {
+    return with_flag(third != nullptr, [&](auto RES) {
+    return with_flag(relu, [&](auto RELU) {
+    return with_flag(a_bias != nullptr, [&](auto PRO) {
+        constexpr bool UNIT = MODE == kX3Unit;
+        constexpr int SRC = UNIT ? 0 : (int)MODE;
+        if constexpr (x3_exists(BN, RES, RELU, PRO, TERMS, SRC, UNIT, UX)) {
+            gemm_f32x3_bias_act_kernel<BN, RES, RELU, PRO, TERMS, SRC, UNIT, UX><<<blocks, 256, 0, st>>>(A, W3, bias, third, out, M, N, K, a_bias, sec);
+            return hipGetLastError();
+        } else {
+            return hipErrorInvalidValue;
+        }
+    }); }); }); }); }); }); });
 }
 
 hipError_t launch_gemm_f32x3_bias_act(const float* A, const unsigned short* W3, const float* bias, const float* res, float* out,
                                       int M, int N, int K, int relu, int terms, hipStream_t st, const float* a_bias) {
-    X3Second none; none.A2 = nullptr; none.K1 = K; none.ho_wo = none.wo = none.hi_wi = none.wi = none.stride = 1; none.hi = 1; none.C = 0; none.batch = 1;
-    none.pix = 1; none.taps_x = 1; none.ntaps = 1; none.padded = 0; none.dil = 1; none.lda = none.ldp = none.n_real = none.k_real = 0; none.act = 0; none.act_param = 0.0f;
-    if (terms == 6) return launch_x3_terms<6>(A, W3, bias, res, out, M, N, K, relu, st, a_bias, none);
-    return launch_x3_terms<9>(A, W3, bias, res, out, M, N, K, relu, st, a_bias, none);
+    return launch_x3(kX3Plain, A, W3, bias, res, out, M, N, K, relu != 0, 0, terms, a_bias, st, X3Second{});
 }
 
 // out[B, ho, wo, N] = act([A1 | pixels of A2 at stride s] * W3cat^T + bias): A1 [B*ho*wo, K1], A2 [B, hi, wi, K2], W3cat [3][N][K1 + K2]
@@ -575,91 +580,25 @@ hipError_t launch_gemm2_f32x3_bias_act(const float* A1, int K1, const float* A2,
                                        const unsigned short* W3, const float* bias, float* out, int N, int relu, int terms,
                                        hipStream_t st, const float* a_bias) {
     const int ho = (hi - 1) / stride + 1, wo = (wi - 1) / stride + 1;
-    X3Second sec; sec.A2 = A2; sec.K1 = K1; sec.ho_wo = ho * wo; sec.wo = wo; sec.hi_wi = hi * wi; sec.wi = wi; sec.stride = stride;
-    sec.hi = hi; sec.C = 0; sec.batch = batch; sec.pix = 1; sec.taps_x = 1; sec.ntaps = 1; sec.padded = 0; sec.dil = 1; sec.lda = sec.ldp = sec.n_real = sec.k_real = 0; sec.act = 0; sec.act_param = 0.0f;
-    const int M = batch * ho * wo, K = K1 + K2;
-    if (terms == 6) return launch_x3_terms<6>(A1, W3, bias, nullptr, out, M, N, K, relu, st, a_bias, sec);
-    return launch_x3_terms<9>(A1, W3, bias, nullptr, out, M, N, K, relu, st, a_bias, sec);
-}
-
-template <int BN, int TERMS>
-static hipError_t launch_unit_bn(const float* a, const unsigned short* w, const float* b, const float* partner, float* o,
-                                 int M, int Np, int Kp, int relu, hipStream_t st, const X3Second& sec) {
-    const unsigned blocks = (unsigned)((long long)((M + kX3BM - 1) / kX3BM) * (Np / BN));
-    if (partner) {
-        if (relu) gemm_f32x3_bias_act_kernel<BN, true, true, false, TERMS, 0, true><<<blocks, 256, 0, st>>>(a, w, b, partner, o, M, Np, Kp, nullptr, sec);
-        else gemm_f32x3_bias_act_kernel<BN, true, false, false, TERMS, 0, true><<<blocks, 256, 0, st>>>(a, w, b, partner, o, M, Np, Kp, nullptr, sec);
-    } else {
-        if (relu) gemm_f32x3_bias_act_kernel<BN, false, true, false, TERMS, 0, true><<<blocks, 256, 0, st>>>(a, w, b, nullptr, o, M, Np, Kp, nullptr, sec);
-        else gemm_f32x3_bias_act_kernel<BN, false, false, false, TERMS, 0, true><<<blocks, 256, 0, st>>>(a, w, b, nullptr, o, M, Np, Kp, nullptr, sec);
-    }
-    return hipGetLastError();
+    X3Second sec;
+    sec.A2 = A2; sec.K1 = K1;
+    sec.ho_wo = ho * wo; sec.wo = wo; sec.hi_wi = hi * wi; sec.wi = wi; sec.stride = stride;
+    return launch_x3(kX3Pair, A1, W3, bias, nullptr, out, batch * ho * wo, N, K1 + K2, relu != 0, 0, terms, a_bias, st, sec);
 }
 
 // The UNIT mode: A [M, K] with `lda` floats between rows, W3 [3][Np][Kp] and bias [Np] padded with zeros (Np, Kp: N, K rounded up
-// to multiples of 64), partner [M, N] with `ldp` floats between rows or null; out [M, N] dense, or [M, 2N] with a partner.  The tile
-// is 128 wide where Np is a multiple of 128, like launch_gemm_f32x3_bias_act chooses it for N -- with six terms: the 128-wide
-// tile with nine terms does not fit the register file (the existing instantiations spill 8 registers), so nine terms take 64.
-static X3Second unit_sec(int lda, int ldp, int N, int K) {
-    X3Second sec; sec.A2 = nullptr; sec.K1 = K; sec.ho_wo = sec.wo = sec.hi_wi = sec.wi = sec.stride = 1; sec.hi = 1; sec.C = 0; sec.batch = 1;
-    sec.pix = 1; sec.taps_x = 1; sec.ntaps = 1; sec.padded = 0; sec.dil = 1; sec.lda = lda; sec.ldp = ldp; sec.n_real = N; sec.k_real = K;
-    sec.act = 0; sec.act_param = 0.0f;
-    return sec;
-}
-
-// f.template operator()<BN, TERMS>(Np, Kp) with the unit mode's tile width and term count for these sizes
-template <typename F>
-static hipError_t unit_dispatch(int N, int K, int terms, F f) {
-    const int Np = (N + 63) / 64 * 64, Kp = (K + 63) / 64 * 64;
-    if (Np % 128 == 0 && terms == 6) return f.template operator()<128, 6>(Np, Kp);
-    if (terms == 6) return f.template operator()<64, 6>(Np, Kp);
-    return f.template operator()<64, 9>(Np, Kp);
-}
-
-struct UnitLaunch {
-    const float* a; const unsigned short* w; const float* b; const float* third; bool residual; float* o;
-    int M, act; hipStream_t st; X3Second sec;
-    template <int BN, int TERMS> hipError_t operator()(int Np, int Kp) const;
-};
-
-// The unit mode's instantiations with hardswish, a residual or a run-time activation (see x3_unit_epilogue's UX; act 3 / 4 are read
-// from `sec`); `third` is the partner or the residual.
-template <int BN, int TERMS>
-static hipError_t launch_unit_act_bn(const float* a, const unsigned short* w, const float* b, const float* third, bool residual, float* o,
-                                     int M, int Np, int Kp, int act, hipStream_t st, const X3Second& sec) {
-    const unsigned blocks = (unsigned)((long long)((M + kX3BM - 1) / kX3BM) * (Np / BN));
-#define OPA_UNIT_ACT(RES_, RELU_, UX_) gemm_f32x3_bias_act_kernel<BN, RES_, RELU_, false, TERMS, 0, true, UX_><<<blocks, 256, 0, st>>>(a, w, b, third, o, M, Np, Kp, nullptr, sec)
-    if (act == 3 || act == 4) {
-        if (residual) return hipErrorInvalidValue;
-        if (third) OPA_UNIT_ACT(true, false, 8);
-        else OPA_UNIT_ACT(false, false, 8);
-    } else if (residual) {
-        if (act == 2) OPA_UNIT_ACT(true, false, 6);
-        else if (act == 1) OPA_UNIT_ACT(true, true, 4);
-        else OPA_UNIT_ACT(true, false, 4);
-    } else if (third) {
-        OPA_UNIT_ACT(true, false, 2);
-    } else {
-        OPA_UNIT_ACT(false, false, 2);
-    }
-#undef OPA_UNIT_ACT
-    return hipGetLastError();
-}
-
+// to multiples of 64), partner or residual [M, N] with `ldp` / `ldr` floats between rows or null; out [M, N] dense, or [M, 2N] with
+// a partner.  act 3 / 4 are read from `sec` at run time; with a residual they have no instantiation.
 hipError_t launch_gemm_unit_act_f32x3(const float* A, int lda, const unsigned short* W3, const float* bias, const float* partner, int ldp,
                                       const float* residual, int ldr, float* out, int M, int N, int K, int act, int terms, hipStream_t st,
                                       float act_param) {
-    if (partner && residual) return hipErrorInvalidValue;
-    X3Second sec = unit_sec(lda, residual ? ldr : ldp, N, K);
-    if (act == 3 || act == 4) { sec.act = act; sec.act_param = act_param; }
-    return unit_dispatch(N, K, terms, UnitLaunch{A, W3, bias, residual ? residual : partner, residual != nullptr, out, M, act, st, sec});
-}
-
-// act 0 / 1 without a residual: the instantiations the ShuffleNetV2K units use (launch_unit_bn)
-template <int BN, int TERMS>
-hipError_t UnitLaunch::operator()(int Np, int Kp) const {
-    if (!residual && (act == 0 || act == 1)) return launch_unit_bn<BN, TERMS>(a, w, b, third, o, M, Np, Kp, act, st, sec);
-    return launch_unit_act_bn<BN, TERMS>(a, w, b, third, residual, o, M, Np, Kp, act, st, sec);
+    if ((partner && residual) || act < 0 || act > 4) return hipErrorInvalidValue;
+    X3Second sec;
+    sec.lda = lda; sec.ldp = residual ? ldr : ldp; sec.n_real = N; sec.k_real = K;
+    if (act >= 3) { sec.act = act; sec.act_param = act_param; }
+    const int ux = (act == 2 ? kUxHardswish : 0) | (act >= 3 ? kUxActParam : 0) | (residual ? kUxResidual : 0);
+    const int Np = (N + 63) / 64 * 64, Kp = (K + 63) / 64 * 64;
+    return launch_x3(kX3Unit, A, W3, bias, residual ? residual : partner, out, M, Np, Kp, act == 1, ux, terms, nullptr, st, sec);
 }
 
 // 3x3 convolution, dilation d, padding d, stride s: out[B, ho, wo, N] = act(im2col(x) * W3^T + bias), x [B, hi, wi, C] channels-last,
@@ -667,11 +606,11 @@ hipError_t UnitLaunch::operator()(int Np, int Kp) const {
 hipError_t launch_conv3x3_f32x3(const float* x, int batch, int hi, int wi, int C, int stride, int dilation, const unsigned short* W3,
                                 const float* bias, float* out, int N, int relu, int terms, hipStream_t st) {
     const int ho = (hi - 1) / stride + 1, wo = (wi - 1) / stride + 1;
-    X3Second sec; sec.A2 = nullptr; sec.K1 = C; sec.ho_wo = ho * wo; sec.wo = wo; sec.hi_wi = hi * wi; sec.wi = wi; sec.stride = stride;
-    sec.hi = hi; sec.C = C; sec.batch = batch; sec.pix = C; sec.taps_x = 3; sec.ntaps = 9; sec.padded = 0; sec.dil = dilation; sec.lda = sec.ldp = sec.n_real = sec.k_real = 0; sec.act = 0; sec.act_param = 0.0f;
-    const int M = batch * ho * wo, K = 9 * C;
-    if (terms == 6) return launch_x3_terms<6>(x, W3, bias, nullptr, out, M, N, K, relu, st, nullptr, sec);
-    return launch_x3_terms<9>(x, W3, bias, nullptr, out, M, N, K, relu, st, nullptr, sec);
+    X3Second sec;
+    sec.ho_wo = ho * wo; sec.wo = wo; sec.hi_wi = hi * wi; sec.wi = wi; sec.stride = stride;
+    sec.hi = hi; sec.C = C; sec.batch = batch;
+    sec.pix = C; sec.taps_x = 3; sec.ntaps = 9; sec.dil = dilation;
+    return launch_x3(kX3Taps, x, W3, bias, nullptr, out, batch * ho * wo, N, 9 * C, relu != 0, 0, terms, nullptr, st, sec);
 }
 
 // A convolution whose window ROWS are the taps: x [B, hp, wp, pix] is padded in memory (pix floats per pixel), output pixel
@@ -680,11 +619,11 @@ hipError_t launch_conv3x3_f32x3(const float* x, int batch, int hi, int wi, int C
 // fourth channel meet zero weights).  W3 [3][N][ntaps * tap_floats].  out [B, ho, wo, N].
 hipError_t launch_convrows_f32x3(const float* x, int batch, int hp, int wp, int pix, int ho, int wo, int stride, int ntaps, int tap_floats,
                                  const unsigned short* W3, const float* bias, float* out, int N, int relu, int terms, hipStream_t st) {
-    X3Second sec; sec.A2 = nullptr; sec.K1 = tap_floats; sec.ho_wo = ho * wo; sec.wo = wo; sec.hi_wi = hp * wp; sec.wi = wp; sec.stride = stride;
-    sec.hi = hp; sec.C = tap_floats; sec.batch = batch; sec.pix = pix; sec.taps_x = 1; sec.ntaps = ntaps; sec.padded = 1; sec.dil = 1; sec.lda = sec.ldp = sec.n_real = sec.k_real = 0; sec.act = 0; sec.act_param = 0.0f;
-    const int M = batch * ho * wo, K = ntaps * tap_floats;
-    if (terms == 6) return launch_x3_terms<6>(x, W3, bias, nullptr, out, M, N, K, relu, st, nullptr, sec);
-    return launch_x3_terms<9>(x, W3, bias, nullptr, out, M, N, K, relu, st, nullptr, sec);
+    X3Second sec;
+    sec.ho_wo = ho * wo; sec.wo = wo; sec.hi_wi = hp * wp; sec.wi = wp; sec.stride = stride;
+    sec.hi = hp; sec.C = tap_floats; sec.batch = batch;
+    sec.pix = pix; sec.taps_x = 1; sec.ntaps = ntaps; sec.padded = 1;
+    return launch_x3(kX3Taps, x, W3, bias, nullptr, out, batch * ho * wo, N, ntaps * tap_floats, relu != 0, 0, terms, nullptr, st, sec);
 }
 
 }  // namespace opa
