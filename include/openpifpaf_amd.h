@@ -666,6 +666,34 @@ int opa_se_gate(const void* workspace_dev, size_t workspace_bytes, int32_t batch
 int opa_se_scale(float* x_dev, int64_t x_pixel_stride, int32_t batch, int64_t pixels, int32_t channels, const float* gate_dev,
                  void* stream);
 
+/* Group norm and the activation behind it, for a ShuffleNetV2K built with --shufflenetv2k-group-norm (reference
+ * network/basenetworks.py:376-400: torch.nn.GroupNorm in place of every BatchNorm2d; csrc/groupnorm.hip):
+ *     out[b, p, c] = act((x[b, p, c] - mean[b, g]) * rstd[b, g] * gamma[c] + beta[c]),   g = c / (channels / groups),
+ * mean and the biased variance over the (channels / groups) x pixels elements of group g of image b, rstd = 1 / sqrt(var + eps).
+ *  x_dev    float32 channels-innermost [batch, pixels, *] with x_pixel_stride floats between pixels (a channel slice of a wider
+ *           tensor is fine), on an 8-byte boundary;  out_dev likewise with out_pixel_stride.  out_dev == x_dev with equal strides
+ *           works in place; any other overlap of the two is undefined (out_dev == x_dev with unequal strides is refused);
+ *  gamma_dev, beta_dev  [channels] float32, or NULL (each on its own): 1 and 0;
+ *  workspace_dev  opa_groupnorm_workspace_bytes(batch, pixels, channels) bytes on a 16-byte boundary: the partial moments
+ *           [batch][ceil(pixels / OPA_GN_CHUNK_PIXELS)][channels] (sum, sum of squares) in float64, then (a, s) [batch][channels].
+ * Three launches on the stream: the moments of every chunk of OPA_GN_CHUNK_PIXELS pixels per channel in float64; per (image,
+ * group) the chunks added in their order, then the group's channels in their order, mean = sum / n, var = max(sumsq / n - mean^2, 0),
+ * rstd = 1 / sqrt(var + (double)eps) in float64 and, rounded to float32 once each, a = gamma * rstd and s = beta - mean * a;
+ * out = act(fmaf(x, a, s)) in float32.  The order of every addition depends on the shape alone (no atomics): equal inputs give
+ * equal bits.  act and act_param as opa_stem3x3_actp.
+ * The checks, in this order, each with its own message: x_dev / out_dev NULL; alignment (x_dev / out_dev 8, gamma_dev / beta_dev 4,
+ * workspace_dev 16 bytes); batch < 0 or pixels, channels, groups <= 0; channels % groups; an odd channels / groups; pixel strides odd
+ * or below channels; eps not finite or negative; act outside 0 .. 4; act_param not finite, negative with act 3, not positive with
+ * act 4; out_dev == x_dev with unequal strides -- then batch == 0: OPA_OK, nothing runs -- then batch > 65535; pixels > 65535 *
+ * OPA_GN_CHUNK_PIXELS; channels / groups > 2048; pixels * channels / 2 >= 2^31; workspace_dev NULL, workspace_bytes too small (both
+ * OPA_ERR_WORKSPACE; every other refusal is OPA_ERR_INVALID_ARGUMENT).  Nothing is launched by a refused call.
+ * opa_groupnorm_workspace_bytes is 0 for a non-positive argument. */
+#define OPA_GN_CHUNK_PIXELS 512
+size_t opa_groupnorm_workspace_bytes(int32_t batch, int64_t pixels, int32_t channels);
+int opa_groupnorm_actp(const float* x_dev, int64_t x_pixel_stride, const float* gamma_dev, const float* beta_dev, float* out_dev,
+                       int64_t out_pixel_stride, int32_t batch, int64_t pixels, int32_t channels, int32_t groups, float eps,
+                       int32_t act, float act_param, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* The head of the field-producing network after its 1x1 convolution, in one pass (ref: network/heads.py:330-378
  * CompositeField4.forward): PixelShuffle(upsample) -> crop -> [B, n_fields, n_components, H, W] float32 -> sigmoid on
  * the n_confidences components after component 0, cell-index offsets on the vector components whose bit is set in

@@ -179,6 +179,9 @@ SYMBOLS = {
     'opa_se_pool': (ctypes.c_int, [_vp, _i64, _i32, _i64, _i32, _vp, _sz, _vp]),
     'opa_se_gate': (ctypes.c_int, [_vp, _sz, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'opa_se_scale': (ctypes.c_int, [_vp, _i64, _i32, _i64, _i32, _vp, _vp]),
+    'opa_groupnorm_workspace_bytes': (_sz, [_i32, _i64, _i32]),
+    'opa_groupnorm_actp': (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, ctypes.c_float, _i32, ctypes.c_float, _vp, _sz,
+                                          _vp]),
     'opa_channel_interleave': (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp]),
     'opa_head_epilogue': (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _i32, _vp, _vp]),
     'opa_pre_image_bytes': (_sz, []),

@@ -14,11 +14,12 @@
 //                      opa_conv3x3_dilated_f32x3, opa_maxpool3x3_bias_act, opa_maxpool3x3_ceil_bias_act, opa_fire_expand_f32x3 and
 //                      opa_gconv3x3_bias_act_f32, after every check that does not need a size (all but the first test their grid
 //                      only behind it); an empty batch alone (h and w must be positive) for opa_stem3x3_actp, after every check
-//                      but those of the sizes' products.  opa_conv3x3_f32x3, opa_gemm2_*,
+//                      but those of the sizes' products, and for opa_groupnorm_actp (pixels, channels and groups must be positive),
+//                      after every check of its arguments but the limits and the workspace.  opa_conv3x3_f32x3, opa_gemm2_*,
 //                      opa_conv_rows_*, Winograd, dwconv, squeeze-excite, interleave and the head epilogue refuse empties.
 //   last error         a call that succeeds leaves opa_last_error's text as it was.
 //   marks              the entry points that pass a kernel's name to Entry::launched mark the profile here; the launchers of the
-//                      others (dwconv, gconv, se, interleave, head epilogue, preprocessing) mark it themselves.
+//                      others (dwconv, gconv, se, group norm, interleave, head epilogue, preprocessing) mark it themselves.
 //   Winograd variants  opa_conv3x3_winograd_f32 lets the variants 11-18 past its checks and ..._f32x3 21-23 (timing experiments of
 //                      OPA_WINO_DIAG builds); the production launcher answers hipErrorInvalidValue before it touches the device:
 //                      OPA_ERR_HIP, "winograd_f23: invalid argument".
@@ -455,6 +456,44 @@ int opa_se_scale(float* x_dev, int64_t x_pixel_stride, int32_t batch, int64_t pi
     if (const char* why = se_check(x_pixel_stride, batch, pixels, channels)) return E.refuse(why);
     if (misaligned(15, {x_dev, gate_dev})) return E.refuse("pointers must be 16-B aligned");
     return E.launched(launch_se_scale(x_dev, x_pixel_stride, batch, pixels, channels, gate_dev, E.st), "se scale");
+}
+
+size_t opa_groupnorm_workspace_bytes(int32_t batch, int64_t pixels, int32_t channels) {
+    if (batch <= 0 || pixels <= 0 || channels <= 0) return 0;
+    return groupnorm_partial_bytes(batch, pixels, channels) + (size_t)batch * (size_t)channels * 2 * sizeof(float);
+}
+
+int opa_groupnorm_actp(const float* x_dev, int64_t x_pixel_stride, const float* gamma_dev, const float* beta_dev, float* out_dev,
+                       int64_t out_pixel_stride, int32_t batch, int64_t pixels, int32_t channels, int32_t groups, float eps,
+                       int32_t act, float act_param, void* workspace_dev, size_t workspace_bytes, void* stream) {
+    const Entry E("opa_groupnorm_actp", stream);
+    if (!x_dev || !out_dev) return E.refuse("x_dev and out_dev must not be NULL");
+    if (misaligned(7, {x_dev, out_dev}) || misaligned(3, {gamma_dev, beta_dev}) || misaligned(15, {workspace_dev}))
+        return E.refuse("x_dev / out_dev must be 8-B, gamma_dev / beta_dev 4-B, workspace_dev 16-B aligned");
+    if (batch < 0 || pixels <= 0 || channels <= 0 || groups <= 0)
+        return E.refuse("batch must not be negative, pixels, channels and groups must be positive");
+    if (channels % groups != 0) return E.refuse("channels must be a multiple of groups");
+    if ((channels / groups) % 2 != 0) return E.refuse("channels / groups must be even");
+    if (x_pixel_stride % 2 != 0 || out_pixel_stride % 2 != 0 || x_pixel_stride < channels || out_pixel_stride < channels)
+        return E.refuse("pixel strides must be even and at least channels");
+    if (!std::isfinite(eps) || eps < 0.0f) return E.refuse("eps must be finite and not negative");
+    if (act < 0 || act > 4) return E.refuse("act must be 0 (none), 1 (ReLU), 2 (hardswish), 3 (LeakyReLU) or 4 (clipped ReLU)");
+    if (!std::isfinite(act_param)) return E.refuse("act_param must be finite");
+    if (act == 3 && act_param < 0.0f) return E.refuse("act_param must not be negative with act 3 (the LeakyReLU's slope)");
+    if (act == 4 && act_param <= 0.0f) return E.refuse("act_param must be positive with act 4 (the clipped ReLU's cap)");
+    if (out_dev == x_dev && out_pixel_stride != x_pixel_stride) return E.refuse("out_dev == x_dev (in place) needs equal pixel strides");
+    if (batch == 0) return OPA_OK;
+    // the grids and the indices first: behind them the workspace's size is a product that fits
+    if (batch > 65535) return E.refuse("batch must not exceed 65535 (grid.y)");
+    if (pixels > 65535ll * kGnChunkPixels) return E.refuse("pixels must not exceed 65535 * OPA_GN_CHUNK_PIXELS (grid.y)");
+    if (channels / groups > kGnMaxGroupWidth) return E.refuse("channels / groups must not exceed 2048");
+    // (in double: exact up to 2^53, and no product of these arguments overflows it)
+    if ((double)pixels * (double)(channels / 2) >= 2147483648.0)
+        return E.refuse("pixels * channels / 2 must stay below 2^31 (32-bit vector indices within an image)");
+    if (!workspace_dev) return E.refuse(OPA_ERR_WORKSPACE, "workspace_dev must not be NULL");
+    if (workspace_bytes < opa_groupnorm_workspace_bytes(batch, pixels, channels)) return E.refuse(OPA_ERR_WORKSPACE, "the workspace is too small");
+    return E.launched(launch_groupnorm(x_dev, x_pixel_stride, gamma_dev, beta_dev, out_dev, out_pixel_stride, batch, pixels, channels, groups,
+                                       eps, act, act_param, workspace_dev, E.st), "group norm");
 }
 
 int opa_channel_interleave(const void* a_dev, int64_t a_pixel_stride, const void* b_dev, int64_t b_pixel_stride,

@@ -340,6 +340,18 @@ hipError_t launch_se_gate(const double* partial, int B, long long HW, int C, int
                           const float* w2, const float* b2, float* gate, float* mean_out, hipStream_t st);
 hipError_t launch_se_scale(float* x, long long xs, int B, long long HW, int C, const float* gate, hipStream_t st);
 
+// Group norm + activation (groupnorm.hip) of a channels-last float32 tensor or channel slice [B, HW, C] with pixel stride xs into
+// out with pixel stride os (out == x with os == xs: in place): moments (partial sums and sums of squares [B][gn_chunks(HW)][C] in
+// float64), coefficients ((a, s) [B][C] in float32 behind them: `workspace` holds groupnorm_partial_bytes + B * C * 8 bytes),
+// apply (out = act(fmaf(x, a, s))).  gamma / beta [C] or null; C, C / G, xs, os even; act 0 .. 4 with act_param (act_f32 below).
+// The caller checks the sizes: B <= 65535, HW <= 65535 * kGnChunkPixels, C / G <= kGnMaxGroupWidth, HW * C / 2 < 2^31.
+constexpr int kGnChunkPixels = 512;       // OPA_GN_CHUNK_PIXELS: pixels of one partial sum
+constexpr int kGnMaxGroupWidth = 2048;    // channels of one group, at most (32 KB of LDS in the coefficients kernel)
+inline long long gn_chunks(long long hw) { return (hw + kGnChunkPixels - 1) / kGnChunkPixels; }
+size_t groupnorm_partial_bytes(int B, long long HW, int C);
+hipError_t launch_groupnorm(const float* x, long long xs, const float* gamma, const float* beta, float* out, long long os, int B,
+                            long long HW, int C, int G, float eps, int act, float act_param, void* workspace, hipStream_t st);
+
 hipError_t launch_head_epilogue(const void* conv, int dtype, int B, int Hc, int Wc, int n_fields, int n_comp, int us,
                                 int n_conf, int n_vec, unsigned offset_mask, int n_scales, float* out, hipStream_t st);
 

@@ -7,7 +7,7 @@ the choice is made once per shape and remembered in one table (``_CHOICE``, ship
 and ``pick`` say what the candidates are, ``_decide`` makes the choice.  In this order: the launcher, the switches, the choice
 table and the decision, the derived operands, then the routes by kernel family -- the epilogue passes, the 1x1 GEMMs, the
 split-operand convolutions (pair, 3x3 and dilated 3x3, stem, heads, unit mode), the Fire expand, the max-pools, the grouped and
-the depthwise stencils, the RGB stem, squeeze-and-excitation."""
+the depthwise stencils, the RGB stem, group norm, squeeze-and-excitation."""
 import os
 
 import torch
@@ -98,6 +98,12 @@ UNIT_LEAKY = _switch('OPA_UNIT_LEAKY', '0')
 # switch is on and ``stem_conv3x3_supported`` the kernel runs.  It ships OFF; the one timing is tools/gpu/stem_times.py,
 # profiles/stem/times.log, and switching the default is a change of its own that rests on it.
 STEM = _switch('OPA_STEM', '0')
+# The group norms of a ShuffleNetV2K built with ``layer_norm='group'`` -- each with the ReLU or LeakyReLU behind it -- as three HIP
+# kernels in place on the producer's output (csrc/groupnorm.hip, network._norm_act), the convolutions between them through the unit-mode
+# GEMM, the depthwise stencil and (with STEM) the stem kernel without an activation: OPA_GN=1 (or fused.GN = True).  Never timed, no
+# choice-table entry: where the switch is on and ``group_norm_supported`` the kernels run, else torch's ``GroupNorm``.  It ships OFF;
+# the one timing is tools/gpu/shufflenetv2k_norm_times.py, profiles/shufflenetv2k_norms/times.log.
+GN = _switch('OPA_GN', '0')
 
 
 # ---- the choice table and the decision ---------------------------------------------------------------------------------------------
@@ -958,6 +964,69 @@ def stem_conv3x3_bias_act(conv, x, act=ACT_NONE, act_param=0.0):
     out = _empty_nhwc(x, conv.out_channels, stem_conv_out_hw(H, W, s), torch.float32)
     _launch('opa_stem3x3_actp', _ptr(x), x.stride(0), x.stride(1), x.stride(2), x.stride(3), _ptr(w), _ptr(conv.bias), _ptr(out),
             B, H, W, conv.out_channels, s, int(act), float(act_param))
+    return out
+
+
+# ---- group norm ---------------------------------------------------------------------------------------------------------------------------
+
+GN_CHUNK_PIXELS = 512                    # OPA_GN_CHUNK_PIXELS: pixels of one partial sum
+GN_MAX_PIXELS = 65535 * GN_CHUNK_PIXELS  # grid.y of the moments kernel
+GN_MAX_GROUP_WIDTH = 2048                # channels of one group (the coefficients kernel's LDS)
+_GN_WORKSPACE = {}                       # (device, stream handle) -> the float64 tensor that holds the moments and the coefficients
+
+
+def group_norm_supported(norm, x):
+    """Can ``group_norm_act(norm, x)`` run?  ``norm``: a ``torch.nn.GroupNorm`` of ``x``'s channels with an EVEN number of channels per
+    group, float32 affine terms on ``x``'s device or none; ``x``: float32 on the GPU, channels innermost -- a channels-last tensor or a
+    channel slice of one -- with an even pitch between pixels, on an 8-byte boundary, outside autocast, nothing that autograd follows;
+    sizes ``opa_groupnorm_actp`` takes; a library that has the entry point."""
+    if not (isinstance(norm, torch.nn.GroupNorm) and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32
+            and not torch.is_autocast_enabled()):
+        return False
+    if x.requires_grad or (torch.is_grad_enabled() and any(p.requires_grad for p in norm.parameters())):
+        return False
+    B, C, H, W = x.shape
+    G = norm.num_groups
+    ps = _pixel_stride(x)
+    if not (ps is not None and ps % 2 == 0 and x.data_ptr() % 8 == 0 and C == norm.num_channels and C % G == 0 and (C // G) % 2 == 0):
+        return False
+    for t in (norm.weight, norm.bias):
+        if t is not None and not (t.dtype == torch.float32 and t.device == x.device and t.is_contiguous() and t.numel() == C):
+            return False
+    if not (0 < B <= 65535 and 0 < H * W <= GN_MAX_PIXELS and C // G <= GN_MAX_GROUP_WIDTH and H * W * (C // 2) < 2 ** 31
+            and 0.0 <= norm.eps < float('inf')):
+        return False
+    return _lib.available() and hasattr(_lib.lib(), 'opa_groupnorm_actp')
+
+
+def _gn_workspace(x, nbytes):
+    """The workspace of ``group_norm_act``: one float64 tensor per device and stream, kept between calls and replaced by a larger one
+    when a call needs more (the calls of a stream run in order, so they can share it; torch's allocator keeps a replaced tensor's
+    memory until the stream has passed its last use).  Nothing is kept of a call inside a stream capture: that memory is the graph's."""
+    key = (str(x.device), _stream())
+    ws = _GN_WORKSPACE.get(key)
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
+        if not (x.device.type == 'cuda' and torch.cuda.is_current_stream_capturing()):
+            _GN_WORKSPACE[key] = ws
+    return ws
+
+
+def group_norm_act(norm, x, act=ACT_NONE, act_param=0.0, out=None):
+    """``act(norm(x))`` for a ``torch.nn.GroupNorm`` (reference ``network/basenetworks.py:398-400``: the norms of a ShuffleNetV2K built
+    with ``--shufflenetv2k-group-norm``) and the activation behind it, three launches of ``csrc/groupnorm.hip`` through
+    ``opa_groupnorm_actp``: the moments of every 512 pixels per channel in float64, the coefficients per (image, channel), then
+    ``act(fmaf(x, a, s))``.  ``x``: channels-last float32 or a channel slice; ``out``: a tensor of ``x``'s shape, channels innermost
+    (``x`` itself: in place), default a new dense channels-last one; returned.  ``act``: ``ACT_NONE`` / ``ACT_RELU`` / ``ACT_HARDSWISH`` /
+    ``ACT_LEAKY_RELU`` / ``ACT_RELU6``, the last two with ``act_param``.  The order of every addition depends on the shape alone.
+    ``group_norm_supported`` says whether this can run."""
+    B, C, H, W = x.shape
+    if out is None:
+        out = _empty_nhwc(x, C, dtype=torch.float32)
+    nbytes = _lib.lib().opa_groupnorm_workspace_bytes(B, H * W, C)
+    ws = _gn_workspace(x, nbytes)
+    _launch('opa_groupnorm_actp', _ptr(x), _pixel_stride(x), _ptr(norm.weight), _ptr(norm.bias), _ptr(out), _pixel_stride(out), B, H * W, C,
+            norm.num_groups, float(norm.eps), int(act), float(act_param), _ptr(ws), ws.numel() * 8)
     return out
 
 

@@ -393,17 +393,49 @@ def _stem_act(nonlin):
     return None
 
 
-def _stem_route(net, conv, nonlin, x):
+def _stem_route(net, conv, nonlin, x, norm=None):
     """``nonlin(conv(x))`` for the 3x3 RGB stem of an optimized ShuffleNetV2K, ShuffleNetV2, MobileNetV2, MobileNetV3 or SqueezeNet (``conv``
     folded with its batch norm: the bias is ``conv.bias``) in one HIP kernel, or None where the route is not taken: ``fused.STEM`` off
     (the default), a network that is not optimized, or a call ``fused.stem_conv3x3_supported`` declines (bfloat16, autocast, the CPU).
-    One route for the five families, independent of their own switches; ``x`` in any layout, the result channels-last."""
+    One route for the five families, independent of their own switches; ``x`` in any layout, the result channels-last.
+
+    ``norm``: the module between the two (a ShuffleNetV2K's): anything but an ``Identity`` did not fold into ``conv``, and the route
+    declines -- but for a ``GroupNorm`` with ``fused.GN`` on: the kernel computes the convolution alone and ``_norm_act`` the rest."""
     if not (net.fused and fused.STEM and x.is_cuda and isinstance(conv, nn.Conv2d)):
         return None
+    if norm is not None and not isinstance(norm, nn.Identity):
+        if not (fused.GN and isinstance(norm, nn.GroupNorm) and fused.stem_conv3x3_supported(conv, x)):
+            return None
+        return _norm_act(norm, nonlin, fused.stem_conv3x3_bias_act(conv, x, act=fused.ACT_NONE))
     act = _stem_act(nonlin)
     if act is None or not fused.stem_conv3x3_supported(conv, x):
         return None
     return fused.stem_conv3x3_bias_act(conv, x, act=act[0], act_param=act[1])
+
+
+def _layer_norm_of(layer_norm):
+    """``ShuffleNetV2K.layer_norm`` -> what builds the norm of ``c`` channels (reference ``network/basenetworks.py:250-259, 395-400``):
+    None ``BatchNorm2d``; 'instance' ``InstanceNorm2d`` with affine terms and running statistics (in ``eval()`` the batch-norm formula:
+    it folds); 'group' ``GroupNorm`` in 32 groups where ``c`` divides, else 29, and 4 up to 100 channels (torch's own ``ValueError``
+    where the count does not divide ``c``)."""
+    if layer_norm is None:
+        return nn.BatchNorm2d
+    if layer_norm == 'instance':
+        return lambda c: nn.InstanceNorm2d(c, affine=True, track_running_stats=True)
+    if layer_norm == 'group':
+        return lambda c: nn.GroupNorm((32 if c % 32 == 0 else 29) if c > 100 else 4, c)
+    raise ValueError('layer_norm must be None, \'instance\' or \'group\', not %r' % (layer_norm,))
+
+
+def _norm_act(norm, nonlin, t):
+    """``nonlin(norm(t))`` (``nonlin`` None: the norm alone) behind a convolution that did not absorb ``norm``, IN PLACE on the
+    producer's output ``t``: a ``GroupNorm`` followed by nothing or by an activation the kernels have a code for (``_stem_act``)
+    through ``fused.group_norm_act`` where ``fused.GN`` is on and ``fused.group_norm_supported`` takes the call, else torch's modules."""
+    act = (fused.ACT_NONE, 0.0) if nonlin is None else _stem_act(nonlin)
+    if fused.GN and act is not None and fused.group_norm_supported(norm, t):
+        return fused.group_norm_act(norm, t, act=act[0], act_param=act[1], out=t)
+    t = norm(t)
+    return t if nonlin is None else nonlin(t)
 
 
 def _channel_shuffle(x, groups=2):
@@ -413,9 +445,10 @@ def _channel_shuffle(x, groups=2):
 
 class _InvertedResidualK(nn.Module):
     """ShuffleNetV2 unit with a k x k depthwise conv (reference ``basenetworks.py:186-268``), optionally dilated (padding
-    ``(k - 1) // 2 * dilation``) and with ``nn.LeakyReLU`` (slope 0.01) in place of its ReLUs."""
+    ``(k - 1) // 2 * dilation``), with ``nn.LeakyReLU`` (slope 0.01) in place of its ReLUs and with the instance or group norm of
+    ``ShuffleNetV2K.layer_norm`` in place of its batch norms (``_layer_norm_of``)."""
 
-    def __init__(self, inp, oup, first_in_stage, *, stride=1, kernel_size=5, dilation=1, leaky_relu=False):
+    def __init__(self, inp, oup, first_in_stage, *, stride=1, kernel_size=5, dilation=1, leaky_relu=False, layer_norm=None):
         super().__init__()
         assert stride in (1, 2) and (stride != 1 or inp == oup or first_in_stage)
         self.first_in_stage = first_in_stage
@@ -423,15 +456,16 @@ class _InvertedResidualK(nn.Module):
         bf = oup // 2
         pad = (kernel_size - 1) // 2 * dilation
         act = nn.LeakyReLU if leaky_relu else nn.ReLU
+        norm = _layer_norm_of(layer_norm)
         self.branch1 = None
         if first_in_stage:
             self.branch1 = nn.Sequential(
-                nn.Conv2d(inp, inp, kernel_size, stride, pad, dilation, groups=inp, bias=False), nn.BatchNorm2d(inp),
-                nn.Conv2d(inp, bf, 1, bias=False), nn.BatchNorm2d(bf), act(inplace=True))
+                nn.Conv2d(inp, inp, kernel_size, stride, pad, dilation, groups=inp, bias=False), norm(inp),
+                nn.Conv2d(inp, bf, 1, bias=False), norm(bf), act(inplace=True))
         self.branch2 = nn.Sequential(
-            nn.Conv2d(inp if first_in_stage else bf, bf, 1, bias=False), nn.BatchNorm2d(bf), act(inplace=True),
-            nn.Conv2d(bf, bf, kernel_size, stride, pad, dilation, groups=bf, bias=False), nn.BatchNorm2d(bf),
-            nn.Conv2d(bf, bf, 1, bias=False), nn.BatchNorm2d(bf), act(inplace=True))
+            nn.Conv2d(inp if first_in_stage else bf, bf, 1, bias=False), norm(bf), act(inplace=True),
+            nn.Conv2d(bf, bf, kernel_size, stride, pad, dilation, groups=bf, bias=False), norm(bf),
+            nn.Conv2d(bf, bf, 1, bias=False), norm(bf), act(inplace=True))
 
     fused = False
 
@@ -482,6 +516,16 @@ class _InvertedResidualK(nn.Module):
             return False
         if self.leaky_relu and not (fused.UNIT_LEAKY and not torch.is_autocast_enabled()):
             return False
+        if not all(isinstance(m, nn.Identity) for m in self._norms()):      # a norm that did not fold (a GroupNorm) must run
+            return False
+        return self._convs_supported(x)
+
+    def _norms(self):
+        """The modules where the unit was built with norms: ``Identity`` after folding, a ``GroupNorm`` still itself."""
+        return ([] if self.branch1 is None else [self.branch1[1], self.branch1[3]]) + [self.branch2[i] for i in (1, 4, 6)]
+
+    def _convs_supported(self, x):
+        """Every 1x1 convolution through the unit-mode GEMM, every depthwise convolution through the stencil kernel?"""
         branches = (self.branch2,) if self.branch1 is None else (self.branch1, self.branch2)
         for branch in branches:
             for m in branch:
@@ -508,6 +552,27 @@ class _InvertedResidualK(nn.Module):
         h = self._dw(b2[3], fused.conv1x1_unit_x3(b2[0], x2, **act))
         return fused.conv1x1_unit_x3(b2[5], h, partner=x1, **act)
 
+    def _gn_route_supported(self, x):
+        """Can the unit of a group-norm network run ``_forward_gn``?  ``fused.GN`` on, float32 outside autocast, every norm a
+        ``GroupNorm`` and the convolutions as ``_convs_supported`` says; each norm decides for itself (``_norm_act``)."""
+        return (fused.GN and x.dtype == torch.float32 and x.dim() == 4 and not torch.is_autocast_enabled()
+                and all(isinstance(m, nn.GroupNorm) for m in self._norms()) and self._convs_supported(x))
+
+    def _forward_gn(self, x):
+        """The unit of a group-norm network on the project's kernels: every 1x1 convolution through the unit-mode GEMM without an
+        activation, every depthwise convolution through the stencil, every norm -- with the ReLU or LeakyReLU behind it -- through
+        the group-norm kernels in place on its producer's output (``_norm_act``), the interleave pass at the end."""
+        b1, b2 = self.branch1, self.branch2
+        if b1 is None:
+            x1, x2 = x.chunk(2, dim=1)
+        else:
+            h = _norm_act(b1[1], None, self._dw(b1[0], x))
+            x1, x2 = _norm_act(b1[3], b1[4], fused.conv1x1_unit_x3(b1[2], h, act=fused.ACT_NONE)), x
+        h = _norm_act(b2[1], b2[2], fused.conv1x1_unit_x3(b2[0], x2, act=fused.ACT_NONE))
+        h = _norm_act(b2[4], None, self._dw(b2[3], h))
+        h = _norm_act(b2[6], b2[7], fused.conv1x1_unit_x3(b2[5], h, act=fused.ACT_NONE))
+        return fused.channel_interleave(x1, h)
+
     def _forward_fused(self, x):
         if self.branch1 is None:
             x1, x2 = x.chunk(2, dim=1)
@@ -520,6 +585,8 @@ class _InvertedResidualK(nn.Module):
                 last = self.branch2[5]
                 return fused.pick('unit', fused.out_pixels(x, self.branch2[3].stride[0]), last.in_channels, last.out_channels, True, False,
                                   lambda: self._forward_unit(x), lambda: self._forward_fused(x), timing=False)
+            if self._gn_route_supported(x):
+                return self._forward_gn(x)
             return self._forward_fused(x)
         if self.branch1 is None:
             x1, x2 = x.chunk(2, dim=1)
@@ -543,8 +610,15 @@ class ShuffleNetV2K(BaseNetwork):
     * ``conv5_as_stage``: ``conv5`` is two units with dilation ``stage4_dilation``, the first a first-in-stage unit if and only if
       the widths differ.
     * ``leaky_relu``: ``nn.LeakyReLU(inplace=True)`` wherever the network has a ReLU.
-
-    The reference's instance and group norms are not offered: neither folds into a convolution."""
+    * ``layer_norm`` 'instance' / 'group' (the reference's ``--shufflenetv2k-instance-norm`` / ``--shufflenetv2k-group-norm``): in
+      place of every ``BatchNorm2d`` -- stem, second input convolution, units, ``conv5`` -- ``InstanceNorm2d(c, affine=True,
+      track_running_stats=True)`` or ``GroupNorm((32 if c % 32 == 0 else 29) if c > 100 else 4, c)`` at the same positions under the
+      same state-dict keys (a group norm has ``weight`` and ``bias`` alone).  A width the group rule does not divide raises torch's
+      ``ValueError`` as in the reference (shufflenetv2kx5's 42-channel stem).  In ``eval()`` the instance norm computes with its
+      running statistics -- the batch-norm formula -- and ``fuse_conv_bn_`` folds it like one: the optimized network is a folded
+      batch-norm network's and takes every route of one.  A group norm's statistics belong to the image: it folds into nothing, the
+      modules stay, and an optimized network runs them through ``csrc/groupnorm.hip`` behind ``fused.GN`` (``_norm_act``), through
+      torch without."""
     CONFIGS = {
         'shufflenetv2k16': ([4, 8, 4], [24, 348, 696, 1392, 1392]),
         'shufflenetv2k20': ([5, 10, 5], [32, 512, 1024, 2048, 2048]),
@@ -558,13 +632,15 @@ class ShuffleNetV2K(BaseNetwork):
     kernel_width = 5
     conv5_as_stage = False
     leaky_relu = False
-    OPTIONS = ('input_conv2_stride', 'input_conv2_outchannels', 'stage4_dilation', 'kernel_width', 'conv5_as_stage', 'leaky_relu')
+    layer_norm = None
+    OPTIONS = ('input_conv2_stride', 'input_conv2_outchannels', 'stage4_dilation', 'kernel_width', 'conv5_as_stage', 'leaky_relu',
+               'layer_norm')
 
     def __init__(self, name='shufflenetv2k16', *, input_conv2_stride=None, input_conv2_outchannels=None, stage4_dilation=None,
-                 kernel_width=None, conv5_as_stage=None, leaky_relu=None, config=None):
+                 kernel_width=None, conv5_as_stage=None, leaky_relu=None, layer_norm=None, config=None):
         given = dict(zip(self.OPTIONS, (input_conv2_stride, input_conv2_outchannels, stage4_dilation, kernel_width, conv5_as_stage,
-                                        leaky_relu)))
-        input_conv2_stride, input_conv2_outchannels, stage4_dilation, kernel_width, conv5_as_stage, leaky_relu = (
+                                        leaky_relu, layer_norm)))
+        input_conv2_stride, input_conv2_outchannels, stage4_dilation, kernel_width, conv5_as_stage, leaky_relu, layer_norm = (
             getattr(type(self), k) if v is None else v for k, v in given.items())
         assert kernel_width % 2 == 1 and stage4_dilation >= 1
         repeats, ch = config or self.CONFIGS[name]          # (``config``: (stage repeats, five channel counts) of a network of one's own)
@@ -577,12 +653,13 @@ class ShuffleNetV2K(BaseNetwork):
         for option in self.OPTIONS:
             setattr(self, option, locals()[option])
         act = nn.LeakyReLU if leaky_relu else nn.ReLU
-        unit = dict(kernel_size=kernel_width, leaky_relu=leaky_relu)
-        input_modules = [nn.Conv2d(3, ch[0], 3, 2, 1, bias=False), nn.BatchNorm2d(ch[0]), act(inplace=True)]
+        norm = _layer_norm_of(layer_norm)
+        unit = dict(kernel_size=kernel_width, leaky_relu=leaky_relu, layer_norm=layer_norm)
+        input_modules = [nn.Conv2d(3, ch[0], 3, 2, 1, bias=False), norm(ch[0]), act(inplace=True)]
         inp = ch[0]
         if input_conv2_stride:
             out = input_conv2_outchannels or inp
-            input_modules.append(nn.Sequential(nn.Conv2d(inp, out, 3, 2, 1, bias=False), nn.BatchNorm2d(out), act(inplace=True)))
+            input_modules.append(nn.Sequential(nn.Conv2d(inp, out, 3, 2, 1, bias=False), norm(out), act(inplace=True)))
             inp = out
         self.input_block = nn.Sequential(*input_modules)
         stages = []
@@ -598,12 +675,13 @@ class ShuffleNetV2K(BaseNetwork):
                                        _InvertedResidualK(ch[-1], ch[-1], False, dilation=stage4_dilation, **unit))
         else:
             self.conv5 = nn.Sequential(
-                nn.Conv2d(inp, ch[-1], 1, bias=False), nn.BatchNorm2d(ch[-1]), act(inplace=True))
+                nn.Conv2d(inp, ch[-1], 1, bias=False), norm(ch[-1]), act(inplace=True))
 
     @classmethod
     def cli(cls, parser):
-        """The reference's flags (``network/basenetworks.py:357-384``) but ``--shufflenetv2k-instance-norm`` and
-        ``--shufflenetv2k-group-norm``: those norms do not fold into a convolution."""
+        """The reference's flags (``network/basenetworks.py:357-384``).  ``--shufflenetv2k-instance-norm`` and
+        ``--shufflenetv2k-group-norm`` exclude each other and share ONE destination, ``shufflenetv2k_layer_norm`` ('instance' /
+        'group'; None without either), so that ``configure`` reads them like every other option."""
         group = parser.add_argument_group('shufflenetv2k')
         group.add_argument('--shufflenetv2k-input-conv2-stride', default=cls.input_conv2_stride, type=int,
                            help='stride of the optional 2nd input convolution')
@@ -614,6 +692,11 @@ class ShuffleNetV2K(BaseNetwork):
         group.add_argument('--shufflenetv2k-kernel', default=cls.kernel_width, type=int, help='kernel width')
         group.add_argument('--shufflenetv2k-conv5-as-stage', default=False, action='store_true')
         group.add_argument('--shufflenetv2k-leaky-relu', default=False, action='store_true')
+        layer_norm = group.add_mutually_exclusive_group()
+        layer_norm.add_argument('--shufflenetv2k-instance-norm', dest='shufflenetv2k_layer_norm', default=cls.layer_norm,
+                                action='store_const', const='instance')
+        layer_norm.add_argument('--shufflenetv2k-group-norm', dest='shufflenetv2k_layer_norm', default=cls.layer_norm,
+                                action='store_const', const='group')
 
     @classmethod
     def configure(cls, args):
@@ -622,13 +705,18 @@ class ShuffleNetV2K(BaseNetwork):
             setattr(cls, option, getattr(args, flag, getattr(cls, option)))
 
     def _input_block_forward(self, x):
-        """``input_block(x)``, the stem through ``_stem_route`` where that takes it (the second input convolution stays with torch)."""
+        """``input_block(x)``, the stem through ``_stem_route`` where that takes it (the second input convolution stays with torch).
+        In an optimized group-norm network with ``fused.GN`` on, the norms of both convolutions go through ``_norm_act``, whoever
+        computed the convolution."""
         modules = list(self.input_block)
-        y = _stem_route(self, modules[0], modules[2], x)
+        y = _stem_route(self, modules[0], modules[2], x, norm=modules[1])
+        gn = self.fused and fused.GN and x.is_cuda and isinstance(modules[1], nn.GroupNorm)
         if y is None:
-            return self.input_block(x)
+            if not gn:
+                return self.input_block(x)
+            y = _norm_act(modules[1], modules[2], modules[0](x))
         for m in modules[3:]:
-            y = m(y)
+            y = _norm_act(m[1], m[2], m[0](y)) if gn and isinstance(m, nn.Sequential) else m(y)
         return y
 
     def forward(self, x):
@@ -639,10 +727,16 @@ def _conv5_forward(net, x):
     """``net.conv5(x)`` of a ShuffleNetV2K or a ShuffleNetV2: ``Sequential(Conv2d 1x1, BatchNorm2d, non-linearity)`` through the
     split-operand GEMM's unit mode where that takes it, decided like the units (the table, else by size, never timed).  A stage
     ``conv5`` routes itself, unit by unit.  The GEMM's epilogue applies a ReLU, or a LeakyReLU where ``fused.UNIT_LEAKY`` is on (outside
-    autocast); with the switch off a LeakyReLU ``conv5`` stays with torch."""
+    autocast); with the switch off a LeakyReLU ``conv5`` stays with torch.  The module between the two must be the ``Identity`` that
+    folding leaves: a ``GroupNorm`` there runs -- with ``fused.GN`` on behind the GEMM without an activation (``_norm_act``), else
+    with torch's ``conv5``."""
     conv = net.conv5[0]
     if net.fused and x.is_cuda and isinstance(conv, nn.Conv2d) and fused.unit_conv_x3_supported(conv, x):
         nonlin, act = net.conv5[2], None
+        if not isinstance(net.conv5[1], nn.Identity):
+            if fused.GN and isinstance(net.conv5[1], nn.GroupNorm) and x.dtype == torch.float32 and not torch.is_autocast_enabled():
+                return _norm_act(net.conv5[1], nonlin, fused.conv1x1_unit_x3(conv, x, act=fused.ACT_NONE))
+            return net.conv5(x)
         if isinstance(nonlin, nn.ReLU):
             act = {}
         elif isinstance(nonlin, nn.LeakyReLU) and fused.UNIT_LEAKY and not torch.is_autocast_enabled():
@@ -1109,8 +1203,16 @@ def factory(base_name='resnet50', head_metas=None, *, seed=0):
     return net.eval()
 
 
+def _folds(norm):
+    """Is ``norm`` a per-channel affine map in ``eval()`` -- a ``BatchNorm2d``, or an ``InstanceNorm2d`` that has affine terms and
+    running statistics (which it then uses in place of the image's: the batch-norm formula, reference ``network/basenetworks.py:395-397``)?
+    Every other instance norm, and a group norm, depend on the image."""
+    return isinstance(norm, nn.BatchNorm2d) or (isinstance(norm, nn.InstanceNorm2d) and norm.affine and norm.track_running_stats
+                                                and not norm.training)
+
+
 def _fold(conv, bn):
-    """conv <- conv followed by eval-mode batch norm."""
+    """conv <- conv followed by eval-mode batch norm (or an instance norm that ``_folds``)."""
     with torch.no_grad():
         scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
         conv.weight.mul_(scale.reshape(-1, 1, 1, 1))
@@ -1128,7 +1230,7 @@ def fuse_conv_bn_(model):
         if isinstance(module, nn.Sequential):
             prev_name, prev = None, None
             for name, child in list(module.named_children()):
-                if isinstance(child, nn.BatchNorm2d) and isinstance(prev, nn.Conv2d):
+                if _folds(child) and isinstance(prev, nn.Conv2d):
                     _fold(prev, child)
                     setattr(module, name, nn.Identity())
                 prev_name, prev = name, child
@@ -1150,7 +1252,9 @@ def optimize_for_inference_(model):
       (behind ``fused.MBV3``);
     * the MobileNetV2 blocks and last convolution to that GEMM and that stencil with ReLU6 (behind ``fused.MBV2``);
     * the SqueezeNet Fire modules and max-pools to that GEMM, the Fire expand kernel and the ceil-mode pool (behind ``fused.FIRE``);
-    * the 3x3 RGB stem of these five families to the stem kernel with the bias and the activation inside (behind ``fused.STEM``)."""
+    * the 3x3 RGB stem of these five families to the stem kernel with the bias and the activation inside (behind ``fused.STEM``);
+    * a ShuffleNetV2K's instance norms fold like batch norms; its group norms stay and run through the group-norm kernels, each with
+      the activation behind it (behind ``fused.GN``)."""
     fuse_conv_bn_(model)
     for m in model.modules():
         if isinstance(m, (_Bottleneck, _BasicBlock, _InvertedResidualK, _InvertedResidual, _Fire, BaseNetwork)):
