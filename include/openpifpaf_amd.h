@@ -548,6 +548,23 @@ int opa_gemm_unit_actp_f32x3(const float* a_dev, int64_t a_pitch, const void* w3
                              const float* partner_dev, int64_t partner_pitch, const float* residual_dev, int64_t residual_pitch,
                              float* out_dev, int64_t m, int32_t n, int32_t k, int32_t act, float act_param, int32_t terms, void* stream);
 
+/* The unit mode in bfloat16 (csrc/gemm_unit_bf16.hip): the 1x1 convolutions of a ShuffleNetV2K / ShuffleNetV2 unit, conv5 and the
+ * heads of a network cast to bfloat16, one bf16 MFMA per product, float32 accumulation, ONE rounding at the store:
+ *     out[m, n]  = bf16_rne(act(sum_k a[m, k] * w[n, k] + bias[n] (+ residual[m, n])))
+ *     out[m, 2n]: out[., 2c] = partner[., c] (bits copied), out[., 2c + 1] = the above                      (partner_dev not NULL)
+ * a_dev: bf16 [m, k] with a_pitch bf16 ELEMENTS between rows (a channel slice of a wider channels-last tensor); partner_dev /
+ * residual_dev: bf16 [m, n] with their pitches, never both.  w_dev: bf16 [N_pad][K_pad], bias_dev: FLOAT32 [N_pad] -- n and k
+ * rounded up to multiples of 64, padded with zeros (a bf16 bias upcast, zeros where there is none).  out_dev: dense bf16.
+ * Any even n and k; m < 2^31; k <= a_pitch <= 2^21; partner / residual pitch >= n, even.  a_dev, partner_dev and residual_dev on
+ * 4 bytes, w_dev, bias_dev and out_dev on 16: the kernel issues no access wider than the launch's pointers and pitches allow.
+ * Columns from k on contribute exactly zero whatever the memory behind a row holds, and no byte behind column k of the last row is
+ * read.  act and act_param as opa_gemm_unit_actp_f32x3 (0 none, 1 ReLU, 2 hardswish, 3 LeakyReLU(slope), 4 ReLU clipped at the
+ * cap), applied in float32 before the rounding; a residual together with a partner, or with act 3 / 4, is refused.
+ * m == 0: OPA_OK, nothing runs. */
+int opa_gemm_unit_actp_bf16(const void* a_dev, int64_t a_pitch, const void* w_dev, const float* bias_dev,
+                            const void* partner_dev, int64_t partner_pitch, const void* residual_dev, int64_t residual_pitch,
+                            void* out_dev, int64_t m, int32_t n, int32_t k, int32_t act, float act_param, void* stream);
+
 /* 3x3 convolution, stride 1, padding 1, of an NHWC float32 activation as Winograd F(2x2, 3x3) in ONE kernel (input
  * transform -> sixteen float32 MFMA GEMMs -> output transform; csrc/winograd.hip): the bottleneck convolutions of the
  * ResNet trunk (reference network/basenetworks.py:71-150 runs them through torch.nn.Conv2d), 2.25x fewer multiplications

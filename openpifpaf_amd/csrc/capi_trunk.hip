@@ -9,7 +9,8 @@
 //                      The Winograd entry points, opa_dwconv_*, opa_gconv3x3_* and opa_maxpool3x3_* accept a null bias.
 //                      opa_fire_expand_f32x3 tests all four pointers.
 //                      opa_dwconv_*, opa_channel_interleave and opa_head_epilogue test no alignment at all.  The unit mode asks
-//                      8 bytes of a_dev, partner_dev and residual_dev, 16 of the rest.  A null pointer is aligned everywhere.
+//                      8 bytes of a_dev, partner_dev and residual_dev, 16 of the rest (opa_gemm_unit_actp_bf16: 4 and 16).  A null
+//                      pointer is aligned everywhere.
 //   empty calls        m == 0 (opa_bias_act: rows == 0) is OPA_OK for the GEMMs; an empty batch, h or w is OPA_OK for
 //                      opa_conv3x3_dilated_f32x3, opa_maxpool3x3_bias_act, opa_maxpool3x3_ceil_bias_act, opa_fire_expand_f32x3 and
 //                      opa_gconv3x3_bias_act_f32, after every check that does not need a size (all but the first test their grid
@@ -277,6 +278,32 @@ int opa_gemm_unit_actp_f32x3(const float* a_dev, int64_t a_pitch, const void* w3
     return gemm_unit_f32x3("opa_gemm_unit_actp_f32x3", "a_dev / partner_dev / residual_dev", "gemm_unit_actp_f32x3", 4, act_param, a_dev,
                            a_pitch, w3_dev, bias_dev, partner_dev, partner_pitch, residual_dev, residual_pitch, out_dev, m, n, k, act,
                            terms, stream);
+}
+
+// The unit mode in bfloat16 (csrc/gemm_unit_bf16.hip): opa_gemm_unit_actp_f32x3's checks in its order and with its words wherever
+// the rule is the same -- no terms; the pitches count bf16 elements; a_dev, partner_dev and residual_dev on 4 bytes.
+int opa_gemm_unit_actp_bf16(const void* a_dev, int64_t a_pitch, const void* w_dev, const float* bias_dev,
+                            const void* partner_dev, int64_t partner_pitch, const void* residual_dev, int64_t residual_pitch,
+                            void* out_dev, int64_t m, int32_t n, int32_t k, int32_t act, float act_param, void* stream) {
+    const Entry E("opa_gemm_unit_actp_bf16", stream);
+    if (!a_dev || !w_dev || !bias_dev || !out_dev || m < 0 || n <= 0 || k <= 0 || m > 0x7fffffffll || act < 0 || act > 4)
+        return E.refuse("bad arguments");
+    if (!std::isfinite(act_param)) return E.refuse("act_param must be finite");
+    if (act == 3 && act_param < 0.0f) return E.refuse("act_param must not be negative with act 3 (the LeakyReLU's slope)");
+    if (act == 4 && act_param <= 0.0f) return E.refuse("act_param must be positive with act 4 (the clipped ReLU's cap)");
+    if (partner_dev && residual_dev) return E.refuse("a residual cannot be combined with a partner");
+    if (residual_dev && act > 2) return E.refuse("a residual cannot be combined with act 3 or 4");
+    if (n % 2 != 0 || k % 2 != 0) return E.refuse("K and N must be even");
+    if (a_pitch < k || a_pitch % 2 != 0 || a_pitch > (1 << 21) ||
+        (partner_dev && (partner_pitch < n || partner_pitch % 2 != 0 || partner_pitch > 0x7fffffffll)) ||
+        (residual_dev && (residual_pitch < n || residual_pitch % 2 != 0 || residual_pitch > 0x7fffffffll)))
+        return E.refuse("a row pitch is shorter than its row, odd, or too long");
+    if (misaligned(3, {a_dev, partner_dev, residual_dev}) || misaligned(15, {w_dev, out_dev, bias_dev}))
+        return E.refuse("a_dev / partner_dev / residual_dev must be 4-B, w_dev / bias_dev / out_dev 16-B aligned");
+    if (m == 0) return OPA_OK;
+    return E.launched(launch_gemm_unit_act_bf16(a_dev, a_pitch, w_dev, bias_dev, partner_dev, partner_dev ? partner_pitch : 0, residual_dev,
+                                                residual_dev ? residual_pitch : 0, out_dev, (int)m, n, k, act, act_param, E.st),
+                      "gemm_unit_actp_bf16", "gemm_unit_bf16_kernel");
 }
 
 // opa_conv3x3_winograd_f32 and opa_conv3x3_winograd_f32x3 (`x3`: u_dev holds the three bf16 planes of the filter)

@@ -311,6 +311,10 @@ hipError_t launch_fire_expand(const float* h, const unsigned short* w3, const fl
 hipError_t launch_gemm_unit_act_f32x3(const float* A, int lda, const unsigned short* W3, const float* bias, const float* partner, int ldp,
                                       const float* residual, int ldr, float* out, int M, int N, int K, int act, int terms, hipStream_t st,
                                       float act_param = 0.0f);
+// csrc/gemm_unit_bf16.hip: the unit mode in bfloat16 (pitches in bf16 elements; bias float32; act 0 .. 4 read at run time)
+hipError_t launch_gemm_unit_act_bf16(const void* A, long long lda, const void* W, const float* bias, const void* partner, long long ldp,
+                                     const void* residual, long long ldr, void* out, int M, int n, int k, int act, float act_param,
+                                     hipStream_t st);
 hipError_t launch_gemm_f32_bias_act(const float* A, const float* W, const float* bias, const float* res, float* out,
                                     int M, int N, int K, int relu, hipStream_t st, const float* a_bias = nullptr);
 hipError_t launch_winograd_f23(const float* x, const float* U, float* y, const float* bias, int N, int H, int W, int Cin,

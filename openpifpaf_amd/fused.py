@@ -104,6 +104,12 @@ STEM = _switch('OPA_STEM', '0')
 # choice-table entry: where the switch is on and ``group_norm_supported`` the kernels run, else torch's ``GroupNorm``.  It ships OFF;
 # the one timing is tools/gpu/shufflenetv2k_norm_times.py, profiles/shufflenetv2k_norms/times.log.
 GN = _switch('OPA_GN', '0')
+# The 1x1 convolutions of a ShuffleNetV2K / ShuffleNetV2 cast to bfloat16 (``model.to(torch.bfloat16)``: units, ``conv5``, and a head
+# whose input channels are no multiple of 64) through the unit mode of the bf16 GEMM (csrc/gemm_unit_bf16.hip, ``conv1x1_unit_bf16``)
+# instead of MIOpen: OPA_UNIT_BF16=1 (or fused.UNIT_BF16 = True).  Never timed by ``pick``, no choice-table entry (the table's 'unit'
+# keys are float32's): where the switch is on and ``unit_conv_bf16_supported`` the kernel runs.  It ships OFF; the one timing is
+# tools/gpu/unit_bf16_times.py, profiles/unit_bf16/times.log.
+UNIT_BF16 = _switch('OPA_UNIT_BF16', '0')
 
 
 # ---- the choice table and the decision ---------------------------------------------------------------------------------------------
@@ -338,6 +344,23 @@ def _unit_weight_of(conv):
             bp[:n] = conv.bias.detach()
         return split_weight(wp), bp
     return derived(conv, '_opa_w3_unit', (conv.weight, conv.bias), make)
+
+
+def _unit_weight_bf16_of(conv):
+    """The operands of ``conv1x1_unit_bf16`` derived from the current parameters: the ``[N, K]`` bfloat16 weight padded with zeros to
+    ``[N_pad, K_pad]`` (multiples of 64) and the bias as FLOAT32 ``[N_pad]`` -- a bfloat16 bias upcast exactly, zeros where the
+    convolution has none and in the padding -- kept on the module (``derived``), keyed on weight and bias."""
+    def make():
+        w = conv.weight
+        n, k = w.shape[0], w.shape[1]
+        npad, kpad = (n + 63) // 64 * 64, (k + 63) // 64 * 64
+        wp = torch.zeros((npad, kpad), dtype=torch.bfloat16, device=w.device)
+        wp[:n, :k] = w.detach().reshape(n, k)
+        bp = torch.zeros(npad, dtype=torch.float32, device=w.device)
+        if conv.bias is not None:
+            bp[:n] = conv.bias.detach().to(torch.float32)
+        return wp, bp
+    return derived(conv, '_opa_w_unit_bf16', (conv.weight, conv.bias), make)
 
 
 def gconv_weight_of(conv):
@@ -710,6 +733,55 @@ def conv1x1_unit_x3(conv, x, relu=True, partner=None, residual=None, act=None, t
         _launch('opa_gemm_unit_actp_f32x3', *operands, float(act_param), terms)
     else:
         _launch('opa_gemm_unit_act_f32x3', *operands, terms)
+    return out
+
+
+def _unit_conv_bf16_ok(conv):
+    """The part of ``unit_conv_bf16_supported`` that depends on the convolution alone."""
+    return (UNIT_BF16 and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.in_channels % 2 == 0 and conv.out_channels % 2 == 0
+            and conv.weight.dtype == torch.bfloat16 and (conv.bias is None or conv.bias.dtype == torch.bfloat16))
+
+
+def _unit_operand_bf16_ok(t, channels):
+    """Layout of an activation operand of the bf16 unit mode (``x``, the partner or the residual), whatever its device: bfloat16,
+    ``channels`` channels innermost with an even pitch between pixels, on a 4-byte boundary, not followed by autograd."""
+    ps = _pixel_stride(t)
+    return (t.dtype == torch.bfloat16 and not t.requires_grad and ps is not None and t.shape[1] == channels
+            and ps % 2 == 0 and ps <= 2 ** 21 and t.data_ptr() % 4 == 0)
+
+
+def unit_conv_bf16_supported(conv, x, partner=None, residual=None):
+    """Can ``conv1x1_unit_bf16(conv, x, partner=partner, residual=residual)`` run?  ``fused.UNIT_BF16`` on, bfloat16 weight and
+    activation on the same GPU, outside autocast (whose parameters stay float32), a 1x1 convolution of stride 1 without padding or
+    groups and with EVEN channel counts, ``x`` (and ``partner`` or ``residual``, never both) channels-innermost tensors or channel
+    slices of such on 4-byte boundaries, nothing that autograd follows (like ``unit_conv_x3_supported``: no operand requires a gradient)."""
+    if not (x.is_cuda and conv.weight.device == x.device and not torch.is_autocast_enabled() and _unit_conv_bf16_ok(conv)
+            and _unit_operand_bf16_ok(x, conv.in_channels) and 0 < x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31):
+        return False
+    if partner is not None and residual is not None:
+        return False
+    for third in (partner, residual):
+        if third is not None and not (third.device == x.device and _unit_operand_bf16_ok(third, conv.out_channels)
+                                      and (third.shape[0], third.shape[2], third.shape[3]) == (x.shape[0], x.shape[2], x.shape[3])):
+            return False
+    return True
+
+
+def conv1x1_unit_bf16(conv, x, relu=True, partner=None, residual=None, act=None, act_param=0.0):
+    """``conv1x1_unit_x3`` for bfloat16: ``act(conv(x) (+ residual))`` for a 1x1 convolution of ANY even channel counts on a
+    channels-last bfloat16 tensor or channel slice, one bf16 MFMA per product, float32 accumulation and one rounding
+    (``opa_gemm_unit_actp_bf16``, csrc/gemm_unit_bf16.hip).  With ``partner`` the result is ``channel_shuffle(cat((partner, y), 1), 2)``
+    -- ``[B, 2N, H, W]``, the partner's bits copied into the even positions by the same kernel.  ``act`` (any of the five codes, 3 and 4
+    with ``act_param``, never with a residual) instead of ``relu``.  channels_last bfloat16 out.  ``unit_conv_bf16_supported`` says
+    whether this can run."""
+    wp, bp = _unit_weight_bf16_of(conv)
+    n = conv.out_channels
+    out = _empty_nhwc(x, n if partner is None else 2 * n, dtype=torch.bfloat16)
+    _launch('opa_gemm_unit_actp_bf16', _ptr(x), _pixel_stride(x), _ptr(wp), _ptr(bp),
+            _ptr(partner), _pixel_stride(partner) if partner is not None else 0,
+            _ptr(residual), _pixel_stride(residual) if residual is not None else 0,
+            _ptr(out), out_pixels(x), n, x.shape[1], _act_code(relu, act), float(act_param))
     return out
 
 

@@ -524,8 +524,10 @@ class _InvertedResidualK(nn.Module):
         """The modules where the unit was built with norms: ``Identity`` after folding, a ``GroupNorm`` still itself."""
         return ([] if self.branch1 is None else [self.branch1[1], self.branch1[3]]) + [self.branch2[i] for i in (1, 4, 6)]
 
-    def _convs_supported(self, x):
-        """Every 1x1 convolution through the unit-mode GEMM, every depthwise convolution through the stencil kernel?"""
+    def _convs_supported(self, x, conv_ok=None, supported=None):
+        """Every 1x1 convolution through the unit-mode GEMM, every depthwise convolution through the stencil kernel?  (``conv_ok``,
+        ``supported``: the GEMM's two predicates -- the split-operand kernel's where not given, the bf16 kernel's in ``_unit_bf16_route_supported``)"""
+        conv_ok, supported = conv_ok or fused._unit_conv_ok, supported or fused.unit_conv_x3_supported
         branches = (self.branch2,) if self.branch1 is None else (self.branch1, self.branch2)
         for branch in branches:
             for m in branch:
@@ -534,23 +536,36 @@ class _InvertedResidualK(nn.Module):
                 if m.groups > 1:
                     if not self._dw_ok(m, x):
                         return False
-                elif not fused._unit_conv_ok(m):
+                elif not conv_ok(m):
                     return False
         first = x if self.branch1 is not None else x.chunk(2, dim=1)[1]
-        return fused.unit_conv_x3_supported(self.branch2[0], first)
+        return supported(self.branch2[0], first)
 
-    def _forward_unit(self, x):
+    def _unit_bf16_route_supported(self, x):
+        """``_unit_route_supported`` for a unit cast to bfloat16: ``fused.UNIT_BF16`` on, every 1x1 convolution through the bf16
+        GEMM's unit mode (``fused.conv1x1_unit_bf16``), outside autocast, the same rules for a LeakyReLU unit and for norms."""
+        if not (fused.UNIT_BF16 and x.dtype == torch.bfloat16 and x.dim() == 4 and not torch.is_autocast_enabled()):
+            return False
+        if self.leaky_relu and not fused.UNIT_LEAKY:
+            return False
+        if not all(isinstance(m, nn.Identity) for m in self._norms()):
+            return False
+        return self._convs_supported(x, fused._unit_conv_bf16_ok, fused.unit_conv_bf16_supported)
+
+    def _forward_unit(self, x, gemm=None):
         """Three launches (five in a first unit): GEMM + bias + ReLU on the channel slice, the depthwise stencil, GEMM + bias + ReLU
         stored into the shuffled position with the pass-through half copied by the same kernel.  A ``leaky_relu`` unit: the same
-        launches with the module's LeakyReLU in the GEMM's epilogue."""
+        launches with the module's LeakyReLU in the GEMM's epilogue.  ``gemm``: ``fused.conv1x1_unit_x3`` where not given, or
+        ``fused.conv1x1_unit_bf16`` for a bfloat16 unit."""
+        gemm = gemm or fused.conv1x1_unit_x3
         b2 = self.branch2
         act = dict(act=fused.ACT_LEAKY_RELU, act_param=b2[2].negative_slope) if self.leaky_relu else {}
         if self.branch1 is None:
             x1, x2 = x.chunk(2, dim=1)
         else:
-            x1, x2 = fused.conv1x1_unit_x3(self.branch1[2], self._dw(self.branch1[0], x), **act), x
-        h = self._dw(b2[3], fused.conv1x1_unit_x3(b2[0], x2, **act))
-        return fused.conv1x1_unit_x3(b2[5], h, partner=x1, **act)
+            x1, x2 = gemm(self.branch1[2], self._dw(self.branch1[0], x), **act), x
+        h = self._dw(b2[3], gemm(b2[0], x2, **act))
+        return gemm(b2[5], h, partner=x1, **act)
 
     def _gn_route_supported(self, x):
         """Can the unit of a group-norm network run ``_forward_gn``?  ``fused.GN`` on, float32 outside autocast, every norm a
@@ -587,6 +602,8 @@ class _InvertedResidualK(nn.Module):
                                   lambda: self._forward_unit(x), lambda: self._forward_fused(x), timing=False)
             if self._gn_route_supported(x):
                 return self._forward_gn(x)
+            if self._unit_bf16_route_supported(x):  # bfloat16: no table entry, no timing -- where the route is on and supported it runs
+                return self._forward_unit(x, fused.conv1x1_unit_bf16)
             return self._forward_fused(x)
         if self.branch1 is None:
             x1, x2 = x.chunk(2, dim=1)
@@ -729,8 +746,16 @@ def _conv5_forward(net, x):
     ``conv5`` routes itself, unit by unit.  The GEMM's epilogue applies a ReLU, or a LeakyReLU where ``fused.UNIT_LEAKY`` is on (outside
     autocast); with the switch off a LeakyReLU ``conv5`` stays with torch.  The module between the two must be the ``Identity`` that
     folding leaves: a ``GroupNorm`` there runs -- with ``fused.GN`` on behind the GEMM without an activation (``_norm_act``), else
-    with torch's ``conv5``."""
+    with torch's ``conv5``.  A bfloat16 ``conv5`` (ReLU or, with ``fused.UNIT_LEAKY``, LeakyReLU behind an ``Identity``) goes through the bf16
+    GEMM's unit mode where ``fused.UNIT_BF16`` is on and ``fused.unit_conv_bf16_supported``: no table entry, no timing."""
     conv = net.conv5[0]
+    if (net.fused and x.is_cuda and x.dtype == torch.bfloat16 and isinstance(conv, nn.Conv2d) and isinstance(net.conv5[1], nn.Identity)
+            and fused.unit_conv_bf16_supported(conv, x)):
+        nonlin = net.conv5[2]
+        if isinstance(nonlin, nn.ReLU):
+            return fused.conv1x1_unit_bf16(conv, x)
+        if isinstance(nonlin, nn.LeakyReLU) and fused.UNIT_LEAKY:
+            return fused.conv1x1_unit_bf16(conv, x, act=fused.ACT_LEAKY_RELU, act_param=nonlin.negative_slope)
     if net.fused and x.is_cuda and isinstance(conv, nn.Conv2d) and fused.unit_conv_x3_supported(conv, x):
         nonlin, act = net.conv5[2], None
         if not isinstance(net.conv5[1], nn.Identity):
@@ -1134,6 +1159,10 @@ class CompositeField4(nn.Module):
             conv, x0 = self.conv, x
             x = fused.pick('unit', fused.out_pixels(x0), conv.in_channels, conv.out_channels, False, False,
                            lambda: fused.conv1x1_unit_x3(conv, x0, relu=False), lambda: conv(x0), timing=False)
+        elif (not self.training and self.conv.in_channels % 64 != 0 and x.dtype == torch.bfloat16
+              and fused.unit_conv_bf16_supported(self.conv, x)):
+            # a bfloat16 head whose input channels are no multiple of 64 (k16: 1392): the bf16 GEMM's unit mode behind fused.UNIT_BF16
+            x = fused.conv1x1_unit_bf16(self.conv, x, relu=False)
         else:
             x = self.conv(x)
         if self.fused_epilogue and fused.head_epilogue_supported(x, self.meta, self.training):
