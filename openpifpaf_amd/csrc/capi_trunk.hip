@@ -9,8 +9,9 @@
 //                      The Winograd entry points, opa_dwconv_*, opa_gconv3x3_* and opa_maxpool3x3_* accept a null bias.
 //                      opa_fire_expand_f32x3 tests all four pointers.
 //                      opa_dwconv_*, opa_channel_interleave and opa_head_epilogue test no alignment at all.  The unit mode asks
-//                      8 bytes of a_dev, partner_dev and residual_dev, 16 of the rest (opa_gemm_unit_actp_bf16: 4 and 16).  A null
-//                      pointer is aligned everywhere.
+//                      8 bytes of a_dev, partner_dev and residual_dev, 16 of the rest (opa_gemm_unit_actp_bf16: 4 and 16): one
+//                      list of checks, unit_refusal, for its four entry points.  A null pointer is aligned everywhere.
+//   act_param          one rule wherever an entry point takes it (bad_act_param); opa_dwconv_actp refuses code 3 before it.
 //   empty calls        m == 0 (opa_bias_act: rows == 0) is OPA_OK for the GEMMs; an empty batch, h or w is OPA_OK for
 //                      opa_conv3x3_dilated_f32x3, opa_maxpool3x3_bias_act, opa_maxpool3x3_ceil_bias_act, opa_fire_expand_f32x3 and
 //                      opa_gconv3x3_bias_act_f32, after every check that does not need a size (all but the first test their grid
@@ -54,6 +55,14 @@ bool misaligned(uintptr_t mask, std::initializer_list<const void*> pointers) {  
 }
 
 bool bad_terms(int32_t terms) { return terms != 6 && terms != 9; }
+
+// The parameter of an activation code: 3 (LeakyReLU) reads it as the slope, 4 (clipped ReLU) as the cap.  -> what is wrong with it, or null
+const char* bad_act_param(int32_t act, float act_param) {
+    if (!std::isfinite(act_param)) return "act_param must be finite";
+    if (act == 3 && act_param < 0.0f) return "act_param must not be negative with act 3 (the LeakyReLU's slope)";
+    if (act == 4 && act_param <= 0.0f) return "act_param must be positive with act 4 (the clipped ReLU's cap)";
+    return nullptr;
+}
 }  // namespace
 
 extern "C" {
@@ -229,29 +238,38 @@ int opa_fire_expand_f32x3(const float* h_dev, const void* w_dev, const float* bi
                                          E.st), "fire_expand_f32x3", "fire_expand_kernel");
 }
 
-// opa_gemm_unit_actp_f32x3; opa_gemm_unit_act_f32x3 as its call with act 0 .. 2 (`act_max`) and no parameter, and
-// opa_gemm_unit_bias_act_f32x3 as that one's call without a residual and with act 0 / 1 (`eight`: the pointers the alignment
-// message names, `where`: the launch in a HIP error's text).  act 3 (LeakyReLU) and 4 (clipped ReLU) read act_param.
-static int gemm_unit_f32x3(const char* fn, const char* eight, const char* where, int32_t act_max, float act_param, const float* a_dev, int64_t a_pitch, const void* w3_dev,
-                           const float* bias_dev, const float* partner_dev, int64_t partner_pitch, const float* residual_dev,
-                           int64_t residual_pitch, float* out_dev, int64_t m, int32_t n, int32_t k, int32_t act, int32_t terms,
-                           void* stream) {
-    const Entry E(fn, stream);
-    if (!a_dev || !w3_dev || !bias_dev || !out_dev || m < 0 || n <= 0 || k <= 0 || m > 0x7fffffffll || bad_terms(terms) || act < 0 || act > act_max)
-        return E.refuse("bad arguments");
-    if (!std::isfinite(act_param)) return E.refuse("act_param must be finite");
-    if (act == 3 && act_param < 0.0f) return E.refuse("act_param must not be negative with act 3 (the LeakyReLU's slope)");
-    if (act == 4 && act_param <= 0.0f) return E.refuse("act_param must be positive with act 4 (the clipped ReLU's cap)");
-    if (partner_dev && residual_dev) return E.refuse("a residual cannot be combined with a partner");
-    if (residual_dev && act > 2) return E.refuse("a residual cannot be combined with act 3 or 4");
-    if (n % 2 != 0 || k % 2 != 0) return E.refuse("K and N must be even");
-    // (a tile's 128 rows are addressed with 32-bit byte offsets: 2^21 floats per row leave room)
+// The checks of the unit mode's four entry points -> what is wrong, or null.  What differs between them: `act_max`; `mask`, the alignment
+// of a_dev / partner_dev / residual_dev (8 bytes, 4 for bfloat16), and `unaligned`, the message that names it; `terms`, null where the
+// entry point has none.  The pitches count elements.  act 3 (LeakyReLU) and 4 (clipped ReLU) read act_param.
+static const char* unit_refusal(int32_t act_max, uintptr_t mask, const char* unaligned, const int32_t* terms, const void* a_dev, int64_t a_pitch,
+                                const void* w_dev, const float* bias_dev, const void* partner_dev, int64_t partner_pitch, const void* residual_dev,
+                                int64_t residual_pitch, const void* out_dev, int64_t m, int32_t n, int32_t k, int32_t act, float act_param) {
+    if (!a_dev || !w_dev || !bias_dev || !out_dev || m < 0 || n <= 0 || k <= 0 || m > 0x7fffffffll || (terms && bad_terms(*terms)) || act < 0 ||
+        act > act_max)
+        return "bad arguments";
+    if (const char* why = bad_act_param(act, act_param)) return why;
+    if (partner_dev && residual_dev) return "a residual cannot be combined with a partner";
+    if (residual_dev && act > 2) return "a residual cannot be combined with act 3 or 4";
+    if (n % 2 != 0 || k % 2 != 0) return "K and N must be even";
+    // (a tile's 128 rows are addressed with 32-bit byte offsets: 2^21 elements per row leave room)
     if (a_pitch < k || a_pitch % 2 != 0 || a_pitch > (1 << 21) ||
         (partner_dev && (partner_pitch < n || partner_pitch % 2 != 0 || partner_pitch > 0x7fffffffll)) ||
         (residual_dev && (residual_pitch < n || residual_pitch % 2 != 0 || residual_pitch > 0x7fffffffll)))
-        return E.refuse("a row pitch is shorter than its row, odd, or too long");
-    if (misaligned(7, {a_dev, partner_dev, residual_dev}) || misaligned(15, {w3_dev, out_dev, bias_dev}))
-        return E.refuse(OPA_ERR_INVALID_ARGUMENT, std::string(eight) + " must be 8-B, w3_dev / bias_dev / out_dev 16-B aligned");
+        return "a row pitch is shorter than its row, odd, or too long";
+    return misaligned(mask, {a_dev, partner_dev, residual_dev}) || misaligned(15, {w_dev, out_dev, bias_dev}) ? unaligned : nullptr;
+}
+
+// opa_gemm_unit_actp_f32x3; opa_gemm_unit_act_f32x3 as its call with act 0 .. 2 (`act_max`) and no parameter, and
+// opa_gemm_unit_bias_act_f32x3 as that one's call without a residual and with act 0 / 1 (`eight`: the pointers the alignment message names, `where`: the launch in a HIP error's text)
+static int gemm_unit_f32x3(const char* fn, const char* eight, const char* where, int32_t act_max, float act_param, const float* a_dev,
+                           int64_t a_pitch, const void* w3_dev, const float* bias_dev, const float* partner_dev, int64_t partner_pitch,
+                           const float* residual_dev, int64_t residual_pitch, float* out_dev, int64_t m, int32_t n, int32_t k, int32_t act,
+                           int32_t terms, void* stream) {
+    const Entry E(fn, stream);
+    const std::string unaligned = std::string(eight) + " must be 8-B, w3_dev / bias_dev / out_dev 16-B aligned";
+    if (const char* why = unit_refusal(act_max, 7, unaligned.c_str(), &terms, a_dev, a_pitch, w3_dev, bias_dev, partner_dev, partner_pitch, residual_dev,
+                                       residual_pitch, out_dev, m, n, k, act, act_param))
+        return E.refuse(why);
     if (m == 0) return OPA_OK;
     return E.launched(launch_gemm_unit_act_f32x3(a_dev, (int)a_pitch, (const unsigned short*)w3_dev, bias_dev, partner_dev,
                                                  partner_dev ? (int)partner_pitch : 0, residual_dev, residual_dev ? (int)residual_pitch : 0,
@@ -268,38 +286,26 @@ int opa_gemm_unit_bias_act_f32x3(const float* a_dev, int64_t a_pitch, const void
 int opa_gemm_unit_act_f32x3(const float* a_dev, int64_t a_pitch, const void* w3_dev, const float* bias_dev,
                             const float* partner_dev, int64_t partner_pitch, const float* residual_dev, int64_t residual_pitch,
                             float* out_dev, int64_t m, int32_t n, int32_t k, int32_t act, int32_t terms, void* stream) {
-    return gemm_unit_f32x3("opa_gemm_unit_act_f32x3", "a_dev / partner_dev / residual_dev", "gemm_unit_act_f32x3", 2, 0.0f, a_dev, a_pitch,
-                           w3_dev, bias_dev, partner_dev, partner_pitch, residual_dev, residual_pitch, out_dev, m, n, k, act, terms, stream);
+    return gemm_unit_f32x3("opa_gemm_unit_act_f32x3", "a_dev / partner_dev / residual_dev", "gemm_unit_act_f32x3", 2, 0.0f, a_dev, a_pitch, w3_dev, bias_dev,
+                           partner_dev, partner_pitch, residual_dev, residual_pitch, out_dev, m, n, k, act, terms, stream);
 }
 
 int opa_gemm_unit_actp_f32x3(const float* a_dev, int64_t a_pitch, const void* w3_dev, const float* bias_dev,
                              const float* partner_dev, int64_t partner_pitch, const float* residual_dev, int64_t residual_pitch,
                              float* out_dev, int64_t m, int32_t n, int32_t k, int32_t act, float act_param, int32_t terms, void* stream) {
-    return gemm_unit_f32x3("opa_gemm_unit_actp_f32x3", "a_dev / partner_dev / residual_dev", "gemm_unit_actp_f32x3", 4, act_param, a_dev,
-                           a_pitch, w3_dev, bias_dev, partner_dev, partner_pitch, residual_dev, residual_pitch, out_dev, m, n, k, act,
-                           terms, stream);
+    return gemm_unit_f32x3("opa_gemm_unit_actp_f32x3", "a_dev / partner_dev / residual_dev", "gemm_unit_actp_f32x3", 4, act_param, a_dev, a_pitch, w3_dev,
+                           bias_dev, partner_dev, partner_pitch, residual_dev, residual_pitch, out_dev, m, n, k, act, terms, stream);
 }
 
-// The unit mode in bfloat16 (csrc/gemm_unit_bf16.hip): opa_gemm_unit_actp_f32x3's checks in its order and with its words wherever
-// the rule is the same -- no terms; the pitches count bf16 elements; a_dev, partner_dev and residual_dev on 4 bytes.
+// the unit mode in bfloat16 (csrc/gemm_unit_bf16.hip): no terms
 int opa_gemm_unit_actp_bf16(const void* a_dev, int64_t a_pitch, const void* w_dev, const float* bias_dev,
                             const void* partner_dev, int64_t partner_pitch, const void* residual_dev, int64_t residual_pitch,
                             void* out_dev, int64_t m, int32_t n, int32_t k, int32_t act, float act_param, void* stream) {
     const Entry E("opa_gemm_unit_actp_bf16", stream);
-    if (!a_dev || !w_dev || !bias_dev || !out_dev || m < 0 || n <= 0 || k <= 0 || m > 0x7fffffffll || act < 0 || act > 4)
-        return E.refuse("bad arguments");
-    if (!std::isfinite(act_param)) return E.refuse("act_param must be finite");
-    if (act == 3 && act_param < 0.0f) return E.refuse("act_param must not be negative with act 3 (the LeakyReLU's slope)");
-    if (act == 4 && act_param <= 0.0f) return E.refuse("act_param must be positive with act 4 (the clipped ReLU's cap)");
-    if (partner_dev && residual_dev) return E.refuse("a residual cannot be combined with a partner");
-    if (residual_dev && act > 2) return E.refuse("a residual cannot be combined with act 3 or 4");
-    if (n % 2 != 0 || k % 2 != 0) return E.refuse("K and N must be even");
-    if (a_pitch < k || a_pitch % 2 != 0 || a_pitch > (1 << 21) ||
-        (partner_dev && (partner_pitch < n || partner_pitch % 2 != 0 || partner_pitch > 0x7fffffffll)) ||
-        (residual_dev && (residual_pitch < n || residual_pitch % 2 != 0 || residual_pitch > 0x7fffffffll)))
-        return E.refuse("a row pitch is shorter than its row, odd, or too long");
-    if (misaligned(3, {a_dev, partner_dev, residual_dev}) || misaligned(15, {w_dev, out_dev, bias_dev}))
-        return E.refuse("a_dev / partner_dev / residual_dev must be 4-B, w_dev / bias_dev / out_dev 16-B aligned");
+    if (const char* why = unit_refusal(4, 3, "a_dev / partner_dev / residual_dev must be 4-B, w_dev / bias_dev / out_dev 16-B aligned", nullptr,
+                                       a_dev, a_pitch, w_dev, bias_dev, partner_dev, partner_pitch, residual_dev, residual_pitch, out_dev, m, n, k,
+                                       act, act_param))
+        return E.refuse(why);
     if (m == 0) return OPA_OK;
     return E.launched(launch_gemm_unit_act_bf16(a_dev, a_pitch, w_dev, bias_dev, partner_dev, partner_dev ? partner_pitch : 0, residual_dev,
                                                 residual_dev ? residual_pitch : 0, out_dev, (int)m, n, k, act, act_param, E.st),
@@ -348,8 +354,7 @@ static int dwconv(const char* fn, bool dilated, bool actp, float act_param, cons
     const Entry E(fn, stream);
     if (actp ? (act < 0 || act > 4 || act == 3) : (act < 0 || act > 2))
         return E.refuse(actp ? "act must be 0 (none), 1 (ReLU), 2 (hardswish) or 4 (clipped ReLU)" : "act must be 0 (none), 1 (ReLU) or 2 (hardswish)");
-    if (!std::isfinite(act_param)) return E.refuse("act_param must be finite");
-    if (act == 4 && act_param <= 0.0f) return E.refuse("act_param must be positive with act 4 (the clipped ReLU's cap)");
+    if (const char* why = bad_act_param(act, act_param)) return E.refuse(why);          // (act 3 never gets here)
     const bool k_ok = k == 3 || k == 5 || (dilated && k == 7);
     const bool d_ok = dilation == 1 || (dilated && (dilation == 2 || dilation == 4) && stride == 1);
     if (!x_dev || !w_dev || !out_dev || batch <= 0 || h <= 0 || w <= 0 || channels <= 0 || x_pixel_stride < channels ||
@@ -425,9 +430,7 @@ int opa_stem3x3_actp(const float* x_dev, int64_t x_batch_stride, int64_t x_chann
     if (stride != 1 && stride != 2) return E.refuse("stride must be 1 or 2");
     if (!stem3x3_channels_ok(channels_out)) return E.refuse("channels_out must be 16, 24, 32, 42 or 64");
     if (act < 0 || act > 4) return E.refuse("act must be 0 (none), 1 (ReLU), 2 (hardswish), 3 (LeakyReLU) or 4 (clipped ReLU)");
-    if (!std::isfinite(act_param)) return E.refuse("act_param must be finite");
-    if (act == 3 && act_param < 0.0f) return E.refuse("act_param must not be negative with act 3 (the LeakyReLU's slope)");
-    if (act == 4 && act_param <= 0.0f) return E.refuse("act_param must be positive with act 4 (the clipped ReLU's cap)");
+    if (const char* why = bad_act_param(act, act_param)) return E.refuse(why);
     if (batch == 0) return OPA_OK;
     // 32-bit element indices in the kernel (in double: exact up to 2^53, and no product of these arguments overflows it); the
     // stride of a dimension of one element addresses nothing
@@ -505,9 +508,7 @@ int opa_groupnorm_actp(const float* x_dev, int64_t x_pixel_stride, const float* 
         return E.refuse("pixel strides must be even and at least channels");
     if (!std::isfinite(eps) || eps < 0.0f) return E.refuse("eps must be finite and not negative");
     if (act < 0 || act > 4) return E.refuse("act must be 0 (none), 1 (ReLU), 2 (hardswish), 3 (LeakyReLU) or 4 (clipped ReLU)");
-    if (!std::isfinite(act_param)) return E.refuse("act_param must be finite");
-    if (act == 3 && act_param < 0.0f) return E.refuse("act_param must not be negative with act 3 (the LeakyReLU's slope)");
-    if (act == 4 && act_param <= 0.0f) return E.refuse("act_param must be positive with act 4 (the clipped ReLU's cap)");
+    if (const char* why = bad_act_param(act, act_param)) return E.refuse(why);
     if (out_dev == x_dev && out_pixel_stride != x_pixel_stride) return E.refuse("out_dev == x_dev (in place) needs equal pixel strides");
     if (batch == 0) return OPA_OK;
     // the grids and the indices first: behind them the workspace's size is a product that fits

@@ -6,9 +6,12 @@ kernel's contract), the operands derived from the module's parameters (split, pa
 the choice is made once per shape and remembered in one table (``_CHOICE``, shipped as ``conv1x1_pinned.json``): ``conv_bias_act``
 and ``pick`` say what the candidates are, ``_decide`` makes the choice.  In this order: the launcher, the switches, the choice
 table and the decision, the derived operands, then the routes by kernel family -- the epilogue passes, the 1x1 GEMMs, the
-split-operand convolutions (pair, 3x3 and dilated 3x3, stem, heads, unit mode), the Fire expand, the max-pools, the grouped and
-the depthwise stencils, the RGB stem, group norm, squeeze-and-excitation."""
+split-operand convolutions (pair, 3x3 and dilated 3x3, stem, heads), the unit mode (ONE route with a ``UnitMode`` record per element
+type -- float32 on the split-operand GEMM, bfloat16 on the bf16 MFMA -- whose callers pass tensors and name no dtype), the Fire expand,
+the max-pools, the grouped and the depthwise stencils, the RGB stem, group norm, squeeze-and-excitation."""
+import functools
 import os
+import typing
 
 import torch
 
@@ -17,8 +20,8 @@ from .native import _ptr, _stream
 
 _DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 ACT_NONE, ACT_RELU, ACT_HARDSWISH = 0, 1, 2      # the activation codes of opa_dwconv_act and opa_gemm_unit_act_f32x3
-# ... and the two with a parameter (``act_param``), which only opa_gemm_unit_actp_f32x3 and opa_dwconv_actp take: LeakyReLU(slope)
-# (the GEMM alone) and the ReLU clipped at a cap (ReLU6: 6); opa_stem3x3_actp takes all five
+# ... and the two with a parameter (``act_param``), which the opa_*_actp entry points take: LeakyReLU(slope) -- not the stencil -- and
+# the ReLU clipped at a cap (ReLU6: 6)
 ACT_LEAKY_RELU, ACT_RELU6 = 3, 4
 
 
@@ -328,39 +331,24 @@ def _stem_weight_of(conv):
     return derived(conv, '_opa_w3_stem', (conv.weight,), make)
 
 
-def _unit_weight_of(conv):
-    """The operands of ``conv1x1_unit_x3`` and ``head_conv_x3`` derived from the current parameters: ``split_weight`` of the
-    ``[N, K]`` weight padded with zeros to ``[N_pad, K_pad]`` (multiples of 64: the kernel's tile width and two of its K-steps) and
-    the bias padded to ``N_pad`` (zeros where the convolution has none) -- kept on the module like ``_split_weight_of``; the
-    convolution keeps its parameters, and the key holds the bias tensor too (a bias REPLACED by a new Parameter is a new operand)."""
+def _unit_operands_of(mode, conv):
+    """The operands of ``conv1x1_unit`` (float32: of ``head_conv_x3`` too) derived from the current parameters: the ``[N, K]`` weight in
+    ``mode``'s dtype padded with zeros to ``[N_pad, K_pad]`` (multiples of 64: the kernel's tile width and two of its K-steps) as
+    ``mode.weight`` lays it out -- float32 ``split_weight``'s ``[3, N_pad, K_pad]``, bfloat16 as it is -- and the bias as FLOAT32 ``[N_pad]``
+    (a bfloat16 bias upcast exactly; zeros where the convolution has none and in the padding) -- kept on the module as ``mode.cache``
+    like ``_split_weight_of``; the convolution keeps its parameters, and the key holds the bias tensor too (a bias REPLACED by a new
+    Parameter is a new operand)."""
     def make():
         w = conv.weight
         n, k = w.shape[0], w.shape[1]
         npad, kpad = (n + 63) // 64 * 64, (k + 63) // 64 * 64
-        wp = torch.zeros((npad, kpad), dtype=torch.float32, device=w.device)
+        wp = torch.zeros((npad, kpad), dtype=mode.dtype, device=w.device)
         wp[:n, :k] = w.detach().reshape(n, k)
         bp = torch.zeros(npad, dtype=torch.float32, device=w.device)
         if conv.bias is not None:
             bp[:n] = conv.bias.detach()
-        return split_weight(wp), bp
-    return derived(conv, '_opa_w3_unit', (conv.weight, conv.bias), make)
-
-
-def _unit_weight_bf16_of(conv):
-    """The operands of ``conv1x1_unit_bf16`` derived from the current parameters: the ``[N, K]`` bfloat16 weight padded with zeros to
-    ``[N_pad, K_pad]`` (multiples of 64) and the bias as FLOAT32 ``[N_pad]`` -- a bfloat16 bias upcast exactly, zeros where the
-    convolution has none and in the padding -- kept on the module (``derived``), keyed on weight and bias."""
-    def make():
-        w = conv.weight
-        n, k = w.shape[0], w.shape[1]
-        npad, kpad = (n + 63) // 64 * 64, (k + 63) // 64 * 64
-        wp = torch.zeros((npad, kpad), dtype=torch.bfloat16, device=w.device)
-        wp[:n, :k] = w.detach().reshape(n, k)
-        bp = torch.zeros(npad, dtype=torch.float32, device=w.device)
-        if conv.bias is not None:
-            bp[:n] = conv.bias.detach().to(torch.float32)
-        return wp, bp
-    return derived(conv, '_opa_w_unit_bf16', (conv.weight, conv.bias), make)
+        return mode.weight(wp), bp
+    return derived(conv, mode.cache, (conv.weight, conv.bias), make)
 
 
 def gconv_weight_of(conv):
@@ -547,7 +535,7 @@ def conv_bias_act(conv, x, bias, residual=None, relu=True, a_bias=None):
     return bias_act_(conv(x), bias, residual, relu)
 
 
-# ---- the split-operand convolutions: pair, strided 3x3, stem, heads, unit mode ----------------------------------------------------------
+# ---- the split-operand convolutions: pair, strided 3x3, stem, heads; the unit mode, float32 and bfloat16 --------------------------------
 
 def pair_supported(conv, dconv, h, x, bias, a_bias=None):
     """Can ``conv(h) + dconv(x)`` run as ONE split-operand product (``conv1x1_pair_bias_act_x3``)?  float32, channels_last,
@@ -674,115 +662,126 @@ def head_conv_x3(conv, x):
     return out[:, :n].contiguous(memory_format=torch.channels_last) if w3.shape[1] != n else out
 
 
-def _unit_conv_ok(conv):
-    """The part of ``unit_conv_x3_supported`` that depends on the convolution alone."""
-    return (X3_UNIT and X3_TERMS in (6, 9) and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
+class UnitMode(typing.NamedTuple):
+    """The unit mode for one element type: what the predicates, the derived operands and the launcher of the route read."""
+    dtype: torch.dtype                  # of the weight, the bias and the activations
+    align: int                          # bytes: the boundary ``x``, the partner and the residual lie on
+    enabled: typing.Callable            # () -> the route's switch as it reads NOW
+    declines_autocast: bool             # does ``unit_conv_supported`` itself decline under autocast (whose parameters stay float32)?
+    weight: typing.Callable             # the padded ``[N_pad, K_pad]`` weight -> the kernel's weight operand
+    cache: str                          # the attribute ``_unit_operands_of`` keeps the operands under
+    launch: typing.Callable             # (operands, act code, act_param, terms) -> the launch
+    gemm: str                           # the name ``conv1x1_unit`` calls the mode's GEMM by
+    table: bool                         # is a competing torch path chosen through the choice table (``pick_unit``)?
+    head: typing.Callable               # () -> may a head's convolution take the mode NOW?
+
+
+def _launch_unit_x3(operands, code, act_param, terms):
+    """``ACT_LEAKY_RELU`` / ``ACT_RELU6`` to ``opa_gemm_unit_actp_f32x3``, every other code to the symbol it has always gone to: one kernel."""
+    terms = int(X3_TERMS if terms is None else terms)
+    if code in (ACT_LEAKY_RELU, ACT_RELU6):
+        _launch('opa_gemm_unit_actp_f32x3', *operands, code, float(act_param), terms)
+    else:
+        _launch('opa_gemm_unit_act_f32x3', *operands, code, terms)
+
+
+# float32 through the split-operand GEMM (csrc/gemm_f32x3.hip); bfloat16 on the bf16 MFMA (csrc/gemm_unit_bf16.hip): one symbol, no terms
+UNIT_MODE_X3 = UnitMode(torch.float32, 8, lambda: X3_UNIT and X3_TERMS in (6, 9), False, split_weight, '_opa_w3_unit', _launch_unit_x3,
+                        'conv1x1_unit_x3', True, lambda: X3_HEAD)
+UNIT_MODE_BF16 = UnitMode(torch.bfloat16, 4, lambda: UNIT_BF16, True, lambda wp: wp, '_opa_w_unit_bf16',
+                          lambda operands, code, act_param, terms: _launch('opa_gemm_unit_actp_bf16', *operands, code, float(act_param)),
+                          'conv1x1_unit_bf16', False, lambda: True)
+_UNIT_MODES = {mode.dtype: mode for mode in (UNIT_MODE_X3, UNIT_MODE_BF16)}
+
+
+def unit_mode_of(t):
+    """The unit mode for tensors of ``t``'s dtype, or None where there is none."""
+    return _UNIT_MODES.get(t.dtype)
+
+
+def _unit_conv_ok(mode, conv):
+    """The part of ``unit_conv_supported`` that depends on the convolution alone."""
+    return (mode.enabled() and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
             and conv.dilation == (1, 1) and conv.groups == 1 and conv.in_channels % 2 == 0 and conv.out_channels % 2 == 0
-            and conv.weight.dtype == torch.float32
-            and (conv.bias is None or conv.bias.dtype == torch.float32))
+            and conv.weight.dtype == mode.dtype and (conv.bias is None or conv.bias.dtype == mode.dtype))
 
 
-def _unit_operand_ok(t, channels):
-    """Layout of an activation operand of the unit mode (``x`` or the partner), whatever its device: float32, ``channels`` channels
-    innermost with an even pitch between pixels, on an 8-byte boundary, not followed by autograd."""
+def _unit_operand_ok(mode, t, channels):
+    """Layout of an activation operand of the unit mode (``x``, the partner or the residual), whatever its device: ``mode``'s dtype,
+    ``channels`` channels innermost with an even pitch between pixels, on ``mode``'s boundary, not followed by autograd."""
     ps = _pixel_stride(t)
-    return (t.dtype == torch.float32 and not t.requires_grad and ps is not None and t.shape[1] == channels
-            and ps % 2 == 0 and ps <= 2 ** 21 and t.data_ptr() % 8 == 0)
+    return (t.dtype == mode.dtype and not t.requires_grad and ps is not None and t.shape[1] == channels
+            and ps % 2 == 0 and ps <= 2 ** 21 and t.data_ptr() % mode.align == 0)
 
 
-def unit_conv_x3_supported(conv, x, partner=None, residual=None):
-    """Can ``conv1x1_unit_x3(conv, x, partner=partner, residual=residual)`` run?  float32 on the GPU, a 1x1 convolution of stride 1
-    without padding or groups and with EVEN channel counts, ``x`` (and ``partner`` or ``residual``, never both) channels-innermost
-    tensors or channel slices of such, on 8-byte boundaries, nothing that autograd follows; the partner and the residual have the
-    output's pixels and ``conv.out_channels`` channels."""
-    if not (x.is_cuda and conv.weight.device == x.device and _unit_conv_ok(conv) and _unit_operand_ok(x, conv.in_channels)
-            and 0 < x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31):
+def unit_conv_supported(conv, x, partner=None, residual=None, mode=None, head=False):
+    """Can ``conv1x1_unit(conv, x, partner=partner, residual=residual)`` run?  The mode of ``x``'s dtype (``mode`` where given) switched
+    on, weight and activation of that dtype on the same GPU -- bfloat16: outside autocast, whose parameters stay float32 -- a 1x1
+    convolution of stride 1 without padding or groups and with EVEN channel counts, ``x`` (and ``partner`` or ``residual``, never both:
+    the output's pixels, ``conv.out_channels`` channels) channels-innermost tensors or channel slices of such, on 8-byte boundaries
+    (bfloat16: 4), nothing that autograd follows.  ``head``: ``conv`` is a head's, which float32 takes behind ``X3_HEAD`` only."""
+    mode = mode or unit_mode_of(x)
+    if not (mode is not None and x.is_cuda and conv.weight.device == x.device and (not head or mode.head())
+            and not (mode.declines_autocast and torch.is_autocast_enabled()) and _unit_conv_ok(mode, conv)
+            and _unit_operand_ok(mode, x, conv.in_channels) and 0 < x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31):
         return False
     if partner is not None and residual is not None:
         return False
     for third in (partner, residual):
-        if third is not None and not (third.device == x.device and _unit_operand_ok(third, conv.out_channels)
+        if third is not None and not (third.device == x.device and _unit_operand_ok(mode, third, conv.out_channels)
                                       and (third.shape[0], third.shape[2], third.shape[3]) == (x.shape[0], x.shape[2], x.shape[3])):
             return False
     return True
 
 
-def conv1x1_unit_x3(conv, x, relu=True, partner=None, residual=None, act=None, terms=None, act_param=0.0):
+def _conv1x1_unit(mode, conv, x, relu=True, partner=None, residual=None, act=None, terms=None, act_param=0.0):
     """``act(conv(x))`` for a biased 1x1 convolution of ANY even channel counts on a channels-last tensor or channel slice
     (reference ``network/basenetworks.py:186-242``: the 1x1 convolutions of a ShuffleNetV2K unit, folded with their batch norms),
-    through the split-operand GEMM's unit mode (``opa_gemm_unit_act_f32x3``).  With ``partner`` (``[B, N, H, W]``, may be a
-    slice) the result is ``channel_shuffle(cat((partner, y), 1), 2)`` -- ``[B, 2N, H, W]``, the partner's channels copied into the
-    even positions by the same kernel.  channels_last float32 out.  ``unit_conv_x3_supported`` says whether this can run.
+    through the unit mode ``mode``: float32 the split-operand GEMM's (``opa_gemm_unit_act_f32x3``),
+    bfloat16 one bf16 MFMA per product, float32 accumulation and one rounding (``opa_gemm_unit_actp_bf16``).  With ``partner``
+    (``[B, N, H, W]``, may be a slice) the result is ``channel_shuffle(cat((partner, y), 1), 2)`` -- ``[B, 2N, H, W]``, the partner's
+    channels copied into the even positions by the same kernel.  channels_last ``x.dtype`` out.  ``unit_conv_supported``: can it run?
 
     ``act`` (``ACT_NONE`` / ``ACT_RELU`` / ``ACT_HARDSWISH``) instead of ``relu``, and ``residual`` (``[B, N, H, W]``, may be a slice,
     never together with a partner): ``act(conv(x) + residual)`` in the same launch -- the 1x1 convolutions of a MobileNetV3 block.
-    ``terms``: 6 or 9 instead of ``X3_TERMS`` (the squeeze of a SqueezeNet Fire: ``FIRE_TERMS``).
-    ``act`` ``ACT_LEAKY_RELU`` / ``ACT_RELU6`` with ``act_param`` (the slope / the cap; never with a residual) -- a LeakyReLU unit, the
-    expanding and the last convolution of MobileNetV2 -- go to ``opa_gemm_unit_actp_f32x3``, the same kernel; every other code to the
-    symbol it has always gone to."""
-    w3, bp = _unit_weight_of(conv)
+    ``act`` ``ACT_LEAKY_RELU`` / ``ACT_RELU6`` with ``act_param`` (the slope / the cap; never with a residual): a LeakyReLU unit, the
+    expanding and the last convolution of MobileNetV2.  ``terms`` (float32 alone): 6 or 9 instead of ``X3_TERMS`` (the squeeze of a
+    SqueezeNet Fire: ``FIRE_TERMS``).  ``mode.launch`` says which symbol takes which code."""
+    w, bp = _unit_operands_of(mode, conv)
     n = conv.out_channels
-    out = _empty_nhwc(x, n if partner is None else 2 * n, dtype=torch.float32)
-    code = _act_code(relu, act)
-    operands = (_ptr(x), _pixel_stride(x), _ptr(w3), _ptr(bp),
+    out = _empty_nhwc(x, n if partner is None else 2 * n, dtype=mode.dtype)
+    operands = (_ptr(x), _pixel_stride(x), _ptr(w), _ptr(bp),
                 _ptr(partner), _pixel_stride(partner) if partner is not None else 0,
                 _ptr(residual), _pixel_stride(residual) if residual is not None else 0,
-                _ptr(out), out_pixels(x), n, x.shape[1], code)
-    terms = int(X3_TERMS if terms is None else terms)
-    if code in (ACT_LEAKY_RELU, ACT_RELU6):
-        _launch('opa_gemm_unit_actp_f32x3', *operands, float(act_param), terms)
-    else:
-        _launch('opa_gemm_unit_act_f32x3', *operands, terms)
+                _ptr(out), out_pixels(x), n, x.shape[1])
+    mode.launch(operands, _act_code(relu, act), act_param, terms)
     return out
 
 
-def _unit_conv_bf16_ok(conv):
-    """The part of ``unit_conv_bf16_supported`` that depends on the convolution alone."""
-    return (UNIT_BF16 and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
-            and conv.dilation == (1, 1) and conv.groups == 1 and conv.in_channels % 2 == 0 and conv.out_channels % 2 == 0
-            and conv.weight.dtype == torch.bfloat16 and (conv.bias is None or conv.bias.dtype == torch.bfloat16))
+def conv1x1_unit(conv, x, **kwargs):
+    """``_conv1x1_unit`` in the mode of ``x``'s dtype, called by the mode's public name as it reads NOW: a recorder that a test or a
+    tool puts on ``conv1x1_unit_x3`` / ``conv1x1_unit_bf16`` sees every launch of the routes."""
+    return globals()[unit_mode_of(x).gemm](conv, x, **kwargs)
 
 
-def _unit_operand_bf16_ok(t, channels):
-    """Layout of an activation operand of the bf16 unit mode (``x``, the partner or the residual), whatever its device: bfloat16,
-    ``channels`` channels innermost with an even pitch between pixels, on a 4-byte boundary, not followed by autograd."""
-    ps = _pixel_stride(t)
-    return (t.dtype == torch.bfloat16 and not t.requires_grad and ps is not None and t.shape[1] == channels
-            and ps % 2 == 0 and ps <= 2 ** 21 and t.data_ptr() % 4 == 0)
+def pick_unit(x, m, k, n, has_partner, run_unit, run_other):
+    """``run_unit``, a route through the unit mode of ``x``'s dtype that the caller found supported, or ``run_other``, what the trunk did
+    before.  float32: ``pick``'s decision, key ``'unit'``, never timed.  bfloat16: no table entry -- the supported route runs."""
+    if unit_mode_of(x).table:
+        return pick('unit', m, k, n, has_partner, False, run_unit, run_other, timing=False)
+    return run_unit()
 
 
-def unit_conv_bf16_supported(conv, x, partner=None, residual=None):
-    """Can ``conv1x1_unit_bf16(conv, x, partner=partner, residual=residual)`` run?  ``fused.UNIT_BF16`` on, bfloat16 weight and
-    activation on the same GPU, outside autocast (whose parameters stay float32), a 1x1 convolution of stride 1 without padding or
-    groups and with EVEN channel counts, ``x`` (and ``partner`` or ``residual``, never both) channels-innermost tensors or channel
-    slices of such on 4-byte boundaries, nothing that autograd follows (like ``unit_conv_x3_supported``: no operand requires a gradient)."""
-    if not (x.is_cuda and conv.weight.device == x.device and not torch.is_autocast_enabled() and _unit_conv_bf16_ok(conv)
-            and _unit_operand_bf16_ok(x, conv.in_channels) and 0 < x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31):
-        return False
-    if partner is not None and residual is not None:
-        return False
-    for third in (partner, residual):
-        if third is not None and not (third.device == x.device and _unit_operand_bf16_ok(third, conv.out_channels)
-                                      and (third.shape[0], third.shape[2], third.shape[3]) == (x.shape[0], x.shape[2], x.shape[3])):
-            return False
-    return True
+# The per-dtype names (tests, tools/gpu and the documents use them; launch recorders wrap the two GEMMs): the functions above, one mode bound
+_unit_weight_of = functools.partial(_unit_operands_of, UNIT_MODE_X3)
+_unit_weight_bf16_of = functools.partial(_unit_operands_of, UNIT_MODE_BF16)
+unit_conv_x3_supported = functools.partial(unit_conv_supported, mode=UNIT_MODE_X3)
+unit_conv_bf16_supported = functools.partial(unit_conv_supported, mode=UNIT_MODE_BF16)
+conv1x1_unit_x3 = functools.partial(_conv1x1_unit, UNIT_MODE_X3)
 
 
-def conv1x1_unit_bf16(conv, x, relu=True, partner=None, residual=None, act=None, act_param=0.0):
-    """``conv1x1_unit_x3`` for bfloat16: ``act(conv(x) (+ residual))`` for a 1x1 convolution of ANY even channel counts on a
-    channels-last bfloat16 tensor or channel slice, one bf16 MFMA per product, float32 accumulation and one rounding
-    (``opa_gemm_unit_actp_bf16``, csrc/gemm_unit_bf16.hip).  With ``partner`` the result is ``channel_shuffle(cat((partner, y), 1), 2)``
-    -- ``[B, 2N, H, W]``, the partner's bits copied into the even positions by the same kernel.  ``act`` (any of the five codes, 3 and 4
-    with ``act_param``, never with a residual) instead of ``relu``.  channels_last bfloat16 out.  ``unit_conv_bf16_supported`` says
-    whether this can run."""
-    wp, bp = _unit_weight_bf16_of(conv)
-    n = conv.out_channels
-    out = _empty_nhwc(x, n if partner is None else 2 * n, dtype=torch.bfloat16)
-    _launch('opa_gemm_unit_actp_bf16', _ptr(x), _pixel_stride(x), _ptr(wp), _ptr(bp),
-            _ptr(partner), _pixel_stride(partner) if partner is not None else 0,
-            _ptr(residual), _pixel_stride(residual) if residual is not None else 0,
-            _ptr(out), out_pixels(x), n, x.shape[1], _act_code(relu, act), float(act_param))
-    return out
+def conv1x1_unit_bf16(conv, x, relu=True, partner=None, residual=None, act=None, act_param=0.0):          # (its signature: no ``terms``)
+    return _conv1x1_unit(UNIT_MODE_BF16, conv, x, relu, partner, residual, act, None, act_param)
 
 
 # ---- the Fire expand ------------------------------------------------------------------------------------------------------------------

@@ -508,11 +508,12 @@ class _InvertedResidualK(nn.Module):
         return x
 
     def _unit_route_supported(self, x):
-        """Can the WHOLE unit run on the project's kernels alone (``_forward_unit``)?  Every 1x1 convolution through the
-        split-operand GEMM's unit mode, every depthwise convolution through the stencil kernel.  The GEMM's epilogue applies the
-        ReLU, or the LeakyReLU of a ``leaky_relu`` unit where ``fused.UNIT_LEAKY`` is on and outside autocast: otherwise such a unit
-        takes ``_forward_fused``."""
-        if not (x.dtype == torch.float32 and x.dim() == 4):
+        """Can the WHOLE unit run on the project's kernels alone (``_forward_unit``)?  Every 1x1 convolution through the unit mode of
+        ``x``'s dtype (``fused.unit_mode_of``: the split-operand GEMM's for float32, the bf16 GEMM's behind ``fused.UNIT_BF16`` and
+        outside autocast for bfloat16), every depthwise convolution through the stencil kernel.  The GEMM's epilogue applies the ReLU, or
+        the LeakyReLU of a ``leaky_relu`` unit where ``fused.UNIT_LEAKY`` is on and outside autocast: otherwise such a unit takes
+        ``_forward_fused``."""
+        if fused.unit_mode_of(x) is None or x.dim() != 4:
             return False
         if self.leaky_relu and not (fused.UNIT_LEAKY and not torch.is_autocast_enabled()):
             return False
@@ -524,10 +525,9 @@ class _InvertedResidualK(nn.Module):
         """The modules where the unit was built with norms: ``Identity`` after folding, a ``GroupNorm`` still itself."""
         return ([] if self.branch1 is None else [self.branch1[1], self.branch1[3]]) + [self.branch2[i] for i in (1, 4, 6)]
 
-    def _convs_supported(self, x, conv_ok=None, supported=None):
-        """Every 1x1 convolution through the unit-mode GEMM, every depthwise convolution through the stencil kernel?  (``conv_ok``,
-        ``supported``: the GEMM's two predicates -- the split-operand kernel's where not given, the bf16 kernel's in ``_unit_bf16_route_supported``)"""
-        conv_ok, supported = conv_ok or fused._unit_conv_ok, supported or fused.unit_conv_x3_supported
+    def _convs_supported(self, x):
+        """Every 1x1 convolution through the unit-mode GEMM of ``x``'s dtype, every depthwise convolution through the stencil kernel?"""
+        mode = fused.unit_mode_of(x)
         branches = (self.branch2,) if self.branch1 is None else (self.branch1, self.branch2)
         for branch in branches:
             for m in branch:
@@ -536,29 +536,16 @@ class _InvertedResidualK(nn.Module):
                 if m.groups > 1:
                     if not self._dw_ok(m, x):
                         return False
-                elif not conv_ok(m):
+                elif not fused._unit_conv_ok(mode, m):
                     return False
         first = x if self.branch1 is not None else x.chunk(2, dim=1)[1]
-        return supported(self.branch2[0], first)
+        return fused.unit_conv_supported(self.branch2[0], first)
 
-    def _unit_bf16_route_supported(self, x):
-        """``_unit_route_supported`` for a unit cast to bfloat16: ``fused.UNIT_BF16`` on, every 1x1 convolution through the bf16
-        GEMM's unit mode (``fused.conv1x1_unit_bf16``), outside autocast, the same rules for a LeakyReLU unit and for norms."""
-        if not (fused.UNIT_BF16 and x.dtype == torch.bfloat16 and x.dim() == 4 and not torch.is_autocast_enabled()):
-            return False
-        if self.leaky_relu and not fused.UNIT_LEAKY:
-            return False
-        if not all(isinstance(m, nn.Identity) for m in self._norms()):
-            return False
-        return self._convs_supported(x, fused._unit_conv_bf16_ok, fused.unit_conv_bf16_supported)
-
-    def _forward_unit(self, x, gemm=None):
+    def _forward_unit(self, x):
         """Three launches (five in a first unit): GEMM + bias + ReLU on the channel slice, the depthwise stencil, GEMM + bias + ReLU
         stored into the shuffled position with the pass-through half copied by the same kernel.  A ``leaky_relu`` unit: the same
-        launches with the module's LeakyReLU in the GEMM's epilogue.  ``gemm``: ``fused.conv1x1_unit_x3`` where not given, or
-        ``fused.conv1x1_unit_bf16`` for a bfloat16 unit."""
-        gemm = gemm or fused.conv1x1_unit_x3
-        b2 = self.branch2
+        launches with the module's LeakyReLU in the GEMM's epilogue."""
+        gemm, b2 = fused.conv1x1_unit, self.branch2
         act = dict(act=fused.ACT_LEAKY_RELU, act_param=b2[2].negative_slope) if self.leaky_relu else {}
         if self.branch1 is None:
             x1, x2 = x.chunk(2, dim=1)
@@ -582,10 +569,10 @@ class _InvertedResidualK(nn.Module):
             x1, x2 = x.chunk(2, dim=1)
         else:
             h = _norm_act(b1[1], None, self._dw(b1[0], x))
-            x1, x2 = _norm_act(b1[3], b1[4], fused.conv1x1_unit_x3(b1[2], h, act=fused.ACT_NONE)), x
-        h = _norm_act(b2[1], b2[2], fused.conv1x1_unit_x3(b2[0], x2, act=fused.ACT_NONE))
+            x1, x2 = _norm_act(b1[3], b1[4], fused.conv1x1_unit(b1[2], h, act=fused.ACT_NONE)), x
+        h = _norm_act(b2[1], b2[2], fused.conv1x1_unit(b2[0], x2, act=fused.ACT_NONE))
         h = _norm_act(b2[4], None, self._dw(b2[3], h))
-        h = _norm_act(b2[6], b2[7], fused.conv1x1_unit_x3(b2[5], h, act=fused.ACT_NONE))
+        h = _norm_act(b2[6], b2[7], fused.conv1x1_unit(b2[5], h, act=fused.ACT_NONE))
         return fused.channel_interleave(x1, h)
 
     def _forward_fused(self, x):
@@ -596,14 +583,12 @@ class _InvertedResidualK(nn.Module):
 
     def forward(self, x):
         if self.fused and x.is_cuda:
-            if self._unit_route_supported(x):       # ONE decision per unit: its output pixels and its last convolution
+            if self._unit_route_supported(x):       # ONE decision per unit (float32: its output pixels and its last convolution)
                 last = self.branch2[5]
-                return fused.pick('unit', fused.out_pixels(x, self.branch2[3].stride[0]), last.in_channels, last.out_channels, True, False,
-                                  lambda: self._forward_unit(x), lambda: self._forward_fused(x), timing=False)
+                return fused.pick_unit(x, fused.out_pixels(x, self.branch2[3].stride[0]), last.in_channels, last.out_channels, True,
+                                       lambda: self._forward_unit(x), lambda: self._forward_fused(x))
             if self._gn_route_supported(x):
                 return self._forward_gn(x)
-            if self._unit_bf16_route_supported(x):  # bfloat16: no table entry, no timing -- where the route is on and supported it runs
-                return self._forward_unit(x, fused.conv1x1_unit_bf16)
             return self._forward_fused(x)
         if self.branch1 is None:
             x1, x2 = x.chunk(2, dim=1)
@@ -746,29 +731,23 @@ def _conv5_forward(net, x):
     ``conv5`` routes itself, unit by unit.  The GEMM's epilogue applies a ReLU, or a LeakyReLU where ``fused.UNIT_LEAKY`` is on (outside
     autocast); with the switch off a LeakyReLU ``conv5`` stays with torch.  The module between the two must be the ``Identity`` that
     folding leaves: a ``GroupNorm`` there runs -- with ``fused.GN`` on behind the GEMM without an activation (``_norm_act``), else
-    with torch's ``conv5``.  A bfloat16 ``conv5`` (ReLU or, with ``fused.UNIT_LEAKY``, LeakyReLU behind an ``Identity``) goes through the bf16
-    GEMM's unit mode where ``fused.UNIT_BF16`` is on and ``fused.unit_conv_bf16_supported``: no table entry, no timing."""
+    with torch's ``conv5``.  A bfloat16 ``conv5`` (ReLU or, with ``fused.UNIT_LEAKY``, LeakyReLU behind an ``Identity``) takes the same
+    branch where ``fused.UNIT_BF16`` is on -- ``fused.unit_conv_supported`` goes by ``x``'s dtype -- and runs: no table entry, no timing
+    (``fused.pick_unit``); a group norm is float32's alone."""
     conv = net.conv5[0]
-    if (net.fused and x.is_cuda and x.dtype == torch.bfloat16 and isinstance(conv, nn.Conv2d) and isinstance(net.conv5[1], nn.Identity)
-            and fused.unit_conv_bf16_supported(conv, x)):
-        nonlin = net.conv5[2]
-        if isinstance(nonlin, nn.ReLU):
-            return fused.conv1x1_unit_bf16(conv, x)
-        if isinstance(nonlin, nn.LeakyReLU) and fused.UNIT_LEAKY:
-            return fused.conv1x1_unit_bf16(conv, x, act=fused.ACT_LEAKY_RELU, act_param=nonlin.negative_slope)
-    if net.fused and x.is_cuda and isinstance(conv, nn.Conv2d) and fused.unit_conv_x3_supported(conv, x):
-        nonlin, act = net.conv5[2], None
-        if not isinstance(net.conv5[1], nn.Identity):
-            if fused.GN and isinstance(net.conv5[1], nn.GroupNorm) and x.dtype == torch.float32 and not torch.is_autocast_enabled():
-                return _norm_act(net.conv5[1], nonlin, fused.conv1x1_unit_x3(conv, x, act=fused.ACT_NONE))
+    if net.fused and x.is_cuda and isinstance(conv, nn.Conv2d) and fused.unit_conv_supported(conv, x):
+        norm, nonlin, act = net.conv5[1], net.conv5[2], None
+        if not isinstance(norm, nn.Identity):
+            if fused.GN and isinstance(norm, nn.GroupNorm) and x.dtype == torch.float32 and not torch.is_autocast_enabled():
+                return _norm_act(norm, nonlin, fused.conv1x1_unit(conv, x, act=fused.ACT_NONE))
             return net.conv5(x)
         if isinstance(nonlin, nn.ReLU):
             act = {}
         elif isinstance(nonlin, nn.LeakyReLU) and fused.UNIT_LEAKY and not torch.is_autocast_enabled():
             act = dict(act=fused.ACT_LEAKY_RELU, act_param=nonlin.negative_slope)
         if act is not None:
-            return fused.pick('unit', fused.out_pixels(x), conv.in_channels, conv.out_channels, False, False,
-                              lambda: fused.conv1x1_unit_x3(conv, x, **act), lambda: net.conv5(x), timing=False)
+            return fused.pick_unit(x, fused.out_pixels(x), conv.in_channels, conv.out_channels, False,
+                                   lambda: fused.conv1x1_unit(conv, x, **act), lambda: net.conv5(x))
     return net.conv5(x)
 
 
@@ -876,9 +855,9 @@ class _InvertedResidual(nn.Module):
         if se is not None and not (fused._se_convs_ok(se.fc1, se.fc2) and se.fc1.weight.device == x.device
                                    and x.shape[0] <= 65535 and pixels <= fused.SE_MAX_PIXELS and fused._lib.available()):
             return False
-        if not (project.bias is not None and fused._unit_conv_ok(project) and project.weight.device == x.device):
+        if not (project.bias is not None and fused._unit_conv_ok(fused.UNIT_MODE_X3, project) and project.weight.device == x.device):
             return False
-        return not self.use_res_connect or fused._unit_operand_ok(x, project.out_channels)
+        return not self.use_res_connect or fused._unit_operand_ok(fused.UNIT_MODE_X3, x, project.out_channels)
 
     def _forward_unit(self, x):
         """Two to six launches: [GEMM + bias + activation,] the depthwise stencil + bias + activation, [the SE pool, its gate, the
@@ -1153,16 +1132,13 @@ class CompositeField4(nn.Module):
             conv, x0 = self.conv, x                                                # the split-operand GEMM where that is faster
             x = fused.pick('head', fused.out_pixels(x0), conv.in_channels, conv.out_channels, False, False,
                            lambda: fused.head_conv_x3(conv, x0), lambda: conv(x0))
-        elif not self.training and self.conv.in_channels % 64 != 0 and fused.X3_HEAD and fused.unit_conv_x3_supported(self.conv, x):
-            # input channels that are no multiple of 64 (k16: 1392): the unit mode of the same kernel, N tail native (no padded
-            # pitch, no copy-out), decided like the units: the table, else by size, never timed
+        elif not self.training and self.conv.in_channels % 64 != 0 and fused.unit_conv_supported(self.conv, x, head=True):
+            # input channels that are no multiple of 64 (k16: 1392): the unit mode of x's dtype.  float32: the same kernel, N tail native
+            # (no padded pitch, no copy-out), decided like the units -- the table, else by size, never timed; bfloat16 (behind
+            # fused.UNIT_BF16): where it is supported it runs
             conv, x0 = self.conv, x
-            x = fused.pick('unit', fused.out_pixels(x0), conv.in_channels, conv.out_channels, False, False,
-                           lambda: fused.conv1x1_unit_x3(conv, x0, relu=False), lambda: conv(x0), timing=False)
-        elif (not self.training and self.conv.in_channels % 64 != 0 and x.dtype == torch.bfloat16
-              and fused.unit_conv_bf16_supported(self.conv, x)):
-            # a bfloat16 head whose input channels are no multiple of 64 (k16: 1392): the bf16 GEMM's unit mode behind fused.UNIT_BF16
-            x = fused.conv1x1_unit_bf16(self.conv, x, relu=False)
+            x = fused.pick_unit(x0, fused.out_pixels(x0), conv.in_channels, conv.out_channels, False,
+                                lambda: fused.conv1x1_unit(conv, x0, relu=False), lambda: conv(x0))
         else:
             x = self.conv(x)
         if self.fused_epilogue and fused.head_epilogue_supported(x, self.meta, self.training):

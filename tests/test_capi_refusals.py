@@ -1,6 +1,7 @@
 """Every status and message with which the trunk's C entry points (``csrc/capi_trunk.hip``: ``opa_bias_act`` ... ``opa_head_epilogue``
 and ``opa_se_workspace_bytes``) answer a call they do not launch, against ``golden/capi_refusals.json``
-(``golden/make_golden_capi_refusals.py``; written from the commit before the entry points moved into their own file).
+(``golden/make_golden_abi.py capi_refusals``; written from the commit before the entry points moved into their own file), on the
+harness of ``abi_tables.py``.
 
 Per entry point one valid base call with fake pointers, and rows that each change one argument -- or two, where the point is the
 ORDER of the checks (which message wins), a pointer the entry point does not test, or a bound's accepting side.  A row is of one of
@@ -18,54 +19,14 @@ have a single check and test no alignment: their pointers appear as null only). 
 sees no GPU and says so (``opa_device_count() == 0``) before its first row: a check that a later change drops meets "no device"
 there, not a fake pointer on a card.
 """
-import importlib.util
 import json
-import os
-import subprocess
-import sys
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-GOLDEN = os.path.join(HERE, 'golden', 'capi_refusals.json')
-LIB_PY = os.path.join(os.path.dirname(HERE), 'openpifpaf_amd', '_lib.py')
-HIDE_GPUS = {'HIP_VISIBLE_DEVICES': '-1', 'ROCR_VISIBLE_DEVICES': '-1'}
-P = 4096                                          # a fake device pointer (never dereferenced on the host)
-OPA_ERR_HIP = 2
+import abi_tables as at
+
+P, I31, Entry = at.P, at.I31, at.Entry
+GOLDEN = at.golden('capi_refusals')
 ENTRY_POINTS = 23
-I31 = 2 ** 31
-
-
-class Entry:
-    def __init__(self, table, symbol, tag='', **base):
-        self.table, self.symbol, self.tag, self.base = table, symbol, tag, base
-
-    def row(self, kind, **change):
-        assert set(change) <= set(self.base), (self.symbol, change)
-        args = [dict(self.base, **change)[k] for k in self.base]
-        if self.symbol != 'opa_se_workspace_bytes':
-            args.append(None)                                                            # the stream
-        row_id = '%s%s(%s)' % (self.symbol, self.tag, ', '.join('%s=%s' % (k, 'null' if v is None else 'P+%d' % (v - P) if P < v < P + 16 else v)
-                                                    for k, v in change.items()))
-        assert row_id not in self.table, row_id
-        self.table[row_id] = (kind, self.symbol, args)
-
-    def refused(self, *changes, **also):
-        for change in changes:
-            self.row('refused', **dict(change, **also))
-
-    def empty(self, *changes, **also):
-        for change in changes:
-            self.row('empty', **dict(change, **also))
-
-    def each(self, names, values, **also):
-        """Refused: every argument of ``names`` (one name or several) at every value of ``values``, one at a time."""
-        for name in names.split():
-            self.refused(*[{name: v} for v in values], **also)
-
-    def null(self, names, **also):
-        self.each(names, [None], **also)
-
-    def off(self, names, by=(4, 8), **also):
-        self.each(names, [P + d for d in by], **also)
+STATUSES = {1, at.OPA_ERR_WORKSPACE}              # of a refused row: OPA_ERR_INVALID_ARGUMENT; a workspace too small (squeeze-excite)
 
 
 def table():
@@ -233,55 +194,17 @@ def canonical(symbol, message):
     return 'opa_dwconv_act: ' + message[len(old):] if symbol == 'opa_dwconv_act' and message.startswith(old) else message
 
 
-def run_table(lib):
-    """-> {row id: [status, message]} (``size`` rows: [the size, '']; the message of an OPA_OK is not read: success leaves it)."""
-    out = {}
-    for row_id, (kind, symbol, args) in table().items():
-        status = getattr(lib, symbol)(*args)
-        out[row_id] = [status, canonical(symbol, lib.opa_last_error().decode()) if status != 0 and kind != 'size' else '']
-    return out
-
-
-def child():
-    spec = importlib.util.spec_from_file_location('opa_lib', LIB_PY)                      # (the binding alone: no torch in this process)
-    _lib = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(_lib)
-    lib = _lib.lib()
-    if lib.opa_device_count() != 0:
-        sys.exit('refusal table: %d GPU(s) visible with %r: not run' % (lib.opa_device_count(), HIDE_GPUS))
-    json.dump(run_table(lib), sys.stdout)
-
-
-def run_in_child():
-    proc = subprocess.run([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, **HIDE_GPUS), capture_output=True, text=True,
-                          timeout=300)
-    assert proc.returncode == 0, (proc.stdout[-2000:], proc.stderr[-2000:])
-    return json.loads(proc.stdout)
-
-
-def check_kinds(got):
-    """What the table promises of its own rows, whatever the golden file says."""
-    rows = table()
-    assert len({symbol for _, symbol, _ in rows.values()}) == ENTRY_POINTS
-    for row_id, (kind, symbol, _) in rows.items():
-        status, message = got[row_id]
-        if kind == 'refused':
-            assert status not in (0, OPA_ERR_HIP) and message.startswith(symbol + ': '), (row_id, status, message)
-        elif kind == 'empty':
-            assert status == 0, (row_id, status, message)
-        elif kind == 'variant':
-            assert status == OPA_ERR_HIP and message.endswith(': invalid argument'), (row_id, status, message)
+def refusals():
+    """The table run and checked -> what the golden file holds"""
+    return at.refusals(__file__, table(), STATUSES)
 
 
 def test_refusals_match_the_golden_table():
-    got = run_in_child()
-    check_kinds(got)
+    got = refusals()
+    assert len({symbol for _, symbol, _ in table().values()}) == ENTRY_POINTS
     with open(GOLDEN) as f:
-        want = json.load(f)['rows']
-    assert sorted(got) == sorted(want)
-    different = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
-    assert not different, different
+        at.assert_same(got['rows'], json.load(f)['rows'])
 
 
 if __name__ == '__main__':
-    child()
+    at.child(table(), canonical)

@@ -1,23 +1,20 @@
 """Every status and message with which ``opa_gemm_unit_actp_f32x3`` and ``opa_dwconv_actp`` (``csrc/capi_trunk.hip``: the unit-mode GEMM
 and the depthwise stencil with the activation codes that take a parameter, 3 LeakyReLU(slope) and 4 clipped ReLU(cap)) answer a call
-they do not launch, against ``golden/capi_refusals_actp.json`` (``golden/make_golden_capi_refusals_actp.py``).
+they do not launch, against ``golden/capi_refusals_actp.json`` (``golden/make_golden_abi.py capi_refusals_actp``).
 
-The table is built and run like ``test_capi_refusals.py``'s, whose ``Entry``, kinds and child process it uses: per entry point one
-valid base call with fake pointers, rows that each change one argument (or two, where the point is the ORDER of the checks), in one
+The table is built and run like ``test_capi_refusals.py``'s, on the harness of ``abi_tables.py`` (``Entry``, the kinds, the child
+process): per entry point one valid base call with fake pointers, rows that each change one argument (or two, where the point is the ORDER of the checks), in one
 fresh child process that sees no GPU.  What is new here: the parameter (NaN, +-Inf, a negative slope, a cap of zero or below), a
 residual together with the codes 3 and 4, code 3 at the stencil -- and that the older entry points still refuse the new codes."""
 import json
-import os
-import subprocess
-import sys
 
-import test_capi_refusals as tcr
+import abi_tables as at
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-GOLDEN = os.path.join(HERE, 'golden', 'capi_refusals_actp.json')
-P, I31 = tcr.P, tcr.I31
+GOLDEN = at.golden('capi_refusals_actp')
+P, I31 = at.P, at.I31
 NAN, INF = float('nan'), float('inf')
 ENTRY_POINTS = 5
+STATUSES = {1}                                    # of a refused row: OPA_ERR_INVALID_ARGUMENT
 
 
 def table():
@@ -27,7 +24,7 @@ def table():
 
     base = dict(a=P, a_pitch=64, w3=P, bias=P, partner=P, partner_pitch=64, residual=None, residual_pitch=0, out=P, m=128, n=64, k=64,
                 act=3, act_param=0.01, terms=6)
-    e = tcr.Entry(t, 'opa_gemm_unit_actp_f32x3', **base)
+    e = at.Entry(t, 'opa_gemm_unit_actp_f32x3', **base)
     e.null('a w3 bias out'); e.off('w3 bias out'); e.off('a partner', by=[4])
     e.empty(dict(m=0), dict(m=0, a=P + 8), dict(m=0, partner=P + 8), dict(m=0, partner=None), dict(m=0, partner=None, partner_pitch=63),
             dict(m=0, a_pitch=2 ** 21), dict(m=0, partner_pitch=I31 - 2), dict(m=0, terms=9))
@@ -46,14 +43,14 @@ def table():
     e.refused(dict(act=5, act_param=NAN), dict(act_param=NAN, residual=P, residual_pitch=64), dict(act_param=-0.01, n=63),
               dict(residual=P, residual_pitch=64), dict(residual=P, residual_pitch=64, m=0), dict(terms=7, n=63), dict(n=63, a_pitch=63),
               dict(a_pitch=63, a=P + 4), dict(a=P + 4, m=0), dict(bias=P + 4, m=0))
-    r = tcr.Entry(t, 'opa_gemm_unit_actp_f32x3', '[residual]', **dict(base, partner=None, partner_pitch=0, residual=P, residual_pitch=64, act=0,
+    r = at.Entry(t, 'opa_gemm_unit_actp_f32x3', '[residual]', **dict(base, partner=None, partner_pitch=0, residual=P, residual_pitch=64, act=0,
                                                                       act_param=0.0))
     r.each('act', [3, 4], act_param=1.0)
     r.refused(dict(act=3, act_param=0.01, m=0), dict(act=4, act_param=6.0, m=0), dict(act=4, act_param=6.0, n=63), dict(act=4, act_param=0.0))
     r.off('residual', by=[4]); r.each('residual_pitch', [-1, 62, 63, 65, I31])
     r.empty(dict(m=0), dict(m=0, act=1), dict(m=0, act=2), dict(m=0, residual=P + 8), dict(m=0, residual_pitch=I31 - 2))
 
-    e = tcr.Entry(t, 'opa_dwconv_actp', x=P, x_pixel_stride=64, w=P, bias=P, out=P, out_pixel_stride=64, batch=1, h=8, width=8, channels=64, k=3,
+    e = at.Entry(t, 'opa_dwconv_actp', x=P, x_pixel_stride=64, w=P, bias=P, out=P, out_pixel_stride=64, batch=1, h=8, width=8, channels=64, k=3,
                   stride=1, dilation=1, dtype=0, act=4, act_param=6.0)
     rows = dict(batch=8192)                                                          # 65536 output rows: one too many
     e.null('x w out'); e.off('x w bias out', **rows); e.null('bias', **rows)         # (no alignment is tested, the bias may be null)
@@ -69,62 +66,26 @@ def table():
     e.refused(dict(act=3, act_param=NAN), dict(act_param=NAN, x=None), dict(act_param=0.0, x=None), dict(act_param=1.5, x=None))
 
     # the older entry points keep their ranges: the new codes are refused there, with the words they have always used
-    e = tcr.Entry(t, 'opa_gemm_unit_act_f32x3', a=P, a_pitch=64, w3=P, bias=P, partner=P, partner_pitch=64, residual=None, residual_pitch=0, out=P,
+    e = at.Entry(t, 'opa_gemm_unit_act_f32x3', a=P, a_pitch=64, w3=P, bias=P, partner=P, partner_pitch=64, residual=None, residual_pitch=0, out=P,
                   m=128, n=64, k=64, act=1, terms=6)
     e.each('act', [3, 4, 5]); e.refused(dict(act=4, m=0), dict(act=4, partner=None, residual=P, residual_pitch=64))
     for symbol, dilated in (('opa_dwconv_act', {}), ('opa_dwconv_dilated_act', dict(dilation=1))):
-        e = tcr.Entry(t, symbol, x=P, x_pixel_stride=64, w=P, bias=P, out=P, out_pixel_stride=64, batch=1, h=8, width=8, channels=64, k=3, stride=1,
+        e = at.Entry(t, symbol, x=P, x_pixel_stride=64, w=P, bias=P, out=P, out_pixel_stride=64, batch=1, h=8, width=8, channels=64, k=3, stride=1,
                       **dilated, dtype=0, act=1)
         e.each('act', [3, 4, 5]); e.refused(dict(act=4, x=None))
     return t
 
 
-def run_table(lib):
-    out = {}
-    for row_id, (kind, symbol, args) in table().items():
-        status = getattr(lib, symbol)(*args)
-        out[row_id] = [status, lib.opa_last_error().decode() if status != 0 else '']
-    return out
-
-
-def child():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location('opa_lib', tcr.LIB_PY)                  # (the binding alone: no torch in this process)
-    _lib = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(_lib)
-    lib = _lib.lib()
-    if lib.opa_device_count() != 0:
-        sys.exit('refusal table: %d GPU(s) visible with %r: not run' % (lib.opa_device_count(), tcr.HIDE_GPUS))
-    json.dump(run_table(lib), sys.stdout)
-
-
-def run_in_child():
-    proc = subprocess.run([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, **tcr.HIDE_GPUS), capture_output=True, text=True,
-                          timeout=300)                                                    # (the script's directory leads its sys.path)
-    assert proc.returncode == 0, (proc.stdout[-2000:], proc.stderr[-2000:])
-    return json.loads(proc.stdout)
-
-
-def check_kinds(got):
-    """What the table promises of its own rows, whatever the golden file says: no row reaches a launcher."""
-    rows = table()
-    assert len({symbol for _, symbol, _ in rows.values()}) == ENTRY_POINTS
-    for row_id, (kind, symbol, _) in rows.items():
-        status, message = got[row_id]
-        if kind == 'refused':
-            assert status not in (0, tcr.OPA_ERR_HIP) and message.startswith(symbol + ': '), (row_id, status, message)
-        else:
-            assert kind == 'empty' and status == 0, (row_id, status, message)
+def refusals():
+    """The table run and checked -> what the golden file holds"""
+    return at.refusals(__file__, table(), STATUSES)
 
 
 def test_refusals_match_the_golden_table():
-    got = run_in_child()
-    check_kinds(got)
+    got = refusals()
+    assert len({symbol for _, symbol, _ in table().values()}) == ENTRY_POINTS
     with open(GOLDEN) as f:
-        want = json.load(f)['rows']
-    assert sorted(got) == sorted(want)
-    different = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
-    assert not different, different
+        at.assert_same(got['rows'], json.load(f)['rows'])
 
 
 def test_the_refusals_name_what_is_wrong():
@@ -143,4 +104,4 @@ def test_the_refusals_name_what_is_wrong():
 
 
 if __name__ == '__main__':
-    child()
+    at.child(table())

@@ -1,6 +1,6 @@
 """Every status and message with which ``opa_groupnorm_actp`` (``csrc/capi_trunk.hip``: group norm + activation of a ShuffleNetV2K built
 with ``--shufflenetv2k-group-norm``, ``csrc/groupnorm.hip``) answers a call it does not launch, against
-``golden/capi_refusals_groupnorm.json`` (``golden/make_golden_capi_refusals_groupnorm.py``).
+``golden/capi_refusals_groupnorm.json`` (``golden/make_golden_abi.py capi_refusals_groupnorm``).
 
 The table is built and run like ``test_capi_refusals_stem.py``'s: one valid base call with fake pointers, rows that each change one
 argument (or two, where the point is the ORDER of the checks), in one fresh child process that sees no GPU.  A refusing row has status
@@ -10,18 +10,15 @@ The documented order (``include/openpifpaf_amd.h``): NULL, alignment, sizes, ``c
 strides, ``eps``, ``act``, ``act_param``, in place with unequal strides -- the empty batch's ``OPA_OK`` -- the grid and index limits,
 the workspace."""
 import json
-import os
-import subprocess
-import sys
 
-import test_capi_refusals as tcr
+import abi_tables as at
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-GOLDEN = os.path.join(HERE, 'golden', 'capi_refusals_groupnorm.json')
-P, I31 = tcr.P, tcr.I31
+GOLDEN = at.golden('capi_refusals_groupnorm')
+P, I31 = at.P, at.I31
 NAN, INF = float('nan'), float('inf')
 SYMBOL = 'opa_groupnorm_actp'
 OPA_ERR_INVALID_ARGUMENT, OPA_ERR_WORKSPACE = 1, 4
+STATUSES = {OPA_ERR_INVALID_ARGUMENT}                # of a refused row; a ``workspace`` row: OPA_ERR_WORKSPACE (``at.check_kinds``)
 CHUNK = 512
 
 
@@ -35,7 +32,7 @@ def table():
     """-> {row id: (kind, symbol, arguments)}"""
     t = {}
     # [2, 63, 24] in 4 groups, out of place, LeakyReLU
-    e = tcr.Entry(t, SYMBOL, x=P, x_pixel_stride=24, gamma=P, beta=P, out=2 * P, out_pixel_stride=24, batch=2, pixels=63, channels=24,
+    e = at.Entry(t, SYMBOL, x=P, x_pixel_stride=24, gamma=P, beta=P, out=2 * P, out_pixel_stride=24, batch=2, pixels=63, channels=24,
                   groups=4, eps=1e-5, act=3, act_param=0.01, workspace=3 * P, workspace_bytes=need(2, 63, 24))
     e.null('x out'); e.off('x out', by=[4, 12]); e.off('gamma beta', by=[1, 2, 3]); e.off('workspace', by=[4, 8])
     e.each('batch', [-1]); e.each('pixels channels groups', [-1, 0])
@@ -86,64 +83,25 @@ def table():
     return t
 
 
-def run_table(lib):
-    out = {}
-    for row_id, (kind, symbol, args) in table().items():
-        status = getattr(lib, symbol)(*args)
-        out[row_id] = [status, lib.opa_last_error().decode() if status != 0 else '']
-    return out
-
-
-def child():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location('opa_lib', tcr.LIB_PY)                  # (the binding alone: no torch in this process)
-    _lib = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(_lib)
-    lib = _lib.lib()
-    if lib.opa_device_count() != 0:
-        sys.exit('refusal table: %d GPU(s) visible with %r: not run' % (lib.opa_device_count(), tcr.HIDE_GPUS))
-    sizes = {'%d,%d,%d' % a: lib.opa_groupnorm_workspace_bytes(*a) for a in SIZES}
-    json.dump({'rows': run_table(lib), 'sizes': sizes}, sys.stdout)
-
-
 # opa_groupnorm_workspace_bytes: (batch, pixels, channels)
 SIZES = [(2, 63, 24), (1, 512, 8), (1, 513, 8), (32, 321 * 321, 24), (3, 1, 2048), (0, 5, 8), (-1, 5, 8), (1, 0, 8), (1, -1, 8), (1, 5, 0), (1, 5, -2)]
 
 
-def run_in_child():
-    proc = subprocess.run([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, **tcr.HIDE_GPUS), capture_output=True, text=True,
-                          timeout=300)                                                    # (the script's directory leads its sys.path)
-    assert proc.returncode == 0, (proc.stdout[-2000:], proc.stderr[-2000:])
-    return json.loads(proc.stdout)
-
-
-def check_kinds(got):
-    """What the table promises of its own rows, whatever the golden file says: no row reaches the launcher, every refusal is
-    OPA_ERR_INVALID_ARGUMENT -- OPA_ERR_WORKSPACE for the workspace -- under the entry point's name; the sizes are ``need``'s."""
-    rows = table()
-    assert {symbol for _, symbol, _ in rows.values()} == {SYMBOL}
-    for row_id, (kind, symbol, _) in rows.items():
-        status, message = got['rows'][row_id]
-        if kind == 'refused':
-            assert status == OPA_ERR_INVALID_ARGUMENT and message.startswith(symbol + ': '), (row_id, status, message)
-        elif kind == 'workspace':
-            assert status == OPA_ERR_WORKSPACE and message.startswith(symbol + ': '), (row_id, status, message)
-        else:
-            assert kind == 'empty' and status == 0, (row_id, status, message)
+def refusals():
+    """The table run and checked, and the sizes ``need``'s -> what the golden file holds"""
+    got = at.refusals(__file__, table(), STATUSES)
     for a in SIZES:
         assert got['sizes']['%d,%d,%d' % a] == (need(*a) if min(a) > 0 else 0), a
+    return got
 
 
 def test_refusals_match_the_golden_table():
-    got = run_in_child()
-    check_kinds(got)
+    got = refusals()
+    assert {symbol for _, symbol, _ in table().values()} == {SYMBOL}
     with open(GOLDEN) as f:
         want = json.load(f)
     assert got['sizes'] == want['sizes']
-    got, want = got['rows'], want['rows']
-    assert sorted(got) == sorted(want)
-    different = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
-    assert not different, different
+    at.assert_same(got['rows'], want['rows'])
 
 
 def test_the_refusals_name_what_is_wrong():
@@ -174,4 +132,4 @@ def test_the_refusals_name_what_is_wrong():
 
 
 if __name__ == '__main__':
-    child()
+    at.child(table(), also=lambda lib: {'sizes': {'%d,%d,%d' % a: lib.opa_groupnorm_workspace_bytes(*a) for a in SIZES}})

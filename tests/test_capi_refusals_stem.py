@@ -1,30 +1,27 @@
 """Every status and message with which ``opa_stem3x3_actp`` (``csrc/capi_trunk.hip``: the 3x3 RGB stem of the non-ResNet backbones,
 ``csrc/stem.hip``) answers a call it does not launch, against ``golden/capi_refusals_stem.json``
-(``golden/make_golden_capi_refusals_stem.py``).
+(``golden/make_golden_abi.py capi_refusals_stem``).
 
-The table is built and run like ``test_capi_refusals.py``'s, whose ``Entry``, kinds and child process it uses: one valid base call
-with fake pointers, rows that each change one argument (or two, where the point is the ORDER of the checks), in one fresh child
+The table is built and run like ``test_capi_refusals.py``'s, on the harness of ``abi_tables.py`` (``Entry``, the kinds, the child
+process): one valid base call with fake pointers, rows that each change one argument (or two, where the point is the ORDER of the checks), in one fresh child
 process that sees no GPU.  A refusing row has status 1 (``OPA_ERR_INVALID_ARGUMENT``) in the table itself; the JSON pins the messages."""
 import json
-import os
-import subprocess
-import sys
 
-import test_capi_refusals as tcr
+import abi_tables as at
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-GOLDEN = os.path.join(HERE, 'golden', 'capi_refusals_stem.json')
-P, I31 = tcr.P, tcr.I31
+GOLDEN = at.golden('capi_refusals_stem')
+P, I31 = at.P, at.I31
 NAN, INF = float('nan'), float('inf')
 SYMBOL = 'opa_stem3x3_actp'
 OPA_ERR_INVALID_ARGUMENT = 1
+STATUSES = {OPA_ERR_INVALID_ARGUMENT}                # of a refused row
 
 
 def table():
     """-> {row id: (kind, symbol, arguments)}"""
     t = {}
     # a channels-last [2, 3, 9, 7] input: strides 189, 1, 21, 3
-    e = tcr.Entry(t, SYMBOL, x=P, x_batch_stride=189, x_channel_stride=1, x_row_stride=21, x_pixel_stride=3, w=P, bias=P, out=P, batch=2, h=9,
+    e = at.Entry(t, SYMBOL, x=P, x_batch_stride=189, x_channel_stride=1, x_row_stride=21, x_pixel_stride=3, w=P, bias=P, out=P, batch=2, h=9,
                   width=7, channels_out=32, stride=2, act=4, act_param=6.0)
     e.null('x w out'); e.off('w bias out'); e.off('x', by=[1, 2, 3])
     e.each('batch', [-1]); e.each('h width', [-1, 0])
@@ -54,53 +51,16 @@ def table():
     return t
 
 
-def run_table(lib):
-    out = {}
-    for row_id, (kind, symbol, args) in table().items():
-        status = getattr(lib, symbol)(*args)
-        out[row_id] = [status, lib.opa_last_error().decode() if status != 0 else '']
-    return out
-
-
-def child():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location('opa_lib', tcr.LIB_PY)                  # (the binding alone: no torch in this process)
-    _lib = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(_lib)
-    lib = _lib.lib()
-    if lib.opa_device_count() != 0:
-        sys.exit('refusal table: %d GPU(s) visible with %r: not run' % (lib.opa_device_count(), tcr.HIDE_GPUS))
-    json.dump(run_table(lib), sys.stdout)
-
-
-def run_in_child():
-    proc = subprocess.run([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, **tcr.HIDE_GPUS), capture_output=True, text=True,
-                          timeout=300)                                                    # (the script's directory leads its sys.path)
-    assert proc.returncode == 0, (proc.stdout[-2000:], proc.stderr[-2000:])
-    return json.loads(proc.stdout)
-
-
-def check_kinds(got):
-    """What the table promises of its own rows, whatever the golden file says: no row reaches the launcher, every refusal is
-    OPA_ERR_INVALID_ARGUMENT under the entry point's name."""
-    rows = table()
-    assert {symbol for _, symbol, _ in rows.values()} == {SYMBOL}
-    for row_id, (kind, symbol, _) in rows.items():
-        status, message = got[row_id]
-        if kind == 'refused':
-            assert status == OPA_ERR_INVALID_ARGUMENT and message.startswith(symbol + ': '), (row_id, status, message)
-        else:
-            assert kind == 'empty' and status == 0, (row_id, status, message)
+def refusals():
+    """The table run and checked -> what the golden file holds"""
+    return at.refusals(__file__, table(), STATUSES)
 
 
 def test_refusals_match_the_golden_table():
-    got = run_in_child()
-    check_kinds(got)
+    got = refusals()
+    assert {symbol for _, symbol, _ in table().values()} == {SYMBOL}
     with open(GOLDEN) as f:
-        want = json.load(f)['rows']
-    assert sorted(got) == sorted(want)
-    different = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
-    assert not different, different
+        at.assert_same(got['rows'], json.load(f)['rows'])
 
 
 def test_the_refusals_name_what_is_wrong():
@@ -123,4 +83,4 @@ def test_the_refusals_name_what_is_wrong():
 
 
 if __name__ == '__main__':
-    child()
+    at.child(table())

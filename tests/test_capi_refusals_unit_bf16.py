@@ -1,25 +1,22 @@
 """Every status and message with which ``opa_gemm_unit_actp_bf16`` (``csrc/capi_trunk.hip``: the unit mode of the bf16 GEMM,
 ``csrc/gemm_unit_bf16.hip``) answers a call it does not launch, against ``golden/capi_refusals_unit_bf16.json``
-(``golden/make_golden_capi_refusals_unit_bf16.py``).
+(``golden/make_golden_abi.py capi_refusals_unit_bf16``).
 
-The table is built and run like ``test_capi_refusals_actp.py``'s, with ``test_capi_refusals.py``'s ``Entry``, kinds and child process:
+The table is built and run like ``test_capi_refusals_actp.py``'s, on the harness of ``abi_tables.py`` (``Entry``, the kinds, the child process):
 one valid base call with fake pointers, rows that each change one argument (or two, where the point is the ORDER of the checks), in one
 fresh child process that sees no GPU.  The checks are ``opa_gemm_unit_actp_f32x3``'s in its order and, where the rule is the same, with
 its words; what differs: no ``terms``, and the activation operands need 4 bytes, not 8 -- an offset of 4, 8 or 12 is accepted (shown by
 the empty call, which returns OPA_OK only behind every check), an offset of 2 refused."""
 import json
-import os
-import subprocess
-import sys
 
-import test_capi_refusals as tcr
+import abi_tables as at
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-GOLDEN = os.path.join(HERE, 'golden', 'capi_refusals_unit_bf16.json')
-P, I31 = tcr.P, tcr.I31
+GOLDEN = at.golden('capi_refusals_unit_bf16')
+P, I31 = at.P, at.I31
 NAN, INF = float('nan'), float('inf')
 SYMBOL = 'opa_gemm_unit_actp_bf16'
 OPA_ERR_INVALID_ARGUMENT = 1
+STATUSES = {OPA_ERR_INVALID_ARGUMENT}                # of a refused row
 
 
 def table():
@@ -27,7 +24,7 @@ def table():
     t = {}
     base = dict(a=P, a_pitch=64, w=P, bias=P, partner=P, partner_pitch=64, residual=None, residual_pitch=0, out=P, m=128, n=64, k=64,
                 act=3, act_param=0.01)
-    e = tcr.Entry(t, SYMBOL, **base)
+    e = at.Entry(t, SYMBOL, **base)
     e.null('a w bias out'); e.off('w bias out', by=[2, 4, 8]); e.off('a partner', by=[1, 2, 3, 6, 10, 14])
     # 4-byte offsets are accepted: the empty call is OPA_OK only behind every check
     e.empty(dict(m=0), dict(m=0, a=P + 4), dict(m=0, a=P + 8), dict(m=0, a=P + 12), dict(m=0, partner=P + 4), dict(m=0, partner=P + 12),
@@ -48,7 +45,7 @@ def table():
     e.refused(dict(act=5, act_param=NAN), dict(act_param=NAN, residual=P, residual_pitch=64), dict(act_param=-0.01, n=63),
               dict(residual=P, residual_pitch=64), dict(residual=P, residual_pitch=64, m=0), dict(n=63, a_pitch=63),
               dict(a_pitch=63, a=P + 2), dict(a=P + 2, m=0), dict(bias=P + 4, m=0), dict(out=P + 8, m=0), dict(w=P + 8, m=0))
-    r = tcr.Entry(t, SYMBOL, '[residual]', **dict(base, partner=None, partner_pitch=0, residual=P, residual_pitch=64, act=0, act_param=0.0))
+    r = at.Entry(t, SYMBOL, '[residual]', **dict(base, partner=None, partner_pitch=0, residual=P, residual_pitch=64, act=0, act_param=0.0))
     r.each('act', [3, 4], act_param=1.0)
     r.refused(dict(act=3, act_param=0.01, m=0), dict(act=4, act_param=6.0, m=0), dict(act=4, act_param=6.0, n=63), dict(act=4, act_param=0.0))
     r.off('residual', by=[1, 2, 3, 6]); r.each('residual_pitch', [-1, 62, 63, 65, I31])
@@ -56,52 +53,16 @@ def table():
     return t
 
 
-def run_table(lib):
-    out = {}
-    for row_id, (kind, symbol, args) in table().items():
-        status = getattr(lib, symbol)(*args)
-        out[row_id] = [status, lib.opa_last_error().decode() if status != 0 else '']
-    return out
-
-
-def child():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location('opa_lib', tcr.LIB_PY)                  # (the binding alone: no torch in this process)
-    _lib = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(_lib)
-    lib = _lib.lib()
-    if lib.opa_device_count() != 0:
-        sys.exit('refusal table: %d GPU(s) visible with %r: not run' % (lib.opa_device_count(), tcr.HIDE_GPUS))
-    json.dump(run_table(lib), sys.stdout)
-
-
-def run_in_child():
-    proc = subprocess.run([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, **tcr.HIDE_GPUS), capture_output=True, text=True,
-                          timeout=300)                                                    # (the script's directory leads its sys.path)
-    assert proc.returncode == 0, (proc.stdout[-2000:], proc.stderr[-2000:])
-    return json.loads(proc.stdout)
-
-
-def check_kinds(got):
-    """What the table promises of its own rows, whatever the golden file says: no row reaches the launcher."""
-    rows = table()
-    assert {symbol for _, symbol, _ in rows.values()} == {SYMBOL}
-    for row_id, (kind, symbol, _) in rows.items():
-        status, message = got[row_id]
-        if kind == 'refused':
-            assert status == OPA_ERR_INVALID_ARGUMENT and message.startswith(symbol + ': '), (row_id, status, message)
-        else:
-            assert kind == 'empty' and status == 0, (row_id, status, message)
+def refusals():
+    """The table run and checked -> what the golden file holds"""
+    return at.refusals(__file__, table(), STATUSES)
 
 
 def test_refusals_match_the_golden_table():
-    got = run_in_child()
-    check_kinds(got)
+    got = refusals()
+    assert {symbol for _, symbol, _ in table().values()} == {SYMBOL}
     with open(GOLDEN) as f:
-        want = json.load(f)['rows']
-    assert sorted(got) == sorted(want)
-    different = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
-    assert not different, different
+        at.assert_same(got['rows'], json.load(f)['rows'])
 
 
 def test_the_refusals_use_the_float32_unit_modes_words():
@@ -109,7 +70,7 @@ def test_the_refusals_use_the_float32_unit_modes_words():
     the alignment message names 4 bytes."""
     with open(GOLDEN) as f:
         rows = json.load(f)['rows']
-    with open(os.path.join(HERE, 'golden', 'capi_refusals_actp.json')) as f:
+    with open(at.golden('capi_refusals_actp')) as f:
         f32 = json.load(f)['rows']
     other = 'opa_gemm_unit_actp_f32x3'
     same = ['(a=null)', '(m=-1)', '(n=63)', '(k=65)', '(a_pitch=62)', '(partner_pitch=%d)' % I31, '(act=5)', '(act_param=nan)', '(act_param=-0.01)',
@@ -124,4 +85,4 @@ def test_the_refusals_use_the_float32_unit_modes_words():
 
 
 if __name__ == '__main__':
-    child()
+    at.child(table())

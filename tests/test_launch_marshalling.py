@@ -3,26 +3,24 @@ not ask where their tensors live (the ``*_supported`` predicates do), so they ru
 ``_lib.lib()`` that calls nothing and returns 0.  Per native call the symbol and every argument are recorded: an integer as it is,
 a pointer as the label of the input tensor it addresses (``x``, ``bias``, ... as the case names them; a derived operand the launcher
 keeps on the module under the names the case gives it), ``new<i>`` for the i-th tensor the launcher allocated itself, ``null``.
-``ctypes.c_void_p`` objects and plain integers are read alike.  The record is compared with ``golden/launch_marshalling.json``
-(``golden/make_golden_launch_marshalling.py``): an argument that moves, a pitch taken from the wrong tensor, an activation code
+``ctypes.c_void_p`` objects and plain integers are read alike.  Recorder, labels and comparison are ``abi_tables.py``'s; the record is
+compared with ``golden/launch_marshalling.json`` (``golden/make_golden_abi.py launch_marshalling``): an argument that moves, a pitch taken from the wrong tensor, an activation code
 that changes shows as a difference in one line.
 
 ``bias_act_`` and ``channel_interleave`` do ask ``is_cuda`` before they launch: they get a tensor subclass that answers yes."""
-import contextlib
 import ctypes
 import itertools
-import json
-import os
 
 import torch
 from torch import nn
 
-from openpifpaf_amd import _lib, fused, headmeta, winograd
+from openpifpaf_amd import fused, headmeta, winograd
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'launch_marshalling.json')
+import abi_tables as at
+
+GOLDEN = at.golden('launch_marshalling')
 CL = torch.channels_last
 F32, BF16 = torch.float32, torch.bfloat16
-STREAM = 0x7F00DEAD0040
 # every symbol fused.py and winograd.py launch (the two retired twins under the name of their superset: ``canonical``)
 SYMBOLS = {'opa_bias_act', 'opa_gemm_bias_act_bf16', 'opa_gemm_pro_bias_act_bf16', 'opa_gemm_bias_act_f32', 'opa_gemm_bias_act_f32x3',
            'opa_gemm_unit_act_f32x3', 'opa_conv_rows_f32x3', 'opa_conv3x3_f32x3', 'opa_gemm2_bias_act_f32x3', 'opa_conv3x3_winograd_f32',
@@ -32,71 +30,6 @@ SYMBOLS = {'opa_bias_act', 'opa_gemm_bias_act_bf16', 'opa_gemm_pro_bias_act_bf16
 
 class _OnDevice(torch.Tensor):
     is_cuda = True
-
-
-class Recorder:
-    """Stands in for the loaded library: every symbol of ``_lib.SYMBOLS`` is a function that records its arguments."""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        if name not in _lib.SYMBOLS:
-            raise AttributeError(name)
-
-        def call(*args):
-            self.calls.append((name, args))
-            if name == 'opa_se_workspace_bytes':                # (a size, not a status: csrc/se.hip)
-                return args[0] * ((args[1] + 511) // 512) * args[2] * 8
-            return 0
-        return call
-
-
-@contextlib.contextmanager
-def recording():
-    """-> the recorder in place of the library, a current stream with a known handle, the library reported as built."""
-    rec = Recorder()
-
-    class Stream:
-        cuda_stream = STREAM
-    saved = _lib.lib, _lib.available, torch.cuda.current_stream
-    _lib.lib, _lib.available, torch.cuda.current_stream = (lambda: rec), (lambda: True), (lambda *a: Stream())
-    try:
-        yield rec
-    finally:
-        _lib.lib, _lib.available, torch.cuda.current_stream = saved
-
-
-def canonical(name, row):
-    """``opa_gemm_unit_bias_act_f32x3`` and ``opa_dwconv_bias_act`` are the calls of ``opa_gemm_unit_act_f32x3`` without a residual
-    and of ``opa_dwconv_act`` with the activation codes 0 / 1 (``csrc/capi_trunk.hip`` forwards them literally): a record of either
-    is read as the record of its superset, so that the golden file holds ONE spelling of these launches."""
-    if name == 'opa_gemm_unit_bias_act_f32x3':
-        return ['opa_gemm_unit_act_f32x3', row[:6] + ['null', 0] + row[6:]]
-    if name == 'opa_dwconv_bias_act':
-        return ['opa_dwconv_act', row]
-    return [name, row]
-
-
-def normalise(calls, labels):
-    """[(symbol, raw arguments)] -> [[symbol, [integers and pointer labels]]]; ``labels``: {address: label}."""
-    labels = dict(labels)
-    labels[STREAM] = 'stream'
-    out = []
-    for name, args in calls:
-        argtypes = _lib.SYMBOLS[name][1]
-        assert len(args) == len(argtypes), (name, len(args), len(argtypes))
-        row = []
-        for a, ty in zip(args, argtypes):
-            a = a.value if isinstance(a, ctypes.c_void_p) else a
-            if ty is ctypes.c_void_p:
-                assert a is None or (isinstance(a, int) and a != 0), (name, a)
-                row.append('null' if a is None else labels.setdefault(a, 'new%d' % sum(1 for v in labels.values() if v.startswith('new'))))
-            else:
-                assert isinstance(a, int), (name, a)
-                row.append(int(a))
-        out.append(canonical(name, row))
-    return out
 
 
 def _act(b, c, h, w, dtype=F32):
@@ -255,38 +188,18 @@ def cases():
 
 def record_all():
     """-> {case id: [[symbol, [arguments]], ...]}"""
-    result = {}
-    saved_terms = fused.X3_TERMS
-    try:
-        with recording() as rec, torch.no_grad():
-            for case_id, (call, tensors, derived, terms) in cases().items():
-                fused.X3_TERMS = terms
-                rec.calls = []
-                kept = call()                                   # (kept: what the launcher allocated stays allocated while it is labelled)
-                labels = dict(tensors, **(derived() if derived is not None else {}))
-                addresses = {t.data_ptr(): label for label, t in labels.items()}
-                assert len(addresses) == len(labels), case_id  # (no two operands of a case at one address)
-                result[case_id] = normalise(rec.calls, addresses)
-                del kept
-    finally:
-        fused.X3_TERMS = saved_terms
-    return result
+    return at.record_all(cases())
 
 
 def test_every_launch_hands_over_what_the_golden_file_says():
-    with open(GOLDEN) as f:
-        golden = json.load(f)['cases']
-    got = record_all()
-    assert sorted(got) == sorted(golden)
-    different = {k: (got[k], golden[k]) for k in got if got[k] != golden[k]}
-    assert not different, different
+    got = at.marshalling(cases(), GOLDEN)
     assert all(calls for calls in got.values())
     assert {name for calls in got.values() for name, _ in calls} == SYMBOLS
 
 
 def test_a_pointer_is_read_alike_as_an_object_and_as_an_integer():
     t = torch.zeros(4)
-    raw = [('opa_se_scale', (ctypes.c_void_p(t.data_ptr()), 4, 1, 1, 4, None, ctypes.c_void_p(STREAM))),
-           ('opa_se_scale', (t.data_ptr(), 4, 1, 1, 4, ctypes.c_void_p(None), STREAM))]
-    a, b = normalise(raw, {t.data_ptr(): 'x'})
+    raw = [('opa_se_scale', (ctypes.c_void_p(t.data_ptr()), 4, 1, 1, 4, None, ctypes.c_void_p(at.STREAM))),
+           ('opa_se_scale', (t.data_ptr(), 4, 1, 1, 4, ctypes.c_void_p(None), at.STREAM))]
+    a, b = at.normalise(raw, {t.data_ptr(): 'x'})
     assert a == b == ['opa_se_scale', ['x', 4, 1, 1, 4, 'null', 'stream']]

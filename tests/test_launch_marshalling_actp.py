@@ -1,48 +1,24 @@
 """What ``fused.conv1x1_unit_x3`` and ``fused.dwconv_bias_act`` hand to the C ABI for the activation codes that take a parameter
 (``ACT_LEAKY_RELU``, ``ACT_RELU6``), argument by argument, without a GPU -- recorded like ``test_launch_marshalling.py`` records its
-cases (whose recorder, tensors and labels this uses) and compared with ``golden/launch_marshalling_actp.json``
-(``golden/make_golden_launch_marshalling_actp.py``).  The new codes go to ``opa_gemm_unit_actp_f32x3`` / ``opa_dwconv_actp`` with the
+cases (whose tensors and labels this uses, on the harness of ``abi_tables.py``) and compared with ``golden/launch_marshalling_actp.json``
+(``golden/make_golden_abi.py launch_marshalling_actp``).  The new codes go to ``opa_gemm_unit_actp_f32x3`` / ``opa_dwconv_actp`` with the
 parameter in its place (a float: recorded as it is); one case each with code 1 shows that every other code still goes to the symbol it
 has always gone to, parameter or not."""
 import ctypes
 import itertools
-import json
 import os
 
 import torch
 from torch import nn
 
-from openpifpaf_amd import _lib, fused
+from openpifpaf_amd import fused
 
+import abi_tables as at
 import test_launch_marshalling as tlm
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'launch_marshalling_actp.json')
+GOLDEN = at.golden('launch_marshalling_actp')
 F32, BF16 = torch.float32, torch.bfloat16
 SYMBOLS = {'opa_gemm_unit_actp_f32x3', 'opa_dwconv_actp', 'opa_gemm_unit_act_f32x3', 'opa_dwconv_act', 'opa_dwconv_dilated_act'}
-
-
-def normalise(calls, labels):
-    """``tlm.normalise`` with a float argument (``ctypes.c_float``) recorded as the float32 the library receives."""
-    labels = dict(labels)
-    labels[tlm.STREAM] = 'stream'
-    out = []
-    for name, args in calls:
-        argtypes = _lib.SYMBOLS[name][1]
-        assert len(args) == len(argtypes), (name, len(args), len(argtypes))
-        row = []
-        for a, ty in zip(args, argtypes):
-            a = a.value if isinstance(a, ctypes.c_void_p) else a
-            if ty is ctypes.c_void_p:
-                assert a is None or (isinstance(a, int) and a != 0), (name, a)
-                row.append('null' if a is None else labels.setdefault(a, 'new%d' % sum(1 for v in labels.values() if v.startswith('new'))))
-            elif ty is ctypes.c_float:
-                assert isinstance(a, float), (name, a)
-                row.append(ctypes.c_float(a).value)
-            else:
-                assert isinstance(a, int), (name, a)
-                row.append(int(a))
-        out.append([name, row])
-    return out
 
 
 def cases():
@@ -90,31 +66,11 @@ def cases():
 
 def record_all():
     """-> {case id: [[symbol, [arguments]], ...]}"""
-    result = {}
-    saved_terms = fused.X3_TERMS
-    try:
-        with tlm.recording() as rec, torch.no_grad():
-            for case_id, (call, tensors, derived, terms) in cases().items():
-                fused.X3_TERMS = terms
-                rec.calls = []
-                kept = call()
-                labels = dict(tensors, **(derived() if derived is not None else {}))
-                addresses = {t.data_ptr(): label for label, t in labels.items()}
-                assert len(addresses) == len(labels), case_id
-                result[case_id] = normalise(rec.calls, addresses)
-                del kept
-    finally:
-        fused.X3_TERMS = saved_terms
-    return result
+    return at.record_all(cases())
 
 
 def test_every_launch_hands_over_what_the_golden_file_says():
-    with open(GOLDEN) as f:
-        golden = json.load(f)['cases']
-    got = record_all()
-    assert sorted(got) == sorted(golden)
-    different = {k: (got[k], golden[k]) for k in got if got[k] != golden[k]}
-    assert not different, different
+    got = at.marshalling(cases(), GOLDEN)
     assert all(len(calls) == 1 for calls in got.values())
     assert {name for calls in got.values() for name, _ in calls} == SYMBOLS
 

@@ -1,23 +1,19 @@
 """What ``fused.group_norm_act`` hands to the C ABI (``opa_groupnorm_workspace_bytes``, ``opa_groupnorm_actp``), argument by argument,
-without a GPU -- recorded like ``test_launch_marshalling.py`` records its cases (whose recorder this uses; floats as
-``test_launch_marshalling_actp.normalise`` reads them) and compared with ``golden/launch_marshalling_groupnorm.json``
-(``golden/make_golden_launch_marshalling_groupnorm.py``).
+without a GPU -- recorded like ``test_launch_marshalling.py`` records its cases (on the harness of ``abi_tables.py``) and compared with ``golden/launch_marshalling_groupnorm.json``
+(``golden/make_golden_abi.py launch_marshalling_groupnorm``).
 
 Operands: a dense channels-last tensor and the upper channel half of a tensor of twice the channels; out of place (a new dense
 tensor), in place (``out`` is ``x``: the same pointer, the same pitch) and into a slice; with and without affine terms; each
 activation.  The pitches handed over must be the VIEWS' own and the pointers their first elements: the launcher makes no copy."""
-import json
-import os
-
 import torch
 from torch import nn
 
 from openpifpaf_amd import fused
 
+import abi_tables as at
 import test_launch_marshalling as tlm
-import test_launch_marshalling_actp as tlma
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'launch_marshalling_groupnorm.json')
+GOLDEN = at.golden('launch_marshalling_groupnorm')
 CL = torch.channels_last
 ACTS = {'none': (fused.ACT_NONE, 0.0), 'relu': (fused.ACT_RELU, 0.0), 'hardswish': (fused.ACT_HARDSWISH, 0.0),
         'leaky0.01': (fused.ACT_LEAKY_RELU, 0.01), 'relu6': (fused.ACT_RELU6, 6.0)}
@@ -63,30 +59,23 @@ def cases():
     return out
 
 
-def record_all():
-    """-> {case id: [[symbol, [arguments]], ...]}"""
-    result = {}
-    with tlm.recording() as rec, torch.no_grad():
-        rec.opa_groupnorm_workspace_bytes = lambda b, p, c: rec.calls.append(('opa_groupnorm_workspace_bytes', (b, p, c))) or workspace_bytes(b, p, c)
-        for case_id, (call, tensors) in cases().items():
-            rec.calls = []
-            fused._GN_WORKSPACE.clear()                               # (every case allocates its workspace: ``new0``)
-            kept = call()
-            addresses = {t.data_ptr(): label for label, t in tensors.items()}
-            assert len(addresses) == len(tensors), case_id
-            result[case_id] = tlma.normalise(rec.calls, addresses)
-            del kept
+def _before(rec):
+    """The size query recorded and answered (``opa_groupnorm_workspace_bytes`` returns a size, not a status); every case allocates its
+    workspace: ``new0``."""
+    rec.opa_groupnorm_workspace_bytes = lambda b, p, c: rec.calls.append(('opa_groupnorm_workspace_bytes', (b, p, c))) or workspace_bytes(b, p, c)
+    fused._GN_WORKSPACE.clear()
+
+
+def record_all(golden=None):
+    """-> {case id: [[symbol, [arguments]], ...]}, compared with the file ``golden`` where one is given"""
+    try:
+        return at.record_all(cases(), before=_before) if golden is None else at.marshalling(cases(), golden, before=_before)
+    finally:
         fused._GN_WORKSPACE.clear()
-    return result
 
 
 def test_every_launch_hands_over_what_the_golden_file_says():
-    with open(GOLDEN) as f:
-        golden = json.load(f)['cases']
-    got = record_all()
-    assert sorted(got) == sorted(golden)
-    different = {k: (got[k], golden[k]) for k in got if got[k] != golden[k]}
-    assert not different, different
+    got = record_all(GOLDEN)
     assert all([name for name, _ in calls] == ['opa_groupnorm_workspace_bytes', 'opa_groupnorm_actp'] for calls in got.values())
 
 
@@ -110,7 +99,7 @@ def test_the_pitches_are_the_views_and_nothing_is_copied():
 
 
 def test_the_output_and_the_workspace():
-    with tlm.recording() as rec, torch.no_grad():
+    with at.recording() as rec, torch.no_grad():
         rec.opa_groupnorm_workspace_bytes = lambda b, p, c: workspace_bytes(b, p, c)
         fused._GN_WORKSPACE.clear()
         norm = nn.GroupNorm(29, 174)

@@ -1,21 +1,17 @@
 """What ``fused.stem_conv3x3_bias_act`` hands to the C ABI (``opa_stem3x3_actp``), argument by argument, without a GPU -- recorded like
-``test_launch_marshalling.py`` records its cases (whose recorder this uses; floats as ``test_launch_marshalling_actp.normalise`` reads
-them) and compared with ``golden/launch_marshalling_stem.json`` (``golden/make_golden_launch_marshalling_stem.py``).
+``test_launch_marshalling.py`` records its cases (on the harness of ``abi_tables.py``) and compared with ``golden/launch_marshalling_stem.json`` (``golden/make_golden_abi.py launch_marshalling_stem``).
 
 Three inputs: NCHW-contiguous, channels-last, and a view cropped by one pixel on each side out of a larger tensor of either layout.
 The four strides handed over must be the VIEW's own and the pointer the view's first element: the launcher makes no copy."""
-import json
-import os
-
 import torch
 from torch import nn
 
 from openpifpaf_amd import fused
 
+import abi_tables as at
 import test_launch_marshalling as tlm
-import test_launch_marshalling_actp as tlma
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'launch_marshalling_stem.json')
+GOLDEN = at.golden('launch_marshalling_stem')
 CL = torch.channels_last
 ACTS = {'none': (fused.ACT_NONE, 0.0), 'relu': (fused.ACT_RELU, 0.0), 'hardswish': (fused.ACT_HARDSWISH, 0.0),
         'leaky0.01': (fused.ACT_LEAKY_RELU, 0.01), 'relu6': (fused.ACT_RELU6, 6.0)}
@@ -49,26 +45,11 @@ def cases():
 
 def record_all():
     """-> {case id: [[symbol, [arguments]], ...]}"""
-    result = {}
-    with tlm.recording() as rec, torch.no_grad():
-        for case_id, (call, tensors, derived) in cases().items():
-            rec.calls = []
-            kept = call()
-            labels = dict(tensors, **derived())
-            addresses = {t.data_ptr(): label for label, t in labels.items()}
-            assert len(addresses) == len(labels), case_id
-            result[case_id] = tlma.normalise(rec.calls, addresses)
-            del kept
-    return result
+    return at.record_all(cases())
 
 
 def test_every_launch_hands_over_what_the_golden_file_says():
-    with open(GOLDEN) as f:
-        golden = json.load(f)['cases']
-    got = record_all()
-    assert sorted(got) == sorted(golden)
-    different = {k: (got[k], golden[k]) for k in got if got[k] != golden[k]}
-    assert not different, different
+    got = at.marshalling(cases(), GOLDEN)
     assert all(len(calls) == 1 and calls[0][0] == 'opa_stem3x3_actp' for calls in got.values())
 
 
@@ -91,7 +72,7 @@ def test_the_strides_are_the_views_and_nothing_is_copied():
 
 
 def test_the_output_is_dense_channels_last():
-    with tlm.recording(), torch.no_grad():
+    with at.recording(), torch.no_grad():
         for layout, (x, _) in inputs().items():
             for stride in (1, 2):
                 out = fused.stem_conv3x3_bias_act(nn.Conv2d(3, 24, 3, stride, 1), x)

@@ -1,23 +1,19 @@
 """What ``fused.conv1x1_unit_bf16`` hands to the C ABI (``opa_gemm_unit_actp_bf16``), argument by argument, without a GPU -- recorded like
-``test_launch_marshalling.py`` records its cases (whose recorder this uses; floats as ``test_launch_marshalling_actp.normalise`` reads
-them) and compared with ``golden/launch_marshalling_unit_bf16.json`` (``golden/make_golden_launch_marshalling_unit_bf16.py``).
+``test_launch_marshalling.py`` records its cases (on the harness of ``abi_tables.py``) and compared with ``golden/launch_marshalling_unit_bf16.json`` (``golden/make_golden_abi.py launch_marshalling_unit_bf16``).
 
 Operands: a dense channels-last bfloat16 tensor and a channel slice of a wider one; alone, with a partner, with a residual; every
 activation code.  The pitches handed over must be the VIEWS' own, in bf16 elements, and the pointers their first elements: the
 launcher makes no copy.  The derived operands are the padded bfloat16 weight and the padded FLOAT32 bias."""
 import ctypes
-import json
-import os
-
 import torch
 from torch import nn
 
 from openpifpaf_amd import fused
 
+import abi_tables as at
 import test_launch_marshalling as tlm
-import test_launch_marshalling_actp as tlma
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'launch_marshalling_unit_bf16.json')
+GOLDEN = at.golden('launch_marshalling_unit_bf16')
 BF16 = torch.bfloat16
 SYMBOL = 'opa_gemm_unit_actp_bf16'
 B, H, W = 2, 3, 5
@@ -53,30 +49,18 @@ def cases():
     return out
 
 
+def _check(case_id, out):
+    assert out.dtype == BF16 and out.is_contiguous(memory_format=torch.channels_last), case_id
+    assert tuple(out.shape) == (B, 2 * N if '/partner/' in case_id else N, H, W), case_id
+
+
 def record_all():
     """-> {case id: [[symbol, [arguments]], ...]}"""
-    result = {}
-    with tlm.recording() as rec, torch.no_grad():
-        for case_id, (call, tensors, derived) in cases().items():
-            rec.calls = []
-            kept = call()
-            labels = dict(tensors, **derived())
-            addresses = {t.data_ptr(): label for label, t in labels.items()}
-            assert len(addresses) == len(labels), case_id
-            result[case_id] = tlma.normalise(rec.calls, addresses)
-            assert kept.dtype == BF16 and kept.is_contiguous(memory_format=torch.channels_last), case_id
-            assert tuple(kept.shape) == (B, 2 * N if '/partner/' in case_id else N, H, W), case_id
-            del kept
-    return result
+    return at.record_all(cases(), check=_check)
 
 
 def test_every_launch_hands_over_what_the_golden_file_says():
-    with open(GOLDEN) as f:
-        golden = json.load(f)['cases']
-    got = record_all()
-    assert sorted(got) == sorted(golden)
-    different = {k: (got[k], golden[k]) for k in got if got[k] != golden[k]}
-    assert not different, different
+    got = at.marshalling(cases(), GOLDEN, check=_check)
     assert all([name for name, _ in calls] == [SYMBOL] for calls in got.values())
 
 

@@ -182,12 +182,12 @@ def test_routes_decline_on_the_cpu_and_when_switched_off(monkeypatch):
     # a LeakyReLU unit asks the switch before anything else
     unit = network.optimize_for_inference_(tc.randomize_(network._InvertedResidualK(32, 32, False, leaky_relu=True), 0))
     seen = []
-    monkeypatch.setattr(fused, 'unit_conv_x3_supported', lambda *a, **k: seen.append(1) or False)
+    monkeypatch.setattr(fused, 'unit_conv_supported', lambda *a, **k: seen.append(1) or False)
     monkeypatch.setattr(fused, 'UNIT_LEAKY', False)
     assert not unit._unit_route_supported(x) and not seen
     monkeypatch.setattr(fused, 'UNIT_LEAKY', True)
     monkeypatch.setattr(network._InvertedResidualK, '_dw_ok', staticmethod(lambda m, t: True))
-    monkeypatch.setattr(fused, '_unit_conv_ok', lambda conv: True)
+    monkeypatch.setattr(fused, '_unit_conv_ok', lambda mode, conv: True)
     assert not unit._unit_route_supported(x) and seen                # (past the switch: the operands decide)
 
 

@@ -1,5 +1,7 @@
 """Host side of the ShuffleNetV2K unit route (``fused.conv1x1_unit_x3``, ``opa_gemm_unit_bias_act_f32x3``), without a GPU: the
 derived weight operand, the decision (table, then size, never timing) and what the predicate declines."""
+import functools
+
 import pytest
 import torch
 from torch import nn
@@ -151,21 +153,22 @@ def test_what_the_predicate_declines(monkeypatch):
     monkeypatch.setattr(fused, 'X3_UNIT', True)
     monkeypatch.setattr(fused, 'X3_TERMS', 6)
     cl = torch.channels_last
+    conv_ok, operand_ok = (functools.partial(f, fused.UNIT_MODE_X3) for f in (fused._unit_conv_ok, fused._unit_operand_ok))
     conv = nn.Conv2d(174, 174, 1).requires_grad_(False)
     x = torch.randn(2, 348, 5, 7).contiguous(memory_format=cl)
     x1, x2 = x.chunk(2, dim=1)
-    assert fused._unit_conv_ok(conv) and fused._unit_operand_ok(x2, 174) and fused._unit_operand_ok(x1, 174)     # the positive controls
+    assert conv_ok(conv) and operand_ok(x2, 174) and operand_ok(x1, 174)     # the positive controls
     assert fused._pixel_stride(x2) == 348 and x2.data_ptr() % 16 == 8
     assert not fused.unit_conv_x3_supported(conv, x2)                 # not on the GPU
-    assert not fused._unit_conv_ok(nn.Conv2d(174, 173, 1)) and not fused._unit_conv_ok(nn.Conv2d(173, 174, 1))         # odd widths
-    assert not fused._unit_conv_ok(nn.Conv2d(174, 174, 3, padding=1)) and not fused._unit_conv_ok(nn.Conv2d(174, 174, 1, stride=2))
-    assert not fused._unit_conv_ok(nn.Conv2d(174, 174, 1, groups=2)) and not fused._unit_conv_ok(nn.Conv2d(174, 174, 1).bfloat16())
-    assert not fused._unit_operand_ok(x2.bfloat16(), 174)             # bfloat16
-    assert not fused._unit_operand_ok(torch.randn(2, 174, 5, 7), 174)  # channels outermost
-    assert not fused._unit_operand_ok(x2, 172) and not fused._unit_operand_ok(x[:, 1:175], 174)                         # 4 bytes off
-    assert not fused._unit_operand_ok(x2.clone(memory_format=torch.preserve_format).requires_grad_(True), 174)
+    assert not conv_ok(nn.Conv2d(174, 173, 1)) and not conv_ok(nn.Conv2d(173, 174, 1))         # odd widths
+    assert not conv_ok(nn.Conv2d(174, 174, 3, padding=1)) and not conv_ok(nn.Conv2d(174, 174, 1, stride=2))
+    assert not conv_ok(nn.Conv2d(174, 174, 1, groups=2)) and not conv_ok(nn.Conv2d(174, 174, 1).bfloat16())
+    assert not operand_ok(x2.bfloat16(), 174)             # bfloat16
+    assert not operand_ok(torch.randn(2, 174, 5, 7), 174)  # channels outermost
+    assert not operand_ok(x2, 172) and not operand_ok(x[:, 1:175], 174)                         # 4 bytes off
+    assert not operand_ok(x2.clone(memory_format=torch.preserve_format).requires_grad_(True), 174)
     monkeypatch.setattr(fused, 'X3_UNIT', False)
-    assert not fused._unit_conv_ok(conv)
+    assert not conv_ok(conv)
     monkeypatch.setattr(fused, 'X3_UNIT', True)
     monkeypatch.setattr(fused, 'X3_TERMS', 0)
-    assert not fused._unit_conv_ok(conv)
+    assert not conv_ok(conv)
