@@ -565,6 +565,22 @@ int opa_gemm_unit_actp_bf16(const void* a_dev, int64_t a_pitch, const void* w_de
                             const void* partner_dev, int64_t partner_pitch, const void* residual_dev, int64_t residual_pitch,
                             void* out_dev, int64_t m, int32_t n, int32_t k, int32_t act, float act_param, void* stream);
 
+/* The 3x3 convolutions of a ResNet cast to bfloat16 (csrc/conv3x3_bf16.hip; reference network/basenetworks.py:71-150 runs them
+ * through torch.nn.Conv2d) as an implicit GEMM on the bf16 MFMA, float32 accumulation, ONE rounding at the store:
+ *     out[b, oy, ox, co] = bf16_rne(act(sum_{ky,kx,ci} x[b, s*oy - d + d*ky, s*ox - d + d*kx, ci] * w[co][3*ky + kx][ci]
+ *                                       + bias[co] (+ residual[b, oy, ox, co])))
+ * x_dev: dense channels-last bf16 [batch, h_in, w_in, c_in]; w_dev: bf16 [c_out][9][c_in] (K-major, K = 9 c_in: the convolution's
+ * weight permuted to [c_out, ky, kx, c_in]); bias_dev: FLOAT32 [c_out] or NULL (a bf16 folded bias upcast); residual_dev: dense
+ * bf16 [batch, ho, wo, c_out] or NULL; out_dev: dense bf16 of that shape, ho = (h_in - 1) / stride + 1 (wo alike).  s = stride 1 or
+ * 2; d = dilation = the padding, 1, or 2 or 4 with stride 1; relu 0 / 1 (a select in float32 behind the sums: NaN stays NaN).
+ * c_in % 64 == 0, c_out % 64 == 0; x and out each fewer than 2^31 elements; all five pointers 16-B aligned (NULL passes).
+ * A tap outside the image is not loaded: the padding contributes exactly zero whatever memory holds, and no address outside x is
+ * read.  No workspace, no atomics: equal inputs give equal bits.  batch, h_in or w_in == 0: OPA_OK, nothing runs; everything
+ * else outside this contract is OPA_ERR_INVALID_ARGUMENT. */
+int opa_conv3x3_act_bf16(const void* x_dev, const void* w_dev, const float* bias_dev, const void* residual_dev, void* out_dev,
+                         int32_t batch, int32_t h_in, int32_t w_in, int32_t c_in, int32_t c_out,
+                         int32_t stride, int32_t dilation, int32_t relu, void* stream);
+
 /* 3x3 convolution, stride 1, padding 1, of an NHWC float32 activation as Winograd F(2x2, 3x3) in ONE kernel (input
  * transform -> sixteen float32 MFMA GEMMs -> output transform; csrc/winograd.hip): the bottleneck convolutions of the
  * ResNet trunk (reference network/basenetworks.py:71-150 runs them through torch.nn.Conv2d), 2.25x fewer multiplications

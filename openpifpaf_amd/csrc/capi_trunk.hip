@@ -17,7 +17,8 @@
 //                      opa_gconv3x3_bias_act_f32, after every check that does not need a size (all but the first test their grid
 //                      only behind it); an empty batch alone (h and w must be positive) for opa_stem3x3_actp, after every check
 //                      but those of the sizes' products, and for opa_groupnorm_actp (pixels, channels and groups must be positive),
-//                      after every check of its arguments but the limits and the workspace.  opa_conv3x3_f32x3, opa_gemm2_*,
+//                      after every check of its arguments but the limits and the workspace; an empty batch, h or w for
+//                      opa_conv3x3_act_bf16, after every check but the grid's.  opa_conv3x3_f32x3, opa_gemm2_*,
 //                      opa_conv_rows_*, Winograd, dwconv, squeeze-excite, interleave and the head epilogue refuse empties.
 //   last error         a call that succeeds leaves opa_last_error's text as it was.
 //   marks              the entry points that pass a kernel's name to Entry::launched mark the profile here; the launchers of the
@@ -310,6 +311,29 @@ int opa_gemm_unit_actp_bf16(const void* a_dev, int64_t a_pitch, const void* w_de
     return E.launched(launch_gemm_unit_act_bf16(a_dev, a_pitch, w_dev, bias_dev, partner_dev, partner_dev ? partner_pitch : 0, residual_dev,
                                                 residual_dev ? residual_pitch : 0, out_dev, (int)m, n, k, act, act_param, E.st),
                       "gemm_unit_actp_bf16", "gemm_unit_bf16_kernel");
+}
+
+// the 3x3 convolutions of a bfloat16 ResNet as an implicit GEMM on the bf16 MFMA (csrc/conv3x3_bf16.hip): one message per check
+int opa_conv3x3_act_bf16(const void* x_dev, const void* w_dev, const float* bias_dev, const void* residual_dev, void* out_dev,
+                         int32_t batch, int32_t h_in, int32_t w_in, int32_t c_in, int32_t c_out,
+                         int32_t stride, int32_t dilation, int32_t relu, void* stream) {
+    const Entry E("opa_conv3x3_act_bf16", stream);
+    if (!x_dev || !w_dev || !out_dev) return E.refuse("x_dev, w_dev and out_dev must not be NULL");
+    if (misaligned(15, {x_dev, w_dev, bias_dev, residual_dev, out_dev})) return E.refuse("pointers must be 16-B aligned");
+    if (batch < 0 || h_in < 0 || w_in < 0) return E.refuse("negative batch, h_in or w_in");
+    if (c_in <= 0 || c_out <= 0 || c_in % 64 != 0 || c_out % 64 != 0) return E.refuse("c_in and c_out must be positive multiples of 64");
+    if (stride != 1 && stride != 2) return E.refuse("stride must be 1 or 2");
+    if (dilation != 1 && dilation != 2 && dilation != 4) return E.refuse("dilation must be 1, 2 or 4");
+    if (dilation > 1 && stride != 1) return E.refuse("a dilation above 1 needs stride 1");
+    // 32-bit element offsets into both tensors (in double: exact up to 2^53, and no product of these arguments overflows it)
+    const double ho = h_in > 0 ? (h_in - 1) / stride + 1 : 0, wo = w_in > 0 ? (w_in - 1) / stride + 1 : 0;
+    if ((double)batch * h_in * w_in * c_in >= 2147483648.0) return E.refuse("x must hold fewer than 2^31 elements (32-bit offsets)");
+    if ((double)batch * ho * wo * c_out >= 2147483648.0) return E.refuse("out must hold fewer than 2^31 elements (32-bit offsets)");
+    if (batch == 0 || h_in == 0 || w_in == 0) return OPA_OK;
+    // (grid.x; with out below 2^31 elements of at least 64 channels it holds today: it guards the launch should a limit above move)
+    if (conv3x3_bf16_workgroups(batch, h_in, w_in, c_out, stride) > 0x7fffffffll) return E.refuse("too many tiles for grid.x");
+    return E.launched(launch_conv3x3_bf16(x_dev, w_dev, bias_dev, residual_dev, out_dev, batch, h_in, w_in, c_in, c_out, stride, dilation,
+                                          relu, E.st), "conv3x3_act_bf16", "conv3x3_bf16_kernel");
 }
 
 // opa_conv3x3_winograd_f32 and opa_conv3x3_winograd_f32x3 (`x3`: u_dev holds the three bf16 planes of the filter)

@@ -315,6 +315,13 @@ hipError_t launch_gemm_unit_act_f32x3(const float* A, int lda, const unsigned sh
 hipError_t launch_gemm_unit_act_bf16(const void* A, long long lda, const void* W, const float* bias, const void* partner, long long ldp,
                                      const void* residual, long long ldr, void* out, int M, int n, int k, int act, float act_param,
                                      hipStream_t st);
+// csrc/conv3x3_bf16.hip: the 3x3 convolution of a dense channels-last bf16 tensor as an implicit GEMM on the bf16 MFMA: x [B, H, W, c_in],
+// w [c_out][9][c_in], bias float32 [c_out] or null, residual / out dense bf16 [B, Ho, Wo, c_out]; c_in % 64 == 0, c_out % 64 == 0, S 1 or
+// 2, D = padding 1, or 2 or 4 with S = 1; x and out below 2^31 elements (anything else: hipErrorInvalidValue).
+// conv3x3_bf16_workgroups = grid.x of the launch.
+long long conv3x3_bf16_workgroups(int B, int H, int W, int c_out, int S);
+hipError_t launch_conv3x3_bf16(const void* x, const void* w, const float* bias, const void* residual, void* out, int B, int H, int W,
+                               int c_in, int c_out, int S, int D, int relu, hipStream_t st);
 hipError_t launch_gemm_f32_bias_act(const float* A, const float* W, const float* bias, const float* res, float* out,
                                     int M, int N, int K, int relu, hipStream_t st, const float* a_bias = nullptr);
 hipError_t launch_winograd_f23(const float* x, const float* U, float* y, const float* bias, int N, int H, int W, int Cin,

@@ -113,6 +113,13 @@ GN = _switch('OPA_GN', '0')
 # keys are float32's): where the switch is on and ``unit_conv_bf16_supported`` the kernel runs.  It ships OFF; the one timing is
 # tools/gpu/unit_bf16_times.py, profiles/unit_bf16/times.log.
 UNIT_BF16 = _switch('OPA_UNIT_BF16', '0')
+# The 3x3 convolutions of a ResNet cast to bfloat16 (``model.to(torch.bfloat16)``: conv2 of a Bottleneck, both convolutions of a
+# BasicBlock, strided ones and the dilated ones of block 5 under ``block5_dilation`` included) as an implicit GEMM on the bf16 MFMA with
+# the folded bias, the residual and the ReLU inside (csrc/conv3x3_bf16.hip, ``conv3x3_bias_act_bf16``) instead of MIOpen's convolution
+# and a separate epilogue: OPA_CONV3_BF16=1 (or fused.CONV3_BF16 = True).  Never timed by ``pick``, no choice-table entry: where the
+# switch is on and ``conv3x3_bf16_supported`` the kernel runs.  It ships OFF; the one timing is tools/gpu/conv3_bf16_times.py,
+# profiles/conv3_bf16/times.log, and switching the default is a change of its own that rests on it.
+CONV3_BF16 = _switch('OPA_CONV3_BF16', '0')
 
 
 # ---- the choice table and the decision ---------------------------------------------------------------------------------------------
@@ -618,6 +625,63 @@ def conv3x3_dilated_bias_act_x3(conv, x, bias, relu=True):
     out = _empty_nhwc(x, conv.out_channels, _out_hw(x, s), torch.float32)
     _launch('opa_conv3x3_dilated_f32x3', _ptr(x), _ptr(w3), _ptr(bias), _ptr(out), B, H, W, C, conv.out_channels, s,
             conv.dilation[0], int(bool(relu)), int(X3_TERMS))
+    return out
+
+
+def conv3x3_bf16_weight_of(conv, bias=None):
+    """The operands of ``conv3x3_bias_act_bf16`` derived from the CURRENT ``conv.weight`` (``[N, C, 3, 3]`` bfloat16) and the folded
+    ``bias`` the block keeps (``[N]`` bfloat16, or None): the weight as ``[N][9][C]`` -- ``weight.permute(0, 2, 3, 1)``, K-major with
+    K = 9 C, ``split_weight_3x3``'s layout without the split -- and the bias as FLOAT32 (upcast exactly; None stays None).  Derived and
+    cached (``derived``, keyed on both tensors' storage and version): no buffer, no part of a state dict, computed again whenever the
+    weight or the bias was replaced, moved, converted or changed in place (``load_state_dict`` into an optimized model)."""
+    def make():
+        w = conv.weight.detach()
+        return (w.permute(0, 2, 3, 1).reshape(w.shape[0], 9, w.shape[1]).contiguous(),
+                None if bias is None else bias.detach().to(torch.float32).contiguous())
+    return derived(conv, '_opa_w_conv3_bf16', (conv.weight, bias), make)
+
+
+def conv3x3_bf16_supported(conv, x, bias, residual=None):
+    """Can ``conv3x3_bias_act_bf16(conv, x, bias, residual)`` run?  The switch on; a dense channels-last bfloat16 tensor on the GPU,
+    outside autocast (whose parameters stay float32), nothing that autograd follows; a 3x3 convolution without groups or a bias of
+    its own (the folded one arrives separately: bfloat16 or float32, one element per output channel, or None), square stride 1 or 2,
+    square dilation 1, 2 or 4 -- above 1 with stride 1 only -- and padding equal to the dilation; input and output channels
+    multiples of 64; ``residual`` a dense channels-last bfloat16 tensor of the output's shape; 16-byte boundaries; ``x`` and the
+    output fewer than 2^31 elements each."""
+    if not (CONV3_BF16 and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and not torch.is_autocast_enabled()):
+        return False
+    if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad or (bias is not None and bias.requires_grad)
+                                    or (residual is not None and residual.requires_grad)):
+        return False
+    s, d = conv.stride[0], conv.dilation[0]
+    if not (conv.kernel_size == (3, 3) and conv.groups == 1 and conv.bias is None and conv.stride == (s, s) and s in (1, 2)
+            and conv.dilation == (d, d) and d in (1, 2, 4) and (d == 1 or s == 1) and conv.padding == (d, d)
+            and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0 and x.shape[1] == conv.in_channels
+            and conv.weight.dtype == torch.bfloat16 and conv.weight.device == x.device
+            and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0 and 0 < x.numel() < 2 ** 31
+            and out_pixels(x, s) * conv.out_channels < 2 ** 31):
+        return False
+    if bias is not None and not (bias.dtype in (torch.bfloat16, torch.float32) and bias.device == x.device and bias.dim() == 1
+                                 and bias.numel() == conv.out_channels):
+        return False
+    if residual is not None and not (residual.dtype == torch.bfloat16 and residual.device == x.device and residual.is_cuda
+                                     and tuple(residual.shape) == (x.shape[0], conv.out_channels) + _out_hw(x, s)
+                                     and residual.is_contiguous(memory_format=torch.channels_last) and residual.data_ptr() % 16 == 0):
+        return False
+    return _lib.available()
+
+
+def conv3x3_bias_act_bf16(conv, x, bias, residual=None, relu=True):
+    """``act(conv(x) + bias (+ residual))`` for a 3x3 convolution of a bfloat16 ResNet (reference ``network/basenetworks.py:71-150``:
+    torchvision's BasicBlock and Bottleneck; ``:121-135``: block 5 dilated) as ONE implicit GEMM on the bf16 MFMA
+    (``opa_conv3x3_act_bf16``, csrc/conv3x3_bf16.hip): float32 accumulation, one rounding -- bfloat16 in and out.
+    ``conv3x3_bf16_supported`` says whether this can run."""
+    w9, b32 = conv3x3_bf16_weight_of(conv, bias)
+    B, C, H, W = x.shape
+    s = conv.stride[0]
+    out = _empty_nhwc(x, conv.out_channels, _out_hw(x, s))
+    _launch('opa_conv3x3_act_bf16', _ptr(x), _ptr(w9), _ptr(b32), _ptr(residual), _ptr(out), B, H, W, C, conv.out_channels, s,
+            conv.dilation[0], int(bool(relu)))
     return out
 
 

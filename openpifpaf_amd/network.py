@@ -101,6 +101,8 @@ class _Bottleneck(nn.Module):
                                  lambda: fused.bias_act_(self.conv2(h), self.fb2))
             elif fused.gconv3x3_supported(self.conv2, out, self.fb2):    # ... float32 grouped (ResNeXt): one stencil kernel,
                 out = fused.gconv3x3_bias_act(self.conv2, out, self.fb2, True)        # bias + ReLU inside
+            elif fused.conv3x3_bf16_supported(self.conv2, out, self.fb2):  # ... bfloat16 behind OPA_CONV3_BF16: the implicit GEMM on
+                out = fused.conv3x3_bias_act_bf16(self.conv2, out, self.fb2, relu=True)   # the bf16 MFMA, bias + ReLU inside, one rounding
             else:
                 out = self.conv2(out)                                     # ... bfloat16: MIOpen, raw output ...
                 epilogue_done = False
@@ -179,8 +181,12 @@ class _BasicBlock(nn.Module):
                 pass
             elif winograd.takes(self.conv1, x, self._wino[0]):  # bias + ReLU in the kernel's output transform
                 out = winograd.run(self.conv1, x, bias=self.fb1, relu=True)
+            elif fused.conv3x3_bf16_supported(self.conv1, x, self.fb1):   # bfloat16 behind OPA_CONV3_BF16: bias + ReLU in the kernel
+                out = fused.conv3x3_bias_act_bf16(self.conv1, x, self.fb1, relu=True)
             else:
                 out = fused.bias_act_(self.conv1(x), self.fb1)
+            if fused.conv3x3_bf16_supported(self.conv2, out, self.fb2, identity):      # ... and bias + identity + ReLU: no separate pass
+                return fused.conv3x3_bias_act_bf16(self.conv2, out, self.fb2, identity, relu=True)
             last = self._dilated(self.conv2, out, self.fb2, identity)
             if last is not None:
                 return last
