@@ -6,38 +6,26 @@
 // ANY even k and n; A, the partner and the residual may be channel slices of wider channels-last tensors.  W [Np][Kp] bf16 and
 // bias [Np] float32 are padded with zeros on the host (Np, Kp: n, k rounded up to multiples of 64), `out` is dense.
 //
-// Tile and fragments are csrc/gemm_epilogue.hip's: 128 x BN per 256-thread workgroup (BN = 128 where Np allows, else 64), BK = 64,
-// 4 waves as 2 (M) x 2 (N), LDS rows 72 bf16 apart, XCD-aware tile order, a wave-private float32 patch in the epilogue.  What differs
-// is how the operands are reached.  The contract guarantees 4-byte alignment only (k16's stage-2 slice starts 348 bytes into the
+// Tile shape, tile order, accumulator layout and patch fence are csrc/bf16_tile.hpp's (BN = 128 where Np allows, else 64).  The K
+// loop below is that header's bf16_tile_mainloop written out: on the shared function this kernel's code changes, and one layer timed
+// outside its range (profiles/bf16_tile/README.md), so it stays here, compiled to the bytes it had.  What differs from the other two
+// kernels is how the operands are reached.  The contract guarantees 4-byte alignment only (k16's stage-2 slice starts 348 bytes into the
 // pixel), so the width of A's loads -- 16, 8 or 4 bytes -- is chosen per launch from the base address and the pitch, uniformly for
 // the grid; columns from k on are never loaded (their registers keep zeros: a select, not a product with a zero weight) and no byte
 // behind column k of the last row is addressed.  Which bytes which thread loads is decided in csrc/unit_bf16_plan.hpp, which a CPU
 // program enumerates (tests/test_unit_bf16_plan.py).  The epilogue works in column pairs: 4-byte loads of the partner / residual,
 // 4-byte stores of the output (8-byte with a partner: its two elements and the two results interleaved).
-#include "common.hpp"
+#include "bf16_tile.hpp"
 #include "unit_bf16_plan.hpp"
 
 namespace opa {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
 typedef __attribute__((ext_vector_type(2))) float f32x2_t;
 
-constexpr int kPitch = kUnitBf16BK + 8;        // LDS row pitch in bf16 (gemm_epilogue.hip: fragment reads at <= 2-way conflicts)
 enum Third { kNone = 0, kPartner = 1, kResidual = 2 };
-
-__device__ __forceinline__ float bf16_lo(unsigned w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
-__device__ __forceinline__ unsigned bf16_rne(float x) {
-    unsigned u = __float_as_uint(x);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return u >> 16;
-}
 
 // N and K are the padded sizes (W [N][K], bias [N]); n, k the columns that exist; W_A the width of A's loads in bytes
 template <int BN, int W_A, int THIRD>
@@ -45,24 +33,16 @@ __global__ __launch_bounds__(256, 3) void gemm_unit_bf16_kernel(
         const unsigned short* __restrict__ A, long long lda, const unsigned short* __restrict__ W, const float* __restrict__ bias,
         const unsigned short* __restrict__ third, long long ldt, unsigned short* __restrict__ out, int M, int N, int K, int n, int k,
         int act, float act_param) {
-    constexpr int WN = BN / 2;                 // wave tile width
-    constexpr int NT = WN / 32;                // 32-wide MFMA blocks per wave in N (2 or 1)
-    constexpr int LDS_A = kUnitBf16BM * kPitch, LDS_B = BN * kPitch;
-    constexpr int STAGE_BYTES = (LDS_A + LDS_B) * 2;
-    constexpr int EPI_BYTES = 4 * 32 * WN * 4; // per wave a 32 x WN f32 patch
-    __shared__ __attribute__((aligned(16))) unsigned char smem[STAGE_BYTES > EPI_BYTES ? STAGE_BYTES : EPI_BYTES];
+    using T = Bf16Tile<BN>;
+    constexpr int WN = T::WN, NT = T::NT;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[T::LDS_BYTES];
     unsigned short* sA = reinterpret_cast<unsigned short*>(smem);
-    unsigned short* sB = sA + LDS_A;
+    unsigned short* sB = sA + T::LDS_A;
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int n_tiles = N / BN;
-    // XCD-aware tile order (see gemm_epilogue.hip): the N-tiles sharing one A row-block run on ONE L2
-    const unsigned nwg = gridDim.x, xcd = blockIdx.x & 7u, in_xcd = blockIdx.x >> 3;
-    const unsigned q = nwg >> 3, r8 = nwg & 7u;
-    const unsigned logical = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + in_xcd;
-    const int m0 = (int)(logical / n_tiles) * kUnitBf16BM;
-    const int n0 = (int)(logical % n_tiles) * BN;
+    const int tid = threadIdx.x, lane = bf16_tile_wave().lane, wave = bf16_tile_wave().wave;
+    const int wm = bf16_tile_wave().wm, wn = bf16_tile_wave().wn;
+    const Bf16TileOrigin org = bf16_tile_origin<BN>(N);
+    const int m0 = org.m0, n0 = org.n0;
 
     f32x16_t acc[2][NT];
 #pragma unroll
@@ -72,9 +52,8 @@ __global__ __launch_bounds__(256, 3) void gemm_unit_bf16_kernel(
 #pragma unroll
             for (int r = 0; r < 16; r++) acc[i][j][r] = 0.0f;
 
-    // staging map (unit_bf16_plan.hpp): a 64-wide bf16 row is 8 chunks of 16 B; 256 threads cover 32 rows per pass
-    const int s_row = tid >> 3, s_col = (tid & 7) * 8;
-    u32x4_t ra[kUnitBf16Passes], rb[BN / 32];
+    const int s_row = bf16_tile_stage(tid).row, s_col = bf16_tile_stage(tid).col;
+    u32x4_t ra[kBf16Passes], rb[BN / 32];
     auto load_a = [&](int p, int e, long long at, int bytes) {     // (p, e and bytes are constants once the plan is unrolled)
         const unsigned short* src = A + at;
         if (bytes == 16) {
@@ -88,35 +67,35 @@ __global__ __launch_bounds__(256, 3) void gemm_unit_bf16_kernel(
     };
     auto fetch = [&](int k0) {                 // global -> registers for K-step k0
 #pragma unroll
-        for (int p = 0; p < kUnitBf16Passes; p++) ra[p] = (u32x4_t){0u, 0u, 0u, 0u};
+        for (int p = 0; p < kBf16Passes; p++) ra[p] = (u32x4_t){0u, 0u, 0u, 0u};
         // (a K-step that ends at or before k has whole pieces only: with k out of the way the plan's tail folds away)
-        if (k0 + kUnitBf16BK <= k) unit_bf16_plan_a<W_A>(M, 0x7fffffff, lda, m0, tid, k0, load_a);
+        if (k0 + kBf16BK <= k) unit_bf16_plan_a<W_A>(M, 0x7fffffff, lda, m0, tid, k0, load_a);
         else unit_bf16_plan_a<W_A>(M, k, lda, m0, tid, k0, load_a);
 #pragma unroll
         for (int p = 0; p < BN / 32; p++)
             rb[p] = *reinterpret_cast<const u32x4_t*>(W + (size_t)(n0 + p * 32 + s_row) * K + k0 + s_col);
     };
     fetch(0);
-    for (int k0 = 0; k0 < K; k0 += kUnitBf16BK) {
+    for (int k0 = 0; k0 < K; k0 += kBf16BK) {
         __syncthreads();                       // previous step's fragment reads are done
 #pragma unroll
-        for (int p = 0; p < kUnitBf16Passes; p++)
-            *reinterpret_cast<u32x4_t*>(sA + (p * 32 + s_row) * kPitch + s_col) = ra[p];
+        for (int p = 0; p < kBf16Passes; p++)
+            *reinterpret_cast<u32x4_t*>(sA + (p * 32 + s_row) * kBf16Pitch + s_col) = ra[p];
 #pragma unroll
         for (int p = 0; p < BN / 32; p++)
-            *reinterpret_cast<u32x4_t*>(sB + (p * 32 + s_row) * kPitch + s_col) = rb[p];
+            *reinterpret_cast<u32x4_t*>(sB + (p * 32 + s_row) * kBf16Pitch + s_col) = rb[p];
         __syncthreads();
-        if (k0 + kUnitBf16BK < K) fetch(k0 + kUnitBf16BK);   // the next K-step's operands travel while this one multiplies
+        if (k0 + kBf16BK < K) fetch(k0 + kBf16BK);   // the next K-step's operands travel while this one multiplies
 #pragma unroll
-        for (int kk = 0; kk < kUnitBf16BK; kk += 16) {
+        for (int kk = 0; kk < kBf16BK; kk += 16) {
             bf16x8_t fa[2], fb[NT];
             const int kof = kk + (lane >> 5) * 8;
 #pragma unroll
             for (int i = 0; i < 2; i++)
-                fa[i] = *reinterpret_cast<const bf16x8_t*>(sA + (wm * 64 + i * 32 + (lane & 31)) * kPitch + kof);
+                fa[i] = *reinterpret_cast<const bf16x8_t*>(sA + (wm * 64 + i * 32 + (lane & 31)) * kBf16Pitch + kof);
 #pragma unroll
             for (int j = 0; j < NT; j++)
-                fb[j] = *reinterpret_cast<const bf16x8_t*>(sB + (wn * WN + j * 32 + (lane & 31)) * kPitch + kof);
+                fb[j] = *reinterpret_cast<const bf16x8_t*>(sB + (wn * WN + j * 32 + (lane & 31)) * kBf16Pitch + kof);
 #pragma unroll
             for (int i = 0; i < 2; i++)
 #pragma unroll
@@ -146,13 +125,9 @@ __global__ __launch_bounds__(256, 3) void gemm_unit_bf16_kernel(
             const int col = j * 32 + (lane & 31);
             const float b = bias[n0w + col];
 #pragma unroll
-            for (int r = 0; r < 16; r++) {     // C layout: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
-                const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                patch[row * WN + col] = acc[i][j][r] + b;
-            }
+            for (int r = 0; r < 16; r++) patch[bf16_tile_acc_row(r) * WN + col] = acc[i][j][r] + b;
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        bf16_tile_patch_sync();
         unit_bf16_plan_third<WN>(M, n, ldt, m0w, n0w, lane, [&](int t, long long row, int col, long long) {
             f32x2_t f = *reinterpret_cast<const f32x2_t*>(patch + (int)(row - m0w) * WN + (col - n0w));
             if (THIRD == kResidual) { f[0] += bf16_lo(tv[t]); f[1] += bf16_hi(tv[t]); }
@@ -164,8 +139,7 @@ __global__ __launch_bounds__(256, 3) void gemm_unit_bf16_kernel(
             else
                 *reinterpret_cast<unsigned*>(out + (size_t)row * n + col) = y0 | (y1 << 16);
         });
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        bf16_tile_patch_sync();
         // (as in x3_unit_epilogue of gemm_f32x3.hip, whose column-pair epilogue this is: the compiler, too, keeps the next block's
         //  patch writes behind this block's patch reads -- the fence orders the memory, this the unrolled code)
         asm volatile("" ::: "memory");
@@ -182,7 +156,7 @@ hipError_t launch_gemm_unit_act_bf16(const void* A, long long lda, const void* W
     if ((partner && residual) || act < 0 || act > 4 || (residual && act > 2) || M <= 0 || n <= 0 || k <= 0) return hipErrorInvalidValue;
     const int Np = (n + 63) / 64 * 64, Kp = (k + 63) / 64 * 64;
     const int bn = Np % 128 == 0 ? 128 : 64;
-    const long long blocks = (long long)((M + (long long)kUnitBf16BM - 1) / kUnitBf16BM) * (Np / bn);
+    const long long blocks = (long long)((M + (long long)kBf16BM - 1) / kBf16BM) * (Np / bn);
     if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
     const int third = partner ? kPartner : residual ? kResidual : kNone;
     const unsigned short* t = (const unsigned short*)(partner ? partner : residual);
@@ -190,7 +164,7 @@ hipError_t launch_gemm_unit_act_bf16(const void* A, long long lda, const void* W
     return with_value<64, 128>(bn, [&](auto BN) {
     return with_value<4, 8, 16>(unit_bf16_width((uintptr_t)A, lda), [&](auto W_A) {
     return with_value<(int)kNone, (int)kPartner, (int)kResidual>(third, [&](auto THIRD) {
-        gemm_unit_bf16_kernel<BN, W_A, THIRD><<<(unsigned)blocks, kUnitBf16Threads, 0, st>>>(
+        gemm_unit_bf16_kernel<BN, W_A, THIRD><<<(unsigned)blocks, kBf16Threads, 0, st>>>(
             (const unsigned short*)A, lda, (const unsigned short*)W, bias, t, ldt, (unsigned short*)out, M, Np, Kp, n, k, act, act_param);
         return hipGetLastError();
     }); }); });

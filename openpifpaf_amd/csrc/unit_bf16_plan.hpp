@@ -18,21 +18,15 @@
 #pragma once
 #include <cstdint>
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define OPA_PLAN_HD __host__ __device__ inline
-#define OPA_PLAN_UNROLL _Pragma("unroll")
-#else
-#define OPA_PLAN_HD inline
-#define OPA_PLAN_UNROLL
-#endif
+#include "bf16_tile_shape.hpp"
 
 namespace opa {
 
-constexpr int kUnitBf16BM = 128, kUnitBf16BK = 64, kUnitBf16Threads = 256;
-constexpr int kUnitBf16Passes = kUnitBf16BM / 32;      // row passes of the A staging map
+// the shared tile's constants under the names that the CPU program of this plan (tests/host/unit_bf16_plan_main.cpp) uses
+constexpr int kUnitBf16BM = kBf16BM, kUnitBf16BK = kBf16BK, kUnitBf16Threads = kBf16Threads, kUnitBf16Passes = kBf16Passes;
 
 // the widest access (bytes) that a base address and a row pitch (in bf16 elements) allow for every row: 16, 8 or 4
-OPA_PLAN_HD int unit_bf16_width(uintptr_t base, long long pitch_elems) {
+OPA_TILE_HD int unit_bf16_width(uintptr_t base, long long pitch_elems) {
     const uintptr_t bits = base | (uintptr_t)(pitch_elems * 2);
     return (bits & 15) == 0 ? 16 : (bits & 7) == 0 ? 8 : 4;
 }
@@ -41,21 +35,21 @@ OPA_PLAN_HD int unit_bf16_width(uintptr_t base, long long pitch_elems) {
 // emit(p, e, elem_offset, bytes): load `bytes` (W or 4) from element offset `elem_offset` (from A's first element, 64-bit) into
 // elements e ... e + bytes / 2 - 1 of the chunk of pass p.
 template <int W, typename Emit>
-OPA_PLAN_HD void unit_bf16_plan_a(int m, int k, long long pitch, int m0, int t, int k0, Emit&& emit) {
+OPA_TILE_HD void unit_bf16_plan_a(int m, int k, long long pitch, int m0, int t, int k0, Emit&& emit) {
     static_assert(W == 16 || W == 8 || W == 4, "access widths");
     constexpr int PE = W / 2;                       // elements of a piece
-    const int s_row = t >> 3, s_col = (t & 7) * 8;
-    OPA_PLAN_UNROLL
-    for (int p = 0; p < kUnitBf16Passes; p++) {
+    const int s_row = bf16_tile_stage(t).row, s_col = bf16_tile_stage(t).col;
+    OPA_TILE_UNROLL
+    for (int p = 0; p < kBf16Passes; p++) {
         const long long row = (long long)m0 + p * 32 + s_row;      // (64-bit: m0 + 127 may pass 2^31)
         if (row >= m) continue;
         const long long at = row * pitch + k0 + s_col;
-        OPA_PLAN_UNROLL
+        OPA_TILE_UNROLL
         for (int e = 0; e < 8; e += PE) {
             const long long col = (long long)k0 + s_col + e;
             if (col + PE <= k) emit(p, e, at + e, W);
             else {
-                OPA_PLAN_UNROLL
+                OPA_TILE_UNROLL
                 for (int d = 0; d < PE; d += 2)
                     if (col + d < k) emit(p, e + d, at + e + d, 4);
             }
@@ -68,9 +62,9 @@ OPA_PLAN_HD void unit_bf16_plan_a(int m, int k, long long pitch, int m0, int t, 
 // residual for that pair -- rows from m and columns from n on have none.
 // (m0w, n0w: the first row and column of the wave's 32-row block in the whole product)
 template <int WN, typename Emit>
-OPA_PLAN_HD void unit_bf16_plan_third(int m, int n, long long pitch, long long m0w, int n0w, int lane, Emit&& emit) {
+OPA_TILE_HD void unit_bf16_plan_third(int m, int n, long long pitch, long long m0w, int n0w, int lane, Emit&& emit) {
     constexpr int PPR = WN / 2, PPL = 32 * PPR / 64;
-    OPA_PLAN_UNROLL
+    OPA_TILE_UNROLL
     for (int i = 0; i < PPL; i++) {
         const int v = i * 64 + lane;
         const long long row = m0w + v / PPR;

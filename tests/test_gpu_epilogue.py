@@ -1,4 +1,5 @@
 """Fused conv epilogue kernel (csrc/epilogue.hip) against plain PyTorch fp32 math."""
+import numpy as np
 import pytest
 
 torch = pytest.importorskip('torch')
@@ -83,6 +84,58 @@ def test_gemm_with_fused_operand_prologue_equals_two_passes(cin, cout, hw, with_
     want = fused.conv1x1_bias_act(fused.bias_act_(x.clone(), ab), w, b, r, True)
     got = fused.conv1x1_bias_act(x, w, b, r, True, a_bias=ab)
     assert torch.equal(got, want)
+
+
+_KNOWN = {}
+_SENTINEL = 0x5a5a                                   # bfloat16 bits no result of the known-answer test has (1.5e16)
+
+
+def _known_case(m, n, k):
+    """Integer operands of the known-answer test as float64 numpy arrays, made once per shape and left unchanged: t in [-2, 1],
+    a_bias in [-1, 1], w in [-1, 1], bias in [-4, 4], residual in [-8, 8]."""
+    if (m, n, k) not in _KNOWN:
+        rng = np.random.default_rng(1000 * m + n + k)
+        t, ab = rng.integers(-2, 2, (m, k)), rng.integers(-1, 2, k)
+        w, bias, res = rng.integers(-1, 2, (n, k)), rng.integers(-4, 5, n), rng.integers(-8, 9, (m, n))
+        _KNOWN[(m, n, k)] = tuple(a.astype(np.float64) for a in (t, ab, w, bias, res))
+    return _KNOWN[(m, n, k)]
+
+
+@pytest.mark.parametrize('pro', [False, True])
+@pytest.mark.parametrize('relu', [False, True])
+@pytest.mark.parametrize('with_res', [False, True])
+@pytest.mark.parametrize('m,n,k', [(130, 64, 64), (257, 128, 128), (130, 192, 128)])
+def test_fused_conv1x1_gemm_known_answers_bit_for_bit(m, n, k, with_res, relu, pro):
+    """opa_gemm_bias_act_bf16 / opa_gemm_pro_bias_act_bf16 (csrc/gemm_epilogue.hip), all 16 instantiations: one and three row blocks
+    with a ragged last one, the 64- and the 128-wide tile, one and three N tiles, one and two K-steps.  The operand that is
+    multiplied is A = clip(t, -1, 1) without the prologue and relu(A + a_bias) = relu(t) in {0, 1} with it (A = t - a_bias, integers
+    in [-3, 2]): every product is -1, 0 or 1, every result an integer of magnitude <= k + 4 + 8 <= 140 -- exact in float32 in any
+    order of summation and a bfloat16.  The float64 reference is formed on the host; the bits must be equal.  `out` continues past
+    row m to the end of the last 128-row tile and one row more: those rows must keep their sentinel."""
+    from openpifpaf_amd import fused
+    t, ab, w, bias, res = _known_case(m, n, k)
+    a, eff = (t - ab, t.clip(min=0)) if pro else (t.clip(-1, 1), t.clip(-1, 1))
+    want = eff @ w.T + bias + (res if with_res else 0.0)
+    want = want.clip(min=0) if relu else want
+    assert float(np.abs(want).max()) <= 140 and np.array_equal(want, np.rint(want))
+
+    def dev(x):
+        return torch.from_numpy(x).to(torch.bfloat16).cuda().contiguous()
+
+    da, dab, dw, db, dr = dev(a), dev(ab), dev(w), dev(bias), dev(res)
+    assert all(np.array_equal(d.double().cpu().numpy(), h) for d, h in ((da, a), (dab, ab), (dw, w), (db, bias), (dr, res)))
+    rows = (m + 127) // 128 * 128 + 1
+    out = torch.full((rows, n), _SENTINEL, dtype=torch.int16, device='cuda')
+    rest = (dw.data_ptr(), db.data_ptr(), dr.data_ptr() if with_res else None, out.data_ptr(), m, n, k, int(relu))
+    if pro:
+        fused._launch('opa_gemm_pro_bias_act_bf16', da.data_ptr(), dab.data_ptr(), *rest)
+    else:
+        fused._launch('opa_gemm_bias_act_bf16', da.data_ptr(), *rest)
+    torch.cuda.synchronize()
+    want_bits = torch.from_numpy(want).to(torch.bfloat16)
+    assert np.array_equal(want_bits.double().numpy(), want)
+    assert torch.equal(out[:m].cpu(), want_bits.view(torch.int16))
+    assert bool((out[m:] == _SENTINEL).all())
 
 
 @pytest.mark.parametrize('cin,cout,hw,with_res,pro', [(64, 256, 37, True, False), (64, 256, 37, True, True), (256, 64, 41, False, False),
