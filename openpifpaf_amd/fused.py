@@ -580,52 +580,47 @@ def conv1x1_pair_bias_act_x3(conv, dconv, h, x, bias, relu=True, a_bias=None):
     return out
 
 
-def conv3x3_x3_supported(conv, x, bias):
+def _conv3x3_x3_ok(conv, x, bias, d):
+    """What both predicates of the float32 implicit GEMM ask, for a 3x3 convolution with square dilation ``d`` and padding ``d`` (the
+    kernel's buffer begins d rows + d pixels before the tensor: that share counts towards 2 GB)."""
     return (X3_CONV3 and X3_TERMS in (6, 9) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
-            and x.is_contiguous(memory_format=torch.channels_last) and conv.kernel_size == (3, 3) and conv.padding == (1, 1)
-            and conv.stride[0] == conv.stride[1] and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
-            and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0 and x.shape[1] == conv.in_channels
-            and x.data_ptr() % 16 == 0 and bias.dtype == torch.float32 and bias.is_contiguous() and bias.data_ptr() % 16 == 0
-            and (x.shape[0] * x.shape[2] * x.shape[3] + x.shape[3] + 1) * x.shape[1] * 4 < 2 ** 31)
-
-
-def conv3x3_bias_act_x3(conv, x, bias, relu=True):
-    """``act(conv(x) + bias)`` for a 3x3 convolution with padding 1 and any stride (reference ``network/basenetworks.py:71-150``: the
-    strided convolution of a ResNet block) as an implicit GEMM of the split-operand kernel -- float32 in and out."""
-    w3 = _split_weight_3x3_of(conv)
-    B, C, H, W = x.shape
-    s = conv.stride[0]
-    out = _empty_nhwc(x, conv.out_channels, _out_hw(x, s), torch.float32)
-    _launch('opa_conv3x3_f32x3', _ptr(x), _ptr(w3), _ptr(bias), _ptr(out), B, H, W, C, conv.out_channels, s,
-            int(bool(relu)), int(X3_TERMS))
-    return out
-
-
-def conv3x3_dilated_x3_supported(conv, x, bias):
-    """Can ``conv3x3_dilated_bias_act_x3(conv, x, bias)`` run?  As ``conv3x3_x3_supported``, for a 3x3 convolution with a square
-    dilation d >= 1 and padding d (the kernel's buffer begins d rows + d pixels before the tensor: that share counts towards 2 GB)."""
-    d = conv.dilation[0]
-    return (X3_CONV3 and X3_TERMS in (6, 9) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
-            and x.is_contiguous(memory_format=torch.channels_last) and conv.kernel_size == (3, 3) and d >= 1
+            and x.is_contiguous(memory_format=torch.channels_last) and conv.kernel_size == (3, 3)
             and conv.dilation == (d, d) and conv.padding == (d, d)
             and conv.stride[0] == conv.stride[1] and conv.groups == 1 and conv.bias is None
             and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0 and x.shape[1] == conv.in_channels
-            and conv.weight.dtype == torch.float32 and conv.weight.device == x.device
             and x.data_ptr() % 16 == 0 and bias.dtype == torch.float32 and bias.is_contiguous() and bias.data_ptr() % 16 == 0
-            and x.numel() > 0 and (x.shape[0] * x.shape[2] * x.shape[3] + d * (x.shape[3] + 1)) * x.shape[1] * 4 < 2 ** 31)
+            and (x.shape[0] * x.shape[2] * x.shape[3] + d * (x.shape[3] + 1)) * x.shape[1] * 4 < 2 ** 31)
 
 
-def conv3x3_dilated_bias_act_x3(conv, x, bias, relu=True):
-    """``act(conv(x) + bias)`` for a 3x3 convolution with dilation d, padding d and any stride (reference
-    ``network/basenetworks.py:121-135``: the convolutions of block 5 under ``--resnet-block5-dilation``) as an implicit GEMM of the
-    split-operand kernel (``opa_conv3x3_dilated_f32x3``: ``conv3x3_bias_act_x3``'s kernel, whose taps step by d) -- float32 in and out."""
+def _conv3x3_x3(symbol, conv, x, bias, relu, *dilation):
+    """``act(conv(x) + bias)`` as an implicit GEMM of the split-operand kernel, float32 in and out, behind both launchers."""
     w3 = _split_weight_3x3_of(conv)
     B, C, H, W = x.shape
     s = conv.stride[0]
     out = _empty_nhwc(x, conv.out_channels, _out_hw(x, s), torch.float32)
-    _launch('opa_conv3x3_dilated_f32x3', _ptr(x), _ptr(w3), _ptr(bias), _ptr(out), B, H, W, C, conv.out_channels, s,
-            conv.dilation[0], int(bool(relu)), int(X3_TERMS))
+    _launch(symbol, _ptr(x), _ptr(w3), _ptr(bias), _ptr(out), B, H, W, C, conv.out_channels, s, *dilation, int(bool(relu)), int(X3_TERMS))
     return out
+
+
+def conv3x3_x3_supported(conv, x, bias):
+    return _conv3x3_x3_ok(conv, x, bias, 1)
+
+
+def conv3x3_bias_act_x3(conv, x, bias, relu=True):
+    """A 3x3 convolution with padding 1 and any stride (reference ``network/basenetworks.py:71-150``: the strided one of a ResNet block)."""
+    return _conv3x3_x3('opa_conv3x3_f32x3', conv, x, bias, relu)
+
+
+def conv3x3_dilated_x3_supported(conv, x, bias):
+    """As ``conv3x3_x3_supported``, for any square dilation d >= 1 with padding d."""
+    d = conv.dilation[0]
+    return (d >= 1 and conv.weight.dtype == torch.float32 and conv.weight.device == x.device and x.numel() > 0
+            and _conv3x3_x3_ok(conv, x, bias, d))
+
+
+def conv3x3_dilated_bias_act_x3(conv, x, bias, relu=True):
+    """... with dilation d and padding d (``:121-135``: block 5 under ``--resnet-block5-dilation``): the same kernel, its taps d apart."""
+    return _conv3x3_x3('opa_conv3x3_dilated_f32x3', conv, x, bias, relu, conv.dilation[0])
 
 
 def conv3x3_bf16_weight_of(conv, bias=None):

@@ -50,6 +50,54 @@ def _take_biases(block, conv_names):
         block.register_buffer('fb%d' % i, bias)
 
 
+# The routes of a ResNet's 3x3 convolution in precedence order ("3x3 convolution of a ResNet -> route").  Per row: its
+# name; the predicate; the launcher -- ``bare``: the convolution alone, no bias (Winograd: none, the split-operand kernel: a zero
+# one) and no ReLU; whether the kernel adds the residual itself; (kind, flag_b) of its ``fused.pick`` against MIOpen + ``bias_act_``,
+# or None where it does not compete.  Every row reaches ``fused.*`` / ``winograd.*`` at the call: the route tests put recorders there.
+_CONV3_ROUTES = (
+    ('wino', lambda c, x, b, r, u: winograd.takes(c, x, u),
+     lambda c, x, b, r, u, bare: winograd.run(c, x, u, bias=None if bare else b, relu=not bare), False, None),
+    ('x3', lambda c, x, b, r, u: fused.conv3x3_x3_supported(c, x, b),
+     lambda c, x, b, r, u, bare: fused.conv3x3_bias_act_x3(c, x, _zero_bias(c, b) if bare else b, not bare), False,
+     lambda c, r: ('conv3', False)),
+    ('x3-dilated', lambda c, x, b, r, u: c.dilation != (1, 1) and fused.conv3x3_dilated_x3_supported(c, x, b),
+     lambda c, x, b, r, u, bare: fused.conv3x3_dilated_bias_act_x3(c, x, _zero_bias(c, b) if bare else b, not bare), False,
+     lambda c, r: ('conv3d%d' % c.dilation[0], r is not None)),
+    ('gconv', lambda c, x, b, r, u: fused.gconv3x3_supported(c, x, b),
+     lambda c, x, b, r, u, bare: fused.gconv3x3_bias_act(c, x, None if bare else b, not bare), False, None),
+    ('bf16', lambda c, x, b, r, u: fused.conv3x3_bf16_supported(c, x, b, r),
+     lambda c, x, b, r, u, bare: fused.conv3x3_bias_act_bf16(c, x, b, r, relu=not bare), True, None),
+)
+
+
+def _zero_bias(conv, bias):
+    return fused.derived(conv, '_opa_zero_bias', (conv.weight,), lambda: torch.zeros_like(bias))
+
+
+def _conv3x3(conv, x, bias, residual=None, *, u=False, defer=False, skip=()):
+    """``relu(conv(x) + bias (+ residual))`` for a bias-free 3x3 ``conv`` of a ResNet through the first route of ``_CONV3_ROUTES`` that
+    takes it -> (the result, what is still owed).  A kernel without a residual operand runs bare where there is a residual, and
+    ``fused.bias_act_`` adds the rest, as behind MIOpen.  ``u``: ``winograd.takes``'s.  No route: MIOpen + ``bias_act_``, nothing owed;
+    with ``defer`` MIOpen's raw output, and owed is ``bias``: the caller's next GEMM applies bias + ReLU to its operand (``a_bias``).
+    ``skip``: names of routes not to try."""
+    for name, takes, run, adds_residual, pick_key in _CONV3_ROUTES:
+        if name in skip or not takes(conv, x, bias, residual, u):
+            continue
+        bare = residual is not None and not adds_residual
+        if pick_key is None:                    # (no closure on this path: it is the one every stride-1 block of a float32 step takes)
+            return _run_route(run, conv, x, bias, residual, u, bare), None
+        (kind, flag_b), s = pick_key(conv, residual), conv.stride[0]
+        return fused.pick(kind, fused.out_pixels(x, s), 9 * x.shape[1], conv.out_channels, s > 1, flag_b,
+                          lambda: _run_route(run, conv, x, bias, residual, u, bare),
+                          lambda: fused.bias_act_(conv(x), bias, residual)), None
+    return (conv(x), bias) if defer else (fused.bias_act_(conv(x), bias, residual), None)
+
+
+def _run_route(run, conv, x, bias, residual, u, bare):
+    out = run(conv, x, bias, residual, u, bare)
+    return fused.bias_act_(out, bias, residual) if bare else out
+
+
 class _Bottleneck(nn.Module):
     expansion = 4
 
@@ -82,31 +130,8 @@ class _Bottleneck(nn.Module):
     def forward(self, x):
         if self.fused:      # conv (no bias) -> ONE fused bias(+residual)+ReLU pass each
             out = fused.conv_bias_act(self.conv1, x, self.fb1)            # 1x1: fused MFMA GEMM
-            # 3x3: float32 stride 1 -> Winograd F(2x2, 3x3) in one HIP kernel, whose output transform adds the bias and applies
-            # the ReLU on the way out (nothing extra to read or write), so the expanding 1x1 is the plain GEMM ...
-            epilogue_done = True        # conv2's bias + ReLU applied by whatever ran it: nothing left for the next operand
-            if winograd.takes(self.conv2, out, self._wino):
-                out = winograd.run(self.conv2, out, bias=self.fb2, relu=True)
-            elif fused.conv3x3_x3_supported(self.conv2, out, self.fb2):  # ... float32 strided: implicit GEMM of the split-operand kernel
-                h = out                                                   # (or MIOpen + the epilogue pass, whichever is faster for the shape)
-                s = self.conv2.stride[0]
-                out = fused.pick('conv3', fused.out_pixels(h, s), 9 * h.shape[1], self.conv2.out_channels, s > 1, False,
-                                 lambda: fused.conv3x3_bias_act_x3(self.conv2, h, self.fb2, True),
-                                 lambda: fused.bias_act_(self.conv2(h), self.fb2))
-            elif self.conv2.dilation != (1, 1) and fused.conv3x3_dilated_x3_supported(self.conv2, out, self.fb2):
-                h = out                                                   # ... float32 dilated (block 5 under block5_dilation): the same
-                s, d = self.conv2.stride[0], self.conv2.dilation[0]      # implicit GEMM with its taps d apart, against MIOpen + the pass
-                out = fused.pick('conv3d%d' % d, fused.out_pixels(h, s), 9 * h.shape[1], self.conv2.out_channels, s > 1, False,
-                                 lambda: fused.conv3x3_dilated_bias_act_x3(self.conv2, h, self.fb2, True),
-                                 lambda: fused.bias_act_(self.conv2(h), self.fb2))
-            elif fused.gconv3x3_supported(self.conv2, out, self.fb2):    # ... float32 grouped (ResNeXt): one stencil kernel,
-                out = fused.gconv3x3_bias_act(self.conv2, out, self.fb2, True)        # bias + ReLU inside
-            elif fused.conv3x3_bf16_supported(self.conv2, out, self.fb2):  # ... bfloat16 behind OPA_CONV3_BF16: the implicit GEMM on
-                out = fused.conv3x3_bias_act_bf16(self.conv2, out, self.fb2, relu=True)   # the bf16 MFMA, bias + ReLU inside, one rounding
-            else:
-                out = self.conv2(out)                                     # ... bfloat16: MIOpen, raw output ...
-                epilogue_done = False
-            a_bias = None if epilogue_done else self.fb2
+            # 3x3: whatever route takes it; where none does, MIOpen's raw output, and conv2's bias + ReLU are owed to the next operand
+            out, a_bias = _conv3x3(self.conv2, out, self.fb2, u=self._wino, defer=True)
 
             def two_launches():
                 identity = x if self.downsample is None else self.downsample[0](x)
@@ -156,41 +181,15 @@ class _BasicBlock(nn.Module):
     wino_u1 = property(lambda self: self._wino_u(1), doc='like ``_Bottleneck.wino_u``, of ``conv1``')
     wino_u2 = property(lambda self: self._wino_u(2), doc='like ``_Bottleneck.wino_u``, of ``conv2``')
 
-    def _dilated(self, conv, x, bias, identity=None):
-        """``relu(conv(x) + bias (+ identity))`` for a dilated 3x3 convolution the split-operand kernel takes, else None.  The kernel
-        has no residual operand: with an identity it adds a zero bias and the epilogue pass adds the rest, as behind MIOpen."""
-        if conv.dilation == (1, 1) or not fused.conv3x3_dilated_x3_supported(conv, x, bias):
-            return None
-        s, d = conv.stride[0], conv.dilation[0]
-        if identity is None:
-            def run_x3():
-                return fused.conv3x3_dilated_bias_act_x3(conv, x, bias, True)
-        else:
-            zero = fused.derived(conv, '_opa_zero_bias', (conv.weight,), lambda: torch.zeros_like(bias))
-
-            def run_x3():
-                return fused.bias_act_(fused.conv3x3_dilated_bias_act_x3(conv, x, zero, False), bias, identity)
-        return fused.pick('conv3d%d' % d, fused.out_pixels(x, s), 9 * x.shape[1], conv.out_channels, s > 1, identity is not None,
-                          run_x3, lambda: fused.bias_act_(conv(x), bias, identity))
+    # The plain (d = 1) split-operand kernel is not tried, although the strided convolutions of resnet18/34 qualify: the exclusion is
+    # inherited from the block's first fused forward and has never been timed.  Lifting it changes what runs: with a measurement.
+    _SKIP = ('x3',)
 
     def forward(self, x):
         if self.fused:
             identity = x if self.downsample is None else self.downsample[0](x)
-            out = self._dilated(self.conv1, x, self.fb1)                  # (block 5 under block5_dilation)
-            if out is not None:
-                pass
-            elif winograd.takes(self.conv1, x, self._wino[0]):  # bias + ReLU in the kernel's output transform
-                out = winograd.run(self.conv1, x, bias=self.fb1, relu=True)
-            elif fused.conv3x3_bf16_supported(self.conv1, x, self.fb1):   # bfloat16 behind OPA_CONV3_BF16: bias + ReLU in the kernel
-                out = fused.conv3x3_bias_act_bf16(self.conv1, x, self.fb1, relu=True)
-            else:
-                out = fused.bias_act_(self.conv1(x), self.fb1)
-            if fused.conv3x3_bf16_supported(self.conv2, out, self.fb2, identity):      # ... and bias + identity + ReLU: no separate pass
-                return fused.conv3x3_bias_act_bf16(self.conv2, out, self.fb2, identity, relu=True)
-            last = self._dilated(self.conv2, out, self.fb2, identity)
-            if last is not None:
-                return last
-            return fused.bias_act_(winograd.conv_or_fallback(self.conv2, out, self._wino[1]), self.fb2, identity)
+            out = _conv3x3(self.conv1, x, self.fb1, u=self._wino[0], skip=self._SKIP)[0]
+            return _conv3x3(self.conv2, out, self.fb2, identity, u=self._wino[1], skip=self._SKIP)[0]       # (the bf16 kernel adds the identity)
         identity = x if self.downsample is None else self.downsample(x)
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.bn2(self.conv2(out))
@@ -369,14 +368,8 @@ class Resnet(BaseNetwork):
         else:
             x = fused.bias_act_(conv(x), self.fb0)
         if self.input_conv2_stride:
-            conv2, h = self.input_block[3][0], x
-            if fused.conv3x3_x3_supported(conv2, h, self.fb0_2):
-                s = conv2.stride[0]
-                x = fused.pick('conv3', fused.out_pixels(h, s), 9 * h.shape[1], conv2.out_channels, s > 1, False,
-                               lambda: fused.conv3x3_bias_act_x3(conv2, h, self.fb0_2, True),
-                               lambda: fused.bias_act_(conv2(h), self.fb0_2))
-            else:
-                x = fused.bias_act_(conv2(h), self.fb0_2)
+            # (the bf16 kernel would take this convolution and was never routed here: left out as inherited, never timed)
+            x = _conv3x3(self.input_block[3][0], x, self.fb0_2, skip=('bf16',))[0]
         return x
 
     def forward(self, x):
