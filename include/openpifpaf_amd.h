@@ -581,6 +581,24 @@ int opa_conv3x3_act_bf16(const void* x_dev, const void* w_dev, const float* bias
                          int32_t batch, int32_t h_in, int32_t w_in, int32_t c_in, int32_t c_out,
                          int32_t stride, int32_t dilation, int32_t relu, void* stream);
 
+/* The 7x7 RGB stem of a ResNet cast to bfloat16 (csrc/stem7x7_bf16.hip; reference network/basenetworks.py:71-150 runs it through
+ * torch.nn.Conv2d) as an implicit GEMM on the bf16 MFMA, float32 accumulation, ONE rounding at the store:
+ *     out[b, oy, ox, co] = bf16_rne(act(sum_{ky,kx,ci} x[b, ci, s*oy - 3 + ky, s*ox - 3 + kx] * w[co][ky * 24 + kx * 3 + ci] + bias[co]))
+ * x_dev: bf16 [batch, 3, h, w] read WHERE IT LIES: element (b, ci, y, x) at b * x_batch_stride + ci * x_channel_stride +
+ * y * x_row_stride + x * x_pixel_stride ELEMENTS from x_dev (NCHW, channels-last, a cropped view: any four positive strides; no copy
+ * is made); w_dev: bf16 [c_out][192], K-major, k = ky * 24 + kx * 3 + ci for ky, kx = 0 .. 6 and ci = 0 .. 2, ZEROS in the 45 other
+ * columns; bias_dev: FLOAT32 [c_out] or NULL (a bf16 folded bias upcast); out_dev: dense channels-last bf16 [batch, ho, wo, c_out],
+ * ho = (h - 1) / stride + 1 (wo alike).  s = stride 1 or 2, padding 3; relu 0 / 1 (a select in float32 behind the sums: NaN stays NaN).
+ * c_out % 64 == 0; x fewer than 2^31 elements from the first to the last addressed, out fewer than 2^31 elements; x_dev 2-B, w_dev,
+ * bias_dev and out_dev 16-B aligned (NULL passes).  A tap outside the image is not loaded: the padding contributes exactly zero
+ * whatever memory holds, an Inf or NaN pixel reaches exactly the windows that hold it, and no address outside x is read.  No
+ * workspace, no atomics: equal inputs give equal bits.  The checks in order -- null pointers, alignment, negative sizes, c_out, stride,
+ * x's strides, x's extent, out's size -- each with a message of its own; behind them batch, h or w == 0: OPA_OK, nothing runs;
+ * everything else outside this contract is OPA_ERR_INVALID_ARGUMENT. */
+int opa_stem7x7_act_bf16(const void* x_dev, int64_t x_batch_stride, int64_t x_channel_stride, int64_t x_row_stride,
+                         int64_t x_pixel_stride, const void* w_dev, const float* bias_dev, void* out_dev,
+                         int32_t batch, int32_t h, int32_t w, int32_t c_out, int32_t stride, int32_t relu, void* stream);
+
 /* 3x3 convolution, stride 1, padding 1, of an NHWC float32 activation as Winograd F(2x2, 3x3) in ONE kernel (input
  * transform -> sixteen float32 MFMA GEMMs -> output transform; csrc/winograd.hip): the bottleneck convolutions of the
  * ResNet trunk (reference network/basenetworks.py:71-150 runs them through torch.nn.Conv2d), 2.25x fewer multiplications

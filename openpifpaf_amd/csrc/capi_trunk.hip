@@ -336,6 +336,34 @@ int opa_conv3x3_act_bf16(const void* x_dev, const void* w_dev, const float* bias
                                           relu, E.st), "conv3x3_act_bf16", "conv3x3_bf16_kernel");
 }
 
+// the 7x7 RGB stem of a bfloat16 ResNet as an implicit GEMM on the bf16 MFMA (csrc/stem7x7_bf16.hip): one message per check, in this
+// order: null pointers, alignment, negative sizes, c_out, the stride, x's strides, x's extent, out's size; then the empty call; then the grid
+int opa_stem7x7_act_bf16(const void* x_dev, int64_t x_batch_stride, int64_t x_channel_stride, int64_t x_row_stride, int64_t x_pixel_stride,
+                         const void* w_dev, const float* bias_dev, void* out_dev, int32_t batch, int32_t h, int32_t w, int32_t c_out,
+                         int32_t stride, int32_t relu, void* stream) {
+    const Entry E("opa_stem7x7_act_bf16", stream);
+    if (!x_dev || !w_dev || !out_dev) return E.refuse("x_dev, w_dev and out_dev must not be NULL");
+    if (misaligned(1, {x_dev}) || misaligned(15, {w_dev, bias_dev, out_dev}))
+        return E.refuse("x_dev must be 2-B, w_dev / bias_dev / out_dev 16-B aligned");
+    if (batch < 0 || h < 0 || w < 0) return E.refuse("negative batch, h or w");
+    if (c_out <= 0 || c_out % 64 != 0) return E.refuse("c_out must be a positive multiple of 64");
+    if (stride != 1 && stride != 2) return E.refuse("stride must be 1 or 2");
+    if (x_batch_stride <= 0 || x_channel_stride <= 0 || x_row_stride <= 0 || x_pixel_stride <= 0)
+        return E.refuse("the four strides of x must be positive");
+    // 32-bit element offsets into both tensors (in double: no product of these arguments overflows it, and what it rounds is far
+    // above 2^31); the stride of a dimension of one element -- or of none -- addresses nothing
+    const double last = std::max(batch - 1.0, 0.0) * (double)x_batch_stride + 2.0 * (double)x_channel_stride +
+                        std::max(h - 1.0, 0.0) * (double)x_row_stride + std::max(w - 1.0, 0.0) * (double)x_pixel_stride;
+    if (last >= 2147483648.0) return E.refuse("x must span fewer than 2^31 elements, first to last addressed (32-bit offsets)");
+    const double ho = h > 0 ? (h - 1) / stride + 1 : 0, wo = w > 0 ? (w - 1) / stride + 1 : 0;
+    if ((double)batch * ho * wo * c_out >= 2147483648.0) return E.refuse("out must hold fewer than 2^31 elements (32-bit offsets)");
+    if (batch == 0 || h == 0 || w == 0) return OPA_OK;
+    // (grid.x; with out below 2^31 elements of at least 64 channels it holds today: it guards the launch should a limit above move)
+    if (stem7x7_bf16_workgroups(batch, h, w, c_out, stride) > 0x7fffffffll) return E.refuse("too many tiles for grid.x");
+    return E.launched(launch_stem7x7_bf16(x_dev, x_batch_stride, x_channel_stride, x_row_stride, x_pixel_stride, w_dev, bias_dev, out_dev,
+                                          batch, h, w, c_out, stride, relu, E.st), "stem7x7_act_bf16", "stem7x7_bf16_kernel");
+}
+
 // opa_conv3x3_winograd_f32 and opa_conv3x3_winograd_f32x3 (`x3`: u_dev holds the three bf16 planes of the filter)
 static int conv3x3_winograd(const char* fn, bool x3, const float* x_dev, const void* u_dev, const float* bias_dev, float* out_dev,
                             int32_t batch, int32_t h, int32_t w, int32_t c_in, int32_t c_out, int32_t relu, int32_t variant,

@@ -322,6 +322,14 @@ hipError_t launch_gemm_unit_act_bf16(const void* A, long long lda, const void* W
 long long conv3x3_bf16_workgroups(int B, int H, int W, int c_out, int S);
 hipError_t launch_conv3x3_bf16(const void* x, const void* w, const float* bias, const void* residual, void* out, int B, int H, int W,
                                int c_in, int c_out, int S, int D, int relu, hipStream_t st);
+// csrc/stem7x7_bf16.hip: the 7x7 RGB stem (padding 3) of a bf16 image read through its four element strides (batch xb, channel xc, row
+// xr, pixel xp: any layout) as an implicit GEMM on the bf16 MFMA: x [B, 3, H, W], w [c_out][192] (k = ky * 24 + kx * 3 + ci, zeros in
+// the padding columns), bias float32 [c_out] or null, out dense channels-last bf16 [B, Ho, Wo, c_out]; c_out % 64 == 0, S 1 or 2, the
+// strides positive; x's extent and out below 2^31 elements (anything else: hipErrorInvalidValue).
+// stem7x7_bf16_workgroups = grid.x of the launch.
+long long stem7x7_bf16_workgroups(int B, int H, int W, int c_out, int S);
+hipError_t launch_stem7x7_bf16(const void* x, long long xb, long long xc, long long xr, long long xp, const void* w, const float* bias,
+                               void* out, int B, int H, int W, int c_out, int S, int relu, hipStream_t st);
 hipError_t launch_gemm_f32_bias_act(const float* A, const float* W, const float* bias, const float* res, float* out,
                                     int M, int N, int K, int relu, hipStream_t st, const float* a_bias = nullptr);
 hipError_t launch_winograd_f23(const float* x, const float* U, float* y, const float* bias, int N, int H, int W, int Cin,

@@ -120,6 +120,12 @@ UNIT_BF16 = _switch('OPA_UNIT_BF16', '0')
 # switch is on and ``conv3x3_bf16_supported`` the kernel runs.  It ships OFF; the one timing is tools/gpu/conv3_bf16_times.py,
 # profiles/conv3_bf16/times.log, and switching the default is a change of its own that rests on it.
 CONV3_BF16 = _switch('OPA_CONV3_BF16', '0')
+# The 7x7 RGB stem of a ResNet cast to bfloat16, stride 1 or 2, as an implicit GEMM on the bf16 MFMA with the folded bias and the ReLU
+# inside (csrc/stem7x7_bf16.hip, ``stem7x7_bias_act_bf16``) instead of MIOpen's convolution and a separate epilogue pass; the image is
+# read where it lies, in any layout: OPA_STEM7_BF16=1 (or fused.STEM7_BF16 = True).  Never timed by ``pick``, no choice-table entry:
+# where the switch is on and ``stem7x7_bf16_supported`` the kernel runs.  It ships OFF; the one timing is
+# tools/gpu/stem7_bf16_times.py, profiles/stem7_bf16/times.log, and switching the default is a change of its own that rests on it.
+STEM7_BF16 = _switch('OPA_STEM7_BF16', '0')
 
 
 # ---- the choice table and the decision ---------------------------------------------------------------------------------------------
@@ -700,6 +706,64 @@ def stem7x7_bias_act_x3(conv, x, bias, relu=True):
     out = _empty_nhwc(x, conv.out_channels, (ho, wo), torch.float32)
     _launch('opa_conv_rows_f32x3', _ptr(xp), _ptr(w3), _ptr(bias), _ptr(out), B, H + 7, W + 7, 4, ho, wo, 2, 8, 32,
             conv.out_channels, int(bool(relu)), int(X3_TERMS))
+    return out
+
+
+STEM7_BF16_K = 192                        # kStem7Bf16K: 8 window rows (the eighth zeros) of 8 pixels (the eighth zeros) of 3 channels
+
+
+def stem7x7_bf16_weight_of(conv, bias=None):
+    """The operands of ``stem7x7_bias_act_bf16`` derived from the CURRENT ``conv.weight`` (``[N, 3, 7, 7]`` bfloat16) and the folded
+    ``bias`` the network keeps (``[N]`` bfloat16 or float32, or None): the weight as ``[N][192]``, K-major in the load plan's order
+    (csrc/stem7x7_bf16_plan.hpp) -- ``w[co][ky * 24 + kx * 3 + ci] = weight[co][ci][ky][kx]``, ZEROS in the columns ``kx = 7`` and
+    ``ky = 7`` that pad 147 to 192 -- and the bias as FLOAT32 (upcast exactly; None stays None).  Derived and cached (``derived``,
+    keyed on both tensors' storage and version): no buffer, no part of a state dict, computed again whenever the weight or the bias
+    was replaced, moved, converted or changed in place (``load_state_dict`` into an optimized model)."""
+    def make():
+        w = conv.weight.detach()
+        wk = w.new_zeros((w.shape[0], 8, 8, 3))
+        wk[:, :7, :7] = w.permute(0, 2, 3, 1)
+        return (wk.reshape(w.shape[0], STEM7_BF16_K), None if bias is None else bias.detach().to(torch.float32).contiguous())
+    return derived(conv, '_opa_w_stem7_bf16', (conv.weight, bias), make)
+
+
+def stem7x7_bf16_supported(conv, x, bias):
+    """Can ``stem7x7_bias_act_bf16(conv, x, bias)`` run?  The switch on; ``x`` a bfloat16 ``[B, 3, H, W]`` tensor on the GPU in ANY
+    layout with positive strides (channels-last, NCHW, a cropped view), outside autocast (whose parameters stay float32), nothing
+    that autograd follows; a 7x7 convolution with padding 3, no dilation, no groups and no bias of its own (the folded one arrives
+    separately: bfloat16 or float32, one element per output channel, or None), square stride 1 or 2, output channels a multiple of
+    64, bfloat16 weights on ``x``'s device; ``x`` fewer than 2^31 elements from the first to the last addressed, the output fewer
+    than 2^31 elements."""
+    if not (STEM7_BF16 and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and x.shape[1] == 3
+            and not torch.is_autocast_enabled()):
+        return False
+    if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad or (bias is not None and bias.requires_grad)):
+        return False
+    s = conv.stride[0]
+    if not (isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (7, 7) and conv.padding == (3, 3) and conv.dilation == (1, 1)
+            and conv.groups == 1 and conv.bias is None and conv.padding_mode == 'zeros' and conv.stride == (s, s) and s in (1, 2)
+            and conv.in_channels == 3 and conv.out_channels % 64 == 0
+            and conv.weight.dtype == torch.bfloat16 and conv.weight.device == x.device):
+        return False
+    if bias is not None and not (bias.dtype in (torch.bfloat16, torch.float32) and bias.device == x.device and bias.dim() == 1
+                                 and bias.numel() == conv.out_channels):
+        return False
+    last = sum((n - 1) * st for n, st in zip(x.shape, x.stride()))               # the last element addressed
+    return (min(x.shape) > 0 and min(x.stride()) > 0 and x.data_ptr() % 2 == 0 and last < 2 ** 31
+            and out_pixels(x, s) * conv.out_channels < 2 ** 31 and _lib.available())
+
+
+def stem7x7_bias_act_bf16(conv, x, bias, relu=True):
+    """``act(conv(x) + bias)`` for the 7x7 padding-3 stem of a bfloat16 ResNet on RGB input (reference ``network/basenetworks.py:71-150``),
+    stride 1 or 2, as ONE implicit GEMM on the bf16 MFMA (``opa_stem7x7_act_bf16``, csrc/stem7x7_bf16.hip): ``x`` is read through its
+    own four strides, whatever its layout -- no padded copy, no 4-channel copy --, float32 accumulation, one rounding; the result is
+    a dense channels-last bfloat16 tensor.  ``stem7x7_bf16_supported`` says whether this can run."""
+    wk, b32 = stem7x7_bf16_weight_of(conv, bias)
+    B, _, H, W = x.shape
+    s = conv.stride[0]
+    out = _empty_nhwc(x, conv.out_channels, _out_hw(x, s))
+    _launch('opa_stem7x7_act_bf16', _ptr(x), x.stride(0), x.stride(1), x.stride(2), x.stride(3), _ptr(wk), _ptr(b32), _ptr(out),
+            B, H, W, conv.out_channels, s, int(bool(relu)))
     return out
 
 

@@ -363,6 +363,10 @@ class Resnet(BaseNetwork):
                 x = fused.pick('stem', fused.out_pixels(x0, 2), 256, conv.out_channels,
                                True, False, lambda: fused.stem7x7_bias_act_x3(conv, x0, self.fb0),
                                lambda: fused.bias_act_(conv(x0), self.fb0))
+        elif fused.stem7x7_bf16_supported(conv, x, self.fb0):   # bfloat16 with fused.STEM7_BF16: one launch, bias + ReLU inside
+            x = fused.stem7x7_bias_act_bf16(conv, x, self.fb0)
+            if pool:
+                x = self._pooled(x)
         elif pool:                                          # torch's raw convolution (bfloat16, a stem stride other than 2)
             x = self._pooled(conv(x), self.fb0)
         else:
