@@ -599,6 +599,25 @@ int opa_stem7x7_act_bf16(const void* x_dev, int64_t x_batch_stride, int64_t x_ch
                          int64_t x_pixel_stride, const void* w_dev, const float* bias_dev, void* out_dev,
                          int32_t batch, int32_t h, int32_t w, int32_t c_out, int32_t stride, int32_t relu, void* stream);
 
+/* The tail of the first block of a stage of a ResNet cast to bfloat16 (csrc/gemm2_bf16.hip; reference network/basenetworks.py:71-150
+ * runs both convolutions through torch.nn.Conv2d): the block's last 1x1 convolution and its downsampling 1x1 convolution as ONE
+ * product on the bf16 MFMA, float32 accumulation, ONE rounding at the store -- the identity tensor is never written:
+ *     out[b, oy, ox, :] = bf16_rne(act([a1[m, 0:k1] | a2[b, s*oy, s*ox, 0:k2]] * wcat[n, 0:k1+k2]^T + bias[n])),  m = (b*ho + oy)*wo + ox
+ * a1_dev: dense bf16 [batch * ho * wo, k1] (the block's inner activation), NULL exactly when k1 == 0 (the strided 1x1 convolution
+ * alone); a2_dev: dense channels-last bf16 [batch, h_in, w_in, k2] (the block's input), read at stride s; ho = (h_in - 1) / stride + 1
+ * (wo alike); a_bias_dev: bf16 [k1] or NULL -- with it a1 is the RAW output of the preceding convolution and
+ * bf16_rne(max(a1[m, k] + a_bias[k], 0)) in float32 is what is multiplied (opa_gemm_pro_bias_act_bf16's arithmetic; a2 is taken as
+ * it is), it needs k1 > 0; wcat_dev: bf16 [n][k1 + k2], K-major (both weights side by side); bias_dev: FLOAT32 [n] or NULL (a bf16
+ * folded bias upcast); out_dev: dense bf16 [batch, ho, wo, n].  s = stride 1 or 2; relu 0 / 1 (a select in float32 behind the sums:
+ * NaN stays NaN).  k1 % 64 == 0, k2 % 64 == 0 and k2 > 0, n % 64 == 0; a2, a1 and out each fewer than 2^31 elements; all six pointers
+ * 16-B aligned (NULL passes).  A row of the tile behind the last output pixel is not loaded, and no address outside a1 or a2 is
+ * read.  No workspace, no atomics: equal inputs give equal bits.  The checks in order -- null pointers, alignment, negative sizes,
+ * k1, k2, n, stride, the three sizes -- each with a message of its own; behind them batch, h_in or w_in == 0: OPA_OK, nothing runs;
+ * everything else outside this contract is OPA_ERR_INVALID_ARGUMENT. */
+int opa_gemm2_bias_act_bf16(const void* a1_dev, int32_t k1, const void* a2_dev, int32_t k2, int32_t batch, int32_t h_in, int32_t w_in,
+                            int32_t stride, const void* a_bias_dev, const void* wcat_dev, const float* bias_dev, void* out_dev,
+                            int32_t n, int32_t relu, void* stream);
+
 /* 3x3 convolution, stride 1, padding 1, of an NHWC float32 activation as Winograd F(2x2, 3x3) in ONE kernel (input
  * transform -> sixteen float32 MFMA GEMMs -> output transform; csrc/winograd.hip): the bottleneck convolutions of the
  * ResNet trunk (reference network/basenetworks.py:71-150 runs them through torch.nn.Conv2d), 2.25x fewer multiplications

@@ -18,8 +18,8 @@
 //                      only behind it); an empty batch alone (h and w must be positive) for opa_stem3x3_actp, after every check
 //                      but those of the sizes' products, and for opa_groupnorm_actp (pixels, channels and groups must be positive),
 //                      after every check of its arguments but the limits and the workspace; an empty batch, h or w for
-//                      opa_conv3x3_act_bf16, after every check but the grid's.  opa_conv3x3_f32x3, opa_gemm2_*,
-//                      opa_conv_rows_*, Winograd, dwconv, squeeze-excite, interleave and the head epilogue refuse empties.
+//                      opa_conv3x3_act_bf16, opa_stem7x7_act_bf16 and opa_gemm2_bias_act_bf16, after every check but the grid's.
+//                      opa_conv3x3_f32x3, opa_gemm2_bias_act_f32x3, opa_conv_rows_*, Winograd, dwconv, squeeze-excite, interleave and the head epilogue refuse empties.
 //   last error         a call that succeeds leaves opa_last_error's text as it was.
 //   marks              the entry points that pass a kernel's name to Entry::launched mark the profile here; the launchers of the
 //                      others (dwconv, gconv, se, group norm, interleave, head epilogue, preprocessing) mark it themselves.
@@ -362,6 +362,34 @@ int opa_stem7x7_act_bf16(const void* x_dev, int64_t x_batch_stride, int64_t x_ch
     if (stem7x7_bf16_workgroups(batch, h, w, c_out, stride) > 0x7fffffffll) return E.refuse("too many tiles for grid.x");
     return E.launched(launch_stem7x7_bf16(x_dev, x_batch_stride, x_channel_stride, x_row_stride, x_pixel_stride, w_dev, bias_dev, out_dev,
                                           batch, h, w, c_out, stride, relu, E.st), "stem7x7_act_bf16", "stem7x7_bf16_kernel");
+}
+
+// a bfloat16 block's last 1x1 convolution and its downsampling 1x1 convolution as one product on the bf16 MFMA (csrc/gemm2_bf16.hip):
+// one message per check, in this order: null pointers, alignment, negative sizes, k1, k2, n, the stride, the sizes; then the empty call;
+// then the grid
+int opa_gemm2_bias_act_bf16(const void* a1_dev, int32_t k1, const void* a2_dev, int32_t k2, int32_t batch, int32_t h_in, int32_t w_in,
+                            int32_t stride, const void* a_bias_dev, const void* wcat_dev, const float* bias_dev, void* out_dev,
+                            int32_t n, int32_t relu, void* stream) {
+    const Entry E("opa_gemm2_bias_act_bf16", stream);
+    if (!a2_dev || !wcat_dev || !out_dev) return E.refuse("a2_dev, wcat_dev and out_dev must not be NULL");
+    if ((a1_dev == nullptr) != (k1 == 0)) return E.refuse("a1_dev must be NULL with k1 == 0 and with no other k1");
+    if (a_bias_dev && k1 <= 0) return E.refuse("a_bias_dev needs k1 > 0");
+    if (misaligned(15, {a1_dev, a2_dev, a_bias_dev, wcat_dev, bias_dev, out_dev})) return E.refuse("pointers must be 16-B aligned");
+    if (batch < 0 || h_in < 0 || w_in < 0) return E.refuse("negative batch, h_in or w_in");
+    if (k1 < 0 || k1 % 64 != 0) return E.refuse("k1 must be 0 or a positive multiple of 64");
+    if (k2 <= 0 || k2 % 64 != 0) return E.refuse("k2 must be a positive multiple of 64");
+    if (n <= 0 || n % 64 != 0) return E.refuse("n must be a positive multiple of 64");
+    if (stride != 1 && stride != 2) return E.refuse("stride must be 1 or 2");
+    // 32-bit element offsets into the three tensors (in double: exact up to 2^53, and no product of these arguments overflows it)
+    const double ho = h_in > 0 ? (h_in - 1) / stride + 1 : 0, wo = w_in > 0 ? (w_in - 1) / stride + 1 : 0;
+    if ((double)batch * h_in * w_in * k2 >= 2147483648.0) return E.refuse("a2 must hold fewer than 2^31 elements (32-bit offsets)");
+    if ((double)batch * ho * wo * k1 >= 2147483648.0) return E.refuse("a1 must hold fewer than 2^31 elements (32-bit offsets)");
+    if ((double)batch * ho * wo * n >= 2147483648.0) return E.refuse("out must hold fewer than 2^31 elements (32-bit offsets)");
+    if (batch == 0 || h_in == 0 || w_in == 0) return OPA_OK;
+    // (grid.x; with out below 2^31 elements of at least 64 channels it holds today: it guards the launch should a limit above move)
+    if (gemm2_bf16_workgroups(batch, h_in, w_in, n, stride) > 0x7fffffffll) return E.refuse("too many tiles for grid.x");
+    return E.launched(launch_gemm2_bf16(a1_dev, k1, a2_dev, k2, batch, h_in, w_in, stride, a_bias_dev, wcat_dev, bias_dev, out_dev, n, relu,
+                                        E.st), "gemm2_bias_act_bf16", a_bias_dev ? "gemm2_pro_bf16_kernel" : "gemm2_bf16_kernel");
 }
 
 // opa_conv3x3_winograd_f32 and opa_conv3x3_winograd_f32x3 (`x3`: u_dev holds the three bf16 planes of the filter)

@@ -330,6 +330,14 @@ hipError_t launch_conv3x3_bf16(const void* x, const void* w, const float* bias, 
 long long stem7x7_bf16_workgroups(int B, int H, int W, int c_out, int S);
 hipError_t launch_stem7x7_bf16(const void* x, long long xb, long long xc, long long xr, long long xp, const void* w, const float* bias,
                                void* out, int B, int H, int W, int c_out, int S, int relu, hipStream_t st);
+// csrc/gemm2_bf16.hip: a block's last 1x1 convolution and its downsampling 1x1 convolution as one product on the bf16 MFMA: a1 [M, k1]
+// dense bf16 (null with k1 == 0: the strided 1x1 convolution alone), x [B, H, W, k2] dense channels-last bf16 read at stride S, a_bias
+// bf16 [k1] or null (a1's owed bias + ReLU, applied while it is staged; not with k1 == 0), wcat [n][k1 + k2], bias float32 [n] or null,
+// out dense bf16 [B, Ho, Wo, n]; k1 % 64 == 0, k2 % 64 == 0, n % 64 == 0, S 1 or 2; x, M * k1 and M * n below 2^31 elements (anything
+// else: hipErrorInvalidValue).  gemm2_bf16_workgroups = grid.x of the launch.
+long long gemm2_bf16_workgroups(int B, int H, int W, int n, int S);
+hipError_t launch_gemm2_bf16(const void* a1, int k1, const void* x, int k2, int B, int H, int W, int S, const void* a_bias,
+                             const void* wcat, const float* bias, void* out, int n, int relu, hipStream_t st);
 hipError_t launch_gemm_f32_bias_act(const float* A, const float* W, const float* bias, const float* res, float* out,
                                     int M, int N, int K, int relu, hipStream_t st, const float* a_bias = nullptr);
 hipError_t launch_winograd_f23(const float* x, const float* U, float* y, const float* bias, int N, int H, int W, int Cin,

@@ -126,6 +126,14 @@ CONV3_BF16 = _switch('OPA_CONV3_BF16', '0')
 # where the switch is on and ``stem7x7_bf16_supported`` the kernel runs.  It ships OFF; the one timing is
 # tools/gpu/stem7_bf16_times.py, profiles/stem7_bf16/times.log, and switching the default is a change of its own that rests on it.
 STEM7_BF16 = _switch('OPA_STEM7_BF16', '0')
+# The downsampling 1x1 convolution of a ResNet cast to bfloat16 -- the first block of every stage -- on the bf16 MFMA
+# (csrc/gemm2_bf16.hip) instead of MIOpen: in a Bottleneck together with the block's last 1x1 convolution, the folded bias and the ReLU
+# as ONE product (``conv1x1_pair_bias_act_bf16``: the identity tensor is never written, one rounding instead of two), in a BasicBlock
+# as the strided 1x1 convolution alone (``conv1x1_strided_bf16``): OPA_PAIR_BF16=1 (or fused.PAIR_BF16 = True).  Never timed by
+# ``pick``, no choice-table entry: where the switch is on and ``pair_bf16_supported`` / ``conv1x1_strided_bf16_supported`` the kernel
+# runs.  It ships OFF; the one timing is tools/gpu/gemm2_bf16_times.py, profiles/gemm2_bf16/times.log, and switching the default is a
+# change of its own that rests on it.
+PAIR_BF16 = _switch('OPA_PAIR_BF16', '0')
 
 
 # ---- the choice table and the decision ---------------------------------------------------------------------------------------------
@@ -583,6 +591,107 @@ def conv1x1_pair_bias_act_x3(conv, dconv, h, x, bias, relu=True, a_bias=None):
     out = _empty_nhwc(h, n, dtype=torch.float32)
     _launch('opa_gemm2_bias_act_f32x3', _ptr(h), k1, _ptr(x), k2, B, H, W, dconv.stride[0], _ptr(ab), _ptr(w3), _ptr(bias),
             _ptr(out), n, int(bool(relu)), int(X3_TERMS))
+    return out
+
+
+# (k1, k2, n, stride) of products that ``opa_gemm2_bias_act_bf16`` can run but that came out SLOWER at batch 32 than what runs with the
+# switch off (tools/gpu/gemm2_bf16_times.py, profiles/gemm2_bf16/times.log): both predicates decline them.
+PAIR_BF16_DECLINED = frozenset()
+
+
+def pair_bf16_weight_of(conv, dconv, bias):
+    """The operands of ``conv1x1_pair_bias_act_bf16`` derived from the CURRENT weights (``conv``: ``[N, k1, 1, 1]``, ``dconv``:
+    ``[N, k2, 1, 1]``, bfloat16) and the folded ``bias`` the block keeps (``[N]`` bfloat16 or float32, or None): ``Wcat`` =
+    ``[W | Wd]`` as ``[N][k1 + k2]``, K-major, and the bias as FLOAT32 (upcast exactly; None stays None).  ``conv`` None: ``dconv``'s
+    weight alone, ``[N][k2]`` (``conv1x1_strided_bf16``).  Derived and cached on ``dconv`` (``derived``, keyed on the three tensors'
+    storage and version): no buffer, no part of a state dict, computed again whenever a weight or the bias was replaced, moved,
+    converted or changed in place (``load_state_dict`` into an optimized model)."""
+    n, k2 = dconv.out_channels, dconv.in_channels
+
+    def make():
+        wd = dconv.weight.detach().reshape(n, k2)
+        w = wd.contiguous() if conv is None else torch.cat((conv.weight.detach().reshape(n, conv.in_channels), wd), dim=1).contiguous()
+        return w, None if bias is None else bias.detach().to(torch.float32).contiguous()
+    return derived(dconv, '_opa_w_pair_bf16', (None if conv is None else conv.weight, dconv.weight, bias), make)
+
+
+def _dense_bf16(t, channels):
+    """``t``: a dense channels-last bfloat16 ``[B, channels, H, W]`` on the GPU, 16-byte aligned, nothing that autograd follows?"""
+    return (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 4 and t.shape[1] == channels
+            and t.is_contiguous(memory_format=torch.channels_last) and t.data_ptr() % 16 == 0
+            and not (torch.is_grad_enabled() and t.requires_grad))
+
+
+def _plain_1x1_bf16(conv, like):
+    """``conv``: a 1x1 ``Conv2d`` without groups, padding, dilation or a bias of its own, bfloat16 weights on ``like``'s device that
+    autograd does not follow?  (The stride is the caller's to test.)"""
+    return (isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (1, 1) and conv.groups == 1 and conv.padding == (0, 0)
+            and conv.dilation == (1, 1) and conv.bias is None and conv.weight.dtype == torch.bfloat16
+            and conv.weight.device == like.device and not (torch.is_grad_enabled() and conv.weight.requires_grad))
+
+
+def pair_bf16_supported(conv, dconv, h, x, bias, a_bias=None):
+    """Can ``conv1x1_pair_bias_act_bf16(conv, dconv, h, x, bias, ..., a_bias)`` run?  The switch on; ``h`` and ``x`` dense channels-last
+    bfloat16 tensors on the GPU of one batch, outside autocast (whose parameters stay float32), nothing that autograd follows; both
+    convolutions 1x1 without groups, padding or a bias of their own, ``conv`` of stride 1, ``dconv`` of square stride 1 or 2, equal
+    output channels; ``conv``'s input channels, ``dconv``'s and the output channels multiples of 64; ``h``'s pixels those of ``x`` at
+    ``dconv``'s stride; ``x``, ``h`` and the output fewer than 2^31 elements each; 16-byte boundaries; the folded ``bias`` bfloat16
+    or float32, one element per output channel, or None; ``a_bias`` (``h``'s owed bias, a ReLU behind it) bfloat16 ``[k1]``,
+    contiguous, 16-byte aligned, or None; the library built; ``(k1, k2, n, stride)`` not in ``PAIR_BF16_DECLINED``."""
+    if not (PAIR_BF16 and not torch.is_autocast_enabled() and _plain_1x1_bf16(dconv, x) and _plain_1x1_bf16(conv, x)):
+        return False
+    k1, k2, n, s = conv.in_channels, dconv.in_channels, conv.out_channels, dconv.stride[0]
+    if not (conv.stride == (1, 1) and dconv.stride == (s, s) and s in (1, 2) and dconv.out_channels == n
+            and k1 % 64 == 0 and k2 % 64 == 0 and n % 64 == 0 and _dense_bf16(h, k1) and _dense_bf16(x, k2)
+            and h.shape[0] == x.shape[0] and h.device == x.device and tuple(h.shape[2:]) == _out_hw(x, s)
+            and 0 < x.numel() < 2 ** 31 and h.numel() < 2 ** 31 and out_pixels(x, s) * n < 2 ** 31):
+        return False
+    if bias is not None and not (bias.dtype in (torch.bfloat16, torch.float32) and bias.device == x.device and bias.dim() == 1
+                                 and bias.numel() == n and not (torch.is_grad_enabled() and bias.requires_grad)):
+        return False
+    if a_bias is not None and not (a_bias.dtype == torch.bfloat16 and a_bias.device == x.device and a_bias.dim() == 1
+                                   and a_bias.numel() == k1 and a_bias.is_contiguous() and a_bias.data_ptr() % 16 == 0
+                                   and not (torch.is_grad_enabled() and a_bias.requires_grad)):
+        return False
+    return _lib.available() and (k1, k2, n, s) not in PAIR_BF16_DECLINED
+
+
+def conv1x1_pair_bias_act_bf16(conv, dconv, h, x, bias, relu=True, a_bias=None):
+    """``act(conv(h) + dconv(x) + bias)`` -- the last 1x1 convolution of a bfloat16 ResNet block and the block's downsampling
+    convolution (reference ``network/basenetworks.py:71-150``: torchvision's Bottleneck) -- as ONE product ``[h | x at stride] *
+    [W | Wd]^T`` on the bf16 MFMA (``opa_gemm2_bias_act_bf16``, csrc/gemm2_bf16.hip): float32 accumulation, one rounding; the identity
+    tensor is neither written nor read back.  With ``a_bias``, ``h`` is the raw output of the preceding convolution and
+    ``relu(h + a_bias)`` is applied while it is staged (``x`` is taken as it is).  ``pair_bf16_supported`` says whether this can run."""
+    k1, k2, n = conv.in_channels, dconv.in_channels, conv.out_channels
+    wcat, b32 = pair_bf16_weight_of(conv, dconv, bias)
+    B, _, H, W = x.shape
+    out = _empty_nhwc(h, n)
+    _launch('opa_gemm2_bias_act_bf16', _ptr(h), k1, _ptr(x), k2, B, H, W, dconv.stride[0], _ptr(a_bias), _ptr(wcat), _ptr(b32),
+            _ptr(out), n, int(bool(relu)))
+    return out
+
+
+def conv1x1_strided_bf16_supported(dconv, x):
+    """Can ``conv1x1_strided_bf16(dconv, x)`` run?  ``pair_bf16_supported``'s conditions on ``dconv`` and ``x`` alone: the product
+    without a first source (k1 = 0)."""
+    if not (PAIR_BF16 and not torch.is_autocast_enabled() and _plain_1x1_bf16(dconv, x)):
+        return False
+    k2, n, s = dconv.in_channels, dconv.out_channels, dconv.stride[0]
+    return (dconv.stride == (s, s) and s in (1, 2) and k2 % 64 == 0 and n % 64 == 0 and _dense_bf16(x, k2)
+            and 0 < x.numel() < 2 ** 31 and out_pixels(x, s) * n < 2 ** 31 and _lib.available()
+            and (0, k2, n, s) not in PAIR_BF16_DECLINED)
+
+
+def conv1x1_strided_bf16(dconv, x):
+    """``dconv(x)`` for the downsampling 1x1 convolution, stride 1 or 2, of a bfloat16 BasicBlock (reference
+    ``network/basenetworks.py:71-150``) on the bf16 MFMA: ``opa_gemm2_bias_act_bf16`` without a first source, a bias or a ReLU.
+    ``conv1x1_strided_bf16_supported`` says whether this can run."""
+    wd, _ = pair_bf16_weight_of(None, dconv, None)
+    B, k2, H, W = x.shape
+    s = dconv.stride[0]
+    out = _empty_nhwc(x, dconv.out_channels, _out_hw(x, s))
+    _launch('opa_gemm2_bias_act_bf16', _ptr(None), 0, _ptr(x), k2, B, H, W, s, _ptr(None), _ptr(wd), _ptr(None), _ptr(out),
+            dconv.out_channels, 0)
     return out
 
 

@@ -137,6 +137,10 @@ class _Bottleneck(nn.Module):
                 identity = x if self.downsample is None else self.downsample[0](x)
                 # (a_bias: conv2's bias + ReLU applied by the 1x1 GEMM while it stages its operand)
                 return fused.conv_bias_act(self.conv3, out, self.fb3, identity, a_bias=a_bias)
+            # a block WITH a downsampling convolution, bfloat16 with fused.PAIR_BF16: conv3(out) + downsample(x) as ONE launch on the
+            # bf16 MFMA, one rounding; conv2's bias + ReLU applied to the operand where conv2 left them out
+            if self.downsample is not None and fused.pair_bf16_supported(self.conv3, self.downsample[0], out, x, self.fb3, a_bias):
+                return fused.conv1x1_pair_bias_act_bf16(self.conv3, self.downsample[0], out, x, self.fb3, True, a_bias)
             # a block WITH a downsampling convolution, float32: conv3(out) + downsample(x) as ONE product (the identity tensor
             # is never written), conv2's bias + ReLU applied to the operand where conv2 left them out -- where that is faster
             if self.downsample is not None and fused.pair_supported(self.conv3, self.downsample[0], out, x, self.fb3, a_bias):
@@ -187,7 +191,12 @@ class _BasicBlock(nn.Module):
 
     def forward(self, x):
         if self.fused:
-            identity = x if self.downsample is None else self.downsample[0](x)
+            if self.downsample is None:
+                identity = x
+            elif fused.conv1x1_strided_bf16_supported(self.downsample[0], x):    # bfloat16 with fused.PAIR_BF16: the strided 1x1 on the bf16 MFMA
+                identity = fused.conv1x1_strided_bf16(self.downsample[0], x)
+            else:
+                identity = self.downsample[0](x)
             out = _conv3x3(self.conv1, x, self.fb1, u=self._wino[0], skip=self._SKIP)[0]
             return _conv3x3(self.conv2, out, self.fb2, identity, u=self._wino[1], skip=self._SKIP)[0]       # (the bf16 kernel adds the identity)
         identity = x if self.downsample is None else self.downsample(x)
