@@ -581,6 +581,29 @@ int opa_conv3x3_act_bf16(const void* x_dev, const void* w_dev, const float* bias
                          int32_t batch, int32_t h_in, int32_t w_in, int32_t c_in, int32_t c_out,
                          int32_t stride, int32_t dilation, int32_t relu, void* stream);
 
+/* The GROUPED 3x3 convolution of a ResNeXt cast to bfloat16 (csrc/gconv3x3_bf16.hip; reference network/basenetworks.py:71-150 runs it
+ * through torch.nn.Conv2d with groups = 32) as an implicit GEMM per 64-channel chunk on the bf16 MFMA, float32 accumulation, ONE
+ * rounding at the store.  As many output as input channels; the group width divides 64, so the 64 output channels of a chunk
+ * depend on its 64 input channels alone:
+ *     out[b, oy, ox, co] = bf16_rne(act(sum_{ky,kx} sum_{j<64} x[b, s*oy - d + d*ky, s*ox - d + d*kx, 64*(co/64) + j] * w[co][3*ky + kx][j]
+ *                                       + bias[co]))
+ * x_dev: dense channels-last bf16 [batch, h_in, w_in, channels]; w_dev: bf16 [channels][9][64] (K-major, K = 576): column j of row co
+ * holds the weight of input channel 64*(co/64) + j and is ZERO wherever j / group_width != (co % 64) / group_width (the caller packs
+ * it so; the kernel multiplies what it is given); bias_dev: FLOAT32 [channels] or NULL (a bf16 folded bias upcast); out_dev: dense
+ * bf16 [batch, ho, wo, channels], ho = (h_in - 1) / stride + 1 (wo alike).  s = stride 1 or 2; d = dilation = the padding, 1, or 2
+ * or 4 with stride 1; relu 0 / 1 (a select in float32 behind the sums: NaN stays NaN).  channels % 64 == 0; group_width 4, 8, 16, 32
+ * or 64 and below channels; x and out each fewer than 2^31 elements; all four pointers 16-B aligned (NULL passes).
+ * A tap outside the image is not loaded: the padding contributes exactly zero whatever memory holds, and no address outside x is
+ * read.  NON-FINITE VALUES: the off-group weights are zeros that the MFMA does multiply, so a NaN or Inf in an input channel reaches
+ * every output channel of the same 32-ALIGNED CHANNEL BLOCK (group_width 4, 8, 16) at the pixels whose window holds it, not only its
+ * own group's; with group_width 32 and 64 it reaches only its own group.  No workspace, no atomics: equal inputs give equal bits.
+ * The checks in order -- null pointers, alignment, negative sizes, channels, group_width, stride, dilation, x's size, out's size --
+ * each with a message of its own; behind them batch, h_in or w_in == 0: OPA_OK, nothing runs; everything else outside this contract
+ * is OPA_ERR_INVALID_ARGUMENT. */
+int opa_gconv3x3_act_bf16(const void* x_dev, const void* w_dev, const float* bias_dev, void* out_dev,
+                          int32_t batch, int32_t h_in, int32_t w_in, int32_t channels, int32_t group_width,
+                          int32_t stride, int32_t dilation, int32_t relu, void* stream);
+
 /* The 7x7 RGB stem of a ResNet cast to bfloat16 (csrc/stem7x7_bf16.hip; reference network/basenetworks.py:71-150 runs it through
  * torch.nn.Conv2d) as an implicit GEMM on the bf16 MFMA, float32 accumulation, ONE rounding at the store:
  *     out[b, oy, ox, co] = bf16_rne(act(sum_{ky,kx,ci} x[b, ci, s*oy - 3 + ky, s*ox - 3 + kx] * w[co][ky * 24 + kx * 3 + ci] + bias[co]))

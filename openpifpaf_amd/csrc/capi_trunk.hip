@@ -18,7 +18,8 @@
 //                      only behind it); an empty batch alone (h and w must be positive) for opa_stem3x3_actp, after every check
 //                      but those of the sizes' products, and for opa_groupnorm_actp (pixels, channels and groups must be positive),
 //                      after every check of its arguments but the limits and the workspace; an empty batch, h or w for
-//                      opa_conv3x3_act_bf16, opa_stem7x7_act_bf16 and opa_gemm2_bias_act_bf16, after every check but the grid's.
+//                      opa_conv3x3_act_bf16, opa_gconv3x3_act_bf16, opa_stem7x7_act_bf16 and opa_gemm2_bias_act_bf16, after every check
+//                      but the grid's.
 //                      opa_conv3x3_f32x3, opa_gemm2_bias_act_f32x3, opa_conv_rows_*, Winograd, dwconv, squeeze-excite, interleave and the head epilogue refuse empties.
 //   last error         a call that succeeds leaves opa_last_error's text as it was.
 //   marks              the entry points that pass a kernel's name to Entry::launched mark the profile here; the launchers of the
@@ -334,6 +335,34 @@ int opa_conv3x3_act_bf16(const void* x_dev, const void* w_dev, const float* bias
     if (conv3x3_bf16_workgroups(batch, h_in, w_in, c_out, stride) > 0x7fffffffll) return E.refuse("too many tiles for grid.x");
     return E.launched(launch_conv3x3_bf16(x_dev, w_dev, bias_dev, residual_dev, out_dev, batch, h_in, w_in, c_in, c_out, stride, dilation,
                                           relu, E.st), "conv3x3_act_bf16", "conv3x3_bf16_kernel");
+}
+
+// the grouped 3x3 convolution of a bfloat16 ResNeXt as an implicit GEMM per 64-channel chunk on the bf16 MFMA (csrc/gconv3x3_bf16.hip):
+// one message per check, in this order: null pointers, alignment, negative sizes, channels, group_width, the stride, the dilation, x's
+// size, out's size; then the empty call; then the grid
+int opa_gconv3x3_act_bf16(const void* x_dev, const void* w_dev, const float* bias_dev, void* out_dev,
+                          int32_t batch, int32_t h_in, int32_t w_in, int32_t channels, int32_t group_width,
+                          int32_t stride, int32_t dilation, int32_t relu, void* stream) {
+    const Entry E("opa_gconv3x3_act_bf16", stream);
+    if (!x_dev || !w_dev || !out_dev) return E.refuse("x_dev, w_dev and out_dev must not be NULL");
+    if (misaligned(15, {x_dev, w_dev, bias_dev, out_dev})) return E.refuse("pointers must be 16-B aligned");
+    if (batch < 0 || h_in < 0 || w_in < 0) return E.refuse("negative batch, h_in or w_in");
+    if (channels <= 0 || channels % 64 != 0) return E.refuse("channels must be a positive multiple of 64");
+    if (group_width != 4 && group_width != 8 && group_width != 16 && group_width != 32 && group_width != 64)
+        return E.refuse("group_width must be 4, 8, 16, 32 or 64");
+    if (group_width == channels) return E.refuse("group_width must be below channels (one group is the dense convolution)");
+    if (stride != 1 && stride != 2) return E.refuse("stride must be 1 or 2");
+    if (dilation != 1 && dilation != 2 && dilation != 4) return E.refuse("dilation must be 1, 2 or 4");
+    if (dilation > 1 && stride != 1) return E.refuse("a dilation above 1 needs stride 1");
+    // 32-bit element offsets into both tensors (in double: exact up to 2^53, and no product of these arguments overflows it)
+    const double ho = h_in > 0 ? (h_in - 1) / stride + 1 : 0, wo = w_in > 0 ? (w_in - 1) / stride + 1 : 0;
+    if ((double)batch * h_in * w_in * channels >= 2147483648.0) return E.refuse("x must hold fewer than 2^31 elements (32-bit offsets)");
+    if ((double)batch * ho * wo * channels >= 2147483648.0) return E.refuse("out must hold fewer than 2^31 elements (32-bit offsets)");
+    if (batch == 0 || h_in == 0 || w_in == 0) return OPA_OK;
+    // (grid.x; with out below 2^31 elements and 64 channels per tile it holds today: it guards the launch should a limit above move)
+    if (gconv3x3_bf16_workgroups(batch, h_in, w_in, channels, stride) > 0x7fffffffll) return E.refuse("too many tiles for grid.x");
+    return E.launched(launch_gconv3x3_bf16(x_dev, w_dev, bias_dev, out_dev, batch, h_in, w_in, channels, group_width, stride, dilation,
+                                           relu, E.st), "gconv3x3_act_bf16", "gconv3x3_bf16_kernel");
 }
 
 // the 7x7 RGB stem of a bfloat16 ResNet as an implicit GEMM on the bf16 MFMA (csrc/stem7x7_bf16.hip): one message per check, in this

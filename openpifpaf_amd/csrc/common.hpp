@@ -322,6 +322,14 @@ hipError_t launch_gemm_unit_act_bf16(const void* A, long long lda, const void* W
 long long conv3x3_bf16_workgroups(int B, int H, int W, int c_out, int S);
 hipError_t launch_conv3x3_bf16(const void* x, const void* w, const float* bias, const void* residual, void* out, int B, int H, int W,
                                int c_in, int c_out, int S, int D, int relu, hipStream_t st);
+// csrc/gconv3x3_bf16.hip: the GROUPED 3x3 convolution (as many output as input channels C, group width CG) of a dense channels-last bf16
+// tensor as an implicit GEMM per 64-channel chunk on the bf16 MFMA: x [B, H, W, C], w [C][9][64] block diagonal (column j of row co:
+// input channel 64 * (co / 64) + j; zero outside co's group), bias float32 [C] or null, out dense bf16 [B, Ho, Wo, C]; C % 64 == 0, CG
+// 4, 8, 16, 32 or 64 and below C, S 1 or 2, D = padding 1, or 2 or 4 with S = 1; x and out below 2^31 elements (anything else:
+// hipErrorInvalidValue).  gconv3x3_bf16_workgroups = grid.x of the launch.
+long long gconv3x3_bf16_workgroups(int B, int H, int W, int C, int S);
+hipError_t launch_gconv3x3_bf16(const void* x, const void* w, const float* bias, void* out, int B, int H, int W, int C, int CG, int S,
+                                int D, int relu, hipStream_t st);
 // csrc/stem7x7_bf16.hip: the 7x7 RGB stem (padding 3) of a bf16 image read through its four element strides (batch xb, channel xc, row
 // xr, pixel xp: any layout) as an implicit GEMM on the bf16 MFMA: x [B, 3, H, W], w [c_out][192] (k = ky * 24 + kx * 3 + ci, zeros in
 // the padding columns), bias float32 [c_out] or null, out dense channels-last bf16 [B, Ho, Wo, c_out]; c_out % 64 == 0, S 1 or 2, the

@@ -134,6 +134,14 @@ STEM7_BF16 = _switch('OPA_STEM7_BF16', '0')
 # runs.  It ships OFF; the one timing is tools/gpu/gemm2_bf16_times.py, profiles/gemm2_bf16/times.log, and switching the default is a
 # change of its own that rests on it.
 PAIR_BF16 = _switch('OPA_PAIR_BF16', '0')
+# The GROUPED 3x3 convolution of a ResNeXt cast to bfloat16 (``model.to(torch.bfloat16)``: conv2 of every Bottleneck, 32 groups of
+# 4 ... 64 channels, strided ones and the dilated ones of block 5 under ``block5_dilation`` included) as an implicit GEMM per 64-channel
+# chunk on the bf16 MFMA with the folded bias and the ReLU inside (csrc/gconv3x3_bf16.hip, ``gconv3x3_bias_act_bf16``) instead of torch's
+# grouped bfloat16 convolution, whose bias and ReLU the next GEMM's operand prologue then owes: OPA_GCONV_BF16=1 (or
+# fused.GCONV_BF16 = True).  Never timed by ``pick``, no choice-table entry: where the switch is on and ``gconv3x3_bf16_supported`` the
+# kernel runs.  It ships OFF; the one timing is tools/gpu/gconv_bf16_times.py, profiles/gconv_bf16/times.log, and switching the default
+# is a change of its own that rests on it.
+GCONV_BF16 = _switch('OPA_GCONV_BF16', '0')
 
 
 # ---- the choice table and the decision ---------------------------------------------------------------------------------------------
@@ -792,6 +800,66 @@ def conv3x3_bias_act_bf16(conv, x, bias, residual=None, relu=True):
     out = _empty_nhwc(x, conv.out_channels, _out_hw(x, s))
     _launch('opa_conv3x3_act_bf16', _ptr(x), _ptr(w9), _ptr(b32), _ptr(residual), _ptr(out), B, H, W, C, conv.out_channels, s,
             conv.dilation[0], int(bool(relu)))
+    return out
+
+
+GCONV_BF16_WIDTHS = (4, 8, 16, 32, 64)       # channels per group that divide the kernel's 64-channel chunk
+# (C, CG, stride) of grouped convolutions that ``opa_gconv3x3_act_bf16`` can run but that came out SLOWER at batch 32 than torch's grouped
+# bfloat16 convolution + ``bias_act_`` (tools/gpu/gconv_bf16_times.py, profiles/gconv_bf16/times.log): the predicate declines them.
+GCONV_BF16_DECLINED = frozenset()
+
+
+def gconv3x3_bf16_weight_of(conv, bias=None):
+    """The operands of ``gconv3x3_bias_act_bf16`` derived from the CURRENT ``conv.weight`` (``[C, CG, 3, 3]`` bfloat16, CG = C / groups)
+    and the folded ``bias`` the block keeps (``[C]`` bfloat16 or float32, or None): the weight as ``[C][9][64]``, K-major with K = 576
+    and BLOCK DIAGONAL per 64-channel chunk -- column ``j`` of row ``co`` is the weight of input channel ``64 * (co // 64) + j``:
+    ``weight[co, j % CG, ky, kx]`` where ``j // CG == (co % 64) // CG``, exactly zero elsewhere -- and the bias as FLOAT32 (upcast
+    exactly; None stays None).  Derived and cached (``derived``, keyed on both tensors' storage and version): no buffer, no part of a
+    state dict, computed again whenever the weight or the bias was replaced, moved, converted or changed in place
+    (``load_state_dict`` into an optimized model)."""
+    def make():
+        w = conv.weight.detach()
+        c, cg = w.shape[0], w.shape[1]
+        packed = w.new_zeros((c, 9, 64 // cg, cg))
+        rows = torch.arange(c, device=w.device)
+        packed[rows, :, (rows % 64) // cg, :] = w.permute(0, 2, 3, 1).reshape(c, 9, cg)
+        return (packed.reshape(c, 9, 64), None if bias is None else bias.detach().to(torch.float32).contiguous())
+    return derived(conv, '_opa_w_gconv_bf16', (conv.weight, bias), make)
+
+
+def gconv3x3_bf16_supported(conv, x, bias):
+    """Can ``gconv3x3_bias_act_bf16(conv, x, bias)`` run?  ``conv3x3_bf16_supported`` with these differences: the switch is
+    ``GCONV_BF16``; the convolution HAS groups; as many output as input channels C, C a multiple of 64, and a group width C / groups
+    of ``GCONV_BF16_WIDTHS``; no residual; ``(C, C // groups, stride)`` not in ``GCONV_BF16_DECLINED``."""
+    if not (GCONV_BF16 and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and not torch.is_autocast_enabled()):
+        return False
+    if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad or (bias is not None and bias.requires_grad)):
+        return False
+    s, d, c = conv.stride[0], conv.dilation[0], conv.in_channels
+    if not (conv.kernel_size == (3, 3) and conv.groups > 1 and conv.bias is None and conv.stride == (s, s) and s in (1, 2)
+            and conv.dilation == (d, d) and d in (1, 2, 4) and (d == 1 or s == 1) and conv.padding == (d, d)
+            and c == conv.out_channels and c % 64 == 0 and c % conv.groups == 0 and c // conv.groups in GCONV_BF16_WIDTHS
+            and x.shape[1] == c and conv.weight.dtype == torch.bfloat16 and conv.weight.device == x.device
+            and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0 and 0 < x.numel() < 2 ** 31
+            and out_pixels(x, s) * c < 2 ** 31):
+        return False
+    if bias is not None and not (bias.dtype in (torch.bfloat16, torch.float32) and bias.device == x.device and bias.dim() == 1
+                                 and bias.numel() == c):
+        return False
+    return _lib.available() and (c, c // conv.groups, s) not in GCONV_BF16_DECLINED
+
+
+def gconv3x3_bias_act_bf16(conv, x, bias, relu=True):
+    """``act(conv(x) + bias)`` for the grouped 3x3 convolution of a bfloat16 ResNeXt (reference ``network/basenetworks.py:71-150`` with
+    torchvision's grouped Bottleneck; ``:121-135``: block 5 dilated) as ONE implicit GEMM per 64-channel chunk on the bf16 MFMA
+    (``opa_gconv3x3_act_bf16``, csrc/gconv3x3_bf16.hip): float32 accumulation, one rounding -- bfloat16 in and out.
+    ``gconv3x3_bf16_supported`` says whether this can run."""
+    w9, b32 = gconv3x3_bf16_weight_of(conv, bias)
+    B, C, H, W = x.shape
+    s = conv.stride[0]
+    out = _empty_nhwc(x, C, _out_hw(x, s))
+    _launch('opa_gconv3x3_act_bf16', _ptr(x), _ptr(w9), _ptr(b32), _ptr(out), B, H, W, C, C // conv.groups, s, conv.dilation[0],
+            int(bool(relu)))
     return out
 
 

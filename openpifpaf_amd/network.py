@@ -67,6 +67,8 @@ _CONV3_ROUTES = (
      lambda c, x, b, r, u, bare: fused.gconv3x3_bias_act(c, x, None if bare else b, not bare), False, None),
     ('bf16', lambda c, x, b, r, u: fused.conv3x3_bf16_supported(c, x, b, r),
      lambda c, x, b, r, u, bare: fused.conv3x3_bias_act_bf16(c, x, b, r, relu=not bare), True, None),
+    ('gconv-bf16', lambda c, x, b, r, u: fused.gconv3x3_bf16_supported(c, x, b),
+     lambda c, x, b, r, u, bare: fused.gconv3x3_bias_act_bf16(c, x, None if bare else b, not bare), False, None),
 )
 
 
