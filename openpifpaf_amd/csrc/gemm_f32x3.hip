@@ -30,6 +30,8 @@
 // (ds_read_b128 fragments of 16 consecutive rows fall on 16 different bank groups AND the 8-byte plane stores of the split do
 // not collide: with rows padded to 80 B a third of the LDS cycles were store conflicts; profiles/r6/gemm_x3_swizzle_ab.log:
 // 2-7 % on the reduce shapes); XCD-aware tile order and epilogue as in gemm_f32.hip.
+// A third tile, 128 x 256 per 512-thread workgroup, for launches of six terms with N % 256 == 0 that are large enough for it:
+// gemm_f32x3_wide_kernel, further down, with a header of its own.
 // Block tails (RES): the last two K-steps used to request the last tile again (unconditional loads, nothing read them); the residual
 // of epilogue block 0 travels in those slots, block 1's from the epilogue's entry, the bias waits in LDS: layer-3 tail 0.81 -> 0.66 ms.
 //
@@ -40,6 +42,7 @@
 // activation into 0 before the split.  The stem's eighth window row and column meet zero weights, so a non-finite pixel
 // reaches every output whose 8x8 window holds it (0 x Inf), not the 7x7 ones alone: written down and pinned by a test.  Operands below 2^-110: see split_bf16.hpp; an element loses less than
 // 2^-125 sum_k (|a_mk| + |w_nk|).
+#include <cstdlib>
 #include <type_traits>
 #include "common.hpp"
 #include "split_bf16.hpp"
@@ -532,6 +535,334 @@ __global__ __launch_bounds__(256, OPA_X3_WGS) void gemm_f32x3_bias_act_kernel(
     }
 }
 
+// ---- The 128 x 256 tile: the two 256-thread workgroups a compute unit hosts above, as ONE of 512 threads that stages, and splits,
+// its 128-row activation tile ONCE for 256 output columns instead of once per 128.  Eight waves as 2(M) x 4(N); the wave tile is
+// the 64 x 64 of the 128-wide tile with the same accumulator sets, fragment maps and MFMA order (the leading product, then the
+// corrections smallest first), the same split, prologue and epilogue arithmetic: every output element sees the same additions in
+// the same order, the results are bit for bit those of the 128-wide tile (tests/test_gpu_gemm_x3_wide.py).  Six terms, not UNIT.
+// Per wave and K-step the activation loads (4 -> 2 x 16 B), the split (88 -> 44 VALU) and the plane stores (12 -> 6 ds_write_b64)
+// halve; MFMAs, fragment reads and weight staging stay what they were.
+// LDS (dynamic, 145 KB of the compute unit's 160): TWO stages of three planes x (128 + 256) rows x 64 B, the same XOR swizzle; the
+// epilogue's eight 8 KB patches alias stage 0; the tile's 256 bias values sit behind the stages.
+// Loop: ONE barrier per K-step.  Step k requests the weight of tile k + 1 and the activation of tile k + 2 (buffer loads, weight
+// first, unconditional), multiplies from stage k & 1, and splits and stores tile k + 1 into the other stage -- which every wave
+// finished reading before the barrier that ended step k - 1.  With one workgroup per compute unit nothing but the kernel itself
+// can put the split under MFMAs: every wave issues one VALU instruction of its split behind each of its MFMAs (see `step`).
+// The last two K-steps are peeled in EVERY instantiation: no tile is requested twice, a block tail's residual vectors of epilogue
+// block 0 travel in those slots as above.
+// What one workgroup per compute unit costs: nothing runs under a workgroup's epilogue, and the last round of a launch occupies
+// whole compute units where a 256-thread workgroup leaves half of one to its neighbour.  launch_x3 keeps the 128-wide tile where
+// that outweighs the halved staging (a round of workgroups that has only begun; a residual behind a short K loop):
+// x3_wide_pays, profiles/x3_wide/README.md.
+// The operand prologue is applied where the tile is split, not where it is requested (its a_bias vector travels with the tile):
+// the same float32 add and fmaxf on the same values.
+#if OPA_X3_BK == 32 && OPA_X3_SWIZZLE && !OPA_X3_ONE_ACC && OPA_X3_DIAG == 0
+#define OPA_X3_HAS_WIDE 1
+constexpr int kX3WideBN = 256, kX3WideThreads = 512;
+constexpr int kX3WideStageBytes = 3 * (kX3BM + kX3WideBN) * kX3Pitch * 2;          // 73 728
+constexpr int kX3WideLdsBytes = 2 * kX3WideStageBytes + kX3WideBN * 4;             // 148 480
+// Where launch_x3 takes this tile (measured: tools/gpu/gemm_x3_tile_ab.py, profiles/x3_wide/README.md).  ONE workgroup per compute
+// unit: W workgroups take ceil(W / 256) whole rounds on the 256 compute units of an MI355X, at about 15/16 of the time the 128-wide
+// tile needs for the same rows -- whose 2 W workgroups, two to a compute unit, end in a partial round that costs about a quarter
+// of one.  And nothing runs under a workgroup's epilogue: behind a residual it is long -- alone, the tile gains from K = 384 on, but
+// inside a resnet50 step the K = 512 tails of layer 4 did not: a residual only from K = 768 on.
+constexpr unsigned kX3WideCUs = 256;
+constexpr int kX3WideMinKRes = 768;
+constexpr bool x3_wide_pays(unsigned long long wide_blocks, bool res, int K) {
+    if (res && K < kX3WideMinKRes) return false;
+    const unsigned long long rounds = (wide_blocks + kX3WideCUs - 1) / kX3WideCUs;
+    return wide_blocks >= 2 * kX3WideCUs && rounds * kX3WideCUs * 15 <= (wide_blocks + kX3WideCUs / 4) * 16;
+}
+
+template <bool RES, bool RELU, bool PRO, int SRC>
+__global__ __launch_bounds__(kX3WideThreads, 2) void gemm_f32x3_wide_kernel(
+        const float* __restrict__ A, const unsigned short* __restrict__ W3, const float* __restrict__ bias,
+        const float* __restrict__ res, float* __restrict__ out, int M, int N, int K, const float* __restrict__ a_bias,
+        const X3Second sec) {
+    constexpr int BN = kX3WideBN, WN = 64, NT = 2;
+    constexpr int LDS_A = kX3BM * kX3Pitch, LDS_B = BN * kX3Pitch;        // bf16 elements of ONE plane
+    static_assert(kX3WideThreads / 64 * 32 * WN * 4 <= kX3WideStageBytes, "the epilogue patches alias stage 0 alone");
+    extern __shared__ __attribute__((aligned(16))) unsigned char x3w_smem[];
+    float* s_bias = reinterpret_cast<float*>(x3w_smem + 2 * kX3WideStageBytes);
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 2, wn = wave & 3;
+    const int n_tiles = N / BN;
+    const unsigned nwg = gridDim.x, xcd = blockIdx.x & 7u, in_xcd = blockIdx.x >> 3;
+    const unsigned q = nwg >> 3, r8 = nwg & 7u;
+    const unsigned logical = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + in_xcd;
+    const int m0 = (int)(logical / n_tiles) * kX3BM;
+    const int n0 = (int)(logical % n_tiles) * BN;
+
+    f32x16_t acc[2][NT], low[2][NT];
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+        for (int j = 0; j < NT; j++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) { acc[i][j][r] = 0.0f; low[i][j][r] = 0.0f; }
+
+    // staging maps.  A: a 32-float row is 8 x 16 B, 512 threads cover 64 rows per pass, two passes.  W3: a 32-bf16 row of one plane
+    // is 4 x 16 B, 512 threads cover 128 rows of a plane: vector t of a thread is plane t / 2, row (t % 2) * 128 + tid / 4 -- ONE
+    // offset per thread, plane and half as the load's scalar offset and the store's immediate (the swizzle has a period of 16 rows)
+    constexpr int VA = kX3BK / 4, RPP = kX3WideThreads / VA, NPA = kX3BM / RPP, WV = 6;
+    static_assert(NPA == 2 && 3 * BN * (kX3BK / 8) == WV * kX3WideThreads, "staging maps");
+    const int s_row = tid / VA, s_col = (tid % VA) * 4;
+    f32x4_t ra0[NPA], ra1[NPA], ab0, ab1;      // the activation travels TWO K-steps ahead, the weight one
+    u32x4_t rb[WV];
+    constexpr bool TWO = SRC == 1, TAPS = SRC == 2;
+    const int rows_here = M - m0 < kX3BM ? M - m0 : kX3BM;
+    const int KA = TWO ? sec.K1 : TAPS ? sec.C : K;
+    const int shift = TAPS && !sec.padded ? sec.dil * (sec.wi + 1) * sec.pix : 0;
+    const float* a1_base = TAPS ? A - (size_t)shift : A + (size_t)m0 * KA;
+    const int a1_bytes = TAPS ? (int)(((size_t)sec.batch * sec.hi_wi * sec.pix + shift) * 4) : (int)((size_t)rows_here * KA * 4);
+    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a1_base), 0, a1_bytes, 0x00020000);
+    const int K2 = K - KA;
+    auto in_row = [&](int m) -> long long {
+        const int b = m / sec.ho_wo, r = m - b * sec.ho_wo, oy = r / sec.wo, ox = r - oy * sec.wo;
+        return (long long)b * sec.hi_wi + (long long)oy * sec.stride * sec.wi + (long long)ox * sec.stride;
+    };
+    long long row0_2 = 0;
+    const float* a2_base = nullptr;
+    int a2_bytes = 0;
+    unsigned pa2[NPA];
+    if constexpr (TWO) {
+        row0_2 = in_row(__builtin_amdgcn_readfirstlane(m0));
+        const int m_end = m0 + rows_here - 1;
+        a2_base = sec.A2 + (size_t)row0_2 * K2;
+        a2_bytes = (int)((size_t)(in_row(__builtin_amdgcn_readfirstlane(m_end)) - row0_2 + 1) * K2 * 4);
+    }
+    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<unsigned short*>(W3 + (size_t)n0 * K), 0, (int)(((size_t)3 * N - n0) * K * 2), 0x00020000);
+    unsigned pa[NPA], vmask[NPA];
+#pragma unroll
+    for (int p = 0; p < NPA; p++) {            // rows past M read row M - 1 (valid memory; the epilogue never stores them)
+        int m = m0 + p * RPP + s_row;
+        if (m > M - 1) m = M - 1;
+        pa[p] = ((unsigned)(m - m0) * (unsigned)KA + (unsigned)s_col) * 4u;
+        vmask[p] = 0u;
+        if constexpr (TAPS) {
+            const int b = m / sec.ho_wo, r = m - b * sec.ho_wo, oy = r / sec.wo, ox = r - oy * sec.wo;
+            pa[p] = (unsigned)((long long)b * sec.hi_wi + (long long)oy * sec.stride * sec.wi + (long long)ox * sec.stride) * (unsigned)sec.pix * 4u
+                    + (unsigned)s_col * 4u;
+            if (sec.padded) vmask[p] = 0xffffffffu;
+            else
+                for (int t = 0; t < sec.ntaps; t++) {
+                    const int iy = oy * sec.stride - sec.dil + sec.dil * (t / sec.taps_x), ix = ox * sec.stride - sec.dil + sec.dil * (t % sec.taps_x);
+                    if (iy >= 0 && iy < sec.hi && ix >= 0 && ix < sec.wi) vmask[p] |= 1u << t;
+                }
+        }
+        if constexpr (TWO) pa2[p] = ((unsigned)(in_row(m) - row0_2) * (unsigned)K2 + (unsigned)s_col) * 4u;
+    }
+    const unsigned pb = ((unsigned)(tid >> 2) * (unsigned)K + (unsigned)(tid & 3) * 8u) * 2u;
+    const int sb_off = x3_lds(tid >> 2, (tid & 3) * 8);
+    const int sa_off = x3_lds(s_row, s_col);
+    auto fetch_a = [&](f32x4_t (&ra)[NPA], f32x4_t& ab, int k0) {        // global -> registers for K-step k0
+        if constexpr (TAPS) {
+            const int t = k0 / KA, kc = k0 - t * KA;
+            const int soff = (int)((((unsigned)(sec.dil * (t / sec.taps_x)) * (unsigned)sec.wi + (unsigned)(sec.dil * (t % sec.taps_x))) * (unsigned)sec.pix + (unsigned)kc) * 4u);
+#pragma unroll
+            for (int p = 0; p < NPA; p++)
+                ra[p] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, (vmask[p] >> t) & 1u ? pa[p] : 0xFFFFFFF0u, soff, 0));
+        } else if constexpr (TWO) {
+            const bool second = k0 >= KA;
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<float*>(second ? a2_base : a1_base), 0, second ? a2_bytes : a1_bytes, 0x00020000);
+            const int ks = (second ? k0 - KA : k0) * 4;
+#pragma unroll
+            for (int p = 0; p < NPA; p++)
+                ra[p] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rs, second ? pa2[p] : pa[p], ks, 0));
+        } else {
+#pragma unroll
+            for (int p = 0; p < NPA; p++) ra[p] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, pa[p], k0 * 4, 0));
+        }
+        if (PRO) ab = *reinterpret_cast<const f32x4_t*>(a_bias + k0 + s_col);
+    };
+    auto fetch_b = [&](int k0) {
+#pragma unroll
+        for (int t = 0; t < WV; t++)
+            rb[t] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(
+                w_rsrc, pb, (int)((((unsigned)(t >> 1) * (unsigned)N + (unsigned)(t & 1) * 128u) * (unsigned)K + (unsigned)k0) * 2u), 0));
+    };
+    auto store_a = [&](const f32x4_t (&ra)[NPA], const f32x4_t& ab, int stage) {    // prologue, split, three plane stores
+        unsigned short* sA = reinterpret_cast<unsigned short*>(x3w_smem + stage * kX3WideStageBytes);
+#pragma unroll
+        for (int p = 0; p < NPA; p++) {
+            f32x4_t v = ra[p];
+            if (PRO) {
+#pragma unroll
+                for (int e = 0; e < 4; e++) v[e] = fmaxf(v[e] + ab[e], 0.0f);
+            }
+            u32x2_t p1, p2, p3;
+            split4(v, p1, p2, p3);
+            unsigned short* d = sA + sa_off + p * RPP * kX3Pitch;
+            *reinterpret_cast<u32x2_t*>(d) = p1;
+            *reinterpret_cast<u32x2_t*>(d + LDS_A) = p2;
+            *reinterpret_cast<u32x2_t*>(d + 2 * LDS_A) = p3;
+        }
+    };
+    auto store_b = [&](int stage) {
+        unsigned short* sB = reinterpret_cast<unsigned short*>(x3w_smem + stage * kX3WideStageBytes) + 3 * LDS_A;
+#pragma unroll
+        for (int t = 0; t < WV; t++)
+            *reinterpret_cast<u32x4_t*>(sB + (t >> 1) * LDS_B + (t & 1) * 128 * kX3Pitch + sb_off) = rb[t];
+    };
+    // the residual of a block tail in the epilogue's own layout, as in the 128-wide tile (the wave tile is the same 64 x 64)
+    constexpr int VEC_PER_ROW = WN / 4, VPL = 32 * VEC_PER_ROW / 64, VRA = 1;
+    f32x4_t rres[2][RES ? VPL : 1];
+    auto fetch_res = [&](int i, int t_begin, int t_end) {
+        if constexpr (RES) {
+            const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<float*>(res + (size_t)m0 * N + n0), 0, (int)(((size_t)(rows_here - 1) * N + BN) * 4), 0x00020000);
+            const int lrow = wm * 64 + lane / VEC_PER_ROW;
+            const unsigned off = ((unsigned)lrow * (unsigned)N + (unsigned)(wn * WN + (lane % VEC_PER_ROW) * 4)) * 4u;
+#pragma unroll
+            for (int t = t_begin; t < t_end; t++) {
+                const int urow = i * 32 + t * (64 / VEC_PER_ROW);
+                rres[i][t] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(
+                    r_rsrc, lrow < rows_here - urow ? off : 0xFFFFFFF0u, urow * N * 4, 0));
+            }
+        }
+    };
+    // fragment BYTE offsets of the wave's first A and B rows for the two halves of a K-step, opaque (the steps are copies of one
+    // another: put together from pieces they would stay live, and spill, across the K loop)
+    int frag_a[2], frag_b[2];
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        frag_a[h] = 2 * x3_lds(wm * 64 + (lane & 31), h * 16 + (lane >> 5) * 8);
+        frag_b[h] = 2 * (3 * LDS_A + x3_lds(wn * WN + (lane & 31), h * 16 + (lane >> 5) * 8));
+        asm volatile("" : "+v"(frag_a[h]), "+v"(frag_b[h]));
+    }
+    auto multiply = [&](int stage) {
+        const unsigned char* base = x3w_smem + stage * kX3WideStageBytes;
+#pragma unroll
+        for (int kh = 0; kh < 2; kh++) {
+            bf16x8_t fa[3][2], fb[3][NT];
+#pragma unroll
+            for (int pl = 0; pl < 3; pl++) {
+#pragma unroll
+                for (int i = 0; i < 2; i++)
+                    fa[pl][i] = *reinterpret_cast<const bf16x8_t*>(reinterpret_cast<const unsigned short*>(base + frag_a[kh]) + (pl * LDS_A + i * 32 * kX3Pitch));
+#pragma unroll
+                for (int j = 0; j < NT; j++)
+                    fb[pl][j] = *reinterpret_cast<const bf16x8_t*>(reinterpret_cast<const unsigned short*>(base + frag_b[kh]) + (pl * LDS_B + j * 32 * kX3Pitch));
+            }
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+#pragma unroll
+                for (int j = 0; j < NT; j++)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0][i], fb[0][j], acc[i][j], 0, 0, 0);
+            // the corrections, smallest first
+#pragma unroll
+            for (int s = 2; s >= 1; s--) {
+#pragma unroll
+                for (int pa_ = 0; pa_ < 3; pa_++) {
+                    const int pb_ = s - pa_;
+                    if (pb_ < 0 || pb_ > 2) continue;
+#pragma unroll
+                    for (int i = 0; i < 2; i++)
+#pragma unroll
+                        for (int j = 0; j < NT; j++)
+                            low[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[pa_][i], fb[pb_][j], low[i][j], 0, 0, 0);
+                }
+            }
+        }
+    };
+    // one K-step: stage `stage` holds tile k0, `cur` the activation of tile k0 + BK (requested a step ago), `nxt` is free.
+    // `tail` 0: any step but the last two.  1: step k_last - BK requests the last weight tile and no activation; 2: step k_last
+    // requests and stores nothing.  A block tail's residual of epilogue block 0 travels in the slots that are free there.
+    auto step = [&](auto tail, auto stage_c, int k0, f32x4_t (&cur)[NPA], f32x4_t& cur_ab, f32x4_t (&nxt)[NPA], f32x4_t& nxt_ab) {
+        constexpr int TAIL = decltype(tail)::value, STAGE = decltype(stage_c)::value;
+        if constexpr (TAIL == 0) {
+            fetch_b(k0 + kX3BK);
+            fetch_a(nxt, nxt_ab, k0 + 2 * kX3BK);
+        } else if constexpr (TAIL == 1) {
+            fetch_b(k0 + kX3BK);
+            fetch_res(0, 0, VRA);
+        } else {
+            fetch_res(0, VRA, VPL);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        multiply(STAGE);
+        if constexpr (TAIL != 2) {
+            // The split rides in the MFMAs' shadow INSIDE each wave: one of its VALU instructions behind each of the first 44 MFMAs
+            // (an MFMA occupies its pipe for 8 passes; the wave issues other work meanwhile).  Measured against the two shifts of
+            // winograd_f23_w8_kernel -- the second wave of a SIMD splitting first, multiplying second -- this order was faster on
+            // ten of thirteen shapes, and so was no shift at all (profiles/x3_wide/README.md): all eight waves meet at one
+            // barrier per K-step, which leaves two shifts little room to drift apart.
+            store_a(cur, cur_ab, STAGE ^ 1);
+#pragma unroll
+            for (int g = 0; g < 44; g++) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);         // one MFMA,
+                __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);         // one VALU instruction
+            }
+            store_b(STAGE ^ 1);
+        }
+        __syncthreads();                       // the other stage is written, this one read by every wave
+    };
+    const float bias_v = bias[n0 + (tid & (BN - 1))];      // (requested first: its wait leaves the tiles in flight)
+    fetch_b(0);
+    fetch_a(ra0, ab0, 0);
+    fetch_a(ra1, ab1, kX3BK);                  // (K is a multiple of 2 BK: the launcher checks)
+    if (tid < BN) s_bias[tid] = bias_v;
+    store_a(ra0, ab0, 0);
+    store_b(0);
+    __syncthreads();
+    constexpr std::integral_constant<int, 0> c0{};
+    constexpr std::integral_constant<int, 1> c1{};
+    constexpr std::integral_constant<int, 2> c2{};
+    int k0 = 0;
+    for (; k0 < K - 2 * kX3BK; k0 += 2 * kX3BK) {
+        step(c0, c0, k0, ra1, ab1, ra0, ab0);
+        step(c0, c1, k0 + kX3BK, ra0, ab0, ra1, ab1);
+    }
+    step(c1, c0, k0, ra1, ab1, ra0, ab0);
+    step(c2, c1, k0 + kX3BK, ra0, ab0, ra1, ab1);
+
+    // epilogue: as the 128-wide tile's, one 32-row block of the wave tile at a time through a wave-private f32 patch
+    float* patch = reinterpret_cast<float*>(x3w_smem) + wave * (32 * WN);
+    if constexpr (RES) {
+        fetch_res(1, 0, VPL);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+#pragma unroll
+        for (int j = 0; j < NT; j++) {
+            const int col = j * 32 + (lane & 31);
+            const float b = s_bias[wn * WN + col];
+#pragma unroll
+            for (int r = 0; r < 16; r++) {     // C layout: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+                const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                patch[row * WN + col] = acc[i][j][r] + low[i][j][r] + b;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int t = 0; t < VPL; t++) {
+            const int v = t * 64 + lane;
+            const int row = v / VEC_PER_ROW, c4 = (v % VEC_PER_ROW) * 4;
+            const int m = m0 + wm * 64 + i * 32 + row;
+            if (m < M) {
+                f32x4_t f = *reinterpret_cast<const f32x4_t*>(patch + row * WN + c4);
+                if constexpr (RES) f += rres[i][t];
+                if (RELU) {
+#pragma unroll
+                    for (int e = 0; e < 4; e++) f[e] = fmaxf(f[e], 0.0f);
+                }
+                *reinterpret_cast<f32x4_t*>(out + (size_t)m * N + n0 + wn * WN + c4) = f;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        asm volatile("" ::: "memory");
+    }
+}
+#else
+#define OPA_X3_HAS_WIDE 0
+#endif
+
 enum X3Mode { kX3Plain = 0, kX3Pair = 1, kX3Taps = 2, kX3Unit = 3 };      // SRC 0, 1, 2; UNIT (whose SRC is 0)
 
 // The instantiations that exist, 89: launch_x3 launches these and refuses everything else.
@@ -552,6 +883,33 @@ static hipError_t launch_x3(X3Mode mode, const float* A, const unsigned short* W
     const int bn = mode != kX3Unit ? (N % 128 == 0 ? 128 : 64)
                                    : (N % 128 == 0 && terms == 6 ? 128 : 64);
     const unsigned blocks = (unsigned)((long long)((M + kX3BM - 1) / kX3BM) * (N / bn));
+#if OPA_X3_HAS_WIDE
+    // The 128 x 256 tile: not UNIT, six terms, N a multiple of 256, and a launch for which x3_wide_pays.  OPA_X3_TILE = 128 | 256
+    // overrides the latter -- never the first three conditions -- and is read on every launch: A/B runs and the tests switch
+    // tiles inside one process.
+    if (mode != kX3Unit && terms == 6 && N % kX3WideBN == 0) {
+        const char* env = std::getenv("OPA_X3_TILE");
+        const int forced = env && *env ? std::atoi(env) : 0;
+        const unsigned wide_blocks = blocks / 2;
+        if (forced == kX3WideBN || (forced != 128 && x3_wide_pays(wide_blocks, third != nullptr, K)))
+            return with_value<kX3Plain, kX3Pair, kX3Taps>(mode, [&](auto MODE) {
+            return with_flag(third != nullptr, [&](auto RES) {
+            return with_flag(relu, [&](auto RELU) {
+            return with_flag(a_bias != nullptr, [&](auto PRO) {
+                constexpr int SRC = (int)decltype(MODE)::value;
+                if constexpr (x3_exists(kX3WideBN, RES, RELU, PRO, 6, SRC, false, 0)) {
+                    auto* kernel = &gemm_f32x3_wide_kernel<RES, RELU, PRO, SRC>;
+                    // (per device, not per process: set on every launch)
+                    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kX3WideLdsBytes);
+                    if (e != hipSuccess) return e;
+                    kernel<<<wide_blocks, kX3WideThreads, kX3WideLdsBytes, st>>>(A, W3, bias, third, out, M, N, K, a_bias, sec);
+                    return hipGetLastError();
+                } else {
+                    return hipErrorInvalidValue;
+                }
+            }); }); }); });
+    }
+#endif
     return with_value<64, 128>(bn, [&](auto BN) {
     return with_value<6, 9>(terms == 6 ? 6 : 9, [&](auto TERMS) {
     return with_value<kX3Plain, kX3Pair, kX3Taps, kX3Unit>(mode, [&](auto MODE) {
