@@ -424,6 +424,17 @@ int opa_gemm_pro_bias_act_bf16(const void* a_dev, const void* a_bias_dev, const 
                                const void* residual_dev, void* out_dev, int64_t m, int32_t n, int32_t k,
                                int32_t relu, void* stream);
 
+/* Both of the above for FLOAT16 operands (dtype code 1: a, a_bias, w, bias, residual and out all float16) on v_mfma_f32_32x32x16_f16:
+ * the same kernel (csrc/gemm_epilogue.hip) with the element type as its template parameter, the same contract, checks and messages
+ * under these names.  float32 accumulation, one rounding to float16 at the store, round to nearest even: what rounds beyond 65504
+ * becomes +-inf, NaN stays NaN (also through the ReLU, a select here), a result below 2^-14 keeps its subnormal bits --
+ * tensor.to(torch.float16) bit for bit.  The prologue is relu(a + a_bias) in float32 rounded once to float16: opa_bias_act with dtype 1. */
+int opa_gemm_bias_act_f16(const void* a_dev, const void* w_dev, const void* bias_dev, const void* residual_dev,
+                          void* out_dev, int64_t m, int32_t n, int32_t k, int32_t relu, void* stream);
+int opa_gemm_pro_bias_act_f16(const void* a_dev, const void* a_bias_dev, const void* w_dev, const void* bias_dev,
+                              const void* residual_dev, void* out_dev, int64_t m, int32_t n, int32_t k,
+                              int32_t relu, void* stream);
+
 /* Both of the above in float32 (v_mfma_f32_32x32x2f32, f32 operands and accumulation): the network at the
  * reference's precision.  a_bias_dev may be NULL (no prologue).  K % 32 == 0, N % 64 == 0, pointers 16-B aligned. */
 int opa_gemm_bias_act_f32(const float* a_dev, const float* a_bias_dev, const float* w_dev, const float* bias_dev,
@@ -581,6 +592,13 @@ int opa_conv3x3_act_bf16(const void* x_dev, const void* w_dev, const float* bias
                          int32_t batch, int32_t h_in, int32_t w_in, int32_t c_in, int32_t c_out,
                          int32_t stride, int32_t dilation, int32_t relu, void* stream);
 
+/* opa_conv3x3_act_bf16 for a ResNet cast to FLOAT16, on v_mfma_f32_32x32x16_f16: the same kernel with the element type as its template
+ * parameter -- x, w, residual and out float16 where the twin has bf16, bias_dev FLOAT32 as there -- and the same contract, checks and
+ * messages under this name.  The store is float16's round to nearest even: beyond 65504 +-inf, NaN stays NaN, subnormal results kept. */
+int opa_conv3x3_act_f16(const void* x_dev, const void* w_dev, const float* bias_dev, const void* residual_dev, void* out_dev,
+                        int32_t batch, int32_t h_in, int32_t w_in, int32_t c_in, int32_t c_out,
+                        int32_t stride, int32_t dilation, int32_t relu, void* stream);
+
 /* The GROUPED 3x3 convolution of a ResNeXt cast to bfloat16 (csrc/gconv3x3_bf16.hip; reference network/basenetworks.py:71-150 runs it
  * through torch.nn.Conv2d with groups = 32) as an implicit GEMM per 64-channel chunk on the bf16 MFMA, float32 accumulation, ONE
  * rounding at the store.  As many output as input channels; the group width divides 64, so the 64 output channels of a chunk
@@ -640,6 +658,15 @@ int opa_stem7x7_act_bf16(const void* x_dev, int64_t x_batch_stride, int64_t x_ch
 int opa_gemm2_bias_act_bf16(const void* a1_dev, int32_t k1, const void* a2_dev, int32_t k2, int32_t batch, int32_t h_in, int32_t w_in,
                             int32_t stride, const void* a_bias_dev, const void* wcat_dev, const float* bias_dev, void* out_dev,
                             int32_t n, int32_t relu, void* stream);
+
+/* opa_gemm2_bias_act_bf16 for a ResNet cast to FLOAT16, on v_mfma_f32_32x32x16_f16: the same kernel with the element type as its
+ * template parameter -- a1, a2, a_bias, wcat and out float16 where the twin has bf16, bias_dev FLOAT32 as there -- and the same
+ * contract, checks and messages under this name.  With a_bias_dev, f16_rne(max(a1[m, k] + a_bias[k], 0)) in float32 is what is
+ * multiplied (opa_gemm_pro_bias_act_f16's arithmetic).  The store is float16's round to nearest even: beyond 65504 +-inf, NaN stays
+ * NaN, subnormal results kept. */
+int opa_gemm2_bias_act_f16(const void* a1_dev, int32_t k1, const void* a2_dev, int32_t k2, int32_t batch, int32_t h_in, int32_t w_in,
+                           int32_t stride, const void* a_bias_dev, const void* wcat_dev, const float* bias_dev, void* out_dev,
+                           int32_t n, int32_t relu, void* stream);
 
 /* 3x3 convolution, stride 1, padding 1, of an NHWC float32 activation as Winograd F(2x2, 3x3) in ONE kernel (input
  * transform -> sixteen float32 MFMA GEMMs -> output transform; csrc/winograd.hip): the bottleneck convolutions of the

@@ -153,6 +153,8 @@ SYMBOLS = {
     'opa_bias_act': (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     'opa_gemm_bias_act_bf16': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     'opa_gemm_pro_bias_act_bf16': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    'opa_gemm_bias_act_f16': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    'opa_gemm_pro_bias_act_f16': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     'opa_gemm_bias_act_f32': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     'opa_gemm_bias_act_f32x3': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     'opa_gemm_unit_bias_act_f32x3': (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
@@ -161,6 +163,7 @@ SYMBOLS = {
                                                 _vp]),
     'opa_gemm_unit_actp_bf16': (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, ctypes.c_float, _vp]),
     'opa_conv3x3_act_bf16': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp] + [_i32] * 8 + [_vp]),
+    'opa_conv3x3_act_f16': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp] + [_i32] * 8 + [_vp]),
     'opa_gconv3x3_act_bf16': (ctypes.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 8 + [_vp]),
     'opa_stem7x7_act_bf16': (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp] + [_i32] * 6 + [_vp]),
     'opa_conv_rows_f32x3': (ctypes.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 12 + [_vp]),
@@ -171,6 +174,7 @@ SYMBOLS = {
     'opa_fire_expand_f32x3': (ctypes.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 7 + [_vp]),
     'opa_gemm2_bias_act_f32x3': (ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     'opa_gemm2_bias_act_bf16': (ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    'opa_gemm2_bias_act_f16': (ctypes.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     'opa_conv3x3_winograd_f32': (ctypes.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 8 + [_vp]),
     'opa_conv3x3_winograd_f32x3': (ctypes.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 8 + [_vp]),
     'opa_dwconv_bias_act': (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),

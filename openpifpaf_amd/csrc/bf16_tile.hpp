@@ -1,5 +1,9 @@
 // The tile that the kernels on v_mfma_f32_32x32x16_bf16 share (csrc/gemm_epilogue.hip, csrc/gemm_unit_bf16.hip, csrc/conv3x3_bf16.hip):
-//     acc[128, BN] = A[128, K] * W[BN, K]^T        (bf16 operands, float32 accumulation)
+//     acc[128, BN] = A[128, K] * W[BN, K]^T        (16-bit operands, float32 accumulation)
+// The element type is a template parameter, the C ABI's dtype code DT (csrc/vec16.hpp): 2 = bfloat16, the default, which the kernels
+// that exist in bfloat16 alone never name; 1 = float16 on v_mfma_f32_32x32x16_f16, the same fragment order at the same rate.  Only
+// TileElem<DT> depends on it -- the fragment type, the MFMA, the decoding of an element to float32 and the rounding at the store; every
+// operand travels as raw 16-bit words, so shape, LDS pitch, staging map, tile order and the patch epilogue are one for both.
 // 128 x BN (BN = 128 or 64) per 256-thread workgroup, BK = 64; 4 waves as 2 (M) x 2 (N), each wave a 64 x BN/2 sub-tile of 32x32 MFMA
 // blocks.  Both operands are K-major, the fragment order of the instruction (lane l holds 8 consecutive k of row l & 31, k-offset
 // 8 * (l >> 5)); they are staged global -> registers -> LDS (row pitch 72 bf16 = 144 B keeps the ds_read_b128 fragment reads at
@@ -21,6 +25,7 @@
 namespace opa {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 
@@ -32,6 +37,30 @@ __device__ __forceinline__ unsigned bf16_rne(float x) {
     u += 0x7fffu + ((u >> 16) & 1u);
     return u >> 16;
 }
+
+// What the tile's element type decides: the two elements of a 32-bit word as float32 (lo, hi), float32 -> element bits, round to
+// nearest even (rne), the fragment type and the MFMA.
+template <int DT> struct TileElem;
+template <> struct TileElem<2> {   // bf16
+    typedef bf16x8_t frag_t;
+    static __device__ __forceinline__ float lo(unsigned w) { return bf16_lo(w); }
+    static __device__ __forceinline__ float hi(unsigned w) { return bf16_hi(w); }
+    static __device__ __forceinline__ unsigned rne(float x) { return bf16_rne(x); }
+    static __device__ __forceinline__ f32x16_t mfma(frag_t a, frag_t b, f32x16_t c) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+    }
+};
+// f16: the conversions are the language's (v_cvt_f32_f16 / v_cvt_f16_f32, round to nearest even): what rounds beyond 65504 becomes
+// +-inf, NaN stays NaN, a result below 2^-14 keeps its subnormal bits -- tensor.to(torch.float16) bit for bit.
+template <> struct TileElem<1> {
+    typedef f16x8_t frag_t;
+    static __device__ __forceinline__ float lo(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)w); }
+    static __device__ __forceinline__ float hi(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
+    static __device__ __forceinline__ unsigned rne(float x) { return __builtin_bit_cast(unsigned short, (_Float16)x); }
+    static __device__ __forceinline__ f32x16_t mfma(frag_t a, frag_t b, f32x16_t c) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+    }
+};
 
 template <int BN>
 struct Bf16Tile {
@@ -73,10 +102,11 @@ __device__ __forceinline__ Bf16TileOrigin bf16_tile_origin(int N) {
 // acc = A * W^T over K (a multiple of 64) for the tile whose first column is n0; W [N][K].  fetch_a(k0, ra): fill this thread's four
 // staged 16-byte chunks of A for K-step k0 -- chunk column bf16_tile_stage(tid).col of the tile's rows p * 32 + bf16_tile_stage(tid).row.
 // `smem`: Bf16Tile<BN>::LDS_BYTES, 16-byte aligned; free for the epilogue on return.
-template <int BN, typename FetchA>
+template <int BN, int DT = 2, typename FetchA>
 __device__ __forceinline__ void bf16_tile_mainloop(unsigned char* smem, const unsigned short* W, int K, int n0,
                                                    f32x16_t (&acc)[2][Bf16Tile<BN>::NT], FetchA&& fetch_a) {
     constexpr int WN = Bf16Tile<BN>::WN, NT = Bf16Tile<BN>::NT;
+    typedef typename TileElem<DT>::frag_t frag_t;
     unsigned short* sA = reinterpret_cast<unsigned short*>(smem);
     unsigned short* sB = sA + Bf16Tile<BN>::LDS_A;
     const int lane = bf16_tile_wave().lane, wm = bf16_tile_wave().wm, wn = bf16_tile_wave().wn;
@@ -108,19 +138,19 @@ __device__ __forceinline__ void bf16_tile_mainloop(unsigned char* smem, const un
         if (k0 + kBf16BK < K) fetch(k0 + kBf16BK);   // the next K-step's operands travel while this one multiplies
 #pragma unroll
         for (int kk = 0; kk < kBf16BK; kk += 16) {
-            bf16x8_t fa[2], fb[NT];
+            frag_t fa[2], fb[NT];
             const int kof = kk + (lane >> 5) * 8;
 #pragma unroll
             for (int i = 0; i < 2; i++)
-                fa[i] = *reinterpret_cast<const bf16x8_t*>(sA + (wm * 64 + i * 32 + (lane & 31)) * kBf16Pitch + kof);
+                fa[i] = *reinterpret_cast<const frag_t*>(sA + (wm * 64 + i * 32 + (lane & 31)) * kBf16Pitch + kof);
 #pragma unroll
             for (int j = 0; j < NT; j++)
-                fb[j] = *reinterpret_cast<const bf16x8_t*>(sB + (wn * WN + j * 32 + (lane & 31)) * kBf16Pitch + kof);
+                fb[j] = *reinterpret_cast<const frag_t*>(sB + (wn * WN + j * 32 + (lane & 31)) * kBf16Pitch + kof);
 #pragma unroll
             for (int i = 0; i < 2; i++)
 #pragma unroll
                 for (int j = 0; j < NT; j++)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+                    acc[i][j] = TileElem<DT>::mfma(fa[i], fb[j], acc[i][j]);
         }
     }
     __syncthreads();                           // staging LDS is free: reuse it for the epilogue
@@ -163,12 +193,13 @@ __device__ __forceinline__ void bf16_tile_fetch_residual(u32x4_t (&rpre)[Bf16Til
     }
 }
 
-// The patch of the i-th 32-row block (+ the prefetched residual) -> relu -> bf16, round to nearest even -> out [M][N], in 16-byte
-// vectors along the rows.  `relu` is the kernel's own form of max(x, 0); it is applied where RELU.
-template <int BN, bool RES, bool RELU, typename Relu>
+// The patch of the i-th 32-row block (+ the prefetched residual) -> relu -> the element type, round to nearest even -> out [M][N], in
+// 16-byte vectors along the rows.  `relu` is the kernel's own form of max(x, 0); it is applied where RELU.
+template <int BN, bool RES, bool RELU, int DT = 2, typename Relu>
 __device__ __forceinline__ void bf16_tile_store_rows(const float* patch, const u32x4_t (&rpre)[Bf16Tile<BN>::VPL], unsigned short* out,
                                                      int M, int N, int m0, int n0, int i, Relu&& relu) {
     constexpr int WN = Bf16Tile<BN>::WN, VEC_PER_ROW = Bf16Tile<BN>::VEC_PER_ROW;
+    typedef TileElem<DT> E;
     const int lane = bf16_tile_wave().lane, wm = bf16_tile_wave().wm, wn = bf16_tile_wave().wn;
 #pragma unroll
     for (int t = 0; t < Bf16Tile<BN>::VPL; t++) {
@@ -183,7 +214,7 @@ __device__ __forceinline__ void bf16_tile_store_rows(const float* patch, const u
             if (RES) {
                 const u32x4_t rv = rpre[t];
 #pragma unroll
-                for (int q = 0; q < 4; q++) { f[2 * q] += bf16_lo(rv[q]); f[2 * q + 1] += bf16_hi(rv[q]); }
+                for (int q = 0; q < 4; q++) { f[2 * q] += E::lo(rv[q]); f[2 * q + 1] += E::hi(rv[q]); }
             }
             if (RELU) {
 #pragma unroll
@@ -191,7 +222,7 @@ __device__ __forceinline__ void bf16_tile_store_rows(const float* patch, const u
             }
             u32x4_t ov;
 #pragma unroll
-            for (int q = 0; q < 4; q++) ov[q] = bf16_rne(f[2 * q]) | (bf16_rne(f[2 * q + 1]) << 16);
+            for (int q = 0; q < 4; q++) ov[q] = E::rne(f[2 * q]) | (E::rne(f[2 * q + 1]) << 16);
             *reinterpret_cast<u32x4_t*>(out + g) = ov;
         }
     }

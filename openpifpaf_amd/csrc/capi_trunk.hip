@@ -79,8 +79,9 @@ int opa_bias_act(void* x_dev, const void* bias_dev, const void* residual_dev, in
     return E.launched(launch_bias_act(x_dev, bias_dev, residual_dev, rows, channels, dtype, relu, E.st), "bias_act", "bias_act_kernel");
 }
 
-// opa_gemm_bias_act_bf16 and opa_gemm_pro_bias_act_bf16 (`pro`: a_bias_dev is required; without, it is null)
-static int gemm_bf16(const char* fn, bool pro, const void* a_dev, const void* a_bias_dev, const void* w_dev, const void* bias_dev,
+// opa_gemm_bias_act_bf16 and opa_gemm_pro_bias_act_bf16 (`pro`: a_bias_dev is required; without, it is null), and their float16 twins
+// (`dtype` 1: every operand float16, the kernel on the f16 MFMA)
+static int gemm_bf16(const char* fn, int dtype, bool pro, const void* a_dev, const void* a_bias_dev, const void* w_dev, const void* bias_dev,
                      const void* residual_dev, void* out_dev, int64_t m, int32_t n, int32_t k, int32_t relu, void* stream) {
     const Entry E(fn, stream);
     if (!a_dev || (pro && !a_bias_dev) || !w_dev || !bias_dev || !out_dev || m < 0 || n <= 0 || k <= 0 || m > 0x7fffffffll)
@@ -88,19 +89,32 @@ static int gemm_bf16(const char* fn, bool pro, const void* a_dev, const void* a_
     if (k % 64 != 0 || n % 64 != 0) return E.refuse("K and N must be multiples of 64");
     if (misaligned(15, {a_dev, a_bias_dev, w_dev, out_dev, residual_dev})) return E.refuse("pointers must be 16-B aligned");
     if (m == 0) return OPA_OK;
-    return E.launched(launch_gemm_bias_act(a_dev, w_dev, bias_dev, residual_dev, out_dev, (int)m, n, k, relu, E.st, a_bias_dev),
-                      pro ? "gemm_pro_bias_act" : "gemm_bias_act", pro ? "gemm_pro_bias_act_kernel" : "gemm_bias_act_kernel");
+    const hipError_t e = launch_gemm_bias_act(a_dev, w_dev, bias_dev, residual_dev, out_dev, (int)m, n, k, relu, E.st, a_bias_dev, dtype);
+    if (dtype == 1)
+        return E.launched(e, pro ? "gemm_pro_bias_act_f16" : "gemm_bias_act_f16", pro ? "gemm_pro_bias_act_f16_kernel" : "gemm_bias_act_f16_kernel");
+    return E.launched(e, pro ? "gemm_pro_bias_act" : "gemm_bias_act", pro ? "gemm_pro_bias_act_kernel" : "gemm_bias_act_kernel");
 }
 
 int opa_gemm_bias_act_bf16(const void* a_dev, const void* w_dev, const void* bias_dev, const void* residual_dev,
                            void* out_dev, int64_t m, int32_t n, int32_t k, int32_t relu, void* stream) {
-    return gemm_bf16("opa_gemm_bias_act_bf16", false, a_dev, nullptr, w_dev, bias_dev, residual_dev, out_dev, m, n, k, relu, stream);
+    return gemm_bf16("opa_gemm_bias_act_bf16", 2, false, a_dev, nullptr, w_dev, bias_dev, residual_dev, out_dev, m, n, k, relu, stream);
 }
 
 int opa_gemm_pro_bias_act_bf16(const void* a_dev, const void* a_bias_dev, const void* w_dev, const void* bias_dev,
                                const void* residual_dev, void* out_dev, int64_t m, int32_t n, int32_t k,
                                int32_t relu, void* stream) {
-    return gemm_bf16("opa_gemm_pro_bias_act_bf16", true, a_dev, a_bias_dev, w_dev, bias_dev, residual_dev, out_dev, m, n, k, relu, stream);
+    return gemm_bf16("opa_gemm_pro_bias_act_bf16", 2, true, a_dev, a_bias_dev, w_dev, bias_dev, residual_dev, out_dev, m, n, k, relu, stream);
+}
+
+int opa_gemm_bias_act_f16(const void* a_dev, const void* w_dev, const void* bias_dev, const void* residual_dev,
+                          void* out_dev, int64_t m, int32_t n, int32_t k, int32_t relu, void* stream) {
+    return gemm_bf16("opa_gemm_bias_act_f16", 1, false, a_dev, nullptr, w_dev, bias_dev, residual_dev, out_dev, m, n, k, relu, stream);
+}
+
+int opa_gemm_pro_bias_act_f16(const void* a_dev, const void* a_bias_dev, const void* w_dev, const void* bias_dev,
+                              const void* residual_dev, void* out_dev, int64_t m, int32_t n, int32_t k,
+                              int32_t relu, void* stream) {
+    return gemm_bf16("opa_gemm_pro_bias_act_f16", 1, true, a_dev, a_bias_dev, w_dev, bias_dev, residual_dev, out_dev, m, n, k, relu, stream);
 }
 
 int opa_gemm_bias_act_f32(const float* a_dev, const float* a_bias_dev, const float* w_dev, const float* bias_dev,
@@ -314,11 +328,12 @@ int opa_gemm_unit_actp_bf16(const void* a_dev, int64_t a_pitch, const void* w_de
                       "gemm_unit_actp_bf16", "gemm_unit_bf16_kernel");
 }
 
-// the 3x3 convolutions of a bfloat16 ResNet as an implicit GEMM on the bf16 MFMA (csrc/conv3x3_bf16.hip): one message per check
-int opa_conv3x3_act_bf16(const void* x_dev, const void* w_dev, const float* bias_dev, const void* residual_dev, void* out_dev,
-                         int32_t batch, int32_t h_in, int32_t w_in, int32_t c_in, int32_t c_out,
-                         int32_t stride, int32_t dilation, int32_t relu, void* stream) {
-    const Entry E("opa_conv3x3_act_bf16", stream);
+// the 3x3 convolutions of a bfloat16 ResNet as an implicit GEMM on the bf16 MFMA (csrc/conv3x3_bf16.hip): one message per check.
+// opa_conv3x3_act_bf16 and its float16 twin (`dtype` 1: x, w, residual and out float16, the kernel on the f16 MFMA)
+static int conv3x3_16(const char* fn, int dtype, const void* x_dev, const void* w_dev, const float* bias_dev, const void* residual_dev,
+                      void* out_dev, int32_t batch, int32_t h_in, int32_t w_in, int32_t c_in, int32_t c_out,
+                      int32_t stride, int32_t dilation, int32_t relu, void* stream) {
+    const Entry E(fn, stream);
     if (!x_dev || !w_dev || !out_dev) return E.refuse("x_dev, w_dev and out_dev must not be NULL");
     if (misaligned(15, {x_dev, w_dev, bias_dev, residual_dev, out_dev})) return E.refuse("pointers must be 16-B aligned");
     if (batch < 0 || h_in < 0 || w_in < 0) return E.refuse("negative batch, h_in or w_in");
@@ -334,7 +349,22 @@ int opa_conv3x3_act_bf16(const void* x_dev, const void* w_dev, const float* bias
     // (grid.x; with out below 2^31 elements of at least 64 channels it holds today: it guards the launch should a limit above move)
     if (conv3x3_bf16_workgroups(batch, h_in, w_in, c_out, stride) > 0x7fffffffll) return E.refuse("too many tiles for grid.x");
     return E.launched(launch_conv3x3_bf16(x_dev, w_dev, bias_dev, residual_dev, out_dev, batch, h_in, w_in, c_in, c_out, stride, dilation,
-                                          relu, E.st), "conv3x3_act_bf16", "conv3x3_bf16_kernel");
+                                          relu, E.st, dtype), dtype == 1 ? "conv3x3_act_f16" : "conv3x3_act_bf16",
+                      dtype == 1 ? "conv3x3_f16_kernel" : "conv3x3_bf16_kernel");
+}
+
+int opa_conv3x3_act_bf16(const void* x_dev, const void* w_dev, const float* bias_dev, const void* residual_dev, void* out_dev,
+                         int32_t batch, int32_t h_in, int32_t w_in, int32_t c_in, int32_t c_out,
+                         int32_t stride, int32_t dilation, int32_t relu, void* stream) {
+    return conv3x3_16("opa_conv3x3_act_bf16", 2, x_dev, w_dev, bias_dev, residual_dev, out_dev, batch, h_in, w_in, c_in, c_out, stride,
+                      dilation, relu, stream);
+}
+
+int opa_conv3x3_act_f16(const void* x_dev, const void* w_dev, const float* bias_dev, const void* residual_dev, void* out_dev,
+                        int32_t batch, int32_t h_in, int32_t w_in, int32_t c_in, int32_t c_out,
+                        int32_t stride, int32_t dilation, int32_t relu, void* stream) {
+    return conv3x3_16("opa_conv3x3_act_f16", 1, x_dev, w_dev, bias_dev, residual_dev, out_dev, batch, h_in, w_in, c_in, c_out, stride,
+                      dilation, relu, stream);
 }
 
 // the grouped 3x3 convolution of a bfloat16 ResNeXt as an implicit GEMM per 64-channel chunk on the bf16 MFMA (csrc/gconv3x3_bf16.hip):
@@ -395,11 +425,11 @@ int opa_stem7x7_act_bf16(const void* x_dev, int64_t x_batch_stride, int64_t x_ch
 
 // a bfloat16 block's last 1x1 convolution and its downsampling 1x1 convolution as one product on the bf16 MFMA (csrc/gemm2_bf16.hip):
 // one message per check, in this order: null pointers, alignment, negative sizes, k1, k2, n, the stride, the sizes; then the empty call;
-// then the grid
-int opa_gemm2_bias_act_bf16(const void* a1_dev, int32_t k1, const void* a2_dev, int32_t k2, int32_t batch, int32_t h_in, int32_t w_in,
-                            int32_t stride, const void* a_bias_dev, const void* wcat_dev, const float* bias_dev, void* out_dev,
-                            int32_t n, int32_t relu, void* stream) {
-    const Entry E("opa_gemm2_bias_act_bf16", stream);
+// then the grid.  opa_gemm2_bias_act_bf16 and its float16 twin (`dtype` 1: a1, a2, a_bias, wcat and out float16, the kernel on the f16 MFMA)
+static int gemm2_16(const char* fn, int dtype, const void* a1_dev, int32_t k1, const void* a2_dev, int32_t k2, int32_t batch, int32_t h_in,
+                    int32_t w_in, int32_t stride, const void* a_bias_dev, const void* wcat_dev, const float* bias_dev, void* out_dev,
+                    int32_t n, int32_t relu, void* stream) {
+    const Entry E(fn, stream);
     if (!a2_dev || !wcat_dev || !out_dev) return E.refuse("a2_dev, wcat_dev and out_dev must not be NULL");
     if ((a1_dev == nullptr) != (k1 == 0)) return E.refuse("a1_dev must be NULL with k1 == 0 and with no other k1");
     if (a_bias_dev && k1 <= 0) return E.refuse("a_bias_dev needs k1 > 0");
@@ -417,8 +447,24 @@ int opa_gemm2_bias_act_bf16(const void* a1_dev, int32_t k1, const void* a2_dev, 
     if (batch == 0 || h_in == 0 || w_in == 0) return OPA_OK;
     // (grid.x; with out below 2^31 elements of at least 64 channels it holds today: it guards the launch should a limit above move)
     if (gemm2_bf16_workgroups(batch, h_in, w_in, n, stride) > 0x7fffffffll) return E.refuse("too many tiles for grid.x");
-    return E.launched(launch_gemm2_bf16(a1_dev, k1, a2_dev, k2, batch, h_in, w_in, stride, a_bias_dev, wcat_dev, bias_dev, out_dev, n, relu,
-                                        E.st), "gemm2_bias_act_bf16", a_bias_dev ? "gemm2_pro_bf16_kernel" : "gemm2_bf16_kernel");
+    const hipError_t e = launch_gemm2_bf16(a1_dev, k1, a2_dev, k2, batch, h_in, w_in, stride, a_bias_dev, wcat_dev, bias_dev, out_dev, n, relu,
+                                           E.st, dtype);
+    if (dtype == 1) return E.launched(e, "gemm2_bias_act_f16", a_bias_dev ? "gemm2_pro_f16_kernel" : "gemm2_f16_kernel");
+    return E.launched(e, "gemm2_bias_act_bf16", a_bias_dev ? "gemm2_pro_bf16_kernel" : "gemm2_bf16_kernel");
+}
+
+int opa_gemm2_bias_act_bf16(const void* a1_dev, int32_t k1, const void* a2_dev, int32_t k2, int32_t batch, int32_t h_in, int32_t w_in,
+                            int32_t stride, const void* a_bias_dev, const void* wcat_dev, const float* bias_dev, void* out_dev,
+                            int32_t n, int32_t relu, void* stream) {
+    return gemm2_16("opa_gemm2_bias_act_bf16", 2, a1_dev, k1, a2_dev, k2, batch, h_in, w_in, stride, a_bias_dev, wcat_dev, bias_dev, out_dev,
+                    n, relu, stream);
+}
+
+int opa_gemm2_bias_act_f16(const void* a1_dev, int32_t k1, const void* a2_dev, int32_t k2, int32_t batch, int32_t h_in, int32_t w_in,
+                           int32_t stride, const void* a_bias_dev, const void* wcat_dev, const float* bias_dev, void* out_dev,
+                           int32_t n, int32_t relu, void* stream) {
+    return gemm2_16("opa_gemm2_bias_act_f16", 1, a1_dev, k1, a2_dev, k2, batch, h_in, w_in, stride, a_bias_dev, wcat_dev, bias_dev, out_dev,
+                    n, relu, stream);
 }
 
 // opa_conv3x3_winograd_f32 and opa_conv3x3_winograd_f32x3 (`x3`: u_dev holds the three bf16 planes of the filter)

@@ -270,8 +270,9 @@ hipError_t with_value(T v, F&& f) {
 template <typename F>
 hipError_t with_flag(bool v, F&& f) { return with_value<false, true>(v, f); }
 
+// csrc/gemm_epilogue.hip; dtype: the element type of every operand, 2 bfloat16 or 1 float16 (anything else: hipErrorInvalidValue)
 hipError_t launch_gemm_bias_act(const void* A, const void* W, const void* bias, const void* res, void* out,
-                                int M, int N, int K, int relu, hipStream_t st, const void* a_bias = nullptr);
+                                int M, int N, int K, int relu, hipStream_t st, const void* a_bias, int dtype);
 
 hipError_t launch_gemm_f32x3_bias_act(const float* A, const unsigned short* W3, const float* bias, const float* res, float* out,
                                       int M, int N, int K, int relu, int terms, hipStream_t st, const float* a_bias);
@@ -317,11 +318,11 @@ hipError_t launch_gemm_unit_act_bf16(const void* A, long long lda, const void* W
                                      hipStream_t st);
 // csrc/conv3x3_bf16.hip: the 3x3 convolution of a dense channels-last bf16 tensor as an implicit GEMM on the bf16 MFMA: x [B, H, W, c_in],
 // w [c_out][9][c_in], bias float32 [c_out] or null, residual / out dense bf16 [B, Ho, Wo, c_out]; c_in % 64 == 0, c_out % 64 == 0, S 1 or
-// 2, D = padding 1, or 2 or 4 with S = 1; x and out below 2^31 elements (anything else: hipErrorInvalidValue).
-// conv3x3_bf16_workgroups = grid.x of the launch.
+// 2, D = padding 1, or 2 or 4 with S = 1; x and out below 2^31 elements (anything else: hipErrorInvalidValue).  dtype 2; with dtype 1
+// the same for float16 tensors on the f16 MFMA.  conv3x3_bf16_workgroups = grid.x of the launch.
 long long conv3x3_bf16_workgroups(int B, int H, int W, int c_out, int S);
 hipError_t launch_conv3x3_bf16(const void* x, const void* w, const float* bias, const void* residual, void* out, int B, int H, int W,
-                               int c_in, int c_out, int S, int D, int relu, hipStream_t st);
+                               int c_in, int c_out, int S, int D, int relu, hipStream_t st, int dtype);
 // csrc/gconv3x3_bf16.hip: the GROUPED 3x3 convolution (as many output as input channels C, group width CG) of a dense channels-last bf16
 // tensor as an implicit GEMM per 64-channel chunk on the bf16 MFMA: x [B, H, W, C], w [C][9][64] block diagonal (column j of row co:
 // input channel 64 * (co / 64) + j; zero outside co's group), bias float32 [C] or null, out dense bf16 [B, Ho, Wo, C]; C % 64 == 0, CG
@@ -342,10 +343,11 @@ hipError_t launch_stem7x7_bf16(const void* x, long long xb, long long xc, long l
 // dense bf16 (null with k1 == 0: the strided 1x1 convolution alone), x [B, H, W, k2] dense channels-last bf16 read at stride S, a_bias
 // bf16 [k1] or null (a1's owed bias + ReLU, applied while it is staged; not with k1 == 0), wcat [n][k1 + k2], bias float32 [n] or null,
 // out dense bf16 [B, Ho, Wo, n]; k1 % 64 == 0, k2 % 64 == 0, n % 64 == 0, S 1 or 2; x, M * k1 and M * n below 2^31 elements (anything
-// else: hipErrorInvalidValue).  gemm2_bf16_workgroups = grid.x of the launch.
+// else: hipErrorInvalidValue).  dtype 2; with dtype 1 the same for float16 tensors on the f16 MFMA.  gemm2_bf16_workgroups = grid.x of
+// the launch.
 long long gemm2_bf16_workgroups(int B, int H, int W, int n, int S);
 hipError_t launch_gemm2_bf16(const void* a1, int k1, const void* x, int k2, int B, int H, int W, int S, const void* a_bias,
-                             const void* wcat, const float* bias, void* out, int n, int relu, hipStream_t st);
+                             const void* wcat, const float* bias, void* out, int n, int relu, hipStream_t st, int dtype);
 hipError_t launch_gemm_f32_bias_act(const float* A, const float* W, const float* bias, const float* res, float* out,
                                     int M, int N, int K, int relu, hipStream_t st, const float* a_bias = nullptr);
 hipError_t launch_winograd_f23(const float* x, const float* U, float* y, const float* bias, int N, int H, int W, int Cin,

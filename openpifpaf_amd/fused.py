@@ -142,6 +142,26 @@ PAIR_BF16 = _switch('OPA_PAIR_BF16', '0')
 # kernel runs.  It ships OFF; the one timing is tools/gpu/gconv_bf16_times.py, profiles/gconv_bf16/times.log, and switching the default
 # is a change of its own that rests on it.
 GCONV_BF16 = _switch('OPA_GCONV_BF16', '0')
+# A ResNet cast to FLOAT16 (``model.half()``) on the same kernels, instantiated for the other 16-bit type on v_mfma_f32_32x32x16_f16
+# (csrc/bf16_tile.hpp's ``TileElem<1>``): the 1x1 GEMM with the fused epilogue (``conv1x1_bias_act``, choices 'gemm' / 'pass+gemm' /
+# 'conv' as for bfloat16), the 3x3 implicit GEMM (``conv3x3_bias_act_bf16``), the block tail + downsampling product and the strided
+# 1x1 alone (``conv1x1_pair_bias_act_bf16`` / ``conv1x1_strided_bf16``) -- the ``opa_*_f16`` entry points: OPA_F16=1 (or
+# fused.F16 = True).  ONE switch for the three routes, independent of the bfloat16 switches, which a float16 operand never asks
+# (``_route16``); with it off every predicate declines a float16 operand and the network runs MIOpen's convolutions + ``bias_act_``.
+# Never timed by ``pick``.  The 7x7 stem, the grouped 3x3, the unit mode, the max-pool and the heads' convolution have no float16
+# form.  It ships OFF; the one timing is tools/gpu/f16_times.py, profiles/f16/times.log, and switching the default is a change of its
+# own that rests on it.
+F16 = _switch('OPA_F16', '0')
+# element type -> (is the route on, given the route's own bfloat16 switch?; the suffix of its entry points) for the routes on the
+# shared 16-bit MFMA tile
+_ROUTES16 = {torch.bfloat16: (lambda own: own, '_bf16'), torch.float16: (lambda own: F16, '_f16')}
+
+
+def _route16(dtype, own=True):
+    """The symbol suffix of the 16-bit MFMA routes for operands of ``dtype`` -- ``'_bf16'`` where ``own``, the route's own bfloat16
+    switch, is on; ``'_f16'`` where ``F16`` is -- or None: another dtype, or the switch off."""
+    on, suffix = _ROUTES16.get(dtype, (lambda own: False, None))
+    return suffix if on(own) else None
 
 
 # ---- the choice table and the decision ---------------------------------------------------------------------------------------------
@@ -462,15 +482,20 @@ def head_epilogue(x, meta):
 
 def conv1x1_supported(x, weight, bias=None, residual=None, a_bias=None):
     """True if ``conv1x1_bias_act`` can run the HIP GEMM for these operands.  The kernels read raw buffers:
-    EVERY operand must have the activation's dtype, bfloat16 or float32 (autocast keeps parameters in float32
-    next to bfloat16 activations -- those take the PyTorch path), the activation channels_last, the residual
-    channels_last of the output's shape."""
+    EVERY operand must have the activation's dtype, bfloat16, float32 or -- with ``F16`` -- float16 (autocast keeps
+    parameters in float32 next to 16-bit activations -- those take the PyTorch path), the activation channels_last,
+    the residual channels_last of the output's shape."""
     dt = x.dtype
-    if not (x.is_cuda and dt in (torch.bfloat16, torch.float32) and x.dim() == 4
+    if not (x.is_cuda and (dt == torch.float32 or _route16(dt)) and x.dim() == 4
             and x.is_contiguous(memory_format=torch.channels_last)
             and weight.dtype == dt and weight.is_cuda
-            and weight.shape[1] % (64 if dt == torch.bfloat16 else 32) == 0 and weight.shape[0] % 64 == 0
+            and weight.shape[1] % (32 if dt == torch.float32 else 64) == 0 and weight.shape[0] % 64 == 0
             and weight.shape[1] == x.shape[1]):
+        return False
+    # (float16 asks what the other routes of its switch ask: outside autocast, nothing that autograd follows; the bfloat16 and the
+    # float32 GEMM keep their contract as it was)
+    if dt == torch.float16 and (torch.is_autocast_enabled() or (torch.is_grad_enabled() and any(
+            t is not None and t.requires_grad for t in (x, weight, bias, residual, a_bias)))):
         return False
     for vec, n in ((bias, weight.shape[0]), (a_bias, weight.shape[1])):
         if vec is not None and not (vec.dtype == dt and vec.is_cuda and vec.is_contiguous()
@@ -487,7 +512,7 @@ def conv1x1_supported(x, weight, bias=None, residual=None, a_bias=None):
 def conv1x1_bias_act(x, weight2d, bias, residual=None, relu=True, a_bias=None):
     """``act(conv1x1(x, weight) + bias (+ residual))`` as ONE MFMA GEMM kernel with fused epilogue.
 
-    :param x: ``[B, C_in, H, W]`` bfloat16 or float32, channels_last
+    :param x: ``[B, C_in, H, W]`` bfloat16, float16 or float32, channels_last
     :param weight2d: ``[C_out, C_in]`` of the same dtype, contiguous
     :param a_bias: ``[C_in]``: ``x`` is the RAW output of the preceding convolution and
         ``relu(x + a_bias)`` -- that convolution's epilogue -- is applied while the operand is staged
@@ -499,9 +524,9 @@ def conv1x1_bias_act(x, weight2d, bias, residual=None, relu=True, a_bias=None):
     if x.dtype == torch.float32:
         _launch('opa_gemm_bias_act_f32', _ptr(x), _ptr(a_bias), *rest)
     elif a_bias is not None:
-        _launch('opa_gemm_pro_bias_act_bf16', _ptr(x), _ptr(a_bias), *rest)
+        _launch('opa_gemm_pro_bias_act' + _ROUTES16[x.dtype][1], _ptr(x), _ptr(a_bias), *rest)
     else:
-        _launch('opa_gemm_bias_act_bf16', _ptr(x), *rest)
+        _launch('opa_gemm_bias_act' + _ROUTES16[x.dtype][1], _ptr(x), *rest)
     return out
 
 
@@ -609,7 +634,7 @@ PAIR_BF16_DECLINED = frozenset()
 
 def pair_bf16_weight_of(conv, dconv, bias):
     """The operands of ``conv1x1_pair_bias_act_bf16`` derived from the CURRENT weights (``conv``: ``[N, k1, 1, 1]``, ``dconv``:
-    ``[N, k2, 1, 1]``, bfloat16) and the folded ``bias`` the block keeps (``[N]`` bfloat16 or float32, or None): ``Wcat`` =
+    ``[N, k2, 1, 1]``, 16-bit) and the folded ``bias`` the block keeps (``[N]`` of that dtype or float32, or None): ``Wcat`` =
     ``[W | Wd]`` as ``[N][k1 + k2]``, K-major, and the bias as FLOAT32 (upcast exactly; None stays None).  ``conv`` None: ``dconv``'s
     weight alone, ``[N][k2]`` (``conv1x1_strided_bf16``).  Derived and cached on ``dconv`` (``derived``, keyed on the three tensors'
     storage and version): no buffer, no part of a state dict, computed again whenever a weight or the bias was replaced, moved,
@@ -623,41 +648,43 @@ def pair_bf16_weight_of(conv, dconv, bias):
     return derived(dconv, '_opa_w_pair_bf16', (None if conv is None else conv.weight, dconv.weight, bias), make)
 
 
-def _dense_bf16(t, channels):
-    """``t``: a dense channels-last bfloat16 ``[B, channels, H, W]`` on the GPU, 16-byte aligned, nothing that autograd follows?"""
-    return (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 4 and t.shape[1] == channels
+def _dense_bf16(t, channels, dtype=torch.bfloat16):
+    """``t``: a dense channels-last 16-bit ``[B, channels, H, W]`` of ``dtype`` on the GPU, 16-byte aligned, nothing that autograd follows?"""
+    return (t.is_cuda and t.dtype == dtype and t.dim() == 4 and t.shape[1] == channels
             and t.is_contiguous(memory_format=torch.channels_last) and t.data_ptr() % 16 == 0
             and not (torch.is_grad_enabled() and t.requires_grad))
 
 
 def _plain_1x1_bf16(conv, like):
-    """``conv``: a 1x1 ``Conv2d`` without groups, padding, dilation or a bias of its own, bfloat16 weights on ``like``'s device that
-    autograd does not follow?  (The stride is the caller's to test.)"""
+    """``conv``: a 1x1 ``Conv2d`` without groups, padding, dilation or a bias of its own, 16-bit weights of ``like``'s dtype on its
+    device that autograd does not follow?  (The stride is the caller's to test, the dtype's route ``_route16``'s.)"""
     return (isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (1, 1) and conv.groups == 1 and conv.padding == (0, 0)
-            and conv.dilation == (1, 1) and conv.bias is None and conv.weight.dtype == torch.bfloat16
+            and conv.dilation == (1, 1) and conv.bias is None and conv.weight.dtype == like.dtype
             and conv.weight.device == like.device and not (torch.is_grad_enabled() and conv.weight.requires_grad))
 
 
 def pair_bf16_supported(conv, dconv, h, x, bias, a_bias=None):
-    """Can ``conv1x1_pair_bias_act_bf16(conv, dconv, h, x, bias, ..., a_bias)`` run?  The switch on; ``h`` and ``x`` dense channels-last
-    bfloat16 tensors on the GPU of one batch, outside autocast (whose parameters stay float32), nothing that autograd follows; both
+    """Can ``conv1x1_pair_bias_act_bf16(conv, dconv, h, x, bias, ..., a_bias)`` run?  The switch on (bfloat16: ``PAIR_BF16``, float16:
+    ``F16``); ``h`` and ``x`` dense channels-last 16-bit tensors of one dtype on the GPU of one batch, the weights of that dtype, outside
+    autocast (whose parameters stay float32), nothing that autograd follows; both
     convolutions 1x1 without groups, padding or a bias of their own, ``conv`` of stride 1, ``dconv`` of square stride 1 or 2, equal
     output channels; ``conv``'s input channels, ``dconv``'s and the output channels multiples of 64; ``h``'s pixels those of ``x`` at
-    ``dconv``'s stride; ``x``, ``h`` and the output fewer than 2^31 elements each; 16-byte boundaries; the folded ``bias`` bfloat16
-    or float32, one element per output channel, or None; ``a_bias`` (``h``'s owed bias, a ReLU behind it) bfloat16 ``[k1]``,
+    ``dconv``'s stride; ``x``, ``h`` and the output fewer than 2^31 elements each; 16-byte boundaries; the folded ``bias`` of that dtype
+    or float32, one element per output channel, or None; ``a_bias`` (``h``'s owed bias, a ReLU behind it) of that dtype, ``[k1]``,
     contiguous, 16-byte aligned, or None; the library built; ``(k1, k2, n, stride)`` not in ``PAIR_BF16_DECLINED``."""
-    if not (PAIR_BF16 and not torch.is_autocast_enabled() and _plain_1x1_bf16(dconv, x) and _plain_1x1_bf16(conv, x)):
+    dt = x.dtype
+    if not (_route16(dt, PAIR_BF16) and not torch.is_autocast_enabled() and _plain_1x1_bf16(dconv, x) and _plain_1x1_bf16(conv, x)):
         return False
     k1, k2, n, s = conv.in_channels, dconv.in_channels, conv.out_channels, dconv.stride[0]
     if not (conv.stride == (1, 1) and dconv.stride == (s, s) and s in (1, 2) and dconv.out_channels == n
-            and k1 % 64 == 0 and k2 % 64 == 0 and n % 64 == 0 and _dense_bf16(h, k1) and _dense_bf16(x, k2)
+            and k1 % 64 == 0 and k2 % 64 == 0 and n % 64 == 0 and _dense_bf16(h, k1, dt) and _dense_bf16(x, k2, dt)
             and h.shape[0] == x.shape[0] and h.device == x.device and tuple(h.shape[2:]) == _out_hw(x, s)
             and 0 < x.numel() < 2 ** 31 and h.numel() < 2 ** 31 and out_pixels(x, s) * n < 2 ** 31):
         return False
-    if bias is not None and not (bias.dtype in (torch.bfloat16, torch.float32) and bias.device == x.device and bias.dim() == 1
+    if bias is not None and not (bias.dtype in (dt, torch.float32) and bias.device == x.device and bias.dim() == 1
                                  and bias.numel() == n and not (torch.is_grad_enabled() and bias.requires_grad)):
         return False
-    if a_bias is not None and not (a_bias.dtype == torch.bfloat16 and a_bias.device == x.device and a_bias.dim() == 1
+    if a_bias is not None and not (a_bias.dtype == dt and a_bias.device == x.device and a_bias.dim() == 1
                                    and a_bias.numel() == k1 and a_bias.is_contiguous() and a_bias.data_ptr() % 16 == 0
                                    and not (torch.is_grad_enabled() and a_bias.requires_grad)):
         return False
@@ -665,16 +692,16 @@ def pair_bf16_supported(conv, dconv, h, x, bias, a_bias=None):
 
 
 def conv1x1_pair_bias_act_bf16(conv, dconv, h, x, bias, relu=True, a_bias=None):
-    """``act(conv(h) + dconv(x) + bias)`` -- the last 1x1 convolution of a bfloat16 ResNet block and the block's downsampling
+    """``act(conv(h) + dconv(x) + bias)`` -- the last 1x1 convolution of a 16-bit ResNet block and the block's downsampling
     convolution (reference ``network/basenetworks.py:71-150``: torchvision's Bottleneck) -- as ONE product ``[h | x at stride] *
-    [W | Wd]^T`` on the bf16 MFMA (``opa_gemm2_bias_act_bf16``, csrc/gemm2_bf16.hip): float32 accumulation, one rounding; the identity
+    [W | Wd]^T`` on the 16-bit MFMA (``opa_gemm2_bias_act_bf16`` / ``..._f16``, csrc/gemm2_bf16.hip): float32 accumulation, one rounding; the identity
     tensor is neither written nor read back.  With ``a_bias``, ``h`` is the raw output of the preceding convolution and
     ``relu(h + a_bias)`` is applied while it is staged (``x`` is taken as it is).  ``pair_bf16_supported`` says whether this can run."""
     k1, k2, n = conv.in_channels, dconv.in_channels, conv.out_channels
     wcat, b32 = pair_bf16_weight_of(conv, dconv, bias)
     B, _, H, W = x.shape
     out = _empty_nhwc(h, n)
-    _launch('opa_gemm2_bias_act_bf16', _ptr(h), k1, _ptr(x), k2, B, H, W, dconv.stride[0], _ptr(a_bias), _ptr(wcat), _ptr(b32),
+    _launch('opa_gemm2_bias_act' + _ROUTES16[x.dtype][1], _ptr(h), k1, _ptr(x), k2, B, H, W, dconv.stride[0], _ptr(a_bias), _ptr(wcat), _ptr(b32),
             _ptr(out), n, int(bool(relu)))
     return out
 
@@ -682,23 +709,23 @@ def conv1x1_pair_bias_act_bf16(conv, dconv, h, x, bias, relu=True, a_bias=None):
 def conv1x1_strided_bf16_supported(dconv, x):
     """Can ``conv1x1_strided_bf16(dconv, x)`` run?  ``pair_bf16_supported``'s conditions on ``dconv`` and ``x`` alone: the product
     without a first source (k1 = 0)."""
-    if not (PAIR_BF16 and not torch.is_autocast_enabled() and _plain_1x1_bf16(dconv, x)):
+    if not (_route16(x.dtype, PAIR_BF16) and not torch.is_autocast_enabled() and _plain_1x1_bf16(dconv, x)):
         return False
     k2, n, s = dconv.in_channels, dconv.out_channels, dconv.stride[0]
-    return (dconv.stride == (s, s) and s in (1, 2) and k2 % 64 == 0 and n % 64 == 0 and _dense_bf16(x, k2)
+    return (dconv.stride == (s, s) and s in (1, 2) and k2 % 64 == 0 and n % 64 == 0 and _dense_bf16(x, k2, x.dtype)
             and 0 < x.numel() < 2 ** 31 and out_pixels(x, s) * n < 2 ** 31 and _lib.available()
             and (0, k2, n, s) not in PAIR_BF16_DECLINED)
 
 
 def conv1x1_strided_bf16(dconv, x):
-    """``dconv(x)`` for the downsampling 1x1 convolution, stride 1 or 2, of a bfloat16 BasicBlock (reference
-    ``network/basenetworks.py:71-150``) on the bf16 MFMA: ``opa_gemm2_bias_act_bf16`` without a first source, a bias or a ReLU.
+    """``dconv(x)`` for the downsampling 1x1 convolution, stride 1 or 2, of a 16-bit BasicBlock (reference
+    ``network/basenetworks.py:71-150``) on the 16-bit MFMA: ``opa_gemm2_bias_act_bf16`` / ``..._f16`` without a first source, a bias or a ReLU.
     ``conv1x1_strided_bf16_supported`` says whether this can run."""
     wd, _ = pair_bf16_weight_of(None, dconv, None)
     B, k2, H, W = x.shape
     s = dconv.stride[0]
     out = _empty_nhwc(x, dconv.out_channels, _out_hw(x, s))
-    _launch('opa_gemm2_bias_act_bf16', _ptr(None), 0, _ptr(x), k2, B, H, W, s, _ptr(None), _ptr(wd), _ptr(None), _ptr(out),
+    _launch('opa_gemm2_bias_act' + _ROUTES16[x.dtype][1], _ptr(None), 0, _ptr(x), k2, B, H, W, s, _ptr(None), _ptr(wd), _ptr(None), _ptr(out),
             dconv.out_channels, 0)
     return out
 
@@ -747,8 +774,8 @@ def conv3x3_dilated_bias_act_x3(conv, x, bias, relu=True):
 
 
 def conv3x3_bf16_weight_of(conv, bias=None):
-    """The operands of ``conv3x3_bias_act_bf16`` derived from the CURRENT ``conv.weight`` (``[N, C, 3, 3]`` bfloat16) and the folded
-    ``bias`` the block keeps (``[N]`` bfloat16, or None): the weight as ``[N][9][C]`` -- ``weight.permute(0, 2, 3, 1)``, K-major with
+    """The operands of ``conv3x3_bias_act_bf16`` derived from the CURRENT ``conv.weight`` (``[N, C, 3, 3]`` 16-bit) and the folded
+    ``bias`` the block keeps (``[N]`` of that dtype or float32, or None): the weight as ``[N][9][C]`` -- ``weight.permute(0, 2, 3, 1)``, K-major with
     K = 9 C, ``split_weight_3x3``'s layout without the split -- and the bias as FLOAT32 (upcast exactly; None stays None).  Derived and
     cached (``derived``, keyed on both tensors' storage and version): no buffer, no part of a state dict, computed again whenever the
     weight or the bias was replaced, moved, converted or changed in place (``load_state_dict`` into an optimized model)."""
@@ -760,13 +787,15 @@ def conv3x3_bf16_weight_of(conv, bias=None):
 
 
 def conv3x3_bf16_supported(conv, x, bias, residual=None):
-    """Can ``conv3x3_bias_act_bf16(conv, x, bias, residual)`` run?  The switch on; a dense channels-last bfloat16 tensor on the GPU,
-    outside autocast (whose parameters stay float32), nothing that autograd follows; a 3x3 convolution without groups or a bias of
-    its own (the folded one arrives separately: bfloat16 or float32, one element per output channel, or None), square stride 1 or 2,
+    """Can ``conv3x3_bias_act_bf16(conv, x, bias, residual)`` run?  The switch on (bfloat16: ``CONV3_BF16``, float16: ``F16``); a dense
+    channels-last 16-bit tensor on the GPU, the weight of its dtype, outside autocast (whose parameters stay float32), nothing that
+    autograd follows; a 3x3 convolution without groups or a bias of its own (the folded one arrives separately: of ``x``'s dtype or
+    float32, one element per output channel, or None), square stride 1 or 2,
     square dilation 1, 2 or 4 -- above 1 with stride 1 only -- and padding equal to the dilation; input and output channels
-    multiples of 64; ``residual`` a dense channels-last bfloat16 tensor of the output's shape; 16-byte boundaries; ``x`` and the
+    multiples of 64; ``residual`` a dense channels-last tensor of ``x``'s dtype and the output's shape; 16-byte boundaries; ``x`` and the
     output fewer than 2^31 elements each."""
-    if not (CONV3_BF16 and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and not torch.is_autocast_enabled()):
+    dt = x.dtype
+    if not (_route16(dt, CONV3_BF16) and x.is_cuda and x.dim() == 4 and not torch.is_autocast_enabled()):
         return False
     if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad or (bias is not None and bias.requires_grad)
                                     or (residual is not None and residual.requires_grad)):
@@ -775,14 +804,14 @@ def conv3x3_bf16_supported(conv, x, bias, residual=None):
     if not (conv.kernel_size == (3, 3) and conv.groups == 1 and conv.bias is None and conv.stride == (s, s) and s in (1, 2)
             and conv.dilation == (d, d) and d in (1, 2, 4) and (d == 1 or s == 1) and conv.padding == (d, d)
             and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0 and x.shape[1] == conv.in_channels
-            and conv.weight.dtype == torch.bfloat16 and conv.weight.device == x.device
+            and conv.weight.dtype == dt and conv.weight.device == x.device
             and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0 and 0 < x.numel() < 2 ** 31
             and out_pixels(x, s) * conv.out_channels < 2 ** 31):
         return False
-    if bias is not None and not (bias.dtype in (torch.bfloat16, torch.float32) and bias.device == x.device and bias.dim() == 1
+    if bias is not None and not (bias.dtype in (dt, torch.float32) and bias.device == x.device and bias.dim() == 1
                                  and bias.numel() == conv.out_channels):
         return False
-    if residual is not None and not (residual.dtype == torch.bfloat16 and residual.device == x.device and residual.is_cuda
+    if residual is not None and not (residual.dtype == dt and residual.device == x.device and residual.is_cuda
                                      and tuple(residual.shape) == (x.shape[0], conv.out_channels) + _out_hw(x, s)
                                      and residual.is_contiguous(memory_format=torch.channels_last) and residual.data_ptr() % 16 == 0):
         return False
@@ -790,15 +819,15 @@ def conv3x3_bf16_supported(conv, x, bias, residual=None):
 
 
 def conv3x3_bias_act_bf16(conv, x, bias, residual=None, relu=True):
-    """``act(conv(x) + bias (+ residual))`` for a 3x3 convolution of a bfloat16 ResNet (reference ``network/basenetworks.py:71-150``:
-    torchvision's BasicBlock and Bottleneck; ``:121-135``: block 5 dilated) as ONE implicit GEMM on the bf16 MFMA
-    (``opa_conv3x3_act_bf16``, csrc/conv3x3_bf16.hip): float32 accumulation, one rounding -- bfloat16 in and out.
+    """``act(conv(x) + bias (+ residual))`` for a 3x3 convolution of a 16-bit ResNet (reference ``network/basenetworks.py:71-150``:
+    torchvision's BasicBlock and Bottleneck; ``:121-135``: block 5 dilated) as ONE implicit GEMM on the 16-bit MFMA
+    (``opa_conv3x3_act_bf16`` / ``..._f16``, csrc/conv3x3_bf16.hip): float32 accumulation, one rounding -- ``x``'s dtype in and out.
     ``conv3x3_bf16_supported`` says whether this can run."""
     w9, b32 = conv3x3_bf16_weight_of(conv, bias)
     B, C, H, W = x.shape
     s = conv.stride[0]
     out = _empty_nhwc(x, conv.out_channels, _out_hw(x, s))
-    _launch('opa_conv3x3_act_bf16', _ptr(x), _ptr(w9), _ptr(b32), _ptr(residual), _ptr(out), B, H, W, C, conv.out_channels, s,
+    _launch('opa_conv3x3_act' + _ROUTES16[x.dtype][1], _ptr(x), _ptr(w9), _ptr(b32), _ptr(residual), _ptr(out), B, H, W, C, conv.out_channels, s,
             conv.dilation[0], int(bool(relu)))
     return out
 

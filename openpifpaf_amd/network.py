@@ -65,6 +65,7 @@ _CONV3_ROUTES = (
      lambda c, r: ('conv3d%d' % c.dilation[0], r is not None)),
     ('gconv', lambda c, x, b, r, u: fused.gconv3x3_supported(c, x, b),
      lambda c, x, b, r, u, bare: fused.gconv3x3_bias_act(c, x, None if bare else b, not bare), False, None),
+    # (bfloat16 behind fused.CONV3_BF16 and float16 behind fused.F16: one row for both 16-bit types)
     ('bf16', lambda c, x, b, r, u: fused.conv3x3_bf16_supported(c, x, b, r),
      lambda c, x, b, r, u, bare: fused.conv3x3_bias_act_bf16(c, x, b, r, relu=not bare), True, None),
     ('gconv-bf16', lambda c, x, b, r, u: fused.gconv3x3_bf16_supported(c, x, b),
@@ -139,8 +140,8 @@ class _Bottleneck(nn.Module):
                 identity = x if self.downsample is None else self.downsample[0](x)
                 # (a_bias: conv2's bias + ReLU applied by the 1x1 GEMM while it stages its operand)
                 return fused.conv_bias_act(self.conv3, out, self.fb3, identity, a_bias=a_bias)
-            # a block WITH a downsampling convolution, bfloat16 with fused.PAIR_BF16: conv3(out) + downsample(x) as ONE launch on the
-            # bf16 MFMA, one rounding; conv2's bias + ReLU applied to the operand where conv2 left them out
+            # a block WITH a downsampling convolution, bfloat16 with fused.PAIR_BF16 or float16 with fused.F16: conv3(out) + downsample(x)
+            # as ONE launch on the 16-bit MFMA, one rounding; conv2's bias + ReLU applied to the operand where conv2 left them out
             if self.downsample is not None and fused.pair_bf16_supported(self.conv3, self.downsample[0], out, x, self.fb3, a_bias):
                 return fused.conv1x1_pair_bias_act_bf16(self.conv3, self.downsample[0], out, x, self.fb3, True, a_bias)
             # a block WITH a downsampling convolution, float32: conv3(out) + downsample(x) as ONE product (the identity tensor
@@ -195,12 +196,12 @@ class _BasicBlock(nn.Module):
         if self.fused:
             if self.downsample is None:
                 identity = x
-            elif fused.conv1x1_strided_bf16_supported(self.downsample[0], x):    # bfloat16 with fused.PAIR_BF16: the strided 1x1 on the bf16 MFMA
+            elif fused.conv1x1_strided_bf16_supported(self.downsample[0], x):    # (PAIR_BF16, or F16 for float16:) the strided 1x1 on the 16-bit MFMA
                 identity = fused.conv1x1_strided_bf16(self.downsample[0], x)
             else:
                 identity = self.downsample[0](x)
             out = _conv3x3(self.conv1, x, self.fb1, u=self._wino[0], skip=self._SKIP)[0]
-            return _conv3x3(self.conv2, out, self.fb2, identity, u=self._wino[1], skip=self._SKIP)[0]       # (the bf16 kernel adds the identity)
+            return _conv3x3(self.conv2, out, self.fb2, identity, u=self._wino[1], skip=self._SKIP)[0]       # (the 16-bit kernel adds the identity)
         identity = x if self.downsample is None else self.downsample(x)
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.bn2(self.conv2(out))
