@@ -826,6 +826,37 @@ int opa_head_epilogue(const void* conv_dev, int32_t dtype, int32_t batch, int32_
                       int32_t n_fields, int32_t n_components, int32_t upsample, int32_t n_confidences,
                       int32_t n_vectors, uint32_t vector_offset_mask, int32_t n_scales, float* out_dev, void* stream);
 
+/* A head of a network cast to bfloat16 in ONE kernel (csrc/head16.hip; reference network/heads.py:330-378 runs torch.nn.Conv2d,
+ * PixelShuffle, a crop and three in-place passes): its 1x1 convolution on the bf16 MFMA, float32 accumulation, and opa_head_epilogue's
+ * arithmetic on the float32 sums -- nothing 16-bit is written, the convolution's output is never rounded:
+ *     out[b, f, c, y*us + dy, x*us + dx] = field_c(x[m, 0:k] * w[n, 0:k]^T + bias[n]),   m = (b*hc + y)*wc + x, n = (f*C + c)*us^2 + dy*us + dx
+ * us = upsample 1 or 2, C = n_components, field_c as opa_head_epilogue defines it (one device function for both), positions of the last
+ * us - 1 rows and columns cropped: H = hc*us - (us-1), W likewise.
+ *  x_dev     the trunk's output, dense channels-last bf16 [batch, hc, wc, k], k % 64 == 0, read where it lies
+ *  w_dev     bf16 [Np][k], K-major, Np = N = n_fields*n_components*us^2 rounded UP to a multiple of 64: rows 0 .. N-1 the convolution's
+ *            weight, the rows from N on ZEROS (they are multiplied; their columns are never stored)
+ *  bias_dev  FLOAT32 [Np] (a bf16 bias upcast; what stands behind N is read and not used)
+ *  out_dev   float32 [batch, n_fields, n_components, H, W], every element written exactly once
+ * n_components == 1 + n_confidences + 2*n_vectors + n_scales.  x (batch*hc*wc*k) and out fewer than 2^31 elements each (32-bit element
+ * offsets into both; the weight's rows are addressed in 64 bits), N at most 2^31 - 64; x_dev and w_dev 16-B, bias_dev and out_dev 4-B
+ * aligned.  A row of the tile behind the last pixel is not loaded, and no address outside x is read.  Plain stores, no workspace, no
+ * atomics: equal inputs give equal bits.  The checks in order -- null pointers (all four), alignment, batch < 0, non-positive hc, wc, k,
+ * n_fields or n_components, k % 64, upsample, the component counts (none negative), x's size, N, out's size -- each with a message of its
+ * own; behind them batch == 0: OPA_OK, nothing runs; everything else outside this contract is OPA_ERR_INVALID_ARGUMENT.  Nothing is
+ * launched by a refused call. */
+int opa_head_conv_fields_bf16(const void* x_dev, const void* w_dev, const float* bias_dev, float* out_dev,
+                              int32_t batch, int32_t hc, int32_t wc, int32_t k,
+                              int32_t n_fields, int32_t n_components, int32_t upsample, int32_t n_confidences,
+                              int32_t n_vectors, uint32_t vector_offset_mask, int32_t n_scales, void* stream);
+
+/* opa_head_conv_fields_bf16 for a network cast to FLOAT16, on v_mfma_f32_32x32x16_f16: the same kernel with the element type as its
+ * template parameter -- x and w float16 where the twin has bf16, bias_dev and out_dev FLOAT32 as there -- and the same contract, checks
+ * and messages under this name. */
+int opa_head_conv_fields_f16(const void* x_dev, const void* w_dev, const float* bias_dev, float* out_dev,
+                             int32_t batch, int32_t hc, int32_t wc, int32_t k,
+                             int32_t n_fields, int32_t n_components, int32_t upsample, int32_t n_confidences,
+                             int32_t n_vectors, uint32_t vector_offset_mask, int32_t n_scales, void* stream);
+
 /* ---- image preprocessing ------------------------------------------------ */
 /* The evaluation pipeline in front of the network (ref: transforms/scale.py:42-63,150-174 RescaleAbsolute,
  * transforms/pad.py:15-112 CenterPad / CenterPadTight, transforms/__init__.py:26-33 ToTensor + Normalize) for a whole batch of

@@ -193,6 +193,8 @@ SYMBOLS = {
                                           _vp]),
     'opa_channel_interleave': (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp]),
     'opa_head_epilogue': (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.c_uint32, _i32, _vp, _vp]),
+    'opa_head_conv_fields_bf16': (ctypes.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 9 + [ctypes.c_uint32, _i32, _vp]),
+    'opa_head_conv_fields_f16': (ctypes.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 9 + [ctypes.c_uint32, _i32, _vp]),
     'opa_pre_image_bytes': (_sz, []),
     'opa_preprocess_workspace_bytes': (_sz, [_P(PreImage), _i32, _i32]),
     'opa_preprocess_u8': (ctypes.c_int, [_P(PreImage), _vp, _i32, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _i32, _i32, _i32, _i32,

@@ -19,7 +19,8 @@
 //                      but those of the sizes' products, and for opa_groupnorm_actp (pixels, channels and groups must be positive),
 //                      after every check of its arguments but the limits and the workspace; an empty batch, h or w for
 //                      opa_conv3x3_act_bf16, opa_gconv3x3_act_bf16, opa_stem7x7_act_bf16 and opa_gemm2_bias_act_bf16, after every check
-//                      but the grid's.
+//                      but the grid's; an empty batch alone (the other sizes must be positive) for opa_head_conv_fields_bf16 / _f16,
+//                      after every check but the grid's.
 //                      opa_conv3x3_f32x3, opa_gemm2_bias_act_f32x3, opa_conv_rows_*, Winograd, dwconv, squeeze-excite, interleave and the head epilogue refuse empties.
 //   last error         a call that succeeds leaves opa_last_error's text as it was.
 //   marks              the entry points that pass a kernel's name to Entry::launched mark the profile here; the launchers of the
@@ -699,6 +700,55 @@ int opa_head_epilogue(const void* conv_dev, int32_t dtype, int32_t batch, int32_
         return E.refuse("bad arguments");
     return E.launched(launch_head_epilogue(conv_dev, dtype, batch, hc, wc, n_fields, n_components, upsample, n_confidences,
                                            n_vectors, vector_offset_mask, n_scales, out_dev, E.st), "head epilogue");
+}
+
+// a 16-bit head's 1x1 convolution and the head epilogue as one kernel on the 16-bit MFMA (csrc/head16.hip): one message per check, in
+// this order: null pointers, alignment, a negative batch, the sizes, k, upsample, the component counts, x's size, the weight's rows,
+// out's size; then the empty call; then the grid.  opa_head_conv_fields_bf16 and its float16 twin (`dtype` 1: x and w float16, the
+// kernel on the f16 MFMA)
+static int head_conv_fields_16(const char* fn, int dtype, const void* x_dev, const void* w_dev, const float* bias_dev, float* out_dev,
+                               int32_t batch, int32_t hc, int32_t wc, int32_t k, int32_t n_fields, int32_t n_components, int32_t upsample,
+                               int32_t n_confidences, int32_t n_vectors, uint32_t vector_offset_mask, int32_t n_scales, void* stream) {
+    const Entry E(fn, stream);
+    if (!x_dev || !w_dev || !bias_dev || !out_dev) return E.refuse("x_dev, w_dev, bias_dev and out_dev must not be NULL");
+    if (misaligned(15, {x_dev, w_dev}) || misaligned(3, {bias_dev, out_dev}))
+        return E.refuse("x_dev / w_dev must be 16-B, bias_dev / out_dev 4-B aligned");
+    if (batch < 0) return E.refuse("negative batch");
+    if (hc <= 0 || wc <= 0 || k <= 0 || n_fields <= 0 || n_components <= 0) return E.refuse("hc, wc, k, n_fields and n_components must be positive");
+    if (k % 64 != 0) return E.refuse("k must be a multiple of 64");
+    if (upsample != 1 && upsample != 2) return E.refuse("upsample must be 1 or 2");
+    // (in 64 bits: the counts are 32-bit)
+    if (n_confidences < 0 || n_vectors < 0 || n_scales < 0 || 1ll + n_confidences + 2ll * n_vectors + n_scales != n_components)
+        return E.refuse("n_components must be 1 + n_confidences + 2 * n_vectors + n_scales, no count negative");
+    // 32-bit element offsets into x and out, a 32-bit column count (in double: exact up to 2^53, and no product of these arguments
+    // overflows it); the weight's rows are addressed in 64 bits
+    const double pixels = (double)batch * hc * wc, n = (double)n_fields * n_components * upsample * upsample;
+    if (pixels * k >= 2147483648.0) return E.refuse("x must hold fewer than 2^31 elements (32-bit offsets)");
+    if (n > 2147483584.0) return E.refuse("n_fields * n_components * upsample^2 must not exceed 2^31 - 64");
+    const double ho = (double)hc * upsample - (upsample - 1), wo = (double)wc * upsample - (upsample - 1);
+    if ((double)batch * n_fields * n_components * ho * wo >= 2147483648.0) return E.refuse("out must hold fewer than 2^31 elements (32-bit offsets)");
+    if (batch == 0) return OPA_OK;
+    // (grid.x: tiles of 128 pixels x 64 columns)
+    if (head16_workgroups(batch, hc, wc, n_fields, n_components, upsample) > 0x7fffffffll) return E.refuse("too many tiles for grid.x");
+    return E.launched(launch_head16(x_dev, w_dev, bias_dev, out_dev, batch, hc, wc, k, n_fields, n_components, upsample, n_confidences, n_vectors,
+                                    vector_offset_mask, n_scales, E.st, dtype), dtype == 1 ? "head_conv_fields_f16" : "head_conv_fields_bf16",
+                      dtype == 1 ? "head16_f16_kernel" : "head16_bf16_kernel");
+}
+
+int opa_head_conv_fields_bf16(const void* x_dev, const void* w_dev, const float* bias_dev, float* out_dev,
+                              int32_t batch, int32_t hc, int32_t wc, int32_t k,
+                              int32_t n_fields, int32_t n_components, int32_t upsample, int32_t n_confidences,
+                              int32_t n_vectors, uint32_t vector_offset_mask, int32_t n_scales, void* stream) {
+    return head_conv_fields_16("opa_head_conv_fields_bf16", 2, x_dev, w_dev, bias_dev, out_dev, batch, hc, wc, k, n_fields, n_components, upsample,
+                               n_confidences, n_vectors, vector_offset_mask, n_scales, stream);
+}
+
+int opa_head_conv_fields_f16(const void* x_dev, const void* w_dev, const float* bias_dev, float* out_dev,
+                             int32_t batch, int32_t hc, int32_t wc, int32_t k,
+                             int32_t n_fields, int32_t n_components, int32_t upsample, int32_t n_confidences,
+                             int32_t n_vectors, uint32_t vector_offset_mask, int32_t n_scales, void* stream) {
+    return head_conv_fields_16("opa_head_conv_fields_f16", 1, x_dev, w_dev, bias_dev, out_dev, batch, hc, wc, k, n_fields, n_components, upsample,
+                               n_confidences, n_vectors, vector_offset_mask, n_scales, stream);
 }
 
 size_t opa_pre_image_bytes(void) { return sizeof(opa_pre_image); }

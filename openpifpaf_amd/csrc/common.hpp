@@ -391,6 +391,13 @@ hipError_t launch_groupnorm(const float* x, long long xs, const float* gamma, co
 
 hipError_t launch_head_epilogue(const void* conv, int dtype, int B, int Hc, int Wc, int n_fields, int n_comp, int us,
                                 int n_conf, int n_vec, unsigned offset_mask, int n_scales, float* out, hipStream_t st);
+// csrc/head16.hip: a 16-bit head's 1x1 convolution and that epilogue in one kernel.  x [B, hc, wc, K] dense channels-last, 16-bit
+// (dtype 2 bfloat16, 1 float16; anything else, or us outside {1, 2}: hipErrorInvalidValue), K % 64 == 0; w [Np][K] of that type, Np =
+// n_fields * n_comp * us^2 rounded up to 64, zero rows behind; bias float32 [Np]; out float32 [B, n_fields, n_comp, H, W].  B * hc * wc * K,
+// B * hc * wc and out's elements below 2^31.  head16_workgroups = grid.x of the launch.
+long long head16_workgroups(int B, int hc, int wc, int n_fields, int n_comp, int us);
+hipError_t launch_head16(const void* x, const void* w, const float* bias, float* out, int B, int hc, int wc, int K, int n_fields,
+                         int n_comp, int us, int n_conf, int n_vec, unsigned offset_mask, int n_scales, hipStream_t st, int dtype);
 
 // Image preprocessing (preprocess.hip): pass H (h_blocks workgroups per image; 0: no image needs it) + pass V, or with
 // `precise` the zoom kernel.  in_cap: source pixels of one row that 256 output columns can reach (sizes the dynamic LDS).

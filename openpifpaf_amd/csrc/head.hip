@@ -9,6 +9,7 @@
 // rows of the 16 planes those channels feed (coalesced along x).  Reads 0.1 GB + writes 0.2 GB per batch of 32
 // instead of five PyTorch passes over the 0.2 GB field tensors.
 #include "common.hpp"
+#include "head_field.hpp"
 
 #include <hip/hip_fp16.h>
 
@@ -51,15 +52,7 @@ __global__ __launch_bounds__(kHeadThreads) void head_epilogue_kernel(
         const int xs = x + low_cut, j = xs % US, w = xs / US;
         float v = tile[(p * SUB + i * US + j) * pitch + w];
         const int plane = p0 + p, c = plane % n_comp;    // component within its field
-        if (c >= 1 && c < 1 + n_conf) {
-            v = 1.0f / (1.0f + expf(-v));                // sigmoid (heads.py:364)
-        } else if (c >= 1 + n_conf && c < 1 + n_conf + 2 * n_vec) {
-            const int vi = (c - 1 - n_conf) >> 1, is_y = (c - 1 - n_conf) & 1;
-            if ((offset_mask >> vi) & 1u) v += is_y ? (float)y : (float)x;              // heads.py:366-370
-        } else if (c >= 1 + n_conf + 2 * n_vec && c < 1 + n_conf + 2 * n_vec + n_scales) {
-            v = v > 20.0f ? v : log1pf(expf(v));         // softplus, beta 1, threshold 20 (heads.py:374)
-        }
-        out[(((size_t)b * n_planes + plane) * Ho + y) * Wo + x] = v;
+        out[(((size_t)b * n_planes + plane) * Ho + y) * Wo + x] = head_field(v, c, x, y, n_conf, n_vec, offset_mask, n_scales);
     }
 }
 

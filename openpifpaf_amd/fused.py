@@ -148,10 +148,19 @@ GCONV_BF16 = _switch('OPA_GCONV_BF16', '0')
 # 1x1 alone (``conv1x1_pair_bias_act_bf16`` / ``conv1x1_strided_bf16``) -- the ``opa_*_f16`` entry points: OPA_F16=1 (or
 # fused.F16 = True).  ONE switch for the three routes, independent of the bfloat16 switches, which a float16 operand never asks
 # (``_route16``); with it off every predicate declines a float16 operand and the network runs MIOpen's convolutions + ``bias_act_``.
-# Never timed by ``pick``.  The 7x7 stem, the grouped 3x3, the unit mode, the max-pool and the heads' convolution have no float16
-# form.  It ships OFF; the one timing is tools/gpu/f16_times.py, profiles/f16/times.log, and switching the default is a change of its
-# own that rests on it.
+# Never timed by ``pick``.  The 7x7 stem, the grouped 3x3, the unit mode and the max-pool have no float16 form; the heads have a 16-bit
+# form of their own behind their own switch (``HEAD16``, below), which this one does not touch.  It ships OFF; the one timing is
+# tools/gpu/f16_times.py, profiles/f16/times.log, and switching the default is a change of its own that rests on it.
 F16 = _switch('OPA_F16', '0')
+# The heads of a network cast to bfloat16 or float16 -- the 1x1 convolution AND everything ``CompositeField4`` does behind it -- as ONE
+# kernel on the 16-bit MFMA (csrc/head16.hip, ``head_conv_fields16``: ``opa_head_conv_fields_bf16`` / ``..._f16``) instead of torch's
+# 16-bit ``Conv2d`` + ``opa_head_epilogue``: the float32 accumulators go through the field function straight to the float32 fields, so
+# the convolution's output is neither rounded to 16 bits nor written and read back.  OPA_HEAD16=1 (or fused.HEAD16 = True).  ONE
+# switch for both 16-bit types, independent of ``F16`` and the ``*_BF16`` switches (``_route16`` is not asked).  Never timed by ``pick``,
+# no choice-table entry: where the switch is on and ``head_conv_fields16_supported`` the kernel runs.  A head whose input width is no
+# multiple of 64 (shufflenetv2k16: 1392) keeps its unit-mode route.  It ships OFF; the one timing is tools/gpu/head16_times.py,
+# profiles/head16/times.log, and switching the default is a change of its own that rests on it.
+HEAD16 = _switch('OPA_HEAD16', '0')
 # element type -> (is the route on, given the route's own bfloat16 switch?; the suffix of its entry points) for the routes on the
 # shared 16-bit MFMA tile
 _ROUTES16 = {torch.bfloat16: (lambda own: own, '_bf16'), torch.float16: (lambda own: F16, '_f16')}
@@ -475,6 +484,82 @@ def head_epilogue(x, meta):
     mask = sum(1 << i for i, on in enumerate(meta.vector_offsets) if on)
     _launch('opa_head_epilogue', _ptr(x), _DTYPES[x.dtype], B, hc, wc, n_fields, n_comp, us, meta.n_confidences,
             meta.n_vectors, mask, meta.n_scales, _ptr(out))
+    return out
+
+
+# ---- a 16-bit head in one kernel ------------------------------------------------------------------------------------------------------
+
+HEAD16_TILE_N = 64                        # kHead16BN: the weight's rows and the bias are padded to it
+_HEAD16_SUFFIX = {torch.bfloat16: '_bf16', torch.float16: '_f16'}
+# (k, n, upsample) of heads that ``opa_head_conv_fields_bf16`` / ``..._f16`` can run but that came out SLOWER at batch 32 than what runs
+# with the switch off (tools/gpu/head16_times.py, profiles/head16/times.log): the predicate declines them.
+HEAD16_DECLINED = frozenset()
+
+
+def head16_operands_of(conv):
+    """The operands of ``head_conv_fields16`` derived from the CURRENT parameters of a head's 1x1 convolution (16-bit ``[N, K, 1, 1]``
+    and ``[N]``): the weight as ``[Np][K]`` of its dtype, K-major, ``Np`` = ``N`` rounded up to ``HEAD16_TILE_N``, ZEROS in the rows from
+    ``N`` on, and the bias as FLOAT32 ``[Np]`` (upcast exactly, zeros behind ``N``).  Derived and cached on ``conv`` (``derived``, keyed on
+    both tensors' storage and version): no buffer, no part of a state dict, computed again whenever the weight or the bias was replaced,
+    moved, converted or changed in place."""
+    def make():
+        w = conv.weight.detach()
+        n, k = w.shape[0], w.shape[1]
+        npad = (n + HEAD16_TILE_N - 1) // HEAD16_TILE_N * HEAD16_TILE_N
+        wp = torch.zeros((npad, k), dtype=w.dtype, device=w.device)
+        wp[:n] = w.reshape(n, k)
+        bp = torch.zeros(npad, dtype=torch.float32, device=w.device)
+        bp[:n] = conv.bias.detach()
+        return wp, bp
+    return derived(conv, '_opa_head16', (conv.weight, conv.bias), make)
+
+
+def _head16_shape(conv, x, meta):
+    """(n_components, H, W) of the fields that ``conv`` and ``meta`` make of ``x``."""
+    us = meta.upsample_stride
+    return (1 + meta.n_confidences + meta.n_vectors * 2 + meta.n_scales, x.shape[2] * us - (us - 1), x.shape[3] * us - (us - 1))
+
+
+def head_conv_fields16_supported(conv, x, meta, training=False):
+    """Can ``head_conv_fields16(conv, x, meta)`` run?  The switch ``HEAD16`` on and the library built; not training; ``x`` a dense
+    channels-last bfloat16 or float16 ``[B, K, hc, wc]`` on the GPU, 16-byte aligned, with pixels; weight and bias of ``x``'s dtype on its
+    device (autocast's float32 parameters are declined), outside autocast, nothing that autograd follows; ``conv`` 1x1, stride 1, no
+    padding or dilation, one group, with a bias; ``K % 64 == 0``; ``meta.upsample_stride`` 1 or 2 and ``conv.out_channels`` the
+    ``n_fields * n_components * upsample^2`` of ``meta``'s counts, none negative; ``x`` and the fields fewer than 2^31 elements each;
+    ``(K, N, upsample)`` not in ``HEAD16_DECLINED``.  No limit on the row width: nothing here buffers a row."""
+    if not (HEAD16 and not training and x.dtype in _HEAD16_SUFFIX and x.is_cuda and not torch.is_autocast_enabled()
+            and isinstance(conv, torch.nn.Conv2d) and conv.bias is not None):
+        return False
+    w, b = conv.weight, conv.bias
+    if not (w.dtype == x.dtype and b.dtype == x.dtype and w.device == x.device and b.device == x.device
+            and not (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or b.requires_grad))):
+        return False
+    k, n, us = conv.in_channels, conv.out_channels, meta.upsample_stride
+    if not (conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1
+            and k % 64 == 0 and us in (1, 2) and x.dim() == 4 and x.shape[1] == k and x.shape[2] > 0 and x.shape[3] > 0
+            and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0):
+        return False
+    counts = (meta.n_fields, meta.n_confidences, meta.n_vectors, meta.n_scales)
+    n_comp, H, W = _head16_shape(conv, x, meta)
+    if not (meta.n_fields > 0 and min(counts) >= 0 and len(meta.vector_offsets) <= 32 and n == meta.n_fields * n_comp * us * us):
+        return False
+    return (x.numel() < 2 ** 31 and x.shape[0] * meta.n_fields * n_comp * H * W < 2 ** 31 and _lib.available()
+            and (k, n, us) not in HEAD16_DECLINED)
+
+
+def head_conv_fields16(conv, x, meta):
+    """A 16-bit head in ONE launch (``opa_head_conv_fields_bf16`` / ``..._f16``, csrc/head16.hip): ``conv``, the head's 1x1 convolution,
+    on the 16-bit MFMA with float32 accumulation and, on the float32 sums, everything ``CompositeField4`` does behind it (reference
+    ``network/heads.py:330-378``: PixelShuffle -> crop -> sigmoid / index offsets / softplus; ``head_epilogue``'s arithmetic, one device
+    function for both) -> ``[B, F, C, H, W]`` float32.  The convolution's output is never rounded to 16 bits and never written.
+    ``head_conv_fields16_supported`` says whether this can run."""
+    wp, bp = head16_operands_of(conv)
+    B, k, hc, wc = x.shape
+    n_comp, H, W = _head16_shape(conv, x, meta)
+    out = torch.empty((B, meta.n_fields, n_comp, H, W), dtype=torch.float32, device=x.device)
+    mask = sum(1 << i for i, on in enumerate(meta.vector_offsets) if on)
+    _launch('opa_head_conv_fields' + _HEAD16_SUFFIX[x.dtype], _ptr(x), _ptr(wp), _ptr(bp), _ptr(out), B, hc, wc, k, meta.n_fields, n_comp,
+            meta.upsample_stride, meta.n_confidences, meta.n_vectors, mask, meta.n_scales)
     return out
 
 

@@ -1143,6 +1143,9 @@ class CompositeField4(nn.Module):
     fused_epilogue = True      # one HIP kernel for everything behind the convolution (inference, channels_last)
 
     def forward(self, x):
+        if not self.training and self.fused_epilogue and fused.head_conv_fields16_supported(self.conv, x, self.meta, self.training):
+            # 16-bit inference behind fused.HEAD16: the convolution on the 16-bit MFMA and the epilogue on its float32 sums, one kernel
+            return fused.head_conv_fields16(self.conv, x, self.meta)
         if not self.training and fused.head_conv_x3_supported(self.conv, x):     # float32 inference: the head's 1x1 convolution through
             conv, x0 = self.conv, x                                                # the split-operand GEMM where that is faster
             x = fused.pick('head', fused.out_pixels(x0), conv.in_channels, conv.out_channels, False, False,
