@@ -576,6 +576,14 @@ int opa_gemm_unit_actp_bf16(const void* a_dev, int64_t a_pitch, const void* w_de
                             const void* partner_dev, int64_t partner_pitch, const void* residual_dev, int64_t residual_pitch,
                             void* out_dev, int64_t m, int32_t n, int32_t k, int32_t act, float act_param, void* stream);
 
+/* The same for a network cast to FLOAT16: a_dev, w_dev, partner_dev, residual_dev and out_dev float16, bias_dev float32, the same
+ * kernel on v_mfma_f32_32x32x16_f16.  Float32 accumulation, bias and activation; ONE round-to-nearest-even conversion at the store:
+ * what rounds beyond 65504 is +-inf, NaN stays NaN, subnormal operands and results are kept (tensor.to(torch.float16) bit for bit).
+ * The partner's bits pass through untouched.  Arguments, limits, refusals and their order are opa_gemm_unit_actp_bf16's. */
+int opa_gemm_unit_actp_f16(const void* a_dev, int64_t a_pitch, const void* w_dev, const float* bias_dev,
+                           const void* partner_dev, int64_t partner_pitch, const void* residual_dev, int64_t residual_pitch,
+                           void* out_dev, int64_t m, int32_t n, int32_t k, int32_t act, float act_param, void* stream);
+
 /* The 3x3 convolutions of a ResNet cast to bfloat16 (csrc/conv3x3_bf16.hip; reference network/basenetworks.py:71-150 runs them
  * through torch.nn.Conv2d) as an implicit GEMM on the bf16 MFMA, float32 accumulation, ONE rounding at the store:
  *     out[b, oy, ox, co] = bf16_rne(act(sum_{ky,kx,ci} x[b, s*oy - d + d*ky, s*ox - d + d*kx, ci] * w[co][3*ky + kx][ci]
@@ -722,6 +730,14 @@ int opa_dwconv_dilated_act(const void* x_dev, int64_t x_pixel_stride, const void
 int opa_dwconv_actp(const void* x_dev, int64_t x_pixel_stride, const void* w_dev, const void* bias_dev,
                     void* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w,
                     int32_t channels, int32_t k, int32_t stride, int32_t dilation, int32_t dtype, int32_t act, float act_param, void* stream);
+
+/* opa_dwconv_actp for FLOAT16 tensors (x, w, bias and out float16; the depthwise convolutions of a ShuffleNetV2K cast with .half()):
+ * the same stencil, float32 accumulation (float64 products for act 2), one round-to-nearest-even conversion at the store -- beyond
+ * 65504 +-inf, NaN stays NaN, subnormal results kept.  No dtype argument: the four entry points above keep refusing dtype 1.
+ * Every window, stride, dilation and code opa_dwconv_actp accepts is accepted; the checks, their order and their words are its own. */
+int opa_dwconv_actp_f16(const void* x_dev, int64_t x_pixel_stride, const void* w_dev, const void* bias_dev,
+                        void* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w,
+                        int32_t channels, int32_t k, int32_t stride, int32_t dilation, int32_t act, float act_param, void* stream);
 
 /* The RGB stem of the non-ResNet backbones (reference network/basenetworks.py: ShuffleNetV2K, ShuffleNetV2, MobileNetV2 / V3,
  * SqueezeNet): a direct 3x3 convolution from 3 input channels, padding 1, dilation 1, stride 1 or 2, float32, with the folded bias

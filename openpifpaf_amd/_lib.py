@@ -162,6 +162,7 @@ SYMBOLS = {
     'opa_gemm_unit_actp_f32x3': (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, ctypes.c_float, _i32,
                                                 _vp]),
     'opa_gemm_unit_actp_bf16': (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, ctypes.c_float, _vp]),
+    'opa_gemm_unit_actp_f16': (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, ctypes.c_float, _vp]),
     'opa_conv3x3_act_bf16': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp] + [_i32] * 8 + [_vp]),
     'opa_conv3x3_act_f16': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp] + [_i32] * 8 + [_vp]),
     'opa_gconv3x3_act_bf16': (ctypes.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 8 + [_vp]),
@@ -182,6 +183,7 @@ SYMBOLS = {
     'opa_dwconv_dilated_act': (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     'opa_dwconv_actp': (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.c_float,
                                        _vp]),
+    'opa_dwconv_actp_f16': (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.c_float, _vp]),
     'opa_stem3x3_actp': (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.c_float, _vp]),
     'opa_gconv3x3_bias_act_f32': (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     'opa_se_workspace_bytes': (_sz, [_i32, _i64, _i32]),

@@ -9,8 +9,8 @@
 //                      The Winograd entry points, opa_dwconv_*, opa_gconv3x3_* and opa_maxpool3x3_* accept a null bias.
 //                      opa_fire_expand_f32x3 tests all four pointers.
 //                      opa_dwconv_*, opa_channel_interleave and opa_head_epilogue test no alignment at all.  The unit mode asks
-//                      8 bytes of a_dev, partner_dev and residual_dev, 16 of the rest (opa_gemm_unit_actp_bf16: 4 and 16): one
-//                      list of checks, unit_refusal, for its four entry points.  A null pointer is aligned everywhere.
+//                      8 bytes of a_dev, partner_dev and residual_dev, 16 of the rest (opa_gemm_unit_actp_bf16 / _f16: 4 and 16): one
+//                      list of checks, unit_refusal, for its five entry points.  A null pointer is aligned everywhere.
 //   act_param          one rule wherever an entry point takes it (bad_act_param); opa_dwconv_actp refuses code 3 before it.
 //   empty calls        m == 0 (opa_bias_act: rows == 0) is OPA_OK for the GEMMs; an empty batch, h or w is OPA_OK for
 //                      opa_conv3x3_dilated_f32x3, opa_maxpool3x3_bias_act, opa_maxpool3x3_ceil_bias_act, opa_fire_expand_f32x3 and
@@ -255,8 +255,8 @@ int opa_fire_expand_f32x3(const float* h_dev, const void* w_dev, const float* bi
                                          E.st), "fire_expand_f32x3", "fire_expand_kernel");
 }
 
-// The checks of the unit mode's four entry points -> what is wrong, or null.  What differs between them: `act_max`; `mask`, the alignment
-// of a_dev / partner_dev / residual_dev (8 bytes, 4 for bfloat16), and `unaligned`, the message that names it; `terms`, null where the
+// The checks of the unit mode's five entry points -> what is wrong, or null.  What differs between them: `act_max`; `mask`, the alignment
+// of a_dev / partner_dev / residual_dev (8 bytes, 4 for the 16-bit types), and `unaligned`, the message that names it; `terms`, null where the
 // entry point has none.  The pitches count elements.  act 3 (LeakyReLU) and 4 (clipped ReLU) read act_param.
 static const char* unit_refusal(int32_t act_max, uintptr_t mask, const char* unaligned, const int32_t* terms, const void* a_dev, int64_t a_pitch,
                                 const void* w_dev, const float* bias_dev, const void* partner_dev, int64_t partner_pitch, const void* residual_dev,
@@ -314,19 +314,34 @@ int opa_gemm_unit_actp_f32x3(const float* a_dev, int64_t a_pitch, const void* w3
                            bias_dev, partner_dev, partner_pitch, residual_dev, residual_pitch, out_dev, m, n, k, act, terms, stream);
 }
 
-// the unit mode in bfloat16 (csrc/gemm_unit_bf16.hip): no terms
-int opa_gemm_unit_actp_bf16(const void* a_dev, int64_t a_pitch, const void* w_dev, const float* bias_dev,
-                            const void* partner_dev, int64_t partner_pitch, const void* residual_dev, int64_t residual_pitch,
-                            void* out_dev, int64_t m, int32_t n, int32_t k, int32_t act, float act_param, void* stream) {
-    const Entry E("opa_gemm_unit_actp_bf16", stream);
+// the unit mode in 16 bits (csrc/gemm_unit_bf16.hip): no terms.  opa_gemm_unit_actp_bf16 and its float16 twin (`dtype` 1: a, w, the
+// partner, the residual and out float16, the kernel on the f16 MFMA)
+static int gemm_unit_16(const char* fn, int dtype, const void* a_dev, int64_t a_pitch, const void* w_dev, const float* bias_dev,
+                        const void* partner_dev, int64_t partner_pitch, const void* residual_dev, int64_t residual_pitch,
+                        void* out_dev, int64_t m, int32_t n, int32_t k, int32_t act, float act_param, void* stream) {
+    const Entry E(fn, stream);
     if (const char* why = unit_refusal(4, 3, "a_dev / partner_dev / residual_dev must be 4-B, w_dev / bias_dev / out_dev 16-B aligned", nullptr,
                                        a_dev, a_pitch, w_dev, bias_dev, partner_dev, partner_pitch, residual_dev, residual_pitch, out_dev, m, n, k,
                                        act, act_param))
         return E.refuse(why);
     if (m == 0) return OPA_OK;
     return E.launched(launch_gemm_unit_act_bf16(a_dev, a_pitch, w_dev, bias_dev, partner_dev, partner_dev ? partner_pitch : 0, residual_dev,
-                                                residual_dev ? residual_pitch : 0, out_dev, (int)m, n, k, act, act_param, E.st),
-                      "gemm_unit_actp_bf16", "gemm_unit_bf16_kernel");
+                                                residual_dev ? residual_pitch : 0, out_dev, (int)m, n, k, act, act_param, E.st, dtype),
+                      dtype == 1 ? "gemm_unit_actp_f16" : "gemm_unit_actp_bf16", dtype == 1 ? "gemm_unit_f16_kernel" : "gemm_unit_bf16_kernel");
+}
+
+int opa_gemm_unit_actp_bf16(const void* a_dev, int64_t a_pitch, const void* w_dev, const float* bias_dev,
+                            const void* partner_dev, int64_t partner_pitch, const void* residual_dev, int64_t residual_pitch,
+                            void* out_dev, int64_t m, int32_t n, int32_t k, int32_t act, float act_param, void* stream) {
+    return gemm_unit_16("opa_gemm_unit_actp_bf16", 2, a_dev, a_pitch, w_dev, bias_dev, partner_dev, partner_pitch, residual_dev, residual_pitch,
+                        out_dev, m, n, k, act, act_param, stream);
+}
+
+int opa_gemm_unit_actp_f16(const void* a_dev, int64_t a_pitch, const void* w_dev, const float* bias_dev,
+                           const void* partner_dev, int64_t partner_pitch, const void* residual_dev, int64_t residual_pitch,
+                           void* out_dev, int64_t m, int32_t n, int32_t k, int32_t act, float act_param, void* stream) {
+    return gemm_unit_16("opa_gemm_unit_actp_f16", 1, a_dev, a_pitch, w_dev, bias_dev, partner_dev, partner_pitch, residual_dev, residual_pitch,
+                        out_dev, m, n, k, act, act_param, stream);
 }
 
 // the 3x3 convolutions of a bfloat16 ResNet as an implicit GEMM on the bf16 MFMA (csrc/conv3x3_bf16.hip): one message per check.
@@ -503,10 +518,11 @@ int opa_conv3x3_winograd_f32x3(const float* x_dev, const void* u3_dev, const flo
 
 // opa_dwconv_act, opa_dwconv_bias_act as its call with act 0 / 1, opa_dwconv_dilated_act (`dilated`: k = 7 and a dilation of 2
 // or 4 at stride 1 are accepted too; the other two pass dilation 1) and opa_dwconv_actp (`actp`: act 4, the ReLU clipped at
-// act_param, is accepted too; the others pass no parameter)
+// act_param, is accepted too; the others pass no parameter).  These four take dtype 0 (float32) or 2 (bfloat16); opa_dwconv_actp_f16
+// is opa_dwconv_actp's call for float16 tensors (`f16`: dtype 1, which no argument of the others reaches)
 static int dwconv(const char* fn, bool dilated, bool actp, float act_param, const void* x_dev, int64_t x_pixel_stride, const void* w_dev, const void* bias_dev,
                   void* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w, int32_t channels, int32_t k, int32_t stride,
-                  int32_t dilation, int32_t dtype, int32_t act, void* stream) {
+                  int32_t dilation, int32_t dtype, int32_t act, void* stream, bool f16 = false) {
     const Entry E(fn, stream);
     if (actp ? (act < 0 || act > 4 || act == 3) : (act < 0 || act > 2))
         return E.refuse(actp ? "act must be 0 (none), 1 (ReLU), 2 (hardswish) or 4 (clipped ReLU)" : "act must be 0 (none), 1 (ReLU) or 2 (hardswish)");
@@ -514,7 +530,7 @@ static int dwconv(const char* fn, bool dilated, bool actp, float act_param, cons
     const bool k_ok = k == 3 || k == 5 || (dilated && k == 7);
     const bool d_ok = dilation == 1 || (dilated && (dilation == 2 || dilation == 4) && stride == 1);
     if (!x_dev || !w_dev || !out_dev || batch <= 0 || h <= 0 || w <= 0 || channels <= 0 || x_pixel_stride < channels ||
-        out_pixel_stride < channels || !k_ok || (stride != 1 && stride != 2) || !d_ok || (dtype != 0 && dtype != 2))
+        out_pixel_stride < channels || !k_ok || (stride != 1 && stride != 2) || !d_ok || (f16 ? dtype != 1 : (dtype != 0 && dtype != 2)))
         return E.refuse("bad arguments");
     // grid.y of the stencil kernel (dwconv.hip); the padding is (k / 2) * dilation, so the window takes dilation * (k - 1) rows off
     if ((int64_t)batch * (((int64_t)h + 2 * (k / 2) * dilation - dilation * (k - 1) - 1) / stride + 1) > 65535)
@@ -549,6 +565,13 @@ int opa_dwconv_actp(const void* x_dev, int64_t x_pixel_stride, const void* w_dev
                     int32_t channels, int32_t k, int32_t stride, int32_t dilation, int32_t dtype, int32_t act, float act_param, void* stream) {
     return dwconv("opa_dwconv_actp", true, true, act_param, x_dev, x_pixel_stride, w_dev, bias_dev, out_dev, out_pixel_stride, batch, h, w, channels,
                   k, stride, dilation, dtype, act, stream);
+}
+
+int opa_dwconv_actp_f16(const void* x_dev, int64_t x_pixel_stride, const void* w_dev, const void* bias_dev,
+                        void* out_dev, int64_t out_pixel_stride, int32_t batch, int32_t h, int32_t w,
+                        int32_t channels, int32_t k, int32_t stride, int32_t dilation, int32_t act, float act_param, void* stream) {
+    return dwconv("opa_dwconv_actp_f16", true, true, act_param, x_dev, x_pixel_stride, w_dev, bias_dev, out_dev, out_pixel_stride, batch, h, w, channels,
+                  k, stride, dilation, 1, act, stream, true);
 }
 
 int opa_gconv3x3_bias_act_f32(const float* x_dev, int64_t x_pixel_stride, const float* wt_dev, const float* bias_dev,

@@ -312,10 +312,11 @@ hipError_t launch_fire_expand(const float* h, const unsigned short* w3, const fl
 hipError_t launch_gemm_unit_act_f32x3(const float* A, int lda, const unsigned short* W3, const float* bias, const float* partner, int ldp,
                                       const float* residual, int ldr, float* out, int M, int N, int K, int act, int terms, hipStream_t st,
                                       float act_param = 0.0f);
-// csrc/gemm_unit_bf16.hip: the unit mode in bfloat16 (pitches in bf16 elements; bias float32; act 0 .. 4 read at run time)
+// csrc/gemm_unit_bf16.hip: the unit mode in 16 bits (pitches in elements; bias float32; act 0 .. 4 read at run time); dtype 2 every
+// 16-bit operand bfloat16, 1 float16 on the f16 MFMA (anything else: hipErrorInvalidValue)
 hipError_t launch_gemm_unit_act_bf16(const void* A, long long lda, const void* W, const float* bias, const void* partner, long long ldp,
                                      const void* residual, long long ldr, void* out, int M, int n, int k, int act, float act_param,
-                                     hipStream_t st);
+                                     hipStream_t st, int dtype = 2);
 // csrc/conv3x3_bf16.hip: the 3x3 convolution of a dense channels-last bf16 tensor as an implicit GEMM on the bf16 MFMA: x [B, H, W, c_in],
 // w [c_out][9][c_in], bias float32 [c_out] or null, residual / out dense bf16 [B, Ho, Wo, c_out]; c_in % 64 == 0, c_out % 64 == 0, S 1 or
 // 2, D = padding 1, or 2 or 4 with S = 1; x and out below 2^31 elements (anything else: hipErrorInvalidValue).  dtype 2; with dtype 1

@@ -26,6 +26,10 @@
 // window in front of the multiply-adds, so these instantiations still take 92 - 172 registers at V = 4 (no scratch; a rolled row
 // loop took more): profiles/shufflenetv2k_options/resource_usage.md.  Measured at 696 channels, 81 x 81, batch 32: 0.87 ms for the
 // dilated 5 x 5 against 0.64 undilated and 4.15 for MIOpen (profiles/shufflenetv2k_options/times.log).
+//
+// FLOAT16 (a network cast with .half(), opa_dwconv_actp_f16): DwVec<_Float16, V> and the same kernel template over the same windows,
+// strides, dilations and activation codes -- float32 accumulation (float64 for hardswish), one conversion at the store.  `unsigned short`
+// stays bfloat16's element type; the float32 and bfloat16 instantiations are untouched (profiles/unit_f16/).
 #include "common.hpp"
 #include <type_traits>
 
@@ -67,6 +71,29 @@ template <int V> struct DwVec<unsigned short, V> {               // bfloat16
         if constexpr (V == 4) *reinterpret_cast<uint2*>(p) = make_uint2(rne(v[0]) | (rne(v[1]) << 16), rne(v[2]) | (rne(v[3]) << 16));
         else if constexpr (V == 2) *reinterpret_cast<unsigned*>(p) = rne(v[0]) | (rne(v[1]) << 16);
         else *p = (unsigned short)rne(v[0]);
+    }
+};
+// float16: 8 / 4 / 2-byte loads and stores; the conversions are the language's (v_cvt_f32_f16 / v_cvt_f16_f32, round to nearest even:
+// beyond 65504 +-inf, NaN stays NaN, subnormal results kept) -- tensor.to(torch.float16) bit for bit
+template <int V> struct DwVec<_Float16, V> {
+    typedef __attribute__((ext_vector_type(V))) _Float16 vec_t;
+    float v[V];
+    __device__ __forceinline__ void load(const _Float16* p) {
+        if constexpr (V == 1) v[0] = (float)*p;
+        else {
+            const vec_t t = *reinterpret_cast<const vec_t*>(p);
+#pragma unroll
+            for (int q = 0; q < V; q++) v[q] = (float)t[q];
+        }
+    }
+    __device__ __forceinline__ void store(_Float16* p) const {
+        if constexpr (V == 1) *p = (_Float16)v[0];
+        else {
+            vec_t t;
+#pragma unroll
+            for (int q = 0; q < V; q++) t[q] = (_Float16)v[q];
+            *reinterpret_cast<vec_t*>(p) = t;
+        }
     }
 };
 
@@ -230,6 +257,7 @@ hipError_t launch_dwconv(const void* x, long long xs, const void* w, const void*
                          int B, int H, int W, int C, int K, int S, int D, int dtype, int act, hipStream_t st, float cap) {
     if (dtype == 0) return launch_dw_t<float>(x, xs, w, bias, out, os, B, H, W, C, K, S, D, act, st, cap);
     if (dtype == 2) return launch_dw_t<unsigned short>(x, xs, w, bias, out, os, B, H, W, C, K, S, D, act, st, cap);
+    if (dtype == 1) return launch_dw_t<_Float16>(x, xs, w, bias, out, os, B, H, W, C, K, S, D, act, st, cap);
     return hipErrorInvalidValue;
 }
 

@@ -15,6 +15,12 @@
 // behind column k of the last row is addressed.  Which bytes which thread loads is decided in csrc/unit_bf16_plan.hpp, which a CPU
 // program enumerates (tests/test_unit_bf16_plan.py).  The epilogue works in column pairs: 4-byte loads of the partner / residual,
 // 4-byte stores of the output (8-byte with a partner: its two elements and the two results interleaved).
+//
+// The same kernel serves a network cast to FLOAT16 (opa_gemm_unit_actp_f16): the element type is the leading template parameter DT, and
+// only TileElem<DT> (csrc/bf16_tile.hpp) depends on it -- v_mfma_f32_32x32x16_f16 on f16x8 fragments, a residual element decoded and the
+// result rounded by the language's conversions (round to nearest even; beyond 65504 +-inf, NaN stays NaN, subnormals kept).  Loads,
+// staging, the epilogue's pairs and the partner's bits are raw 16-bit words for both types; the bfloat16 instantiations compile to the
+// instructions they had (profiles/unit_f16/bf16_codegen.md).
 #include "bf16_tile.hpp"
 #include "unit_bf16_plan.hpp"
 
@@ -27,13 +33,17 @@ typedef __attribute__((ext_vector_type(2))) float f32x2_t;
 
 enum Third { kNone = 0, kPartner = 1, kResidual = 2 };
 
-// N and K are the padded sizes (W [N][K], bias [N]); n, k the columns that exist; W_A the width of A's loads in bytes
-template <int BN, int W_A, int THIRD>
+// N and K are the padded sizes (W [N][K], bias [N]); n, k the columns that exist; W_A the width of A's loads in bytes; DT the element
+// type (the C ABI's dtype code: 2 bfloat16, 1 float16), which decides the fragment type, the MFMA, how a residual element becomes float32
+// and how a result is rounded (TileElem<DT>) -- every operand travels as raw 16-bit words
+template <int DT, int BN, int W_A, int THIRD>
 __global__ __launch_bounds__(256, 3) void gemm_unit_bf16_kernel(
         const unsigned short* __restrict__ A, long long lda, const unsigned short* __restrict__ W, const float* __restrict__ bias,
         const unsigned short* __restrict__ third, long long ldt, unsigned short* __restrict__ out, int M, int N, int K, int n, int k,
         int act, float act_param) {
     using T = Bf16Tile<BN>;
+    using E = TileElem<DT>;
+    typedef typename E::frag_t frag_t;
     constexpr int WN = T::WN, NT = T::NT;
     __shared__ __attribute__((aligned(16))) unsigned char smem[T::LDS_BYTES];
     unsigned short* sA = reinterpret_cast<unsigned short*>(smem);
@@ -88,19 +98,19 @@ __global__ __launch_bounds__(256, 3) void gemm_unit_bf16_kernel(
         if (k0 + kBf16BK < K) fetch(k0 + kBf16BK);   // the next K-step's operands travel while this one multiplies
 #pragma unroll
         for (int kk = 0; kk < kBf16BK; kk += 16) {
-            bf16x8_t fa[2], fb[NT];
+            frag_t fa[2], fb[NT];
             const int kof = kk + (lane >> 5) * 8;
 #pragma unroll
             for (int i = 0; i < 2; i++)
-                fa[i] = *reinterpret_cast<const bf16x8_t*>(sA + (wm * 64 + i * 32 + (lane & 31)) * kBf16Pitch + kof);
+                fa[i] = *reinterpret_cast<const frag_t*>(sA + (wm * 64 + i * 32 + (lane & 31)) * kBf16Pitch + kof);
 #pragma unroll
             for (int j = 0; j < NT; j++)
-                fb[j] = *reinterpret_cast<const bf16x8_t*>(sB + (wn * WN + j * 32 + (lane & 31)) * kBf16Pitch + kof);
+                fb[j] = *reinterpret_cast<const frag_t*>(sB + (wn * WN + j * 32 + (lane & 31)) * kBf16Pitch + kof);
 #pragma unroll
             for (int i = 0; i < 2; i++)
 #pragma unroll
                 for (int j = 0; j < NT; j++)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+                    acc[i][j] = E::mfma(fa[i], fb[j], acc[i][j]);
         }
     }
     __syncthreads();                           // staging LDS is free: reuse it for the epilogue
@@ -130,9 +140,9 @@ __global__ __launch_bounds__(256, 3) void gemm_unit_bf16_kernel(
         bf16_tile_patch_sync();
         unit_bf16_plan_third<WN>(M, n, ldt, m0w, n0w, lane, [&](int t, long long row, int col, long long) {
             f32x2_t f = *reinterpret_cast<const f32x2_t*>(patch + (int)(row - m0w) * WN + (col - n0w));
-            if (THIRD == kResidual) { f[0] += bf16_lo(tv[t]); f[1] += bf16_hi(tv[t]); }
+            if (THIRD == kResidual) { f[0] += E::lo(tv[t]); f[1] += E::hi(tv[t]); }
             f[0] = act_f32(f[0], act, act_param); f[1] = act_f32(f[1], act, act_param);
-            const unsigned y0 = bf16_rne(f[0]), y1 = bf16_rne(f[1]);
+            const unsigned y0 = E::rne(f[0]), y1 = E::rne(f[1]);
             if (THIRD == kPartner)             // the partner's bits pass through untouched
                 *reinterpret_cast<u32x2_t*>(out + (size_t)row * (2 * (size_t)n) + 2 * col) =
                     (u32x2_t){(tv[t] & 0xffffu) | (y0 << 16), (tv[t] >> 16) | (y1 << 16)};
@@ -150,9 +160,11 @@ __global__ __launch_bounds__(256, 3) void gemm_unit_bf16_kernel(
 
 // A [M, k] with `lda` elements between rows, W [Np][Kp] and bias [Np] padded with zeros, partner or residual [M, n] with `ldp` / `ldr`
 // elements between rows or null (never both); out [M, n] dense, or [M, 2n] with a partner.  act 0 .. 4 is read at run time.
+// dtype: 2 every 16-bit operand bfloat16, 1 float16 (the same kernel on v_mfma_f32_32x32x16_f16).
 hipError_t launch_gemm_unit_act_bf16(const void* A, long long lda, const void* W, const float* bias, const void* partner, long long ldp,
                                      const void* residual, long long ldr, void* out, int M, int n, int k, int act, float act_param,
-                                     hipStream_t st) {
+                                     hipStream_t st, int dtype) {
+    if (dtype != 1 && dtype != 2) return hipErrorInvalidValue;
     if ((partner && residual) || act < 0 || act > 4 || (residual && act > 2) || M <= 0 || n <= 0 || k <= 0) return hipErrorInvalidValue;
     const int Np = (n + 63) / 64 * 64, Kp = (k + 63) / 64 * 64;
     const int bn = Np % 128 == 0 ? 128 : 64;
@@ -161,13 +173,14 @@ hipError_t launch_gemm_unit_act_bf16(const void* A, long long lda, const void* W
     const int third = partner ? kPartner : residual ? kResidual : kNone;
     const unsigned short* t = (const unsigned short*)(partner ? partner : residual);
     const long long ldt = partner ? ldp : residual ? ldr : 0;
+    return with_value<2, 1>(dtype, [&](auto DT) {
     return with_value<64, 128>(bn, [&](auto BN) {
     return with_value<4, 8, 16>(unit_bf16_width((uintptr_t)A, lda), [&](auto W_A) {
     return with_value<(int)kNone, (int)kPartner, (int)kResidual>(third, [&](auto THIRD) {
-        gemm_unit_bf16_kernel<BN, W_A, THIRD><<<(unsigned)blocks, kBf16Threads, 0, st>>>(
+        gemm_unit_bf16_kernel<DT, BN, W_A, THIRD><<<(unsigned)blocks, kBf16Threads, 0, st>>>(
             (const unsigned short*)A, lda, (const unsigned short*)W, bias, t, ldt, (unsigned short*)out, M, Np, Kp, n, k, act, act_param);
         return hipGetLastError();
-    }); }); });
+    }); }); }); });
 }
 
 }  // namespace opa

@@ -148,8 +148,9 @@ GCONV_BF16 = _switch('OPA_GCONV_BF16', '0')
 # 1x1 alone (``conv1x1_pair_bias_act_bf16`` / ``conv1x1_strided_bf16``) -- the ``opa_*_f16`` entry points: OPA_F16=1 (or
 # fused.F16 = True).  ONE switch for the three routes, independent of the bfloat16 switches, which a float16 operand never asks
 # (``_route16``); with it off every predicate declines a float16 operand and the network runs MIOpen's convolutions + ``bias_act_``.
-# Never timed by ``pick``.  The 7x7 stem, the grouped 3x3, the unit mode and the max-pool have no float16 form; the heads have a 16-bit
-# form of their own behind their own switch (``HEAD16``, below), which this one does not touch.  It ships OFF; the one timing is
+# Never timed by ``pick``.  The 7x7 stem, the grouped 3x3 and the max-pool have no float16 form (the unit mode has its own switch,
+# ``UNIT_F16``, below); the heads have a 16-bit form of their own behind their own switch (``HEAD16``, below), which this one does
+# not touch.  It ships OFF; the one timing is
 # tools/gpu/f16_times.py, profiles/f16/times.log, and switching the default is a change of its own that rests on it.
 F16 = _switch('OPA_F16', '0')
 # The heads of a network cast to bfloat16 or float16 -- the 1x1 convolution AND everything ``CompositeField4`` does behind it -- as ONE
@@ -161,6 +162,15 @@ F16 = _switch('OPA_F16', '0')
 # multiple of 64 (shufflenetv2k16: 1392) keeps its unit-mode route.  It ships OFF; the one timing is tools/gpu/head16_times.py,
 # profiles/head16/times.log, and switching the default is a change of its own that rests on it.
 HEAD16 = _switch('OPA_HEAD16', '0')
+# A ShuffleNetV2K / ShuffleNetV2 cast to FLOAT16 (``model.half()``) on the kernels its bfloat16 twin takes, instantiated for the other
+# 16-bit type: every 1x1 convolution of the units, ``conv5`` and a head whose input channels are no multiple of 64 through the unit mode
+# of the 16-bit GEMM on v_mfma_f32_32x32x16_f16 (csrc/gemm_unit_bf16.hip, ``conv1x1_unit_f16``: ``opa_gemm_unit_actp_f16``), every
+# depthwise convolution through the stencil (csrc/dwconv.hip: ``opa_dwconv_actp_f16``) instead of MIOpen's convolutions:
+# OPA_UNIT_F16=1 (or fused.UNIT_F16 = True).  Independent of ``F16``, ``HEAD16``, ``UNIT_BF16`` and ``UNIT_LEAKY``; with it off
+# ``unit_conv_supported`` and ``dwconv_supported`` decline a float16 operand and the network does what it did without the switch.
+# Never timed by ``pick``, no choice-table entry.  It ships OFF; the one timing is tools/gpu/unit_f16_times.py,
+# profiles/unit_f16/times.log, and switching the default is a change of its own that rests on it.
+UNIT_F16 = _switch('OPA_UNIT_F16', '0')
 # element type -> (is the route on, given the route's own bfloat16 switch?; the suffix of its entry points) for the routes on the
 # shared 16-bit MFMA tile
 _ROUTES16 = {torch.bfloat16: (lambda own: own, '_bf16'), torch.float16: (lambda own: F16, '_f16')}
@@ -392,8 +402,8 @@ def _stem_weight_of(conv):
 def _unit_operands_of(mode, conv):
     """The operands of ``conv1x1_unit`` (float32: of ``head_conv_x3`` too) derived from the current parameters: the ``[N, K]`` weight in
     ``mode``'s dtype padded with zeros to ``[N_pad, K_pad]`` (multiples of 64: the kernel's tile width and two of its K-steps) as
-    ``mode.weight`` lays it out -- float32 ``split_weight``'s ``[3, N_pad, K_pad]``, bfloat16 as it is -- and the bias as FLOAT32 ``[N_pad]``
-    (a bfloat16 bias upcast exactly; zeros where the convolution has none and in the padding) -- kept on the module as ``mode.cache``
+    ``mode.weight`` lays it out -- float32 ``split_weight``'s ``[3, N_pad, K_pad]``, bfloat16 and float16 as it is -- and the bias as FLOAT32
+    ``[N_pad]`` (a 16-bit bias upcast exactly; zeros where the convolution has none and in the padding) -- kept on the module as ``mode.cache``
     like ``_split_weight_of``; the convolution keeps its parameters, and the key holds the bias tensor too (a bias REPLACED by a new
     Parameter is a new operand)."""
     def make():
@@ -1105,7 +1115,11 @@ UNIT_MODE_X3 = UnitMode(torch.float32, 8, lambda: X3_UNIT and X3_TERMS in (6, 9)
 UNIT_MODE_BF16 = UnitMode(torch.bfloat16, 4, lambda: UNIT_BF16, True, lambda wp: wp, '_opa_w_unit_bf16',
                           lambda operands, code, act_param, terms: _launch('opa_gemm_unit_actp_bf16', *operands, code, float(act_param)),
                           'conv1x1_unit_bf16', False, lambda: True)
-_UNIT_MODES = {mode.dtype: mode for mode in (UNIT_MODE_X3, UNIT_MODE_BF16)}
+# float16: the same kernel on the f16 MFMA behind its own switch and symbol, its operands under its own attribute
+UNIT_MODE_F16 = UnitMode(torch.float16, 4, lambda: UNIT_F16, True, lambda wp: wp, '_opa_w_unit_f16',
+                         lambda operands, code, act_param, terms: _launch('opa_gemm_unit_actp_f16', *operands, code, float(act_param)),
+                         'conv1x1_unit_f16', False, lambda: True)
+_UNIT_MODES = {mode.dtype: mode for mode in (UNIT_MODE_X3, UNIT_MODE_BF16, UNIT_MODE_F16)}
 
 
 def unit_mode_of(t):
@@ -1130,10 +1144,10 @@ def _unit_operand_ok(mode, t, channels):
 
 def unit_conv_supported(conv, x, partner=None, residual=None, mode=None, head=False):
     """Can ``conv1x1_unit(conv, x, partner=partner, residual=residual)`` run?  The mode of ``x``'s dtype (``mode`` where given) switched
-    on, weight and activation of that dtype on the same GPU -- bfloat16: outside autocast, whose parameters stay float32 -- a 1x1
+    on, weight and activation of that dtype on the same GPU -- bfloat16 and float16: outside autocast, whose parameters stay float32 -- a 1x1
     convolution of stride 1 without padding or groups and with EVEN channel counts, ``x`` (and ``partner`` or ``residual``, never both:
     the output's pixels, ``conv.out_channels`` channels) channels-innermost tensors or channel slices of such, on 8-byte boundaries
-    (bfloat16: 4), nothing that autograd follows.  ``head``: ``conv`` is a head's, which float32 takes behind ``X3_HEAD`` only."""
+    (bfloat16 and float16: 4), nothing that autograd follows.  ``head``: ``conv`` is a head's, which float32 takes behind ``X3_HEAD`` only."""
     mode = mode or unit_mode_of(x)
     if not (mode is not None and x.is_cuda and conv.weight.device == x.device and (not head or mode.head())
             and not (mode.declines_autocast and torch.is_autocast_enabled()) and _unit_conv_ok(mode, conv)
@@ -1152,7 +1166,7 @@ def _conv1x1_unit(mode, conv, x, relu=True, partner=None, residual=None, act=Non
     """``act(conv(x))`` for a biased 1x1 convolution of ANY even channel counts on a channels-last tensor or channel slice
     (reference ``network/basenetworks.py:186-242``: the 1x1 convolutions of a ShuffleNetV2K unit, folded with their batch norms),
     through the unit mode ``mode``: float32 the split-operand GEMM's (``opa_gemm_unit_act_f32x3``),
-    bfloat16 one bf16 MFMA per product, float32 accumulation and one rounding (``opa_gemm_unit_actp_bf16``).  With ``partner``
+    bfloat16 / float16 one 16-bit MFMA per product, float32 accumulation and one rounding (``opa_gemm_unit_actp_bf16`` / ``..._f16``).  With ``partner``
     (``[B, N, H, W]``, may be a slice) the result is ``channel_shuffle(cat((partner, y), 1), 2)`` -- ``[B, 2N, H, W]``, the partner's
     channels copied into the even positions by the same kernel.  channels_last ``x.dtype`` out.  ``unit_conv_supported``: can it run?
 
@@ -1174,13 +1188,13 @@ def _conv1x1_unit(mode, conv, x, relu=True, partner=None, residual=None, act=Non
 
 def conv1x1_unit(conv, x, **kwargs):
     """``_conv1x1_unit`` in the mode of ``x``'s dtype, called by the mode's public name as it reads NOW: a recorder that a test or a
-    tool puts on ``conv1x1_unit_x3`` / ``conv1x1_unit_bf16`` sees every launch of the routes."""
+    tool puts on ``conv1x1_unit_x3`` / ``conv1x1_unit_bf16`` / ``conv1x1_unit_f16`` sees every launch of the routes."""
     return globals()[unit_mode_of(x).gemm](conv, x, **kwargs)
 
 
 def pick_unit(x, m, k, n, has_partner, run_unit, run_other):
     """``run_unit``, a route through the unit mode of ``x``'s dtype that the caller found supported, or ``run_other``, what the trunk did
-    before.  float32: ``pick``'s decision, key ``'unit'``, never timed.  bfloat16: no table entry -- the supported route runs."""
+    before.  float32: ``pick``'s decision, key ``'unit'``, never timed.  bfloat16 and float16: no table entry -- the supported route runs."""
     if unit_mode_of(x).table:
         return pick('unit', m, k, n, has_partner, False, run_unit, run_other, timing=False)
     return run_unit()
@@ -1196,6 +1210,14 @@ conv1x1_unit_x3 = functools.partial(_conv1x1_unit, UNIT_MODE_X3)
 
 def conv1x1_unit_bf16(conv, x, relu=True, partner=None, residual=None, act=None, act_param=0.0):          # (its signature: no ``terms``)
     return _conv1x1_unit(UNIT_MODE_BF16, conv, x, relu, partner, residual, act, None, act_param)
+
+
+_unit_weight_f16_of = functools.partial(_unit_operands_of, UNIT_MODE_F16)
+unit_conv_f16_supported = functools.partial(unit_conv_supported, mode=UNIT_MODE_F16)
+
+
+def conv1x1_unit_f16(conv, x, relu=True, partner=None, residual=None, act=None, act_param=0.0):           # (float16: ``opa_gemm_unit_actp_f16``)
+    return _conv1x1_unit(UNIT_MODE_F16, conv, x, relu, partner, residual, act, None, act_param)
 
 
 # ---- the Fire expand ------------------------------------------------------------------------------------------------------------------
@@ -1355,7 +1377,8 @@ def dwconv_out_hw(h, w, kernel_size, stride, dilation=1):
 
 def dwconv_supported(x, kernel_size, stride, dilation=1):
     """Can ``dwconv_bias_act(x, ..., kernel_size, stride, dilation=dilation)`` run?  A float32 or bfloat16 channels-innermost tensor
-    or channel slice on the GPU; a 3 x 3, 5 x 5 or 7 x 7 window; stride 1 or 2; dilation 1, or 2 or 4 at stride 1."""
+    or channel slice on the GPU -- or a float16 one where ``UNIT_F16`` is on, outside autocast and not followed by autograd; a 3 x 3,
+    5 x 5 or 7 x 7 window; stride 1 or 2; dilation 1, or 2 or 4 at stride 1."""
     if not (x.is_cuda and x.dim() == 4):
         return False
     if not (kernel_size in (3, 5, 7) and stride in (1, 2) and (dilation == 1 or (dilation in (2, 4) and stride == 1))):
@@ -1363,8 +1386,12 @@ def dwconv_supported(x, kernel_size, stride, dilation=1):
     if DW_DECLINED and (kernel_size, dilation) in DW_DECLINED:
         return False
     rows_out = dwconv_out_hw(x.shape[2], x.shape[3], kernel_size, stride, dilation)[0]
-    return (x.dtype in (torch.float32, torch.bfloat16)
-            and x.shape[0] * rows_out <= 65535                              # grid.y of the stencil kernel (dwconv.hip)
+    if x.dtype == torch.float16:
+        if not (UNIT_F16 and not torch.is_autocast_enabled() and not x.requires_grad):
+            return False
+    elif x.dtype not in (torch.float32, torch.bfloat16):
+        return False
+    return (x.shape[0] * rows_out <= 65535                              # grid.y of the stencil kernel (dwconv.hip)
             and _pixel_stride(x) is not None and _lib.available())
 
 
@@ -1374,10 +1401,14 @@ def dwconv_bias_act(x, w_taps, bias, kernel_size, stride, relu=False, act=None, 
     ``depthwise_taps``) in ``x``'s dtype.  ``act`` (``ACT_NONE`` / ``ACT_RELU`` / ``ACT_HARDSWISH``) instead of ``relu``.
     A 3 x 3 or 5 x 5 window without dilation goes to ``opa_dwconv_act``, a 7 x 7 window or a dilation of 2 or 4 (stride 1) to
     ``opa_dwconv_dilated_act``: the same kernel template; ``act`` ``ACT_RELU6`` with ``act_param`` (the cap) -- the depthwise
-    convolution of a MobileNetV2 block -- to ``opa_dwconv_actp``, whatever the window."""
+    convolution of a MobileNetV2 block -- to ``opa_dwconv_actp``, whatever the window.  A float16 ``x`` (``w_taps`` and ``bias`` float16
+    too) goes to ``opa_dwconv_actp_f16``, whatever the window and the code."""
     B, C, H, W = x.shape
     out = _empty_nhwc(x, C, dwconv_out_hw(H, W, kernel_size, stride, dilation))
-    if _act_code(relu, act) == ACT_RELU6:
+    if x.dtype == torch.float16:
+        _launch('opa_dwconv_actp_f16', _ptr(x), _pixel_stride(x), _ptr(w_taps), _ptr(bias), _ptr(out), C, B, H, W, C, kernel_size,
+                stride, dilation, _act_code(relu, act), float(act_param))
+    elif _act_code(relu, act) == ACT_RELU6:
         _launch('opa_dwconv_actp', _ptr(x), _pixel_stride(x), _ptr(w_taps), _ptr(bias), _ptr(out), C, B, H, W, C, kernel_size,
                 stride, dilation, _DTYPES[x.dtype], ACT_RELU6, float(act_param))
     elif kernel_size in (3, 5) and dilation == 1:

@@ -525,7 +525,8 @@ class _InvertedResidualK(nn.Module):
     def _unit_route_supported(self, x):
         """Can the WHOLE unit run on the project's kernels alone (``_forward_unit``)?  Every 1x1 convolution through the unit mode of
         ``x``'s dtype (``fused.unit_mode_of``: the split-operand GEMM's for float32, the bf16 GEMM's behind ``fused.UNIT_BF16`` and
-        outside autocast for bfloat16), every depthwise convolution through the stencil kernel.  The GEMM's epilogue applies the ReLU, or
+        outside autocast for bfloat16, the same GEMM on the f16 MFMA behind ``fused.UNIT_F16`` for float16), every depthwise convolution
+        through the stencil kernel.  The GEMM's epilogue applies the ReLU, or
         the LeakyReLU of a ``leaky_relu`` unit where ``fused.UNIT_LEAKY`` is on and outside autocast: otherwise such a unit takes
         ``_forward_fused``."""
         if fused.unit_mode_of(x) is None or x.dim() != 4:
@@ -748,7 +749,7 @@ def _conv5_forward(net, x):
     folding leaves: a ``GroupNorm`` there runs -- with ``fused.GN`` on behind the GEMM without an activation (``_norm_act``), else
     with torch's ``conv5``.  A bfloat16 ``conv5`` (ReLU or, with ``fused.UNIT_LEAKY``, LeakyReLU behind an ``Identity``) takes the same
     branch where ``fused.UNIT_BF16`` is on -- ``fused.unit_conv_supported`` goes by ``x``'s dtype -- and runs: no table entry, no timing
-    (``fused.pick_unit``); a group norm is float32's alone."""
+    (``fused.pick_unit``), and so does a float16 one where ``fused.UNIT_F16`` is on; a group norm is float32's alone."""
     conv = net.conv5[0]
     if net.fused and x.is_cuda and isinstance(conv, nn.Conv2d) and fused.unit_conv_supported(conv, x):
         norm, nonlin, act = net.conv5[1], net.conv5[2], None
@@ -1153,7 +1154,7 @@ class CompositeField4(nn.Module):
         elif not self.training and self.conv.in_channels % 64 != 0 and fused.unit_conv_supported(self.conv, x, head=True):
             # input channels that are no multiple of 64 (k16: 1392): the unit mode of x's dtype.  float32: the same kernel, N tail native
             # (no padded pitch, no copy-out), decided like the units -- the table, else by size, never timed; bfloat16 (behind
-            # fused.UNIT_BF16): where it is supported it runs
+            # fused.UNIT_BF16) and float16 (behind fused.UNIT_F16): where it is supported it runs
             conv, x0 = self.conv, x
             x = fused.pick_unit(x0, fused.out_pixels(x0), conv.in_channels, conv.out_channels, False,
                                 lambda: fused.conv1x1_unit(conv, x0, relu=False), lambda: conv(x0))
