@@ -630,6 +630,14 @@ int opa_gconv3x3_act_bf16(const void* x_dev, const void* w_dev, const float* bia
                           int32_t batch, int32_t h_in, int32_t w_in, int32_t channels, int32_t group_width,
                           int32_t stride, int32_t dilation, int32_t relu, void* stream);
 
+/* opa_gconv3x3_act_bf16 for a ResNeXt cast to FLOAT16, on v_mfma_f32_32x32x16_f16: the same kernel with the element type as its
+ * template parameter -- x, w and out float16 where the twin has bf16, bias_dev FLOAT32 as there -- and the same contract (the one on
+ * non-finite values included), checks and messages under this name.  The store is float16's round to nearest even: beyond 65504
+ * +-inf, NaN stays NaN, subnormal results kept. */
+int opa_gconv3x3_act_f16(const void* x_dev, const void* w_dev, const float* bias_dev, void* out_dev,
+                         int32_t batch, int32_t h_in, int32_t w_in, int32_t channels, int32_t group_width,
+                         int32_t stride, int32_t dilation, int32_t relu, void* stream);
+
 /* The 7x7 RGB stem of a ResNet cast to bfloat16 (csrc/stem7x7_bf16.hip; reference network/basenetworks.py:71-150 runs it through
  * torch.nn.Conv2d) as an implicit GEMM on the bf16 MFMA, float32 accumulation, ONE rounding at the store:
  *     out[b, oy, ox, co] = bf16_rne(act(sum_{ky,kx,ci} x[b, ci, s*oy - 3 + ky, s*ox - 3 + kx] * w[co][ky * 24 + kx * 3 + ci] + bias[co]))
@@ -647,6 +655,13 @@ int opa_gconv3x3_act_bf16(const void* x_dev, const void* w_dev, const float* bia
 int opa_stem7x7_act_bf16(const void* x_dev, int64_t x_batch_stride, int64_t x_channel_stride, int64_t x_row_stride,
                          int64_t x_pixel_stride, const void* w_dev, const float* bias_dev, void* out_dev,
                          int32_t batch, int32_t h, int32_t w, int32_t c_out, int32_t stride, int32_t relu, void* stream);
+
+/* opa_stem7x7_act_bf16 for a ResNet cast to FLOAT16, on v_mfma_f32_32x32x16_f16: the same kernel with the element type as its template
+ * parameter -- x, w and out float16 where the twin has bf16, bias_dev FLOAT32 as there -- and the same contract, checks and messages
+ * under this name.  The store is float16's round to nearest even: beyond 65504 +-inf, NaN stays NaN, subnormal results kept. */
+int opa_stem7x7_act_f16(const void* x_dev, int64_t x_batch_stride, int64_t x_channel_stride, int64_t x_row_stride,
+                        int64_t x_pixel_stride, const void* w_dev, const float* bias_dev, void* out_dev,
+                        int32_t batch, int32_t h, int32_t w, int32_t c_out, int32_t stride, int32_t relu, void* stream);
 
 /* The tail of the first block of a stage of a ResNet cast to bfloat16 (csrc/gemm2_bf16.hip; reference network/basenetworks.py:71-150
  * runs both convolutions through torch.nn.Conv2d): the block's last 1x1 convolution and its downsampling 1x1 convolution as ONE

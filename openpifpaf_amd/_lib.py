@@ -167,6 +167,8 @@ SYMBOLS = {
     'opa_conv3x3_act_f16': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp] + [_i32] * 8 + [_vp]),
     'opa_gconv3x3_act_bf16': (ctypes.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 8 + [_vp]),
     'opa_stem7x7_act_bf16': (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp] + [_i32] * 6 + [_vp]),
+    'opa_gconv3x3_act_f16': (ctypes.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 8 + [_vp]),
+    'opa_stem7x7_act_f16': (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp] + [_i32] * 6 + [_vp]),
     'opa_conv_rows_f32x3': (ctypes.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 12 + [_vp]),
     'opa_conv3x3_f32x3': (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     'opa_conv3x3_dilated_f32x3': (ctypes.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 9 + [_vp]),

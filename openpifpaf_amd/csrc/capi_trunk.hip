@@ -18,7 +18,7 @@
 //                      only behind it); an empty batch alone (h and w must be positive) for opa_stem3x3_actp, after every check
 //                      but those of the sizes' products, and for opa_groupnorm_actp (pixels, channels and groups must be positive),
 //                      after every check of its arguments but the limits and the workspace; an empty batch, h or w for
-//                      opa_conv3x3_act_bf16, opa_gconv3x3_act_bf16, opa_stem7x7_act_bf16 and opa_gemm2_bias_act_bf16, after every check
+//                      opa_conv3x3_act_bf16, opa_gconv3x3_act_bf16, opa_stem7x7_act_bf16 and opa_gemm2_bias_act_bf16 (and their _f16 twins), after every check
 //                      but the grid's; an empty batch alone (the other sizes must be positive) for opa_head_conv_fields_bf16 / _f16,
 //                      after every check but the grid's.
 //                      opa_conv3x3_f32x3, opa_gemm2_bias_act_f32x3, opa_conv_rows_*, Winograd, dwconv, squeeze-excite, interleave and the head epilogue refuse empties.
@@ -385,11 +385,12 @@ int opa_conv3x3_act_f16(const void* x_dev, const void* w_dev, const float* bias_
 
 // the grouped 3x3 convolution of a bfloat16 ResNeXt as an implicit GEMM per 64-channel chunk on the bf16 MFMA (csrc/gconv3x3_bf16.hip):
 // one message per check, in this order: null pointers, alignment, negative sizes, channels, group_width, the stride, the dilation, x's
-// size, out's size; then the empty call; then the grid
-int opa_gconv3x3_act_bf16(const void* x_dev, const void* w_dev, const float* bias_dev, void* out_dev,
-                          int32_t batch, int32_t h_in, int32_t w_in, int32_t channels, int32_t group_width,
-                          int32_t stride, int32_t dilation, int32_t relu, void* stream) {
-    const Entry E("opa_gconv3x3_act_bf16", stream);
+// size, out's size; then the empty call; then the grid.  opa_gconv3x3_act_bf16 and its float16 twin (`dtype` 1: x, w and out float16,
+// the kernel on the f16 MFMA)
+static int gconv3x3_16(const char* fn, int dtype, const void* x_dev, const void* w_dev, const float* bias_dev, void* out_dev,
+                       int32_t batch, int32_t h_in, int32_t w_in, int32_t channels, int32_t group_width,
+                       int32_t stride, int32_t dilation, int32_t relu, void* stream) {
+    const Entry E(fn, stream);
     if (!x_dev || !w_dev || !out_dev) return E.refuse("x_dev, w_dev and out_dev must not be NULL");
     if (misaligned(15, {x_dev, w_dev, bias_dev, out_dev})) return E.refuse("pointers must be 16-B aligned");
     if (batch < 0 || h_in < 0 || w_in < 0) return E.refuse("negative batch, h_in or w_in");
@@ -408,15 +409,31 @@ int opa_gconv3x3_act_bf16(const void* x_dev, const void* w_dev, const float* bia
     // (grid.x; with out below 2^31 elements and 64 channels per tile it holds today: it guards the launch should a limit above move)
     if (gconv3x3_bf16_workgroups(batch, h_in, w_in, channels, stride) > 0x7fffffffll) return E.refuse("too many tiles for grid.x");
     return E.launched(launch_gconv3x3_bf16(x_dev, w_dev, bias_dev, out_dev, batch, h_in, w_in, channels, group_width, stride, dilation,
-                                           relu, E.st), "gconv3x3_act_bf16", "gconv3x3_bf16_kernel");
+                                           relu, E.st, dtype), dtype == 1 ? "gconv3x3_act_f16" : "gconv3x3_act_bf16",
+                      dtype == 1 ? "gconv3x3_f16_kernel" : "gconv3x3_bf16_kernel");
+}
+
+int opa_gconv3x3_act_bf16(const void* x_dev, const void* w_dev, const float* bias_dev, void* out_dev,
+                          int32_t batch, int32_t h_in, int32_t w_in, int32_t channels, int32_t group_width,
+                          int32_t stride, int32_t dilation, int32_t relu, void* stream) {
+    return gconv3x3_16("opa_gconv3x3_act_bf16", 2, x_dev, w_dev, bias_dev, out_dev, batch, h_in, w_in, channels, group_width, stride,
+                       dilation, relu, stream);
+}
+
+int opa_gconv3x3_act_f16(const void* x_dev, const void* w_dev, const float* bias_dev, void* out_dev,
+                         int32_t batch, int32_t h_in, int32_t w_in, int32_t channels, int32_t group_width,
+                         int32_t stride, int32_t dilation, int32_t relu, void* stream) {
+    return gconv3x3_16("opa_gconv3x3_act_f16", 1, x_dev, w_dev, bias_dev, out_dev, batch, h_in, w_in, channels, group_width, stride,
+                       dilation, relu, stream);
 }
 
 // the 7x7 RGB stem of a bfloat16 ResNet as an implicit GEMM on the bf16 MFMA (csrc/stem7x7_bf16.hip): one message per check, in this
-// order: null pointers, alignment, negative sizes, c_out, the stride, x's strides, x's extent, out's size; then the empty call; then the grid
-int opa_stem7x7_act_bf16(const void* x_dev, int64_t x_batch_stride, int64_t x_channel_stride, int64_t x_row_stride, int64_t x_pixel_stride,
-                         const void* w_dev, const float* bias_dev, void* out_dev, int32_t batch, int32_t h, int32_t w, int32_t c_out,
-                         int32_t stride, int32_t relu, void* stream) {
-    const Entry E("opa_stem7x7_act_bf16", stream);
+// order: null pointers, alignment, negative sizes, c_out, the stride, x's strides, x's extent, out's size; then the empty call; then the
+// grid.  opa_stem7x7_act_bf16 and its float16 twin (`dtype` 1: x, w and out float16, the kernel on the f16 MFMA)
+static int stem7x7_16(const char* fn, int dtype, const void* x_dev, int64_t x_batch_stride, int64_t x_channel_stride, int64_t x_row_stride,
+                      int64_t x_pixel_stride, const void* w_dev, const float* bias_dev, void* out_dev, int32_t batch, int32_t h, int32_t w,
+                      int32_t c_out, int32_t stride, int32_t relu, void* stream) {
+    const Entry E(fn, stream);
     if (!x_dev || !w_dev || !out_dev) return E.refuse("x_dev, w_dev and out_dev must not be NULL");
     if (misaligned(1, {x_dev}) || misaligned(15, {w_dev, bias_dev, out_dev}))
         return E.refuse("x_dev must be 2-B, w_dev / bias_dev / out_dev 16-B aligned");
@@ -436,7 +453,22 @@ int opa_stem7x7_act_bf16(const void* x_dev, int64_t x_batch_stride, int64_t x_ch
     // (grid.x; with out below 2^31 elements of at least 64 channels it holds today: it guards the launch should a limit above move)
     if (stem7x7_bf16_workgroups(batch, h, w, c_out, stride) > 0x7fffffffll) return E.refuse("too many tiles for grid.x");
     return E.launched(launch_stem7x7_bf16(x_dev, x_batch_stride, x_channel_stride, x_row_stride, x_pixel_stride, w_dev, bias_dev, out_dev,
-                                          batch, h, w, c_out, stride, relu, E.st), "stem7x7_act_bf16", "stem7x7_bf16_kernel");
+                                          batch, h, w, c_out, stride, relu, E.st, dtype), dtype == 1 ? "stem7x7_act_f16" : "stem7x7_act_bf16",
+                      dtype == 1 ? "stem7x7_f16_kernel" : "stem7x7_bf16_kernel");
+}
+
+int opa_stem7x7_act_bf16(const void* x_dev, int64_t x_batch_stride, int64_t x_channel_stride, int64_t x_row_stride, int64_t x_pixel_stride,
+                         const void* w_dev, const float* bias_dev, void* out_dev, int32_t batch, int32_t h, int32_t w, int32_t c_out,
+                         int32_t stride, int32_t relu, void* stream) {
+    return stem7x7_16("opa_stem7x7_act_bf16", 2, x_dev, x_batch_stride, x_channel_stride, x_row_stride, x_pixel_stride, w_dev, bias_dev, out_dev,
+                      batch, h, w, c_out, stride, relu, stream);
+}
+
+int opa_stem7x7_act_f16(const void* x_dev, int64_t x_batch_stride, int64_t x_channel_stride, int64_t x_row_stride, int64_t x_pixel_stride,
+                        const void* w_dev, const float* bias_dev, void* out_dev, int32_t batch, int32_t h, int32_t w, int32_t c_out,
+                        int32_t stride, int32_t relu, void* stream) {
+    return stem7x7_16("opa_stem7x7_act_f16", 1, x_dev, x_batch_stride, x_channel_stride, x_row_stride, x_pixel_stride, w_dev, bias_dev, out_dev,
+                      batch, h, w, c_out, stride, relu, stream);
 }
 
 // a bfloat16 block's last 1x1 convolution and its downsampling 1x1 convolution as one product on the bf16 MFMA (csrc/gemm2_bf16.hip):

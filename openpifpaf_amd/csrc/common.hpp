@@ -328,18 +328,19 @@ hipError_t launch_conv3x3_bf16(const void* x, const void* w, const float* bias, 
 // tensor as an implicit GEMM per 64-channel chunk on the bf16 MFMA: x [B, H, W, C], w [C][9][64] block diagonal (column j of row co:
 // input channel 64 * (co / 64) + j; zero outside co's group), bias float32 [C] or null, out dense bf16 [B, Ho, Wo, C]; C % 64 == 0, CG
 // 4, 8, 16, 32 or 64 and below C, S 1 or 2, D = padding 1, or 2 or 4 with S = 1; x and out below 2^31 elements (anything else:
-// hipErrorInvalidValue).  gconv3x3_bf16_workgroups = grid.x of the launch.
+// hipErrorInvalidValue).  dtype 2; with dtype 1 the same for float16 tensors on the f16 MFMA.  gconv3x3_bf16_workgroups = grid.x of the
+// launch.
 long long gconv3x3_bf16_workgroups(int B, int H, int W, int C, int S);
 hipError_t launch_gconv3x3_bf16(const void* x, const void* w, const float* bias, void* out, int B, int H, int W, int C, int CG, int S,
-                                int D, int relu, hipStream_t st);
+                                int D, int relu, hipStream_t st, int dtype);
 // csrc/stem7x7_bf16.hip: the 7x7 RGB stem (padding 3) of a bf16 image read through its four element strides (batch xb, channel xc, row
 // xr, pixel xp: any layout) as an implicit GEMM on the bf16 MFMA: x [B, 3, H, W], w [c_out][192] (k = ky * 24 + kx * 3 + ci, zeros in
 // the padding columns), bias float32 [c_out] or null, out dense channels-last bf16 [B, Ho, Wo, c_out]; c_out % 64 == 0, S 1 or 2, the
 // strides positive; x's extent and out below 2^31 elements (anything else: hipErrorInvalidValue).
-// stem7x7_bf16_workgroups = grid.x of the launch.
+// dtype 2; with dtype 1 the same for a float16 image, weight and output on the f16 MFMA.  stem7x7_bf16_workgroups = grid.x of the launch.
 long long stem7x7_bf16_workgroups(int B, int H, int W, int c_out, int S);
 hipError_t launch_stem7x7_bf16(const void* x, long long xb, long long xc, long long xr, long long xp, const void* w, const float* bias,
-                               void* out, int B, int H, int W, int c_out, int S, int relu, hipStream_t st);
+                               void* out, int B, int H, int W, int c_out, int S, int relu, hipStream_t st, int dtype);
 // csrc/gemm2_bf16.hip: a block's last 1x1 convolution and its downsampling 1x1 convolution as one product on the bf16 MFMA: a1 [M, k1]
 // dense bf16 (null with k1 == 0: the strided 1x1 convolution alone), x [B, H, W, k2] dense channels-last bf16 read at stride S, a_bias
 // bf16 [k1] or null (a1's owed bias + ReLU, applied while it is staged; not with k1 == 0), wcat [n][k1 + k2], bias float32 [n] or null,

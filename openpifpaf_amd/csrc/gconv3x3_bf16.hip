@@ -23,6 +23,11 @@
 // outside the image is not loaded: exact zeros whatever memory holds).  The ReLU is a select: NaN stays NaN.
 //
 // No im2col buffer, no workspace, no atomics (equal inputs give equal bits), no scratch.
+//
+// The same kernel serves a ResNeXt cast to float16 on v_mfma_f32_32x32x16_f16: DT, the C ABI's dtype code (2 bfloat16, 1 float16), is the
+// element type of x, w and out (csrc/bf16_tile.hpp's TileElem<DT>: the fragment type, the MFMA, the rounding at the store); the bias
+// stays float32, everything else moves raw 16-bit words.  The NON-FINITE contract above holds for BOTH types: the f16 MFMA multiplies
+// the off-group zeros as the bf16 one does, and float16's store keeps NaN and sends what lies beyond 65504 to +-inf.
 #include "bf16_tile.hpp"
 #include "gconv3x3_bf16_plan.hpp"
 
@@ -31,12 +36,13 @@ namespace opa {
 namespace {
 
 // M = batch * ho * wo output pixels, N = C, K = 576 per N-tile
-template <bool HALF, bool RELU>
+template <int DT, bool HALF, bool RELU>
 __global__ __launch_bounds__(256, 3) void gconv3x3_bf16_kernel(
         const unsigned short* __restrict__ x, const unsigned short* __restrict__ W, const float* __restrict__ bias,
         unsigned short* __restrict__ out, Conv3Bf16Geometry g, int M) {
     constexpr int BN = kGconv3Bf16BN, K = kGconv3Bf16K;
     using T = Bf16Tile<BN>;
+    typedef typename TileElem<DT>::frag_t frag_t;
     static_assert(T::NT == 1 && T::WN == 32, "a wave owns one 32-column block");
     __shared__ __attribute__((aligned(16))) unsigned char smem[T::LDS_BYTES];
     const int tid = threadIdx.x, lane = bf16_tile_wave().lane, wm = bf16_tile_wave().wm, wn = bf16_tile_wave().wn;
@@ -80,13 +86,13 @@ __global__ __launch_bounds__(256, 3) void gconv3x3_bf16_kernel(
 #pragma unroll
         for (int q = 0; q < (HALF ? 2 : 4); q++) {
             const int kof = kk0 + q * 16 + (lane >> 5) * 8;
-            bf16x8_t fa[2];
+            frag_t fa[2];
 #pragma unroll
             for (int i = 0; i < 2; i++)
-                fa[i] = *reinterpret_cast<const bf16x8_t*>(sA + (wm * 64 + i * 32 + (lane & 31)) * kBf16Pitch + kof);
-            const bf16x8_t fb = *reinterpret_cast<const bf16x8_t*>(sB + (wn * T::WN + (lane & 31)) * kBf16Pitch + kof);
+                fa[i] = *reinterpret_cast<const frag_t*>(sA + (wm * 64 + i * 32 + (lane & 31)) * kBf16Pitch + kof);
+            const frag_t fb = *reinterpret_cast<const frag_t*>(sB + (wn * T::WN + (lane & 31)) * kBf16Pitch + kof);
 #pragma unroll
-            for (int i = 0; i < 2; i++) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb, acc[i], 0, 0, 0);
+            for (int i = 0; i < 2; i++) acc[i] = TileElem<DT>::mfma(fa[i], fb, acc[i]);
         }
     }
     __syncthreads();                           // staging LDS is free: reuse it for the epilogue
@@ -101,8 +107,8 @@ __global__ __launch_bounds__(256, 3) void gconv3x3_bf16_kernel(
 #pragma unroll
         for (int r = 0; r < 16; r++) patch[bf16_tile_acc_row(r) * T::WN + col] = acc[i][r] + b;
         bf16_tile_patch_sync();
-        bf16_tile_store_rows<BN, false, RELU>(patch, none, out, M, N, m0, n0, i,
-                                              [](float v) { return v < 0.0f ? 0.0f : v; });   // (a select: NaN stays NaN)
+        bf16_tile_store_rows<BN, false, RELU, DT>(patch, none, out, M, N, m0, n0, i,
+                                                  [](float v) { return v < 0.0f ? 0.0f : v; });   // (a select: NaN stays NaN)
         bf16_tile_patch_sync();
     }
 }
@@ -115,7 +121,7 @@ long long gconv3x3_bf16_workgroups(int B, int H, int W, int C, int S) {
 }
 
 hipError_t launch_gconv3x3_bf16(const void* x, const void* w, const float* bias, void* out, int B, int H, int W, int C, int CG, int S,
-                                int D, int relu, hipStream_t st) {
+                                int D, int relu, hipStream_t st, int dtype) {
     if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 64 != 0 || (CG != 4 && CG != 8 && CG != 16 && CG != 32 && CG != 64) || C == CG ||
         (S != 1 && S != 2) || (D != 1 && D != 2 && D != 4) || (D > 1 && S != 1))
         return hipErrorInvalidValue;
@@ -123,12 +129,13 @@ hipError_t launch_gconv3x3_bf16(const void* x, const void* w, const float* bias,
     const long long blocks = gconv3x3_bf16_workgroups(B, H, W, C, S);
     if ((long long)B * H * W * C > 0x7fffffffll || M * C > 0x7fffffffll || blocks > 0x7fffffffll) return hipErrorInvalidValue;
     const Conv3Bf16Geometry g = {B, H, W, C, S, D};
+    return with_value<1, 2>(dtype, [&](auto DT) {
     return with_flag(CG <= 32, [&](auto HALF) {
     return with_flag(relu != 0, [&](auto RELU) {
-        gconv3x3_bf16_kernel<HALF, RELU><<<(unsigned)blocks, kBf16Threads, 0, st>>>(
+        gconv3x3_bf16_kernel<DT, HALF, RELU><<<(unsigned)blocks, kBf16Threads, 0, st>>>(
             (const unsigned short*)x, (const unsigned short*)w, bias, (unsigned short*)out, g, (int)M);
         return hipGetLastError();
-    }); });
+    }); }); });
 }
 
 }  // namespace opa

@@ -11,6 +11,10 @@
 // the image, a zero column of K, a row >= M), is decided in csrc/stem7x7_bf16_plan.hpp, which a CPU program enumerates
 // (tests/test_stem7x7_bf16_plan.py); each staged row's centre pixel and its two 7-bit masks are computed once per workgroup.  No
 // im2col buffer, no atomics (equal inputs give equal bits), no scratch.
+//
+// The same kernel serves a ResNet cast to float16 on v_mfma_f32_32x32x16_f16: DT, the C ABI's dtype code (2 bfloat16, 1 float16), is the
+// element type of x, w and out (csrc/bf16_tile.hpp's TileElem<DT>); the bias stays float32, and the gather ORs raw 16-bit words into the
+// chunks whatever they encode.
 #include "bf16_tile.hpp"
 #include "stem7x7_bf16_plan.hpp"
 
@@ -19,7 +23,7 @@ namespace opa {
 namespace {
 
 // M = batch * ho * wo output pixels, N = c_out, K = 192
-template <int BN, bool RELU>
+template <int DT, int BN, bool RELU>
 __global__ __launch_bounds__(256, 3) void stem7x7_bf16_kernel(
         const unsigned short* __restrict__ x, const unsigned short* __restrict__ W, const float* __restrict__ bias,
         unsigned short* __restrict__ out, Stem7Bf16Geometry g, int M, int N) {
@@ -32,7 +36,7 @@ __global__ __launch_bounds__(256, 3) void stem7x7_bf16_kernel(
     Stem7Bf16Row rows[kBf16Passes];            // this thread's four output pixels: centre and masks, once per workgroup
     stem7x7_bf16_plan_rows(g, m0, tid, rows);
     f32x16_t acc[2][T::NT];
-    bf16_tile_mainloop<BN>(smem, W, kStem7Bf16K, n0, acc, [&](int k0, u32x4_t (&ra)[kBf16Passes]) {   // what is not loaded keeps its zeros
+    bf16_tile_mainloop<BN, DT>(smem, W, kStem7Bf16K, n0, acc, [&](int k0, u32x4_t (&ra)[kBf16Passes]) {   // what is not loaded keeps its zeros
 #pragma unroll
         for (int p = 0; p < kBf16Passes; p++) ra[p] = (u32x4_t){0u, 0u, 0u, 0u};
         stem7x7_bf16_plan_a(g, rows, tid, k0, [&](int p, int slot, long long at) { ra[p][slot >> 1] |= (unsigned)*(x + at) << (16 * (slot & 1)); });
@@ -51,8 +55,8 @@ __global__ __launch_bounds__(256, 3) void stem7x7_bf16_kernel(
             for (int r = 0; r < 16; r++) patch[bf16_tile_acc_row(r) * T::WN + col] = acc[i][j][r] + b;
         }
         bf16_tile_patch_sync();
-        bf16_tile_store_rows<BN, false, RELU>(patch, none, out, M, N, m0, n0, i,
-                                              [](float v) { return v < 0.0f ? 0.0f : v; });   // (a select: NaN stays NaN)
+        bf16_tile_store_rows<BN, false, RELU, DT>(patch, none, out, M, N, m0, n0, i,
+                                                  [](float v) { return v < 0.0f ? 0.0f : v; });   // (a select: NaN stays NaN)
         bf16_tile_patch_sync();
     }
 }
@@ -65,7 +69,7 @@ long long stem7x7_bf16_workgroups(int B, int H, int W, int c_out, int S) {
 }
 
 hipError_t launch_stem7x7_bf16(const void* x, long long xb, long long xc, long long xr, long long xp, const void* w, const float* bias,
-                               void* out, int B, int H, int W, int c_out, int S, int relu, hipStream_t st) {
+                               void* out, int B, int H, int W, int c_out, int S, int relu, hipStream_t st, int dtype) {
     if (B <= 0 || H <= 0 || W <= 0 || c_out <= 0 || c_out % 64 != 0 || (S != 1 && S != 2) || xb <= 0 || xc <= 0 || xr <= 0 || xp <= 0)
         return hipErrorInvalidValue;
     const long long M = (long long)B * stem7x7_bf16_out(H, S) * stem7x7_bf16_out(W, S);
@@ -74,12 +78,13 @@ hipError_t launch_stem7x7_bf16(const void* x, long long xb, long long xc, long l
     const double last = (B - 1.0) * (double)xb + 2.0 * (double)xc + (H - 1.0) * (double)xr + (W - 1.0) * (double)xp;
     if (last >= 2147483648.0 || M * c_out > 0x7fffffffll || blocks > 0x7fffffffll) return hipErrorInvalidValue;
     const Stem7Bf16Geometry g = {B, H, W, S, xb, xc, xr, xp};
+    return with_value<1, 2>(dtype, [&](auto DT) {
     return with_value<64, 128>(c_out % 128 == 0 ? 128 : 64, [&](auto BN) {
     return with_flag(relu != 0, [&](auto RELU) {
-        stem7x7_bf16_kernel<BN, RELU><<<(unsigned)blocks, kBf16Threads, 0, st>>>(
+        stem7x7_bf16_kernel<DT, BN, RELU><<<(unsigned)blocks, kBf16Threads, 0, st>>>(
             (const unsigned short*)x, (const unsigned short*)w, bias, (unsigned short*)out, g, (int)M, c_out);
         return hipGetLastError();
-    }); });
+    }); }); });
 }
 
 }  // namespace opa

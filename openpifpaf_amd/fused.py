@@ -148,9 +148,9 @@ GCONV_BF16 = _switch('OPA_GCONV_BF16', '0')
 # 1x1 alone (``conv1x1_pair_bias_act_bf16`` / ``conv1x1_strided_bf16``) -- the ``opa_*_f16`` entry points: OPA_F16=1 (or
 # fused.F16 = True).  ONE switch for the three routes, independent of the bfloat16 switches, which a float16 operand never asks
 # (``_route16``); with it off every predicate declines a float16 operand and the network runs MIOpen's convolutions + ``bias_act_``.
-# Never timed by ``pick``.  The 7x7 stem, the grouped 3x3 and the max-pool have no float16 form (the unit mode has its own switch,
-# ``UNIT_F16``, below); the heads have a 16-bit form of their own behind their own switch (``HEAD16``, below), which this one does
-# not touch.  It ships OFF; the one timing is
+# Never timed by ``pick``.  The 7x7 stem and the grouped 3x3 have float16 forms behind switches of their own (``STEM7_F16``,
+# ``GCONV_F16``, below), the max-pool has none (the unit mode has its own switch, ``UNIT_F16``, below); the heads have a 16-bit form
+# of their own behind their own switch (``HEAD16``, below), which this one does not touch.  It ships OFF; the one timing is
 # tools/gpu/f16_times.py, profiles/f16/times.log, and switching the default is a change of its own that rests on it.
 F16 = _switch('OPA_F16', '0')
 # The heads of a network cast to bfloat16 or float16 -- the 1x1 convolution AND everything ``CompositeField4`` does behind it -- as ONE
@@ -171,16 +171,30 @@ HEAD16 = _switch('OPA_HEAD16', '0')
 # Never timed by ``pick``, no choice-table entry.  It ships OFF; the one timing is tools/gpu/unit_f16_times.py,
 # profiles/unit_f16/times.log, and switching the default is a change of its own that rests on it.
 UNIT_F16 = _switch('OPA_UNIT_F16', '0')
-# element type -> (is the route on, given the route's own bfloat16 switch?; the suffix of its entry points) for the routes on the
-# shared 16-bit MFMA tile
-_ROUTES16 = {torch.bfloat16: (lambda own: own, '_bf16'), torch.float16: (lambda own: F16, '_f16')}
+# The GROUPED 3x3 convolution of a ResNeXt cast to FLOAT16 (``model.half()``: what ``GCONV_BF16`` routes for bfloat16) on the same
+# kernel instantiated for v_mfma_f32_32x32x16_f16 (csrc/gconv3x3_bf16.hip, ``gconv3x3_bias_act_bf16``: ``opa_gconv3x3_act_f16``) instead
+# of torch's grouped float16 convolution: OPA_GCONV_F16=1 (or fused.GCONV_F16 = True).  A switch of its own, independent of ``F16``
+# (with which alone a float16 network keeps calling these convolutions), ``HEAD16``, ``UNIT_F16`` and every ``*_BF16`` switch.  Never
+# timed by ``pick``, no choice-table entry.  It ships OFF; the one timing is tools/gpu/f16x_times.py, profiles/f16x/times.log, and
+# switching the default is a change of its own that rests on it.
+GCONV_F16 = _switch('OPA_GCONV_F16', '0')
+# The 7x7 RGB stem of a ResNet or ResNeXt cast to FLOAT16 (what ``STEM7_BF16`` routes for bfloat16) on the same kernel instantiated for
+# the f16 MFMA (csrc/stem7x7_bf16.hip, ``stem7x7_bias_act_bf16``: ``opa_stem7x7_act_f16``) instead of MIOpen's convolution and a separate
+# epilogue pass: OPA_STEM7_F16=1 (or fused.STEM7_F16 = True).  Independent of every other switch, as ``GCONV_F16`` is; the input max-pool
+# behind it stays torch's (``maxpool3x3_supported`` declines float16).  It ships OFF; timed by the same tool into the same log.
+STEM7_F16 = _switch('OPA_STEM7_F16', '0')
+# element type -> (is the route on, given the route's own bfloat16 switch and its own float16 switch -- None: ``F16``?; the suffix of
+# its entry points) for the routes on the shared 16-bit MFMA tile
+_ROUTES16 = {torch.bfloat16: (lambda own, own_f16: own, '_bf16'),
+             torch.float16: (lambda own, own_f16: F16 if own_f16 is None else own_f16, '_f16')}
 
 
-def _route16(dtype, own=True):
+def _route16(dtype, own=True, own_f16=None):
     """The symbol suffix of the 16-bit MFMA routes for operands of ``dtype`` -- ``'_bf16'`` where ``own``, the route's own bfloat16
-    switch, is on; ``'_f16'`` where ``F16`` is -- or None: another dtype, or the switch off."""
-    on, suffix = _ROUTES16.get(dtype, (lambda own: False, None))
-    return suffix if on(own) else None
+    switch, is on; ``'_f16'`` where the route's float16 switch is: ``own_f16``, or ``F16`` for a route that has none of its own
+    (None) -- or None: another dtype, or the switch off.  A float16 operand never asks ``own``, a bfloat16 one never ``own_f16``."""
+    on, suffix = _ROUTES16.get(dtype, (lambda own, own_f16: False, None))
+    return suffix if on(own, own_f16) else None
 
 
 # ---- the choice table and the decision ---------------------------------------------------------------------------------------------
@@ -931,13 +945,17 @@ GCONV_BF16_WIDTHS = (4, 8, 16, 32, 64)       # channels per group that divide th
 # (C, CG, stride) of grouped convolutions that ``opa_gconv3x3_act_bf16`` can run but that came out SLOWER at batch 32 than torch's grouped
 # bfloat16 convolution + ``bias_act_`` (tools/gpu/gconv_bf16_times.py, profiles/gconv_bf16/times.log): the predicate declines them.
 GCONV_BF16_DECLINED = frozenset()
+# ... and of those that ``opa_gconv3x3_act_f16`` can run but that came out slower than torch's grouped FLOAT16 convolution + ``bias_act_``
+# (tools/gpu/f16x_times.py, profiles/f16x/times.log)
+GCONV_F16_DECLINED = frozenset()
+_GCONV16_DECLINED = {'_bf16': lambda: GCONV_BF16_DECLINED, '_f16': lambda: GCONV_F16_DECLINED}
 
 
 def gconv3x3_bf16_weight_of(conv, bias=None):
-    """The operands of ``gconv3x3_bias_act_bf16`` derived from the CURRENT ``conv.weight`` (``[C, CG, 3, 3]`` bfloat16, CG = C / groups)
-    and the folded ``bias`` the block keeps (``[C]`` bfloat16 or float32, or None): the weight as ``[C][9][64]``, K-major with K = 576
-    and BLOCK DIAGONAL per 64-channel chunk -- column ``j`` of row ``co`` is the weight of input channel ``64 * (co // 64) + j``:
-    ``weight[co, j % CG, ky, kx]`` where ``j // CG == (co % 64) // CG``, exactly zero elsewhere -- and the bias as FLOAT32 (upcast
+    """The operands of ``gconv3x3_bias_act_bf16`` derived from the CURRENT ``conv.weight`` (``[C, CG, 3, 3]`` 16-bit, CG = C / groups)
+    and the folded ``bias`` the block keeps (``[C]`` of that dtype or float32, or None): the weight as ``[C][9][64]`` of the weight's
+    dtype, K-major with K = 576 and BLOCK DIAGONAL per 64-channel chunk -- column ``j`` of row ``co`` is the weight of input channel
+    ``64 * (co // 64) + j``: ``weight[co, j % CG, ky, kx]`` where ``j // CG == (co % 64) // CG``, exactly zero elsewhere -- and the bias as FLOAT32 (upcast
     exactly; None stays None).  Derived and cached (``derived``, keyed on both tensors' storage and version): no buffer, no part of a
     state dict, computed again whenever the weight or the bias was replaced, moved, converted or changed in place
     (``load_state_dict`` into an optimized model)."""
@@ -953,9 +971,12 @@ def gconv3x3_bf16_weight_of(conv, bias=None):
 
 def gconv3x3_bf16_supported(conv, x, bias):
     """Can ``gconv3x3_bias_act_bf16(conv, x, bias)`` run?  ``conv3x3_bf16_supported`` with these differences: the switch is
-    ``GCONV_BF16``; the convolution HAS groups; as many output as input channels C, C a multiple of 64, and a group width C / groups
-    of ``GCONV_BF16_WIDTHS``; no residual; ``(C, C // groups, stride)`` not in ``GCONV_BF16_DECLINED``."""
-    if not (GCONV_BF16 and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and not torch.is_autocast_enabled()):
+    ``GCONV_BF16`` (float16: ``GCONV_F16``, not ``F16``); the convolution HAS groups; as many output as input channels C, C a multiple
+    of 64, and a group width C / groups of ``GCONV_BF16_WIDTHS``; no residual; ``(C, C // groups, stride)`` not in
+    ``GCONV_BF16_DECLINED`` (float16: ``GCONV_F16_DECLINED``)."""
+    dt = x.dtype
+    suffix = _route16(dt, GCONV_BF16, GCONV_F16)
+    if not (suffix and x.is_cuda and x.dim() == 4 and not torch.is_autocast_enabled()):
         return False
     if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad or (bias is not None and bias.requires_grad)):
         return False
@@ -963,26 +984,26 @@ def gconv3x3_bf16_supported(conv, x, bias):
     if not (conv.kernel_size == (3, 3) and conv.groups > 1 and conv.bias is None and conv.stride == (s, s) and s in (1, 2)
             and conv.dilation == (d, d) and d in (1, 2, 4) and (d == 1 or s == 1) and conv.padding == (d, d)
             and c == conv.out_channels and c % 64 == 0 and c % conv.groups == 0 and c // conv.groups in GCONV_BF16_WIDTHS
-            and x.shape[1] == c and conv.weight.dtype == torch.bfloat16 and conv.weight.device == x.device
+            and x.shape[1] == c and conv.weight.dtype == dt and conv.weight.device == x.device
             and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0 and 0 < x.numel() < 2 ** 31
             and out_pixels(x, s) * c < 2 ** 31):
         return False
-    if bias is not None and not (bias.dtype in (torch.bfloat16, torch.float32) and bias.device == x.device and bias.dim() == 1
+    if bias is not None and not (bias.dtype in (dt, torch.float32) and bias.device == x.device and bias.dim() == 1
                                  and bias.numel() == c):
         return False
-    return _lib.available() and (c, c // conv.groups, s) not in GCONV_BF16_DECLINED
+    return _lib.available() and (c, c // conv.groups, s) not in _GCONV16_DECLINED[suffix]()
 
 
 def gconv3x3_bias_act_bf16(conv, x, bias, relu=True):
-    """``act(conv(x) + bias)`` for the grouped 3x3 convolution of a bfloat16 ResNeXt (reference ``network/basenetworks.py:71-150`` with
-    torchvision's grouped Bottleneck; ``:121-135``: block 5 dilated) as ONE implicit GEMM per 64-channel chunk on the bf16 MFMA
-    (``opa_gconv3x3_act_bf16``, csrc/gconv3x3_bf16.hip): float32 accumulation, one rounding -- bfloat16 in and out.
+    """``act(conv(x) + bias)`` for the grouped 3x3 convolution of a 16-bit ResNeXt (reference ``network/basenetworks.py:71-150`` with
+    torchvision's grouped Bottleneck; ``:121-135``: block 5 dilated) as ONE implicit GEMM per 64-channel chunk on the 16-bit MFMA
+    (``opa_gconv3x3_act_bf16`` / ``..._f16``, csrc/gconv3x3_bf16.hip): float32 accumulation, one rounding -- ``x``'s dtype in and out.
     ``gconv3x3_bf16_supported`` says whether this can run."""
     w9, b32 = gconv3x3_bf16_weight_of(conv, bias)
     B, C, H, W = x.shape
     s = conv.stride[0]
     out = _empty_nhwc(x, C, _out_hw(x, s))
-    _launch('opa_gconv3x3_act_bf16', _ptr(x), _ptr(w9), _ptr(b32), _ptr(out), B, H, W, C, C // conv.groups, s, conv.dilation[0],
+    _launch('opa_gconv3x3_act' + _ROUTES16[x.dtype][1], _ptr(x), _ptr(w9), _ptr(b32), _ptr(out), B, H, W, C, C // conv.groups, s, conv.dilation[0],
             int(bool(relu)))
     return out
 
@@ -1011,11 +1032,16 @@ def stem7x7_bias_act_x3(conv, x, bias, relu=True):
 
 
 STEM7_BF16_K = 192                        # kStem7Bf16K: 8 window rows (the eighth zeros) of 8 pixels (the eighth zeros) of 3 channels
+# (c_out, stride, pooled) of FLOAT16 stems that ``opa_stem7x7_act_f16`` can run but that came out SLOWER at batch 32 than torch's float16
+# convolution + ``bias_act_`` (pooled: + ``F.max_pool2d`` behind either) (tools/gpu/f16x_times.py, profiles/f16x/times.log):
+# ``stem7x7_bf16_supported(..., pooled=...)`` declines them.  (The bfloat16 stem has no such set: its predicate answers as it did.)
+STEM7_F16_DECLINED = frozenset()
 
 
 def stem7x7_bf16_weight_of(conv, bias=None):
-    """The operands of ``stem7x7_bias_act_bf16`` derived from the CURRENT ``conv.weight`` (``[N, 3, 7, 7]`` bfloat16) and the folded
-    ``bias`` the network keeps (``[N]`` bfloat16 or float32, or None): the weight as ``[N][192]``, K-major in the load plan's order
+    """The operands of ``stem7x7_bias_act_bf16`` derived from the CURRENT ``conv.weight`` (``[N, 3, 7, 7]`` 16-bit) and the folded
+    ``bias`` the network keeps (``[N]`` of that dtype or float32, or None): the weight as ``[N][192]`` of the weight's dtype, K-major in
+    the load plan's order
     (csrc/stem7x7_bf16_plan.hpp) -- ``w[co][ky * 24 + kx * 3 + ci] = weight[co][ci][ky][kx]``, ZEROS in the columns ``kx = 7`` and
     ``ky = 7`` that pad 147 to 192 -- and the bias as FLOAT32 (upcast exactly; None stays None).  Derived and cached (``derived``,
     keyed on both tensors' storage and version): no buffer, no part of a state dict, computed again whenever the weight or the bias
@@ -1028,15 +1054,18 @@ def stem7x7_bf16_weight_of(conv, bias=None):
     return derived(conv, '_opa_w_stem7_bf16', (conv.weight, bias), make)
 
 
-def stem7x7_bf16_supported(conv, x, bias):
-    """Can ``stem7x7_bias_act_bf16(conv, x, bias)`` run?  The switch on; ``x`` a bfloat16 ``[B, 3, H, W]`` tensor on the GPU in ANY
+def stem7x7_bf16_supported(conv, x, bias, pooled=False):
+    """Can ``stem7x7_bias_act_bf16(conv, x, bias)`` run?  The switch on (bfloat16: ``STEM7_BF16``, float16: ``STEM7_F16``, not
+    ``F16``); ``x`` a 16-bit ``[B, 3, H, W]`` tensor on the GPU in ANY
     layout with positive strides (channels-last, NCHW, a cropped view), outside autocast (whose parameters stay float32), nothing
     that autograd follows; a 7x7 convolution with padding 3, no dilation, no groups and no bias of its own (the folded one arrives
-    separately: bfloat16 or float32, one element per output channel, or None), square stride 1 or 2, output channels a multiple of
-    64, bfloat16 weights on ``x``'s device; ``x`` fewer than 2^31 elements from the first to the last addressed, the output fewer
-    than 2^31 elements."""
-    if not (STEM7_BF16 and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and x.shape[1] == 3
-            and not torch.is_autocast_enabled()):
+    separately: of ``x``'s dtype or float32, one element per output channel, or None), square stride 1 or 2, output channels a multiple of
+    64, weights of ``x``'s dtype on ``x``'s device; ``x`` fewer than 2^31 elements from the first to the last addressed, the output fewer
+    than 2^31 elements; for float16, ``(c_out, stride, pooled)`` not in ``STEM7_F16_DECLINED`` (``pooled``: the caller puts the input
+    max-pool behind the stem)."""
+    dt = x.dtype
+    suffix = _route16(dt, STEM7_BF16, STEM7_F16)
+    if not (suffix and x.is_cuda and x.dim() == 4 and x.shape[1] == 3 and not torch.is_autocast_enabled()):
         return False
     if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad or (bias is not None and bias.requires_grad)):
         return False
@@ -1044,10 +1073,12 @@ def stem7x7_bf16_supported(conv, x, bias):
     if not (isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (7, 7) and conv.padding == (3, 3) and conv.dilation == (1, 1)
             and conv.groups == 1 and conv.bias is None and conv.padding_mode == 'zeros' and conv.stride == (s, s) and s in (1, 2)
             and conv.in_channels == 3 and conv.out_channels % 64 == 0
-            and conv.weight.dtype == torch.bfloat16 and conv.weight.device == x.device):
+            and conv.weight.dtype == dt and conv.weight.device == x.device):
         return False
-    if bias is not None and not (bias.dtype in (torch.bfloat16, torch.float32) and bias.device == x.device and bias.dim() == 1
+    if bias is not None and not (bias.dtype in (dt, torch.float32) and bias.device == x.device and bias.dim() == 1
                                  and bias.numel() == conv.out_channels):
+        return False
+    if suffix == '_f16' and (conv.out_channels, s, bool(pooled)) in STEM7_F16_DECLINED:
         return False
     last = sum((n - 1) * st for n, st in zip(x.shape, x.stride()))               # the last element addressed
     return (min(x.shape) > 0 and min(x.stride()) > 0 and x.data_ptr() % 2 == 0 and last < 2 ** 31
@@ -1055,15 +1086,15 @@ def stem7x7_bf16_supported(conv, x, bias):
 
 
 def stem7x7_bias_act_bf16(conv, x, bias, relu=True):
-    """``act(conv(x) + bias)`` for the 7x7 padding-3 stem of a bfloat16 ResNet on RGB input (reference ``network/basenetworks.py:71-150``),
-    stride 1 or 2, as ONE implicit GEMM on the bf16 MFMA (``opa_stem7x7_act_bf16``, csrc/stem7x7_bf16.hip): ``x`` is read through its
-    own four strides, whatever its layout -- no padded copy, no 4-channel copy --, float32 accumulation, one rounding; the result is
-    a dense channels-last bfloat16 tensor.  ``stem7x7_bf16_supported`` says whether this can run."""
+    """``act(conv(x) + bias)`` for the 7x7 padding-3 stem of a 16-bit ResNet on RGB input (reference ``network/basenetworks.py:71-150``),
+    stride 1 or 2, as ONE implicit GEMM on the 16-bit MFMA (``opa_stem7x7_act_bf16`` / ``..._f16``, csrc/stem7x7_bf16.hip): ``x`` is read
+    through its own four strides, whatever its layout -- no padded copy, no 4-channel copy --, float32 accumulation, one rounding; the
+    result is a dense channels-last tensor of ``x``'s dtype.  ``stem7x7_bf16_supported`` says whether this can run."""
     wk, b32 = stem7x7_bf16_weight_of(conv, bias)
     B, _, H, W = x.shape
     s = conv.stride[0]
     out = _empty_nhwc(x, conv.out_channels, _out_hw(x, s))
-    _launch('opa_stem7x7_act_bf16', _ptr(x), x.stride(0), x.stride(1), x.stride(2), x.stride(3), _ptr(wk), _ptr(b32), _ptr(out),
+    _launch('opa_stem7x7_act' + _ROUTES16[x.dtype][1], _ptr(x), x.stride(0), x.stride(1), x.stride(2), x.stride(3), _ptr(wk), _ptr(b32), _ptr(out),
             B, H, W, conv.out_channels, s, int(bool(relu)))
     return out
 

@@ -68,6 +68,7 @@ _CONV3_ROUTES = (
     # (bfloat16 behind fused.CONV3_BF16 and float16 behind fused.F16: one row for both 16-bit types)
     ('bf16', lambda c, x, b, r, u: fused.conv3x3_bf16_supported(c, x, b, r),
      lambda c, x, b, r, u, bare: fused.conv3x3_bias_act_bf16(c, x, b, r, relu=not bare), True, None),
+    # (bfloat16 behind fused.GCONV_BF16 and float16 behind fused.GCONV_F16: one row for both 16-bit types)
     ('gconv-bf16', lambda c, x, b, r, u: fused.gconv3x3_bf16_supported(c, x, b),
      lambda c, x, b, r, u, bare: fused.gconv3x3_bias_act_bf16(c, x, None if bare else b, not bare), False, None),
 )
@@ -375,9 +376,9 @@ class Resnet(BaseNetwork):
                 x = fused.pick('stem', fused.out_pixels(x0, 2), 256, conv.out_channels,
                                True, False, lambda: fused.stem7x7_bias_act_x3(conv, x0, self.fb0),
                                lambda: fused.bias_act_(conv(x0), self.fb0))
-        elif fused.stem7x7_bf16_supported(conv, x, self.fb0):   # bfloat16 with fused.STEM7_BF16: one launch, bias + ReLU inside
-            x = fused.stem7x7_bias_act_bf16(conv, x, self.fb0)
-            if pool:
+        elif fused.stem7x7_bf16_supported(conv, x, self.fb0, pool):   # bfloat16 with fused.STEM7_BF16, float16 with fused.STEM7_F16:
+            x = fused.stem7x7_bias_act_bf16(conv, x, self.fb0)        # one launch, bias + ReLU inside
+            if pool:                                                  # (float16: the pool kernel declines it, F.max_pool2d runs)
                 x = self._pooled(x)
         elif pool:                                          # torch's raw convolution (bfloat16, a stem stride other than 2)
             x = self._pooled(conv(x), self.fb0)
