@@ -343,17 +343,62 @@ def _empty_nhwc(x, channels, hw=None, dtype=None):
 
 # ---- derived operands -----------------------------------------------------------------------------------------------------------------
 
+def _capturing():
+    """Is the current stream being captured into a HIP graph?  False where no GPU was initialised: nothing can be capturing there,
+    and asking would raise on a machine without one."""
+    return torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing()
+
+
+def _refreshable(kept, new):
+    """Can ``_refresh_(kept, new)`` write ``new`` -- what ``make()`` returned now -- into ``kept``, what it returned before?  Tensors of
+    one shape, dtype, device and layout (an inference tensor only inside inference mode), None for None, a tuple or list element
+    by element, anything else where it compares equal."""
+    if isinstance(kept, torch.Tensor) or isinstance(new, torch.Tensor):
+        return (isinstance(kept, torch.Tensor) and isinstance(new, torch.Tensor) and kept.shape == new.shape and kept.dtype == new.dtype
+                and kept.device == new.device and kept.stride() == new.stride()
+                and (not kept.is_inference() or torch.is_inference_mode_enabled()))
+    if isinstance(kept, (tuple, list)):
+        return type(kept) is type(new) and len(kept) == len(new) and all(_refreshable(k, n) for k, n in zip(kept, new))
+    return type(kept) is type(new) and kept == new
+
+
+def _refresh_(kept, new):
+    if isinstance(kept, torch.Tensor):
+        with torch.no_grad():
+            kept.copy_(new)
+    elif isinstance(kept, (tuple, list)):
+        for k, n in zip(kept, new):
+            _refresh_(k, n)
+
+
 def derived(module, name, sources, make):
-    """``make()`` -- an operand derived from the tensors ``sources`` (parameters, buffers; None where there is none) -- computed
-    once, kept on ``module`` as attribute ``name`` and computed again whenever a source was replaced, moved, converted or changed
-    in place (``load_state_dict``, ``.to()``, an optimizer step): the key is (data pointer, version counter, device, dtype) of each.
-    The entry holds on to the sources' storages, so that no later tensor can be handed the same address while it is the key."""
-    key = tuple(None if t is None else (t.data_ptr(), t._version, str(t.device), t.dtype) for t in sources)
+    """``make()`` -- an operand derived from the tensors ``sources`` (parameters, buffers; None where there is none): a tensor, or a
+    tuple of tensors and None -- computed once, kept on ``module`` as attribute ``name`` and brought up to date whenever a source was
+    replaced, moved, converted or changed in place (``load_state_dict``, ``.to()``, an optimizer step): the key is (data pointer,
+    device, dtype, shape) and the version counter of each.  The entry holds on to the sources' storages, so that no later tensor can
+    be handed the same address while it is the key.  A HIP graph bakes the ADDRESS of whatever a launch is handed, hence:
+
+    (i)   an operand made while a stream is being captured is NOT kept (it lives in the graph's private pool and holds nothing
+          until the first replay): the graph computes it again on every replay from the parameters it read -- it follows them as
+          torch's own modules do -- and an eager call makes and keeps its own;
+    (ii)  where every source still has the pointer, device, dtype and shape of the key and only version counters rose, the kept
+          tensors are OVERWRITTEN IN PLACE with ``make()``'s new values: an address in a graph stays valid and sees the new weights
+          (outside a capture: a stale entry met while capturing is left alone, and the call goes by (i));
+    (iii) where a source was replaced (``.to()``, ``.half()``, a new ``Parameter``) the entry is replaced: a graph captured over the
+          old parameters must be captured again, as with any torch module."""
+    where = tuple(None if t is None else (t.data_ptr(), str(t.device), t.dtype, t.shape) for t in sources)
+    key = (where, tuple(None if t is None else t._version for t in sources))
     cached = getattr(module, name, None)
-    if cached is None or cached[0] != key:
-        cached = (key, make(), [t.untyped_storage() for t in sources if t is not None])
-        setattr(module, name, cached)
-    return cached[1]
+    if cached is not None and cached[0] == key:
+        return cached[1]
+    value = make()
+    if _capturing():
+        return value
+    if cached is not None and cached[0][0] == where and _refreshable(cached[1], value):
+        _refresh_(cached[1], value)
+        value = cached[1]
+    setattr(module, name, (key, value, [t.untyped_storage() for t in sources if t is not None]))
+    return value
 
 
 def split_weight(weight2d):
@@ -1549,13 +1594,15 @@ def group_norm_supported(norm, x):
 def _gn_workspace(x, nbytes):
     """The workspace of ``group_norm_act``: one float64 tensor per device and stream, kept between calls and replaced by a larger one
     when a call needs more (the calls of a stream run in order, so they can share it; torch's allocator keeps a replaced tensor's
-    memory until the stream has passed its last use).  Nothing is kept of a call inside a stream capture: that memory is the graph's."""
+    memory until the stream has passed its last use).  A call inside a stream capture neither takes the kept tensor nor keeps its own:
+    a graph bakes the address it was handed, and a kept tensor is freed as soon as an eager call outgrows it, so the capturing call
+    always allocates -- from the graph's own pool, which lives as long as the graph -- and the table stays as it was."""
+    if _capturing():
+        return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
     key = (str(x.device), _stream())
     ws = _GN_WORKSPACE.get(key)
     if ws is None or ws.numel() * 8 < nbytes:
-        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
-        if not (x.device.type == 'cuda' and torch.cuda.is_current_stream_capturing()):
-            _GN_WORKSPACE[key] = ws
+        ws = _GN_WORKSPACE[key] = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
     return ws
 
 

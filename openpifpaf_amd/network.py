@@ -499,12 +499,14 @@ class _InvertedResidualK(nn.Module):
     @staticmethod
     def taps_of(conv):
         """``w_taps`` of the CURRENT depthwise weight: the buffer (part of the state dict since it was introduced, so it stays one)
-        is written again whenever the weight was replaced, converted or changed in place since."""
-        def make():
-            conv.w_taps = fused.depthwise_taps(conv.weight)
-            return True
-        fused.derived(conv, '_opa_taps', (conv.weight,), make)
-        return conv.w_taps
+        IS the operand ``fused.derived`` keeps, so it is brought up to date -- in place where the weight was changed in place -- whenever
+        the weight was replaced, converted or changed since.  An operand made while a stream is being captured is the graph's and is
+        not kept (``fused.derived``): the buffer stays what it was."""
+        taps = fused.derived(conv, '_opa_taps', (conv.weight,), lambda: fused.depthwise_taps(conv.weight))
+        kept = getattr(conv, '_opa_taps', None)
+        if kept is not None and kept[1] is taps and conv.w_taps is not taps:
+            conv.w_taps = taps
+        return taps
 
     @staticmethod
     def _dw_ok(m, x):

@@ -308,16 +308,19 @@ def test_the_derived_operands_are_float16_with_a_float32_bias_and_follow_the_wei
         return a, b
     # load_state_dict (an in-place copy: the version counter moves)
     before = fresh()
+    old = [t.clone() for t in before]
     conv.load_state_dict({'weight': torch.randn(128, 64, 3, 3, generator=tc.gen(9)).half()})
     dconv.load_state_dict({'weight': torch.randn(256, 128, 1, 1, generator=tc.gen(10)).half()})
     after = check()
-    assert after[0] is not before[0] and after[1] is not before[1] and not torch.equal(after[0], before[0])
+    # (the pointers stayed: the kept tensors are overwritten in place -- an address a HIP graph holds sees the new weights)
+    assert after[0] is before[0] and after[1] is before[1] and not torch.equal(after[0], old[0]) and not torch.equal(after[1], old[1])
+    old = [t.clone() for t in after]
     # an in-place change
     with torch.no_grad():
         conv.weight.mul_(2.0)
         pconv.weight.add_(1.0)
     again = check()
-    assert again[0] is not after[0] and again[1] is not after[1] and torch.equal(again[0], after[0] * 2)
+    assert again[0] is after[0] and again[1] is after[1] and torch.equal(again[0], old[0] * 2) and not torch.equal(again[1], old[1])
     # a round trip through float32: new tensors of equal values
     for m in (conv, pconv, dconv):
         m.half().float().half()

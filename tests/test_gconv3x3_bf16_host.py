@@ -91,16 +91,19 @@ def test_the_operands_are_derived_again_when_the_parameters_change():
         co, j = torch.arange(128)[:, None], torch.arange(64)[None, :]
         return w9.permute(0, 2, 1)[(j // 4) == ((co % 64) // 4)].reshape(128, 4, 3, 3)
     w9, b32 = fused.gconv3x3_bf16_weight_of(conv, bias)
+    w9_0, b32_0 = w9.clone(), b32.clone()
     torch.manual_seed(3)
     state = {k: torch.randn_like(v) for k, v in block.state_dict().items()}
     block.load_state_dict(state)                                                          # (in place: the version counters move)
     w9b, b32b = fused.gconv3x3_bf16_weight_of(conv, bias)
-    assert w9b is not w9 and torch.equal(unpacked(w9b), state['conv2.weight']) and not torch.equal(w9b, w9)
-    assert b32b is not b32 and torch.equal(b32b, state['fb2'].float()) and not torch.equal(b32b, b32)
+    # (the pointers stayed: the KEPT tensors are overwritten in place -- an address a HIP graph holds sees the new weights)
+    assert w9b is w9 and torch.equal(unpacked(w9b), state['conv2.weight']) and not torch.equal(w9b, w9_0)
+    assert b32b is b32 and torch.equal(b32b, state['fb2'].float()) and not torch.equal(b32b, b32_0)
+    w9_1 = w9b.clone()
     with torch.no_grad():                                                                 # an in-place update of the weight alone
         conv.weight.mul_(2.0)
     w9c, b32c = fused.gconv3x3_bf16_weight_of(conv, bias)
-    assert w9c is not w9b and torch.equal(w9c, w9b * 2) and torch.equal(b32c, b32b)
+    assert w9c is w9b and torch.equal(w9c, w9_1 * 2) and torch.equal(b32c, state['fb2'].float())
     with torch.no_grad():                                                                 # ... and of the folded bias alone
         bias.add_(1.0)
     assert torch.equal(fused.gconv3x3_bf16_weight_of(conv, bias)[1], bias.float())

@@ -63,21 +63,25 @@ def test_the_operands_are_derived_again_when_the_parameters_change():
     def cat(w, wd):
         return torch.cat((w.reshape(n, k1), wd.reshape(n, k2)), dim=1)
     wcat, b32 = fused.pair_bf16_weight_of(conv, dconv, bias)
+    wcat_0, b32_0 = wcat.clone(), b32.clone()
     state = {k: torch.randn_like(v) for k, v in block.state_dict().items()}
     block.load_state_dict(state)                                                          # (in place: the version counters move)
     wcat_b, b32_b = fused.pair_bf16_weight_of(conv, dconv, bias)
-    assert wcat_b is not wcat and not torch.equal(wcat_b, wcat)
+    # (the pointers stayed: the KEPT tensors are overwritten in place -- an address a HIP graph holds sees the new weights)
+    assert wcat_b is wcat and not torch.equal(wcat_b, wcat_0)
     assert torch.equal(wcat_b, cat(state['conv3.weight'], state['downsample.0.weight']))
-    assert b32_b is not b32 and torch.equal(b32_b, state['fb3'].float()) and not torch.equal(b32_b, b32)
+    assert b32_b is b32 and torch.equal(b32_b, state['fb3'].float()) and not torch.equal(b32_b, b32_0)
+    wcat_1 = wcat_b.clone()
     with torch.no_grad():                                                                 # an in-place update of conv3's weight alone
         conv.weight.mul_(2.0)
     wcat_c, b32_c = fused.pair_bf16_weight_of(conv, dconv, bias)
-    assert wcat_c is not wcat_b and torch.equal(wcat_c[:, :k1], wcat_b[:, :k1] * 2) and torch.equal(wcat_c[:, k1:], wcat_b[:, k1:])
-    assert torch.equal(b32_c, b32_b)
+    assert wcat_c is wcat_b and torch.equal(wcat_c[:, :k1], wcat_1[:, :k1] * 2) and torch.equal(wcat_c[:, k1:], wcat_1[:, k1:])
+    assert torch.equal(b32_c, state['fb3'].float())
+    wcat_2 = wcat_c.clone()
     with torch.no_grad():                                                                 # ... of the downsampling weight alone
         dconv.weight.mul_(0.5)
     wcat_d = fused.pair_bf16_weight_of(conv, dconv, bias)[0]
-    assert torch.equal(wcat_d[:, k1:], wcat_c[:, k1:] * 0.5) and torch.equal(wcat_d[:, :k1], wcat_c[:, :k1])
+    assert torch.equal(wcat_d[:, k1:], wcat_2[:, k1:] * 0.5) and torch.equal(wcat_d[:, :k1], wcat_2[:, :k1])
     with torch.no_grad():                                                                 # ... and of the folded bias alone
         bias.add_(1.0)
     assert torch.equal(fused.pair_bf16_weight_of(conv, dconv, bias)[1], bias.float())

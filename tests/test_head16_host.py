@@ -170,17 +170,20 @@ def test_the_derived_operands_are_padded_and_follow_the_parameters(built, dt):
         return wp, bp
     first = check()
     assert fused.head16_operands_of(conv)[0] is first[0] and fused.head16_operands_of(conv)[1] is first[1]       # cached
-    with torch.no_grad():                               # an in-place weight update
-        conv.weight.mul_(2.0)
+    old = [t.clone() for t in first]
+    with torch.no_grad():                               # an in-place weight update: the KEPT tensors are overwritten in place (an
+        conv.weight.mul_(2.0)                           # address a HIP graph holds sees the new weights)
     second = check()
-    assert second[0] is not first[0] and torch.equal(second[0], first[0] * 2)
+    assert second[0] is first[0] and second[1] is first[1] and torch.equal(second[0], old[0] * 2)
+    old = [t.clone() for t in second]
     with torch.no_grad():                               # ... and of the bias alone
         conv.bias.add_(1.0)
     third = check()
-    assert third[1] is not second[1] and not torch.equal(third[1], second[1])
+    assert third[1] is second[1] and not torch.equal(third[1], old[1])
+    old = [t.clone() for t in third]
     conv.load_state_dict({'weight': torch.randn(60, 64, 1, 1, generator=tc.gen(9)).to(dt), 'bias': torch.randn(60, generator=tc.gen(10)).to(dt)})
     fourth = check()
-    assert fourth[0] is not third[0] and not torch.equal(fourth[0], third[0])
+    assert fourth[0] is third[0] and not torch.equal(fourth[0], old[0])
     conv.to(torch.float32).to(dt)                       # a round trip: new tensors of equal values
     fifth = check()
     assert fifth[0] is not fourth[0] and torch.equal(fifth[0], fourth[0]) and torch.equal(fifth[1], fourth[1])

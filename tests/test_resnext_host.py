@@ -101,8 +101,9 @@ def test_operand_follows_the_weight(cg, groups):
     assert fused.gconv_weight_of(conv) is wt
     with torch.no_grad():
         conv.weight.mul_(2.0)                               # in place
+    old = wt.clone()
     wt2 = fused.gconv_weight_of(conv)
-    assert wt2 is not wt and torch.equal(wt2, want())
+    assert wt2 is wt and torch.equal(wt2, want()) and torch.equal(wt2, old * 2.0)        # the kept tensor, overwritten in place
     other = tc.randomize_(nn.Conv2d(C, C, 3, 1, 1, groups=groups, bias=False), cg + 100)
     conv.load_state_dict(other.state_dict())
     assert torch.equal(fused.gconv_weight_of(conv), other.weight.detach().permute(2, 3, 1, 0).reshape(9, cg, C))

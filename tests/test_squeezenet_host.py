@@ -136,10 +136,12 @@ def test_derived_weight_follows_the_weight():
         return a, b
     a, b = decoded(w3)
     assert torch.equal(a, e1.weight.detach().reshape(128, 32)) and torch.equal(b, e3.weight.detach().permute(0, 2, 3, 1))
+    old = w3.clone()
     with torch.no_grad():
         e3.weight.mul_(2.0)
-    w3b, _ = fused.fire_weight_of(e1, e3)
-    assert w3b is not w3 and torch.equal(decoded(w3b)[1], e3.weight.detach().permute(0, 2, 3, 1))
+    w3b, bias_b = fused.fire_weight_of(e1, e3)
+    # (the kept tensors, overwritten in place: an address a HIP graph holds sees the new weights)
+    assert w3b is w3 and bias_b is bias and not torch.equal(w3b, old) and torch.equal(decoded(w3b)[1], e3.weight.detach().permute(0, 2, 3, 1))
     with torch.no_grad():
         e1.bias.add_(1.0)
     assert torch.equal(fused.fire_weight_of(e1, e3)[1], torch.cat((e1.bias, e3.bias)).detach())

@@ -236,18 +236,21 @@ def test_the_operands_are_derived_again_when_the_parameters_change(on):
     torch.manual_seed(2)
     conv = _conv(24, 40)
     wp, bp = fused._unit_weight_f16_of(conv)
+    wp_0, bp_0 = wp.clone(), bp.clone()
     state = {k: torch.randn_like(v) for k, v in conv.state_dict().items()}
     conv.load_state_dict(state)                                                           # (in place: the version counters move)
     wp2, bp2 = fused._unit_weight_f16_of(conv)
-    assert wp2 is not wp and torch.equal(wp2[:40, :24], state['weight'].view(40, 24)) and torch.equal(bp2[:40], state['bias'].float())
-    assert not torch.equal(wp2, wp) and not torch.equal(bp2, bp)
+    # (the pointers stayed: the KEPT tensors are overwritten in place -- an address a HIP graph holds sees the new weights)
+    assert wp2 is wp and bp2 is bp and torch.equal(wp2[:40, :24], state['weight'].view(40, 24)) and torch.equal(bp2[:40], state['bias'].float())
+    assert not torch.equal(wp2, wp_0) and not torch.equal(bp2, bp_0)
+    wp_2, bp_2 = wp2.clone(), bp2.clone()
     with torch.no_grad():
         conv.weight.mul_(2.0)                                                             # changed in place
     wp3, _ = fused._unit_weight_f16_of(conv)
-    assert wp3 is not wp2 and torch.equal(wp3, wp2 * 2)
+    assert wp3 is wp2 and torch.equal(wp3, wp_2 * 2)
     conv.half().float().half()                                                            # a round trip through float32: new tensors of equal values
     wp4, bp4 = fused._unit_weight_f16_of(conv)
-    assert wp4 is not wp3 and wp4.dtype == F16 and torch.equal(wp4, wp3) and torch.equal(bp4, bp2)
+    assert wp4 is not wp3 and wp4.dtype == F16 and torch.equal(wp4, wp3) and torch.equal(bp4, bp_2)
     conv.weight = nn.Parameter(torch.ones(40, 24, 1, 1, dtype=F16), requires_grad=False)  # the weight REPLACED
     assert torch.equal(fused._unit_weight_f16_of(conv)[0][:40, :24], torch.ones(40, 24, dtype=F16))
     conv.bias = nn.Parameter(torch.ones(40, dtype=F16), requires_grad=False)              # a bias REPLACED: the key holds it
