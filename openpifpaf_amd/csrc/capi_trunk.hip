@@ -520,7 +520,9 @@ static int conv3x3_winograd(const char* fn, bool x3, const float* x_dev, const v
                             int32_t batch, int32_t h, int32_t w, int32_t c_in, int32_t c_out, int32_t relu, int32_t variant,
                             int32_t order, void* stream) {
     const Entry E(fn, stream);
-    const bool known = x3 ? variant == 4 || (variant >= 21 && variant <= 23) : (variant >= 0 && variant <= 3) || (variant >= 11 && variant <= 18);
+    // (x3's variant 5, the 128-channel workgroups forced, exists for c_out % 128 == 0 only)
+    const bool known = x3 ? variant == 4 || (variant == 5 && c_out > 0 && c_out % 128 == 0) || (variant >= 21 && variant <= 23)
+                          : (variant >= 0 && variant <= 3) || (variant >= 11 && variant <= 18);
     if (!x_dev || !u_dev || !out_dev || batch <= 0 || h <= 0 || w <= 0 || c_in <= 0 || c_out <= 0 || !known) return E.refuse("bad arguments");
     if (!x3 && variant == 1 ? (c_in % 8 != 0 || c_out % 32 != 0) : (c_in % 16 != 0 || c_out % 64 != 0))
         return E.refuse(x3 ? "c_in % 16 and c_out % 64 must be 0" : "channel counts do not fit the variant's tiles");

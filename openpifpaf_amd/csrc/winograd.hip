@@ -22,6 +22,7 @@
 //   * output transform: A^T m A splits into the nu-sum (inside the owning wave, registers) and the xi-sum across the four
 //     waves through LDS (the staging buffers, reused), then bias / ReLU if asked and 256-B contiguous stores.
 #include <atomic>
+#include <cstdlib>
 
 #include "common.hpp"
 #include "split_bf16.hpp"
@@ -755,6 +756,237 @@ __global__ __launch_bounds__(512, 1) void winograd_f23_w8x3_kernel(
     }
 }
 
+// ---- variant 5: variant 4 with workgroups of 32 tiles x 128 output channels.  Variant 4's loop is bound by the vector issue
+// of its activation side (per MFMA 6.6 other vector instructions -- the bf16 split, B^T d B, address sums, the zeroing of the
+// padding -- and every workgroup along the output channels does all of it again for the same tiles).  The same 4096
+// tile x channel accumulators as 32 x 128 halve that work per MFMA: one activation fragment (8 values, split once) now feeds
+// 24 MFMAs instead of 12.  Everything that decides a result is variant 4's -- per accumulator block the six products of a chunk
+// in the same order, the chunks in the same order, the transforms' additions in the same order -- so the two are equal bit for
+// bit (tests/test_gpu_winograd_x3_wide.py).  What differs:
+//   * wave w keeps positions 2 w and 2 w + 1 for ONE block of 32 tiles and four channel blocks of 32: acc[2][4];
+//   * thread (tile = tid / 16, channel = tid % 16) fetches its tile's sixteen pixels of one channel (dword buffer loads, 64 B
+//     contiguous per tile and pixel as in variant 4); V[position][k][tile] has a pitch of 34: the stores (c * 34 + tile,
+//     two tiles per 32 lanes) and the operand reads (32 consecutive tiles) meet no bank twice;
+//   * a pixel in the padding is given an offset past the descriptor's range, which loads as zero: no select, no mask in the
+//     loop.  kW8WRowOut + kW8WColOut + any valid offset stays below 2^32 and every sum with one of them lies at or above
+//     kW8WMaxBytes, which the launcher holds the activation under;
+//   * the filter operand is variant 4's (split_filter: channel halves j = 0, 1 from the 64-channel block 2 nb, j = 2, 3 from
+//     2 nb + 1).  A chunk's eight (position, j) fragments of 12 registers do not fit; four are kept, fragment (pl, j) is
+//     reloaded with (pl ^ 1, j) -- of the next chunk behind position 1 -- right behind its six MFMAs, i.e. three fragments
+//     (72 MFMAs) ahead of its use, the same loads in the same order in every iteration (variant 3's comment: static waits);
+//   * output transform: variant 4's, per 64-channel half instead of per 32-tile half (the same 128 KB of staging).
+constexpr int kW8WP = 34, kW8WVBUF = 16 * kW8KC * kW8WP;
+constexpr unsigned kW8WRowOut = 0x80000000u, kW8WColOut = 0x40000000u, kW8WMaxBytes = 0x40000000u;
+constexpr int kW8WLdsBytes = 8 * 2 * 32 * 64 * 4;       // 131 072 B: an output half (>= the 69 632 B of the two stages)
+static_assert(kW8WLdsBytes <= kW8LdsBytes && 2 * kW8WVBUF * 4 <= kW8WLdsBytes, "the wide kernel's LDS");
+
+__global__ __launch_bounds__(512, 1) void winograd_f23_w8x3w_kernel(
+        const float* __restrict__ x, const unsigned short* __restrict__ U3, float* __restrict__ y, const float* __restrict__ bias,
+        int H, int W, int Cin, int Cout, int TH, int TW, int T, int relu, int nb_major) {
+    constexpr int KC = kW8KC, P = kW8WP, NB = 4, BN = 128, TB = 32, HB = 64;
+    typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
+    typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
+    extern __shared__ __attribute__((aligned(16))) unsigned char wino_smem[];
+    float* const lds = reinterpret_cast<float*>(wino_smem);
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n_nb = Cout / BN;
+    const unsigned nwg = gridDim.x, xcd = blockIdx.x & 7u, in_xcd = blockIdx.x >> 3;
+    const unsigned q8 = nwg >> 3, r8 = nwg & 7u;
+    const unsigned logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + in_xcd;
+    const unsigned n_tb = nwg / (unsigned)n_nb;
+    const int tb = nb_major ? (int)(logical % n_tb) : (int)(logical / (unsigned)n_nb);
+    const int nb = nb_major ? (int)(logical / n_tb) : (int)(logical % (unsigned)n_nb);
+    const int nchunks = Cin / KC;
+
+    const int tile_l = tid >> 4, cl = tid & 15;
+    int t = tb * TB + tile_l;
+    if (t > T - 1) t = T - 1;
+    const int tx = t % TW, ty = (t / TW) % TH, n = t / (TW * TH);
+    // byte offsets of the tile's four rows and four columns; one outside the image is out of the descriptor's range with
+    // every partner.  Buffer loads as in variant 4: the row + column sum is formed in the loop, opaque to the optimiser.
+    unsigned rowoff[4], coloff[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int r = 2 * ty - 1 + i, c = 2 * tx - 1 + i;
+        rowoff[i] = r >= 0 && r < H ? (unsigned)((n * H + r) * W) * (unsigned)Cin * 4u : kW8WRowOut;
+        coloff[i] = c >= 0 && c < W ? ((unsigned)c * (unsigned)Cin + (unsigned)cl) * 4u : kW8WColOut;
+    }
+    const unsigned x_bytes = (unsigned)(T / (TH * TW)) * (unsigned)(H * W) * (unsigned)Cin * 4u;     // (<= kW8WMaxBytes: the launcher)
+    const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, (int)x_bytes, 0x00020000);
+    float d[16];
+    auto fetch_x = [&](int chunk) {
+        unsigned ro[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) { ro[i] = rowoff[i]; asm volatile("" : "+v"(ro[i])); }
+#pragma unroll
+        for (int k = 0; k < 16; k++)
+            d[k] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(x_rsrc, ro[k >> 2] + coloff[k & 3], chunk * KC * 4, 0));
+    };
+    auto transform_store = [&](int buf) {
+        float* const vb = lds + buf * kW8WVBUF + cl * P + tile_l;
+        float s[16];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            s[0 * 4 + j] = d[0 * 4 + j] - d[2 * 4 + j];
+            s[1 * 4 + j] = d[1 * 4 + j] + d[2 * 4 + j];
+            s[2 * 4 + j] = d[2 * 4 + j] - d[1 * 4 + j];
+            s[3 * 4 + j] = d[1 * 4 + j] - d[3 * 4 + j];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            vb[((i * 4 + 0) * KC) * P] = s[i * 4 + 0] - s[i * 4 + 2];
+            vb[((i * 4 + 1) * KC) * P] = s[i * 4 + 1] + s[i * 4 + 2];
+            vb[((i * 4 + 2) * KC) * P] = s[i * 4 + 2] - s[i * 4 + 1];
+            vb[((i * 4 + 3) * KC) * P] = s[i * 4 + 1] - s[i * 4 + 3];
+        }
+    };
+
+    // filter operand: the four channel blocks j of ONE position at a time (see the header), piece q
+    u32x4_t ub[NB][3];
+    const __amdgpu_buffer_rsrc_t u_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<unsigned short*>(U3 + (size_t)(2 * nb) * nchunks * (16 * 2 * 3 * 64 * 8)), 0, 2 * nchunks * (16 * 2 * 3 * 64 * 16), 0x00020000);
+    const unsigned u_lane = (unsigned)lane * 16u;
+    const int wave_s = __builtin_amdgcn_readfirstlane(wave);
+    auto u_load = [&](int chunk, int pl, int j, int q) {
+        return __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(
+            u_rsrc, u_lane, ((((((j >> 1) * nchunks + chunk) * 16 + wave_s * 2 + pl) * 2 + (j & 1)) * 3 + q) * 64) * 16, 0));
+    };
+    wf32x16_t acc[2][NB];
+#pragma unroll
+    for (int pl = 0; pl < 2; pl++)
+#pragma unroll
+        for (int j = 0; j < NB; j++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[pl][j][r] = 0.0f;
+
+    const int a_lane = (lane >> 5) * P + (lane & 31) + (wave * 2 * KC) * P;
+    auto mfma_phase = [&](int chunk, int nxt) {
+        const float* const vb = lds + (chunk & 1) * kW8WVBUF + a_lane;
+#pragma unroll
+        for (int pl = 0; pl < 2; pl++) {
+            const float* const vp = vb + (pl * KC) * P;
+            __builtin_amdgcn_sched_barrier(0);
+            // fragment element j = 4 kq + m <- LDS row 8 kq + 2 m + h (= real k 2 j + h), tile lane % 32: variant 4's
+            wf32x4_t lo, hi;
+#pragma unroll
+            for (int m = 0; m < 4; m++) { lo[m] = vp[(2 * m) * P]; hi[m] = vp[(8 + 2 * m) * P]; }
+            u32x2_t l1, l2, l3, h1, h2, h3;
+            split4(lo, l1, l2, l3);
+            split4(hi, h1, h2, h3);
+            const bf16x8_t a[3] = {__builtin_bit_cast(bf16x8_t, (u32x4_t){l1[0], l1[1], h1[0], h1[1]}),
+                                   __builtin_bit_cast(bf16x8_t, (u32x4_t){l2[0], l2[1], h2[0], h2[1]}),
+                                   __builtin_bit_cast(bf16x8_t, (u32x4_t){l3[0], l3[1], h3[0], h3[1]})};
+#pragma unroll
+            for (int j = 0; j < NB; j++) {
+                const bf16x8_t b[3] = {__builtin_bit_cast(bf16x8_t, ub[j][0]), __builtin_bit_cast(bf16x8_t, ub[j][1]),
+                                       __builtin_bit_cast(bf16x8_t, ub[j][2])};
+                // variant 4's order: the leading product, then the corrections smallest first
+                acc[pl][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc[pl][j], 0, 0, 0);
+                acc[pl][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], acc[pl][j], 0, 0, 0);
+                acc[pl][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], acc[pl][j], 0, 0, 0);
+                acc[pl][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], acc[pl][j], 0, 0, 0);
+                acc[pl][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], acc[pl][j], 0, 0, 0);
+                acc[pl][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc[pl][j], 0, 0, 0);
+#pragma unroll
+                for (int q = 0; q < 3; q++) ub[j][q] = u_load(pl == 0 ? chunk : nxt, pl ^ 1, j, q);
+                // (left to itself the scheduler gathers a position's twelve reloads behind its LAST MFMAs, three MFMAs ahead of
+                // the wait for the first of them)
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    };
+
+    // prologue and the two shifts exactly as variant 2
+    const int last = nchunks - 1;
+    fetch_x(0);
+    transform_store(0);
+    __builtin_amdgcn_sched_barrier(0);
+    if (wave >= 4) fetch_x(nchunks > 1 ? 1 : 0);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int j = 0; j < NB; j++)
+#pragma unroll
+        for (int q = 0; q < 3; q++) ub[j][q] = u_load(0, 0, j, q);
+    __builtin_amdgcn_sched_barrier(0);
+    if (wave < 4) {
+        __syncthreads();
+        for (int chunk = 0; chunk < nchunks; chunk++) {
+            const int nxt = chunk < last ? chunk + 1 : last;
+            fetch_x(nxt);
+            __builtin_amdgcn_sched_barrier(0);
+            mfma_phase(chunk, nxt);
+            __builtin_amdgcn_sched_barrier(0);
+            transform_store((chunk + 1) & 1);
+            __syncthreads();
+        }
+    } else {
+        __syncthreads();
+        for (int chunk = 0; chunk < nchunks; chunk++) {
+            const int nxt = chunk < last ? chunk + 1 : last;
+            transform_store((chunk + 1) & 1);
+            __builtin_amdgcn_sched_barrier(0);
+            fetch_x(chunk + 2 < nchunks ? chunk + 2 : last);
+            __builtin_amdgcn_sched_barrier(0);
+            mfma_phase(chunk, nxt);
+            __syncthreads();
+        }
+    }
+
+    // ---- output transform (variant 2's), the 32 tiles x one 64-channel half (accumulator blocks 2 jh, 2 jh + 1) at a time
+    const int h = wave & 1;
+#pragma unroll
+    for (int jh = 0; jh < 2; jh++) {
+        float* const sw = lds + wave * (2 * 32 * HB);
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int tile = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                const int col = j * 32 + (lane & 31);
+                const float ma = acc[0][2 * jh + j][r], mb = acc[1][2 * jh + j][r];
+                sw[tile * HB + col] = h == 0 ? ma + mb : ma;
+                sw[32 * HB + tile * HB + col] = h == 0 ? mb : -(ma + mb);
+            }
+        __syncthreads();
+        {
+            const int tile = tid >> 4, c4 = (tid & 15) * 4;
+            const int tt = tb * TB + tile;
+            if (tt < T) {
+                const int ox = tt % TW, oy = (tt / TW) % TH, on = tt / (TW * TH);
+                const int ch = nb * BN + jh * HB + c4;
+                wf32x4_t pq[4][2];
+#pragma unroll
+                for (int xi = 0; xi < 4; xi++)
+#pragma unroll
+                    for (int jj = 0; jj < 2; jj++)
+                        pq[xi][jj] = *reinterpret_cast<const wf32x4_t*>(lds + ((2 * xi) * 2 + jj) * (32 * HB) + tile * HB + c4) +
+                                     *reinterpret_cast<const wf32x4_t*>(lds + ((2 * xi + 1) * 2 + jj) * (32 * HB) + tile * HB + c4);
+                wf32x4_t bv = {0.f, 0.f, 0.f, 0.f};
+                if (bias) bv = *reinterpret_cast<const wf32x4_t*>(bias + ch);
+#pragma unroll
+                for (int a = 0; a < 2; a++) {
+                    const int oh = 2 * oy + a;
+                    if (oh >= H) continue;
+#pragma unroll
+                    for (int jj = 0; jj < 2; jj++) {
+                        const int ow = 2 * ox + jj;
+                        if (ow >= W) continue;
+                        wf32x4_t v = a == 0 ? (pq[0][jj] + pq[1][jj]) + pq[2][jj] : (pq[1][jj] - pq[2][jj]) - pq[3][jj];
+                        v += bv;
+                        if (relu) {
+#pragma unroll
+                            for (int e = 0; e < 4; e++) v[e] = fmaxf(v[e], 0.0f);
+                        }
+                        *reinterpret_cast<wf32x4_t*>(y + ((size_t)(on * H + oh) * W + ow) * Cout + ch) = v;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
 // ---- variant 3: variant 2 as PERSISTENT workgroups.  With one workgroup per compute unit nothing overlaps a workgroup's
 // prologue (the first pixels come from HBM: 2-3 us) -- a third of a workgroup's time at 64 input channels.  Here a workgroup
 // walks tile blocks tb, tb + G, ... of ONE channel block, and during a block's LAST chunk both shifts fetch the first chunk
@@ -1059,6 +1291,33 @@ static hipError_t launch_wino_w8x3(const float* x, const unsigned short* U3, flo
     return hipGetLastError();
 }
 
+static hipError_t launch_wino_w8x3w(const float* x, const unsigned short* U3, float* y, const float* bias, int N, int H, int W,
+                                    int Cin, int Cout, int relu, int nb_major, hipStream_t st) {
+    const int TH = (H + 1) / 2, TW = (W + 1) / 2, T = N * TH * TW;
+    const long long blocks = (long long)((T + 31) / 32) * (Cout / 128);
+    static std::atomic<unsigned long long> lds_set{0};
+    hipError_t e = allow_lds(reinterpret_cast<const void*>(&winograd_f23_w8x3w_kernel), kW8WLdsBytes, lds_set);
+    if (e != hipSuccess) return e;
+    winograd_f23_w8x3w_kernel<<<(unsigned)blocks, 512, kW8WLdsBytes, st>>>(x, U3, y, bias, H, W, Cin, Cout, TH, TW, T, relu, nb_major);
+    return hipGetLastError();
+}
+
+// What the 128-channel kernel can run at all: its channel blocks, and an activation under the offsets that stand for the padding.
+static bool wino_x3_wide_runs(int N, int H, int W, int Cin, int Cout) {
+    return Cout % 128 == 0 && (double)N * H * W * Cin * 4.0 <= (double)kW8WMaxBytes;
+}
+
+// Whether variant 4 takes the 128-channel workgroups (T tiles): a rule on shapes, so that every run and every rank of a job
+// take the same kernel -- although the two agree bit for bit.
+//   * the launch must fill the chip as winograd.MIN_WORKGROUPS asks of the 64-channel one;
+//   * the 128-channel block's split filter (16 * 128 * Cin * 6 bytes) is what the workgroups of an XCD read over and over.  The
+//     plan was to ask that it fit the 4 MiB L2 beside the pixels (3.1 MB at 256 input channels); at 512 (6.3 MB) the wide
+//     kernel measured 5 % faster all the same (profiles/wino_x3_wide/README.md), so the bound is the largest size MEASURED.
+static bool wino_x3_wide_pays(int Cin, int Cout, int T) {
+    const long long wide_blocks = (long long)((T + 31) / 32) * (Cout / 128);
+    return Cout % 128 == 0 && Cin <= 512 && wide_blocks >= 256;
+}
+
 template <int KC, int NB, int WGS>
 static hipError_t launch_wino(const float* x, const float* U, float* y, const float* bias, int N, int H, int W, int Cin,
                               int Cout, int relu, int nb_major, hipStream_t st) {
@@ -1098,10 +1357,24 @@ hipError_t launch_winograd_f23(const float* x, const float* U, float* y, const f
 }
 
 // variant 4: variant 2 on the bf16 MFMA pipe, U3 = the three bf16 planes of the filter (openpifpaf_amd.winograd.split_filter).
+// It runs on 64-channel or on 128-channel workgroups (the same bits): by wino_x3_wide_pays, or as OPA_WINO_X3_BN = 64 | 128 says
+// -- read on every launch, A/B runs and the tests switch inside one process; it never overrides what wino_x3_wide_runs asks.
+// variant 5: the 128-channel workgroups or nothing.
 // Any other variant is refused (21-23: variant 4's timing experiments, OPA_WINO_DIAG builds only).
 hipError_t launch_winograd_f23x3(const float* x, const unsigned short* U3, float* y, const float* bias, int N, int H, int W,
                                  int Cin, int Cout, int relu, int variant, int nb_major, hipStream_t st) {
-    if (variant == 4) return launch_wino_w8x3<0>(x, U3, y, bias, N, H, W, Cin, Cout, relu, nb_major, st);
+    if (variant == 5)
+        return wino_x3_wide_runs(N, H, W, Cin, Cout) ? launch_wino_w8x3w(x, U3, y, bias, N, H, W, Cin, Cout, relu, nb_major, st)
+                                                     : hipErrorInvalidValue;
+    if (variant == 4) {
+        if (wino_x3_wide_runs(N, H, W, Cin, Cout)) {
+            const char* env = std::getenv("OPA_WINO_X3_BN");
+            const int forced = env && *env ? std::atoi(env) : 0;
+            if (forced == 128 || (forced != 64 && wino_x3_wide_pays(Cin, Cout, N * ((H + 1) / 2) * ((W + 1) / 2))))
+                return launch_wino_w8x3w(x, U3, y, bias, N, H, W, Cin, Cout, relu, nb_major, st);
+        }
+        return launch_wino_w8x3<0>(x, U3, y, bias, N, H, W, Cin, Cout, relu, nb_major, st);
+    }
 #ifdef OPA_WINO_DIAG
     if (variant == 21) return launch_wino_w8x3<1>(x, U3, y, bias, N, H, W, Cin, Cout, relu, nb_major, st);
     if (variant == 22) return launch_wino_w8x3<2>(x, U3, y, bias, N, H, W, Cin, Cout, relu, nb_major, st);

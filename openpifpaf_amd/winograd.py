@@ -12,7 +12,8 @@ import torch
 from . import _lib, fused
 
 # variant -> (K-chunk, 32-wide channel blocks per workgroup): must match launch_winograd_f23 (csrc/winograd.hip)
-VARIANTS = {0: (16, 2), 1: (8, 1), 2: (16, 2), 3: (16, 2), 4: (16, 2)}     # 2: variant 0's tile and filter layout, eight waves
+VARIANTS = {0: (16, 2), 1: (8, 1), 2: (16, 2), 3: (16, 2), 4: (16, 2),     # 2: variant 0's tile and filter layout, eight waves
+            5: (16, 4)}     # 5: variant 4's 128-channel workgroups, forced (variant 4 picks them by the launcher's rule)
 DEFAULT_VARIANT = 2         # eight waves in two shifts (csrc/winograd.hip): 5-8 % faster than variant 0 on every ResNet-50 shape
 X3_VARIANT = 4              # variant 2 on the bf16 MFMA pipe with exactly split operands (opa_conv3x3_winograd_f32x3)
 # OPA_WINO_X3=0: the network's Winograd convolutions stay on variant 2 (float32 MFMA) -- read ONCE, at import; the two round

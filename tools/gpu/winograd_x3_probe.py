@@ -1,7 +1,10 @@
 """Variant 4 of the Winograd kernel (csrc/winograd.hip: F(2x2, 3x3) on the bf16 MFMA pipe with exactly split operands) beside
 variant 2 (float32 MFMA): error against a float64 convolution (max and rms over the output's largest magnitude) on a small
 batch, then time per launch on the ResNet-50 shapes at 641 px / batch 32.
-    python tools/gpu/winograd_x3_probe.py [--batch 32] [--reps 20] [--diag]
+    python tools/gpu/winograd_x3_probe.py [--batch 32] [--reps 20] [--diag] [--bn 64|128] [--rounds 7]
+--bn: instead of all that, variant 4 on its 64-channel and on its 128-channel workgroups (OPA_WINO_X3_BN, which the launcher
+reads on every launch), alternated in this process: --rounds rounds of --reps launches each, min / median / max of the rounds'
+ms per launch, the given width named first (the one a counter pass wants first); bits compared.
 --diag: also variant 4's timing experiments (wrong results) from a library built with -DOPA_WINO_DIAG
 (lib/libopenpifpaf_amd_winodiag.so, built here if it is not there): 21 no split, 22 the leading products only,
 23 no pixel fetches / transforms."""
@@ -15,6 +18,10 @@ ap = argparse.ArgumentParser()
 ap.add_argument('--batch', type=int, default=32)
 ap.add_argument('--reps', type=int, default=20)
 ap.add_argument('--diag', action='store_true')
+ap.add_argument('--bn', type=int, choices=(64, 128))
+ap.add_argument('--rounds', type=int, default=7)
+ap.add_argument('--order', type=int, default=0, choices=(0, 1), help='--bn: the workgroup order (1: channel block major)')
+ap.add_argument('--channels', type=int, nargs='*', default=[64, 128, 256, 512])
 args = ap.parse_args()
 if args.diag:
     from openpifpaf_amd import build  # noqa: E402
@@ -33,7 +40,42 @@ def errors(y, ref):
     return d.abs().max().item() / s, d.pow(2).mean().sqrt().item() / s
 
 
-for (C, H) in ((64, 321), (128, 161), (256, 81), (512, 41)):
+SHAPES = [(C, H) for (C, H) in ((64, 321), (128, 161), (256, 81), (512, 41)) if C in args.channels]
+
+
+def bn_ab(C, H):
+    """One shape on both workgroup widths, alternated round by round."""
+    w = torch.randn((C, C, 3, 3), device='cuda') * (2.0 / (9 * C)) ** 0.5
+    u3 = winograd.split_filter(w)
+    x = torch.randn((args.batch, C, H, H), device='cuda').contiguous(memory_format=torch.channels_last)
+    widths = [bn for bn in (args.bn, 192 - args.bn) if C % bn == 0]
+    outs = {bn: torch.empty_like(x) for bn in widths}
+    times = {bn: [] for bn in widths}
+    for _ in range(args.rounds):
+        for bn in widths:
+            os.environ['OPA_WINO_X3_BN'] = str(bn)
+            times[bn].append(time_ms(lambda: winograd.conv3x3_x3(x, u3, C, order=args.order, out=outs[bn]), args.reps))
+    del os.environ['OPA_WINO_X3_BN']
+    line = 'C %3d %3dx%3d B%d WGs %5d' % (C, H, H, args.batch, winograd.workgroups(x.shape, C, 4))
+    for bn in sorted(widths):
+        t = sorted(times[bn])
+        line += ' | %3d: min %.4f med %.4f max %.4f' % (bn, t[0], t[len(t) // 2], t[-1])
+    if len(widths) == 2:
+        t64, t128 = sorted(times[64]), sorted(times[128])
+        med = t128[len(t128) // 2]
+        line += ' | med/med %+5.1f %% %s | bits %s' % (100.0 * (med / t64[len(t64) // 2] - 1.0),
+                                                     'WIDE BELOW THE NARROW MINIMUM' if med < t64[0] else 'not below the narrow minimum',
+                                                     'equal' if torch.equal(outs[64].view(torch.int32), outs[128].view(torch.int32)) else 'DIFFER')
+    print(line, flush=True)
+
+
+if args.bn:
+    print('# B %d, order %d, %d rounds of %d launches per width, alternating; ms per launch' % (args.batch, args.order, args.rounds, args.reps), flush=True)
+    for (C, H) in SHAPES:
+        bn_ab(C, H)
+    sys.exit(0)
+
+for (C, H) in SHAPES:
     w = torch.randn((C, C, 3, 3), device='cuda') * (2.0 / (9 * C)) ** 0.5
     u, u3 = winograd.transform_filter(w, 2), winograd.split_filter(w)
     xs = torch.randn((2, C, H, H), device='cuda').contiguous(memory_format=torch.channels_last)
