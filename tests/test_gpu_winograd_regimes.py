@@ -1,8 +1,12 @@
-"""Every variant of csrc/winograd.hip (0-3 through ``winograd.conv3x3``, 4 through ``winograd.conv3x3_x3``) in both workgroup
+"""Every variant of csrc/winograd.hip (0-3 through ``winograd.conv3x3``, 4 and 5 through ``winograd.conv3x3_x3``) in both workgroup
 orders at ``winograd_common.WINO_REGIMES`` -- small shapes that together reach every regime of the launch: the three cases of the
 XCD remap, a last tile block of 1 / 32 / 33 / 64 tiles, H and W of 1, 2, odd and even, blocks that hold many images, waves without a
 border tile, 1 / 2 / 3 / 16 / 32 K-chunks, and variant 3 walking a second tile block.  tests/test_winograd_cases.py says which shape
 reaches what, checks the bit budget of the integer case and shows mutants of the walk failing it.
+Variant 5 (``winograd_f23_w8x3w_kernel``, 32 tiles x 128 channels) runs at ``winograd_common.WIDE_REGIMES``, the same classes for
+its own blocks (a last block of 1 / 31 / 32 tiles, eight images to a block, an odd count of channel blocks).  Variant 4 would take
+that kernel by the launcher's rule where it pays (``WALK``); every test here holds it to its 64-channel kernel with
+``OPA_WINO_X3_BN=64``, so that the kernel that runs is the one ``winograd_common`` models for the variant, whatever the rule says.
   (a) known answer: dense integer operands inside the budget in which float32 is exact -- the float64 convolution, bit for bit;
   (b) the same through interior views of NaN-filled buffers: nothing read that is not selected away, nothing written outside;
   (c) invariances on N(0, 1) data, bit for bit: relaunch, workgroup order, an image alone, the batch reversed, variant 3 = variant 2;
@@ -30,6 +34,12 @@ PATTERN = 0x7FC0BEEF                                    # a NaN the kernels neve
 CASES = [pytest.param(v, s, id='v%d-%s' % (v, 'x'.join(map(str, s)))) for v in wc.VARIANTS for s in wc.shapes_of(v)]
 
 
+@pytest.fixture(autouse=True)
+def _variant_4_on_its_64_channel_kernel(monkeypatch):
+    """The launcher reads the variable on every launch; variant 5 is the 128-channel kernel whatever it says."""
+    monkeypatch.setenv('OPA_WINO_X3_BN', '64')
+
+
 def _cl(t):
     return t.cuda().contiguous(memory_format=CL)
 
@@ -42,15 +52,15 @@ def _cus():
 def _filter(f, variant):
     from openpifpaf_amd import winograd
     f = f.cuda()
-    return winograd.split_filter(f) if variant == 4 else winograd.transform_filter(f, variant)
+    return winograd.split_filter(f) if variant >= 4 else winograd.transform_filter(f, variant)
 
 
 def _launch(x_dev, u, c_out, variant, order, bias=None, relu=False, out=None):
     """One launch on operands already on the device -> the device tensor."""
     from openpifpaf_amd import winograd
     with torch.no_grad():
-        if variant == 4:
-            return winograd.conv3x3_x3(x_dev, u, c_out, bias=bias, relu=relu, order=order, out=out)
+        if variant >= 4:
+            return winograd.conv3x3_x3(x_dev, u, c_out, bias=bias, relu=relu, variant=variant, order=order, out=out)
         return winograd.conv3x3(x_dev, u, c_out, bias=bias, relu=relu, variant=variant, order=order, out=out)
 
 
@@ -226,14 +236,15 @@ ROUNDINGS = 9
 @pytest.mark.parametrize('variant,shape', CASES)
 def test_accuracy_in_the_componentwise_measure(variant, shape, order):
     """N(0, 1) data with bias against the float64 convolution, ``x3_common.err_c`` with S = ``winograd_scale`` + |bias|.
-    (i) ``err_c <= (R + C_in) 2^-24`` (+ 2^-23 for variant 4's three dropped products).  C_in = nchunks x KC roundings in the
+    (i) ``err_c <= (R + C_in) 2^-24`` (+ 2^-23 for variant 4's three dropped products; variant 5 promises variant 4's bits and
+        takes its bars unchanged).  C_in = nchunks x KC roundings in the
         channel sum (one per fma of the MFMA's k-ordered chain), and outside it, counted from the kernels, R = 9: two in
         ``B^T d B`` (one addition per pass and element), one of U (float64 -> float32, once), two in the nu-sum (variant 0:
         (m0 + m1) + m2 in registers; variants 2-4: ma + mb in the wave, the wave pair's halves added from LDS), two in the
         xi-sum ((P0 + P1) + P2), one adding the bias -- eight, each at most 2^-24 of the magnitudes it adds, which S sums up --
         and one for every second-order term ((R + C_in)^2 2^-48 / 2 < 2^-24 up to C_in = 5000).
     (ii) the rms of the same ratio is at most 2 x the rms of a float32 restatement on the CPU (``winograd_common.model_f32``:
-        transforms in float32, U rounded once, channels added in k order; ``winograd_model_f32`` for variant 4) -- 2 is what
+        transforms in float32, U rounded once, channels added in k order; ``winograd_model_f32`` for variants 4 and 5) -- 2 is what
         ``trunk_common.report`` grants another summation order.  Where C_out > 192 both are taken over every eighth channel."""
     _premise(variant, shape)
     x, f, bias, ref, S = wc.winograd_randn_case(shape)
@@ -242,8 +253,8 @@ def test_accuracy_in_the_componentwise_measure(variant, shape, order):
     ch = wc.sampled_channels(shape)
     k_max, _ = wc.max_rms(got, ref, S)
     _, k_rms = wc.max_rms(got[:, ch], ref[:, ch], S[:, ch])
-    m_max, m_rms = wc.max_rms(wc.model_f32(shape, variant == 4), ref[:, ch], S[:, ch])
-    bound = (ROUNDINGS + shape[1]) * 2.0 ** -24 + (xc.EXTRA[6] if variant == 4 else 0.0)
+    m_max, m_rms = wc.max_rms(wc.model_f32(shape, variant >= 4), ref[:, ch], S[:, ch])
+    bound = (ROUNDINGS + shape[1]) * 2.0 ** -24 + (xc.EXTRA[6] if variant >= 4 else 0.0)
     print('WINOREG v%d order %d %-18s | model max %.3e rms %.3e | kernel max %.3e rms %.3e | rms ratio %.2f | bound %.3e %s'
           % (variant, order, 'x'.join(map(str, shape)), m_max, m_rms, k_max, k_rms, k_rms / max(m_rms, 1e-30), bound,
              'ok' if k_max <= bound and k_rms <= 2 * m_rms else 'ABOVE'))

@@ -2,7 +2,14 @@
 32 tiles x 128 output channels) against the 64-channel ones (variant 4 held narrow with ``OPA_WINO_X3_BN=64``).  Every output
 element sums the same products in the same order in both, so the two results are equal BIT FOR BIT (NaNs compared as bit
 patterns) -- and, beside that, within the bound of ``test_gpu_winograd_x3.py`` of a float64 convolution.  Shapes: the smallest
-that reach each path of the kernel (named in ``SHAPES``)."""
+that reach each path of the kernel (named in ``SHAPES``).
+
+The reference here is the other kernel, which shares the filter operand and the transforms' text with this one.  The checks that
+are independent of it live elsewhere: tests/test_gpu_winograd_regimes.py runs variant 5 at ``winograd_common.WIDE_REGIMES`` (every
+regime of its own launch; the dense integer case bit for bit against the float64 convolution, guard bands, invariances, the
+componentwise error bound), and tests/test_gpu_x3_edges.py at ``x3_common.WINO_WIDE`` (power-of-two taps and scalings, the wide
+dynamic range, non-finite pixels, filters and biases against torch's float32 convolution).  This file keeps what only it can
+say: that the two kernels agree in every bit, and that the launcher's rule and its override choose between equal kernels."""
 import pytest
 import torch
 

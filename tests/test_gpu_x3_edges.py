@@ -1,5 +1,5 @@
-"""The split-operand kernels (csrc/gemm_f32x3.hip: plain, pair, implicit 3x3, stem rows, unit / head; csrc/winograd.hip variant 4)
-on the data the other suites never use, with six and with nine terms:
+"""The split-operand kernels (csrc/gemm_f32x3.hip: plain, pair, implicit 3x3, stem rows, unit / head; csrc/winograd.hip variant 4 on its 64-channel kernel
+and variant 5, the 128-channel one, each named by the test and not picked by the launcher's rule) on the data the other suites never use, with six and with nine terms:
   (a) known answers, bit for bit -- selection weights, one-hot activations, integers inside the bit budget;
   (b) power-of-two scaling of the operands scales the result exactly;
   (c) a wide dynamic range against float64 in the COMPONENTWISE measure ``|got - ref| / (sum_k |a||w| + |bias| + |res|)``;
@@ -132,11 +132,25 @@ def _torch32(spec, nat, w, bias, res=None, a_bias=None, relu=False):
     return xc.rows_of(out)
 
 
+@pytest.fixture(autouse=True)
+def _winograd_variant_4_on_its_64_channel_kernel(monkeypatch):
+    """Variant 4 takes the 128-channel kernel where the launcher's rule says it pays; the Winograd tests here name the kernel they
+    run (``_wino_variant``) instead of following the rule.  The launcher reads the variable on every launch."""
+    monkeypatch.setenv('OPA_WINO_X3_BN', '64')
+
+
+def _wino_variant(shape):
+    """Variant 4 (64-channel workgroups, pinned above) on ``x3_common.WINO``, variant 5 (128-channel ones) on ``WINO_WIDE``."""
+    assert (shape in xc.WINO) != (shape in xc.WINO_WIDE)
+    return 5 if shape in xc.WINO_WIDE else 4
+
+
 def _run_wino(x, f, bias, relu, order):
     from openpifpaf_amd import winograd
+    variant = _wino_variant((x.shape[0], x.shape[1], f.shape[0], x.shape[2], x.shape[3]))
     with torch.no_grad():
         out = winograd.conv3x3_x3(_cl(x), winograd.split_filter(f.cuda()), f.shape[0], bias=None if bias is None else bias.cuda(),
-                                  relu=relu, order=order)
+                                  relu=relu, variant=variant, order=order)
         torch.cuda.synchronize()
     assert out.is_contiguous(memory_format=CL)
     return out.cpu().contiguous()
@@ -233,7 +247,7 @@ def test_integer_operands_give_the_int64_result(spec, terms, with_res, with_pro)
 
 
 @pytest.mark.parametrize('order', [0, 1])
-@pytest.mark.parametrize('shape', xc.WINO, ids=str)
+@pytest.mark.parametrize('shape', xc.WINO + xc.WINO_WIDE, ids=str)
 def test_winograd_power_of_two_taps_on_16_bit_integers(shape, order):
     """One power-of-two tap per output channel on 16-bit integer inputs: ``out[b, o, y, x] = 2^p x[b, c(o), y + r - 1, x + s - 1]``,
     zero in the padding -- every intermediate of the transforms fits float32 (asserted in test_x3_cases.py)."""
@@ -266,7 +280,7 @@ def test_power_of_two_scaling_is_exact(spec, terms):
 
 
 @pytest.mark.parametrize('order', [0, 1])
-@pytest.mark.parametrize('shape', xc.WINO, ids=str)
+@pytest.mark.parametrize('shape', xc.WINO + xc.WINO_WIDE, ids=str)
 def test_winograd_power_of_two_scaling_is_exact(shape, order):
     x, f, bias = xc.winograd_randn_case(shape, 8)
     for relu in (False, True):
@@ -309,7 +323,7 @@ def test_wide_dynamic_range_componentwise(spec, terms, relu):
 
 
 @pytest.mark.parametrize('relu', [False, True], ids=['none', 'relu'])
-@pytest.mark.parametrize('shape', xc.WINO, ids=str)
+@pytest.mark.parametrize('shape', xc.WINO + xc.WINO_WIDE, ids=str)
 def test_winograd_wide_dynamic_range(shape, relu):
     """Inputs inside a window span 2^+-4, only the scale per image keeps its 2^+-40, weights 2^+-6.  Winograd's transforms add
     across the taps and across the 4x4 tile and the output transform takes the sums apart again, so the error is measured
@@ -505,7 +519,19 @@ def test_winograd_non_finite_inputs_stay_in_their_windows(order):
     that an output's window does not hold never enters that output.  So the contract is the GEMM modes': with ``ref32`` torch's
     float32 convolution, where it is finite the result is bit for bit the clean run's -- in the same tile too -- and where it is
     NaN or +-Inf the result is NaN or that infinity (an infinite V leaves the split as NaN); with ReLU NaN, 0 or +Inf."""
-    shape = xc.WINO[0]
+    _winograd_non_finite_inputs(xc.WINO[0], order)
+
+
+@pytest.mark.parametrize('order', [0, 1])
+def test_winograd_wide_non_finite_inputs_stay_in_their_windows(order):
+    """The same contract, against the same references (torch's float32 convolution, ``nonfinite_class``), for variant 5.  Its
+    padding is no select but a load past the buffer descriptor's range: the corner pixel and the last pixel are where that zero
+    meets an infinity in ``B^T d B`` -- and must stay a zero (Inf - 0, never Inf x 0 or Inf - Inf) wherever the reference is
+    finite.  40 tiles in two blocks of 32: the planted pixels lie in block 0 (tile 0), block 0's last tiles and block 1."""
+    _winograd_non_finite_inputs(xc.WINO_WIDE[0], order)
+
+
+def _winograd_non_finite_inputs(shape, order):
     x, f, bias = xc.winograd_randn_case(shape, 15)
     B, C, H, W = x.shape
     places = [((0, 3, 0, 0), NAN), ((0, C - 1, H - 1, W - 1), INF), ((1, 0, 3, 4), -INF)]
@@ -528,7 +554,18 @@ def test_winograd_non_finite_filter_and_bias_stay_in_their_channels(order):
     a non-finite tap over the sixteen positions of that (c_out, c_in) pair and nowhere else: the output CHANNEL is non-finite, at
     the borders too (where the tap meets the padding the im2col reference has 0 x Inf = NaN as well); every other channel is
     bit for bit the clean run's."""
-    shape = xc.WINO[0]
+    _winograd_non_finite_filter_and_bias(xc.WINO[0], order)
+
+
+@pytest.mark.parametrize('order', [0, 1])
+def test_winograd_wide_non_finite_filter_and_bias_stay_in_their_channels(order):
+    """The same for variant 5, whose workgroup holds all 128 channels as four accumulator blocks of 32 and rotates the filter
+    fragments through four register sets: channels 1 and 3 (block 0), 64 (block 2) and 127 (block 3) are non-finite, every other
+    channel -- in the same block, the same fragment, the same 64-channel output half -- is bit for bit the clean run's."""
+    _winograd_non_finite_filter_and_bias(xc.WINO_WIDE[0], order)
+
+
+def _winograd_non_finite_filter_and_bias(shape, order):
     x, f, bias = xc.winograd_randn_case(shape, 16)
     B, C, H, W = x.shape
     O = f.shape[0]

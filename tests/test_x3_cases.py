@@ -122,7 +122,7 @@ def test_integer_cases_stay_inside_their_bit_budget(spec, with_res, with_pro):
     assert torch.equal(xc.ref64(a, w, bias, res, ab), full.double()) and float(full.abs().max()) < 2.0 ** 24
 
 
-@pytest.mark.parametrize('shape', xc.WINO, ids=str)
+@pytest.mark.parametrize('shape', xc.WINO + xc.WINO_WIDE, ids=str)
 def test_winograd_integer_case_stays_inside_its_bit_budget(shape):
     """16-bit inputs, one power-of-two tap per output channel: the input transform (both passes), U, every partial sum of U V over
     the channels and every partial sum of the output transform are multiples of 2^-2 below 2^24; U is ONE piece, so the six kept
@@ -168,7 +168,7 @@ def test_scaling_cases_neither_overflow_nor_underflow(spec, s, t):
 
 
 @pytest.mark.parametrize('s,t', xc.SCALINGS)
-@pytest.mark.parametrize('shape', xc.WINO, ids=str)
+@pytest.mark.parametrize('shape', xc.WINO + xc.WINO_WIDE, ids=str)
 def test_winograd_scaling_cases_neither_overflow_nor_underflow(shape, s, t):
     """V is a sum of inputs (a multiple of their lowest bit), U = G g G^T rounded to float32 once: the same condition on (x, U)."""
     x, f, bias = xc.winograd_randn_case(shape, 8)
@@ -294,7 +294,7 @@ def _wino_case(shape):
     return x, f, ref, S, xc.winograd_scale(x, f)
 
 
-@pytest.mark.parametrize('shape', xc.WINO, ids=str)
+@pytest.mark.parametrize('shape', xc.WINO + xc.WINO_WIDE, ids=str)
 def test_winograd_measure_is_the_algorithms_own_and_its_bar_can_be_met(shape):
     """F(2x2, 3x3) multiplies ``B^T d B`` with ``G g G^T``: sums over the 4x4 tile and over all nine taps, which the output
     transform takes apart again.  Against the convolution's own ``S`` (the 3x3 window, zero outside the image) NO float32

@@ -1,6 +1,6 @@
 """Shared by the Winograd regime tests (test_winograd_cases.py on the CPU, test_gpu_winograd_regimes.py on the GPU): a model of
 the launch of every variant of csrc/winograd.hip (``wino_geometry``: read off ``launch_wino*`` and the kernels' first lines), the
-shapes that together reach every regime of that launch (``WINO_REGIMES``), the dense integer case whose convolution every
+shapes that together reach every regime of that launch (``WINO_REGIMES``; ``WIDE_REGIMES`` for variant 5), the dense integer case whose convolution every
 variant must return bit for bit, the kernels' walk over tile blocks restated in float64 with the mutants the CPU test applies to
 it (``tile_walk``), and the float32 restatement the accuracy bar is taken from (``model_f32``).  Everything from a seeded
 ``torch.Generator``, everything on the CPU."""
@@ -10,10 +10,11 @@ import torch
 
 import x3_common as xc
 
-VARIANTS = (0, 1, 2, 3, 4)
-KC = {0: 16, 1: 8, 2: 16, 3: 16, 4: 16}                # input channels per K-chunk
-BN = {0: 64, 1: 32, 2: 64, 3: 64, 4: 64}               # output channels per workgroup
-WAVE_TILES = {0: 16, 1: 16, 2: 8, 3: 8, 4: 8}          # consecutive tiles one wave stages (tile_l = tid >> 2 / tid >> 3)
+VARIANTS = (0, 1, 2, 3, 4, 5)                          # 4: held to its 64-channel kernel by the GPU tests; 5: the 128-channel one
+KC = {0: 16, 1: 8, 2: 16, 3: 16, 4: 16, 5: 16}         # input channels per K-chunk
+BN = {0: 64, 1: 32, 2: 64, 3: 64, 4: 64, 5: 128}       # output channels per workgroup
+TB = {0: 64, 1: 64, 2: 64, 3: 64, 4: 64, 5: 32}        # tiles per workgroup: the tile block
+WAVE_TILES = {0: 16, 1: 16, 2: 8, 3: 8, 4: 8, 5: 4}    # consecutive tiles one wave stages (tile_l = tid >> 2 / tid >> 3 / tid >> 4)
 ONE, BELOW8, MIXED, MULTIPLE8 = 'nwg = 1', 'nwg < 8', 'nwg = 8q + r', 'nwg = 8q'
 
 # (B, C_in, C_out, H, W).  The table of which shape reaches which class for which variant is in test_winograd_cases.py, and
@@ -40,6 +41,25 @@ WINO_REGIMES = [
     (1, 128, 64, 3, 4),           # 16 chunks of 8, two channel blocks
 ]
 NONFINITE_SHAPE = (2, 32, 64, 7, 9)
+# Variant 5 (``winograd_f23_w8x3w_kernel``: 32 tiles x 128 channels per workgroup, grid ceil(T / 32) x C_out / 128) has a list of its
+# own: C_out a multiple of 128, and the tile counts that matter taken modulo 32.
+WIDE_REGIMES = [
+    (1, 16, 128, 1, 1),           # one tile, one workgroup, one chunk; H = W = 1; T % 32 = 1
+    (2, 32, 128, 8, 7),           # T = 32: one full tile block
+    (3, 16, 128, 2, 21),          # T = 33: the second block holds one tile; H = 2; three images in block 0
+    (1, 16, 128, 2, 62),          # T = 31: the block's last tile is a clamped duplicate; W even
+    (2, 32, 128, 7, 9),           # x3_common.WINO_WIDE[0]: two chunks, 40 tiles in 2 blocks; the shape of the non-finite tests
+    (2, 32, 256, 7, 9),           # 2 tile blocks x 2 channel blocks: nwg = 4
+    (3, 48, 384, 9, 11),          # 90 tiles in 3 blocks x 3 channel blocks: nwg = 9 = 8 + 1; three chunks; H, W odd
+    (5, 48, 384, 16, 13),         # 280 tiles in 9 blocks x 3: nwg = 27 = 24 + 3; images straddle the blocks; H even
+    (1, 512, 128, 5, 5),          # 32 chunks
+    (1, 256, 256, 6, 6),          # 16 chunks, two channel blocks
+    WALK,                         # 74 blocks x 4: nwg = 296 = 8 x 37 (where variant 4's rule takes this kernel)
+    (2, 16, 128, 5, 1),           # W = 1 under H > 1
+    (2, 32, 128, 1, 6),           # H = 1 under W > 1
+    (9, 16, 128, 3, 3),           # 4 tiles per image: a block holds 8 images, the 9th starts the next
+    (1, 16, 128, 6, 80),          # tiles 44..47 (and more) lie inside the image: waves of 4 tiles without a border tile
+]
 
 
 def supports(variant, shape):
@@ -47,7 +67,7 @@ def supports(variant, shape):
 
 
 def shapes_of(variant):
-    return [s for s in WINO_REGIMES if supports(variant, s)]
+    return [s for s in (WIDE_REGIMES if variant == 5 else WINO_REGIMES) if supports(variant, s)]
 
 
 def logical_of(block, nwg):
@@ -63,17 +83,18 @@ def _tile_is_inside(t, H, W, TH, TW):
 
 def wino_geometry(shape, variant, order=0, cus=256):
     """The launch of ``shape`` = (B, C_in, C_out, H, W) by ``variant`` on a part with ``cus`` compute units -> dict:
-      T, n_tb, n_nb, nwg, xcd (ONE / BELOW8 / MIXED / MULTIPLE8), t_mod (T % 64), nchunks,
+      T, n_tb, n_nb, nwg, xcd (ONE / BELOW8 / MIXED / MULTIPLE8), t_mod (T % the tile block: 64, variant 5: 32), nchunks,
       interior_wave: some wave of some block stages no border tile (clamped duplicates past T included, as the kernel sees them),
-      images_per_block: the most images one 64-tile block holds tiles of,
+      images_per_block: the most images one tile block holds tiles of,
       blocks: ``blocks[blockIdx.x]`` = (channel block, [tile blocks this workgroup computes, in order]),
       variant 3 only: G, longest_walk, shortest_walk."""
     B, cin, cout, H, W = shape
     assert supports(variant, shape), (variant, shape)
     TH, TW = (H + 1) // 2, (W + 1) // 2
     T = B * TH * TW
-    n_tb, n_nb = (T + 63) // 64, cout // BN[variant]
-    geo = {'T': T, 'TH': TH, 'TW': TW, 'n_tb': n_tb, 'n_nb': n_nb, 't_mod': T % 64, 'nchunks': cin // KC[variant]}
+    tbs = TB[variant]
+    n_tb, n_nb = (T + tbs - 1) // tbs, cout // BN[variant]
+    geo = {'T': T, 'TH': TH, 'TW': TW, 'n_tb': n_tb, 'n_nb': n_nb, 't_mod': T % tbs, 'nchunks': cin // KC[variant]}
     if variant == 3:
         G = min(max(cus // n_nb, 1), n_tb)
         nwg = G * n_nb
@@ -91,9 +112,9 @@ def wino_geometry(shape, variant, order=0, cus=256):
         else:
             blocks.append((logical % n_nb, [logical // n_nb]))
     per = WAVE_TILES[variant]
-    interior = any(all(_tile_is_inside(min(tb * 64 + w * per + i, T - 1), H, W, TH, TW) for i in range(per))
-                   for tb in range(n_tb) for w in range(64 // per))
-    images = max(len({t // (TH * TW) for t in range(tb * 64, min(tb * 64 + 64, T))}) for tb in range(n_tb))
+    interior = any(all(_tile_is_inside(min(tb * tbs + w * per + i, T - 1), H, W, TH, TW) for i in range(per))
+                   for tb in range(n_tb) for w in range(tbs // per))
+    images = max(len({t // (TH * TW) for t in range(tb * tbs, min(tb * tbs + tbs, T))}) for tb in range(n_tb))
     geo.update(nwg=nwg, xcd=ONE if nwg == 1 else BELOW8 if nwg < 8 else MULTIPLE8 if nwg % 8 == 0 else MIXED,
                interior_wave=interior, images_per_block=images, blocks=blocks)
     return geo
@@ -125,6 +146,21 @@ CLASSES = {
     '32 chunks': lambda s, g: g['nchunks'] == 32,
     '16 chunks x 2+ channel blocks': lambda s, g: g['nchunks'] == 16 and g['n_nb'] >= 2,
 }
+# variant 5: the tile counts modulo its 32-tile block (a block of 1 tile, of 31 with one clamped duplicate, a full one), eight images
+# of 4 tiles to a block, and an odd count of 128-channel blocks (the split filter is laid out in 64-channel blocks 2 nb, 2 nb + 1)
+_NARROW_ONLY = ('T % 64 = 1', 'T % 64 = 32', 'T % 64 = 33', 'T % 64 = 0', '3 x 3 images, 17+ of them')
+WIDE_CLASSES = {name: holds for name, holds in CLASSES.items() if name not in _NARROW_ONLY}
+WIDE_CLASSES.update({
+    'T % 32 = 1': lambda s, g: g['t_mod'] == 1,
+    'T % 32 = 31': lambda s, g: g['t_mod'] == 31,
+    'T % 32 = 0': lambda s, g: g['t_mod'] == 0,
+    '3 x 3 images, 9+ of them': lambda s, g: s[3:] == (3, 3) and s[0] >= 9 and g['images_per_block'] == 8,
+    'an odd number of channel blocks': lambda s, g: g['n_nb'] >= 3 and g['n_nb'] % 2 == 1,
+})
+
+
+def classes_of(variant):
+    return WIDE_CLASSES if variant == 5 else CLASSES
 # variant 3 on 256 compute units: a second block is walked, the last (partial) block as a second block, and some workgroup walks one
 WALK_CLASS = 'variant 3 walks a second block'
 
@@ -136,13 +172,13 @@ def walks_a_second_block(shape, geo):
 
 
 def reached(variant, cus=256):
-    """class name -> the shapes of ``WINO_REGIMES`` that reach it under ``variant``."""
-    out = {name: [] for name in CLASSES}
+    """class name -> the shapes of ``shapes_of(variant)`` that reach it under ``variant``."""
+    out = {name: [] for name in classes_of(variant)}
     if variant == 3:
         out[WALK_CLASS] = []
     for shape in shapes_of(variant):
         geo = wino_geometry(shape, variant, 0, cus)
-        for name, holds in CLASSES.items():
+        for name, holds in classes_of(variant).items():
             if holds(shape, geo):
                 out[name].append(shape)
         if variant == 3 and walks_a_second_block(shape, geo):
@@ -175,6 +211,20 @@ BITS = {
     (1, 8, 32, 2, 3): 12,
     (3, 24, 64, 9, 11): 12,
     (1, 128, 64, 3, 4): 10,
+    # WIDE_REGIMES ((2, 16, 128, 5, 1) and WALK are above)
+    (1, 16, 128, 1, 1): 12,
+    (2, 32, 128, 8, 7): 12,
+    (3, 16, 128, 2, 21): 12,
+    (1, 16, 128, 2, 62): 12,
+    (2, 32, 128, 7, 9): 12,
+    (2, 32, 256, 7, 9): 12,
+    (3, 48, 384, 9, 11): 12,
+    (5, 48, 384, 16, 13): 12,
+    (1, 512, 128, 5, 5): 9,
+    (1, 256, 256, 6, 6): 10,
+    (2, 32, 128, 1, 6): 12,
+    (9, 16, 128, 3, 3): 12,
+    (1, 16, 128, 6, 80): 12,
 }
 BUDGET = 2.0 ** 22                                      # 2^24 quarter-units
 BIAS_BITS = 20                                          # |y| < 2^22 and |bias| < 2^20: the sum stays an exact float32
@@ -217,12 +267,25 @@ def winograd_randn_case(shape, seed=22):
 
 MUTANTS = ('last chunk skipped', 'chunks 0 and 1 swapped on V only', 'tile index clamped to T - 2',
            'second output half of the last block not written', 'tile of image n read from image n - 1',
-           'padding select dropped for one border pixel', 'block tb + G of the walk skipped')
+           'padding select dropped for one border pixel', 'block tb + G of the walk skipped',
+           "chunk c's filter used with chunk c + 1's pixels for one position",
+           'an out-of-range offset lands in range for one border pixel')
+# Variant 5 has no padding select: the pixel's offset is out of its buffer descriptor's range, and MUTANTS[8] takes MUTANTS[5]'s
+# place.  Its 'second output half' (MUTANTS[3]) is the second 64 CHANNELS of the block, over all 32 tiles.  MUTANTS[7] is its
+# filter rotation losing one reload (fragment (pl ^ 1, j) of the next chunk): every variant's walk can express it.
+ROTATION_POSITION = (1, 1)                              # the position (xi, nu) whose filter stays a chunk behind: wave 2's second
+                                                        # (d1 + d2 along both axes: not zero by the padding even where H = W = 1)
 
 
-def mutant_applies(mutant, shape, geo):
+def mutant_applies(mutant, shape, geo, variant=2):
     """Whether the mutated code path is executed at all at this shape (where it is not, the mutant is the kernel itself)."""
-    if mutant == MUTANTS[1]:
+    if mutant == MUTANTS[5]:
+        return variant != 5
+    if mutant == MUTANTS[8]:
+        return variant == 5
+    if mutant == MUTANTS[3] and variant == 5:
+        return True                                     # the second channel half of a block is always written
+    if mutant in (MUTANTS[1], MUTANTS[7]):
         return geo['nchunks'] >= 2
     if mutant == MUTANTS[2]:
         return geo['T'] >= 2
@@ -235,53 +298,83 @@ def mutant_applies(mutant, shape, geo):
     return True
 
 
+ROW_OUT, COL_OUT = 0x80000000, 0x40000000              # variant 5's byte offsets of a row / a column in the padding
+
+
+def _pixels_by_select(n, r, c, H, W):
+    """Variants 0-4: offsets clamped into the image, and a select that replaces what lies in the padding by zero.
+    -> (valid [tiles, 4, 4], pixel index [tiles, 4, 4])."""
+    valid = ((r >= 0) & (r < H))[:, :, None] & ((c >= 0) & (c < W))[:, None, :]
+    return valid, ((n[:, None] * H + r.clamp(0, H - 1)) * W)[:, :, None] + c.clamp(0, W - 1)[:, None, :]
+
+
+def _pixels_by_range_check(n, r, c, H, W, C, images):
+    """Variant 5: a row or a column in the padding gets a byte offset that, with any partner, lies past the ``images * H * W * C * 4``
+    bytes of the buffer descriptor (the kernel computes ``images`` as T / (TH * TW)); a load past the range returns zero and reads
+    nothing.  The 32-bit sum of the two offsets, as the kernel forms it.  -> (valid, pixel index; 0 where nothing is read)."""
+    rowoff = torch.where((r >= 0) & (r < H), (n[:, None] * H + r) * W * C * 4, torch.tensor(ROW_OUT))
+    coloff = torch.where((c >= 0) & (c < W), c * C * 4, torch.tensor(COL_OUT))
+    off = (rowoff[:, :, None] + coloff[:, None, :]) & 0xFFFFFFFF
+    valid = off + C * 4 <= images * H * W * C * 4
+    return valid, torch.where(valid, off // (C * 4), torch.zeros((), dtype=off.dtype))
+
+
 def tile_walk(x, f, variant=2, order=0, cus=256, mutant=None):
     """What the kernels do, workgroup by workgroup, in float64: every ``blockIdx.x`` of the launch takes its channel block and its
-    tile blocks from ``wino_geometry``; a block's 64 tiles are clamped to T - 1; each tile's 4x4 pixels are read at offsets clamped
-    into the image and replaced by zero where they lie in the padding; V = B^T d B; the products with U = G g G^T are added chunk
-    by chunk; the output transform runs in two halves of 32 tiles and writes the tiles below T, the pixels inside the image.
-    Unwritten outputs stay NaN.  ``mutant``: one of ``MUTANTS``.  -> float64 [B, C_out, H, W]."""
+    tile blocks from ``wino_geometry``; a block's 64 tiles (variant 5: 32) are clamped to T - 1; each tile's 4x4 pixels are read at
+    offsets clamped into the image and replaced by zero where they lie in the padding (variant 5: at offsets that are out of the
+    descriptor's range in the padding, where nothing is read and the load is zero); V = B^T d B; the products with U = G g G^T
+    are added chunk by chunk; the output transform runs in two halves of 32 tiles (variant 5: of 64 channels, over all 32 tiles)
+    and writes the tiles below T, the pixels inside the image.  Unwritten outputs stay NaN.  ``mutant``: one of ``MUTANTS``.
+    -> float64 [B, C_out, H, W]."""
     B, C, H, W = x.shape
     O = f.shape[0]
     geo = wino_geometry((B, C, O, H, W), variant, order, cus)
-    T, TH, TW, kc, bn = geo['T'], geo['TH'], geo['TW'], KC[variant], BN[variant]
+    T, TH, TW, kc, bn, tbs = geo['T'], geo['TH'], geo['TW'], KC[variant], BN[variant], TB[variant]
+    wide = variant == 5
     bt, at, gm = (torch.tensor(m, dtype=torch.float64) for m in (xc._BT, xc._AT, xc._GM))
     u = torch.einsum('ar,oirs,bs->aboi', gm, f.double(), gm)                 # [4, 4, O, C]
     rows = x.double().permute(0, 2, 3, 1).reshape(B * H * W, C)              # NHWC pixel rows
     y = torch.full((B, H, W, O), float('nan'), dtype=torch.float64)
     i4 = torch.arange(4)
+    pa, pb = ROTATION_POSITION
     for nb, walk in geo['blocks']:
-        oc = slice(nb * bn, (nb + 1) * bn)
         for step, tb in enumerate(walk):
             if mutant == MUTANTS[6] and step == 1:
                 continue
-            t = (tb * 64 + torch.arange(64)).clamp_max(T - 2 if mutant == MUTANTS[2] else T - 1)
+            t = (tb * tbs + torch.arange(tbs)).clamp_max(T - 2 if mutant == MUTANTS[2] else T - 1)
             tx, ty, n = t % TW, (t // TW) % TH, t // (TW * TH)
             if mutant == MUTANTS[4]:
                 n = torch.where(n > 0, n - 1, n)
-            r, c = 2 * ty[:, None] - 1 + i4, 2 * tx[:, None] - 1 + i4       # [64, 4]
-            valid = ((r >= 0) & (r < H))[:, :, None] & ((c >= 0) & (c < W))[:, None, :]
-            if mutant == MUTANTS[5] and tb == 0:
-                valid[0, 0, 0] = True                                        # tile 0's pixel (-1, -1): the clamped pixel is read
-            pix = ((n[:, None] * H + r.clamp(0, H - 1)) * W)[:, :, None] + c.clamp(0, W - 1)[:, None, :]
-            d = torch.where(valid[..., None], rows[pix], torch.zeros((), dtype=torch.float64))      # [64, 4, 4, C]
+            r, c = 2 * ty[:, None] - 1 + i4, 2 * tx[:, None] - 1 + i4       # [tiles, 4]
+            valid, pix = _pixels_by_range_check(n, r, c, H, W, C, T // (TH * TW)) if wide else _pixels_by_select(n, r, c, H, W)
+            if mutant in (MUTANTS[5], MUTANTS[8]) and tb == 0:               # tile 0's pixel (-1, -1): the clamped pixel is read
+                valid[0, 0, 0], pix[0, 0, 0] = True, n[0] * H * W
+            d = torch.where(valid[..., None], rows[pix], torch.zeros((), dtype=torch.float64))      # [tiles, 4, 4, C]
             v = torch.einsum('ai,tijc,bj->abtc', bt, d, bt)
-            m = torch.zeros((4, 4, 64, bn), dtype=torch.float64)
+            m = torch.zeros((4, 4, tbs, bn), dtype=torch.float64)
+            ub = u[:, :, nb * bn:(nb + 1) * bn]
             for chunk in range(geo['nchunks']):
                 if mutant == MUTANTS[0] and chunk == geo['nchunks'] - 1:
                     continue
                 vc = 1 - chunk if mutant == MUTANTS[1] and chunk < 2 else chunk
-                m += torch.einsum('abtc,aboc->abto', v[..., vc * kc:(vc + 1) * kc], u[:, :, oc, chunk * kc:(chunk + 1) * kc])
-            yt = torch.einsum('pa,abto,qb->tpqo', at, m, at)                 # [64, 2, 2, bn]
+                term = torch.einsum('abtc,aboc->abto', v[..., vc * kc:(vc + 1) * kc], ub[..., chunk * kc:(chunk + 1) * kc])
+                if mutant == MUTANTS[7] and chunk == 1:                      # chunk 0's filter is still in the registers
+                    term[pa, pb] = v[pa, pb, :, kc:2 * kc] @ ub[pa, pb, :, :kc].t()
+                m += term
+            yt = torch.einsum('pa,abto,qb->tpqo', at, m, at)                 # [tiles, 2, 2, bn]
             for half in (0, 1):
                 if mutant == MUTANTS[3] and half == 1 and tb == geo['n_tb'] - 1:
                     continue
-                tt = tb * 64 + half * 32 + torch.arange(32)
+                # the 32 tiles and the channels of this half: variant 5 halves its 128 channels, the others their 64 tiles
+                tl = torch.arange(32) + (0 if wide else half * 32)
+                ch = torch.arange(64) + half * 64 if wide else torch.arange(bn)
+                tt = tb * tbs + tl
                 ox, oy, on = tt % TW, (tt // TW) % TH, tt // (TW * TH)
                 oh, ow = 2 * oy[:, None, None] + i4[:2, None], 2 * ox[:, None, None] + i4[None, :2]      # [32, 2, 1], [32, 1, 2]
                 keep = (tt < T)[:, None, None] & (oh < H) & (ow < W)
                 oh, ow, on = (a.expand(32, 2, 2)[keep] for a in (oh, ow, on[:, None, None]))
-                y[on, oh, ow, oc] = yt[half * 32:half * 32 + 32][keep]
+                y[on[:, None], oh[:, None], ow[:, None], (nb * bn + ch)[None, :]] = yt[tl][:, :, :, ch][keep]
     return y.permute(0, 3, 1, 2)
 
 
@@ -322,7 +415,7 @@ def model_plain_f32(x, f):
 @functools.lru_cache(maxsize=None)
 def model_f32(shape, x3):
     """The restatement of the randn case at ``shape`` on ``sampled_channels``, with the bias: ``model_plain_f32`` for variants 0-3,
-    ``x3_common.winograd_model_f32`` for variant 4 (``x3``).  Deterministic, computed once."""
+    ``x3_common.winograd_model_f32`` for variants 4 and 5 (``x3``: the two agree bit for bit).  Deterministic, computed once."""
     x, f, bias, _, _ = winograd_randn_case(shape)
     ch = sampled_channels(shape)
     out = xc.winograd_model_f32(x, f[ch]) if x3 else model_plain_f32(x, f[ch])

@@ -351,7 +351,8 @@ PAIR = [('pair', 32, 96, 64, 2), ('pair', 64, 64, 128, 1)]                  # (k
 CONV3 = [('conv3', 1), ('conv3', 2), ('conv3', 3)]                         # C 64, N 64, input 3 x 9 x 7
 STEM = [('stem',)]                                                         # 2 x 3 x 37 x 52, N 64
 UNIT = [('unit', 72, 40), ('unit', 174, 128), ('unit', 64, 34)]
-WINO = [(2, 32, 64, 7, 9), (1, 16, 64, 1, 1)]                              # (B, C, O, H, W)
+WINO = [(2, 32, 64, 7, 9), (1, 16, 64, 1, 1)]                              # (B, C, O, H, W): variant 4 on its 64-channel kernel
+WINO_WIDE = [(2, 32, 128, 7, 9), (1, 16, 128, 1, 1)]                       # the same for variant 5's 128-channel workgroups
 GEMM_SPECS = PLAIN + PAIR + CONV3 + STEM + UNIT
 SCALINGS = [(40, 0), (-40, 17), (0, -30), (60, -60)]                       # (s, t): A by 2^s, W by 2^t
 
