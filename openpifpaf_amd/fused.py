@@ -4,11 +4,12 @@ For every kernel family it holds the predicate that says whether the kernel can 
 kernel's contract), the operands derived from the module's parameters (split, padded, transposed copies, cached on the module:
 ``derived``) and the launcher that hands them to the C ABI.  Where a kernel competes with another way to compute the same tensor,
 the choice is made once per shape and remembered in one table (``_CHOICE``, shipped as ``conv1x1_pinned.json``): ``conv_bias_act``
-and ``pick`` say what the candidates are, ``_decide`` makes the choice.  In this order: the launcher, the switches, the choice
-table and the decision, the derived operands, then the routes by kernel family -- the epilogue passes, the 1x1 GEMMs, the
-split-operand convolutions (pair, 3x3 and dilated 3x3, stem, heads), the unit mode (ONE route with a ``UnitMode`` record per element
-type -- float32 on the split-operand GEMM, bfloat16 on the bf16 MFMA -- whose callers pass tensors and name no dtype), the Fire expand,
-the max-pools, the grouped and the depthwise stencils, the RGB stem, group norm, squeeze-and-excitation."""
+and ``pick`` say what the candidates are, ``_decide`` makes the choice.  In this order: the launcher, the switches (with one ``Route16``
+record per route on the 16-bit MFMA), the choice table and the decision, layouts, sizes and what else the predicates share, the
+derived operands, then the routes by kernel family -- the epilogue passes, the 1x1 GEMMs, the split-operand convolutions (pair, 3x3
+and dilated 3x3, stem, heads), the unit mode (ONE route with a ``UnitMode`` record per element type -- float32 on the split-operand
+GEMM, bfloat16 on the bf16 MFMA -- whose callers pass tensors and name no dtype), the Fire expand, the max-pools, the grouped and the
+depthwise stencils, the RGB stem, group norm, squeeze-and-excitation."""
 import functools
 import os
 import typing
@@ -147,7 +148,7 @@ GCONV_BF16 = _switch('OPA_GCONV_BF16', '0')
 # 'conv' as for bfloat16), the 3x3 implicit GEMM (``conv3x3_bias_act_bf16``), the block tail + downsampling product and the strided
 # 1x1 alone (``conv1x1_pair_bias_act_bf16`` / ``conv1x1_strided_bf16``) -- the ``opa_*_f16`` entry points: OPA_F16=1 (or
 # fused.F16 = True).  ONE switch for the three routes, independent of the bfloat16 switches, which a float16 operand never asks
-# (``_route16``); with it off every predicate declines a float16 operand and the network runs MIOpen's convolutions + ``bias_act_``.
+# (``Route16``, below); with it off every predicate declines a float16 operand and the network runs MIOpen's convolutions + ``bias_act_``.
 # Never timed by ``pick``.  The 7x7 stem and the grouped 3x3 have float16 forms behind switches of their own (``STEM7_F16``,
 # ``GCONV_F16``, below), the max-pool has none (the unit mode has its own switch, ``UNIT_F16``, below); the heads have a 16-bit form
 # of their own behind their own switch (``HEAD16``, below), which this one does not touch.  It ships OFF; the one timing is
@@ -157,7 +158,7 @@ F16 = _switch('OPA_F16', '0')
 # kernel on the 16-bit MFMA (csrc/head16.hip, ``head_conv_fields16``: ``opa_head_conv_fields_bf16`` / ``..._f16``) instead of torch's
 # 16-bit ``Conv2d`` + ``opa_head_epilogue``: the float32 accumulators go through the field function straight to the float32 fields, so
 # the convolution's output is neither rounded to 16 bits nor written and read back.  OPA_HEAD16=1 (or fused.HEAD16 = True).  ONE
-# switch for both 16-bit types, independent of ``F16`` and the ``*_BF16`` switches (``_route16`` is not asked).  Never timed by ``pick``,
+# switch for both 16-bit types, independent of ``F16`` and the ``*_BF16`` switches (``ROUTE16_HEAD`` names no other).  Never timed by ``pick``,
 # no choice-table entry: where the switch is on and ``head_conv_fields16_supported`` the kernel runs.  A head whose input width is no
 # multiple of 64 (shufflenetv2k16: 1392) keeps its unit-mode route.  It ships OFF; the one timing is tools/gpu/head16_times.py,
 # profiles/head16/times.log, and switching the default is a change of its own that rests on it.
@@ -183,18 +184,40 @@ GCONV_F16 = _switch('OPA_GCONV_F16', '0')
 # epilogue pass: OPA_STEM7_F16=1 (or fused.STEM7_F16 = True).  Independent of every other switch, as ``GCONV_F16`` is; the input max-pool
 # behind it stays torch's (``maxpool3x3_supported`` declines float16).  It ships OFF; timed by the same tool into the same log.
 STEM7_F16 = _switch('OPA_STEM7_F16', '0')
-# element type -> (is the route on, given the route's own bfloat16 switch and its own float16 switch -- None: ``F16``?; the suffix of
-# its entry points) for the routes on the shared 16-bit MFMA tile
-_ROUTES16 = {torch.bfloat16: (lambda own, own_f16: own, '_bf16'),
-             torch.float16: (lambda own, own_f16: F16 if own_f16 is None else own_f16, '_f16')}
 
 
-def _route16(dtype, own=True, own_f16=None):
-    """The symbol suffix of the 16-bit MFMA routes for operands of ``dtype`` -- ``'_bf16'`` where ``own``, the route's own bfloat16
-    switch, is on; ``'_f16'`` where the route's float16 switch is: ``own_f16``, or ``F16`` for a route that has none of its own
-    (None) -- or None: another dtype, or the switch off.  A float16 operand never asks ``own``, a bfloat16 one never ``own_f16``."""
-    on, suffix = _ROUTES16.get(dtype, (lambda own, own_f16: False, None))
-    return suffix if on(own, own_f16) else None
+class Route16(typing.NamedTuple):
+    """One route on the 16-bit MFMA, and the only place that says which switch and which declined set an element type asks and which
+    entry point it takes.  Switches and sets are held by NAME and read from the module when asked: ``fused.GCONV_F16 = True`` acts at once."""
+    stem: str                           # the entry points' name without the element type's suffix
+    switches: tuple                     # per element type (bfloat16, float16) the name of the switch; None: always on
+    declined: tuple = (None, None)      # per element type the name of the ``*_DECLINED`` set; None: there is none
+    stem_pro: str = None                # the 1x1 GEMM's second entry point: the one with the operand prologue
+
+    def suffix(self, dtype):
+        """``'_bf16'`` / ``'_f16'`` where the route is on for operands of ``dtype`` as its switch reads NOW; None: off, or another dtype.
+        A float16 operand never asks a bfloat16 switch, a bfloat16 one never a float16 switch."""
+        i = _ELEMENTS16.get(dtype)
+        if i is None:
+            return None
+        return _SUFFIXES16[i] if self.switches[i] is None or globals()[self.switches[i]] else None
+
+    def symbol(self, dtype, pro=False):
+        return (self.stem_pro if pro else self.stem) + _SUFFIXES16[_ELEMENTS16[dtype]]
+
+    def declined_set(self, dtype):
+        """The keys measured slower that the route's predicate declines for ``dtype``, as the set reads NOW."""
+        name = self.declined[_ELEMENTS16[dtype]]
+        return globals()[name] if name else frozenset()
+
+
+_ELEMENTS16, _SUFFIXES16 = {torch.bfloat16: 0, torch.float16: 1}, ('_bf16', '_f16')
+ROUTE16_GEMM = Route16('opa_gemm_bias_act', (None, 'F16'), stem_pro='opa_gemm_pro_bias_act')
+ROUTE16_CONV3 = Route16('opa_conv3x3_act', ('CONV3_BF16', 'F16'))
+ROUTE16_PAIR = Route16('opa_gemm2_bias_act', ('PAIR_BF16', 'F16'), ('PAIR_BF16_DECLINED', 'PAIR_BF16_DECLINED'))      # the strided 1x1 too
+ROUTE16_GCONV = Route16('opa_gconv3x3_act', ('GCONV_BF16', 'GCONV_F16'), ('GCONV_BF16_DECLINED', 'GCONV_F16_DECLINED'))
+ROUTE16_STEM7 = Route16('opa_stem7x7_act', ('STEM7_BF16', 'STEM7_F16'), (None, 'STEM7_F16_DECLINED'))
+ROUTE16_HEAD = Route16('opa_head_conv_fields', ('HEAD16', 'HEAD16'), ('HEAD16_DECLINED', 'HEAD16_DECLINED'))
 
 
 # ---- the choice table and the decision ---------------------------------------------------------------------------------------------
@@ -302,7 +325,7 @@ def pick(kind, m, k, n, flag_a, flag_b, run_x3, run_other, written=None, timing=
     return run_x3() if choice == 'x3' else run_other()
 
 
-# ---- layouts and sizes --------------------------------------------------------------------------------------------------------------
+# ---- layouts, sizes and what else the predicates share ------------------------------------------------------------------------------
 
 def _nhwc_rows(x):
     """(rows, channels) if ``x`` is physically [rows, channels]-contiguous, else None."""
@@ -339,6 +362,27 @@ def _empty_nhwc(x, channels, hw=None, dtype=None):
     """An uninitialised channels-last ``[B, channels, *hw]`` on ``x``'s device (``hw``: ``x``'s own where not given)."""
     h, w = hw or x.shape[2:]
     return torch.empty((x.shape[0], channels, h, w), dtype=dtype or x.dtype, device=x.device, memory_format=torch.channels_last)
+
+
+def _autograd_follows(*tensors):
+    """Grad is enabled and one of ``tensors`` (None allowed) requires grad: the kernels have no backward."""
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def _folded_bias_ok(bias, n, x):
+    """The folded bias a 16-bit route takes: None, or ``n`` elements in one dimension on ``x``'s device, of ``x``'s dtype or float32."""
+    return bias is None or (bias.dtype in (x.dtype, torch.float32) and bias.device == x.device and bias.dim() == 1 and bias.numel() == n)
+
+
+def _bias_f32(bias):
+    """``bias`` as the launch takes it: float32 (a 16-bit one upcast exactly), contiguous; None stays None."""
+    return None if bias is None else bias.detach().to(torch.float32).contiguous()
+
+
+def _dense_bf16(t, channels, dtype):
+    """``t``: a dense channels-last 16-bit ``[B, channels, H, W]`` of ``dtype`` on the GPU, 16-byte aligned?"""
+    return (t.is_cuda and t.dtype == dtype and t.dim() == 4 and t.shape[1] == channels
+            and t.is_contiguous(memory_format=torch.channels_last) and t.data_ptr() % 16 == 0)
 
 
 # ---- derived operands -----------------------------------------------------------------------------------------------------------------
@@ -532,7 +576,7 @@ def head_epilogue_supported(x, meta, training=False):
     """True if :func:`head_epilogue` can run for this convolution output and head meta."""
     us = meta.upsample_stride
     return (not training and x.is_cuda and x.dim() == 4 and x.dtype in _DTYPES and _lib.available()
-            and not (torch.is_grad_enabled() and x.requires_grad)           # the kernel has no backward
+            and not _autograd_follows(x)
             and x.is_contiguous(memory_format=torch.channels_last) and us in (1, 2)
             and x.shape[1] % (us ** 2) == 0 and x.data_ptr() % 16 == 0
             and 16 * us * us * (x.shape[3] + 1) * 4 <= 64 * 1024)           # the kernel's LDS row buffer (head.hip)
@@ -559,7 +603,6 @@ def head_epilogue(x, meta):
 # ---- a 16-bit head in one kernel ------------------------------------------------------------------------------------------------------
 
 HEAD16_TILE_N = 64                        # kHead16BN: the weight's rows and the bias are padded to it
-_HEAD16_SUFFIX = {torch.bfloat16: '_bf16', torch.float16: '_f16'}
 # (k, n, upsample) of heads that ``opa_head_conv_fields_bf16`` / ``..._f16`` can run but that came out SLOWER at batch 32 than what runs
 # with the switch off (tools/gpu/head16_times.py, profiles/head16/times.log): the predicate declines them.
 HEAD16_DECLINED = frozenset()
@@ -568,9 +611,7 @@ HEAD16_DECLINED = frozenset()
 def head16_operands_of(conv):
     """The operands of ``head_conv_fields16`` derived from the CURRENT parameters of a head's 1x1 convolution (16-bit ``[N, K, 1, 1]``
     and ``[N]``): the weight as ``[Np][K]`` of its dtype, K-major, ``Np`` = ``N`` rounded up to ``HEAD16_TILE_N``, ZEROS in the rows from
-    ``N`` on, and the bias as FLOAT32 ``[Np]`` (upcast exactly, zeros behind ``N``).  Derived and cached on ``conv`` (``derived``, keyed on
-    both tensors' storage and version): no buffer, no part of a state dict, computed again whenever the weight or the bias was replaced,
-    moved, converted or changed in place."""
+    ``N`` on, and the bias as FLOAT32 ``[Np]`` (upcast exactly, zeros behind ``N``).  Kept on ``conv`` by ``derived``, keyed on both tensors."""
     def make():
         w = conv.weight.detach()
         n, k = w.shape[0], w.shape[1]
@@ -596,24 +637,22 @@ def head_conv_fields16_supported(conv, x, meta, training=False):
     padding or dilation, one group, with a bias; ``K % 64 == 0``; ``meta.upsample_stride`` 1 or 2 and ``conv.out_channels`` the
     ``n_fields * n_components * upsample^2`` of ``meta``'s counts, none negative; ``x`` and the fields fewer than 2^31 elements each;
     ``(K, N, upsample)`` not in ``HEAD16_DECLINED``.  No limit on the row width: nothing here buffers a row."""
-    if not (HEAD16 and not training and x.dtype in _HEAD16_SUFFIX and x.is_cuda and not torch.is_autocast_enabled()
+    if not (not training and ROUTE16_HEAD.suffix(x.dtype) and x.is_cuda and not torch.is_autocast_enabled()
             and isinstance(conv, torch.nn.Conv2d) and conv.bias is not None):
         return False
     w, b = conv.weight, conv.bias
-    if not (w.dtype == x.dtype and b.dtype == x.dtype and w.device == x.device and b.device == x.device
-            and not (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or b.requires_grad))):
+    if not (w.dtype == x.dtype == b.dtype and w.device == x.device == b.device and not _autograd_follows(x, w, b)):
         return False
     k, n, us = conv.in_channels, conv.out_channels, meta.upsample_stride
     if not (conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1
-            and k % 64 == 0 and us in (1, 2) and x.dim() == 4 and x.shape[1] == k and x.shape[2] > 0 and x.shape[3] > 0
-            and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0):
+            and k % 64 == 0 and us in (1, 2) and _dense_bf16(x, k, x.dtype) and x.shape[2] > 0 and x.shape[3] > 0):
         return False
     counts = (meta.n_fields, meta.n_confidences, meta.n_vectors, meta.n_scales)
     n_comp, H, W = _head16_shape(conv, x, meta)
     if not (meta.n_fields > 0 and min(counts) >= 0 and len(meta.vector_offsets) <= 32 and n == meta.n_fields * n_comp * us * us):
         return False
     return (x.numel() < 2 ** 31 and x.shape[0] * meta.n_fields * n_comp * H * W < 2 ** 31 and _lib.available()
-            and (k, n, us) not in HEAD16_DECLINED)
+            and (k, n, us) not in ROUTE16_HEAD.declined_set(x.dtype))
 
 
 def head_conv_fields16(conv, x, meta):
@@ -627,7 +666,7 @@ def head_conv_fields16(conv, x, meta):
     n_comp, H, W = _head16_shape(conv, x, meta)
     out = torch.empty((B, meta.n_fields, n_comp, H, W), dtype=torch.float32, device=x.device)
     mask = sum(1 << i for i, on in enumerate(meta.vector_offsets) if on)
-    _launch('opa_head_conv_fields' + _HEAD16_SUFFIX[x.dtype], _ptr(x), _ptr(wp), _ptr(bp), _ptr(out), B, hc, wc, k, meta.n_fields, n_comp,
+    _launch(ROUTE16_HEAD.symbol(x.dtype), _ptr(x), _ptr(wp), _ptr(bp), _ptr(out), B, hc, wc, k, meta.n_fields, n_comp,
             meta.upsample_stride, meta.n_confidences, meta.n_vectors, mask, meta.n_scales)
     return out
 
@@ -640,7 +679,7 @@ def conv1x1_supported(x, weight, bias=None, residual=None, a_bias=None):
     parameters in float32 next to 16-bit activations -- those take the PyTorch path), the activation channels_last,
     the residual channels_last of the output's shape."""
     dt = x.dtype
-    if not (x.is_cuda and (dt == torch.float32 or _route16(dt)) and x.dim() == 4
+    if not (x.is_cuda and (dt == torch.float32 or ROUTE16_GEMM.suffix(dt)) and x.dim() == 4
             and x.is_contiguous(memory_format=torch.channels_last)
             and weight.dtype == dt and weight.is_cuda
             and weight.shape[1] % (32 if dt == torch.float32 else 64) == 0 and weight.shape[0] % 64 == 0
@@ -648,18 +687,16 @@ def conv1x1_supported(x, weight, bias=None, residual=None, a_bias=None):
         return False
     # (float16 asks what the other routes of its switch ask: outside autocast, nothing that autograd follows; the bfloat16 and the
     # float32 GEMM keep their contract as it was)
-    if dt == torch.float16 and (torch.is_autocast_enabled() or (torch.is_grad_enabled() and any(
-            t is not None and t.requires_grad for t in (x, weight, bias, residual, a_bias)))):
+    if dt == torch.float16 and (torch.is_autocast_enabled() or _autograd_follows(x, weight, bias, residual, a_bias)):
         return False
     for vec, n in ((bias, weight.shape[0]), (a_bias, weight.shape[1])):
         if vec is not None and not (vec.dtype == dt and vec.is_cuda and vec.is_contiguous()
                                     and vec.numel() == n and vec.data_ptr() % 16 == 0):
             return False
-    if residual is not None:
-        if not (residual.dtype == dt and residual.is_cuda
-                and tuple(residual.shape) == (x.shape[0], weight.shape[0], x.shape[2], x.shape[3])
-                and residual.is_contiguous(memory_format=torch.channels_last) and residual.data_ptr() % 16 == 0):
-            return False
+    if residual is not None and not (residual.dtype == dt and residual.is_cuda
+                                     and tuple(residual.shape) == (x.shape[0], weight.shape[0], x.shape[2], x.shape[3])
+                                     and residual.is_contiguous(memory_format=torch.channels_last) and residual.data_ptr() % 16 == 0):
+        return False
     return x.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0
 
 
@@ -678,9 +715,9 @@ def conv1x1_bias_act(x, weight2d, bias, residual=None, relu=True, a_bias=None):
     if x.dtype == torch.float32:
         _launch('opa_gemm_bias_act_f32', _ptr(x), _ptr(a_bias), *rest)
     elif a_bias is not None:
-        _launch('opa_gemm_pro_bias_act' + _ROUTES16[x.dtype][1], _ptr(x), _ptr(a_bias), *rest)
+        _launch(ROUTE16_GEMM.symbol(x.dtype, pro=True), _ptr(x), _ptr(a_bias), *rest)
     else:
-        _launch('opa_gemm_bias_act' + _ROUTES16[x.dtype][1], _ptr(x), *rest)
+        _launch(ROUTE16_GEMM.symbol(x.dtype), _ptr(x), *rest)
     return out
 
 
@@ -790,31 +827,22 @@ def pair_bf16_weight_of(conv, dconv, bias):
     """The operands of ``conv1x1_pair_bias_act_bf16`` derived from the CURRENT weights (``conv``: ``[N, k1, 1, 1]``, ``dconv``:
     ``[N, k2, 1, 1]``, 16-bit) and the folded ``bias`` the block keeps (``[N]`` of that dtype or float32, or None): ``Wcat`` =
     ``[W | Wd]`` as ``[N][k1 + k2]``, K-major, and the bias as FLOAT32 (upcast exactly; None stays None).  ``conv`` None: ``dconv``'s
-    weight alone, ``[N][k2]`` (``conv1x1_strided_bf16``).  Derived and cached on ``dconv`` (``derived``, keyed on the three tensors'
-    storage and version): no buffer, no part of a state dict, computed again whenever a weight or the bias was replaced, moved,
-    converted or changed in place (``load_state_dict`` into an optimized model)."""
+    weight alone, ``[N][k2]`` (``conv1x1_strided_bf16``).  Kept on ``dconv`` by ``derived``, keyed on the three tensors."""
     n, k2 = dconv.out_channels, dconv.in_channels
 
     def make():
         wd = dconv.weight.detach().reshape(n, k2)
         w = wd.contiguous() if conv is None else torch.cat((conv.weight.detach().reshape(n, conv.in_channels), wd), dim=1).contiguous()
-        return w, None if bias is None else bias.detach().to(torch.float32).contiguous()
+        return w, _bias_f32(bias)
     return derived(dconv, '_opa_w_pair_bf16', (None if conv is None else conv.weight, dconv.weight, bias), make)
-
-
-def _dense_bf16(t, channels, dtype=torch.bfloat16):
-    """``t``: a dense channels-last 16-bit ``[B, channels, H, W]`` of ``dtype`` on the GPU, 16-byte aligned, nothing that autograd follows?"""
-    return (t.is_cuda and t.dtype == dtype and t.dim() == 4 and t.shape[1] == channels
-            and t.is_contiguous(memory_format=torch.channels_last) and t.data_ptr() % 16 == 0
-            and not (torch.is_grad_enabled() and t.requires_grad))
 
 
 def _plain_1x1_bf16(conv, like):
     """``conv``: a 1x1 ``Conv2d`` without groups, padding, dilation or a bias of its own, 16-bit weights of ``like``'s dtype on its
-    device that autograd does not follow?  (The stride is the caller's to test, the dtype's route ``_route16``'s.)"""
+    device that autograd does not follow?  (The stride is the caller's to test, the dtype's route ``ROUTE16_PAIR``'s.)"""
     return (isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (1, 1) and conv.groups == 1 and conv.padding == (0, 0)
             and conv.dilation == (1, 1) and conv.bias is None and conv.weight.dtype == like.dtype
-            and conv.weight.device == like.device and not (torch.is_grad_enabled() and conv.weight.requires_grad))
+            and conv.weight.device == like.device and not _autograd_follows(conv.weight))
 
 
 def pair_bf16_supported(conv, dconv, h, x, bias, a_bias=None):
@@ -827,22 +855,19 @@ def pair_bf16_supported(conv, dconv, h, x, bias, a_bias=None):
     or float32, one element per output channel, or None; ``a_bias`` (``h``'s owed bias, a ReLU behind it) of that dtype, ``[k1]``,
     contiguous, 16-byte aligned, or None; the library built; ``(k1, k2, n, stride)`` not in ``PAIR_BF16_DECLINED``."""
     dt = x.dtype
-    if not (_route16(dt, PAIR_BF16) and not torch.is_autocast_enabled() and _plain_1x1_bf16(dconv, x) and _plain_1x1_bf16(conv, x)):
+    if not (ROUTE16_PAIR.suffix(dt) and not torch.is_autocast_enabled() and _plain_1x1_bf16(dconv, x) and _plain_1x1_bf16(conv, x)
+            and not _autograd_follows(h, x, bias, a_bias)):
         return False
     k1, k2, n, s = conv.in_channels, dconv.in_channels, conv.out_channels, dconv.stride[0]
     if not (conv.stride == (1, 1) and dconv.stride == (s, s) and s in (1, 2) and dconv.out_channels == n
             and k1 % 64 == 0 and k2 % 64 == 0 and n % 64 == 0 and _dense_bf16(h, k1, dt) and _dense_bf16(x, k2, dt)
             and h.shape[0] == x.shape[0] and h.device == x.device and tuple(h.shape[2:]) == _out_hw(x, s)
-            and 0 < x.numel() < 2 ** 31 and h.numel() < 2 ** 31 and out_pixels(x, s) * n < 2 ** 31):
-        return False
-    if bias is not None and not (bias.dtype in (dt, torch.float32) and bias.device == x.device and bias.dim() == 1
-                                 and bias.numel() == n and not (torch.is_grad_enabled() and bias.requires_grad)):
+            and 0 < x.numel() < 2 ** 31 and h.numel() < 2 ** 31 and out_pixels(x, s) * n < 2 ** 31 and _folded_bias_ok(bias, n, x)):
         return False
     if a_bias is not None and not (a_bias.dtype == dt and a_bias.device == x.device and a_bias.dim() == 1
-                                   and a_bias.numel() == k1 and a_bias.is_contiguous() and a_bias.data_ptr() % 16 == 0
-                                   and not (torch.is_grad_enabled() and a_bias.requires_grad)):
+                                   and a_bias.numel() == k1 and a_bias.is_contiguous() and a_bias.data_ptr() % 16 == 0):
         return False
-    return _lib.available() and (k1, k2, n, s) not in PAIR_BF16_DECLINED
+    return _lib.available() and (k1, k2, n, s) not in ROUTE16_PAIR.declined_set(dt)
 
 
 def conv1x1_pair_bias_act_bf16(conv, dconv, h, x, bias, relu=True, a_bias=None):
@@ -855,7 +880,7 @@ def conv1x1_pair_bias_act_bf16(conv, dconv, h, x, bias, relu=True, a_bias=None):
     wcat, b32 = pair_bf16_weight_of(conv, dconv, bias)
     B, _, H, W = x.shape
     out = _empty_nhwc(h, n)
-    _launch('opa_gemm2_bias_act' + _ROUTES16[x.dtype][1], _ptr(h), k1, _ptr(x), k2, B, H, W, dconv.stride[0], _ptr(a_bias), _ptr(wcat), _ptr(b32),
+    _launch(ROUTE16_PAIR.symbol(x.dtype), _ptr(h), k1, _ptr(x), k2, B, H, W, dconv.stride[0], _ptr(a_bias), _ptr(wcat), _ptr(b32),
             _ptr(out), n, int(bool(relu)))
     return out
 
@@ -863,12 +888,12 @@ def conv1x1_pair_bias_act_bf16(conv, dconv, h, x, bias, relu=True, a_bias=None):
 def conv1x1_strided_bf16_supported(dconv, x):
     """Can ``conv1x1_strided_bf16(dconv, x)`` run?  ``pair_bf16_supported``'s conditions on ``dconv`` and ``x`` alone: the product
     without a first source (k1 = 0)."""
-    if not (_route16(x.dtype, PAIR_BF16) and not torch.is_autocast_enabled() and _plain_1x1_bf16(dconv, x)):
+    if not (ROUTE16_PAIR.suffix(x.dtype) and not torch.is_autocast_enabled() and _plain_1x1_bf16(dconv, x) and not _autograd_follows(x)):
         return False
     k2, n, s = dconv.in_channels, dconv.out_channels, dconv.stride[0]
     return (dconv.stride == (s, s) and s in (1, 2) and k2 % 64 == 0 and n % 64 == 0 and _dense_bf16(x, k2, x.dtype)
             and 0 < x.numel() < 2 ** 31 and out_pixels(x, s) * n < 2 ** 31 and _lib.available()
-            and (0, k2, n, s) not in PAIR_BF16_DECLINED)
+            and (0, k2, n, s) not in ROUTE16_PAIR.declined_set(x.dtype))
 
 
 def conv1x1_strided_bf16(dconv, x):
@@ -879,7 +904,7 @@ def conv1x1_strided_bf16(dconv, x):
     B, k2, H, W = x.shape
     s = dconv.stride[0]
     out = _empty_nhwc(x, dconv.out_channels, _out_hw(x, s))
-    _launch('opa_gemm2_bias_act' + _ROUTES16[x.dtype][1], _ptr(None), 0, _ptr(x), k2, B, H, W, s, _ptr(None), _ptr(wd), _ptr(None), _ptr(out),
+    _launch(ROUTE16_PAIR.symbol(x.dtype), _ptr(None), 0, _ptr(x), k2, B, H, W, s, _ptr(None), _ptr(wd), _ptr(None), _ptr(out),
             dconv.out_channels, 0)
     return out
 
@@ -930,14 +955,27 @@ def conv3x3_dilated_bias_act_x3(conv, x, bias, relu=True):
 def conv3x3_bf16_weight_of(conv, bias=None):
     """The operands of ``conv3x3_bias_act_bf16`` derived from the CURRENT ``conv.weight`` (``[N, C, 3, 3]`` 16-bit) and the folded
     ``bias`` the block keeps (``[N]`` of that dtype or float32, or None): the weight as ``[N][9][C]`` -- ``weight.permute(0, 2, 3, 1)``, K-major with
-    K = 9 C, ``split_weight_3x3``'s layout without the split -- and the bias as FLOAT32 (upcast exactly; None stays None).  Derived and
-    cached (``derived``, keyed on both tensors' storage and version): no buffer, no part of a state dict, computed again whenever the
-    weight or the bias was replaced, moved, converted or changed in place (``load_state_dict`` into an optimized model)."""
+    K = 9 C, ``split_weight_3x3``'s layout without the split -- and the bias as FLOAT32 (upcast exactly; None stays None).  Kept on
+    ``conv`` by ``derived``, keyed on both tensors: no buffer, no part of a state dict, made again when either was replaced or changed."""
     def make():
         w = conv.weight.detach()
-        return (w.permute(0, 2, 3, 1).reshape(w.shape[0], 9, w.shape[1]).contiguous(),
-                None if bias is None else bias.detach().to(torch.float32).contiguous())
+        return w.permute(0, 2, 3, 1).reshape(w.shape[0], 9, w.shape[1]).contiguous(), _bias_f32(bias)
     return derived(conv, '_opa_w_conv3_bf16', (conv.weight, bias), make)
+
+
+def _conv3x3_16_ok(route, conv, x, bias, residual=None):
+    """What ``conv3x3_bf16_supported`` and ``gconv3x3_bf16_supported`` both ask, ``route``'s switch first: all of the former's contract
+    but the groups, the residual's layout and the library."""
+    dt = x.dtype
+    if not (route.suffix(dt) and x.is_cuda and x.dim() == 4 and not torch.is_autocast_enabled()
+            and not _autograd_follows(x, bias, residual) and not _autograd_follows(conv.weight)):       # (``conv`` last: maybe no Conv2d)
+        return False
+    s, d, n = conv.stride[0], conv.dilation[0], conv.out_channels
+    return (conv.kernel_size == (3, 3) and conv.bias is None and conv.stride == (s, s) and s in (1, 2)
+            and conv.dilation == (d, d) and d in (1, 2, 4) and (d == 1 or s == 1) and conv.padding == (d, d)
+            and conv.in_channels % 64 == 0 and n % 64 == 0 and conv.weight.dtype == dt and conv.weight.device == x.device
+            and _dense_bf16(x, conv.in_channels, dt) and 0 < x.numel() < 2 ** 31 and out_pixels(x, s) * n < 2 ** 31
+            and _folded_bias_ok(bias, n, x))
 
 
 def conv3x3_bf16_supported(conv, x, bias, residual=None):
@@ -948,26 +986,11 @@ def conv3x3_bf16_supported(conv, x, bias, residual=None):
     square dilation 1, 2 or 4 -- above 1 with stride 1 only -- and padding equal to the dilation; input and output channels
     multiples of 64; ``residual`` a dense channels-last tensor of ``x``'s dtype and the output's shape; 16-byte boundaries; ``x`` and the
     output fewer than 2^31 elements each."""
-    dt = x.dtype
-    if not (_route16(dt, CONV3_BF16) and x.is_cuda and x.dim() == 4 and not torch.is_autocast_enabled()):
+    if not (_conv3x3_16_ok(ROUTE16_CONV3, conv, x, bias, residual) and conv.groups == 1):
         return False
-    if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad or (bias is not None and bias.requires_grad)
-                                    or (residual is not None and residual.requires_grad)):
-        return False
-    s, d = conv.stride[0], conv.dilation[0]
-    if not (conv.kernel_size == (3, 3) and conv.groups == 1 and conv.bias is None and conv.stride == (s, s) and s in (1, 2)
-            and conv.dilation == (d, d) and d in (1, 2, 4) and (d == 1 or s == 1) and conv.padding == (d, d)
-            and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0 and x.shape[1] == conv.in_channels
-            and conv.weight.dtype == dt and conv.weight.device == x.device
-            and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0 and 0 < x.numel() < 2 ** 31
-            and out_pixels(x, s) * conv.out_channels < 2 ** 31):
-        return False
-    if bias is not None and not (bias.dtype in (dt, torch.float32) and bias.device == x.device and bias.dim() == 1
-                                 and bias.numel() == conv.out_channels):
-        return False
-    if residual is not None and not (residual.dtype == dt and residual.device == x.device and residual.is_cuda
-                                     and tuple(residual.shape) == (x.shape[0], conv.out_channels) + _out_hw(x, s)
-                                     and residual.is_contiguous(memory_format=torch.channels_last) and residual.data_ptr() % 16 == 0):
+    n = conv.out_channels
+    if residual is not None and not (_dense_bf16(residual, n, x.dtype) and residual.device == x.device
+                                     and tuple(residual.shape) == (x.shape[0], n) + _out_hw(x, conv.stride[0])):
         return False
     return _lib.available()
 
@@ -981,7 +1004,7 @@ def conv3x3_bias_act_bf16(conv, x, bias, residual=None, relu=True):
     B, C, H, W = x.shape
     s = conv.stride[0]
     out = _empty_nhwc(x, conv.out_channels, _out_hw(x, s))
-    _launch('opa_conv3x3_act' + _ROUTES16[x.dtype][1], _ptr(x), _ptr(w9), _ptr(b32), _ptr(residual), _ptr(out), B, H, W, C, conv.out_channels, s,
+    _launch(ROUTE16_CONV3.symbol(x.dtype), _ptr(x), _ptr(w9), _ptr(b32), _ptr(residual), _ptr(out), B, H, W, C, conv.out_channels, s,
             conv.dilation[0], int(bool(relu)))
     return out
 
@@ -993,7 +1016,6 @@ GCONV_BF16_DECLINED = frozenset()
 # ... and of those that ``opa_gconv3x3_act_f16`` can run but that came out slower than torch's grouped FLOAT16 convolution + ``bias_act_``
 # (tools/gpu/f16x_times.py, profiles/f16x/times.log)
 GCONV_F16_DECLINED = frozenset()
-_GCONV16_DECLINED = {'_bf16': lambda: GCONV_BF16_DECLINED, '_f16': lambda: GCONV_F16_DECLINED}
 
 
 def gconv3x3_bf16_weight_of(conv, bias=None):
@@ -1001,16 +1023,14 @@ def gconv3x3_bf16_weight_of(conv, bias=None):
     and the folded ``bias`` the block keeps (``[C]`` of that dtype or float32, or None): the weight as ``[C][9][64]`` of the weight's
     dtype, K-major with K = 576 and BLOCK DIAGONAL per 64-channel chunk -- column ``j`` of row ``co`` is the weight of input channel
     ``64 * (co // 64) + j``: ``weight[co, j % CG, ky, kx]`` where ``j // CG == (co % 64) // CG``, exactly zero elsewhere -- and the bias as FLOAT32 (upcast
-    exactly; None stays None).  Derived and cached (``derived``, keyed on both tensors' storage and version): no buffer, no part of a
-    state dict, computed again whenever the weight or the bias was replaced, moved, converted or changed in place
-    (``load_state_dict`` into an optimized model)."""
+    exactly; None stays None).  Kept on ``conv`` by ``derived`` as ``conv3x3_bf16_weight_of``'s are."""
     def make():
         w = conv.weight.detach()
         c, cg = w.shape[0], w.shape[1]
         packed = w.new_zeros((c, 9, 64 // cg, cg))
         rows = torch.arange(c, device=w.device)
         packed[rows, :, (rows % 64) // cg, :] = w.permute(0, 2, 3, 1).reshape(c, 9, cg)
-        return (packed.reshape(c, 9, 64), None if bias is None else bias.detach().to(torch.float32).contiguous())
+        return packed.reshape(c, 9, 64), _bias_f32(bias)
     return derived(conv, '_opa_w_gconv_bf16', (conv.weight, bias), make)
 
 
@@ -1019,24 +1039,11 @@ def gconv3x3_bf16_supported(conv, x, bias):
     ``GCONV_BF16`` (float16: ``GCONV_F16``, not ``F16``); the convolution HAS groups; as many output as input channels C, C a multiple
     of 64, and a group width C / groups of ``GCONV_BF16_WIDTHS``; no residual; ``(C, C // groups, stride)`` not in
     ``GCONV_BF16_DECLINED`` (float16: ``GCONV_F16_DECLINED``)."""
-    dt = x.dtype
-    suffix = _route16(dt, GCONV_BF16, GCONV_F16)
-    if not (suffix and x.is_cuda and x.dim() == 4 and not torch.is_autocast_enabled()):
+    if not (_conv3x3_16_ok(ROUTE16_GCONV, conv, x, bias) and conv.groups > 1):
         return False
-    if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad or (bias is not None and bias.requires_grad)):
-        return False
-    s, d, c = conv.stride[0], conv.dilation[0], conv.in_channels
-    if not (conv.kernel_size == (3, 3) and conv.groups > 1 and conv.bias is None and conv.stride == (s, s) and s in (1, 2)
-            and conv.dilation == (d, d) and d in (1, 2, 4) and (d == 1 or s == 1) and conv.padding == (d, d)
-            and c == conv.out_channels and c % 64 == 0 and c % conv.groups == 0 and c // conv.groups in GCONV_BF16_WIDTHS
-            and x.shape[1] == c and conv.weight.dtype == dt and conv.weight.device == x.device
-            and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0 and 0 < x.numel() < 2 ** 31
-            and out_pixels(x, s) * c < 2 ** 31):
-        return False
-    if bias is not None and not (bias.dtype in (dt, torch.float32) and bias.device == x.device and bias.dim() == 1
-                                 and bias.numel() == c):
-        return False
-    return _lib.available() and (c, c // conv.groups, s) not in _GCONV16_DECLINED[suffix]()
+    c, cg = conv.in_channels, conv.in_channels // conv.groups
+    return (c == conv.out_channels and c % conv.groups == 0 and cg in GCONV_BF16_WIDTHS and _lib.available()
+            and (c, cg, conv.stride[0]) not in ROUTE16_GCONV.declined_set(x.dtype))
 
 
 def gconv3x3_bias_act_bf16(conv, x, bias, relu=True):
@@ -1048,7 +1055,7 @@ def gconv3x3_bias_act_bf16(conv, x, bias, relu=True):
     B, C, H, W = x.shape
     s = conv.stride[0]
     out = _empty_nhwc(x, C, _out_hw(x, s))
-    _launch('opa_gconv3x3_act' + _ROUTES16[x.dtype][1], _ptr(x), _ptr(w9), _ptr(b32), _ptr(out), B, H, W, C, C // conv.groups, s, conv.dilation[0],
+    _launch(ROUTE16_GCONV.symbol(x.dtype), _ptr(x), _ptr(w9), _ptr(b32), _ptr(out), B, H, W, C, C // conv.groups, s, conv.dilation[0],
             int(bool(relu)))
     return out
 
@@ -1088,14 +1095,13 @@ def stem7x7_bf16_weight_of(conv, bias=None):
     ``bias`` the network keeps (``[N]`` of that dtype or float32, or None): the weight as ``[N][192]`` of the weight's dtype, K-major in
     the load plan's order
     (csrc/stem7x7_bf16_plan.hpp) -- ``w[co][ky * 24 + kx * 3 + ci] = weight[co][ci][ky][kx]``, ZEROS in the columns ``kx = 7`` and
-    ``ky = 7`` that pad 147 to 192 -- and the bias as FLOAT32 (upcast exactly; None stays None).  Derived and cached (``derived``,
-    keyed on both tensors' storage and version): no buffer, no part of a state dict, computed again whenever the weight or the bias
-    was replaced, moved, converted or changed in place (``load_state_dict`` into an optimized model)."""
+    ``ky = 7`` that pad 147 to 192 -- and the bias as FLOAT32 (upcast exactly; None stays None).  Kept on ``conv`` by ``derived`` as
+    ``conv3x3_bf16_weight_of``'s are."""
     def make():
         w = conv.weight.detach()
         wk = w.new_zeros((w.shape[0], 8, 8, 3))
         wk[:, :7, :7] = w.permute(0, 2, 3, 1)
-        return (wk.reshape(w.shape[0], STEM7_BF16_K), None if bias is None else bias.detach().to(torch.float32).contiguous())
+        return wk.reshape(w.shape[0], STEM7_BF16_K), _bias_f32(bias)
     return derived(conv, '_opa_w_stem7_bf16', (conv.weight, bias), make)
 
 
@@ -1109,21 +1115,15 @@ def stem7x7_bf16_supported(conv, x, bias, pooled=False):
     than 2^31 elements; for float16, ``(c_out, stride, pooled)`` not in ``STEM7_F16_DECLINED`` (``pooled``: the caller puts the input
     max-pool behind the stem)."""
     dt = x.dtype
-    suffix = _route16(dt, STEM7_BF16, STEM7_F16)
-    if not (suffix and x.is_cuda and x.dim() == 4 and x.shape[1] == 3 and not torch.is_autocast_enabled()):
-        return False
-    if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad or (bias is not None and bias.requires_grad)):
+    if not (ROUTE16_STEM7.suffix(dt) and x.is_cuda and x.dim() == 4 and x.shape[1] == 3 and not torch.is_autocast_enabled()
+            and not _autograd_follows(x, bias) and not _autograd_follows(conv.weight)):                 # (``conv`` last: maybe no Conv2d)
         return False
     s = conv.stride[0]
     if not (isinstance(conv, torch.nn.Conv2d) and conv.kernel_size == (7, 7) and conv.padding == (3, 3) and conv.dilation == (1, 1)
             and conv.groups == 1 and conv.bias is None and conv.padding_mode == 'zeros' and conv.stride == (s, s) and s in (1, 2)
             and conv.in_channels == 3 and conv.out_channels % 64 == 0
-            and conv.weight.dtype == dt and conv.weight.device == x.device):
-        return False
-    if bias is not None and not (bias.dtype in (dt, torch.float32) and bias.device == x.device and bias.dim() == 1
-                                 and bias.numel() == conv.out_channels):
-        return False
-    if suffix == '_f16' and (conv.out_channels, s, bool(pooled)) in STEM7_F16_DECLINED:
+            and conv.weight.dtype == dt and conv.weight.device == x.device and _folded_bias_ok(bias, conv.out_channels, x)
+            and (conv.out_channels, s, bool(pooled)) not in ROUTE16_STEM7.declined_set(dt)):
         return False
     last = sum((n - 1) * st for n, st in zip(x.shape, x.stride()))               # the last element addressed
     return (min(x.shape) > 0 and min(x.stride()) > 0 and x.data_ptr() % 2 == 0 and last < 2 ** 31
@@ -1139,7 +1139,7 @@ def stem7x7_bias_act_bf16(conv, x, bias, relu=True):
     B, _, H, W = x.shape
     s = conv.stride[0]
     out = _empty_nhwc(x, conv.out_channels, _out_hw(x, s))
-    _launch('opa_stem7x7_act' + _ROUTES16[x.dtype][1], _ptr(x), x.stride(0), x.stride(1), x.stride(2), x.stride(3), _ptr(wk), _ptr(b32), _ptr(out),
+    _launch(ROUTE16_STEM7.symbol(x.dtype), _ptr(x), x.stride(0), x.stride(1), x.stride(2), x.stride(3), _ptr(wk), _ptr(b32), _ptr(out),
             B, H, W, conv.out_channels, s, int(bool(relu)))
     return out
 
@@ -1338,7 +1338,7 @@ def fire_expand_supported(expand1x1, expand3x3, h, terms=None):
     their device, input and output smaller than 2 GB, outside autocast, not followed by autograd."""
     if not (h.is_cuda and h.dim() == 4 and h.dtype == torch.float32 and not torch.is_autocast_enabled() and _fire_convs_ok(expand1x1, expand3x3)):
         return False
-    if torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for c in (expand1x1, expand3x3) for p in c.parameters())):
+    if _autograd_follows(h, *expand1x1.parameters(), *expand3x3.parameters()):
         return False
     return (h.shape[1] == expand1x1.in_channels and h.is_contiguous(memory_format=torch.channels_last) and h.data_ptr() % 16 == 0
             and fire_expand_shape_supported(expand1x1, expand3x3, h.device, h.shape[0] * h.shape[2] * h.shape[3], terms))
@@ -1375,9 +1375,8 @@ def gconv3x3_supported(conv, x, bias):
     """Can ``gconv3x3_bias_act(conv, x, bias)`` run?  A grouped 3x3 convolution (padding 1, dilation 1, square stride 1 or 2, as many
     output as input channels, a group width of ``GCONV_WIDTHS``, no bias of its own: the folded one arrives separately) of a dense
     channels-last float32 tensor on the GPU, outside autocast, not followed by autograd."""
-    if not (GCONV and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and not torch.is_autocast_enabled()):
-        return False
-    if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad or (bias is not None and bias.requires_grad)):
+    if not (GCONV and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and not torch.is_autocast_enabled()
+            and not _autograd_follows(x, bias) and not _autograd_follows(conv.weight)):             # (``conv`` last: maybe no Conv2d)
         return False
     c = conv.in_channels
     return (conv.groups > 1 and conv.kernel_size == (3, 3) and conv.padding == (1, 1) and conv.dilation == (1, 1)
@@ -1405,7 +1404,7 @@ def gconv3x3_bias_act(conv, x, bias, relu=True):
 def maxpool3x3_supported(x, bias=None):
     """Can ``maxpool3x3_bias_act_(x, bias)`` run?  A dense channels-last float32 or bfloat16 tensor on the GPU with a multiple of 8
     channels, smaller than 2 GB, not followed by autograd; ``bias`` of ``x``'s dtype, one element per channel."""
-    return (x.is_cuda and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16) and not (torch.is_grad_enabled() and x.requires_grad)
+    return (x.is_cuda and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16) and not _autograd_follows(x)
             and x.is_contiguous(memory_format=torch.channels_last) and x.shape[1] % 8 == 0 and x.data_ptr() % 16 == 0
             and 0 < x.numel() * x.element_size() < 2 ** 31
             and (bias is None or (bias.dtype == x.dtype and bias.device == x.device and bias.is_contiguous()

@@ -276,11 +276,21 @@ def test_the_switch_reads_opa_f16_and_ships_off():
 
 
 def test_the_symbol_table(built):
-    """dtype -> (switch, suffix): bfloat16 asks the route's own switch, float16 asks ``F16``, anything else has no route."""
-    assert fused._route16(F16) == '_f16' and fused._route16(F16, False) == '_f16' and fused._route16(BF) == '_bf16'
-    assert fused._route16(BF, False) is None and fused._route16(torch.float32) is None
+    """route record, dtype -> suffix: bfloat16 asks the route's own switch (the 1x1 GEMM has none), float16 asks ``F16``, anything else
+    has no route.  (The fixture: every ``*_BF16`` switch off, ``F16`` on.)"""
+    gemm, own = fused.ROUTE16_GEMM, {'CONV3_BF16': fused.ROUTE16_CONV3, 'PAIR_BF16': fused.ROUTE16_PAIR}
+    assert gemm.suffix(F16) == '_f16' and all(r.suffix(F16) == '_f16' for r in own.values()) and gemm.suffix(BF) == '_bf16'
+    assert all(r.suffix(BF) is None for r in own.values()) and gemm.suffix(torch.float32) is None
+    assert all(r.suffix(torch.float32) is None for r in own.values())
     built.setattr(fused, 'F16', False)
-    assert fused._route16(F16) is None and fused._route16(F16, True) is None and fused._route16(BF, True) == '_bf16'
+    assert gemm.suffix(F16) is None and gemm.suffix(BF) == '_bf16'
+    for switch, route in own.items():
+        built.setattr(fused, switch, True)
+        assert route.suffix(F16) is None and route.suffix(BF) == '_bf16'
+    assert gemm.symbol(F16) == 'opa_gemm_bias_act_f16' and gemm.symbol(BF, pro=True) == 'opa_gemm_pro_bias_act_bf16'
+    assert fused.ROUTE16_CONV3.symbol(F16) == 'opa_conv3x3_act_f16' and fused.ROUTE16_PAIR.symbol(BF) == 'opa_gemm2_bias_act_bf16'
+    assert {gemm.symbol(dt, pro) for dt in (F16, BF) for pro in (False, True)} | {r.symbol(dt) for r in own.values() for dt in (F16, BF)} \
+        <= set(_lib.SYMBOLS)
 
 
 # ---- the derived operands ----------------------------------------------------------------------------------------------------------

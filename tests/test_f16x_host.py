@@ -52,16 +52,38 @@ def test_the_switches_ship_off_and_read_their_own_variables():
         assert proc.returncode == 0 and proc.stdout.split('\n')[-2] == want, (env, proc.stdout[-500:], proc.stderr[-500:])
 
 
-def test_route16_asks_the_routes_own_float16_switch(monkeypatch):
+def test_a_route_record_asks_the_routes_own_float16_switch(monkeypatch):
+    # (dtype, the route's bfloat16 switch, its float16 switch) -> the suffix
+    rows = ((F16, True, True, '_f16'), (F16, False, True, '_f16'), (F16, True, False, None), (F16, False, False, None),
+            (BF, True, False, '_bf16'), (BF, True, True, '_bf16'), (BF, False, True, None), (F32, True, True, None))
     for f16 in (False, True):
         monkeypatch.setattr(fused, 'F16', f16)
         # a route with a float16 switch of its own: F16 is not asked, and neither dtype asks the other's switch
-        assert fused._route16(F16, True, True) == '_f16' and fused._route16(F16, False, True) == '_f16'
-        assert fused._route16(F16, True, False) is None and fused._route16(F16, False, False) is None
-        assert fused._route16(BF, True, False) == '_bf16' and fused._route16(BF, True, True) == '_bf16'
-        assert fused._route16(BF, False, True) is None and fused._route16(F32, True, True) is None
+        for route, own, own_f16 in ((fused.ROUTE16_GCONV, 'GCONV_BF16', 'GCONV_F16'), (fused.ROUTE16_STEM7, 'STEM7_BF16', 'STEM7_F16')):
+            for dtype, bf16_on, f16_on, want in rows:
+                monkeypatch.setattr(fused, own, bf16_on)
+                monkeypatch.setattr(fused, own_f16, f16_on)
+                assert route.suffix(dtype) == want, (route.stem, dtype, bf16_on, f16_on, f16)
         # a route without one: F16, as before
-        assert fused._route16(F16, True) == ('_f16' if f16 else None) and fused._route16(F16) == ('_f16' if f16 else None)
+        for route, own in ((fused.ROUTE16_CONV3, 'CONV3_BF16'), (fused.ROUTE16_PAIR, 'PAIR_BF16')):
+            monkeypatch.setattr(fused, own, True)
+            assert route.suffix(F16) == ('_f16' if f16 else None) and route.suffix(BF) == '_bf16'
+        assert fused.ROUTE16_GEMM.suffix(F16) == ('_f16' if f16 else None)
+        # the heads: ONE switch for both types, which asks neither F16 nor any switch above
+        for head16 in (False, True):
+            monkeypatch.setattr(fused, 'HEAD16', head16)
+            assert fused.ROUTE16_HEAD.suffix(BF) == ('_bf16' if head16 else None) and fused.ROUTE16_HEAD.suffix(F16) == ('_f16' if head16 else None)
+            assert fused.ROUTE16_HEAD.suffix(F32) is None
+    assert fused.ROUTE16_GCONV.symbol(F16) == GCONV and fused.ROUTE16_STEM7.symbol(F16) == STEM
+    assert fused.ROUTE16_HEAD.symbol(BF) == 'opa_head_conv_fields_bf16' and fused.ROUTE16_HEAD.symbol(F16) == 'opa_head_conv_fields_f16'
+    # the declined sets are read from the module when asked: the grouped 3x3 has one per type, the stem float16's alone, the heads one for both
+    for name, route, dtypes in (('GCONV_BF16_DECLINED', fused.ROUTE16_GCONV, (BF,)), ('GCONV_F16_DECLINED', fused.ROUTE16_GCONV, (F16,)),
+                                ('STEM7_F16_DECLINED', fused.ROUTE16_STEM7, (F16,)), ('HEAD16_DECLINED', fused.ROUTE16_HEAD, (BF, F16)),
+                                ('PAIR_BF16_DECLINED', fused.ROUTE16_PAIR, (BF, F16))):
+        with monkeypatch.context() as m:
+            m.setattr(fused, name, frozenset({'key'}))
+            assert [dt for dt in (BF, F16) if 'key' in route.declined_set(dt)] == list(dtypes), name
+    assert fused.ROUTE16_CONV3.declined_set(BF) == fused.ROUTE16_GEMM.declined_set(F16) == frozenset()
     assert fused.GCONV_F16_DECLINED == frozenset() or all(len(k) == 3 for k in fused.GCONV_F16_DECLINED)
     assert fused.STEM7_F16_DECLINED == frozenset() or all(len(k) == 3 for k in fused.STEM7_F16_DECLINED)
 
